@@ -22,7 +22,11 @@ RCCL all-gather of the match lists.  N = 1 runs the same code with the collectiv
 frames and pairs of all sequences dealt round-robin over the ranks, so both exchanges are real);
 --scaling strong: one sequence whatever N.
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times --steps steps and prints the headline line: metric, value, unit, ms_per_step (wall time of
+one timed step), higher_is_better, dtype, the step bookkeeping and `config`.  --dump-outputs DIR then also writes what the last
+timed step computed (rank 0) as DIR/<name>.npy (dump_outputs).  Everything else is measured or checked only under --full.
+
+Extra objects on the JSON line (--full):
   roofline      the dominant kernel of the step by measured time (HIP events on the launch stream, timed steps)
   mfma          the metric's kernel (k_ham_fp4): achieved multiply-add op/s against the dense FP4 MFMA peak (10 PF)
   rooflines / kernels   every kernel group; traffic = HBM bytes from separate rocprofv3 --pmc passes (profiles/)
@@ -112,7 +116,16 @@ def parse_args(argv=None):
     ap.add_argument("--sustain-s", type=float, default=3.2,
                     help="after the headline region: run the same steps for about this long and report `sustained` (0 = skip)")
     ap.add_argument("--master-port", type=int, default=0)
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beside the headline figure: the check of the timed job against the oracle, per-kernel times and "
+                         "rooflines, the sustained and without-track-graph legs, the stand-alone pass, the other BASELINE configurations, "
+                         "the host-buffer timings and the CPU baseline (the --no-* / --sustain-s / --c-abi-comm options select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps: write what the last one computed (rank 0) as DIR/<name>.npy, float64 / float32")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -397,6 +410,55 @@ def job_slot(job, p):
     return pdist.slot_of(p, job.world, job.ps)
 
 
+DUMP_FRAMES, DUMP_PAIRS = 64, 256   # at 4096 keypoints: <= 26 MB of per-frame arrays + <= 26 MB of match lists (float64)
+
+
+def dump_outputs(out_dir, job, pair_list, track_frames):
+    """--dump-outputs: what the job's last step handed its caller on this rank, as out_dir/<name>.npy -- float64 (every integer,
+    descriptor word and INT_MAX tail distance exact) and float32 for the grey values.  Only valid rows: the first count[f] keypoints
+    and descriptors of frame f, the first count[a] entries of image pair (a, b)'s list, track ids of frame f's first count[f]
+    keypoints; rows of several frames / image pairs are concatenated in the order frames.npy / pairs.npy list them.  Frames are
+    this rank's own (it holds their keypoints), at most DUMP_FRAMES and image pairs at most DUMP_PAIRS: beyond that a fixed seeded
+    sample, so that runs with the same arguments write the same entries."""
+    import numpy as np
+    rng = np.random.default_rng(0)
+    counts = job.counts()
+    frames = list(job.my_frames)
+    if len(frames) > DUMP_FRAMES:
+        frames = sorted(rng.choice(frames, DUMP_FRAMES, replace=False).tolist())
+    pidx = list(range(len(pair_list)))
+    if len(pidx) > DUMP_PAIRS:
+        pidx = sorted(rng.choice(len(pidx), DUMP_PAIRS, replace=False).tolist())
+    local = {f: k for k, f in enumerate(job.my_frames)}
+
+    def cat(parts, width):
+        return np.concatenate(parts) if parts else np.zeros((0, width) if width else 0, np.int64)
+
+    kp = [job.kp_l[local[f]].cpu().numpy()[:counts[f]] for f in frames]
+    out = {"counts": counts.astype(np.float64),   # every frame's survivor count, global frame order
+           "frames": np.asarray(frames, np.float64),
+           "raw_hits": np.asarray([int(job.nraw_l[local[f]]) for f in frames], np.float64),
+           "keypoints": cat([k[:, :3] for k in kp], 3).astype(np.float64),   # x, y, FAST score
+           "keypoint_grey": cat([k[:, 3] for k in kp], 0).astype(np.int32).view(np.float32),
+           "descriptors": cat([job.descriptors(f).cpu().numpy().view(np.uint32)[:counts[f]] for f in frames], 8).astype(np.float64),
+           "pairs": np.asarray([(p,) + tuple(pair_list[p]) for p in pidx], np.float64).reshape(-1, 3),   # index, frame a, frame b
+           "matches": cat([job.matches(p).cpu().numpy()[:counts[pair_list[p][0]]] for p in pidx], 3).astype(np.float64)}   # k1, k2, dist
+    if getattr(job, "trk", None) is not None:
+        s = job.track_summary()
+        tf = {f: i for i, f in enumerate(track_frames)}
+        rows = [f for f in frames if f in tf]
+        tof = job.track_of.cpu().numpy()
+        out["track_summary"] = np.asarray([s[k] for k in ("n_tracks", "n_nodes", "dropped", "dropped_nodes", "edges", "longest",
+                                                          "largest_dropped")], np.float64)
+        out["track_frames"] = np.asarray(rows, np.float64)
+        out["track_of"] = cat([tof[tf[f], :counts[f]] for f in rows], 0).astype(np.float64)
+    assert sum(a.nbytes for a in out.values()) <= 64 << 20
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------
 # one rank
 # ---------------------------------------------------------------------------------------------------
@@ -510,7 +572,7 @@ def worker(args):
             if s not in bases:
                 bases[s] = torch.from_numpy(base_frame(W, H, 4321 + s)).to(dev)
             roll_frames(torch, bases[s], [(3 * i, i)], out=d_frames[k:k + 1])
-    host_base0 = base_frame(W, H, 4321)
+    host_base0 = base_frame(W, H, 4321) if args.full else None   # the host copy for the checks of --full
     bases.clear()
     torch.cuda.synchronize()
     log("[rank %d/%d] setup %.1fs: %d of %d frames resident (%.0f MB), %d of %d image pairs, scaling %s"
@@ -528,8 +590,9 @@ def worker(args):
     torch.cuda.synchronize()
     for e in engs:
         e.check_status()
-    for j in jobs[1:]:   # every context in flight computes the same job: identical results
-        assert torch.equal(j.out_all, job.out_all) and torch.equal(j.counts_all, job.counts_all)
+    if args.full:   # every context in flight computes the same job: identical results
+        for j in jobs[1:]:
+            assert torch.equal(j.out_all, job.out_all) and torch.equal(j.counts_all, job.counts_all)
     counts = job.counts()
     pairs_per_step = float(sum(int(counts[a]) * int(counts[b]) for a, b in pair_list))
     my_pairs_per_step = float(sum(int(counts[a]) * int(counts[b]) for a, b in (pair_list[p] for p in job.my_pairs)))
@@ -537,13 +600,14 @@ def worker(args):
     log("[rank %d] survivors per frame min/mean/max %d/%.0f/%d, raw hits mean %.0f"
         % (rank, counts.min(), counts.mean(), counts.max(), nraw_l.mean() if len(nraw_l) else 0))
 
-    for e in engs:
-        e.profile_reset()
-        # events on every launch cost 0.6 ms of a 10.7 ms step: the timed region brackets the metric's kernel only (the
-        # roofline's live measurement); every other kernel is bracketed in the untimed stand-alone pass below
-        e.profile_filter("ham_argmin")
-        e.profile_enable(not args.no_profile)
-        e.debug_counters()   # clears them
+    if args.full:   # a plain run brackets nothing: its timed steps carry no events
+        for e in engs:
+            e.profile_reset()
+            # events on every launch cost 0.6 ms of a 10.7 ms step: the timed region brackets the metric's kernel only (the
+            # roofline's live measurement); every other kernel is bracketed in the untimed stand-alone pass below
+            e.profile_filter("ham_argmin")
+            e.profile_enable(not args.no_profile)
+            e.debug_counters()   # clears them
     barrier()
     t0 = time.perf_counter()
     run_steps(args.steps)
@@ -551,6 +615,54 @@ def worker(args):
         j.finish()   # the last steps' match-list exchanges belong to the timed region
     barrier()
     dt = time.perf_counter() - t0
+    t = torch.tensor([dt], dtype=torch.float64, device=dev)
+    if world > 1:
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+    dt_max = float(t[0].item())
+    F_l, M_l = len(job.my_frames), len(job.my_pairs)
+
+    def headline():
+        """The result line of a plain run; --full adds its objects to it."""
+        return {
+            "metric": "descriptor pairs matched/sec", "value": pairs_per_step * args.steps / dt_max,
+            "unit": "descriptor pairs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": dt_max / args.steps * 1e3, "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
+            "dtype": "u8 / bits (descriptor bits expanded to fp4 +-1 for the MFMA distance: exact integers in f32 accumulators; "
+                     "integer keys); f32 grey",
+            "data": "synthetic",
+            "config": {"workload": "BASELINE configs[2] (SURVEY 8d config 3) x %d: %d-frame 1920x1080 RGBA64 sequence(s), "
+                                   "dewarp(%s)+gray+FAST(T=0.1)+NMS(r=%d; SURVEY 8d writes r = 20 for this config: both leave more than 4096 "
+                                   "survivors per frame, the lists are cut to the same length either way)+BRIEF-256 per frame, all %d ordered "
+                                   "image pairs per sequence through the greedy Hamming match, <=%d keypoints per frame (first %d in NMS order)"
+                                   % (nseq, FS, "off" if dmap is None else "shipped coeffs", RADIUS, FS * (FS - 1) // 2, NKP, NKP),
+                       "frames": n_frames, "image_pairs": len(pair_list), "frames_per_gpu": F_l, "image_pairs_per_gpu": M_l,
+                       "descriptor_pairs_per_step": pairs_per_step,
+                       "keypoints_min_mean_max": [int(counts.min()), float(counts.mean()), int(counts.max())],
+                       "raw_hits_mean": float(nraw_l.mean()) if len(nraw_l) else 0.0,
+                       "parallelism": "frames f mod %d, image pairs p mod %d; 2 all-gathers per step%s"
+                                      % (world, world, "" if world > 1 else " (elided at N = 1)"),
+                       "jobs_in_flight": NI,
+                       "stage_gates": None if NI < 2 else
+                       "step k+1 on the other context: detect chain waits for %s, matcher for %s of step k (pgx_wait_stage)" % tuple(args.gate.split(",")),
+                       "rehearsal_on_one_gpu_with_gloo": rehearse},
+        }
+
+    def shutdown(rc):
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        for e in engs:
+            e.close()
+        return rc
+
+    for e in engs:
+        e.check_status()
+    if args.dump_outputs and rank == 0:   # step s ran on jobs[s % NI]
+        dump_outputs(args.dump_outputs, jobs[(args.steps - 1) % NI], pair_list, track_frames)
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline()), flush=True)
+        return shutdown(0)
     for j in jobs[1:]:   # every context in flight computed the same job in the timed region: identical results (verify_job checks jobs[0])
         assert torch.equal(j.out_all, job.out_all) and torch.equal(j.counts_all, job.counts_all) and torch.equal(j.desc_all, job.desc_all)
     dbg = [0] * 8
@@ -567,10 +679,6 @@ def worker(args):
     # sustained leg: the same steps, same schedule, for about --sustain-s seconds (every rank the same count: it is derived
     # from the max-over-ranks time of the headline region); outside `value`
     sustained = None
-    t = torch.tensor([dt], dtype=torch.float64, device=dev)
-    if world > 1:
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-    dt_max = float(t[0].item())
     if args.sustain_s > 0:
         for e in engs:
             e.profile_reset()
@@ -700,7 +808,6 @@ def worker(args):
             verified["ok"] = bool(verified["ok"] and tracks_obj["verified"]["ok"])
         if not verified["ok"]:
             rc = 4
-        F_l, M_l = len(job.my_frames), len(job.my_pairs)
         # per-kernel times: the timed region brackets the metric's kernel only; the other groups come from the stand-alone pass
         kern = dict(kern_alone)
         kern.update(kern_timed)
@@ -777,28 +884,8 @@ def worker(args):
                                          "frac": byts / (detect_ms * 1e-3) / HBM_PEAK, "traffic": None,
                                          "algorithmic": "SURVEY 8d: 24 B/pixel for the fused-minimum detect stream x %d frames" % F_l}
         dominant = max((k for k in kern if k in rooflines), key=lambda k: kern[k]["ms_per_step"], default=None)
-        result = {
-            "metric": "descriptor pairs matched/sec", "value": pairs_per_step * args.steps / dt_max,
-            "unit": "descriptor pairs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": step_ms, "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
-            "dtype": "u8 / bits (descriptor bits expanded to fp4 +-1 for the MFMA distance: exact integers in f32 accumulators; "
-                     "integer keys); f32 grey",
-            "data": "synthetic",
-            "config": {"workload": "BASELINE configs[2] (SURVEY 8d config 3) x %d: %d-frame 1920x1080 RGBA64 sequence(s), "
-                                   "dewarp(%s)+gray+FAST(T=0.1)+NMS(r=%d; SURVEY 8d writes r = 20 for this config: both leave more than 4096 "
-                                   "survivors per frame, the lists are cut to the same length either way)+BRIEF-256 per frame, all %d ordered "
-                                   "image pairs per sequence through the greedy Hamming match, <=%d keypoints per frame (first %d in NMS order)"
-                                   % (nseq, FS, "off" if dmap is None else "shipped coeffs", RADIUS, FS * (FS - 1) // 2, NKP, NKP),
-                       "frames": n_frames, "image_pairs": len(pair_list), "frames_per_gpu": F_l, "image_pairs_per_gpu": M_l,
-                       "descriptor_pairs_per_step": pairs_per_step,
-                       "keypoints_min_mean_max": [int(counts.min()), float(counts.mean()), int(counts.max())],
-                       "raw_hits_mean": float(nraw_l.mean()) if len(nraw_l) else 0.0,
-                       "parallelism": "frames f mod %d, image pairs p mod %d; 2 all-gathers per step%s"
-                                      % (world, world, "" if world > 1 else " (elided at N = 1)"),
-                       "jobs_in_flight": NI,
-                       "stage_gates": None if NI < 2 else
-                       "step k+1 on the other context: detect chain waits for %s, matcher for %s of step k (pgx_wait_stage)" % tuple(args.gate.split(",")),
-                       "rehearsal_on_one_gpu_with_gloo": rehearse},
+        result = headline()
+        result.update({
             "roofline": rooflines.get(dominant),
             "verified": verified,
             "tracks": tracks_obj,
@@ -824,7 +911,7 @@ def worker(args):
                            "mfma_frac_of_peak_on_match_stage": (evals * 2.0 * P / (max(step_ms - detect_ms, 1e-9) * 1e-3)) / I8_MFMA_PEAK_OPS
                            if detect_ms else None,
                            "note": "match stage wall = step minus the detect kernels (rank 0); SURVEY 8d's match-only definition"},
-        }
+        })
         if tracks_obj is not None:
             tracks_obj["ms_per_step"] = kern["tracks"]["ms_per_step"] if "tracks" in kern else None
             tracks_obj["in_timed_region"] = True
@@ -860,12 +947,7 @@ def worker(args):
             result["cpu_baseline"] = cb
             log("cpu baseline took %.1fs" % (time.time() - t1))
         print(json.dumps(result), flush=True)
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
-    for e in engs:
-        e.close()
-    return rc
+    return shutdown(rc)
 
 
 # ---------------------------------------------------------------------------------------------------

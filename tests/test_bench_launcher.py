@@ -51,3 +51,20 @@ def test_main_routes_gpus_gt_1_to_the_launcher():
             "assert 'torch' not in sys.modules\n")
     r = _run(code)
     assert r.returncode == 0, r.stderr
+
+
+def test_plain_run_is_the_default_and_steps_are_checked():
+    code = ("import bench\n"
+            "a = bench.parse_args(['--steps', '7', '--warmup', '0'])\n"
+            "assert a.steps == 7 and a.warmup == 0 and a.full is False and a.dump_outputs is None\n"
+            "a = bench.parse_args(['--full', '--dump-outputs', 'out'])\n"
+            "assert a.full is True and a.dump_outputs == 'out'\n"
+            "for bad in (['--steps', '0'], ['--warmup', '-1']):\n"
+            "    try:\n"
+            "        bench.parse_args(bad)\n"
+            "    except SystemExit as e:\n"
+            "        assert e.code == 2\n"
+            "    else:\n"
+            "        raise AssertionError(bad)\n")
+    r = _run(code)
+    assert r.returncode == 0, r.stderr

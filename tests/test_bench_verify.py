@@ -103,3 +103,32 @@ def test_verify_does_not_look_at_unsampled_pairs(small_job):
     the full-size parity tests are the proof (tests/test_gpu_sequence.py)."""
     res = _verify(small_job, lists=lambda lst: lst[1].__setitem__((0, 1), lst[1][0, 1] + 1))
     assert res["ok"]
+
+
+def test_dump_outputs_writes_the_valid_rows_as_floats(small_job, tmp_path):
+    """bench.py --dump-outputs: the first count[f] keypoints / descriptors of every frame and the first count[a] entries of every
+    image pair's list, exact in float64 (grey values as float32), read back equal to what the job holds."""
+    j = small_job
+    job = FakeJob(j["kp"], j["desc"], j["counts"], j["nraw"], j["lists"])
+    bench.dump_outputs(str(tmp_path), job, j["pl"], None)
+    a = {p.name[:-4]: np.load(str(p)) for p in tmp_path.iterdir()}
+    assert set(a) == {"counts", "frames", "raw_hits", "keypoints", "keypoint_grey", "descriptors", "pairs", "matches"}
+    assert all(x.dtype in (np.float32, np.float64) for x in a.values())
+    c = j["counts"]
+    assert (a["counts"] == c).all() and (a["frames"] == [0, 1, 2]).all() and (a["raw_hits"] == j["nraw"]).all()
+    assert (a["keypoints"] == np.concatenate([k[:n, :3] for k, n in zip(j["kp"], c)])).all()
+    assert a["keypoint_grey"].tobytes() == np.concatenate([k[:n, 3] for k, n in zip(j["kp"], c)]).tobytes()
+    assert (a["descriptors"].astype(np.uint32) == np.concatenate([d[:n].view(np.uint32) for d, n in zip(j["desc"], c)])).all()
+    assert (a["pairs"] == [(p, x, y) for p, (x, y) in enumerate(j["pl"])]).all()
+    assert (a["matches"] == np.concatenate([m[:c[x]] for m, (x, _) in zip(j["lists"], j["pl"])])).all()
+
+
+def test_dump_outputs_samples_large_jobs_the_same_way_every_time(small_job, tmp_path, monkeypatch):
+    j = small_job
+    monkeypatch.setattr(bench, "DUMP_FRAMES", 2)
+    monkeypatch.setattr(bench, "DUMP_PAIRS", 3)
+    job = FakeJob(j["kp"], j["desc"], j["counts"], j["nraw"], j["lists"])
+    first, second = (bench.dump_outputs(str(tmp_path / k), job, j["pl"], None) for k in ("a", "b"))
+    assert len(first["frames"]) == 2 and len(first["pairs"]) == 3
+    assert all(np.array_equal(first[k], second[k]) for k in first)
+    assert len(first["keypoints"]) == sum(j["counts"][int(f)] for f in first["frames"])
