@@ -191,6 +191,40 @@ int pgx_wait_stage(pgx_ctx *ctx, pgx_ctx *other, int stage);
  * init kernel sits on the critical path: 0.2 ms per step of the bench job).  `other` must outlive that call. */
 int pgx_gate_match(pgx_ctx *ctx, pgx_ctx *other, int stage);
 
+/* ---- exact nearest-neighbour matching (k_knn.hip) --------------------------------------------------------------------- */
+/* A second matching mode beside the reference's greedy one-to-one assignment (pgx_match*): per image pair the nearest columns
+ * of every row and the nearest row of every column, and from them a match list with a distance gate, Lowe's ratio test and a
+ * mutual (cross) check.  Not in the C# reference; the reference's Python matcher (keypoint_matching.py) keeps a row's nearest
+ * column under --match-threshold.
+ * Inputs as for pgx_match_batch_dev: d_desc [F][stride][words], d_counts [F], d_pairlist [M][2] = (a, b), max_count (counts
+ * above it are clamped to it).  For image pair m = (a, b), row i < counts[a], column j < counts[b]:
+ * d(i, j) = popcount(desc_a[i] ^ desc_b[j]).  Every result is exact and does not depend on launch configuration or run.
+ *   row neighbours  the k in {1, 2} columns with the smallest (d, j), ascending in (d, j): a tie goes to the smaller index.
+ *                   Missing entries (counts[b] < k) are (-1, PGX_DIST_NONE).
+ *   column nearest  for every column j < counts[b] the row with the smallest (d, i); -1 when counts[a] == 0.
+ *   NN list         one pgx_pair per row, entry i for row i: (i, j1, d1) when the row is accepted, else (i, -1, PGX_DIST_NONE)
+ *                   (pgx_tracks_dev / pgx_tracks_add_pair never link such an entry).  Accepted when d1 <= max_dist; and,
+ *                   with ratio > 0, there is no second neighbour or (double)d1 < (double)ratio * (double)d2 (exact: d <= 4064;
+ *                   two equal nearest distances are rejected); and, with cross_check != 0, column-nearest(j1) == i.
+ *                   ratio <= 0: no ratio test; ratio > 1 or NaN: PGX_E_BADARG.
+ * counts[b] == 0 < counts[a] is NOT an error here: every row of the pair is rejected.  Rows >= counts[a] (columns >= counts[b]
+ * of the column output) are not written.  Limits: stride <= 2^20, 1 <= words <= 127; k other than 1, 2 -> PGX_E_BADARG.
+ * 256-bit descriptors (words == 8) run on the FP4 matrix instruction with the top-2 and the column argmin fused into the tile
+ * loop (no distance matrix in memory); other lengths on a plain xor + popcount path. */
+/* Asynchronous on the context's stream, stream hand-off contract as above.  d_idx, d_dist [M][stride][k]; d_col_nn [M][stride]
+ * or NULL. */
+int pgx_knn_batch_dev(pgx_ctx *ctx, const uint32_t *d_desc, const int32_t *d_counts, int stride, int words, const int32_t *d_pairlist,
+                      int M, int max_count, int k, int32_t *d_idx, int32_t *d_dist, int32_t *d_col_nn);
+/* The NN lists (k = 2 and the column nearest, then the selection above): d_out [M][stride], the first counts[a] entries of row m
+ * are pair m's list, ready for pgx_tracks_dev as they are.  Workspace: 20 bytes per slot of a chunk of pgx_set_match_chunk pairs. */
+int pgx_match_nn_batch_dev(pgx_ctx *ctx, const uint32_t *d_desc, const int32_t *d_counts, int stride, int words,
+                           const int32_t *d_pairlist, int M, int max_count, int max_dist, float ratio, int cross_check,
+                           pgx_pair *d_out);
+/* Host buffers, one pair (the form a C# host with managed arrays calls, like pgx_match): idx_out, dist_out [n1][k],
+ * col_nn_out [n2] or NULL.  Returns when the results are in the caller's buffers. */
+int pgx_knn(pgx_ctx *ctx, const uint32_t *desc1, int n1, const uint32_t *desc2, int n2, int words, int k, int32_t *idx_out,
+            int32_t *dist_out, int32_t *col_nn_out);
+
 /* ---- RANSAC fundamental matrix and camera pose, batched over image pairs (asynchronous, device pointers) --- */
 /* CameraPoseEstimation.GetFundamentalMatrix (CameraPoseEstimation.cs:26-94) for M image pairs at once: `keypointPairs` of
  * image pair m = the first counts[a] entries of d_matches[m] (indices into d_kp[a] / d_kp[b], (a, b) = d_pairlist[m]); per

@@ -54,12 +54,21 @@ internal static unsafe class PgxNative
                                                               int* pairList, int nPairs, PgxPair* o, long* outOffsets);
     [DllImport(Lib)] public static extern int pgx_detect(IntPtr ctx, ushort* rgba64, int w, int h, PgxKeypoint* kp, uint* desc,
                                                          int capacity, out int n, out int nRaw);
+    // exact nearest neighbours of one pair (not KeypointMatching: see INTEGRATION.md); idx, dist [n1][k], colNn [n2] or null
+    [DllImport(Lib)] public static extern int pgx_knn(IntPtr ctx, uint* d1, int n1, uint* d2, int n2, int words, int k, int* idx,
+                                                      int* dist, int* colNn);
 
     // batched, device-resident entry points and the multi-GPU / pose / track-graph additions (include/pgx.h)
     [DllImport(Lib)] public static extern int pgx_detect_batch_dev(IntPtr ctx, void* dRgba64, int f, int w, int h, void* dKp, void* dDesc,
                                                                    void* dCounts, void* dNraw, int capacity);
     [DllImport(Lib)] public static extern int pgx_match_batch_dev(IntPtr ctx, void* dDesc, void* dCounts, int stride, int words,
                                                                   void* dPairlist, int m, int maxCount, void* dOut);
+    [DllImport(Lib)] public static extern int pgx_knn_batch_dev(IntPtr ctx, void* dDesc, void* dCounts, int stride, int words,
+                                                                void* dPairlist, int m, int maxCount, int k, void* dIdx, void* dDist,
+                                                                void* dColNn);
+    [DllImport(Lib)] public static extern int pgx_match_nn_batch_dev(IntPtr ctx, void* dDesc, void* dCounts, int stride, int words,
+                                                                     void* dPairlist, int m, int maxCount, int maxDist, float ratio,
+                                                                     int crossCheck, void* dOut);
     [DllImport(Lib)] public static extern int pgx_check_status(IntPtr ctx);
     [DllImport(Lib)] public static extern int pgx_comm_unique_id(byte* id128);
     [DllImport(Lib)] public static extern int pgx_comm_init(IntPtr ctx, int rank, int world, byte* id128);

@@ -234,6 +234,38 @@ class Engine:
                                               _dptr(d_pairlist), int(M),
                                               int(stride if max_count is None else max_count), _dptr(d_out)))
 
+    # -- exact nearest-neighbour matching (include/pgx.h, "exact nearest-neighbour matching") --------------
+    def knn(self, desc1, desc2, k=2, col=False):
+        """pgx_knn: the k (1 or 2) nearest columns of every row of desc1 in desc2, ascending in (distance, column).
+        Returns (idx [n1][k], dist [n1][k]) int32 arrays, and col_nn [n2] (the nearest row of every column, -1 when desc1 is
+        empty) as a third array when col=True.  Missing neighbours are (-1, PGX_DIST_NONE)."""
+        d1 = np.ascontiguousarray(desc1, dtype=np.uint32)
+        d2 = np.ascontiguousarray(desc2, dtype=np.uint32)
+        words = d1.shape[1] if d1.ndim == 2 and d1.shape[0] else (d2.shape[1] if d2.ndim == 2 and d2.shape[0] else 8)
+        n1, n2 = len(d1), len(d2)
+        kk = max(1, int(k))
+        idx = np.zeros((max(1, n1), kk), dtype=np.int32)
+        dist = np.zeros((max(1, n1), kk), dtype=np.int32)
+        cnn = np.zeros(max(1, n2), dtype=np.int32) if col else None
+        self._chk(self._L.pgx_knn(self._h, _ptr(d1), n1, _ptr(d2), n2, int(words), int(k), _ptr(idx), _ptr(dist), _ptr(cnn)))
+        if col:
+            return idx[:n1].copy(), dist[:n1].copy(), cnn[:n2].copy()
+        return idx[:n1].copy(), dist[:n1].copy()
+
+    def knn_batch_dev(self, d_desc, d_counts, stride, words, d_pairlist, M, k, d_idx, d_dist, d_col_nn=None, max_count=None):
+        """pgx_knn_batch_dev: d_idx, d_dist [M][stride][k] int32, d_col_nn [M][stride] int32 or None (device tensors)."""
+        self._chk(self._L.pgx_knn_batch_dev(self._h, _dptr(d_desc), _dptr(d_counts), int(stride), int(words), _dptr(d_pairlist),
+                                            int(M), int(stride if max_count is None else max_count), int(k), _dptr(d_idx),
+                                            _dptr(d_dist), None if d_col_nn is None else _dptr(d_col_nn)))
+
+    def match_nn_batch_dev(self, d_desc, d_counts, stride, words, d_pairlist, M, d_out, max_dist, ratio=0.0, cross_check=False,
+                           max_count=None):
+        """pgx_match_nn_batch_dev: d_out [M][stride] PAIR_DTYPE (int32 [..][3]) -- per row (i, j1, d1) when accepted, else
+        (i, -1, PGX_DIST_NONE); feeds tracks_dev as it is."""
+        self._chk(self._L.pgx_match_nn_batch_dev(self._h, _dptr(d_desc), _dptr(d_counts), int(stride), int(words), _dptr(d_pairlist),
+                                                 int(M), int(stride if max_count is None else max_count), int(max_dist),
+                                                 C.c_float(ratio), 1 if cross_check else 0, _dptr(d_out)))
+
     # -- RANSAC fundamental matrix / pose (device tensors) ------------------------------------------
     def fundamental_ransac_dev(self, d_kp, d_matches, d_counts, d_pairlist, M, stride, n_samples, pairs_per_sample, threshold,
                                d_F, d_inliers, d_best_sample, rank_check=False, seed=0):

@@ -325,7 +325,7 @@ void pgx_ctx_destroy(pgx_ctx *c)
     for (hipEvent_t ev : c->ev_pool) (void)hipEventDestroy(ev);
     DevBuf *bufs[] = {&c->d_pairs, &c->d_map, &c->ws_gray, &c->ws_seg, &c->ws_segoff, &c->ws_nraw, &c->ws_rawxy,
                       &c->ws_rawscore, &c->ws_nms, &c->ws_order, &c->ws_nkept, &c->st_a, &c->st_b, &c->st_c,
-                      &c->st_d, &c->st_e, &c->st_f, &c->ws_pose, &c->ws_tracks, &c->ws_agree, &c->ws_matchn[0], &c->ws_matchn[1], &c->ws_matchn[2], &c->ws_matchn[3]};
+                      &c->st_d, &c->st_e, &c->st_f, &c->ws_pose, &c->ws_tracks, &c->ws_agree, &c->ws_matchn[0], &c->ws_matchn[1], &c->ws_matchn[2], &c->ws_matchn[3], &c->ws_knn};
     for (DevBuf *b : bufs) b->release();
     c->pin_in.release();
     c->pin_out.release();
@@ -758,6 +758,97 @@ int pgx_match_batch_dev(pgx_ctx *c, const uint32_t *d_desc, const int32_t *d_cou
         return c ? fail(c, PGX_E_BADARG, "null pointer") : PGX_E_BADARG;
     Lock l(c);
     return enqueue_match(c, d_desc, d_counts, stride, words, d_pairlist, M, max_count, d_out);
+}
+
+// ---- exact nearest-neighbour matching (k_knn.hip) -------------------------------------------------------------------
+
+namespace {
+
+int knn_args(pgx_ctx *c, int stride, int words, int M, int k)
+{
+    if (stride <= 0 || stride > (1 << PGX_IDX_BITS)) return fail(c, PGX_E_BADARG, "stride must be in [1, 2^20]");
+    if (words <= 0 || words > 127) return fail(c, PGX_E_BADARG, "words must be in [1, 127] (P <= 4064)");
+    if (k != 1 && k != 2) return fail(c, PGX_E_BADARG, "k must be 1 or 2");
+    if ((long long)M * ((stride + 255) / 256) > 0x7FFFFFFFll) return fail(c, PGX_E_BADARG, "too many image pairs for one call");
+    return PGX_OK;
+}
+
+int clamp_max_count(int max_count, int stride) { return max_count > stride ? stride : (max_count < 1 ? 1 : max_count); }
+
+} // namespace
+
+int pgx_knn_batch_dev(pgx_ctx *c, const uint32_t *d_desc, const int32_t *d_counts, int stride, int words, const int32_t *d_pairlist,
+                      int M, int max_count, int k, int32_t *d_idx, int32_t *d_dist, int32_t *d_col_nn)
+{
+    if (!c || !d_desc || !d_counts || !d_pairlist || !d_idx || !d_dist || M < 0)
+        return c ? fail(c, PGX_E_BADARG, "null pointer") : PGX_E_BADARG;
+    Lock l(c);
+    const int rc = knn_args(c, stride, words, M, k);
+    if (rc != PGX_OK || M == 0) return rc;
+    pgx_launch_knn(c, c->stream, d_desc, d_counts, d_pairlist, M, stride, words, clamp_max_count(max_count, stride), k, d_idx, d_dist,
+                   d_col_nn);
+    HIPCHK(c, hipGetLastError());
+    return PGX_OK;
+}
+
+int pgx_match_nn_batch_dev(pgx_ctx *c, const uint32_t *d_desc, const int32_t *d_counts, int stride, int words,
+                           const int32_t *d_pairlist, int M, int max_count, int max_dist, float ratio, int cross_check, pgx_pair *d_out)
+{
+    if (!c || !d_desc || !d_counts || !d_pairlist || !d_out || M < 0)
+        return c ? fail(c, PGX_E_BADARG, "null pointer") : PGX_E_BADARG;
+    Lock l(c);
+    const int rc = knn_args(c, stride, words, M, 2);
+    if (rc != PGX_OK) return rc;
+    if (!(ratio <= 1.0f)) return fail(c, PGX_E_BADARG, "ratio must be <= 1 (0 or less: no ratio test)");
+    if (M == 0) return PGX_OK;
+    const int max_n = clamp_max_count(max_count, stride);
+    // the top-2 and column-nearest results of one chunk of image pairs (pgx_set_match_chunk): 20 bytes per slot
+    const int CHUNK = c->match_chunk, mc = M < CHUNK ? M : CHUNK;
+    const size_t slots = (size_t)mc * stride;
+    HIPCHK(c, c->ws_knn.ensure(slots * 5 * sizeof(int32_t)));
+    int32_t *idx = c->ws_knn.as<int32_t>(), *dist = idx + 2 * slots, *col = dist + 2 * slots;
+    for (int m0 = 0; m0 < M; m0 += CHUNK) {
+        const int n = M - m0 < CHUNK ? M - m0 : CHUNK;
+        const int32_t *pl = d_pairlist + 2 * (size_t)m0;
+        pgx_launch_knn(c, c->stream, d_desc, d_counts, pl, n, stride, words, max_n, 2, idx, dist, col);
+        pgx_launch_knn_select(c, c->stream, d_counts, pl, n, stride, max_n, idx, dist, col, max_dist, ratio, cross_check ? 1 : 0,
+                              d_out + (size_t)m0 * stride);
+    }
+    HIPCHK(c, hipGetLastError());
+    return PGX_OK;
+}
+
+int pgx_knn(pgx_ctx *c, const uint32_t *desc1, int n1, const uint32_t *desc2, int n2, int words, int k, int32_t *idx_out,
+            int32_t *dist_out, int32_t *col_nn_out)
+{
+    if (!c || n1 < 0 || n2 < 0 || (n1 > 0 && (!desc1 || !idx_out || !dist_out)) || (n2 > 0 && !desc2))
+        return c ? fail(c, PGX_E_BADARG, "null pointer") : PGX_E_BADARG;
+    Lock l(c);
+    const int S = n1 > n2 ? n1 : (n2 > 0 ? n2 : 1);
+    if (S > (1 << PGX_IDX_BITS)) return fail(c, PGX_E_BADARG, "more than 2^20 keypoints");
+    int rc = knn_args(c, S, words, 1, k);
+    if (rc != PGX_OK) return rc;
+    if (n1 == 0 && (n2 == 0 || !col_nn_out)) return PGX_OK;
+    // two "frames" of S slots; outputs idx [S][k], dist [S][k], col [S]
+    HIPCHK(c, c->st_a.ensure((size_t)2 * S * words * 4));
+    HIPCHK(c, c->st_b.ensure(64));
+    HIPCHK(c, c->st_c.ensure((size_t)S * (2 * k + 1) * 4));
+    const int32_t meta[4] = {n1, n2, 0, 1}; // counts[2], pairlist[1][2]
+    if (n1 > 0) HIPCHK(c, hipMemcpyAsync(c->st_a.p, desc1, (size_t)n1 * words * 4, hipMemcpyHostToDevice, c->stream));
+    if (n2 > 0)
+        HIPCHK(c, hipMemcpyAsync(c->st_a.as<uint32_t>() + (size_t)S * words, desc2, (size_t)n2 * words * 4, hipMemcpyHostToDevice,
+                                 c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->st_b.p, meta, sizeof meta, hipMemcpyHostToDevice, c->stream));
+    int32_t *d_idx = c->st_c.as<int32_t>(), *d_dist = d_idx + (size_t)S * k, *d_col = col_nn_out ? d_dist + (size_t)S * k : nullptr;
+    pgx_launch_knn(c, c->stream, c->st_a.as<uint32_t>(), c->st_b.as<int32_t>(), c->st_b.as<int32_t>() + 2, 1, S, words, S, k, d_idx,
+                   d_dist, d_col);
+    HIPCHK(c, hipGetLastError());
+    if (n1 > 0) {
+        HIPCHK(c, hipMemcpyAsync(idx_out, d_idx, (size_t)n1 * k * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(dist_out, d_dist, (size_t)n1 * k * 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (d_col && n2 > 0) HIPCHK(c, hipMemcpyAsync(col_nn_out, d_col, (size_t)n2 * 4, hipMemcpyDeviceToHost, c->stream));
+    return sync_status(c);
 }
 
 // ---- RANSAC fundamental matrix and pose ----------------------------------------------------------

@@ -113,6 +113,7 @@ struct pgx_ctx {
     // match workspaces: four, so that with several chunks of image pairs the stages of consecutive chunks run side by side
     DevBuf ws_matchn[4];
     DevBuf ws_pose, ws_tracks;
+    DevBuf ws_knn; // pgx_match_nn_batch_dev: top-2 and column nearest of a chunk of image pairs
     hipStream_t mstream[4] = {nullptr, nullptr, nullptr, nullptr}; // [0] wide rounds, [1] residual distance rows, [2], [3] per-pair finishes (alternating)
     hipEvent_t ev_in = nullptr, ev_wide[4] = {nullptr, nullptr, nullptr, nullptr}, ev_rows[4] = {nullptr, nullptr, nullptr, nullptr},
                ev_fin[4] = {nullptr, nullptr, nullptr, nullptr}, ev_join[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -274,3 +275,12 @@ void pgx_launch_match_rows(pgx_ctx *ctx, hipStream_t s, const uint32_t *d_desc, 
                            const MatchPlan &plan, void *ws, int *status);
 void pgx_launch_match_finish(pgx_ctx *ctx, hipStream_t s, const uint32_t *d_desc, const int32_t *d_pairlist,
                              const MatchPlan &plan, void *ws, pgx_pair *d_out, int *status);
+
+// k_knn.hip (exact nearest neighbours; pgx_knn_batch_dev semantics, include/pgx.h)
+// d_idx / d_dist [M][S][k], d_col [M][S] or nullptr; max_n in [1, S], k in {1, 2}
+void pgx_launch_knn(pgx_ctx *ctx, hipStream_t s, const uint32_t *d_desc, const int32_t *d_counts, const int32_t *d_pairlist, int M,
+                    int S, int words, int max_n, int k, int32_t *d_idx, int32_t *d_dist, int32_t *d_col);
+// the NN list of every row from k = 2 results and the column nearest: d_out [M][S]
+void pgx_launch_knn_select(pgx_ctx *ctx, hipStream_t s, const int32_t *d_counts, const int32_t *d_pairlist, int M, int S, int max_n,
+                           const int32_t *d_idx, const int32_t *d_dist, const int32_t *d_col, int max_dist, float ratio,
+                           int cross_check, pgx_pair *d_out);
