@@ -225,6 +225,44 @@ int pgx_match_nn_batch_dev(pgx_ctx *ctx, const uint32_t *d_desc, const int32_t *
 int pgx_knn(pgx_ctx *ctx, const uint32_t *desc1, int n1, const uint32_t *desc2, int n2, int words, int k, int32_t *idx_out,
             int32_t *dist_out, int32_t *col_nn_out);
 
+/* ---- epipolar-guided exact matching (k_guided.hip) -------------------------------------------------------------------- */
+/* The nearest-neighbour mode above restricted, per image pair, to the columns that lie near each row's epipolar line, so that
+ * a descriptor repeated elsewhere in the image no longer spoils the ratio test.  Inputs as for pgx_knn_batch_dev, plus
+ * d_kp [F][stride] (the pgx_detect_batch_dev layout, same stride as the descriptors), d_F [M][9] float32 row-major with
+ * h_a^T F h_b = 0, h = (x, y, 1) -- the convention of pgx_fundamental_ransac_dev's score -- and band, in pixels.  Its d_F is
+ * accepted as it is, but its estimate keeps the reference's column-major fill: the matrix it fits to true correspondences
+ * satisfies h_b^T F h_a = 0, so pass its transpose (or the pair swapped) to guide by it.
+ * For image pair m = (a, b), row i at (x, y) = kp_a[i], column j at (u, v) = kp_b[j], every value converted to double and every
+ * operation one IEEE double operation rounded to nearest, in the order written, none contracted into an FMA:
+ *   l0 = (F[0][0]*x + F[1][0]*y) + F[2][0]      (the products are exact in double)
+ *   l1 = (F[0][1]*x + F[1][1]*y) + F[2][1]
+ *   l2 = (F[0][2]*x + F[1][2]*y) + F[2][2]
+ *   n2 = l0*l0 + l1*l1;  e = (l0*u + l1*v) + l2;  T = (double)band * (double)band
+ *   admissible(i, j)  <=>  all nine F entries finite  and  n2 > 0  and  e*e <= T*n2
+ * (numpy float64 reproduces this bit for bit.)
+ *   row neighbours  the k in {1, 2} ADMISSIBLE columns with the smallest (d, j); missing entries are (-1, PGX_DIST_NONE).
+ *   column nearest  the admissible row with the smallest (d, i), -1 when there is none (the row's line decides on both sides).
+ *   NN list         the selection rules of pgx_match_nn_batch_dev (distance gate, ratio, cross-check) on these neighbours.
+ * Errors: band NaN, infinite or negative, and every argument pgx_knn_batch_dev rejects -> PGX_E_BADARG.  A keypoint coordinate
+ * outside [-2^20, 2^20) in a used slot (index < counts) of frame a or b rejects all rows of that pair and reports
+ * PGX_E_BADARG through pgx_check_status.  A pair with a non-finite F is not an error: all its rows are rejected.  Results do
+ * not depend on pgx_set_match_chunk, the launch configuration or the run.  Rows >= counts[a] (columns >= counts[b]) are not
+ * written.  The kernel buckets every frame of a chunk once into a grid and walks only the cells the band crosses.
+ * Asynchronous on the context's stream.  d_idx, d_dist [M][stride][k]; d_col_nn [M][stride] or NULL.  Workspace: the grids
+ * of the frames of one chunk of image pairs, about 10 bytes per keypoint slot (max_count) of 2 * chunk frames. */
+int pgx_knn_guided_batch_dev(pgx_ctx *ctx, const uint32_t *d_desc, const pgx_keypoint *d_kp, const int32_t *d_counts, int stride,
+                             int words, const int32_t *d_pairlist, int M, int max_count, const float *d_F, float band, int k,
+                             int32_t *d_idx, int32_t *d_dist, int32_t *d_col_nn);
+/* The guided NN lists: d_out [M][stride] as pgx_match_nn_batch_dev's, ready for pgx_tracks_dev. */
+int pgx_match_guided_batch_dev(pgx_ctx *ctx, const uint32_t *d_desc, const pgx_keypoint *d_kp, const int32_t *d_counts, int stride,
+                               int words, const int32_t *d_pairlist, int M, int max_count, const float *d_F, float band,
+                               int max_dist, float ratio, int cross_check, pgx_pair *d_out);
+/* Host buffers, one pair (frame a = 1, frame b = 2): F [9]; idx_out, dist_out [n1][k], col_nn_out [n2] or NULL.  Returns when
+ * the results are in the caller's buffers (PGX_E_BADARG for an out-of-range coordinate). */
+int pgx_knn_guided(pgx_ctx *ctx, const uint32_t *desc1, const pgx_keypoint *kp1, int n1, const uint32_t *desc2,
+                   const pgx_keypoint *kp2, int n2, int words, const float *F, float band, int k, int32_t *idx_out,
+                   int32_t *dist_out, int32_t *col_nn_out);
+
 /* ---- RANSAC fundamental matrix and camera pose, batched over image pairs (asynchronous, device pointers) --- */
 /* CameraPoseEstimation.GetFundamentalMatrix (CameraPoseEstimation.cs:26-94) for M image pairs at once: `keypointPairs` of
  * image pair m = the first counts[a] entries of d_matches[m] (indices into d_kp[a] / d_kp[b], (a, b) = d_pairlist[m]); per

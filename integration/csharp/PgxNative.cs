@@ -57,6 +57,10 @@ internal static unsafe class PgxNative
     // exact nearest neighbours of one pair (not KeypointMatching: see INTEGRATION.md); idx, dist [n1][k], colNn [n2] or null
     [DllImport(Lib)] public static extern int pgx_knn(IntPtr ctx, uint* d1, int n1, uint* d2, int n2, int words, int k, int* idx,
                                                       int* dist, int* colNn);
+    // epipolar-guided nearest neighbours of one pair: f [9] row-major (h1^T F h2 = 0), band in pixels; outputs as pgx_knn
+    [DllImport(Lib)] public static extern int pgx_knn_guided(IntPtr ctx, uint* d1, PgxKeypoint* kp1, int n1, uint* d2, PgxKeypoint* kp2,
+                                                             int n2, int words, float* f, float band, int k, int* idx, int* dist,
+                                                             int* colNn);
 
     // batched, device-resident entry points and the multi-GPU / pose / track-graph additions (include/pgx.h)
     [DllImport(Lib)] public static extern int pgx_detect_batch_dev(IntPtr ctx, void* dRgba64, int f, int w, int h, void* dKp, void* dDesc,
@@ -69,6 +73,13 @@ internal static unsafe class PgxNative
     [DllImport(Lib)] public static extern int pgx_match_nn_batch_dev(IntPtr ctx, void* dDesc, void* dCounts, int stride, int words,
                                                                      void* dPairlist, int m, int maxCount, int maxDist, float ratio,
                                                                      int crossCheck, void* dOut);
+    [DllImport(Lib)] public static extern int pgx_knn_guided_batch_dev(IntPtr ctx, void* dDesc, void* dKp, void* dCounts, int stride,
+                                                                       int words, void* dPairlist, int m, int maxCount, void* dF,
+                                                                       float band, int k, void* dIdx, void* dDist, void* dColNn);
+    [DllImport(Lib)] public static extern int pgx_match_guided_batch_dev(IntPtr ctx, void* dDesc, void* dKp, void* dCounts, int stride,
+                                                                         int words, void* dPairlist, int m, int maxCount, void* dF,
+                                                                         float band, int maxDist, float ratio, int crossCheck,
+                                                                         void* dOut);
     [DllImport(Lib)] public static extern int pgx_check_status(IntPtr ctx);
     [DllImport(Lib)] public static extern int pgx_comm_unique_id(byte* id128);
     [DllImport(Lib)] public static extern int pgx_comm_init(IntPtr ctx, int rank, int world, byte* id128);

@@ -30,6 +30,7 @@ EXPORTS = [
     "pgx_allgather_dev", "pgx_sequence_step_dev", "pgx_tracks_create", "pgx_tracks_destroy", "pgx_tracks_add_pair",
     "pgx_tracks_finish", "pgx_tracks_get", "pgx_tracks_dropped", "pgx_tracks_dev", "pgx_fundamental_ransac_dev", "pgx_pose_dev",
     "pgx_knn_batch_dev", "pgx_match_nn_batch_dev", "pgx_knn",
+    "pgx_knn_guided_batch_dev", "pgx_match_guided_batch_dev", "pgx_knn_guided",
 ]
 
 

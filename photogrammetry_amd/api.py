@@ -266,6 +266,47 @@ class Engine:
                                                  int(M), int(stride if max_count is None else max_count), int(max_dist),
                                                  C.c_float(ratio), 1 if cross_check else 0, _dptr(d_out)))
 
+    # -- epipolar-guided exact matching (include/pgx.h, "epipolar-guided exact matching") ----------------
+    def knn_guided(self, desc1, kp1, desc2, kp2, F, band, k=2, col=False):
+        """pgx_knn_guided: knn() restricted to the columns within `band` pixels of each row's epipolar line.  kp1, kp2:
+        KEYPOINT_DTYPE arrays (or int32 [n][4]) of the same lengths as desc1, desc2; F: 9 float32 values, row-major,
+        h1^T F h2 = 0.  Returns (idx [n1][k], dist [n1][k]) and col_nn [n2] as a third array when col=True."""
+        d1 = np.ascontiguousarray(desc1, dtype=np.uint32)
+        d2 = np.ascontiguousarray(desc2, dtype=np.uint32)
+        k1 = np.ascontiguousarray(np.asarray(kp1).view(np.int32).reshape(-1, 4) if len(kp1) else np.zeros((0, 4), np.int32))
+        k2 = np.ascontiguousarray(np.asarray(kp2).view(np.int32).reshape(-1, 4) if len(kp2) else np.zeros((0, 4), np.int32))
+        f = np.ascontiguousarray(np.asarray(F, dtype=np.float32).reshape(9))
+        words = d1.shape[1] if d1.ndim == 2 and d1.shape[0] else (d2.shape[1] if d2.ndim == 2 and d2.shape[0] else 8)
+        n1, n2 = len(d1), len(d2)
+        if len(k1) != n1 or len(k2) != n2:
+            raise ValueError("keypoint and descriptor counts differ")
+        kk = max(1, int(k))
+        idx = np.zeros((max(1, n1), kk), dtype=np.int32)
+        dist = np.zeros((max(1, n1), kk), dtype=np.int32)
+        cnn = np.zeros(max(1, n2), dtype=np.int32) if col else None
+        self._chk(self._L.pgx_knn_guided(self._h, _ptr(d1), _ptr(k1), n1, _ptr(d2), _ptr(k2), n2, int(words), _ptr(f),
+                                         C.c_float(band), int(k), _ptr(idx), _ptr(dist), _ptr(cnn)))
+        if col:
+            return idx[:n1].copy(), dist[:n1].copy(), cnn[:n2].copy()
+        return idx[:n1].copy(), dist[:n1].copy()
+
+    def knn_guided_batch_dev(self, d_desc, d_kp, d_counts, stride, words, d_pairlist, M, d_F, band, k, d_idx, d_dist,
+                             d_col_nn=None, max_count=None):
+        """pgx_knn_guided_batch_dev: d_kp [F][stride] keypoints, d_F [M][9] float32; d_idx, d_dist [M][stride][k] int32,
+        d_col_nn [M][stride] int32 or None (device tensors)."""
+        self._chk(self._L.pgx_knn_guided_batch_dev(self._h, _dptr(d_desc), _dptr(d_kp), _dptr(d_counts), int(stride), int(words),
+                                                   _dptr(d_pairlist), int(M), int(stride if max_count is None else max_count),
+                                                   _dptr(d_F), C.c_float(band), int(k), _dptr(d_idx), _dptr(d_dist),
+                                                   None if d_col_nn is None else _dptr(d_col_nn)))
+
+    def match_guided_batch_dev(self, d_desc, d_kp, d_counts, stride, words, d_pairlist, M, d_F, band, d_out, max_dist, ratio=0.0,
+                               cross_check=False, max_count=None):
+        """pgx_match_guided_batch_dev: the guided NN lists, d_out [M][stride] PAIR_DTYPE as match_nn_batch_dev's."""
+        self._chk(self._L.pgx_match_guided_batch_dev(self._h, _dptr(d_desc), _dptr(d_kp), _dptr(d_counts), int(stride), int(words),
+                                                     _dptr(d_pairlist), int(M), int(stride if max_count is None else max_count),
+                                                     _dptr(d_F), C.c_float(band), int(max_dist), C.c_float(ratio),
+                                                     1 if cross_check else 0, _dptr(d_out)))
+
     # -- RANSAC fundamental matrix / pose (device tensors) ------------------------------------------
     def fundamental_ransac_dev(self, d_kp, d_matches, d_counts, d_pairlist, M, stride, n_samples, pairs_per_sample, threshold,
                                d_F, d_inliers, d_best_sample, rank_check=False, seed=0):

@@ -5,6 +5,7 @@
 #include "pgx_internal.h"
 
 #include <atomic>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <new>
@@ -63,6 +64,8 @@ int decode_status(pgx_ctx *c, int bits)
         return fail(c, PGX_E_CAPACITY, "raw FAST hits exceed max_raw_per_frame (pgx_set_capacity)");
     if (bits & PGX_ST_KP_CAP) return fail(c, PGX_E_CAPACITY, "NMS survivors exceed the output capacity");
     if (bits & PGX_ST_INTERNAL) return fail(c, PGX_E_HIP, "internal error: a device-side loop stopped without progress");
+    if (bits & PGX_ST_BADARG)
+        return fail(c, PGX_E_BADARG, "guided matching: a keypoint coordinate is outside [-2^20, 2^20) (its pairs' rows were rejected)");
     return PGX_OK;
 }
 
@@ -325,7 +328,7 @@ void pgx_ctx_destroy(pgx_ctx *c)
     for (hipEvent_t ev : c->ev_pool) (void)hipEventDestroy(ev);
     DevBuf *bufs[] = {&c->d_pairs, &c->d_map, &c->ws_gray, &c->ws_seg, &c->ws_segoff, &c->ws_nraw, &c->ws_rawxy,
                       &c->ws_rawscore, &c->ws_nms, &c->ws_order, &c->ws_nkept, &c->st_a, &c->st_b, &c->st_c,
-                      &c->st_d, &c->st_e, &c->st_f, &c->ws_pose, &c->ws_tracks, &c->ws_agree, &c->ws_matchn[0], &c->ws_matchn[1], &c->ws_matchn[2], &c->ws_matchn[3], &c->ws_knn};
+                      &c->st_d, &c->st_e, &c->st_f, &c->ws_pose, &c->ws_tracks, &c->ws_agree, &c->ws_matchn[0], &c->ws_matchn[1], &c->ws_matchn[2], &c->ws_matchn[3], &c->ws_knn, &c->ws_guided};
     for (DevBuf *b : bufs) b->release();
     c->pin_in.release();
     c->pin_out.release();
@@ -843,6 +846,120 @@ int pgx_knn(pgx_ctx *c, const uint32_t *desc1, int n1, const uint32_t *desc2, in
     pgx_launch_knn(c, c->stream, c->st_a.as<uint32_t>(), c->st_b.as<int32_t>(), c->st_b.as<int32_t>() + 2, 1, S, words, S, k, d_idx,
                    d_dist, d_col);
     HIPCHK(c, hipGetLastError());
+    if (n1 > 0) {
+        HIPCHK(c, hipMemcpyAsync(idx_out, d_idx, (size_t)n1 * k * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(dist_out, d_dist, (size_t)n1 * k * 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (d_col && n2 > 0) HIPCHK(c, hipMemcpyAsync(col_nn_out, d_col, (size_t)n2 * 4, hipMemcpyDeviceToHost, c->stream));
+    return sync_status(c);
+}
+
+// ---- epipolar-guided exact matching (k_guided.hip) ------------------------------------------------------------------
+
+namespace {
+
+int guided_args(pgx_ctx *c, int stride, int words, int M, int k, float band)
+{
+    const int rc = knn_args(c, stride, words, M, k);
+    if (rc != PGX_OK) return rc;
+    if (!std::isfinite(band) || band < 0.f) return fail(c, PGX_E_BADARG, "band must be finite and >= 0");
+    return PGX_OK;
+}
+
+// the guided top-k (and column nearest) of M image pairs, in chunks of pgx_set_match_chunk pairs that share one grid workspace
+int enqueue_guided(pgx_ctx *c, const uint32_t *d_desc, const pgx_keypoint *d_kp, const int32_t *d_counts, int stride, int words,
+                   const int32_t *d_pairlist, int M, int max_n, const float *d_F, float band, int k, int32_t *d_idx, int32_t *d_dist,
+                   int32_t *d_col)
+{
+    const int CHUNK = c->match_chunk, mc = M < CHUNK ? M : CHUNK;
+    HIPCHK(c, c->ws_guided.ensure(pgx_guided_ws_bytes(mc, max_n)));
+    for (int m0 = 0; m0 < M; m0 += CHUNK) {
+        const int n = M - m0 < CHUNK ? M - m0 : CHUNK;
+        const size_t o = (size_t)m0 * stride;
+        pgx_launch_guided(c, c->stream, d_desc, d_kp, d_counts, d_pairlist + 2 * (size_t)m0, n, stride, words, max_n, d_F + 9 * (size_t)m0,
+                          band, k, d_idx + o * k, d_dist + o * k, d_col ? d_col + o : nullptr, c->ws_guided.p, c->d_status);
+    }
+    HIPCHK(c, hipGetLastError());
+    return PGX_OK;
+}
+
+} // namespace
+
+int pgx_knn_guided_batch_dev(pgx_ctx *c, const uint32_t *d_desc, const pgx_keypoint *d_kp, const int32_t *d_counts, int stride, int words,
+                             const int32_t *d_pairlist, int M, int max_count, const float *d_F, float band, int k, int32_t *d_idx,
+                             int32_t *d_dist, int32_t *d_col_nn)
+{
+    if (!c || !d_desc || !d_kp || !d_counts || !d_pairlist || !d_F || !d_idx || !d_dist || M < 0)
+        return c ? fail(c, PGX_E_BADARG, "null pointer") : PGX_E_BADARG;
+    Lock l(c);
+    const int rc = guided_args(c, stride, words, M, k, band);
+    if (rc != PGX_OK || M == 0) return rc;
+    return enqueue_guided(c, d_desc, d_kp, d_counts, stride, words, d_pairlist, M, clamp_max_count(max_count, stride), d_F, band, k, d_idx,
+                          d_dist, d_col_nn);
+}
+
+int pgx_match_guided_batch_dev(pgx_ctx *c, const uint32_t *d_desc, const pgx_keypoint *d_kp, const int32_t *d_counts, int stride,
+                               int words, const int32_t *d_pairlist, int M, int max_count, const float *d_F, float band, int max_dist,
+                               float ratio, int cross_check, pgx_pair *d_out)
+{
+    if (!c || !d_desc || !d_kp || !d_counts || !d_pairlist || !d_F || !d_out || M < 0)
+        return c ? fail(c, PGX_E_BADARG, "null pointer") : PGX_E_BADARG;
+    Lock l(c);
+    const int rc = guided_args(c, stride, words, M, 2, band);
+    if (rc != PGX_OK) return rc;
+    if (!(ratio <= 1.0f)) return fail(c, PGX_E_BADARG, "ratio must be <= 1 (0 or less: no ratio test)");
+    if (M == 0) return PGX_OK;
+    const int max_n = clamp_max_count(max_count, stride);
+    // as pgx_match_nn_batch_dev: the top-2 and column nearest of one chunk (20 bytes per slot), then the shared selection
+    const int CHUNK = c->match_chunk, mc = M < CHUNK ? M : CHUNK;
+    const size_t slots = (size_t)mc * stride;
+    HIPCHK(c, c->ws_knn.ensure(slots * 5 * sizeof(int32_t)));
+    int32_t *idx = c->ws_knn.as<int32_t>(), *dist = idx + 2 * slots, *col = dist + 2 * slots;
+    for (int m0 = 0; m0 < M; m0 += CHUNK) {
+        const int n = M - m0 < CHUNK ? M - m0 : CHUNK;
+        const int32_t *pl = d_pairlist + 2 * (size_t)m0;
+        const int rg = enqueue_guided(c, d_desc, d_kp, d_counts, stride, words, pl, n, max_n, d_F + 9 * (size_t)m0, band, 2, idx, dist, col);
+        if (rg != PGX_OK) return rg;
+        pgx_launch_knn_select(c, c->stream, d_counts, pl, n, stride, max_n, idx, dist, col, max_dist, ratio, cross_check ? 1 : 0,
+                              d_out + (size_t)m0 * stride);
+    }
+    HIPCHK(c, hipGetLastError());
+    return PGX_OK;
+}
+
+int pgx_knn_guided(pgx_ctx *c, const uint32_t *desc1, const pgx_keypoint *kp1, int n1, const uint32_t *desc2, const pgx_keypoint *kp2,
+                   int n2, int words, const float *F, float band, int k, int32_t *idx_out, int32_t *dist_out, int32_t *col_nn_out)
+{
+    if (!c || !F || n1 < 0 || n2 < 0 || (n1 > 0 && (!desc1 || !kp1 || !idx_out || !dist_out)) || (n2 > 0 && (!desc2 || !kp2)))
+        return c ? fail(c, PGX_E_BADARG, "null pointer") : PGX_E_BADARG;
+    Lock l(c);
+    const int S = n1 > n2 ? n1 : (n2 > 0 ? n2 : 1);
+    if (S > (1 << PGX_IDX_BITS)) return fail(c, PGX_E_BADARG, "more than 2^20 keypoints");
+    const int rc = guided_args(c, S, words, 1, k, band);
+    if (rc != PGX_OK) return rc;
+    if (n1 == 0 && (n2 == 0 || !col_nn_out)) return PGX_OK;
+    // two "frames" of S slots; st_b: counts[2], pairlist[1][2], F[9]; outputs idx [S][k], dist [S][k], col [S]
+    HIPCHK(c, c->st_a.ensure((size_t)2 * S * words * 4));
+    HIPCHK(c, c->st_b.ensure(64));
+    HIPCHK(c, c->st_c.ensure((size_t)S * (2 * k + 1) * 4));
+    HIPCHK(c, c->st_d.ensure((size_t)2 * S * sizeof(pgx_keypoint)));
+    int32_t meta[13] = {n1, n2, 0, 1};
+    std::memcpy(meta + 4, F, 9 * sizeof(float));
+    if (n1 > 0) {
+        HIPCHK(c, hipMemcpyAsync(c->st_a.p, desc1, (size_t)n1 * words * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->st_d.p, kp1, (size_t)n1 * sizeof(pgx_keypoint), hipMemcpyHostToDevice, c->stream));
+    }
+    if (n2 > 0) {
+        HIPCHK(c, hipMemcpyAsync(c->st_a.as<uint32_t>() + (size_t)S * words, desc2, (size_t)n2 * words * 4, hipMemcpyHostToDevice,
+                                 c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->st_d.as<pgx_keypoint>() + S, kp2, (size_t)n2 * sizeof(pgx_keypoint), hipMemcpyHostToDevice, c->stream));
+    }
+    HIPCHK(c, hipMemcpyAsync(c->st_b.p, meta, sizeof meta, hipMemcpyHostToDevice, c->stream));
+    int32_t *d_idx = c->st_c.as<int32_t>(), *d_dist = d_idx + (size_t)S * k, *d_col = col_nn_out ? d_dist + (size_t)S * k : nullptr;
+    const int32_t *d_meta = c->st_b.as<int32_t>();
+    const int rq = enqueue_guided(c, c->st_a.as<uint32_t>(), c->st_d.as<pgx_keypoint>(), d_meta, S, words, d_meta + 2, 1, S,
+                                  reinterpret_cast<const float *>(d_meta + 4), band, k, d_idx, d_dist, d_col);
+    if (rq != PGX_OK) return rq;
     if (n1 > 0) {
         HIPCHK(c, hipMemcpyAsync(idx_out, d_idx, (size_t)n1 * k * 4, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpyAsync(dist_out, d_dist, (size_t)n1 * k * 4, hipMemcpyDeviceToHost, c->stream));

@@ -19,6 +19,7 @@
 #define PGX_ST_KP_CAP     4u
 #define PGX_ST_EMPTY_SET  8u
 #define PGX_ST_INTERNAL   16u  /* a device loop made no progress (a bug, never an input property) */
+#define PGX_ST_BADARG     32u  /* guided matching: a used keypoint coordinate outside [-2^20, 2^20) */
 
 // key = (distance << PGX_IDX_BITS) | index ; limits: index < 2^20, distance < 2^12
 #define PGX_IDX_BITS 20
@@ -114,6 +115,7 @@ struct pgx_ctx {
     DevBuf ws_matchn[4];
     DevBuf ws_pose, ws_tracks;
     DevBuf ws_knn; // pgx_match_nn_batch_dev: top-2 and column nearest of a chunk of image pairs
+    DevBuf ws_guided; // guided matching: the keypoint grids of the frames of a chunk of image pairs
     hipStream_t mstream[4] = {nullptr, nullptr, nullptr, nullptr}; // [0] wide rounds, [1] residual distance rows, [2], [3] per-pair finishes (alternating)
     hipEvent_t ev_in = nullptr, ev_wide[4] = {nullptr, nullptr, nullptr, nullptr}, ev_rows[4] = {nullptr, nullptr, nullptr, nullptr},
                ev_fin[4] = {nullptr, nullptr, nullptr, nullptr}, ev_join[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -284,3 +286,11 @@ void pgx_launch_knn(pgx_ctx *ctx, hipStream_t s, const uint32_t *d_desc, const i
 void pgx_launch_knn_select(pgx_ctx *ctx, hipStream_t s, const int32_t *d_counts, const int32_t *d_pairlist, int M, int S, int max_n,
                            const int32_t *d_idx, const int32_t *d_dist, const int32_t *d_col, int max_dist, float ratio,
                            int cross_check, pgx_pair *d_out);
+
+// k_guided.hip (epipolar-guided exact matching; pgx_knn_guided_batch_dev semantics, include/pgx.h)
+// workspace bytes for a chunk of M image pairs
+size_t pgx_guided_ws_bytes(int M, int max_n);
+// d_idx / d_dist [M][S][k], d_col [M][S] or nullptr; d_F [M][9]; max_n in [1, S], k in {1, 2}, band finite and >= 0
+void pgx_launch_guided(pgx_ctx *ctx, hipStream_t s, const uint32_t *d_desc, const pgx_keypoint *d_kp, const int32_t *d_counts,
+                       const int32_t *d_pairlist, int M, int S, int words, int max_n, const float *d_F, float band, int k,
+                       int32_t *d_idx, int32_t *d_dist, int32_t *d_col, void *ws, int *status);

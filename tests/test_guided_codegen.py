@@ -1,0 +1,120 @@
+"""CPU test (no GPU): the epipolar-guided kernels (photogrammetry_amd/csrc/k_guided.hip) and their numpy yardstick.
+  * the kernels are in libpgx.so's code object with no private segment and no spills;
+  * the compiler's listing of the band walk has no v_fma_f64: the predicate of include/pgx.h is one rounding per operation;
+  * the yardstick of tests/guided_ref.py (used by tests/test_gpu_guided.py) equals a literal Python double loop.
+"""
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import photogrammetry_amd._lib as L
+from guided_ref import NONE, loop_guided, ref_guided
+
+LLVM = "/opt/rocm/lib/llvm/bin"
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+KERNELS = ("k_guided_slots", "k_guided_bucket", "k_guided_walk", "k_guided_col_init", "k_guided_col_finish")
+
+
+@pytest.fixture(scope="module")
+def code_objects(tmp_path_factory):
+    if not os.path.exists(os.path.join(LLVM, "llvm-readelf")):
+        pytest.skip("llvm-readelf not found")
+    L.build()
+    d = str(tmp_path_factory.mktemp("guided_co"))
+    so = os.path.join(d, "libpgx.so")
+    shutil.copy(L.LIB_PATH, so)
+    subprocess.run([os.path.join(LLVM, "llvm-objdump"), "--offloading", so], cwd=d, check=True, capture_output=True)
+    return [os.path.join(d, f) for f in sorted(os.listdir(d)) if "amdgcn" in f]
+
+
+def _kernels(objs, needle):
+    out = []
+    for o in objs:
+        notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", o], check=True, capture_output=True, text=True).stdout
+        for item in re.split(r"\n  - (?=\.)", notes):
+            m = re.search(r"\.name:\s+(\S+)", item)
+            if m and needle in m.group(1) and not m.group(1).endswith(".kd"):
+                md = {"name": m.group(1)}
+                for key in ("vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size"):
+                    mm = re.search(r"\.%s:\s+(\d+)" % key, item)
+                    if mm:
+                        md[key] = int(mm.group(1))
+                out.append(md)
+    return out
+
+
+def test_guided_kernels_exist_without_scratch(code_objects):
+    for needle in KERNELS:
+        mds = _kernels(code_objects, needle)
+        # the walk: k in {1, 2} x column side on / off x (256-bit descriptors in registers, any width)
+        assert len({md["name"] for md in mds}) == (8 if needle == "k_guided_walk" else 1), (needle, [md["name"] for md in mds])
+        for md in mds:
+            assert md["private_segment_fixed_size"] == 0, md
+            assert md["vgpr_spill_count"] == 0 and md["sgpr_spill_count"] == 0, md
+
+
+def test_walk_predicate_is_not_contracted(tmp_path):
+    hipcc = "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("hipcc not found")
+    out = os.path.join(str(tmp_path), "k_guided.s")
+    subprocess.run([hipcc, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-fast-math",
+                    "--cuda-device-only", "-S", os.path.join(ROOT, "photogrammetry_amd", "csrc", "k_guided.hip"), "-o", out],
+                   check=True, capture_output=True)
+    lines = open(out).read().split("\n")
+    starts = [i for i, l in enumerate(lines) if re.match(r"^_ZN.*k_guided_walk.*:", l)]
+    assert len(starts) == 8
+    for start in starts:
+        end = next(i for i in range(start, len(lines)) if lines[i].startswith(".Lfunc_end"))
+        body = [l.strip().split(";")[0].strip() for l in lines[start:end]
+                if l.startswith("\t") and not l.startswith("\t.") and not l.strip().startswith(";")]
+        assert any(i.startswith("v_mul_f64") for i in body) and any(i.startswith("v_add_f64") for i in body), lines[start]
+        assert not [i for i in body if i.startswith("v_fma_f64")], lines[start]
+        assert not [i for i in body if i.startswith("scratch_")], lines[start]
+
+
+def _case(rng, n1, n2, words, span):
+    da = rng.integers(0, 2**32, size=(n1, words), dtype=np.uint32)
+    db = rng.integers(0, 2**32, size=(n2, words), dtype=np.uint32)
+    kpa = rng.integers(-span, span, size=(n1, 2)).astype(np.int32)
+    kpb = rng.integers(-span, span, size=(n2, 2)).astype(np.int32)
+    return da, db, kpa, kpb
+
+
+def _check(da, db, kpa, kpb, F, band):
+    rows, cols = loop_guided(da, db, kpa, kpb, F, band)
+    idx, dist, col = ref_guided(da, db, kpa, kpb, F, band, block=3)
+    for i, row in enumerate(rows):
+        exp = row + [(NONE, -1)] * (2 - len(row))
+        assert [(int(dist[i, e]), int(idx[i, e])) for e in range(2)] == exp, (i, band)
+    assert list(col) == cols, band
+
+
+def test_yardstick_equals_the_literal_loop():
+    rng = np.random.default_rng(0)
+    for words, n1, n2, span in [(8, 9, 11, 50), (5, 7, 13, 20), (1, 12, 6, 8), (3, 5, 0, 10), (8, 0, 4, 10), (2, 16, 16, 4)]:
+        da, db, kpa, kpb = _case(rng, n1, n2, words, span)
+        for F in (rng.normal(size=9), np.array([0, 0, 0, 0, 0, -1, 0, 1, 0]), np.array([1, 0, 0, 0, 1, 0, -3, 2, 1])):
+            for band in (0.0, 0.5, 1.0, 2.0, 7.5, 1e30):
+                _check(da, db, kpa, kpb, np.asarray(F, dtype=np.float32), band)
+
+
+def test_yardstick_edges():
+    rng = np.random.default_rng(1)
+    da, db, kpa, kpb = _case(rng, 6, 9, 8, 10)
+    kpb[:, 1] = kpa[rng.integers(0, 6, 9), 1] + rng.integers(-3, 4, 9)      # rows of the axis-aligned lines at 0..3 px
+    F_axis = np.array([0, 0, 0, 0, 0, -1, 0, 1, 0], dtype=np.float32)
+    for band in (3.0, float(np.nextafter(np.float32(3), np.float32(0))), 0.0):
+        _check(da, db, kpa, kpb, F_axis, band)
+    for bad in (np.zeros(9), np.r_[np.nan, np.ones(8)], np.r_[np.ones(8), np.inf]):
+        _check(da, db, kpa, kpb, np.asarray(bad, dtype=np.float32), 5.0)
+        idx, _, col = ref_guided(da, db, kpa, kpb, np.asarray(bad, dtype=np.float32), 5.0)
+        assert (idx == -1).all() and (col == -1).all()
+    # out-of-range coordinates reject every row
+    kpb[0, 0] = 1 << 20
+    idx, _, col = ref_guided(da, db, kpa, kpb, F_axis, 5.0)
+    assert (idx == -1).all() and (col == -1).all()
