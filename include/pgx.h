@@ -345,17 +345,53 @@ int pgx_tracks_dev(pgx_ctx *ctx, const pgx_pair *d_matches, const int32_t *d_cou
                    int stride, const int32_t *d_frame_ids, int n_frames, int max_dist, int min_len,
                    int32_t *d_track_of, int32_t *d_offsets, int32_t *d_nodes, int32_t *d_summary);
 
+/* Split mode: inconsistent components are split at tighter gates instead of dropped whole.
+ * Inputs: the same as pgx_tracks_dev, plus n_gates refinement gates with max_dist > gates[0] > gates[1] > ... > gates[n-1] >= 0
+ * and 0 <= n_gates <= 7.  Write g_0 = max_dist and g_l = gates[l-1].
+ *   E_l     the match entries that pgx_tracks_dev would use as edges at gate g_l.  These are the same filters as today:
+ *           e < counts[a], k1 and k2 in range, never the PGX_DIST_NONE tail and never k2 = -1 rows of NN lists.  The only
+ *           change is dist <= g_l.  So E_0 ⊇ E_1 ⊇ ... ⊇ E_n.
+ *   C_l(x)  the connected component of node x in (nodes, E_l).  Components nest: C_l(x) ⊆ C_{l-1}(x).
+ *   level   the level of x is the smallest l for which C_l(x) is consistent, meaning it has at most one keypoint per frame.
+ *           If x has a level, its group is C_level(x).  Every node of that group has the same level and the same group, so
+ *           the groups partition the nodes that have a level.
+ *   tracks  the groups with at least min_len nodes.  Nodes of smaller groups get -1.  Nodes with no level (C_n(x) is still
+ *           inconsistent) get -2 and count as dropped.
+ *   order   the same as today: tracks are sorted by first (frame, keypoint), and nodes inside a track ascend.
+ * This is a cut of the single-linkage hierarchy at the coarsest consistent level among the given gates.  It does not depend
+ * on the order in which edges are processed.  With n_gates = 0 it is exactly pgx_tracks_dev.
+ * gates is a HOST array [n_gates].  Unordered gates, a gate at or above max_dist, a negative gate or n_gates outside [0, 7]:
+ * PGX_E_BADARG.  Layouts and argument checks as pgx_tracks_dev; asynchronous on the context's stream.  In this mode the slots
+ * of d_frame_ids must name distinct frames: two slots naming one frame are reported as PGX_E_BADARG by pgx_check_status.
+ *   d_summary [16]  [0..7] as pgx_tracks_dev: [2], [3] and [6] are the components still inconsistent at the last gate, [4]
+ *                   counts the edges of E_0, [7] is 0.  [8 + l] = nodes in tracks whose level is l (unused slots 0);
+ *                   [8] + ... + [15] = [1]. */
+int pgx_tracks_split_dev(pgx_ctx *ctx, const pgx_pair *d_matches, const int32_t *d_counts, const int32_t *d_pairlist, int M, int F,
+                         int stride, const int32_t *d_frame_ids, int n_frames, int max_dist, const int32_t *gates, int n_gates,
+                         int min_len, int32_t *d_track_of, int32_t *d_offsets, int32_t *d_nodes, int32_t *d_summary);
+
 /* Host form, no GPU work (small inputs; a host that holds the lists in managed memory): the same semantics, sequential.
  * counts [n_frames] = keypoints per frame. */
 typedef struct pgx_tracks pgx_tracks;
 int  pgx_tracks_create(const int32_t *counts, int n_frames, pgx_tracks **out);
 void pgx_tracks_destroy(pgx_tracks *t);
-/* matches: the first n entries of one image pair's list (n = counts[frame_a]). */
+/* matches: the first n entries of one image pair's list (n = counts[frame_a]).  The gated edges (node a, node b, dist) are
+ * kept in the object, so that pgx_tracks_finish_split can recompute the levels. */
 int  pgx_tracks_add_pair(pgx_tracks *t, int frame_a, int frame_b, const pgx_pair *matches, int n, int max_dist);
 /* Closes the graph: *n_tracks consistent components of at least min_len nodes with *n_nodes nodes in all. */
 int  pgx_tracks_finish(pgx_tracks *t, int min_len, int *n_tracks, int *n_nodes);
+/* After either finish call. */
 int  pgx_tracks_get(pgx_tracks *t, int32_t *track_offsets /* [n_tracks + 1] */, int32_t *nodes /* [n_nodes][2] = (frame, keypoint) */);
-/* After pgx_tracks_finish: inconsistent components and the nodes in them (what d_summary[2], [3] report on the device). */
+/* The split mode's host form (the rule of pgx_tracks_split_dev; level 0 = the edges as added).  gates [n_gates], strictly
+ * decreasing, >= 0, n_gates in [0, 7], else PGX_E_BADARG.  An edge that was added with a per-pair max_dist smaller than
+ * gates[l] enters level l only if its distance is also within that pair's max_dist: g_l of a pair is min(its max_dist, g_l).
+ * (This follows from pgx_tracks_add_pair keeping only the entries within the pair's max_dist.)
+ * summary [16] as d_summary of pgx_tracks_split_dev (or NULL).  Closes the graph like pgx_tracks_finish; more edges may be
+ * added and either finish call made again. */
+int  pgx_tracks_finish_split(pgx_tracks *t, const int32_t *gates, int n_gates, int min_len, int *n_tracks, int *n_nodes,
+                             int32_t *summary /* [16] */);
+/* After either finish call: inconsistent components (at the last gate) and the nodes in them (what d_summary[2], [3] report
+ * on the device). */
 int  pgx_tracks_dropped(pgx_tracks *t, int *n_components, int *n_nodes);
 
 /* ---- measurement hooks (bench.py) ---------------------------------------------------- */

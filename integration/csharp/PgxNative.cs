@@ -103,6 +103,14 @@ internal static unsafe class PgxNative
     [DllImport(Lib)] public static extern int pgx_tracks_dev(IntPtr ctx, void* dMatches, void* dCounts, void* dPairlist, int m, int f, int stride,
                                                              void* dFrameIds, int nFrames, int maxDist, int minLen, void* dTrackOf,
                                                              void* dOffsets, void* dNodes, void* dSummary);
+    // split mode: components inconsistent at maxDist are split at the tighter gates (host array, strictly decreasing) instead of
+    // dropped; dSummary [16], [8 + l] = nodes in tracks of level l
+    [DllImport(Lib)] public static extern int pgx_tracks_split_dev(IntPtr ctx, void* dMatches, void* dCounts, void* dPairlist, int m, int f,
+                                                                   int stride, void* dFrameIds, int nFrames, int maxDist, int* gates,
+                                                                   int nGates, int minLen, void* dTrackOf, void* dOffsets, void* dNodes,
+                                                                   void* dSummary);
+    [DllImport(Lib)] public static extern int pgx_tracks_finish_split(IntPtr tracks, int* gates, int nGates, int minLen, out int nTracks,
+                                                                      out int nNodes, int* summary);
 
     /// <summary>Maps a status code back to the exception type the managed implementation throws.</summary>
     public static void Check(IntPtr ctx, int rc)

@@ -31,6 +31,7 @@ EXPORTS = [
     "pgx_tracks_finish", "pgx_tracks_get", "pgx_tracks_dropped", "pgx_tracks_dev", "pgx_fundamental_ransac_dev", "pgx_pose_dev",
     "pgx_knn_batch_dev", "pgx_match_nn_batch_dev", "pgx_knn",
     "pgx_knn_guided_batch_dev", "pgx_match_guided_batch_dev", "pgx_knn_guided",
+    "pgx_tracks_split_dev", "pgx_tracks_finish_split",
 ]
 
 

@@ -329,6 +329,17 @@ class Engine:
                                          _dptr(d_frame_ids) if d_frame_ids is not None else None, int(n_frames), int(max_dist),
                                          int(min_len), _dptr(d_track_of), _dptr(d_offsets), _dptr(d_nodes), _dptr(d_summary)))
 
+    def tracks_split_dev(self, d_matches, d_counts, d_pairlist, M, F, stride, n_frames, max_dist, gates, min_len, d_track_of,
+                         d_offsets, d_nodes, d_summary, d_frame_ids=None):
+        """The split mode (pgx_tracks_split_dev): a component inconsistent at max_dist is split at the first of the tighter
+        `gates` (strictly decreasing, below max_dist, >= 0, at most 7) where its parts are consistent, instead of dropped.
+        Layouts as tracks_dev, but d_summary [16]: [8 + l] = nodes in tracks resolved at level l (level 0 = max_dist)."""
+        g = np.ascontiguousarray(list(gates), dtype=np.int32)
+        self._chk(self._L.pgx_tracks_split_dev(self._h, _dptr(d_matches), _dptr(d_counts), _dptr(d_pairlist), int(M), int(F),
+                                               int(stride), _dptr(d_frame_ids) if d_frame_ids is not None else None,
+                                               int(n_frames), int(max_dist), _ptr(g) if len(g) else None, len(g), int(min_len),
+                                               _dptr(d_track_of), _dptr(d_offsets), _dptr(d_nodes), _dptr(d_summary)))
+
     # -- multi-GPU: the context's own RCCL communicator (pgx_comm_*) ------------------------------
     def comm_init(self, rank, world, unique_id):
         """Collective: every rank calls this with the 128 bytes rank 0 got from comm_unique_id()."""
@@ -393,10 +404,12 @@ def comm_unique_id():
     return bytes(buf)
 
 
-def tracks_host(counts, pair_list, lists, max_dist, min_len=2):
+def tracks_host(counts, pair_list, lists, max_dist, min_len=2, gates=None):
     """The host form of the track graph (pgx_tracks_*: sequential, no GPU work; same semantics as Engine.tracks_dev).
     counts [F]; pair_list [(a, b)]; lists[m] = that pair's match list ([n][3] ints or PAIR_DTYPE).
-    -> (tracks, dropped_components, dropped_nodes); tracks = list of [(frame, keypoint)] lists in pgx_tracks_get's order."""
+    -> (tracks, dropped_components, dropped_nodes); tracks = list of [(frame, keypoint)] lists in pgx_tracks_get's order.
+    gates (a list, possibly empty): the split mode (pgx_tracks_finish_split, the rule of Engine.tracks_split_dev)
+    -> (tracks, dropped_components, dropped_nodes, per_level); per_level[l] = nodes in tracks of level l, l = 0 .. len(gates)."""
     L = _lib.lib()
     c = np.ascontiguousarray(counts, dtype=np.int32)
     h = C.c_void_p()
@@ -411,13 +424,25 @@ def tracks_host(counts, pair_list, lists, max_dist, min_len=2):
             if L.pgx_tracks_add_pair(h, int(a), int(b), _ptr(rows), len(rows), int(max_dist)) != PGX_OK:
                 raise PgxError(PGX_E_BADARG, "pgx_tracks_add_pair(%d, %d)" % (a, b))
         nt, nn, nd, ndn = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
-        if L.pgx_tracks_finish(h, int(min_len), C.byref(nt), C.byref(nn)) != PGX_OK:
-            raise PgxError(PGX_E_BADARG, "pgx_tracks_finish")
+        if gates is None:
+            if L.pgx_tracks_finish(h, int(min_len), C.byref(nt), C.byref(nn)) != PGX_OK:
+                raise PgxError(PGX_E_BADARG, "pgx_tracks_finish")
+        else:
+            g = np.ascontiguousarray(list(gates), dtype=np.int32)
+            summary = np.zeros(16, dtype=np.int32)
+            if len(g) and g[0] >= max_dist:
+                raise ArgumentException(PGX_E_BADARG, "gates must be below max_dist")
+            if L.pgx_tracks_finish_split(h, _ptr(g) if len(g) else None, len(g), int(min_len), C.byref(nt), C.byref(nn),
+                                         _ptr(summary)) != PGX_OK:
+                raise ArgumentException(PGX_E_BADARG, "pgx_tracks_finish_split: gates %s" % g.tolist())
         off = np.zeros(nt.value + 1, dtype=np.int32)
         nodes = np.zeros((max(nn.value, 1), 2), dtype=np.int32)
         if L.pgx_tracks_get(h, _ptr(off), _ptr(nodes)) != PGX_OK or L.pgx_tracks_dropped(h, C.byref(nd), C.byref(ndn)) != PGX_OK:
             raise PgxError(PGX_E_BADARG, "pgx_tracks_get")
-        return [[(int(f), int(k)) for f, k in nodes[off[t]:off[t + 1]]] for t in range(nt.value)], nd.value, ndn.value
+        tracks = [[(int(f), int(k)) for f, k in nodes[off[t]:off[t + 1]]] for t in range(nt.value)]
+        if gates is None:
+            return tracks, nd.value, ndn.value
+        return tracks, nd.value, ndn.value, summary[8:9 + len(g)].tolist()
     finally:
         L.pgx_tracks_destroy(h)
 

@@ -46,6 +46,8 @@ constexpr int TRK_ECNT = 256;        // slots of the edge counter
 // 64: 1.45, 128: 0.82, 192: 0.62, 256: 0.55, 512: 0.59, 1024: 0.65, 2048: 0.81, 4096: 0.90, one per 256 entries (32 k): 0.70 --
 // fewer threads in flight see fresher trees and lose fewer CAS, too few leave the dependent L2 reads uncovered; one per CU it is
 constexpr int TRK_UNION_GRID = 256;
+// ... and of k_trks_union, the refinement levels of the split mode
+constexpr int TRKS_UNION_GRID = 256;
 static_assert(TRK_ECNT <= SCAN_NT, "k_trk_scan_sums adds the edge-counter slots up in one block scan");
 constexpr int FL_SLOTS = 512;        // LDS aggregation table of k_trk_flatten (>= 2 * TRK_NT)
 
@@ -170,10 +172,10 @@ __global__ __launch_bounds__(TRK_NT) void k_trk_union(TrkArgs a, long long n_ite
 // insert into the frame's table.  (Straight per-node global atomics serialise on a big component's root: the 56 k nodes of
 // the bench job's largest (inconsistent) component took 0.56 of the launch's 0.64 ms.)  Two nodes of the workgroup with one
 // root are two keypoints of this frame in one component: flagged here, without the global table.
-__global__ __launch_bounds__(TRK_NT) void k_trk_flatten(TrkArgs a)
+// (the body is shared with k_trks_flatten, which passes the active-node mask of a refinement level: nodes outside it keep
+// their root; `active` = nullptr here)
+__device__ __forceinline__ void trk_flatten(const TrkArgs &a, const int32_t *active, uint32_t *hkey, int *hcnt, int *hmin)
 {
-    __shared__ uint32_t hkey[FL_SLOTS];
-    __shared__ int hcnt[FL_SLOTS], hmin[FL_SLOTS];
     const int chunks = (a.stride + TRK_NT - 1) / TRK_NT;
     const int s = blockIdx.x / chunks, k = (blockIdx.x % chunks) * TRK_NT + threadIdx.x;
     const int f = fid_of(a, s);
@@ -183,7 +185,7 @@ __global__ __launch_bounds__(TRK_NT) void k_trk_flatten(TrkArgs a)
     if ((blockIdx.x % chunks) * TRK_NT >= c) return;   // uniform
     for (int i = threadIdx.x; i < FL_SLOTS; i += TRK_NT) { hkey[i] = TRK_EMPTY; hcnt[i] = 0; hmin[i] = 0x7FFFFFFF; }
     __syncthreads();
-    if (k < c) {
+    if (k < c && (!active || active[f * a.stride + k])) {
         const int x = f * a.stride + k;
         const int r = trk_find(a.parent, x);
         // into an array of its own: other threads' pointer jumping still stores (older) ancestors into parent[x] while this runs
@@ -215,6 +217,13 @@ __global__ __launch_bounds__(TRK_NT) void k_trk_flatten(TrkArgs a)
             h++;
         }
     }
+}
+
+__global__ __launch_bounds__(TRK_NT) void k_trk_flatten(TrkArgs a)
+{
+    __shared__ uint32_t hkey[FL_SLOTS];
+    __shared__ int hcnt[FL_SLOTS], hmin[FL_SLOTS];
+    trk_flatten(a, nullptr, hkey, hcnt, hmin);
 }
 
 // A component is named by its FIRST node (smallest id): that is where it stands in the scan.  -> root of the component x names, or -1
@@ -375,6 +384,126 @@ __global__ __launch_bounds__(TRK_NT) void k_trk_rank(TrkArgs a)
     a.nodes[2 * (size_t)(o + rank) + 1] = k;
 }
 
+
+// ---- refinement levels (pgx_tracks_split_dev) -------------------------------------------------------------------------------
+// Level 0 is the graph above at g_0 = max_dist (init -> union -> flatten).  Then, for l = 0 .. n_gates:
+//   k_trks_mark    one thread per node that was still unresolved before level l (every node at l = 0): its component at g_l
+//                  is consistent -> resolved at level l (counted into summary[8 + l] when the group is a track), else
+//                  active[x] = 1 for level l + 1.  live[l] = nodes left active.  At l = 0 it also claims frame f for its slot
+//                  (owner[f]): two slots naming one frame set PGX_ST_DUP_FRAME.
+//   k_trks_reset   (l < n_gates) parent, size, rep, flag of ACTIVE nodes back to init, per-frame tables cleared.  Not fused
+//                  into mark: one node's thread would clear a flag (of its root) that another node's thread is about to read.
+//   k_trks_union   (level l + 1) the edges of E_{l+1} whose end u is active; by nesting v then is active too (both ends of an
+//                  edge of E_{l+1} ⊆ E_l lie in one C_l component, and activity is a property of that component)
+//   k_trks_flatten (level l + 1) k_trk_flatten over the active nodes only
+// Slot reuse: a resolved node is never reset and never reached again -- finds start at active nodes, and the parents of
+// active nodes were reset to themselves, so walks and CAS stay inside the active set.  The root of a resolved group is a
+// node of that group, hence resolved: its size, rep and flag survive, root[] of its nodes still names it.  After the last
+// level root / rep / size / flag describe the final groups, and the scan -> place -> rank kernels above run unchanged.
+// Stale reads: k_trks_union / k_trks_flatten see parent[] as the reset launch left it (kernel boundaries on one stream
+// order the values -- the same argument as for k_trk_init before k_trk_union); within a level every parent value of an
+// active node is that node or an ancestor at this level, so trk_find's argument holds as stated there.
+// No node active any more: the later launches read live[] and return (no host synchronisation).
+struct SplitArgs {
+    int32_t *active;   // [N] 1 = unresolved so far (valid only at nodes below a frame's count)
+    int32_t *live;     // [8] live[l] = nodes still unresolved after level l
+    int32_t *owner;    // [n_frames] the slot that claimed each frame (-1 = none)
+    int *status;
+};
+
+__global__ __launch_bounds__(TRK_NT) void k_trks_prep(TrkArgs a, SplitArgs s)
+{
+    const long long nthreads = (long long)gridDim.x * TRK_NT;
+    const long long t0 = (long long)blockIdx.x * TRK_NT + threadIdx.x;
+    for (long long x = t0; x < a.N; x += nthreads) s.active[x] = 0;
+    for (long long f = t0; f < a.n_frames; f += nthreads) s.owner[f] = -1;
+    if (t0 < 8) { a.summary[8 + t0] = 0; s.live[t0] = 0; }
+}
+
+// grid: F * ceil(stride / TRK_NT), as k_trk_flatten
+__global__ __launch_bounds__(TRK_NT) void k_trks_mark(TrkArgs a, SplitArgs sp, int level, int last)
+{
+    if (level > 0 && ld(sp.live + level - 1) == 0) return;   // uniform: nothing was left unresolved
+    const int chunks = (a.stride + TRK_NT - 1) / TRK_NT;
+    const int s = blockIdx.x / chunks, k = (blockIdx.x % chunks) * TRK_NT + threadIdx.x;
+    const int f = fid_of(a, s);
+    if ((unsigned)f >= (unsigned)a.n_frames) return;   // uniform
+    if (level == 0 && blockIdx.x % chunks == 0 && threadIdx.x == 0) {
+        const int old = atomicCAS(sp.owner + f, -1, s);
+        if (old != -1 && old != s) atomicOr(sp.status, (int)PGX_ST_DUP_FRAME);
+    }
+    int c = a.counts[s];
+    c = c > a.stride ? a.stride : c;
+    if ((blockIdx.x % chunks) * TRK_NT >= c) return;   // uniform
+    bool resolved = false, still = false;
+    if (k < c) {
+        const int x = f * a.stride + k;
+        if (level == 0 || sp.active[x]) {
+            const int r = a.root[x];
+            still = a.flag[r] != 0;
+            resolved = !still && a.size[r] >= a.min_len;
+            if (!last) sp.active[x] = still;
+        }
+    }
+    // per wave by ballot, per workgroup in LDS, then one global atomic each (same-address atomics serialise)
+    __shared__ int agg[2];
+    if (threadIdx.x < 2) agg[threadIdx.x] = 0;
+    __syncthreads();
+    const int nr = __popcll(__ballot(resolved)), ns = __popcll(__ballot(still));
+    if ((threadIdx.x & 63) == 0) {
+        if (nr) atomicAdd(&agg[0], nr);
+        if (ns) atomicAdd(&agg[1], ns);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (agg[0]) atomicAdd(a.summary + 8 + level, agg[0]);
+        if (agg[1] && !last) atomicAdd(sp.live + level, agg[1]);
+    }
+}
+
+// between level `level` and the next one; grid-stride over the nodes and the per-frame tables
+__global__ __launch_bounds__(TRK_NT) void k_trks_reset(TrkArgs a, SplitArgs sp, int level)
+{
+    if (ld(sp.live + level) == 0) return;
+    const long long nthreads = (long long)gridDim.x * TRK_NT;
+    const long long t0 = (long long)blockIdx.x * TRK_NT + threadIdx.x;
+    for (long long x = t0; x < a.N; x += nthreads) {
+        if (!sp.active[x]) continue;
+        a.parent[x] = (int)x;
+        a.rep[x] = 0x7FFFFFFF;
+        a.size[x] = 0;
+        a.flag[x] = 0;
+    }
+    const long long nt = (long long)a.n_frames * a.T;
+    for (long long i = t0; i < nt; i += nthreads) a.table[i] = TRK_EMPTY;
+}
+
+// level >= 1: k_trk_union over the edges of E_level (a.max_dist = the level's gate) with an active end; edges are not counted
+// (summary[4] is |E_0|)
+__global__ __launch_bounds__(TRK_NT) void k_trks_union(TrkArgs a, SplitArgs sp, int level, long long n_items)
+{
+    if (ld(sp.live + level - 1) == 0) return;
+    for (long long item = blockIdx.x; item < n_items; item += gridDim.x) {
+        int u = 0, v = 0;
+        if (!trk_edge(a, item, u, v) || !sp.active[u]) continue;
+        int ru = trk_find(a.parent, u), rv = trk_find(a.parent, v);
+        while (ru != rv) {
+            if (trk_prio(ru) < trk_prio(rv)) { const int t = ru; ru = rv; rv = t; }
+            const int old = atomicCAS(a.parent + ru, ru, rv);
+            if (old == ru) break;
+            ru = trk_find(a.parent, old);
+        }
+    }
+}
+
+__global__ __launch_bounds__(TRK_NT) void k_trks_flatten(TrkArgs a, SplitArgs sp, int level)
+{
+    __shared__ uint32_t hkey[FL_SLOTS];
+    __shared__ int hcnt[FL_SLOTS], hmin[FL_SLOTS];
+    if (ld(sp.live + level - 1) == 0) return;
+    trk_flatten(a, sp.active, hkey, hcnt, hmin);
+}
+
 } // namespace
 
 size_t pgx_tracks_ws_bytes(int n_frames, int stride)
@@ -386,9 +515,11 @@ size_t pgx_tracks_ws_bytes(int n_frames, int stride)
     return 9 * N * 4 + (size_t)n_frames * T * 4 + nb * 8 + TRK_ECNT * 4 + 1024;
 }
 
-void pgx_launch_tracks(hipStream_t s, const pgx_pair *d_matches, const int32_t *d_counts, const int32_t *d_pairlist, int M, int F,
-                       int stride, const int32_t *d_frame_ids, int n_frames, int max_dist, int min_len, void *ws,
-                       int32_t *d_track_of, int32_t *d_offsets, int32_t *d_nodes, int32_t *d_summary)
+namespace {
+
+TrkArgs trk_args(const pgx_pair *d_matches, const int32_t *d_counts, const int32_t *d_pairlist, int M, int F, int stride,
+                 const int32_t *d_frame_ids, int n_frames, int max_dist, int min_len, void *ws, int32_t *d_track_of,
+                 int32_t *d_offsets, int32_t *d_nodes, int32_t *d_summary)
 {
     TrkArgs a;
     a.matches = d_matches; a.counts = d_counts; a.pairlist = d_pairlist; a.frame_ids = d_frame_ids;
@@ -406,25 +537,93 @@ void pgx_launch_tracks(hipStream_t s, const pgx_pair *d_matches, const int32_t *
     a.bsum = reinterpret_cast<unsigned long long *>(static_cast<char *>(ws) + ((tab_end + 7) & ~(size_t)7));
     a.ecnt = reinterpret_cast<int32_t *>(a.bsum + (a.N + SCAN_ITEMS - 1) / SCAN_ITEMS);
     a.track_of = d_track_of; a.offsets = d_offsets; a.nodes = d_nodes; a.summary = d_summary;
+    return a;
+}
 
-    const int chunks = (stride + TRK_NT - 1) / TRK_NT;
-    const long long init_items = a.N > (long long)n_frames * a.T ? a.N : (long long)n_frames * a.T;
+// grid of the grid-stride kernels over the nodes and the tables
+unsigned trk_init_grid(const TrkArgs &a)
+{
+    const long long init_items = a.N > (long long)a.n_frames * a.T ? a.N : (long long)a.n_frames * a.T;
     long long gi = (init_items + TRK_NT - 1) / TRK_NT;
     if (gi > 4096) gi = 4096;
     if (gi < 1) gi = 1;
-    hipLaunchKernelGGL(k_trk_init, dim3((unsigned)gi), dim3(TRK_NT), 0, s, a);
-    if (M > 0) {
-        const long long n_items = (long long)M * chunks;
+    return (unsigned)gi;
+}
+
+// init -> union -> flatten at a.max_dist
+void trk_launch_graph(hipStream_t s, const TrkArgs &a)
+{
+    const int chunks = (a.stride + TRK_NT - 1) / TRK_NT;
+    hipLaunchKernelGGL(k_trk_init, dim3(trk_init_grid(a)), dim3(TRK_NT), 0, s, a);
+    if (a.M > 0) {
+        const long long n_items = (long long)a.M * chunks;
         const long long gu = n_items < TRK_UNION_GRID ? n_items : TRK_UNION_GRID;
         hipLaunchKernelGGL(k_trk_union, dim3((unsigned)gu), dim3(TRK_NT), 0, s, a, n_items);
     }
-    if (F > 0) hipLaunchKernelGGL(k_trk_flatten, dim3((unsigned)((size_t)F * chunks)), dim3(TRK_NT), 0, s, a);
+    if (a.F > 0) hipLaunchKernelGGL(k_trk_flatten, dim3((unsigned)((size_t)a.F * chunks)), dim3(TRK_NT), 0, s, a);
+}
+
+// scan -> place -> rank: the outputs from root / rep / size / flag
+void trk_launch_output(hipStream_t s, const TrkArgs &a)
+{
+    const int chunks = (a.stride + TRK_NT - 1) / TRK_NT;
     const int nb = (int)((a.N + SCAN_ITEMS - 1) / SCAN_ITEMS);
     hipLaunchKernelGGL(k_trk_scan_reduce, dim3(nb), dim3(SCAN_NT), 0, s, a);
     hipLaunchKernelGGL(k_trk_scan_sums, dim3(1), dim3(SCAN_NT), 0, s, a, nb);
     hipLaunchKernelGGL(k_trk_scan_apply, dim3(nb), dim3(SCAN_NT), 0, s, a);
-    if (F > 0) {
-        hipLaunchKernelGGL(k_trk_place, dim3((unsigned)((size_t)F * chunks)), dim3(TRK_NT), 0, s, a);
-        hipLaunchKernelGGL(k_trk_rank, dim3((unsigned)((size_t)F * chunks)), dim3(TRK_NT), 0, s, a);
+    if (a.F > 0) {
+        hipLaunchKernelGGL(k_trk_place, dim3((unsigned)((size_t)a.F * chunks)), dim3(TRK_NT), 0, s, a);
+        hipLaunchKernelGGL(k_trk_rank, dim3((unsigned)((size_t)a.F * chunks)), dim3(TRK_NT), 0, s, a);
     }
+}
+
+} // namespace
+
+void pgx_launch_tracks(hipStream_t s, const pgx_pair *d_matches, const int32_t *d_counts, const int32_t *d_pairlist, int M, int F,
+                       int stride, const int32_t *d_frame_ids, int n_frames, int max_dist, int min_len, void *ws,
+                       int32_t *d_track_of, int32_t *d_offsets, int32_t *d_nodes, int32_t *d_summary)
+{
+    const TrkArgs a = trk_args(d_matches, d_counts, d_pairlist, M, F, stride, d_frame_ids, n_frames, max_dist, min_len, ws,
+                               d_track_of, d_offsets, d_nodes, d_summary);
+    trk_launch_graph(s, a);
+    trk_launch_output(s, a);
+}
+
+size_t pgx_tracks_split_ws_bytes(int n_frames, int stride)
+{
+    const size_t N = (size_t)n_frames * stride;
+    return pgx_tracks_ws_bytes(n_frames, stride) + N * 4 + 8 * 4 + (size_t)n_frames * 4;
+}
+
+void pgx_launch_tracks_split(hipStream_t s, const pgx_pair *d_matches, const int32_t *d_counts, const int32_t *d_pairlist, int M,
+                             int F, int stride, const int32_t *d_frame_ids, int n_frames, int max_dist, const int *gates,
+                             int n_gates, int min_len, void *ws, int32_t *d_track_of, int32_t *d_offsets, int32_t *d_nodes,
+                             int32_t *d_summary, int *status)
+{
+    TrkArgs a = trk_args(d_matches, d_counts, d_pairlist, M, F, stride, d_frame_ids, n_frames, max_dist, min_len, ws, d_track_of,
+                         d_offsets, d_nodes, d_summary);
+    int32_t *x = reinterpret_cast<int32_t *>(static_cast<char *>(ws) + pgx_tracks_ws_bytes(n_frames, stride));
+    SplitArgs sp;
+    sp.active = x;
+    sp.live = x + a.N;
+    sp.owner = sp.live + 8;
+    sp.status = status;
+    const int chunks = (stride + TRK_NT - 1) / TRK_NT;
+    const unsigned gn = (unsigned)((size_t)F * chunks);
+    hipLaunchKernelGGL(k_trks_prep, dim3(trk_init_grid(a)), dim3(TRK_NT), 0, s, a, sp);
+    trk_launch_graph(s, a);
+    for (int l = 0; l <= n_gates; l++) {
+        if (l > 0) {
+            a.max_dist = gates[l - 1];
+            if (M > 0) {
+                const long long n_items = (long long)M * chunks;
+                const long long gu = n_items < TRKS_UNION_GRID ? n_items : TRKS_UNION_GRID;
+                hipLaunchKernelGGL(k_trks_union, dim3((unsigned)gu), dim3(TRK_NT), 0, s, a, sp, l, n_items);
+            }
+            hipLaunchKernelGGL(k_trks_flatten, dim3(gn), dim3(TRK_NT), 0, s, a, sp, l);
+        }
+        hipLaunchKernelGGL(k_trks_mark, dim3(gn), dim3(TRK_NT), 0, s, a, sp, l, l == n_gates ? 1 : 0);
+        if (l < n_gates) hipLaunchKernelGGL(k_trks_reset, dim3(trk_init_grid(a)), dim3(TRK_NT), 0, s, a, sp, l);
+    }
+    trk_launch_output(s, a);
 }

@@ -66,6 +66,8 @@ int decode_status(pgx_ctx *c, int bits)
     if (bits & PGX_ST_INTERNAL) return fail(c, PGX_E_HIP, "internal error: a device-side loop stopped without progress");
     if (bits & PGX_ST_BADARG)
         return fail(c, PGX_E_BADARG, "guided matching: a keypoint coordinate is outside [-2^20, 2^20) (its pairs' rows were rejected)");
+    if (bits & PGX_ST_DUP_FRAME)
+        return fail(c, PGX_E_BADARG, "track graph: two slots of d_frame_ids name the same frame (the split graph's result is undefined)");
     return PGX_OK;
 }
 
@@ -328,7 +330,7 @@ void pgx_ctx_destroy(pgx_ctx *c)
     for (hipEvent_t ev : c->ev_pool) (void)hipEventDestroy(ev);
     DevBuf *bufs[] = {&c->d_pairs, &c->d_map, &c->ws_gray, &c->ws_seg, &c->ws_segoff, &c->ws_nraw, &c->ws_rawxy,
                       &c->ws_rawscore, &c->ws_nms, &c->ws_order, &c->ws_nkept, &c->st_a, &c->st_b, &c->st_c,
-                      &c->st_d, &c->st_e, &c->st_f, &c->ws_pose, &c->ws_tracks, &c->ws_agree, &c->ws_matchn[0], &c->ws_matchn[1], &c->ws_matchn[2], &c->ws_matchn[3], &c->ws_knn, &c->ws_guided};
+                      &c->st_d, &c->st_e, &c->st_f, &c->ws_pose, &c->ws_tracks, &c->ws_tracks_split, &c->ws_agree, &c->ws_matchn[0], &c->ws_matchn[1], &c->ws_matchn[2], &c->ws_matchn[3], &c->ws_knn, &c->ws_guided};
     for (DevBuf *b : bufs) b->release();
     c->pin_in.release();
     c->pin_out.release();
@@ -1021,6 +1023,38 @@ int pgx_tracks_dev(pgx_ctx *c, const pgx_pair *d_matches, const int32_t *d_count
         ProfScope ps(c, "tracks");
         pgx_launch_tracks(c->stream, d_matches, d_counts, d_pairlist, M, F, stride, d_frame_ids, n_frames, max_dist, min_len,
                           c->ws_tracks.p, d_track_of, d_offsets, d_nodes, d_summary);
+    }
+    HIPCHK(c, hipGetLastError());
+    return PGX_OK;
+}
+
+int pgx_tracks_split_dev(pgx_ctx *c, const pgx_pair *d_matches, const int32_t *d_counts, const int32_t *d_pairlist, int M, int F,
+                         int stride, const int32_t *d_frame_ids, int n_frames, int max_dist, const int32_t *gates, int n_gates,
+                         int min_len, int32_t *d_track_of, int32_t *d_offsets, int32_t *d_nodes, int32_t *d_summary)
+{
+    if (!c || !d_counts || !d_track_of || !d_offsets || !d_nodes || !d_summary || M < 0 || (M > 0 && (!d_matches || !d_pairlist)) ||
+        (n_gates > 0 && !gates))
+        return c ? fail(c, PGX_E_BADARG, "null pointer") : PGX_E_BADARG;
+    Lock l(c);
+    if (F <= 0 || stride <= 0 || n_frames <= 0) return fail(c, PGX_E_BADARG, "F, stride and n_frames must be positive");
+    if (!d_frame_ids && n_frames != F) return fail(c, PGX_E_BADARG, "without d_frame_ids, n_frames must equal F");
+    if ((long long)n_frames * stride > (1ll << 30)) return fail(c, PGX_E_BADARG, "n_frames * stride must be <= 2^30");
+    if ((long long)M * ((stride + 255) / 256) > 0x7FFFFFFFll || (long long)F * ((stride + 255) / 256) > 0x7FFFFFFFll)
+        return fail(c, PGX_E_BADARG, "too many image pairs for one call");
+    if (n_gates < 0 || n_gates > 7) return fail(c, PGX_E_BADARG, "n_gates = %d, must be in [0, 7]", n_gates);
+    int g[7];
+    for (int i = 0; i < n_gates; i++) {
+        g[i] = gates[i];
+        const int above = i == 0 ? max_dist : g[i - 1];
+        if (g[i] < 0 || g[i] >= above)
+            return fail(c, PGX_E_BADARG, "gates[%d] = %d: the gates must be >= 0, below max_dist (%d) and strictly decreasing", i, g[i],
+                        max_dist);
+    }
+    HIPCHK(c, c->ws_tracks_split.ensure(pgx_tracks_split_ws_bytes(n_frames, stride)));
+    {
+        ProfScope ps(c, "tracks_split");
+        pgx_launch_tracks_split(c->stream, d_matches, d_counts, d_pairlist, M, F, stride, d_frame_ids, n_frames, max_dist, g, n_gates,
+                                min_len, c->ws_tracks_split.p, d_track_of, d_offsets, d_nodes, d_summary, c->d_status);
     }
     HIPCHK(c, hipGetLastError());
     return PGX_OK;

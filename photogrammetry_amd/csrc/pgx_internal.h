@@ -20,6 +20,7 @@
 #define PGX_ST_EMPTY_SET  8u
 #define PGX_ST_INTERNAL   16u  /* a device loop made no progress (a bug, never an input property) */
 #define PGX_ST_BADARG     32u  /* guided matching: a used keypoint coordinate outside [-2^20, 2^20) */
+#define PGX_ST_DUP_FRAME  64u  /* pgx_tracks_split_dev: two slots of d_frame_ids name the same frame */
 
 // key = (distance << PGX_IDX_BITS) | index ; limits: index < 2^20, distance < 2^12
 #define PGX_IDX_BITS 20
@@ -114,6 +115,7 @@ struct pgx_ctx {
     // match workspaces: four, so that with several chunks of image pairs the stages of consecutive chunks run side by side
     DevBuf ws_matchn[4];
     DevBuf ws_pose, ws_tracks;
+    DevBuf ws_tracks_split; // pgx_tracks_split_dev: ws_tracks' layout plus the active mask, live counters and frame owners
     DevBuf ws_knn; // pgx_match_nn_batch_dev: top-2 and column nearest of a chunk of image pairs
     DevBuf ws_guided; // guided matching: the keypoint grids of the frames of a chunk of image pairs
     hipStream_t mstream[4] = {nullptr, nullptr, nullptr, nullptr}; // [0] wide rounds, [1] residual distance rows, [2], [3] per-pair finishes (alternating)
@@ -257,6 +259,13 @@ size_t pgx_tracks_ws_bytes(int n_frames, int stride);
 void pgx_launch_tracks(hipStream_t s, const pgx_pair *d_matches, const int32_t *d_counts, const int32_t *d_pairlist, int M, int F,
                        int stride, const int32_t *d_frame_ids, int n_frames, int max_dist, int min_len, void *ws,
                        int32_t *d_track_of, int32_t *d_offsets, int32_t *d_nodes, int32_t *d_summary);
+// the refinement levels of pgx_tracks_split_dev (include/pgx.h); gates: host array [n_gates], checked by the caller;
+// d_summary [16]; duplicate frame ids set PGX_ST_DUP_FRAME in *status
+size_t pgx_tracks_split_ws_bytes(int n_frames, int stride);
+void pgx_launch_tracks_split(hipStream_t s, const pgx_pair *d_matches, const int32_t *d_counts, const int32_t *d_pairlist, int M,
+                             int F, int stride, const int32_t *d_frame_ids, int n_frames, int max_dist, const int *gates,
+                             int n_gates, int min_len, void *ws, int32_t *d_track_of, int32_t *d_offsets, int32_t *d_nodes,
+                             int32_t *d_summary, int *status);
 
 // k_match.hip
 struct MatchPlan {

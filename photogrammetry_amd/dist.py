@@ -72,14 +72,14 @@ def exchange_matches(out_local, n_pairs):
     return all_gather_slots(out_local, n_pairs)
 
 
-def tracks_host(counts_all, pair_list, matches_all, max_dist=64, min_len=2):
+def tracks_host(counts_all, pair_list, matches_all, max_dist=64, min_len=2, gates=None):
     """The track graph of gathered lists through the C ABI's HOST form (pgx_tracks_*: sequential, small inputs; what a host
     without device-resident lists calls) -> (tracks, dropped components, nodes in them).  The device form is
-    ShardedSequence(tracks=...) / Engine.tracks_dev."""
+    ShardedSequence(tracks=...) / Engine.tracks_dev.  gates: the split mode (api.tracks_host), which adds the per-level counts."""
     from . import api
     m = matches_all.cpu().numpy() if isinstance(matches_all, torch.Tensor) else np.asarray(matches_all)
     c = counts_all.cpu().numpy() if isinstance(counts_all, torch.Tensor) else np.asarray(counts_all)
-    return api.tracks_host(c, pair_list, [m[p] for p in range(len(pair_list))], max_dist, min_len)
+    return api.tracks_host(c, pair_list, [m[p] for p in range(len(pair_list))], max_dist, min_len, gates=gates)
 
 
 # ---- the four phases on this rank's GPU ------------------------------------------------------------
@@ -126,7 +126,9 @@ class ShardedSequence:
         global frame numbers this rank's graph covers, numbered 0.. in that order (default: all frames, i.e. every rank
         builds the whole graph; a caller whose job is several independent sequences gives each rank its own sequences'
         frames: image pairs touching other frames are skipped).  Results: track_of / trk_offsets / trk_nodes / trk_summary
-        (device), tracks() / track_summary() (host)."""
+        (device), tracks() / track_summary() (host).
+        tracks = dict(..., gates=[g_1, g_2, ...]): the split mode (pgx_tracks_split_dev) -- components inconsistent at max_dist
+        are split at the tighter gates instead of dropped; track_summary() then also holds `per_level`."""
         assert comm in ("torch", "pgx")
         self.comm = comm
         self.overlap = bool(overlap_exchange) and comm == "torch"
@@ -166,7 +168,8 @@ class ShardedSequence:
             engine.set_stream(self.stream.cuda_stream)
         self.trk = None
         if tracks is not None:
-            self.trk = {"max_dist": int(tracks.get("max_dist", 64)), "min_len": int(tracks.get("min_len", 2))}
+            self.trk = {"max_dist": int(tracks.get("max_dist", 64)), "min_len": int(tracks.get("min_len", 2)),
+                        "gates": None if tracks.get("gates") is None else [int(g) for g in tracks["gates"]]}
             frames = list(tracks["frames"]) if tracks.get("frames") is not None else list(range(n_frames))
             ids = np.full(G * self.fs, -1, dtype=np.int32)
             for i, f in enumerate(frames):
@@ -182,13 +185,19 @@ class ShardedSequence:
             self.track_of = torch.zeros((nfg, nkp), **i32)
             self.trk_offsets = torch.zeros(nfg * nkp + 1, **i32)
             self.trk_nodes = torch.zeros((nfg * nkp, 2), **i32)
-            self.trk_summary = torch.zeros(8, **i32)
+            self.trk_summary = torch.zeros(8 if self.trk["gates"] is None else 16, **i32)
             # the counts a step's lists were made with, kept per output buffer: with the overlapped exchange the next step's
             # detect has overwritten counts_all by the time the lists are complete
             self.trk_counts = [torch.zeros(G * self.fs, **i32) for _ in self.out_bufs]
 
     def _build_tracks(self, buf):
         """Enqueue the track graph over the complete lists in out_bufs[buf] (on the job's stream)."""
+        if self.trk["gates"] is not None:
+            self.e.tracks_split_dev(self.out_bufs[buf], self.trk_counts[buf], self.trk_pairlist, self.world * self.ps,
+                                    self.world * self.fs, self.nkp, max(1, len(self.trk_frames)), self.trk["max_dist"],
+                                    self.trk["gates"], self.trk["min_len"], self.track_of, self.trk_offsets, self.trk_nodes,
+                                    self.trk_summary, d_frame_ids=self.trk_frame_ids)
+            return
         self.e.tracks_dev(self.out_bufs[buf], self.trk_counts[buf], self.trk_pairlist, self.world * self.ps, self.world * self.fs,
                           self.nkp, max(1, len(self.trk_frames)), self.trk["max_dist"], self.trk["min_len"], self.track_of,
                           self.trk_offsets, self.trk_nodes, self.trk_summary, d_frame_ids=self.trk_frame_ids)
@@ -318,10 +327,14 @@ class ShardedSequence:
         return self.out_all[slot_of(pair_index, self.world, self.ps)]
 
     def track_summary(self):
-        """pgx_tracks_dev's d_summary as a dict (synchronises)."""
+        """pgx_tracks_dev's d_summary as a dict (synchronises); in the split mode also `per_level` (nodes in tracks per level,
+        level 0 = max_dist, then one per gate)."""
         v = self.trk_summary.cpu().tolist()
-        return {"n_tracks": v[0], "n_nodes": v[1], "dropped": v[2], "dropped_nodes": v[3], "edges": v[4], "longest": v[5],
-                "largest_dropped": v[6]}
+        out = {"n_tracks": v[0], "n_nodes": v[1], "dropped": v[2], "dropped_nodes": v[3], "edges": v[4], "longest": v[5],
+               "largest_dropped": v[6]}
+        if self.trk["gates"] is not None:
+            out["per_level"] = v[8:9 + len(self.trk["gates"])]
+        return out
 
     def tracks(self):
         """The most recent graph as a list of tracks, each a list of (frame, keypoint) in pgx_tracks_get's order; frames are
