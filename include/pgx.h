@@ -394,6 +394,66 @@ int  pgx_tracks_finish_split(pgx_tracks *t, const int32_t *gates, int n_gates, i
  * on the device). */
 int  pgx_tracks_dropped(pgx_tracks *t, int *n_components, int *n_nodes);
 
+/* ---- multi-view triangulation of tracks ------------------------------------------------ */
+/* The reference's end product is a point cloud: CameraPoseEstimation.EstimateCameraPose (CameraPoseEstimation.cs:96-202)
+ * triangulates every keypoint pair of ONE image pair and hands the points to Utils.CreatePointCloud.  This is the same step
+ * for the tracks of the graph above, over any number of views, with the caller's cameras.
+ * Inputs:
+ *   d_offsets, d_nodes, d_track_summary   the outputs of pgx_tracks_dev / pgx_tracks_split_dev, unchanged.  Only
+ *           d_track_summary[0] = n_tracks is read, and on the device, so the call can follow the graph on the same stream.
+ *   d_kp [F][stride]     the keypoints in the pgx_detect_batch_dev layout.
+ *   d_frame_ids [F]      the array the graph call took (NULL = identity, n_frames = F): nodes name frame NUMBERS, keypoints
+ *           sit in SLOTS.  Two slots naming one frame: PGX_E_BADARG through pgx_check_status.
+ *   d_P [n_frames][12]   float64, row-major 3x4, by frame number: world point -> pixels in the keypoint convention, column
+ *           u = pgx_keypoint.x, row v = pgx_keypoint.y (exact doubles).  Write M = P[:, 0:3], p4 = P[:, 3], m3 = M's 3rd row.
+ *           A camera is UNKNOWN if an entry is not finite or det(M) == 0; observations in its frame are skipped (pass NaN rows
+ *           for the frames that have no pose yet).
+ * Per track, over its used observations i = (u_i, v_i, P_i) in d_nodes order, with C_i = -M_i^-1 p4_i (the adjugate over
+ * det) and S = the mean of the used C_i:
+ *   1 linear  in the frame shifted to S, P'_i = [M_i | p4_i + M_i S].  Rows u_i P'_i[2] - P'_i[0] and v_i P'_i[2] - P'_i[1],
+ *             each divided by its Euclidean norm; v = the unit null vector of the 2n x 4 system (smallest eigenvector of its
+ *             Gram matrix).  |v[3]| <= 1e-12 or a non-finite v: DEGENERATE.  Else X' = v[0:3] / v[3].
+ *   2 refine  refine_iters in [0, 32] Gauss-Newton steps on cost(X') = sum_i e_i^2, each from the 3x3 normal equations
+ *             J^T J d = -J^T r.  Before a step: stop if ||d|| <= 1e-12 (1 + ||S + X'||).  A step is kept only if the cost
+ *             strictly decreases; otherwise X' stays and refinement stops.  X = S + X'.
+ *   3 quality e_i = the pixel distance between (u_i, v_i) and the projection of X; depth_i = sign(det M_i) (P_i[2].(X, 1)) /
+ *             ||m3_i||; parallax = the largest angle in degrees between C_i - X and C_j - X over pairs of used observations.
+ *   4 flags   (PGX_TRI_*, bits; 0 = a valid point)
+ *             FEWVIEWS    fewer than 2 used observations: no point, xyz, quality and the track's node errors are NaN
+ *             DEGENERATE  step 1 found the point at infinity: xyz, quality and node errors NaN
+ *             BEHIND      some depth_i <= 0
+ *             PARALLAX    parallax < min_parallax_deg
+ *             REPROJ      not (max e_i <= max_reproj_px)  (+inf disables it)
+ * Outputs, for t < min(n_tracks, max_tracks):
+ *   d_xyz [max_tracks][3], d_quality [max_tracks][3] = (rms e, max e, parallax) float64, d_flags [max_tracks] int32;
+ *   d_node_err [n_frames * stride] float64 or NULL: e_i in d_nodes order, NaN for a skipped observation;
+ *   d_summary [8] int32: tracks processed, tracks with flags 0, tracks carrying each of the five bits (FEWVIEWS first),
+ *           observations used.
+ * Errors through pgx_check_status: n_tracks > max_tracks (PGX_E_CAPACITY; the first max_tracks are written); a node whose
+ * frame is outside [0, n_frames), whose keypoint is outside [0, stride) or whose frame no slot names (PGX_E_BADARG; the node is
+ * skipped).  Returned at once (PGX_E_BADARG): refine_iters outside [0, 32], min_parallax_deg < 0 or NaN, max_reproj_px <= 0
+ * or NaN, null required pointers, F, stride or n_frames not positive, n_frames * stride > 2^30, max_tracks < 0.
+ * Results depend on the inputs only: the same bits for any max_tracks >= n_tracks, any slot layout of the same frames, from
+ * run to run, and from the host form below.  Asynchronous on the context's stream. */
+#define PGX_TRI_FEWVIEWS   1
+#define PGX_TRI_DEGENERATE 2
+#define PGX_TRI_BEHIND     4
+#define PGX_TRI_PARALLAX   8
+#define PGX_TRI_REPROJ     16
+int pgx_triangulate_tracks_dev(pgx_ctx *ctx, const pgx_keypoint *d_kp, int F, int stride, const int32_t *d_frame_ids, int n_frames,
+                               const double *d_P, const int32_t *d_offsets, const int32_t *d_nodes, const int32_t *d_track_summary,
+                               int max_tracks, double min_parallax_deg, double max_reproj_px, int refine_iters, double *d_xyz,
+                               double *d_quality, int32_t *d_flags, double *d_node_err, int32_t *d_summary);
+/* Host form (what a host calls after pgx_tracks_get): the same kernels on host arrays, returns when the results are in the
+ * caller's buffers.  kps = every frame's keypoints one after another (frame f's counts[f] entries start at counts[0] + ... +
+ * counts[f-1]); P [n_frames][12]; track_offsets [n_tracks + 1], nodes [track_offsets[n_tracks]][2] as pgx_tracks_get writes
+ * them.  A node outside [0, n_frames) x [0, counts[frame]) or offsets that are not non-decreasing from 0: PGX_E_BADARG before
+ * any GPU work.  xyz [n_tracks][3], quality [n_tracks][3], flags [n_tracks], node_err [n_nodes] (or NULL), summary [8]. */
+int pgx_triangulate_tracks(pgx_ctx *ctx, const pgx_keypoint *kps, const int32_t *counts, int n_frames, const double *P,
+                           const int32_t *track_offsets, const int32_t *nodes, int n_tracks, double min_parallax_deg,
+                           double max_reproj_px, int refine_iters, double *xyz, double *quality, int32_t *flags, double *node_err,
+                           int32_t *summary);
+
 /* ---- measurement hooks (bench.py) ---------------------------------------------------- */
 /* When on, the named hot kernels are bracketed by HIP events on the launch stream. */
 int pgx_profile_enable(pgx_ctx *ctx, int on);

@@ -22,6 +22,7 @@ internal static unsafe class PgxNative
     public const int SrcRgba64 = 0, SrcRgba8 = 1;                                         // PGX_SRC_*
     public const int StageDetect = 0, StageMatchWide = 1, StageMatchRows = 2, StageMatchDone = 3;   // PGX_STAGE_*
     public const int CommIdBytes = 128;                                                   // PGX_COMM_ID_BYTES
+    public const int TriFewViews = 1, TriDegenerate = 2, TriBehind = 4, TriParallax = 8, TriReproj = 16;   // PGX_TRI_* (0 = valid)
 
     // Exports of include/pgx.h that this binding deliberately leaves out (tests/test_csharp_binding.py holds the list to the
     // header): the caller's-HIP-stream hook and the measurement hooks (a managed host owns no hipStream_t and reads no HIP event
@@ -111,6 +112,18 @@ internal static unsafe class PgxNative
                                                                    void* dSummary);
     [DllImport(Lib)] public static extern int pgx_tracks_finish_split(IntPtr tracks, int* gates, int nGates, int minLen, out int nTracks,
                                                                       out int nNodes, int* summary);
+    // one 3D point per track from the caller's cameras (p [nFrames][12] float64, row-major 3x4, NaN rows = no pose yet): the device
+    // form follows the graph on the same stream and reads nTracks from dTrackSummary[0]; the host form takes what pgx_tracks_get
+    // wrote and every frame's keypoints one after another (kps), and returns when xyz, quality, flags, nodeErr and summary are filled
+    [DllImport(Lib)] public static extern int pgx_triangulate_tracks_dev(IntPtr ctx, void* dKp, int f, int stride, void* dFrameIds, int nFrames,
+                                                                         void* dP, void* dOffsets, void* dNodes, void* dTrackSummary,
+                                                                         int maxTracks, double minParallaxDeg, double maxReprojPx,
+                                                                         int refineIters, void* dXyz, void* dQuality, void* dFlags,
+                                                                         void* dNodeErr, void* dSummary);
+    [DllImport(Lib)] public static extern int pgx_triangulate_tracks(IntPtr ctx, PgxKeypoint* kps, int* counts, int nFrames, double* p,
+                                                                     int* trackOffsets, int* nodes, int nTracks, double minParallaxDeg,
+                                                                     double maxReprojPx, int refineIters, double* xyz, double* quality,
+                                                                     int* flags, double* nodeErr, int* summary);
 
     /// <summary>Maps a status code back to the exception type the managed implementation throws.</summary>
     public static void Check(IntPtr ctx, int rc)

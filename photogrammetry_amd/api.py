@@ -340,6 +340,45 @@ class Engine:
                                                int(n_frames), int(max_dist), _ptr(g) if len(g) else None, len(g), int(min_len),
                                                _dptr(d_track_of), _dptr(d_offsets), _dptr(d_nodes), _dptr(d_summary)))
 
+    # -- multi-view triangulation of tracks (pgx_triangulate_tracks*) -----------------------------------
+    def triangulate_tracks_dev(self, d_kp, F, stride, n_frames, d_P, d_offsets, d_nodes, d_track_summary, max_tracks, d_xyz,
+                               d_quality, d_flags, d_summary, min_parallax_deg=1.0, max_reproj_px=float("inf"), refine_iters=10,
+                               d_node_err=None, d_frame_ids=None):
+        """One point per track of the graph's output, where it sits in HBM (pgx.h: multi-view triangulation).  d_P [n_frames][12]
+        float64 by frame number; d_xyz / d_quality [max_tracks][3] float64, d_flags [max_tracks] int32, d_summary [8] int32,
+        d_node_err [n_frames * stride] float64 or None.  n_tracks is read on the device: no sync."""
+        self._chk(self._L.pgx_triangulate_tracks_dev(
+            self._h, _dptr(d_kp), int(F), int(stride), _dptr(d_frame_ids) if d_frame_ids is not None else None, int(n_frames),
+            _dptr(d_P), _dptr(d_offsets), _dptr(d_nodes), _dptr(d_track_summary), int(max_tracks), C.c_double(min_parallax_deg),
+            C.c_double(max_reproj_px), int(refine_iters), _dptr(d_xyz), _dptr(d_quality), _dptr(d_flags),
+            _dptr(d_node_err) if d_node_err is not None else None, _dptr(d_summary)))
+
+    def triangulate_tracks(self, kps_per_frame, cameras, track_offsets, nodes=None, min_parallax_deg=1.0,
+                           max_reproj_px=float("inf"), refine_iters=10):
+        """The host form (pgx_triangulate_tracks).  kps_per_frame: one KEYPOINT_DTYPE array per frame; cameras [n_frames][3][4]
+        (or [n_frames][12]) float64, NaN rows for frames without a pose.  Tracks as pgx_tracks_get gives them (track_offsets
+        [n_tracks + 1], nodes [n_nodes][2]) or, with nodes=None, the `tracks` list of tracks_host.
+        -> dict(xyz [n][3], quality [n][3] = (rms, max, parallax), flags [n], node_err [n_nodes], summary [8])."""
+        if nodes is None:
+            tracks = track_offsets
+            track_offsets = np.cumsum([0] + [len(t) for t in tracks])
+            nodes = [fk for t in tracks for fk in t]
+        off = np.ascontiguousarray(track_offsets, dtype=np.int32).reshape(-1)
+        nd = np.ascontiguousarray(nodes, dtype=np.int32).reshape(-1, 2)
+        kp = [np.ascontiguousarray(k, dtype=KEYPOINT_DTYPE) for k in kps_per_frame]
+        counts = np.array([len(k) for k in kp], dtype=np.int32)
+        flat = np.ascontiguousarray(np.concatenate(kp) if len(kp) else np.zeros(0, KEYPOINT_DTYPE))
+        P = np.ascontiguousarray(cameras, dtype=np.float64).reshape(len(kp), 12)
+        n = len(off) - 1
+        xyz, q = np.zeros((max(n, 1), 3)), np.zeros((max(n, 1), 3))
+        flags, err = np.zeros(max(n, 1), dtype=np.int32), np.zeros(max(len(nd), 1))
+        summary = np.zeros(8, dtype=np.int32)
+        self._chk(self._L.pgx_triangulate_tracks(
+            self._h, _ptr(flat) if len(flat) else None, _ptr(counts), len(kp), _ptr(P), _ptr(off), _ptr(nd) if len(nd) else None, n,
+            C.c_double(min_parallax_deg), C.c_double(max_reproj_px), int(refine_iters), _ptr(xyz), _ptr(q), _ptr(flags), _ptr(err),
+            _ptr(summary)))
+        return dict(xyz=xyz[:n], quality=q[:n], flags=flags[:n], node_err=err[:len(nd)], summary=summary)
+
     # -- multi-GPU: the context's own RCCL communicator (pgx_comm_*) ------------------------------
     def comm_init(self, rank, world, unique_id):
         """Collective: every rank calls this with the 128 bytes rank 0 got from comm_unique_id()."""

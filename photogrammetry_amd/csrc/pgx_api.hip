@@ -68,6 +68,12 @@ int decode_status(pgx_ctx *c, int bits)
         return fail(c, PGX_E_BADARG, "guided matching: a keypoint coordinate is outside [-2^20, 2^20) (its pairs' rows were rejected)");
     if (bits & PGX_ST_DUP_FRAME)
         return fail(c, PGX_E_BADARG, "track graph: two slots of d_frame_ids name the same frame (the split graph's result is undefined)");
+    if (bits & PGX_ST_TRI_CAP) return fail(c, PGX_E_CAPACITY, "triangulation: n_tracks exceeds max_tracks (only the first max_tracks were written)");
+    if (bits & PGX_ST_TRI_NODE)
+        return fail(c, PGX_E_BADARG, "triangulation: a node names a frame outside [0, n_frames), a keypoint outside [0, stride) or a frame no slot "
+                                     "holds, or the offsets are malformed (those nodes were skipped)");
+    if (bits & PGX_ST_TRI_DUP)
+        return fail(c, PGX_E_BADARG, "triangulation: two slots of d_frame_ids name the same frame");
     return PGX_OK;
 }
 
@@ -330,7 +336,7 @@ void pgx_ctx_destroy(pgx_ctx *c)
     for (hipEvent_t ev : c->ev_pool) (void)hipEventDestroy(ev);
     DevBuf *bufs[] = {&c->d_pairs, &c->d_map, &c->ws_gray, &c->ws_seg, &c->ws_segoff, &c->ws_nraw, &c->ws_rawxy,
                       &c->ws_rawscore, &c->ws_nms, &c->ws_order, &c->ws_nkept, &c->st_a, &c->st_b, &c->st_c,
-                      &c->st_d, &c->st_e, &c->st_f, &c->ws_pose, &c->ws_tracks, &c->ws_tracks_split, &c->ws_agree, &c->ws_matchn[0], &c->ws_matchn[1], &c->ws_matchn[2], &c->ws_matchn[3], &c->ws_knn, &c->ws_guided};
+                      &c->st_d, &c->st_e, &c->st_f, &c->ws_pose, &c->ws_tracks, &c->ws_tracks_split, &c->ws_agree, &c->ws_matchn[0], &c->ws_matchn[1], &c->ws_matchn[2], &c->ws_matchn[3], &c->ws_knn, &c->ws_guided, &c->ws_tri};
     for (DevBuf *b : bufs) b->release();
     c->pin_in.release();
     c->pin_out.release();
@@ -1058,6 +1064,122 @@ int pgx_tracks_split_dev(pgx_ctx *c, const pgx_pair *d_matches, const int32_t *d
     }
     HIPCHK(c, hipGetLastError());
     return PGX_OK;
+}
+
+// ---- multi-view triangulation of tracks --------------------------------------------------------------------------
+
+namespace {
+int tri_args(pgx_ctx *c, double min_parallax_deg, double max_reproj_px, int refine_iters)
+{
+    if (refine_iters < 0 || refine_iters > 32) return fail(c, PGX_E_BADARG, "refine_iters = %d, must be in [0, 32]", refine_iters);
+    if (!(min_parallax_deg >= 0.0)) return fail(c, PGX_E_BADARG, "min_parallax_deg must be >= 0 (and not NaN)");
+    if (!(max_reproj_px > 0.0)) return fail(c, PGX_E_BADARG, "max_reproj_px must be > 0 (and not NaN; +inf disables the test)");
+    return PGX_OK;
+}
+} // namespace
+
+int pgx_triangulate_tracks_dev(pgx_ctx *c, const pgx_keypoint *d_kp, int F, int stride, const int32_t *d_frame_ids, int n_frames,
+                               const double *d_P, const int32_t *d_offsets, const int32_t *d_nodes, const int32_t *d_track_summary,
+                               int max_tracks, double min_parallax_deg, double max_reproj_px, int refine_iters, double *d_xyz,
+                               double *d_quality, int32_t *d_flags, double *d_node_err, int32_t *d_summary)
+{
+    if (!c || !d_kp || !d_P || !d_offsets || !d_nodes || !d_track_summary || !d_xyz || !d_quality || !d_flags || !d_summary)
+        return c ? fail(c, PGX_E_BADARG, "null pointer") : PGX_E_BADARG;
+    Lock l(c);
+    if (F <= 0 || stride <= 0 || n_frames <= 0) return fail(c, PGX_E_BADARG, "F, stride and n_frames must be positive");
+    if (!d_frame_ids && n_frames != F) return fail(c, PGX_E_BADARG, "without d_frame_ids, n_frames must equal F");
+    if ((long long)n_frames * stride > (1ll << 30)) return fail(c, PGX_E_BADARG, "n_frames * stride must be <= 2^30");
+    if (max_tracks < 0) return fail(c, PGX_E_BADARG, "max_tracks must be >= 0");
+    const int rc = tri_args(c, min_parallax_deg, max_reproj_px, refine_iters);
+    if (rc != PGX_OK) return rc;
+    HIPCHK(c, c->ws_tri.ensure(pgx_triangulate_ws_bytes(n_frames)));
+    {
+        ProfScope ps(c, "triangulate");
+        pgx_launch_triangulate(c->stream, d_kp, F, stride, d_frame_ids, n_frames, d_P, d_offsets, d_nodes, (long long)n_frames * stride,
+                               d_track_summary, max_tracks, min_parallax_deg, max_reproj_px, refine_iters, d_xyz, d_quality, d_flags,
+                               d_node_err, d_summary, c->ws_tri.p, c->d_status);
+    }
+    HIPCHK(c, hipGetLastError());
+    return PGX_OK;
+}
+
+int pgx_triangulate_tracks(pgx_ctx *c, const pgx_keypoint *kps, const int32_t *counts, int n_frames, const double *P,
+                           const int32_t *track_offsets, const int32_t *nodes, int n_tracks, double min_parallax_deg,
+                           double max_reproj_px, int refine_iters, double *xyz, double *quality, int32_t *flags, double *node_err,
+                           int32_t *summary)
+{
+    if (!c || !counts || !P || !track_offsets || !summary || n_frames <= 0 || n_tracks < 0 ||
+        (n_tracks > 0 && (!xyz || !quality || !flags)))
+        return c ? fail(c, PGX_E_BADARG, "null pointer or bad size") : PGX_E_BADARG;
+    Lock l(c);
+    const int rc = tri_args(c, min_parallax_deg, max_reproj_px, refine_iters);
+    if (rc != PGX_OK) return rc;
+    // the host's checks: counts, offsets, nodes (the device then sees no bad node)
+    long long n_kp = 0;
+    int stride = 1;
+    for (int f = 0; f < n_frames; f++) {
+        if (counts[f] < 0) return fail(c, PGX_E_BADARG, "counts[%d] = %d is negative", f, counts[f]);
+        n_kp += counts[f];
+        stride = counts[f] > stride ? counts[f] : stride;
+    }
+    if (n_kp > 0 && !kps) return fail(c, PGX_E_BADARG, "null pointer (kps)");
+    if ((long long)n_frames * stride > (1ll << 30)) return fail(c, PGX_E_BADARG, "n_frames * max(counts) must be <= 2^30");
+    if (track_offsets[0] != 0) return fail(c, PGX_E_BADARG, "track_offsets[0] must be 0");
+    for (int t = 0; t < n_tracks; t++)
+        if (track_offsets[t + 1] < track_offsets[t]) return fail(c, PGX_E_BADARG, "track_offsets decrease at track %d", t);
+    const long long n_nodes = track_offsets[n_tracks];
+    if (n_nodes > 0 && !nodes) return fail(c, PGX_E_BADARG, "null pointer (nodes)");
+    for (long long o = 0; o < n_nodes; o++) {
+        const int f = nodes[2 * o], k = nodes[2 * o + 1];
+        if (f < 0 || f >= n_frames || k < 0 || k >= counts[f])
+            return fail(c, PGX_E_BADARG, "node %lld = (%d, %d) is outside [0, n_frames) x [0, counts[frame])", o, f, k);
+    }
+    for (int i = 0; i < 8; i++) summary[i] = 0;
+    if (n_tracks == 0) return PGX_OK;
+    // staging (pinned, one upload): keypoints [n_frames][stride], P, offsets, nodes, the track summary's n_tracks
+    const size_t b_kp = ((size_t)n_frames * stride * sizeof(pgx_keypoint) + 255) & ~(size_t)255;
+    const size_t b_P = ((size_t)n_frames * 12 * sizeof(double) + 255) & ~(size_t)255;
+    const size_t b_off = ((size_t)(n_tracks + 1) * 4 + 255) & ~(size_t)255;
+    const size_t b_nodes = ((size_t)(n_nodes > 0 ? n_nodes : 1) * 8 + 255) & ~(size_t)255;
+    const size_t b_in = b_kp + b_P + b_off + b_nodes + 256;
+    HIPCHK(c, c->pin_in.ensure(b_in));
+    HIPCHK(c, c->st_a.ensure(b_in));
+    char *h = c->pin_in.as<char>();
+    for (int f = 0, at = 0; f < n_frames; at += counts[f], f++)
+        if (counts[f] > 0) std::memcpy(h + (size_t)f * stride * sizeof(pgx_keypoint), kps + at, (size_t)counts[f] * sizeof(pgx_keypoint));
+    std::memcpy(h + b_kp, P, (size_t)n_frames * 12 * sizeof(double));
+    std::memcpy(h + b_kp + b_P, track_offsets, (size_t)(n_tracks + 1) * 4);
+    if (n_nodes > 0) std::memcpy(h + b_kp + b_P + b_off, nodes, (size_t)n_nodes * 8);
+    const int32_t ts[8] = {n_tracks, (int32_t)n_nodes};
+    std::memcpy(h + b_kp + b_P + b_off + b_nodes, ts, sizeof ts);
+    HIPCHK(c, hipMemcpyAsync(c->st_a.p, h, b_in, hipMemcpyHostToDevice, c->stream));
+    char *d = c->st_a.as<char>();
+    // outputs: xyz, quality, node_err, flags, summary
+    const size_t b_xyz = ((size_t)n_tracks * 24 + 255) & ~(size_t)255;
+    const size_t b_err = ((size_t)(n_nodes > 0 ? n_nodes : 1) * 8 + 255) & ~(size_t)255;
+    const size_t b_fl = ((size_t)n_tracks * 4 + 255) & ~(size_t)255;
+    HIPCHK(c, c->st_b.ensure(2 * b_xyz + b_err + b_fl + 256));
+    char *o = c->st_b.as<char>();
+    double *d_xyz = reinterpret_cast<double *>(o), *d_q = reinterpret_cast<double *>(o + b_xyz);
+    double *d_err = reinterpret_cast<double *>(o + 2 * b_xyz);
+    int32_t *d_fl = reinterpret_cast<int32_t *>(o + 2 * b_xyz + b_err), *d_sum = reinterpret_cast<int32_t *>(o + 2 * b_xyz + b_err + b_fl);
+    HIPCHK(c, c->ws_tri.ensure(pgx_triangulate_ws_bytes(n_frames)));
+    {
+        ProfScope ps(c, "triangulate");
+        pgx_launch_triangulate(c->stream, reinterpret_cast<const pgx_keypoint *>(d), n_frames, stride, nullptr, n_frames,
+                               reinterpret_cast<const double *>(d + b_kp), reinterpret_cast<const int32_t *>(d + b_kp + b_P),
+                               reinterpret_cast<const int32_t *>(d + b_kp + b_P + b_off), n_nodes,
+                               reinterpret_cast<const int32_t *>(d + b_kp + b_P + b_off + b_nodes), n_tracks, min_parallax_deg,
+                               max_reproj_px, refine_iters, d_xyz, d_q, d_fl, node_err ? d_err : nullptr, d_sum, c->ws_tri.p,
+                               c->d_status);
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(xyz, d_xyz, (size_t)n_tracks * 24, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(quality, d_q, (size_t)n_tracks * 24, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(flags, d_fl, (size_t)n_tracks * 4, hipMemcpyDeviceToHost, c->stream));
+    if (node_err && n_nodes > 0) HIPCHK(c, hipMemcpyAsync(node_err, d_err, (size_t)n_nodes * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(summary, d_sum, 8 * 4, hipMemcpyDeviceToHost, c->stream));
+    return sync_status(c);
 }
 
 // ---- measurement hooks ---------------------------------------------------------------------

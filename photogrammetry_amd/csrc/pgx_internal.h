@@ -21,6 +21,9 @@
 #define PGX_ST_INTERNAL   16u  /* a device loop made no progress (a bug, never an input property) */
 #define PGX_ST_BADARG     32u  /* guided matching: a used keypoint coordinate outside [-2^20, 2^20) */
 #define PGX_ST_DUP_FRAME  64u  /* pgx_tracks_split_dev: two slots of d_frame_ids name the same frame */
+#define PGX_ST_TRI_CAP    128u /* pgx_triangulate_tracks_dev: n_tracks > max_tracks */
+#define PGX_ST_TRI_NODE   256u /* pgx_triangulate_tracks_dev: a node outside the frames / keypoint slots, or malformed offsets */
+#define PGX_ST_TRI_DUP    512u /* pgx_triangulate_tracks_dev: two slots of d_frame_ids name the same frame */
 
 // key = (distance << PGX_IDX_BITS) | index ; limits: index < 2^20, distance < 2^12
 #define PGX_IDX_BITS 20
@@ -118,6 +121,7 @@ struct pgx_ctx {
     DevBuf ws_tracks_split; // pgx_tracks_split_dev: ws_tracks' layout plus the active mask, live counters and frame owners
     DevBuf ws_knn; // pgx_match_nn_batch_dev: top-2 and column nearest of a chunk of image pairs
     DevBuf ws_guided; // guided matching: the keypoint grids of the frames of a chunk of image pairs
+    DevBuf ws_tri;    // pgx_triangulate_tracks*: camera table, frame -> slot map, per-workgroup counters
     hipStream_t mstream[4] = {nullptr, nullptr, nullptr, nullptr}; // [0] wide rounds, [1] residual distance rows, [2], [3] per-pair finishes (alternating)
     hipEvent_t ev_in = nullptr, ev_wide[4] = {nullptr, nullptr, nullptr, nullptr}, ev_rows[4] = {nullptr, nullptr, nullptr, nullptr},
                ev_fin[4] = {nullptr, nullptr, nullptr, nullptr}, ev_join[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -303,3 +307,12 @@ size_t pgx_guided_ws_bytes(int M, int max_n);
 void pgx_launch_guided(pgx_ctx *ctx, hipStream_t s, const uint32_t *d_desc, const pgx_keypoint *d_kp, const int32_t *d_counts,
                        const int32_t *d_pairlist, int M, int S, int words, int max_n, const float *d_F, float band, int k,
                        int32_t *d_idx, int32_t *d_dist, int32_t *d_col, void *ws, int *status);
+
+// k_triangulate.hip (multi-view triangulation of tracks; pgx_triangulate_tracks_dev semantics, include/pgx.h)
+size_t pgx_triangulate_ws_bytes(int n_frames);
+// node_cap: entries of d_nodes / d_node_err an offset may reach; PGX_ST_TRI_* bits go to *status
+void pgx_launch_triangulate(hipStream_t s, const pgx_keypoint *d_kp, int F, int stride, const int32_t *d_frame_ids, int n_frames,
+                            const double *d_P, const int32_t *d_offsets, const int32_t *d_nodes, long long node_cap,
+                            const int32_t *d_track_summary, int max_tracks, double min_parallax_deg, double max_reproj_px,
+                            int refine_iters, double *d_xyz, double *d_quality, int32_t *d_flags, double *d_node_err,
+                            int32_t *d_summary, void *ws, int *status);

@@ -70,3 +70,69 @@ def true_match_descriptors(n, words, seed, flip=0.15):
     perm = rng.permutation(n)
     d2 = np.packbits(bits ^ noise, axis=1).view(np.uint32)[perm]
     return d1, np.ascontiguousarray(d2), perm
+
+
+def look_at_camera(centre, target, f=1200.0, W=1920, H=1080):
+    """P = K [R | -R C] (float64 [3][4]) of a pinhole camera at `centre` looking at `target`; principal point at the image
+    centre, image x along the camera's x axis and image y along its y axis (world +y projects downwards)."""
+    c, t = np.asarray(centre, dtype=np.float64), np.asarray(target, dtype=np.float64)
+    z = (t - c) / np.linalg.norm(t - c)
+    x = np.cross([0.0, 1.0, 0.0], z)
+    x /= np.linalg.norm(x)
+    R = np.stack([x, np.cross(z, x), z])
+    K = np.array([[f, 0.0, W / 2.0], [0.0, f, H / 2.0], [0.0, 0.0, 1.0]])
+    return K @ np.concatenate([R, (-R @ c)[:, None]], axis=1)
+
+
+def make_scene(n_points, n_frames, seed=0, box=1.5, radius=5.0, arc_deg=60.0, f=1200.0, W=1920, H=1080, pairs=None,
+               wrong_rate=0.0, offset=(0.0, 0.0, 0.0)):
+    """A synthetic multi-view scene with known truth, for the track graph and triangulation.
+    n_points uniform in the box [-box, box]^3; n_frames pinhole cameras (W x H, focal f) on an arc of arc_deg degrees at `radius`
+    around the box (heights alternate slightly), all looking at its centre.  A point is seen in a frame if it is in front of
+    the camera and its rounded projection lies in the image; the keypoints of a frame are those rounded projections
+    (x = column, y = row), shuffled.  `offset` translates the whole scene (points and cameras): the keypoints do not change.
+    pairs: image pairs (a, b) for which match lists in the pgx_pair layout are made: for every keypoint k1 of frame a
+    (k1, k2, 0) if its point is seen in b as keypoint k2, else (k1, -1, PGX_DIST_NONE); a fraction wrong_rate of the rows with
+    a true link instead link a random other keypoint of b (dist 0).
+    -> dict(points [N][3], P [F][12], centres [F][3], kps [F] of KEYPOINT_DTYPE, point_id [F] (point of each keypoint),
+            uv [F] ([n][2] unrounded projections in keypoint order), counts [F], pairs [(a, b)], lists [M] of PAIR_DTYPE,
+            wrong [M] (bool per row: a planted wrong link))"""
+    from .api import KEYPOINT_DTYPE, PAIR_DTYPE
+    from ._lib import PGX_DIST_NONE
+    rng = np.random.default_rng(seed)
+    off = np.asarray(offset, dtype=np.float64)
+    pts = rng.uniform(-box, box, size=(n_points, 3))
+    ang = np.radians(np.linspace(-arc_deg / 2.0, arc_deg / 2.0, n_frames)) if n_frames > 1 else np.zeros(1)
+    centres = np.stack([radius * np.sin(ang), 0.15 * radius * ((np.arange(n_frames) % 3) - 1) / 3.0, -radius * np.cos(ang)], 1)
+    kps, pid, uvs, Ps = [], [], [], []
+    for j in range(n_frames):
+        P0 = look_at_camera(centres[j], np.zeros(3), f, W, H)
+        h = pts @ P0[:, :3].T + P0[:, 3]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            uv = h[:, :2] / h[:, 2:3]
+        r = np.round(uv)
+        vis = np.flatnonzero((h[:, 2] > 0) & (r[:, 0] >= 0) & (r[:, 0] < W) & (r[:, 1] >= 0) & (r[:, 1] < H))
+        vis = vis[rng.permutation(len(vis))]
+        k = np.zeros(len(vis), dtype=KEYPOINT_DTYPE)
+        k["x"], k["y"] = r[vis, 0].astype(np.int32), r[vis, 1].astype(np.int32)
+        kps.append(k)
+        pid.append(vis.astype(np.int64))
+        uvs.append(uv[vis])
+        Ps.append(look_at_camera(centres[j] + off, off, f, W, H).reshape(12))
+    lists, wrong = [], []
+    for a, b in (pairs or []):
+        where = np.full(n_points, -1, dtype=np.int64)
+        where[pid[b]] = np.arange(len(pid[b]))
+        k2 = where[pid[a]]
+        m = np.zeros(len(pid[a]), dtype=PAIR_DTYPE)
+        m["k1"] = np.arange(len(pid[a]))
+        bad = (k2 >= 0) & (rng.random(len(k2)) < wrong_rate) & (len(pid[b]) > 1)
+        if bad.any():
+            alt = rng.integers(0, len(pid[b]) - 1, size=int(bad.sum()))
+            k2[bad] = alt + (alt >= k2[bad])      # any keypoint of b but the true one
+        m["k2"] = k2
+        m["dist"] = np.where(k2 >= 0, 0, PGX_DIST_NONE)
+        lists.append(m)
+        wrong.append(bad)
+    return dict(points=pts + off, P=np.array(Ps).reshape(n_frames, 12), centres=centres + off, kps=kps, point_id=pid, uv=uvs,
+                counts=np.array([len(k) for k in kps], dtype=np.int32), pairs=list(pairs or []), lists=lists, wrong=wrong)
