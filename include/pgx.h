@@ -454,6 +454,68 @@ int pgx_triangulate_tracks(pgx_ctx *ctx, const pgx_keypoint *kps, const int32_t 
                            double max_reproj_px, int refine_iters, double *xyz, double *quality, int32_t *flags, double *node_err,
                            int32_t *summary);
 
+/* ---- bundle adjustment of cameras and track points -------------------------------------- */
+/* The stage after the triangulation: refines the free cameras and the points of the tracks together by minimising the
+ * reprojection error (Levenberg-Marquardt), on the same stream, with no host sync.  It also writes P_out, so the caller can
+ * triangulate again with the refined cameras.
+ * Inputs: d_kp, F, stride, d_frame_ids, n_frames, d_offsets, d_nodes, d_track_summary and max_tracks as for
+ * pgx_triangulate_tracks_dev (nodes name frame numbers, keypoints sit in slots; n_tracks = d_track_summary[0], read on the
+ * device), and by frame number:
+ *   d_K [n_frames][4]     fx, fy, cx, cy (float64): pinhole, fixed intrinsics
+ *   d_Rt_in [n_frames][12] R row-major, then t (the layout of pgx_pose_dev's d_Rt, in float64).  With (x, y, z) = R X + t a
+ *           point projects to u = fx (x / z) + cx, v = fy (y / z) + cy; u is pgx_keypoint.x, v is pgx_keypoint.y.
+ *   d_fixed [n_frames]    != 0: the frame is held
+ *   d_xyz_in [max_tracks][3], d_track_flags [max_tracks] (or NULL: all 0), e.g. pgx_triangulate_tracks_dev's xyz and flags
+ * Frames.  UNKNOWN if an entry of its K or Rt is not finite or fx or fy is 0: its observations are skipped, its rows are
+ * copied.  A finite R with max |R R^T - I| > 1e-9 or det R <= 0 is PGX_E_BADARG through pgx_check_status and the frame is
+ * unknown.  A known frame with d_fixed != 0 is FIXED, the other known frames are FREE, numbered in frame order.  More than
+ * 128 free frames: PGX_E_CAPACITY through pgx_check_status; no known fixed frame: PGX_E_BADARG the same way; in both cases no
+ * iteration runs (stop reason 0).  One fixed frame leaves the scale free (the damping keeps the solves definite); two fix it.
+ * Tracks.  Track t takes part if t < min(n_tracks, max_tracks), its flag is 0, xyz_in[t] is finite and it has >= 2 USED
+ * observations (nodes in known frames).  The others are copied.  A node outside [0, n_frames) x [0, stride), in a frame no
+ * slot names, or malformed offsets: PGX_E_BADARG through pgx_check_status, the node is skipped.  A track with two nodes in
+ * one frame: PGX_E_BADARG the same way, the track does not take part.
+ * Cost.  Per used observation r = projection - (u, v), s = |r|^2, rho(s) = s for s <= d^2 and 2 d sqrt(s) - d^2 above, with
+ * d = huber_px (+inf: least squares); C = sum rho.  IRLS weights w = 1 or d / sqrt(s); A = sum w J^T J, g = sum w J^T r.
+ * Parameters.  Free camera: (omega, tau), R' = Exp(omega) R (Rodrigues), t' = t + tau, so d(R X + t)/d omega = -[R X]x.
+ * Point: X' = X + dX.
+ * Levenberg-Marquardt.  Solve (A + lambda D) delta = -g, D = diag(clamp(diag A, 1e-6, 1e32)), by eliminating the 3x3 point
+ * blocks (Schur complement), a Cholesky factorisation of the reduced camera system (<= 768 unknowns) and back-substitution.
+ * Start: C = C0, lambda = lambda0, trace[0] = (C0, lambda0).  The stop test (first match wins) runs at the start and after
+ * every attempted step: the call had an error or no track takes part (reason 0); C == 0, or the last step was accepted with
+ * C_old - C_new <= 1e-12 C_old (reason 2); lambda > 1e16 (reason 4); max_iters steps attempted (reason 1).  An attempt:
+ *   1 a point block or pivot of the damped system that is not positive definite: rejected, lambda *= 10, non-PD count + 1;
+ *   2 else ||delta|| <= 1e-12 (1 + ||x||), x the stacked t of the free cameras and X of the points that take part: stop with
+ *     reason 3, the step is not applied;
+ *   3 else C_new = C at the trial state; C_new < C: accepted (lambda = max(lambda / 10, 1e-12), re-linearise); else
+ *     rejected (lambda *= 10, the next attempt re-solves at the same linearisation).
+ *   trace[i] = (C, lambda) after attempt i.
+ * Outputs (out arrays may alias their in arrays):
+ *   d_Rt_out [n_frames][12]  refined free cameras; fixed and unknown frames copied bit for bit
+ *   d_P_out [n_frames][12]   K [R | t] of Rt_out for known frames (rows (fx r0 + cx r2, fy r1 + cy r2, r2)), NaN for unknown
+ *   d_xyz_out [max_tracks][3] for t < min(n_tracks, max_tracks): the refined point, or xyz_in[t] for a track not taking part
+ *   d_node_err [n_frames * stride] or NULL: the final |r| in d_nodes order, NaN for a node not used in a track taking part
+ *   d_trace [max_iters + 1][2] (C, lambda); rows after the stop are NaN
+ *   d_report [8] int32: attempted steps, accepted steps, stop reason, free frames, tracks taking part, used observations of
+ *           those tracks, of them with z <= 0 at the end, non-PD solves
+ * Returned at once (PGX_E_BADARG): max_iters outside [0, 100], huber_px <= 0 or NaN, lambda0 <= 0 or not finite, null
+ * required pointers, and the size checks of pgx_triangulate_tracks_dev.
+ * Results depend on the inputs only: the same bits for any max_tracks >= n_tracks, any slot layout, from run to run, and from
+ * the host form below.  Asynchronous on the context's stream. */
+int pgx_bundle_adjust_dev(pgx_ctx *ctx, const pgx_keypoint *d_kp, int F, int stride, const int32_t *d_frame_ids, int n_frames,
+                          const double *d_K, const double *d_Rt_in, const int32_t *d_fixed, const int32_t *d_offsets,
+                          const int32_t *d_nodes, const int32_t *d_track_summary, int max_tracks, const double *d_xyz_in,
+                          const int32_t *d_track_flags, int max_iters, double huber_px, double lambda0, double *d_Rt_out,
+                          double *d_P_out, double *d_xyz_out, double *d_node_err, double *d_trace, int32_t *d_report);
+/* Host form: the same kernels on host arrays (the conventions of pgx_triangulate_tracks: kps concatenated by frame, tracks
+ * as pgx_tracks_get writes them; a node outside [0, n_frames) x [0, counts[frame]) or offsets that are not non-decreasing
+ * from 0: PGX_E_BADARG before any GPU work).  xyz_in / xyz_out [n_tracks][3], track_flags [n_tracks] or NULL, node_err
+ * [n_nodes] or NULL; returns when the outputs are in the caller's buffers. */
+int pgx_bundle_adjust(pgx_ctx *ctx, const pgx_keypoint *kps, const int32_t *counts, int n_frames, const double *K,
+                      const double *Rt_in, const int32_t *fixed, const int32_t *track_offsets, const int32_t *nodes, int n_tracks,
+                      const double *xyz_in, const int32_t *track_flags, int max_iters, double huber_px, double lambda0,
+                      double *Rt_out, double *P_out, double *xyz_out, double *node_err, double *trace, int32_t *report);
+
 /* ---- measurement hooks (bench.py) ---------------------------------------------------- */
 /* When on, the named hot kernels are bracketed by HIP events on the launch stream. */
 int pgx_profile_enable(pgx_ctx *ctx, int on);

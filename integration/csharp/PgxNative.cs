@@ -124,6 +124,20 @@ internal static unsafe class PgxNative
                                                                      int* trackOffsets, int* nodes, int nTracks, double minParallaxDeg,
                                                                      double maxReprojPx, int refineIters, double* xyz, double* quality,
                                                                      int* flags, double* nodeErr, int* summary);
+    // bundle adjustment of the free cameras (k [nFrames][4] fx fy cx cy, rt [nFrames][12] R row-major then t, float64) and the
+    // points of the tracks: the device form follows the triangulation on the same stream and reads nTracks from
+    // dTrackSummary[0]; the host form takes what pgx_tracks_get wrote and every frame's keypoints one after another (kps)
+    [DllImport(Lib)] public static extern int pgx_bundle_adjust_dev(IntPtr ctx, void* dKp, int f, int stride, void* dFrameIds, int nFrames,
+                                                                    void* dK, void* dRtIn, void* dFixed, void* dOffsets, void* dNodes,
+                                                                    void* dTrackSummary, int maxTracks, void* dXyzIn, void* dTrackFlags,
+                                                                    int maxIters, double huberPx, double lambda0, void* dRtOut,
+                                                                    void* dPOut, void* dXyzOut, void* dNodeErr, void* dTrace,
+                                                                    void* dReport);
+    [DllImport(Lib)] public static extern int pgx_bundle_adjust(IntPtr ctx, PgxKeypoint* kps, int* counts, int nFrames, double* k,
+                                                                double* rtIn, int* fixedFrames, int* trackOffsets, int* nodes,
+                                                                int nTracks, double* xyzIn, int* trackFlags, int maxIters,
+                                                                double huberPx, double lambda0, double* rtOut, double* pOut,
+                                                                double* xyzOut, double* nodeErr, double* trace, int* report);
 
     /// <summary>Maps a status code back to the exception type the managed implementation throws.</summary>
     public static void Check(IntPtr ctx, int rc)

@@ -33,6 +33,7 @@ EXPORTS = [
     "pgx_knn_guided_batch_dev", "pgx_match_guided_batch_dev", "pgx_knn_guided",
     "pgx_tracks_split_dev", "pgx_tracks_finish_split",
     "pgx_triangulate_tracks_dev", "pgx_triangulate_tracks",
+    "pgx_bundle_adjust_dev", "pgx_bundle_adjust",
 ]
 
 

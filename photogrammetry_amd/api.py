@@ -379,6 +379,53 @@ class Engine:
             _ptr(summary)))
         return dict(xyz=xyz[:n], quality=q[:n], flags=flags[:n], node_err=err[:len(nd)], summary=summary)
 
+    # -- bundle adjustment of cameras and track points (pgx_bundle_adjust*) ------------------------------
+    def bundle_adjust_dev(self, d_kp, F, stride, n_frames, d_K, d_Rt_in, d_fixed, d_offsets, d_nodes, d_track_summary, max_tracks,
+                          d_xyz_in, d_Rt_out, d_P_out, d_xyz_out, d_trace, d_report, max_iters=20, huber_px=float("inf"),
+                          lambda0=1e-3, d_track_flags=None, d_node_err=None, d_frame_ids=None):
+        """Levenberg-Marquardt on the free cameras and the points of the graph's tracks, where they sit in HBM (pgx.h: bundle
+        adjustment).  d_K [n_frames][4], d_Rt_in / d_Rt_out / d_P_out [n_frames][12] float64, d_fixed [n_frames] int32,
+        d_xyz_in / d_xyz_out [max_tracks][3] float64, d_track_flags [max_tracks] int32 or None, d_trace [max_iters + 1][2]
+        float64, d_report [8] int32, d_node_err [n_frames * stride] float64 or None.  n_tracks is read on the device: no sync."""
+        opt = lambda t: _dptr(t) if t is not None else None  # noqa: E731
+        self._chk(self._L.pgx_bundle_adjust_dev(
+            self._h, _dptr(d_kp), int(F), int(stride), opt(d_frame_ids), int(n_frames), _dptr(d_K), _dptr(d_Rt_in), _dptr(d_fixed),
+            _dptr(d_offsets), _dptr(d_nodes), _dptr(d_track_summary), int(max_tracks), _dptr(d_xyz_in), opt(d_track_flags),
+            int(max_iters), C.c_double(huber_px), C.c_double(lambda0), _dptr(d_Rt_out), _dptr(d_P_out), _dptr(d_xyz_out),
+            opt(d_node_err), _dptr(d_trace), _dptr(d_report)))
+
+    def bundle_adjust(self, kps_per_frame, K, Rt, fixed, track_offsets, nodes, xyz, track_flags=None, max_iters=20,
+                      huber_px=float("inf"), lambda0=1e-3):
+        """The host form (pgx_bundle_adjust).  kps_per_frame: one KEYPOINT_DTYPE array per frame; K [n_frames][4], Rt
+        [n_frames][12] float64; fixed [n_frames]; tracks as pgx_tracks_get gives them (track_offsets [n_tracks + 1], nodes
+        [n_nodes][2]) or, with nodes=None, the `tracks` list of tracks_host; xyz [n_tracks][3]; track_flags [n_tracks] or None.
+        -> dict(Rt [F][12], P [F][12], xyz [n][3], node_err [n_nodes], trace [max_iters + 1][2], report [8])"""
+        if nodes is None:
+            tracks = track_offsets
+            track_offsets = np.cumsum([0] + [len(t) for t in tracks])
+            nodes = [fk for t in tracks for fk in t]
+        off = np.ascontiguousarray(track_offsets, dtype=np.int32).reshape(-1)
+        nd = np.ascontiguousarray(nodes, dtype=np.int32).reshape(-1, 2)
+        kp = [np.ascontiguousarray(k, dtype=KEYPOINT_DTYPE) for k in kps_per_frame]
+        nf = len(kp)
+        counts = np.array([len(k) for k in kp], dtype=np.int32)
+        flat = np.ascontiguousarray(np.concatenate(kp) if len(kp) else np.zeros(0, KEYPOINT_DTYPE))
+        Kc = np.ascontiguousarray(K, dtype=np.float64).reshape(nf, 4)
+        Rc = np.ascontiguousarray(Rt, dtype=np.float64).reshape(nf, 12)
+        fx = np.ascontiguousarray(fixed, dtype=np.int32).reshape(nf)
+        n = len(off) - 1
+        X = np.ascontiguousarray(xyz, dtype=np.float64).reshape(n, 3)
+        fl = None if track_flags is None else np.ascontiguousarray(track_flags, dtype=np.int32).reshape(n)
+        Rt_out, P_out = np.zeros((nf, 12)), np.zeros((nf, 12))
+        xyz_out, err = np.zeros((max(n, 1), 3)), np.zeros(max(len(nd), 1))
+        trace, report = np.zeros((int(max_iters) + 1, 2)), np.zeros(8, dtype=np.int32)
+        self._chk(self._L.pgx_bundle_adjust(
+            self._h, _ptr(flat) if len(flat) else None, _ptr(counts), nf, _ptr(Kc), _ptr(Rc), _ptr(fx), _ptr(off),
+            _ptr(nd) if len(nd) else None, n, _ptr(X) if n else None, _ptr(fl) if fl is not None and n else None, int(max_iters),
+            C.c_double(huber_px), C.c_double(lambda0), _ptr(Rt_out), _ptr(P_out), _ptr(xyz_out), _ptr(err), _ptr(trace),
+            _ptr(report)))
+        return dict(Rt=Rt_out, P=P_out, xyz=xyz_out[:n], node_err=err[:len(nd)], trace=trace, report=report)
+
     # -- multi-GPU: the context's own RCCL communicator (pgx_comm_*) ------------------------------
     def comm_init(self, rank, world, unique_id):
         """Collective: every rank calls this with the 128 bytes rank 0 got from comm_unique_id()."""

@@ -24,6 +24,12 @@
 #define PGX_ST_TRI_CAP    128u /* pgx_triangulate_tracks_dev: n_tracks > max_tracks */
 #define PGX_ST_TRI_NODE   256u /* pgx_triangulate_tracks_dev: a node outside the frames / keypoint slots, or malformed offsets */
 #define PGX_ST_TRI_DUP    512u /* pgx_triangulate_tracks_dev: two slots of d_frame_ids name the same frame */
+#define PGX_ST_BA_CAP     1024u  /* pgx_bundle_adjust_dev: n_tracks > max_tracks */
+#define PGX_ST_BA_FREE    2048u  /* pgx_bundle_adjust_dev: more than 128 free frames */
+#define PGX_ST_BA_NODE    4096u  /* pgx_bundle_adjust_dev: a bad node, malformed offsets, or two nodes of a track in one frame */
+#define PGX_ST_BA_DUP     8192u  /* pgx_bundle_adjust_dev: two slots of d_frame_ids name the same frame */
+#define PGX_ST_BA_ROT     16384u /* pgx_bundle_adjust_dev: a finite R that is not a rotation */
+#define PGX_ST_BA_NOFIX   32768u /* pgx_bundle_adjust_dev: no known frame is fixed */
 
 // key = (distance << PGX_IDX_BITS) | index ; limits: index < 2^20, distance < 2^12
 #define PGX_IDX_BITS 20
@@ -122,6 +128,7 @@ struct pgx_ctx {
     DevBuf ws_knn; // pgx_match_nn_batch_dev: top-2 and column nearest of a chunk of image pairs
     DevBuf ws_guided; // guided matching: the keypoint grids of the frames of a chunk of image pairs
     DevBuf ws_tri;    // pgx_triangulate_tracks*: camera table, frame -> slot map, per-workgroup counters
+    DevBuf ws_ba;     // pgx_bundle_adjust*: control block, cameras, reduced system, per-track and per-node state
     hipStream_t mstream[4] = {nullptr, nullptr, nullptr, nullptr}; // [0] wide rounds, [1] residual distance rows, [2], [3] per-pair finishes (alternating)
     hipEvent_t ev_in = nullptr, ev_wide[4] = {nullptr, nullptr, nullptr, nullptr}, ev_rows[4] = {nullptr, nullptr, nullptr, nullptr},
                ev_fin[4] = {nullptr, nullptr, nullptr, nullptr}, ev_join[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -316,3 +323,12 @@ void pgx_launch_triangulate(hipStream_t s, const pgx_keypoint *d_kp, int F, int 
                             const int32_t *d_track_summary, int max_tracks, double min_parallax_deg, double max_reproj_px,
                             int refine_iters, double *d_xyz, double *d_quality, int32_t *d_flags, double *d_node_err,
                             int32_t *d_summary, void *ws, int *status);
+
+// k_bundle.hip (bundle adjustment of cameras and track points; pgx_bundle_adjust_dev semantics, include/pgx.h)
+size_t pgx_bundle_ws_bytes(int n_frames, int max_tracks, long long node_cap);
+// node_cap: entries of d_nodes / d_node_err an offset may reach; PGX_ST_BA_* bits go to *status
+void pgx_launch_bundle(hipStream_t s, const pgx_keypoint *d_kp, int F, int stride, const int32_t *d_frame_ids, int n_frames,
+                       const double *d_K, const double *d_Rt_in, const int32_t *d_fixed, const int32_t *d_offsets, const int32_t *d_nodes,
+                       long long node_cap, const int32_t *d_track_summary, int max_tracks, const double *d_xyz_in,
+                       const int32_t *d_track_flags, int max_iters, double huber_px, double lambda0, double *d_Rt_out, double *d_P_out,
+                       double *d_xyz_out, double *d_node_err, double *d_trace, int32_t *d_report, void *ws, int *status);

@@ -75,13 +75,19 @@ def true_match_descriptors(n, words, seed, flip=0.15):
 def look_at_camera(centre, target, f=1200.0, W=1920, H=1080):
     """P = K [R | -R C] (float64 [3][4]) of a pinhole camera at `centre` looking at `target`; principal point at the image
     centre, image x along the camera's x axis and image y along its y axis (world +y projects downwards)."""
+    R, t = look_at_pose(centre, target)
+    K = np.array([[f, 0.0, W / 2.0], [0.0, f, H / 2.0], [0.0, 0.0, 1.0]])
+    return K @ np.concatenate([R, t[:, None]], axis=1)
+
+
+def look_at_pose(centre, target):
+    """(R [3][3], t [3]) of look_at_camera: world -> camera is X -> R X + t, t = -R C."""
     c, t = np.asarray(centre, dtype=np.float64), np.asarray(target, dtype=np.float64)
     z = (t - c) / np.linalg.norm(t - c)
     x = np.cross([0.0, 1.0, 0.0], z)
     x /= np.linalg.norm(x)
     R = np.stack([x, np.cross(z, x), z])
-    K = np.array([[f, 0.0, W / 2.0], [0.0, f, H / 2.0], [0.0, 0.0, 1.0]])
-    return K @ np.concatenate([R, (-R @ c)[:, None]], axis=1)
+    return R, -R @ c
 
 
 def make_scene(n_points, n_frames, seed=0, box=1.5, radius=5.0, arc_deg=60.0, f=1200.0, W=1920, H=1080, pairs=None,
@@ -94,9 +100,10 @@ def make_scene(n_points, n_frames, seed=0, box=1.5, radius=5.0, arc_deg=60.0, f=
     pairs: image pairs (a, b) for which match lists in the pgx_pair layout are made: for every keypoint k1 of frame a
     (k1, k2, 0) if its point is seen in b as keypoint k2, else (k1, -1, PGX_DIST_NONE); a fraction wrong_rate of the rows with
     a true link instead link a random other keypoint of b (dist 0).
-    -> dict(points [N][3], P [F][12], centres [F][3], kps [F] of KEYPOINT_DTYPE, point_id [F] (point of each keypoint),
-            uv [F] ([n][2] unrounded projections in keypoint order), counts [F], pairs [(a, b)], lists [M] of PAIR_DTYPE,
-            wrong [M] (bool per row: a planted wrong link))"""
+    -> dict(points [N][3], P [F][12], K [F][4] (fx, fy, cx, cy), Rt [F][12] (R row-major, then t; P = K [R | t]),
+            centres [F][3], kps [F] of KEYPOINT_DTYPE, point_id [F] (point of each keypoint), uv [F] ([n][2] unrounded
+            projections in keypoint order), counts [F], pairs [(a, b)], lists [M] of PAIR_DTYPE, wrong [M] (bool per row: a
+            planted wrong link))"""
     from .api import KEYPOINT_DTYPE, PAIR_DTYPE
     from ._lib import PGX_DIST_NONE
     rng = np.random.default_rng(seed)
@@ -134,5 +141,50 @@ def make_scene(n_points, n_frames, seed=0, box=1.5, radius=5.0, arc_deg=60.0, f=
         m["dist"] = np.where(k2 >= 0, 0, PGX_DIST_NONE)
         lists.append(m)
         wrong.append(bad)
-    return dict(points=pts + off, P=np.array(Ps).reshape(n_frames, 12), centres=centres + off, kps=kps, point_id=pid, uv=uvs,
-                counts=np.array([len(k) for k in kps], dtype=np.int32), pairs=list(pairs or []), lists=lists, wrong=wrong)
+    Rts = []
+    for j in range(n_frames):
+        R, t = look_at_pose(centres[j] + off, off)
+        Rts.append(np.concatenate([R.reshape(9), t]))
+    Ks = np.tile([f, f, W / 2.0, H / 2.0], (n_frames, 1))
+    return dict(points=pts + off, P=np.array(Ps).reshape(n_frames, 12), K=Ks, Rt=np.array(Rts).reshape(n_frames, 12),
+                centres=centres + off, kps=kps, point_id=pid, uv=uvs, counts=np.array([len(k) for k in kps], dtype=np.int32),
+                pairs=list(pairs or []), lists=lists, wrong=wrong)
+
+
+def scene_tracks(scene, min_len=2):
+    """The true tracks of a make_scene scene: one per point seen in >= min_len frames, nodes in frame order.
+    -> (offsets [n + 1] int32, nodes [n_nodes][2] int32, point [n] (the point of each track))"""
+    seen = {}
+    for f, pid in enumerate(scene["point_id"]):
+        for k, p in enumerate(pid):
+            seen.setdefault(int(p), []).append((f, k))
+    pts = [p for p in sorted(seen) if len(seen[p]) >= min_len]
+    off = np.concatenate([[0], np.cumsum([len(seen[p]) for p in pts])]).astype(np.int32)
+    nodes = np.array([n for p in pts for n in seen[p]], dtype=np.int32).reshape(-1, 2)
+    return off, nodes, np.array(pts, dtype=np.int64)
+
+
+def perturb(Rt, xyz, seed, rot_deg=0.3, centre_sigma=0.05, point_sigma=0.015, fixed=None):
+    """Cameras and points moved by a seeded random amount, for bundle adjustment: each camera's R turned by rot_deg degrees
+    about a random axis (R' = Exp(w) R) and its centre C = -R^T t moved by a random vector of length centre_sigma; each point
+    moved by N(0, point_sigma^2) per coordinate.  Frames with fixed[f] != 0 are returned unchanged.
+    -> (Rt [F][12], xyz [n][3])"""
+    rng = np.random.default_rng(seed)
+    Rt = np.array(Rt, dtype=np.float64).reshape(-1, 12)
+    out = Rt.copy()
+    for f in range(len(Rt)):
+        axis = rng.normal(size=3)
+        dirn = rng.normal(size=3)
+        if fixed is not None and fixed[f]:
+            continue
+        axis *= np.radians(rot_deg) / np.linalg.norm(axis)
+        R, t = Rt[f, :9].reshape(3, 3), Rt[f, 9:]
+        C = -R.T @ t + dirn * (centre_sigma / np.linalg.norm(dirn))
+        th = np.linalg.norm(axis)
+        k = axis / th
+        Kx = np.array([[0.0, -k[2], k[1]], [k[2], 0.0, -k[0]], [-k[1], k[0], 0.0]])
+        R2 = (np.eye(3) + np.sin(th) * Kx + (1.0 - np.cos(th)) * (Kx @ Kx)) @ R
+        out[f, :9] = R2.reshape(9)
+        out[f, 9:] = -R2 @ C
+    X = np.array(xyz, dtype=np.float64).reshape(-1, 3)
+    return out, X + rng.normal(scale=point_sigma, size=X.shape)
