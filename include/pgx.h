@@ -516,6 +516,78 @@ int pgx_bundle_adjust(pgx_ctx *ctx, const pgx_keypoint *kps, const int32_t *coun
                       const double *xyz_in, const int32_t *track_flags, int max_iters, double huber_px, double lambda0,
                       double *Rt_out, double *P_out, double *xyz_out, double *node_err, double *trace, int32_t *report);
 
+/* ---- frame registration (absolute pose) by P3P RANSAC against track points ------------- */
+/* Places frames that have no pose yet into the frame and scale of the existing reconstruction: the stage between two
+ * triangulations of the incremental loop (known frames -> pgx_triangulate_tracks_dev -> this -> triangulate again on P_out
+ * -> pgx_bundle_adjust_dev), on the same stream, with no host sync.
+ * Inputs: d_kp, F, stride, d_frame_ids, n_frames, d_offsets, d_nodes, d_track_summary and max_tracks as for
+ * pgx_bundle_adjust_dev (nodes name frame numbers, keypoints sit in slots; n_tracks = d_track_summary[0], read on the
+ * device); d_K [n_frames][4] (fx, fy, cx, cy) and d_Rt_in [n_frames][12] (R row-major, then t; float64) in BA's
+ * conventions: with (x, y, z) = R X + t a point projects to u = fx x / z + cx, v = fy y / z + cy (u = pgx_keypoint.x,
+ * v = pgx_keypoint.y); d_register [n_frames]; d_xyz [max_tracks][3] and d_track_flags [max_tracks] (or NULL: all 0), e.g.
+ * pgx_triangulate_tracks_dev's xyz and flags.
+ * Targets.  Frame f is a target if d_register[f] != 0; d_Rt_in of a target is not read.  A target whose K has an entry
+ * that is not finite or fx or fy == 0 is failed with PGX_REG_BADK and has no correspondences.  Every other frame is copied
+ * bit for bit into Rt_out, with P_out = K [R | t] if its K passes that test and its Rt is finite, NaN otherwise.
+ * Correspondences of target f, position j in this order: tracks t < min(n_tracks, max_tracks) in order, then the nodes of
+ * each track in order; a node (f, k) is one if the track's flag is 0 and xyz[t] is finite: (u, v) = (kp.x, kp.y), X = xyz[t].
+ * A track with two nodes in one target frame: PGX_E_BADARG through pgx_check_status, those nodes are skipped.  A node
+ * outside [0, n_frames) x [0, stride), in a frame no slot names, malformed offsets, or two slots naming one frame:
+ * PGX_E_BADARG through pgx_check_status, as in the triangulation (the node or track is skipped).
+ * Shift.  S_f = the mean of the correspondences' X (a fixed-order sum), X' = X - S_f; the pose (R, t_S) is found in the
+ * shifted world, and Rt_out's t = t_S - R S_f (each entry t_S[i] - ((R[i][0] S0 + R[i][1] S1) + R[i][2] S2)).
+ * Samples.  For s in [0, n_samples): state = seed ^ ((uint64)f << 32) ^ (uint64)s * 0xD1B54A32D192ED03 (f the frame
+ * number); draw splitmix64(state) % n (n = correspondences) until there are 3 distinct positions (k_pose.hip's generator).
+ * Minimal solver.  P3P by Lambda Twist (Persson and Nordberg, ECCV 2018) on the unit bearings of ((u - cx) / fx,
+ * (v - cy) / fy, 1) and the three X': the cubic's root by monotone Newton, the degenerate conic's eigenvectors by cross
+ * products, up to 3 Newton steps on the depths, R = [Y1 - Y2, Y1 - Y3, (Y1 - Y2) x (Y1 - Y3)] [X'1 - X'2, X'1 - X'3, ...]^-1.
+ * Every real solution with positive depth at its 3 points and finite entries is a hypothesis (at most 4 per sample); a
+ * sample's solutions are ranked by ascending |t_S|^2 (ties: the solver's order), hypothesis h = 4 s + rank.
+ * Inlier predicate (no division, evaluated in this order): x = ((R00 X'0 + R01 X'1) + R02 X'2) + tS0, y and z alike;
+ * a = fx * x + (cx - u) * z, b = fy * y + (cy - v) * z, e = inlier_px * z; inlier iff z > 0 and a * a + b * b <= e * e.
+ * Winner: the most inliers, ties to the smallest h (integers only: the grid and the summation order do not matter).
+ * Refinement: up to refine_iters Gauss-Newton steps on the winner's inlier set with pixel residuals r = (fx (x / z) +
+ * (cx - u), fy (y / z) + (cy - v)), R' = Exp(omega) R, t_S' = t_S + tau (BA's parameterisation), a 6x6 Cholesky solve.  A
+ * step is kept only if the sum of r^2 over that set strictly falls; the refinement stops at the first step not kept, when
+ * ||delta|| <= 1e-12 (1 + ||t_S||), or when the Cholesky solve is not positive definite.  The final inlier set is the
+ * predicate at the refined pose.
+ * Failure: fewer than 3 correspondences PGX_REG_FEWPOINTS; no hypothesis at all PGX_REG_NOSOLUTION; fewer than min_inliers
+ * final inliers PGX_REG_FEWINLIERS.  A failed target has NaN rows in Rt_out and P_out (the triangulation and BA treat it as
+ * unknown).
+ * Outputs:
+ *   d_Rt_out, d_P_out [n_frames][12]  P rows (fx r0 + cx r2, fy r1 + cy r2, r2) of [R | t], as BA writes them
+ *   d_frame_stats [n_frames][4] int32: correspondences, final inliers, winning sample or -1, PGX_REG_* flags;
+ *           (-1, -1, -1, -1) for a frame that is not a target
+ *   d_frame_err [n_frames][2]   rms and max of |r| over the final inliers; NaN when there are none
+ *   d_node_inlier [n_frames * stride] or NULL, in d_nodes order for the nodes of tracks t < min(n_tracks, max_tracks): 1 a
+ *           final inlier, 0 an outlier correspondence, -1 not a correspondence of a target
+ *   d_report [8] int32: targets, registered targets, targets carrying each flag bit (BADK first), correspondences of all
+ *           targets, final inliers of all targets
+ * Returned at once (PGX_E_BADARG): n_samples outside [1, 65536], inlier_px <= 0 or not finite, min_inliers < 3,
+ * refine_iters outside [0, 32], null required pointers, and the size checks of pgx_triangulate_tracks_dev.
+ * n_tracks > max_tracks: PGX_E_CAPACITY through pgx_check_status, the first max_tracks tracks are used.
+ * Results depend on the inputs only: the same bits for any max_tracks >= n_tracks, any slot layout, from run to run, and
+ * from the host form below.  Asynchronous on the context's stream. */
+#define PGX_REG_BADK       1
+#define PGX_REG_FEWPOINTS  2
+#define PGX_REG_NOSOLUTION 4
+#define PGX_REG_FEWINLIERS 8
+int pgx_register_frames_dev(pgx_ctx *ctx, const pgx_keypoint *d_kp, int F, int stride, const int32_t *d_frame_ids, int n_frames,
+                            const double *d_K, const double *d_Rt_in, const int32_t *d_register, const int32_t *d_offsets,
+                            const int32_t *d_nodes, const int32_t *d_track_summary, int max_tracks, const double *d_xyz,
+                            const int32_t *d_track_flags, int n_samples, double inlier_px, int min_inliers, int refine_iters,
+                            uint64_t seed, double *d_Rt_out, double *d_P_out, int32_t *d_frame_stats, double *d_frame_err,
+                            int32_t *d_node_inlier, int32_t *d_report);
+/* Host form: the same kernels on host arrays (the conventions of pgx_bundle_adjust: kps concatenated by frame, tracks as
+ * pgx_tracks_get writes them; a node outside [0, n_frames) x [0, counts[frame]) or offsets that are not non-decreasing
+ * from 0: PGX_E_BADARG before any GPU work).  xyz [n_tracks][3], track_flags [n_tracks] or NULL, node_inlier [n_nodes] or
+ * NULL; returns when the outputs are in the caller's buffers. */
+int pgx_register_frames(pgx_ctx *ctx, const pgx_keypoint *kps, const int32_t *counts, int n_frames, const double *K,
+                        const double *Rt_in, const int32_t *reg, const int32_t *track_offsets, const int32_t *nodes, int n_tracks,
+                        const double *xyz, const int32_t *track_flags, int n_samples, double inlier_px, int min_inliers,
+                        int refine_iters, uint64_t seed, double *Rt_out, double *P_out, int32_t *frame_stats, double *frame_err,
+                        int32_t *node_inlier, int32_t *report);
+
 /* ---- measurement hooks (bench.py) ---------------------------------------------------- */
 /* When on, the named hot kernels are bracketed by HIP events on the launch stream. */
 int pgx_profile_enable(pgx_ctx *ctx, int on);

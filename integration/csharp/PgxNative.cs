@@ -23,6 +23,7 @@ internal static unsafe class PgxNative
     public const int StageDetect = 0, StageMatchWide = 1, StageMatchRows = 2, StageMatchDone = 3;   // PGX_STAGE_*
     public const int CommIdBytes = 128;                                                   // PGX_COMM_ID_BYTES
     public const int TriFewViews = 1, TriDegenerate = 2, TriBehind = 4, TriParallax = 8, TriReproj = 16;   // PGX_TRI_* (0 = valid)
+    public const int RegBadK = 1, RegFewPoints = 2, RegNoSolution = 4, RegFewInliers = 8;   // PGX_REG_* (0 = registered)
 
     // Exports of include/pgx.h that this binding deliberately leaves out (tests/test_csharp_binding.py holds the list to the
     // header): the caller's-HIP-stream hook and the measurement hooks (a managed host owns no hipStream_t and reads no HIP event
@@ -138,6 +139,21 @@ internal static unsafe class PgxNative
                                                                 int nTracks, double* xyzIn, int* trackFlags, int maxIters,
                                                                 double huberPx, double lambda0, double* rtOut, double* pOut,
                                                                 double* xyzOut, double* nodeErr, double* trace, int* report);
+    // frame registration by P3P RANSAC against the track points (k [nFrames][4] fx fy cx cy, rt [nFrames][12] R row-major then
+    // t, float64; frames with reg != 0 are placed): the device form reads nTracks from dTrackSummary[0]; the host form takes
+    // what pgx_tracks_get wrote and every frame's keypoints one after another (kps)
+    [DllImport(Lib)] public static extern int pgx_register_frames_dev(IntPtr ctx, void* dKp, int f, int stride, void* dFrameIds, int nFrames,
+                                                                      void* dK, void* dRtIn, void* dRegister, void* dOffsets, void* dNodes,
+                                                                      void* dTrackSummary, int maxTracks, void* dXyz, void* dTrackFlags,
+                                                                      int nSamples, double inlierPx, int minInliers, int refineIters,
+                                                                      ulong seed, void* dRtOut, void* dPOut, void* dFrameStats,
+                                                                      void* dFrameErr, void* dNodeInlier, void* dReport);
+    [DllImport(Lib)] public static extern int pgx_register_frames(IntPtr ctx, PgxKeypoint* kps, int* counts, int nFrames, double* k,
+                                                                  double* rtIn, int* reg, int* trackOffsets, int* nodes, int nTracks,
+                                                                  double* xyz, int* trackFlags, int nSamples, double inlierPx,
+                                                                  int minInliers, int refineIters, ulong seed, double* rtOut,
+                                                                  double* pOut, int* frameStats, double* frameErr, int* nodeInlier,
+                                                                  int* report);
 
     /// <summary>Maps a status code back to the exception type the managed implementation throws.</summary>
     public static void Check(IntPtr ctx, int rc)

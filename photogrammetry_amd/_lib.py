@@ -34,6 +34,7 @@ EXPORTS = [
     "pgx_tracks_split_dev", "pgx_tracks_finish_split",
     "pgx_triangulate_tracks_dev", "pgx_triangulate_tracks",
     "pgx_bundle_adjust_dev", "pgx_bundle_adjust",
+    "pgx_register_frames_dev", "pgx_register_frames",
 ]
 
 

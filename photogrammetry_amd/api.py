@@ -426,6 +426,55 @@ class Engine:
             _ptr(report)))
         return dict(Rt=Rt_out, P=P_out, xyz=xyz_out[:n], node_err=err[:len(nd)], trace=trace, report=report)
 
+    # -- frame registration by P3P RANSAC against track points (pgx_register_frames*) ------------------
+    def register_frames_dev(self, d_kp, F, stride, n_frames, d_K, d_Rt_in, d_register, d_offsets, d_nodes, d_track_summary,
+                            max_tracks, d_xyz, d_Rt_out, d_P_out, d_frame_stats, d_frame_err, d_report, n_samples=1024,
+                            inlier_px=2.0, min_inliers=12, refine_iters=10, seed=0, d_track_flags=None, d_node_inlier=None,
+                            d_frame_ids=None):
+        """Pose of every frame with d_register != 0 from its 2D-3D correspondences, where they sit in HBM (pgx.h: frame
+        registration).  d_K [n_frames][4], d_Rt_in / d_Rt_out / d_P_out [n_frames][12] float64, d_register [n_frames] int32,
+        d_xyz [max_tracks][3] float64, d_track_flags [max_tracks] int32 or None, d_frame_stats [n_frames][4] int32,
+        d_frame_err [n_frames][2] float64, d_node_inlier [n_frames * stride] int32 or None, d_report [8] int32.  n_tracks is
+        read on the device: no sync."""
+        opt = lambda t: _dptr(t) if t is not None else None  # noqa: E731
+        self._chk(self._L.pgx_register_frames_dev(
+            self._h, _dptr(d_kp), int(F), int(stride), opt(d_frame_ids), int(n_frames), _dptr(d_K), _dptr(d_Rt_in),
+            _dptr(d_register), _dptr(d_offsets), _dptr(d_nodes), _dptr(d_track_summary), int(max_tracks), _dptr(d_xyz),
+            opt(d_track_flags), int(n_samples), C.c_double(inlier_px), int(min_inliers), int(refine_iters), C.c_uint64(seed),
+            _dptr(d_Rt_out), _dptr(d_P_out), _dptr(d_frame_stats), _dptr(d_frame_err), opt(d_node_inlier), _dptr(d_report)))
+
+    def register_frames(self, kps_per_frame, K, Rt, reg, track_offsets, nodes, xyz, track_flags=None, n_samples=1024,
+                        inlier_px=2.0, min_inliers=12, refine_iters=10, seed=0):
+        """The host form (pgx_register_frames).  kps_per_frame: one KEYPOINT_DTYPE array per frame; K [n_frames][4], Rt
+        [n_frames][12] float64; reg [n_frames]; tracks as pgx_tracks_get gives them (track_offsets [n_tracks + 1], nodes
+        [n_nodes][2]) or, with nodes=None, the `tracks` list of tracks_host; xyz [n_tracks][3]; track_flags [n_tracks] or None.
+        -> dict(Rt [F][12], P [F][12], frame_stats [F][4], frame_err [F][2], node_inlier [n_nodes], report [8])"""
+        if nodes is None:
+            tracks = track_offsets
+            track_offsets = np.cumsum([0] + [len(t) for t in tracks])
+            nodes = [fk for t in tracks for fk in t]
+        off = np.ascontiguousarray(track_offsets, dtype=np.int32).reshape(-1)
+        nd = np.ascontiguousarray(nodes, dtype=np.int32).reshape(-1, 2)
+        kp = [np.ascontiguousarray(k, dtype=KEYPOINT_DTYPE) for k in kps_per_frame]
+        nf = len(kp)
+        counts = np.array([len(k) for k in kp], dtype=np.int32)
+        flat = np.ascontiguousarray(np.concatenate(kp) if len(kp) else np.zeros(0, KEYPOINT_DTYPE))
+        Kc = np.ascontiguousarray(K, dtype=np.float64).reshape(nf, 4)
+        Rc = np.ascontiguousarray(Rt, dtype=np.float64).reshape(nf, 12)
+        rg = np.ascontiguousarray(reg, dtype=np.int32).reshape(nf)
+        n = len(off) - 1
+        X = np.ascontiguousarray(xyz, dtype=np.float64).reshape(n, 3)
+        fl = None if track_flags is None else np.ascontiguousarray(track_flags, dtype=np.int32).reshape(n)
+        Rt_out, P_out = np.zeros((nf, 12)), np.zeros((nf, 12))
+        stats, ferr = np.zeros((nf, 4), dtype=np.int32), np.zeros((nf, 2))
+        ni, report = np.zeros(max(len(nd), 1), dtype=np.int32), np.zeros(8, dtype=np.int32)
+        self._chk(self._L.pgx_register_frames(
+            self._h, _ptr(flat) if len(flat) else None, _ptr(counts), nf, _ptr(Kc), _ptr(Rc), _ptr(rg), _ptr(off),
+            _ptr(nd) if len(nd) else None, n, _ptr(X) if n else None, _ptr(fl) if fl is not None and n else None, int(n_samples),
+            C.c_double(inlier_px), int(min_inliers), int(refine_iters), C.c_uint64(seed), _ptr(Rt_out), _ptr(P_out), _ptr(stats),
+            _ptr(ferr), _ptr(ni), _ptr(report)))
+        return dict(Rt=Rt_out, P=P_out, frame_stats=stats, frame_err=ferr, node_inlier=ni[:len(nd)], report=report)
+
     # -- multi-GPU: the context's own RCCL communicator (pgx_comm_*) ------------------------------
     def comm_init(self, rank, world, unique_id):
         """Collective: every rank calls this with the 128 bytes rank 0 got from comm_unique_id()."""

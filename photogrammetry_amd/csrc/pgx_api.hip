@@ -85,6 +85,14 @@ int decode_status(pgx_ctx *c, int bits)
         return fail(c, PGX_E_BADARG, "bundle adjustment: a finite R is not a rotation (max |R R^T - I| > 1e-9 or det R <= 0; the frame was "
                                      "treated as unknown)");
     if (bits & PGX_ST_BA_NOFIX) return fail(c, PGX_E_BADARG, "bundle adjustment: no known frame is fixed (no iteration ran)");
+    if (bits & PGX_ST_REG_CAP)
+        return fail(c, PGX_E_CAPACITY, "registration: n_tracks exceeds max_tracks (only the first max_tracks were used)");
+    if (bits & PGX_ST_REG_NODE)
+        return fail(c, PGX_E_BADARG, "registration: a node outside the frames / keypoint slots, or malformed offsets (those nodes or "
+                                     "tracks were skipped)");
+    if (bits & PGX_ST_REG_DUP) return fail(c, PGX_E_BADARG, "registration: two slots of d_frame_ids name the same frame");
+    if (bits & PGX_ST_REG_TWICE)
+        return fail(c, PGX_E_BADARG, "registration: a track has two nodes in one target frame (those nodes were skipped)");
     return PGX_OK;
 }
 
@@ -347,7 +355,7 @@ void pgx_ctx_destroy(pgx_ctx *c)
     for (hipEvent_t ev : c->ev_pool) (void)hipEventDestroy(ev);
     DevBuf *bufs[] = {&c->d_pairs, &c->d_map, &c->ws_gray, &c->ws_seg, &c->ws_segoff, &c->ws_nraw, &c->ws_rawxy,
                       &c->ws_rawscore, &c->ws_nms, &c->ws_order, &c->ws_nkept, &c->st_a, &c->st_b, &c->st_c,
-                      &c->st_d, &c->st_e, &c->st_f, &c->ws_pose, &c->ws_tracks, &c->ws_tracks_split, &c->ws_agree, &c->ws_matchn[0], &c->ws_matchn[1], &c->ws_matchn[2], &c->ws_matchn[3], &c->ws_knn, &c->ws_guided, &c->ws_tri, &c->ws_ba};
+                      &c->st_d, &c->st_e, &c->st_f, &c->ws_pose, &c->ws_tracks, &c->ws_tracks_split, &c->ws_agree, &c->ws_matchn[0], &c->ws_matchn[1], &c->ws_matchn[2], &c->ws_matchn[3], &c->ws_knn, &c->ws_guided, &c->ws_tri, &c->ws_ba, &c->ws_reg};
     for (DevBuf *b : bufs) b->release();
     c->pin_in.release();
     c->pin_out.release();
@@ -1311,6 +1319,131 @@ int pgx_bundle_adjust(pgx_ctx *c, const pgx_keypoint *kps, const int32_t *counts
     if (n_tracks > 0) HIPCHK(c, hipMemcpyAsync(xyz_out, o + p_xyz, (size_t)n_tracks * 24, hipMemcpyDeviceToHost, c->stream));
     if (node_err && n_nodes > 0) HIPCHK(c, hipMemcpyAsync(node_err, o + p_err, (size_t)n_nodes * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(trace, o + p_tr, (size_t)(max_iters + 1) * 16, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(report, o + p_rep, 8 * 4, hipMemcpyDeviceToHost, c->stream));
+    return sync_status(c);
+}
+
+// ---- frame registration by P3P RANSAC ------------------------------------------------------------------------------
+
+namespace {
+int reg_args(pgx_ctx *c, int n_samples, double inlier_px, int min_inliers, int refine_iters)
+{
+    if (n_samples < 1 || n_samples > 65536) return fail(c, PGX_E_BADARG, "n_samples = %d, must be in [1, 65536]", n_samples);
+    if (!(inlier_px > 0.0) || !std::isfinite(inlier_px)) return fail(c, PGX_E_BADARG, "inlier_px must be finite and > 0");
+    if (min_inliers < 3) return fail(c, PGX_E_BADARG, "min_inliers = %d, must be >= 3", min_inliers);
+    if (refine_iters < 0 || refine_iters > 32) return fail(c, PGX_E_BADARG, "refine_iters = %d, must be in [0, 32]", refine_iters);
+    return PGX_OK;
+}
+} // namespace
+
+int pgx_register_frames_dev(pgx_ctx *c, const pgx_keypoint *d_kp, int F, int stride, const int32_t *d_frame_ids, int n_frames,
+                            const double *d_K, const double *d_Rt_in, const int32_t *d_register, const int32_t *d_offsets,
+                            const int32_t *d_nodes, const int32_t *d_track_summary, int max_tracks, const double *d_xyz,
+                            const int32_t *d_track_flags, int n_samples, double inlier_px, int min_inliers, int refine_iters,
+                            uint64_t seed, double *d_Rt_out, double *d_P_out, int32_t *d_frame_stats, double *d_frame_err,
+                            int32_t *d_node_inlier, int32_t *d_report)
+{
+    if (!c || !d_kp || !d_K || !d_Rt_in || !d_register || !d_offsets || !d_nodes || !d_track_summary || !d_xyz || !d_Rt_out ||
+        !d_P_out || !d_frame_stats || !d_frame_err || !d_report)
+        return c ? fail(c, PGX_E_BADARG, "null pointer") : PGX_E_BADARG;
+    Lock l(c);
+    if (F <= 0 || stride <= 0 || n_frames <= 0) return fail(c, PGX_E_BADARG, "F, stride and n_frames must be positive");
+    if (!d_frame_ids && n_frames != F) return fail(c, PGX_E_BADARG, "without d_frame_ids, n_frames must equal F");
+    if ((long long)n_frames * stride > (1ll << 30)) return fail(c, PGX_E_BADARG, "n_frames * stride must be <= 2^30");
+    if (max_tracks < 0) return fail(c, PGX_E_BADARG, "max_tracks must be >= 0");
+    const int rc = reg_args(c, n_samples, inlier_px, min_inliers, refine_iters);
+    if (rc != PGX_OK) return rc;
+    const long long node_cap = (long long)n_frames * stride;
+    HIPCHK(c, c->ws_reg.ensure(pgx_register_ws_bytes(n_frames, node_cap, n_samples)));
+    {
+        ProfScope ps(c, "register");
+        pgx_launch_register(c->stream, d_kp, F, stride, d_frame_ids, n_frames, d_K, d_Rt_in, d_register, d_offsets, d_nodes, node_cap,
+                            d_track_summary, max_tracks, d_xyz, d_track_flags, n_samples, inlier_px, min_inliers, refine_iters, seed,
+                            d_Rt_out, d_P_out, d_frame_stats, d_frame_err, d_node_inlier, d_report, c->ws_reg.p, c->d_status);
+    }
+    HIPCHK(c, hipGetLastError());
+    return PGX_OK;
+}
+
+int pgx_register_frames(pgx_ctx *c, const pgx_keypoint *kps, const int32_t *counts, int n_frames, const double *K, const double *Rt_in,
+                        const int32_t *reg, const int32_t *track_offsets, const int32_t *nodes, int n_tracks, const double *xyz,
+                        const int32_t *track_flags, int n_samples, double inlier_px, int min_inliers, int refine_iters, uint64_t seed,
+                        double *Rt_out, double *P_out, int32_t *frame_stats, double *frame_err, int32_t *node_inlier, int32_t *report)
+{
+    if (!c || !counts || !K || !Rt_in || !reg || !track_offsets || !Rt_out || !P_out || !frame_stats || !frame_err || !report ||
+        n_frames <= 0 || n_tracks < 0 || (n_tracks > 0 && !xyz))
+        return c ? fail(c, PGX_E_BADARG, "null pointer or bad size") : PGX_E_BADARG;
+    Lock l(c);
+    const int rc = reg_args(c, n_samples, inlier_px, min_inliers, refine_iters);
+    if (rc != PGX_OK) return rc;
+    // the host's checks: counts, offsets, nodes (the device then sees no out-of-range node)
+    long long n_kp = 0;
+    int stride = 1;
+    for (int f = 0; f < n_frames; f++) {
+        if (counts[f] < 0) return fail(c, PGX_E_BADARG, "counts[%d] = %d is negative", f, counts[f]);
+        n_kp += counts[f];
+        stride = counts[f] > stride ? counts[f] : stride;
+    }
+    if (n_kp > 0 && !kps) return fail(c, PGX_E_BADARG, "null pointer (kps)");
+    if ((long long)n_frames * stride > (1ll << 30)) return fail(c, PGX_E_BADARG, "n_frames * max(counts) must be <= 2^30");
+    if (track_offsets[0] != 0) return fail(c, PGX_E_BADARG, "track_offsets[0] must be 0");
+    for (int t = 0; t < n_tracks; t++)
+        if (track_offsets[t + 1] < track_offsets[t]) return fail(c, PGX_E_BADARG, "track_offsets decrease at track %d", t);
+    const long long n_nodes = track_offsets[n_tracks];
+    if (n_nodes > 0 && !nodes) return fail(c, PGX_E_BADARG, "null pointer (nodes)");
+    for (long long o = 0; o < n_nodes; o++) {
+        const int f = nodes[2 * o], k = nodes[2 * o + 1];
+        if (f < 0 || f >= n_frames || k < 0 || k >= counts[f])
+            return fail(c, PGX_E_BADARG, "node %lld = (%d, %d) is outside [0, n_frames) x [0, counts[frame])", o, f, k);
+    }
+    // staging (pinned, one upload): keypoints [n_frames][stride], K, Rt, reg, offsets, nodes, xyz, flags, the track summary
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t nn = (size_t)(n_nodes > 0 ? n_nodes : 1), nt1 = (size_t)(n_tracks > 0 ? n_tracks : 1);
+    const size_t b_kp = al((size_t)n_frames * stride * sizeof(pgx_keypoint)), b_K = al((size_t)n_frames * 32),
+                 b_Rt = al((size_t)n_frames * 96), b_rg = al((size_t)n_frames * 4), b_off = al((size_t)(n_tracks + 1) * 4),
+                 b_nodes = al(nn * 8), b_xyz = al(nt1 * 24), b_fl = al(nt1 * 4);
+    const size_t o_K = b_kp, o_Rt = o_K + b_K, o_rg = o_Rt + b_Rt, o_off = o_rg + b_rg, o_nodes = o_off + b_off, o_xyz = o_nodes + b_nodes,
+                 o_fl = o_xyz + b_xyz, o_ts = o_fl + b_fl, b_in = o_ts + 256;
+    HIPCHK(c, c->pin_in.ensure(b_in));
+    HIPCHK(c, c->st_a.ensure(b_in));
+    char *h = c->pin_in.as<char>();
+    for (int f = 0, at = 0; f < n_frames; at += counts[f], f++)
+        if (counts[f] > 0) std::memcpy(h + (size_t)f * stride * sizeof(pgx_keypoint), kps + at, (size_t)counts[f] * sizeof(pgx_keypoint));
+    std::memcpy(h + o_K, K, (size_t)n_frames * 32);
+    std::memcpy(h + o_Rt, Rt_in, (size_t)n_frames * 96);
+    std::memcpy(h + o_rg, reg, (size_t)n_frames * 4);
+    std::memcpy(h + o_off, track_offsets, (size_t)(n_tracks + 1) * 4);
+    if (n_nodes > 0) std::memcpy(h + o_nodes, nodes, (size_t)n_nodes * 8);
+    if (n_tracks > 0) std::memcpy(h + o_xyz, xyz, (size_t)n_tracks * 24);
+    if (n_tracks > 0 && track_flags) std::memcpy(h + o_fl, track_flags, (size_t)n_tracks * 4);
+    const int32_t ts[8] = {n_tracks, (int32_t)n_nodes};
+    std::memcpy(h + o_ts, ts, sizeof ts);
+    HIPCHK(c, hipMemcpyAsync(c->st_a.p, h, b_in, hipMemcpyHostToDevice, c->stream));
+    char *d = c->st_a.as<char>();
+    // outputs: Rt, P, stats, err, node_inlier, report
+    const size_t b_st = al((size_t)n_frames * 16), b_er = al((size_t)n_frames * 16);
+    const size_t p_P = b_Rt, p_st = 2 * b_Rt, p_er = p_st + b_st, p_ni = p_er + b_er, p_rep = p_ni + al(nn * 4);
+    HIPCHK(c, c->st_b.ensure(p_rep + 256));
+    char *o = c->st_b.as<char>();
+    HIPCHK(c, c->ws_reg.ensure(pgx_register_ws_bytes(n_frames, n_nodes, n_samples)));
+    {
+        ProfScope ps(c, "register");
+        pgx_launch_register(c->stream, reinterpret_cast<const pgx_keypoint *>(d), n_frames, stride, nullptr, n_frames,
+                            reinterpret_cast<const double *>(d + o_K), reinterpret_cast<const double *>(d + o_Rt),
+                            reinterpret_cast<const int32_t *>(d + o_rg), reinterpret_cast<const int32_t *>(d + o_off),
+                            reinterpret_cast<const int32_t *>(d + o_nodes), n_nodes, reinterpret_cast<const int32_t *>(d + o_ts), n_tracks,
+                            reinterpret_cast<const double *>(d + o_xyz), track_flags ? reinterpret_cast<const int32_t *>(d + o_fl) : nullptr,
+                            n_samples, inlier_px, min_inliers, refine_iters, seed, reinterpret_cast<double *>(o),
+                            reinterpret_cast<double *>(o + p_P), reinterpret_cast<int32_t *>(o + p_st), reinterpret_cast<double *>(o + p_er),
+                            node_inlier ? reinterpret_cast<int32_t *>(o + p_ni) : nullptr, reinterpret_cast<int32_t *>(o + p_rep),
+                            c->ws_reg.p, c->d_status);
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(Rt_out, o, (size_t)n_frames * 96, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(P_out, o + p_P, (size_t)n_frames * 96, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(frame_stats, o + p_st, (size_t)n_frames * 16, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(frame_err, o + p_er, (size_t)n_frames * 16, hipMemcpyDeviceToHost, c->stream));
+    if (node_inlier && n_nodes > 0) HIPCHK(c, hipMemcpyAsync(node_inlier, o + p_ni, (size_t)n_nodes * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(report, o + p_rep, 8 * 4, hipMemcpyDeviceToHost, c->stream));
     return sync_status(c);
 }

@@ -30,6 +30,10 @@
 #define PGX_ST_BA_DUP     8192u  /* pgx_bundle_adjust_dev: two slots of d_frame_ids name the same frame */
 #define PGX_ST_BA_ROT     16384u /* pgx_bundle_adjust_dev: a finite R that is not a rotation */
 #define PGX_ST_BA_NOFIX   32768u /* pgx_bundle_adjust_dev: no known frame is fixed */
+#define PGX_ST_REG_CAP    65536u  /* pgx_register_frames_dev: n_tracks > max_tracks */
+#define PGX_ST_REG_NODE   131072u /* pgx_register_frames_dev: a node outside the frames / keypoint slots, or malformed offsets */
+#define PGX_ST_REG_DUP    262144u /* pgx_register_frames_dev: two slots of d_frame_ids name the same frame */
+#define PGX_ST_REG_TWICE  524288u /* pgx_register_frames_dev: a track with two nodes in one target frame */
 
 // key = (distance << PGX_IDX_BITS) | index ; limits: index < 2^20, distance < 2^12
 #define PGX_IDX_BITS 20
@@ -129,6 +133,7 @@ struct pgx_ctx {
     DevBuf ws_guided; // guided matching: the keypoint grids of the frames of a chunk of image pairs
     DevBuf ws_tri;    // pgx_triangulate_tracks*: camera table, frame -> slot map, per-workgroup counters
     DevBuf ws_ba;     // pgx_bundle_adjust*: control block, cameras, reduced system, per-track and per-node state
+    DevBuf ws_reg;    // pgx_register_frames*: target tables, correspondence lists, hypotheses of one chunk, scoring keys
     hipStream_t mstream[4] = {nullptr, nullptr, nullptr, nullptr}; // [0] wide rounds, [1] residual distance rows, [2], [3] per-pair finishes (alternating)
     hipEvent_t ev_in = nullptr, ev_wide[4] = {nullptr, nullptr, nullptr, nullptr}, ev_rows[4] = {nullptr, nullptr, nullptr, nullptr},
                ev_fin[4] = {nullptr, nullptr, nullptr, nullptr}, ev_join[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -332,3 +337,13 @@ void pgx_launch_bundle(hipStream_t s, const pgx_keypoint *d_kp, int F, int strid
                        long long node_cap, const int32_t *d_track_summary, int max_tracks, const double *d_xyz_in,
                        const int32_t *d_track_flags, int max_iters, double huber_px, double lambda0, double *d_Rt_out, double *d_P_out,
                        double *d_xyz_out, double *d_node_err, double *d_trace, int32_t *d_report, void *ws, int *status);
+
+// k_register.hip (frame registration by P3P RANSAC; pgx_register_frames_dev semantics, include/pgx.h)
+size_t pgx_register_ws_bytes(int n_frames, long long node_cap, int n_samples);
+// node_cap: entries of d_nodes / d_node_inlier an offset may reach; PGX_ST_REG_* bits go to *status
+void pgx_launch_register(hipStream_t s, const pgx_keypoint *d_kp, int F, int stride, const int32_t *d_frame_ids, int n_frames,
+                         const double *d_K, const double *d_Rt_in, const int32_t *d_register, const int32_t *d_offsets,
+                         const int32_t *d_nodes, long long node_cap, const int32_t *d_track_summary, int max_tracks,
+                         const double *d_xyz, const int32_t *d_track_flags, int n_samples, double inlier_px, int min_inliers,
+                         int refine_iters, uint64_t seed, double *d_Rt_out, double *d_P_out, int32_t *d_frame_stats,
+                         double *d_frame_err, int32_t *d_node_inlier, int32_t *d_report, void *ws, int *status);

@@ -1,0 +1,280 @@
+"""GPU tests of frame registration (pgx_register_frames_dev / pgx_register_frames; include/pgx.h).  Scenes are synth.make_scene's
+with their true tracks; frames 0 and 1 are known and the points are triangulated from them.  Results are held to the numpy
+yardstick of tests/register_ref.py (winning sample, correspondences, final inlier sets outside a rounding band, poses), to
+themselves across runs, capacities, slot layouts and the host form (bit for bit), every failure flag and every error the
+contract lists is provoked, and the whole chain -- triangulate, register, triangulate, bundle-adjust -- runs on one stream."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+import photogrammetry_amd as pg
+import register_ref as ref
+import triangulate_ref as tri
+from photogrammetry_amd import synth
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+I32 = dict(dtype=torch.int32, device=DEV)
+F64 = dict(dtype=torch.float64, device=DEV)
+INF = float("inf")
+NS, IP, MIN_IN, ITERS, SEED = 128, 2.0, 12, 10, 7
+
+
+def device_problem(kps, off, nodes, slots=None, n_slots=None):
+    nf = len(kps)
+    slots = list(range(nf)) if slots is None else list(slots)
+    F = nf if n_slots is None else n_slots
+    stride = max(1, max(len(k) for k in kps))
+    kp = np.zeros((F, stride), dtype=pg.KEYPOINT_DTYPE)
+    ids = np.full(F, -1, np.int32)
+    for f, k in enumerate(kps):
+        kp[slots[f], :len(k)] = k
+        ids[slots[f]] = f
+    n = len(off) - 1
+    return dict(kp=torch.from_numpy(kp.view(np.int32).reshape(F, stride, 4)).to(DEV), ids=torch.from_numpy(ids).to(DEV), F=F,
+                nf=nf, stride=stride, identity=n_slots is None and slots == list(range(nf)),
+                off=torch.from_numpy(np.asarray(off, np.int32)).to(DEV),
+                nodes=torch.from_numpy(np.ascontiguousarray(nodes, np.int32).reshape(-1, 2)).to(DEV),
+                tsum=torch.tensor([n, len(nodes), 0, 0, 0, 0, 0, 0], **I32), n_tracks=n, n_nodes=len(nodes))
+
+
+def run(engine, d, K, Rt, reg, xyz, flags=None, max_tracks=None, n_samples=NS, inlier_px=IP, min_inliers=MIN_IN,
+        refine_iters=ITERS, seed=SEED):
+    nf, n = d["nf"], d["n_tracks"]
+    mt = n if max_tracks is None else max_tracks
+    dK = torch.from_numpy(np.ascontiguousarray(K, np.float64).reshape(nf, 4)).to(DEV)
+    dRt = torch.from_numpy(np.ascontiguousarray(Rt, np.float64).reshape(nf, 12)).to(DEV)
+    dreg = torch.from_numpy(np.ascontiguousarray(reg, np.int32)).to(DEV)
+    X = torch.full((max(mt, n, 1), 3), 3.0, **F64)
+    X[:n] = torch.from_numpy(np.ascontiguousarray(xyz, np.float64).reshape(n, 3))
+    fl = None
+    if flags is not None:
+        fl = torch.full((max(mt, n, 1),), 0, **I32)
+        fl[:n] = torch.from_numpy(np.asarray(flags, np.int32))
+    Rt_out, P_out = torch.full((nf, 12), 5.0, **F64), torch.full((nf, 12), 5.0, **F64)
+    stats, ferr = torch.full((nf, 4), 9, **I32), torch.full((nf, 2), 5.0, **F64)
+    ni, report = torch.full((nf * d["stride"],), 9, **I32), torch.full((8,), 7, **I32)
+    torch.cuda.synchronize()
+    engine.register_frames_dev(d["kp"], d["F"], d["stride"], nf, dK, dRt, dreg, d["off"], d["nodes"], d["tsum"], mt, X, Rt_out,
+                               P_out, stats, ferr, report, n_samples, inlier_px, min_inliers, refine_iters, seed, d_track_flags=fl,
+                               d_node_inlier=ni, d_frame_ids=None if d["identity"] else d["ids"])
+    engine.check_status()
+    return dict(Rt=Rt_out.cpu().numpy(), P=P_out.cpu().numpy(), frame_stats=stats.cpu().numpy(), frame_err=ferr.cpu().numpy(),
+                node_inlier=ni.cpu().numpy()[:d["n_nodes"]], report=report.cpu().numpy())
+
+
+def bits(a):
+    return np.ascontiguousarray(a).view(np.uint8).tobytes()
+
+
+def same_bits(a, b):
+    for k in ("Rt", "P", "frame_stats", "frame_err", "node_inlier", "report"):
+        assert bits(a[k]) == bits(b[k]), k
+
+
+def problem(n_points=2000, nf=12, seed=5, offset=(0.0, 0.0, 0.0), outlier_frame=6, outlier_rate=0.2):
+    """integer keypoints (make_scene's rounding), 20 % of one target's keypoints moved to random pixels; points triangulated
+    by the yardstick from the two true cameras of frames 0 and 1"""
+    s = synth.make_scene(n_points, nf, seed=seed, offset=offset)
+    off, nodes, pid = synth.scene_tracks(s)
+    kps = [k.copy() for k in s["kps"]]
+    if outlier_frame is not None:
+        rng = np.random.default_rng(9)
+        k = kps[outlier_frame]
+        mv = rng.choice(len(k), size=int(outlier_rate * len(k)), replace=False)
+        k["x"][mv] = rng.integers(0, 1920, len(mv))
+        k["y"][mv] = rng.integers(0, 1080, len(mv))
+    P = s["P"].copy()
+    P[2:] = np.nan
+    t = tri.triangulate(kps, P, off, nodes, 0.0, 1e9, 10)
+    reg = np.ones(nf, np.int32)
+    reg[:2] = 0
+    return s, kps, off, nodes, t["xyz"], t["flags"], reg
+
+
+def test_against_yardstick_and_truth(engine):
+    s, kps, off, nodes, xyz, flags, reg = problem()
+    d = device_problem(kps, off, nodes)
+    got = run(engine, d, s["K"], s["Rt"], reg, xyz, flags)
+    e = ref.register(kps, s["K"], s["Rt"], reg, off, nodes, xyz, flags, NS, IP, MIN_IN, ITERS, SEED)
+    print("gpu stats", got["frame_stats"].tolist(), "report", got["report"].tolist(), "err", got["frame_err"].tolist())
+    assert (got["frame_stats"][:, 0] == e["frame_stats"][:, 0]).all()
+    assert (got["frame_stats"][:, 2] == e["frame_stats"][:, 2]).all(), (got["frame_stats"][:, 2], e["frame_stats"][:, 2])
+    assert (got["frame_stats"][:, 3] == e["frame_stats"][:, 3]).all()
+    assert (got["frame_stats"][2:, 3] == 0).all()
+    for f in range(2, len(kps)):
+        x = e["extra"][f]
+        nd = x["nodes"]
+        resolved = x["margin"] > 1e-9
+        assert (got["node_inlier"][nd][resolved] == e["node_inlier"][nd][resolved]).all(), f
+    assert (got["node_inlier"][e["node_inlier"] == -1] == -1).all()
+    scale = 5.0
+    assert np.abs(got["Rt"] - e["Rt"]).max() <= 1e-9 * scale
+    assert (got["Rt"][:2] == s["Rt"][:2]).all()
+    # truth: the rounding noise of integer keypoints leaves the centres within a few mm of the true ones on a 5 m radius
+    cerr = [float(np.abs(ref.centre(got["Rt"][f]) - s["centres"][f]).max()) for f in range(2, len(kps))]
+    print("centre errors", cerr)
+    for f in range(2, len(kps)):
+        assert cerr[f - 2] <= 0.25, f       # 5 % of the radius: the points come from two cameras and integer keypoints
+        assert got["frame_err"][f, 0] <= 1.5 and got["frame_err"][f, 1] <= IP * (1 + 1e-9)
+    assert got["report"][0] == 10 and got["report"][1] == 10
+    assert got["report"][6] == got["frame_stats"][2:, 0].sum() and got["report"][7] == got["frame_stats"][2:, 1].sum()
+    assert (np.abs(got["P"] - e["P"]) <= 1e-9 * np.abs(e["P"]).max()).all()
+
+
+def test_identical_bits_across_runs_capacity_slots_and_host_form(engine):
+    s, kps, off, nodes, xyz, flags, reg = problem(n_points=1200)
+    d = device_problem(kps, off, nodes)
+    a = run(engine, d, s["K"], s["Rt"], reg, xyz, flags)
+    same_bits(a, run(engine, d, s["K"], s["Rt"], reg, xyz, flags))
+    same_bits(a, run(engine, d, s["K"], s["Rt"], reg, xyz, flags, max_tracks=2 * d["n_tracks"]))
+    nf = len(kps)
+    slots = list(np.random.default_rng(3).permutation(nf + 3)[:nf])
+    dp = device_problem(kps, off, nodes, slots=slots, n_slots=nf + 3)
+    b = run(engine, dp, s["K"], s["Rt"], reg, xyz, flags)
+    for k in ("Rt", "P", "frame_stats", "frame_err", "report"):
+        assert bits(a[k]) == bits(b[k]), k
+    assert bits(a["node_inlier"]) == bits(b["node_inlier"])
+    h = engine.register_frames(kps, s["K"], s["Rt"], reg, off, nodes, xyz, flags, NS, IP, MIN_IN, ITERS, SEED)
+    same_bits(a, h)
+
+
+def test_copies_and_failures(engine):
+    s, kps, off, nodes, xyz, flags, reg = problem(n_points=800, outlier_frame=None)
+    K = s["K"].copy()
+    K[5, 0] = 0.0        # BADK
+    Rt = s["Rt"].copy()
+    Rt[4] = np.nan       # a target's Rt_in is not read
+    d = device_problem(kps, off, nodes)
+    got = run(engine, d, K, Rt, reg, xyz, flags)
+    st = got["frame_stats"]
+    assert (st[:2] == -1).all() and bits(got["Rt"][:2]) == bits(Rt[:2]) and np.isnan(got["frame_err"][:2]).all()
+    assert (got["P"][:2] == ref.make_P(K[0], Rt[0])[None]).all() or np.allclose(got["P"][:2], s["P"][:2], rtol=1e-12)
+    assert tuple(st[5]) == (0, 0, -1, ref.BADK) and np.isnan(got["Rt"][5]).all() and np.isnan(got["P"][5]).all()
+    assert (got["node_inlier"][nodes[:, 0] == 5] == -1).all() and (got["node_inlier"][nodes[:, 0] < 2] == -1).all()
+    assert st[4, 3] == 0 and np.isfinite(got["Rt"][4]).all()
+    assert got["report"][2] == 1 and got["report"][1] == 9
+    # FEWINLIERS: min_inliers above every count
+    g2 = run(engine, d, s["K"], s["Rt"], reg, xyz, flags, min_inliers=100000)
+    assert (g2["frame_stats"][2:, 3] == ref.FEWINLIERS).all() and np.isnan(g2["Rt"][2:]).all()
+    assert (g2["frame_stats"][2:, 1] > 0).all() and np.isfinite(g2["frame_err"][2:]).all()
+    assert g2["report"][1] == 0 and g2["report"][5] == 10
+    # NOSOLUTION and FEWPOINTS on a hand-made graph: frame 1 sees 3 collinear points, frame 2 sees 2 points
+    kp3 = [np.zeros(3, dtype=pg.KEYPOINT_DTYPE) for _ in range(3)]
+    for k in kp3:
+        k["x"], k["y"] = [100, 200, 300], [50, 60, 70]
+    off3 = np.array([0, 2, 4, 6, 7, 8], np.int32)
+    nodes3 = np.array([[0, 0], [1, 0], [0, 1], [1, 1], [0, 2], [1, 2], [2, 0], [2, 1]], np.int32)
+    X3 = np.array([[0.0, 0.0, 5.0], [0.5, 0.0, 5.0], [1.0, 0.0, 5.0], [0.0, 1.0, 6.0], [1.0, 1.0, 6.0]])
+    reg3 = np.array([0, 1, 1], np.int32)
+    g3 = run(engine, device_problem(kp3, off3, nodes3), s["K"][:3], s["Rt"][:3], reg3, X3, min_inliers=3)
+    assert tuple(g3["frame_stats"][1]) == (3, 0, -1, ref.NOSOLUTION), g3["frame_stats"]
+    assert tuple(g3["frame_stats"][2]) == (2, 0, -1, ref.FEWPOINTS), g3["frame_stats"]
+    assert np.isnan(g3["Rt"][1:]).all() and np.isnan(g3["P"][1:]).all() and np.isnan(g3["frame_err"][1:]).all()
+    assert g3["node_inlier"].tolist() == [-1, 0, -1, 0, -1, 0, 0, 0]
+    assert g3["report"].tolist() == [2, 0, 0, 1, 1, 0, 5, 0]
+
+
+def _raw(engine, d, K, Rt, reg, X, mt, n_samples=NS, inlier_px=IP, min_inliers=MIN_IN, refine_iters=ITERS, null_k=False,
+         ids=None):
+    nf = d["nf"]
+    dK = torch.from_numpy(np.ascontiguousarray(K, np.float64)).to(DEV)
+    dRt = torch.from_numpy(np.ascontiguousarray(Rt, np.float64)).to(DEV)
+    dreg = torch.from_numpy(np.ascontiguousarray(reg, np.int32)).to(DEV)
+    dX = torch.from_numpy(np.ascontiguousarray(X, np.float64)).to(DEV)
+    outs = [torch.empty((nf, 12), **F64), torch.empty((nf, 12), **F64), torch.empty((nf, 4), **I32), torch.empty((nf, 2), **F64),
+            torch.empty(8, **I32)]
+    p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    rc = engine._L.pgx_register_frames_dev(
+        engine._h, p(d["kp"]), d["F"], d["stride"], p(ids) if ids is not None else None, nf, None if null_k else p(dK), p(dRt),
+        p(dreg), p(d["off"]), p(d["nodes"]), p(d["tsum"]), int(mt), p(dX), None, int(n_samples), C.c_double(inlier_px),
+        int(min_inliers), int(refine_iters), C.c_uint64(1), p(outs[0]), p(outs[1]), p(outs[2]), p(outs[3]), None, p(outs[4]))
+    return rc
+
+
+def test_errors(engine):
+    s, kps, off, nodes, xyz, flags, reg = problem(n_points=300, outlier_frame=None)
+    X = np.where(np.isfinite(xyz), xyz, 0.0)
+    d = device_problem(kps, off, nodes)
+    n = d["n_tracks"]
+    BAD = 5
+    for kw in (dict(n_samples=0), dict(n_samples=65537), dict(inlier_px=0.0), dict(inlier_px=float("nan")),
+               dict(inlier_px=INF), dict(min_inliers=2), dict(refine_iters=-1), dict(refine_iters=33), dict(null_k=True)):
+        assert _raw(engine, d, s["K"], s["Rt"], reg, X, n, **kw) == BAD, kw
+    torch.cuda.synchronize()
+    with pytest.raises(pg.ArgumentException):
+        run(engine, d, s["K"], s["Rt"], reg, X, n_samples=0)
+    # capacity: max_tracks < n_tracks, through pgx_check_status
+    with pytest.raises(pg.CapacityError):
+        run(engine, d, s["K"], s["Rt"], reg, X, max_tracks=n - 5)
+    # a track with two nodes in one target frame
+    nodes2 = nodes.copy()
+    o = next(o for o in range(len(nodes)) if nodes[o, 0] >= 2)      # a node in a target frame
+    t = int(np.searchsorted(off, o, side="right")) - 1
+    other = off[t] if o != off[t] else off[t] + 1
+    nodes2[other] = nodes2[o]
+    with pytest.raises(pg.ArgumentException):
+        run(engine, device_problem(kps, off, nodes2), s["K"], s["Rt"], reg, X)
+    # a node outside the keypoint slots
+    nodes3 = nodes.copy()
+    nodes3[0, 1] = 10 ** 6
+    with pytest.raises(pg.ArgumentException):
+        run(engine, device_problem(kps, off, nodes3), s["K"], s["Rt"], reg, X)
+    # two slots naming one frame
+    nf = len(kps)
+    dd = device_problem(kps, off, nodes, slots=list(range(nf)), n_slots=nf + 1)
+    dd["ids"][nf] = 3
+    dd["identity"] = False
+    with pytest.raises(pg.ArgumentException):
+        run(engine, dd, s["K"], s["Rt"], reg, X)
+    # the host form checks its nodes before any GPU work
+    with pytest.raises(pg.ArgumentException):
+        engine.register_frames(kps, s["K"], s["Rt"], reg, off, nodes3, X)
+    engine.check_status()
+
+
+def test_chain_on_one_stream(engine):
+    """scene_tracks -> triangulation from the 2 true cameras -> registration of the other 10 -> triangulation on P_out ->
+    bundle adjustment with frames 0 and 1 fixed -> triangulation: the rms is the integer keypoints' rounding noise"""
+    nf = 12
+    s = synth.make_scene(2000, nf, seed=21)
+    off, nodes, pid = synth.scene_tracks(s)
+    d = device_problem(s["kps"], off, nodes)
+    N, n, stride = nf * d["stride"], d["n_tracks"], d["stride"]
+    P0 = s["P"].copy()
+    P0[2:] = np.nan
+    dP0 = torch.from_numpy(P0).to(DEV)
+    dK, dRt = torch.from_numpy(s["K"]).to(DEV), torch.from_numpy(s["Rt"]).to(DEV)
+    reg = torch.ones(nf, **I32)
+    reg[:2] = 0
+    fixed = torch.zeros(nf, **I32)
+    fixed[:2] = 1
+    xyz, q, fl, summ = torch.empty((n, 3), **F64), torch.empty((n, 3), **F64), torch.empty(n, **I32), torch.empty(8, **I32)
+    xyz2, q2, fl2, summ2 = torch.empty((n, 3), **F64), torch.empty((n, 3), **F64), torch.empty(n, **I32), torch.empty(8, **I32)
+    xyz3, q3, fl3, summ3 = torch.empty((n, 3), **F64), torch.empty((n, 3), **F64), torch.empty(n, **I32), torch.empty(8, **I32)
+    Rt1, P1 = torch.empty((nf, 12), **F64), torch.empty((nf, 12), **F64)
+    stats, ferr, rep = torch.empty((nf, 4), **I32), torch.empty((nf, 2), **F64), torch.empty(8, **I32)
+    Rt2, P2, X2 = torch.empty((nf, 12), **F64), torch.empty((nf, 12), **F64), torch.empty((n, 3), **F64)
+    trace, brep = torch.empty((21, 2), **F64), torch.empty(8, **I32)
+    torch.cuda.synchronize()
+    engine.triangulate_tracks_dev(d["kp"], nf, stride, nf, dP0, d["off"], d["nodes"], d["tsum"], n, xyz, q, fl, summ, 1.0, INF, 10)
+    engine.register_frames_dev(d["kp"], nf, stride, nf, dK, dRt, reg, d["off"], d["nodes"], d["tsum"], n, xyz, Rt1, P1, stats, ferr,
+                               rep, 256, 2.0, 12, 10, 3, d_track_flags=fl)
+    engine.triangulate_tracks_dev(d["kp"], nf, stride, nf, P1, d["off"], d["nodes"], d["tsum"], n, xyz2, q2, fl2, summ2, 1.0, INF,
+                                  10)
+    engine.bundle_adjust_dev(d["kp"], nf, stride, nf, dK, Rt1, fixed, d["off"], d["nodes"], d["tsum"], n, xyz2, Rt2, P2, X2, trace,
+                             brep, 20, INF, 1e-3, d_track_flags=fl2)
+    engine.triangulate_tracks_dev(d["kp"], nf, stride, nf, P2, d["off"], d["nodes"], d["tsum"], n, xyz3, q3, fl3, summ3, 1.0, INF,
+                                  10)
+    engine.check_status()
+    r = rep.cpu().numpy()
+    assert r[0] == 10 and r[1] == 10, (r, stats.cpu().numpy())
+    f3 = fl3.cpu().numpy()
+    assert not (f3 & 4).any()   # PGX_TRI_BEHIND
+    ok = f3 == 0
+    rms = np.sqrt(np.mean(q3.cpu().numpy()[ok, 0] ** 2))
+    print("chain: registration report %s, BA report %s, final triangulation rms %.4f over %d tracks" %
+          (r.tolist(), brep.cpu().tolist(), rms, ok.sum()))
+    assert ok.sum() > 0.9 * n and rms <= 0.42
