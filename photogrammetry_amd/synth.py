@@ -164,6 +164,30 @@ def scene_tracks(scene, min_len=2):
     return off, nodes, np.array(pts, dtype=np.int64)
 
 
+def cut_tracks(scene, lengths, seed=0):
+    """Tracks of chosen lengths from a make_scene scene: point p's views, in frame order, cut to one contiguous run of
+    min(lengths[p], views of p) nodes at a seeded random start (tools/bench_triangulate.py's shape_a); points left with fewer
+    than 2 nodes give no track.  lengths: [n_points] ints.
+    -> (offsets [n + 1] int32, nodes [n_nodes][2] int32, point [n] (the point of each track))"""
+    rng = np.random.default_rng(seed)
+    seen = {}
+    for f, pid in enumerate(scene["point_id"]):
+        for k, p in enumerate(pid):
+            seen.setdefault(int(p), []).append((f, k))
+    tracks, pts = [], []
+    for p in sorted(seen):
+        v = seen[p]
+        L = min(len(v), int(lengths[p]))
+        if L < 2:
+            continue
+        a = int(rng.integers(0, len(v) - L + 1))
+        tracks.append(v[a:a + L])
+        pts.append(p)
+    off = np.concatenate([[0], np.cumsum([len(t) for t in tracks])]).astype(np.int32)
+    nodes = np.array([n for t in tracks for n in t], dtype=np.int32).reshape(-1, 2)
+    return off, nodes, np.array(pts, dtype=np.int64)
+
+
 def perturb(Rt, xyz, seed, rot_deg=0.3, centre_sigma=0.05, point_sigma=0.015, fixed=None):
     """Cameras and points moved by a seeded random amount, for bundle adjustment: each camera's R turned by rot_deg degrees
     about a random axis (R' = Exp(w) R) and its centre C = -R^T t moved by a random vector of length centre_sigma; each point

@@ -153,9 +153,9 @@ class Problem:
         Vd = V.copy()
         for i in range(3):
             Vd[:, i, i] += lam * np.clip(V[:, i, i], 1e-6, 1e32)
-        for t in range(npt):
+        if npt:
             try:
-                np.linalg.cholesky(Vd[t])
+                np.linalg.cholesky(Vd)          # raises if any block is not positive definite
             except np.linalg.LinAlgError:
                 raise NotPD()
         Vi = np.linalg.inv(Vd)
@@ -168,28 +168,20 @@ class Problem:
         np.add.at(U, cf, w[idx, None, None] * np.einsum("mki,mkj->mij", Jc[idx], Jc[idx]))
         gc = np.zeros((nfr, 6))
         np.add.at(gc, cf, w[idx, None] * np.einsum("mki,mk->mi", Jc[idx], r[idx]))
-        S = np.zeros((nfr, nfr, 6, 6))
+        Sf = np.zeros((6 * nfr, 6 * nfr))
         for c in range(nfr):
-            S[c, c] = U[c]
-            for i in range(6):
-                S[c, c, i, i] += lam * np.clip(U[c, i, i], 1e-6, 1e32)
+            Sf[6 * c:6 * c + 6, 6 * c:6 * c + 6] = U[c] + lam * np.diag(np.clip(np.diag(U[c]), 1e-6, 1e32))
         rhs = -gc
         np.add.at(rhs, cf, np.einsum("mij,mj->mi", Y, gp[self.ob_t[idx]]))
-        # pairs of free observations in one track
-        by_t = {}
-        for m, t in zip(idx, self.ob_t[idx]):
-            by_t.setdefault(int(t), []).append(m)
-        pa, pb = [], []
-        pos = {int(m): i for i, m in enumerate(idx)}
-        for ms in by_t.values():
-            for ma in ms:
-                for mb in ms:
-                    pa.append(pos[int(ma)])
-                    pb.append(pos[int(mb)])
-        pa, pb = np.array(pa, np.int64), np.array(pb, np.int64)
-        if len(pa):
-            np.add.at(S, (cf[pa], cf[pb]), -np.einsum("mij,mkj->mik", Y[pa], W[pb]))
-        Sf = S.transpose(0, 2, 1, 3).reshape(6 * nfr, 6 * nfr)
+        # every pair (a, b) of free observations in one track adds -Y_a W_b^T to block (cam a, cam b).  A track holds at most one
+        # observation per frame, so (free camera, track) places each Y_a and W_b once in a [6 n_free][3 n_part] matrix, and the
+        # sum over all pairs of all tracks is one product of two of them
+        if len(idx):
+            tcol = self.ob_t[idx]
+            Yb, Wb = np.zeros((nfr, 6, npt, 3)), np.zeros((nfr, 6, npt, 3))
+            Yb[cf, :, tcol, :] = Y
+            Wb[cf, :, tcol, :] = W
+            Sf -= Yb.reshape(6 * nfr, 3 * npt) @ Wb.reshape(6 * nfr, 3 * npt).T
         if nfr:
             try:
                 L = np.linalg.cholesky(np.tril(Sf) + np.tril(Sf, -1).T)

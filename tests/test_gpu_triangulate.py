@@ -99,7 +99,8 @@ def same_bits(x, y):
         assert bits(x[k]) == bits(y[k]), k
 
 
-def check_against_yardstick(got, kps, P, min_par, max_e, iters):
+def check_against_yardstick(got, kps, P, min_par, max_e, iters, stop_band=False):
+    """stop_band: hold the refined points to max(1e-9 dist, ref.stop_band) (scenes with narrow-baseline tracks; see there)"""
     e = ref.triangulate(kps, P, got["offsets"], got["nodes"], min_par, max_e, iters)
     near = ref.near_threshold(e, min_par, max_e)
     assert (got["flags"][~near] == e["flags"][~near]).all(), np.flatnonzero((got["flags"] != e["flags"]) & ~near)
@@ -113,7 +114,10 @@ def check_against_yardstick(got, kps, P, min_par, max_e, iters):
     ok = fin & (e["parallax"] >= 1.0)
     dx = np.linalg.norm(got["xyz"] - e["xyz"], axis=1)
     if iters > 0:
-        assert (dx[ok] <= 1e-9 * dist[ok]).all(), (dx[ok] / dist[ok]).max()
+        tol = 1e-9 * dist
+        if stop_band:
+            tol = np.maximum(tol, ref.stop_band(kps, P, got["offsets"], got["nodes"], e))
+        assert (dx[ok] <= tol[ok]).all(), (dx[ok] / tol[ok]).max()
         assert np.abs(got["quality"][fin, :2] - e["quality"][fin, :2]).max(initial=0) <= 1e-6
     else:
         assert (dx[fin] <= 1e-6 * np.linalg.norm(e["xyz"][fin], axis=1).clip(1.0)).all()

@@ -102,6 +102,39 @@ def triangulate(kps, P, offsets, nodes, min_parallax_deg, max_reproj_px, refine_
     return out
 
 
+def stop_band(kps, P, offsets, nodes, ref):
+    """Per track, how far from the yardstick's refined point another correct implementation may stop: the radius within which
+    the cost cannot tell two points apart in float64.  Each residual is a difference of two values of ~1e3 px, so the cost
+    carries a rounding error of about dC = 2 eps sum |r_i| |uv_i|; a step d changes the cost by about d^T J^T J d, so two points
+    within sqrt(dC / lambda_min(J^T J)) of each other compare in either order, and the refinement's stop test ("the cost did not
+    decrease") may end anywhere in that ball.  On narrow baselines (short tracks of scenes with 64 or 130 frames on a 60..120
+    degree arc) this radius exceeds 1e-9 of the camera distance: two formulations of this yardstick (SVD or Gram matrix start)
+    differ by up to 4e-9 there, and more refinement steps do not reduce it; the kernel stays within 0.7 of the radius.  On
+    33..64-node tracks over 130 frames on a 60-degree arc the two starts still differ by up to 1.1e-9, so tracks of that
+    length can pass 1e-9 only with this band.  Tests
+    whose scenes have such tracks hold the refined points to max(1e-9 dist, this radius) (tests/test_gpu_geometry_limits.py).
+    -> [n_tracks] (NaN where the yardstick has no point)"""
+    P3 = np.asarray(P, dtype=np.float64).reshape(-1, 3, 4)
+    known, C, _, _ = cameras(P)
+    xy = [np.stack([k["x"], k["y"]], 1).astype(np.float64) if k.dtype.names else np.asarray(k, dtype=np.float64) for k in kps]
+    offsets, nodes = np.asarray(offsets), np.asarray(nodes).reshape(-1, 2)
+    eps = np.finfo(np.float64).eps
+    out = np.full(len(offsets) - 1, np.nan)
+    for t in np.flatnonzero(np.isfinite(ref["xyz"]).all(1)):
+        nd = nodes[offsets[t]:offsets[t + 1]]
+        nd = nd[known[nd[:, 0]]]
+        f = nd[:, 0]
+        S = C[f].mean(axis=0)
+        Q = P3[f].copy()
+        Q[:, :, 3] += Q[:, :, :3] @ S
+        uv = np.array([xy[fr][k] for fr, k in nd])
+        p, z = _project(Q, ref["xyz"][t] - S)
+        J = ((Q[:, :2, :3] - p[:, :, None] * Q[:, 2:3, :3]) / z[:, None, None]).reshape(-1, 3)
+        dC = 2.0 * eps * (np.abs(p - uv) * np.abs(uv)).sum()
+        out[t] = np.sqrt(dC / np.linalg.eigvalsh(J.T @ J)[0])
+    return out
+
+
 def near_threshold(ref, min_parallax_deg, max_reproj_px, rel=1e-6):
     """Tracks whose flag decision lies within `rel` of its threshold (the tests exclude them from flag equality)."""
     def close(x, thr):
