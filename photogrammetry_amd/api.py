@@ -63,6 +63,21 @@ def _dptr(t):
     return C.c_void_p(t if isinstance(t, int) else t.data_ptr())
 
 
+def _host_tracks(kps_per_frame, track_offsets, nodes):
+    """The host forms' inputs: tracks as (track_offsets, nodes) or, with nodes=None, as a list of tracks; keypoints per frame.
+    -> (off [n_tracks + 1], nd [n_nodes][2], kp per frame, counts [n_frames], flat keypoints)"""
+    if nodes is None:
+        tracks = track_offsets
+        track_offsets = np.cumsum([0] + [len(t) for t in tracks])
+        nodes = [fk for t in tracks for fk in t]
+    off = np.ascontiguousarray(track_offsets, dtype=np.int32).reshape(-1)
+    nd = np.ascontiguousarray(nodes, dtype=np.int32).reshape(-1, 2)
+    kp = [np.ascontiguousarray(k, dtype=KEYPOINT_DTYPE) for k in kps_per_frame]
+    counts = np.array([len(k) for k in kp], dtype=np.int32)
+    flat = np.ascontiguousarray(np.concatenate(kp) if len(kp) else np.zeros(0, KEYPOINT_DTYPE))
+    return off, nd, kp, counts, flat
+
+
 class Engine:
     """One pgx context = one GPU (pgx_ctx_create).  Thin, 1:1 with the C ABI."""
 
@@ -359,15 +374,7 @@ class Engine:
         (or [n_frames][12]) float64, NaN rows for frames without a pose.  Tracks as pgx_tracks_get gives them (track_offsets
         [n_tracks + 1], nodes [n_nodes][2]) or, with nodes=None, the `tracks` list of tracks_host.
         -> dict(xyz [n][3], quality [n][3] = (rms, max, parallax), flags [n], node_err [n_nodes], summary [8])."""
-        if nodes is None:
-            tracks = track_offsets
-            track_offsets = np.cumsum([0] + [len(t) for t in tracks])
-            nodes = [fk for t in tracks for fk in t]
-        off = np.ascontiguousarray(track_offsets, dtype=np.int32).reshape(-1)
-        nd = np.ascontiguousarray(nodes, dtype=np.int32).reshape(-1, 2)
-        kp = [np.ascontiguousarray(k, dtype=KEYPOINT_DTYPE) for k in kps_per_frame]
-        counts = np.array([len(k) for k in kp], dtype=np.int32)
-        flat = np.ascontiguousarray(np.concatenate(kp) if len(kp) else np.zeros(0, KEYPOINT_DTYPE))
+        off, nd, kp, counts, flat = _host_tracks(kps_per_frame, track_offsets, nodes)
         P = np.ascontiguousarray(cameras, dtype=np.float64).reshape(len(kp), 12)
         n = len(off) - 1
         xyz, q = np.zeros((max(n, 1), 3)), np.zeros((max(n, 1), 3))
@@ -400,16 +407,8 @@ class Engine:
         [n_frames][12] float64; fixed [n_frames]; tracks as pgx_tracks_get gives them (track_offsets [n_tracks + 1], nodes
         [n_nodes][2]) or, with nodes=None, the `tracks` list of tracks_host; xyz [n_tracks][3]; track_flags [n_tracks] or None.
         -> dict(Rt [F][12], P [F][12], xyz [n][3], node_err [n_nodes], trace [max_iters + 1][2], report [8])"""
-        if nodes is None:
-            tracks = track_offsets
-            track_offsets = np.cumsum([0] + [len(t) for t in tracks])
-            nodes = [fk for t in tracks for fk in t]
-        off = np.ascontiguousarray(track_offsets, dtype=np.int32).reshape(-1)
-        nd = np.ascontiguousarray(nodes, dtype=np.int32).reshape(-1, 2)
-        kp = [np.ascontiguousarray(k, dtype=KEYPOINT_DTYPE) for k in kps_per_frame]
+        off, nd, kp, counts, flat = _host_tracks(kps_per_frame, track_offsets, nodes)
         nf = len(kp)
-        counts = np.array([len(k) for k in kp], dtype=np.int32)
-        flat = np.ascontiguousarray(np.concatenate(kp) if len(kp) else np.zeros(0, KEYPOINT_DTYPE))
         Kc = np.ascontiguousarray(K, dtype=np.float64).reshape(nf, 4)
         Rc = np.ascontiguousarray(Rt, dtype=np.float64).reshape(nf, 12)
         fx = np.ascontiguousarray(fixed, dtype=np.int32).reshape(nf)
@@ -449,16 +448,8 @@ class Engine:
         [n_frames][12] float64; reg [n_frames]; tracks as pgx_tracks_get gives them (track_offsets [n_tracks + 1], nodes
         [n_nodes][2]) or, with nodes=None, the `tracks` list of tracks_host; xyz [n_tracks][3]; track_flags [n_tracks] or None.
         -> dict(Rt [F][12], P [F][12], frame_stats [F][4], frame_err [F][2], node_inlier [n_nodes], report [8])"""
-        if nodes is None:
-            tracks = track_offsets
-            track_offsets = np.cumsum([0] + [len(t) for t in tracks])
-            nodes = [fk for t in tracks for fk in t]
-        off = np.ascontiguousarray(track_offsets, dtype=np.int32).reshape(-1)
-        nd = np.ascontiguousarray(nodes, dtype=np.int32).reshape(-1, 2)
-        kp = [np.ascontiguousarray(k, dtype=KEYPOINT_DTYPE) for k in kps_per_frame]
+        off, nd, kp, counts, flat = _host_tracks(kps_per_frame, track_offsets, nodes)
         nf = len(kp)
-        counts = np.array([len(k) for k in kp], dtype=np.int32)
-        flat = np.ascontiguousarray(np.concatenate(kp) if len(kp) else np.zeros(0, KEYPOINT_DTYPE))
         Kc = np.ascontiguousarray(K, dtype=np.float64).reshape(nf, 4)
         Rc = np.ascontiguousarray(Rt, dtype=np.float64).reshape(nf, 12)
         rg = np.ascontiguousarray(reg, dtype=np.int32).reshape(nf)

@@ -25,9 +25,7 @@
 // Determinism: per-track sums are xor butterflies over G = 16 lanes (their bits depend on the track's length only), the
 // reduced system's sums run in track order, and the sums over tracks are strided by 1024 and tree-reduced in a fixed shape.
 // Nothing depends on the grid, max_tracks, the slot layout or the run.  DESIGN.md section 16 has the measurements.
-#include "pgx_internal.h"
-
-#include <cmath>
+#include "pgx_trackgraph.h"
 
 namespace {
 
@@ -48,22 +46,19 @@ struct BaCtrl {
 };
 
 struct BaArgs {
-    const pgx_keypoint *kp;      // [F][stride] by slot
-    const int32_t *frame_ids;    // [F] or nullptr
+    TrackView tv;
     const double *K, *Rt_in;     // [n_frames][4], [n_frames][12]
     const int32_t *fixed;        // [n_frames]
-    const int32_t *offsets, *nodes, *track_summary;
     const double *xyz_in;        // [max_tracks][3]
     const int32_t *track_flags;  // [max_tracks] or nullptr
-    int F, stride, n_frames, max_tracks, max_iters;
-    long long node_cap;
+    int max_iters;
     double huber, lambda0;
     double *Rt_out, *P_out, *xyz_out, *node_err, *trace;
     int32_t *report;
     int *status;
     // workspace
     BaCtrl *ctrl;
-    int32_t *fstate, *inv, *free_frame, *cam_cnt, *csr_off; // [n_frames] x2, [128] x3
+    int32_t *fstate, *free_frame, *cam_cnt, *csr_off; // [n_frames], [128] x3
     double *cams;                // [2][n_frames][12] ping-pong by ctrl->sel
     double *S, *rhs, *dc;        // [BA_LD][BA_LD], [BA_LD], [BA_LD]
     double *X;                   // [2][max_tracks][3]
@@ -74,19 +69,6 @@ struct BaArgs {
     int32_t *ncf;                // [node_cap]: free number, -1 used in a fixed frame, -2 unused
     int32_t *csr_node, *csr_track;  // [node_cap]
 };
-
-template <int G> __device__ __forceinline__ double gsum(double x)
-{
-#pragma unroll
-    for (int m = 1; m < G; m <<= 1) x += __shfl_xor(x, m, G);
-    return x;
-}
-template <int G> __device__ __forceinline__ int gsum_i(int x)
-{
-#pragma unroll
-    for (int m = 1; m < G; m <<= 1) x += __shfl_xor(x, m, G);
-    return x;
-}
 
 // fixed-shape sum of v over the BA_RED threads of the workgroup (sh: BA_RED doubles of LDS); the result is in every thread
 __device__ double block_sum(double v, double *sh)
@@ -113,37 +95,6 @@ __device__ __forceinline__ void huber(double s, double delta, double &rho, doubl
         rho = 2.0 * delta * rs - delta * delta;
         w = delta / rs;
     }
-}
-
-// R' = Exp(omega) R (Rodrigues)
-__device__ __forceinline__ void rotate_left(const double *om, const double *R, double *Ro)
-{
-    const double th2 = om[0] * om[0] + om[1] * om[1] + om[2] * om[2];
-    double A, B;
-    if (th2 < 1e-8) {
-        A = 1.0 - th2 / 6.0;
-        B = 0.5 - th2 / 24.0;
-    } else {
-        const double th = sqrt(th2);
-        A = sin(th) / th;
-        B = (1.0 - cos(th)) / th2;
-    }
-    const double wx = om[0], wy = om[1], wz = om[2];
-    // E = I + A [w]x + B [w]x^2, [w]x^2 = w w^T - th2 I
-    double E[9];
-    E[0] = 1.0 + B * (wx * wx - th2);
-    E[1] = -A * wz + B * (wx * wy);
-    E[2] = A * wy + B * (wx * wz);
-    E[3] = A * wz + B * (wy * wx);
-    E[4] = 1.0 + B * (wy * wy - th2);
-    E[5] = -A * wx + B * (wy * wz);
-    E[6] = -A * wy + B * (wz * wx);
-    E[7] = A * wx + B * (wz * wy);
-    E[8] = 1.0 + B * (wz * wz - th2);
-#pragma unroll
-    for (int r = 0; r < 3; r++)
-#pragma unroll
-        for (int c = 0; c < 3; c++) Ro[3 * r + c] = (E[3 * r] * R[c] + E[3 * r + 1] * R[3 + c]) + E[3 * r + 2] * R[6 + c];
 }
 
 // one used observation: the residual, and the Jacobian rows wrt the point (jp) and the camera (jc = (omega, tau))
@@ -188,36 +139,18 @@ __device__ __forceinline__ void projection_only(const double *Rt, const double *
     rv = (K[1] * (y / z) + K[3]) - kv;
 }
 
-// keypoint of node o (a used node: the frame is valid and named by a slot)
+// keypoint of node o (a used node: node_ok)
 __device__ __forceinline__ void node_kp(const BaArgs &a, long long o, int &f, double &ku, double &kv)
 {
-    f = a.nodes[2 * o];
-    const int k = a.nodes[2 * o + 1];
-    const pgx_keypoint p = a.kp[(size_t)a.inv[f] * a.stride + k];
-    ku = (double)p.x;
-    kv = (double)p.y;
+    f = a.tv.nodes[2 * o];
+    node_keypoint(a.tv, f, a.tv.nodes[2 * o + 1], ku, kv);
 }
-
-__device__ __forceinline__ bool track_range(const BaArgs &a, long long t, int &o0, int &n)
-{
-    o0 = a.offsets[t];
-    const int o1 = a.offsets[t + 1];
-    const bool bad = o0 < 0 || o1 < o0 || (long long)o1 > a.node_cap;
-    n = bad ? 0 : o1 - o0;
-    return !bad;
-}
-
-#define BA_TRACK_LOOP                                                                          \
-    const long long gid = ((long long)blockIdx.x * blockDim.x + threadIdx.x) / BA_G;         \
-    const long long ngroups = (long long)gridDim.x * blockDim.x / BA_G;                        \
-    const int lane = threadIdx.x & (BA_G - 1);                                                 \
-    for (long long t = gid; t < nt; t += ngroups)
 
 // ---- once per call ---------------------------------------------------------------------------------------------------
 
 __global__ __launch_bounds__(BA_NT) void k_ba_frames(BaArgs a)
 {
-    for (int f = threadIdx.x; f < a.n_frames; f += blockDim.x) {
+    for (int f = threadIdx.x; f < a.tv.n_frames; f += blockDim.x) {
         const double *K = a.K + (size_t)f * 4, *R = a.Rt_in + (size_t)f * 12;
         bool fin = K[0] != 0.0 && K[1] != 0.0;
 #pragma unroll
@@ -242,22 +175,18 @@ __global__ __launch_bounds__(BA_NT) void k_ba_frames(BaArgs a)
         }
         a.fstate[f] = known ? (a.fixed[f] != 0 ? FS_FIXED : 0) : FS_UNKNOWN;
         for (int k = 0; k < 12; k++) a.cams[(size_t)f * 12 + k] = R[k];
-        a.inv[f] = -1;
+        a.tv.inv[f] = -1;
     }
     for (int c = threadIdx.x; c < BA_MAX_FREE; c += blockDim.x) {
         a.cam_cnt[c] = 0;
         a.free_frame[c] = -1;
     }
     __syncthreads();
-    for (int s = threadIdx.x; s < a.F; s += blockDim.x) {
-        const int f = a.frame_ids ? a.frame_ids[s] : s;
-        if (f < 0 || f >= a.n_frames) continue;
-        if (atomicCAS(&a.inv[f], -1, s) != -1) atomicOr(a.status, (int)PGX_ST_BA_DUP);
-    }
+    build_slot_inverse(a.tv, a.status, PGX_ST_BA_DUP);
     __syncthreads();
     if (threadIdx.x == 0) {
         int n_free = 0, n_fixed = 0;
-        for (int f = 0; f < a.n_frames; f++) {
+        for (int f = 0; f < a.tv.n_frames; f++) {
             const int st = a.fstate[f];
             if (st == FS_FIXED) n_fixed++;
             if (st >= 0) {
@@ -275,12 +204,7 @@ __global__ __launch_bounds__(BA_NT) void k_ba_frames(BaArgs a)
             atomicOr(a.status, (int)PGX_ST_BA_NOFIX);
             err = 1;
         }
-        int nt = a.track_summary[0];
-        nt = nt < 0 ? 0 : nt;
-        if (nt > a.max_tracks) {
-            atomicOr(a.status, (int)PGX_ST_BA_CAP);
-            nt = a.max_tracks;
-        }
+        const int nt = clamp_tracks(a.tv, a.status, PGX_ST_BA_CAP);
         BaCtrl *c = a.ctrl;
         c->lam = a.lambda0;
         c->C = 0.0;
@@ -309,21 +233,21 @@ __global__ __launch_bounds__(BA_NT) void k_ba_setup(BaArgs a)
 {
     const long long nt = a.ctrl->nt;
     const int err = a.ctrl->err;
-    BA_TRACK_LOOP
+    PGX_TRACK_LOOP(BA_G, nt)
     {
         int o0, n;
-        if (!track_range(a, t, o0, n) && lane == 0) atomicOr(a.status, (int)PGX_ST_BA_NODE);
+        if (!track_range(a.tv, t, o0, n) && lane == 0) atomicOr(a.status, (int)PGX_ST_BA_NODE);
         int used = 0, bad = 0, dup = 0;
         for (int i = lane; i < n; i += BA_G) {
             const long long o = (long long)o0 + i;
-            const int f = a.nodes[2 * o], k = a.nodes[2 * o + 1];
-            if (f < 0 || f >= a.n_frames || k < 0 || k >= a.stride || a.inv[f] < 0) {
+            const int f = a.tv.nodes[2 * o], k = a.tv.nodes[2 * o + 1];
+            if (!node_ok(a.tv, f, k)) {
                 bad = 1;
                 continue;
             }
             used += a.fstate[f] != FS_UNKNOWN;
             for (int j = 0; j < i; j++)   // two nodes in one frame: the track does not take part
-                if (a.nodes[2 * ((long long)o0 + j)] == f) dup = 1;
+                if (a.tv.nodes[2 * ((long long)o0 + j)] == f) dup = 1;
         }
         used = gsum_i<BA_G>(used);
         const int b1 = gsum_i<BA_G>(bad), b2 = gsum_i<BA_G>(dup);
@@ -333,9 +257,9 @@ __global__ __launch_bounds__(BA_NT) void k_ba_setup(BaArgs a)
                            used >= 2 && b2 == 0;
         for (int i = lane; i < n; i += BA_G) {
             const long long o = (long long)o0 + i;
-            const int f = a.nodes[2 * o], k = a.nodes[2 * o + 1];
+            const int f = a.tv.nodes[2 * o], k = a.tv.nodes[2 * o + 1];
             int c = -2;
-            if (takes && f >= 0 && f < a.n_frames && k >= 0 && k < a.stride && a.inv[f] >= 0 && a.fstate[f] != FS_UNKNOWN) {
+            if (takes && node_ok(a.tv, f, k) && a.fstate[f] != FS_UNKNOWN) {
                 c = a.fstate[f] >= 0 ? a.fstate[f] : -1;
                 if (c >= 0) atomicAdd(&a.cam_cnt[c], 1);
             }
@@ -369,7 +293,7 @@ __global__ __launch_bounds__(BA_NT) void k_ba_csr(BaArgs a)
             tot += a.cam_cnt[b];
         }
         a.csr_off[cam] = (int)st;
-        s_base = tot > a.node_cap ? -1 : (int)st;   // overlapping node ranges (malformed offsets): k_ba_start stops the call
+        s_base = tot > a.tv.node_cap ? -1 : (int)st;   // overlapping node ranges (malformed offsets): k_ba_start stops the call
     }
     __syncthreads();
     if (s_base < 0) return;
@@ -379,7 +303,7 @@ __global__ __launch_bounds__(BA_NT) void k_ba_csr(BaArgs a)
         int node = -1;
         if (t < nt && a.part[t] > 0) {
             int o0, n;
-            track_range(a, t, o0, n);
+            track_range(a.tv, t, o0, n);
             for (int i = 0; i < n; i++)
                 if (a.ncf[(long long)o0 + i] == cam) node = o0 + i;
         }
@@ -412,16 +336,16 @@ __global__ __launch_bounds__(BA_NT) void k_ba_lin(BaArgs a, int first)
     if (!first && (c->done || !c->relin)) return;
     const long long nt = c->nt;
     const int sel = c->sel;
-    const double *cams = a.cams + (size_t)sel * a.n_frames * 12;
-    const double *Xs = a.X + (size_t)sel * a.max_tracks * 3;
-    BA_TRACK_LOOP
+    const double *cams = a.cams + (size_t)sel * a.tv.n_frames * 12;
+    const double *Xs = a.X + (size_t)sel * a.tv.max_tracks * 3;
+    PGX_TRACK_LOOP(BA_G, nt)
     {
         if (a.part[t] == 0) {
             if (lane == 0) a.tcost[t] = 0.0;
             continue;
         }
         int o0, n;
-        track_range(a, t, o0, n);
+        track_range(a.tv, t, o0, n);
         const double X[3] = {Xs[3 * t], Xs[3 * t + 1], Xs[3 * t + 2]};
         double v[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, gv[3] = {0.0, 0.0, 0.0}, cost = 0.0;
         for (int i = lane; i < n; i += BA_G) {
@@ -492,7 +416,7 @@ __global__ __launch_bounds__(BA_RED) void k_ba_start(BaArgs a)
     if (threadIdx.x == 0) {
         long long tot = 0;
         for (int b = 0; b < c->n_free && b < BA_MAX_FREE; b++) tot += a.cam_cnt[b];
-        if (tot > a.node_cap) {
+        if (tot > a.tv.node_cap) {
             atomicOr(a.status, (int)PGX_ST_BA_NODE);
             c->err = 1;
         }
@@ -592,7 +516,7 @@ __global__ __launch_bounds__(BA_NT) void k_ba_schur(BaArgs a)
         for (int k = tid >> 6; k < nch; k += BA_NT / 64) {
             const int t = a.csr_track[beg + base + k];
             int o0, n;
-            track_range(a, t, o0, n);
+            track_range(a.tv, t, o0, n);
             for (int i = tid & 63; i < n; i += 64) {
                 const int cf = a.ncf[(long long)o0 + i];
                 if (cf >= 0) s_tab[k][cf] = o0 + i;
@@ -766,9 +690,9 @@ __global__ __launch_bounds__(BA_RED) void k_ba_solve(BaArgs a)
     }
     for (int i = tid; i < n; i += BA_RED) a.dc[i] = s_b[i];
     const int sel = c->sel;
-    const double *cur = a.cams + (size_t)sel * a.n_frames * 12;
-    double *trial = a.cams + (size_t)(1 - sel) * a.n_frames * 12;
-    for (int f = tid; f < a.n_frames; f += BA_RED) {
+    const double *cur = a.cams + (size_t)sel * a.tv.n_frames * 12;
+    double *trial = a.cams + (size_t)(1 - sel) * a.tv.n_frames * 12;
+    for (int f = tid; f < a.tv.n_frames; f += BA_RED) {
         const int st = a.fstate[f];
         const double *R = cur + (size_t)f * 12;
         double *T = trial + (size_t)f * 12;
@@ -798,10 +722,10 @@ __global__ __launch_bounds__(BA_NT) void k_ba_back(BaArgs a)
     if (c->done || c->pdfail) return;
     const long long nt = c->nt;
     const int sel = c->sel;
-    const double *Xs = a.X + (size_t)sel * a.max_tracks * 3;
-    double *Xt = a.X + (size_t)(1 - sel) * a.max_tracks * 3;
-    const double *trial = a.cams + (size_t)(1 - sel) * a.n_frames * 12;
-    BA_TRACK_LOOP
+    const double *Xs = a.X + (size_t)sel * a.tv.max_tracks * 3;
+    double *Xt = a.X + (size_t)(1 - sel) * a.tv.max_tracks * 3;
+    const double *trial = a.cams + (size_t)(1 - sel) * a.tv.n_frames * 12;
+    PGX_TRACK_LOOP(BA_G, nt)
     {
         if (a.part[t] == 0) {
             if (lane == 0) {
@@ -812,7 +736,7 @@ __global__ __launch_bounds__(BA_NT) void k_ba_back(BaArgs a)
             continue;
         }
         int o0, n;
-        track_range(a, t, o0, n);
+        track_range(a.tv, t, o0, n);
         // sum over free nodes of W_a^T dc_a = w Jp^T (Jc dc_a)
         double s[3] = {0.0, 0.0, 0.0};
         for (int i = lane; i < n; i += BA_G) {
@@ -923,13 +847,13 @@ __global__ __launch_bounds__(BA_NT) void k_ba_final(BaArgs a)
     const BaCtrl *c = a.ctrl;
     const long long nt = c->nt;
     const int sel = c->sel;
-    const double *cams = a.cams + (size_t)sel * a.n_frames * 12;
-    const double *Xs = a.X + (size_t)sel * a.max_tracks * 3;
+    const double *cams = a.cams + (size_t)sel * a.tv.n_frames * 12;
+    const double *Xs = a.X + (size_t)sel * a.tv.max_tracks * 3;
     const double NaN = __builtin_nan("");
-    BA_TRACK_LOOP
+    PGX_TRACK_LOOP(BA_G, nt)
     {
         int o0, n;
-        track_range(a, t, o0, n);
+        track_range(a.tv, t, o0, n);
         const bool takes = a.part[t] > 0;
         double X[3];
 #pragma unroll
@@ -960,22 +884,15 @@ __global__ __launch_bounds__(BA_NT) void k_ba_final(BaArgs a)
 __global__ __launch_bounds__(BA_NT) void k_ba_out(BaArgs a)
 {
     const BaCtrl *c = a.ctrl;
-    const double *cams = a.cams + (size_t)c->sel * a.n_frames * 12;
-    const double NaN = __builtin_nan("");
-    for (int f = threadIdx.x; f < a.n_frames; f += blockDim.x) {
+    const double *cams = a.cams + (size_t)c->sel * a.tv.n_frames * 12;
+    for (int f = threadIdx.x; f < a.tv.n_frames; f += blockDim.x) {
         const double *R = cams + (size_t)f * 12, *K = a.K + (size_t)f * 4;
         double *o = a.Rt_out + (size_t)f * 12, *P = a.P_out + (size_t)f * 12;
         const bool known = a.fstate[f] != FS_UNKNOWN;
         double r[12];
         for (int k = 0; k < 12; k++) r[k] = R[k];
         for (int k = 0; k < 12; k++) o[k] = r[k];
-        // K [R | t], column j of [R | t]: (R[j], R[3 + j], R[6 + j]) for j < 3, (t0, t1, t2) for j = 3
-        for (int j = 0; j < 4; j++) {
-            const double c0 = j < 3 ? r[j] : r[9], c1 = j < 3 ? r[3 + j] : r[10], c2 = j < 3 ? r[6 + j] : r[11];
-            P[j] = known ? K[0] * c0 + K[2] * c2 : NaN;
-            P[4 + j] = known ? K[1] * c1 + K[3] * c2 : NaN;
-            P[8 + j] = known ? c2 : NaN;
-        }
+        camera_matrix(K, r, known, P);
     }
     if (threadIdx.x == 0) {
         a.report[0] = c->it;
@@ -989,41 +906,35 @@ __global__ __launch_bounds__(BA_NT) void k_ba_out(BaArgs a)
     }
 }
 
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-struct Layout {
-    size_t ctrl, fstate, inv, free_frame, cam_cnt, csr_off, cams, S, rhs, dc, X, V, g, Vi, tcost, tdx, tx, part, nd, ncf, csr_node,
-        csr_track, total;
-    Layout(int n_frames, int max_tracks, long long node_cap)
-    {
-        const size_t T = (size_t)(max_tracks > 0 ? max_tracks : 1), N = (size_t)(node_cap > 0 ? node_cap : 1);
-        size_t at = 0;
-        auto put = [&at](size_t bytes) { const size_t p = at; at += align256(bytes); return p; };
-        ctrl = put(sizeof(BaCtrl));
-        fstate = put((size_t)n_frames * 4);
-        inv = put((size_t)n_frames * 4);
-        free_frame = put(BA_MAX_FREE * 4);
-        cam_cnt = put(BA_MAX_FREE * 4);
-        csr_off = put(BA_MAX_FREE * 4);
-        cams = put((size_t)2 * n_frames * 12 * 8);
-        S = put((size_t)BA_LD * BA_LD * 8);
-        rhs = put(BA_LD * 8);
-        dc = put(BA_LD * 8);
-        X = put(2 * T * 3 * 8);
-        V = put(T * 6 * 8);
-        g = put(T * 3 * 8);
-        Vi = put(T * 6 * 8);
-        tcost = put(T * 8);
-        tdx = put(T * 8);
-        tx = put(T * 8);
-        part = put(T * 4);
-        nd = put(N * BA_ND * 8);
-        ncf = put(N * 4);
-        csr_node = put(N * 4);
-        csr_track = put(N * 4);
-        total = at;
-    }
-};
+// the workspace, described once: a's workspace pointers (none valid for ws = nullptr) and the bytes
+size_t ba_carve(BaArgs &a, void *ws, int n_frames, int max_tracks, long long node_cap)
+{
+    const size_t T = (size_t)(max_tracks > 0 ? max_tracks : 1), N = (size_t)(node_cap > 0 ? node_cap : 1);
+    WsCarver w(ws);
+    a.ctrl = w.take<BaCtrl>(sizeof(BaCtrl));
+    a.fstate = w.take<int32_t>((size_t)n_frames * 4);
+    a.tv.inv = w.take<int32_t>((size_t)n_frames * 4);
+    a.free_frame = w.take<int32_t>(BA_MAX_FREE * 4);
+    a.cam_cnt = w.take<int32_t>(BA_MAX_FREE * 4);
+    a.csr_off = w.take<int32_t>(BA_MAX_FREE * 4);
+    a.cams = w.take<double>((size_t)2 * n_frames * 12 * 8);
+    a.S = w.take<double>((size_t)BA_LD * BA_LD * 8);
+    a.rhs = w.take<double>(BA_LD * 8);
+    a.dc = w.take<double>(BA_LD * 8);
+    a.X = w.take<double>(2 * T * 3 * 8);
+    a.V = w.take<double>(T * 6 * 8);
+    a.g = w.take<double>(T * 3 * 8);
+    a.Vi = w.take<double>(T * 6 * 8);
+    a.tcost = w.take<double>(T * 8);
+    a.tdx = w.take<double>(T * 8);
+    a.tx = w.take<double>(T * 8);
+    a.part = w.take<int32_t>(T * 4);
+    a.nd = w.take<double>(N * BA_ND * 8);
+    a.ncf = w.take<int32_t>(N * 4);
+    a.csr_node = w.take<int32_t>(N * 4);
+    a.csr_track = w.take<int32_t>(N * 4);
+    return w.total();
+}
 
 int track_grid(int max_tracks)
 {
@@ -1033,7 +944,11 @@ int track_grid(int max_tracks)
 
 } // namespace
 
-size_t pgx_bundle_ws_bytes(int n_frames, int max_tracks, long long node_cap) { return Layout(n_frames, max_tracks, node_cap).total; }
+size_t pgx_bundle_ws_bytes(int n_frames, int max_tracks, long long node_cap)
+{
+    BaArgs a;
+    return ba_carve(a, nullptr, n_frames, max_tracks, node_cap);
+}
 
 void pgx_launch_bundle(hipStream_t s, const pgx_keypoint *d_kp, int F, int stride, const int32_t *d_frame_ids, int n_frames,
                        const double *d_K, const double *d_Rt_in, const int32_t *d_fixed, const int32_t *d_offsets, const int32_t *d_nodes,
@@ -1042,22 +957,13 @@ void pgx_launch_bundle(hipStream_t s, const pgx_keypoint *d_kp, int F, int strid
                        double *d_xyz_out, double *d_node_err, double *d_trace, int32_t *d_report, void *ws, int *status)
 {
     BaArgs a;
-    a.kp = d_kp;
-    a.frame_ids = d_frame_ids;
+    a.tv = TrackView{d_kp, d_frame_ids, d_offsets, d_nodes, d_track_summary, F, stride, n_frames, max_tracks, node_cap, nullptr};
     a.K = d_K;
     a.Rt_in = d_Rt_in;
     a.fixed = d_fixed;
-    a.offsets = d_offsets;
-    a.nodes = d_nodes;
-    a.track_summary = d_track_summary;
     a.xyz_in = d_xyz_in;
     a.track_flags = d_track_flags;
-    a.F = F;
-    a.stride = stride;
-    a.n_frames = n_frames;
-    a.max_tracks = max_tracks;
     a.max_iters = max_iters;
-    a.node_cap = node_cap;
     a.huber = huber_px;
     a.lambda0 = lambda0;
     a.Rt_out = d_Rt_out;
@@ -1067,30 +973,7 @@ void pgx_launch_bundle(hipStream_t s, const pgx_keypoint *d_kp, int F, int strid
     a.trace = d_trace;
     a.report = d_report;
     a.status = status;
-    const Layout L(n_frames, max_tracks, node_cap);
-    char *w = static_cast<char *>(ws);
-    a.ctrl = reinterpret_cast<BaCtrl *>(w + L.ctrl);
-    a.fstate = reinterpret_cast<int32_t *>(w + L.fstate);
-    a.inv = reinterpret_cast<int32_t *>(w + L.inv);
-    a.free_frame = reinterpret_cast<int32_t *>(w + L.free_frame);
-    a.cam_cnt = reinterpret_cast<int32_t *>(w + L.cam_cnt);
-    a.csr_off = reinterpret_cast<int32_t *>(w + L.csr_off);
-    a.cams = reinterpret_cast<double *>(w + L.cams);
-    a.S = reinterpret_cast<double *>(w + L.S);
-    a.rhs = reinterpret_cast<double *>(w + L.rhs);
-    a.dc = reinterpret_cast<double *>(w + L.dc);
-    a.X = reinterpret_cast<double *>(w + L.X);
-    a.V = reinterpret_cast<double *>(w + L.V);
-    a.g = reinterpret_cast<double *>(w + L.g);
-    a.Vi = reinterpret_cast<double *>(w + L.Vi);
-    a.tcost = reinterpret_cast<double *>(w + L.tcost);
-    a.tdx = reinterpret_cast<double *>(w + L.tdx);
-    a.tx = reinterpret_cast<double *>(w + L.tx);
-    a.part = reinterpret_cast<int32_t *>(w + L.part);
-    a.nd = reinterpret_cast<double *>(w + L.nd);
-    a.ncf = reinterpret_cast<int32_t *>(w + L.ncf);
-    a.csr_node = reinterpret_cast<int32_t *>(w + L.csr_node);
-    a.csr_track = reinterpret_cast<int32_t *>(w + L.csr_track);
+    ba_carve(a, ws, n_frames, max_tracks, node_cap);
     const int grid = track_grid(max_tracks);
     hipLaunchKernelGGL(k_ba_frames, dim3(1), dim3(BA_NT), 0, s, a);
     hipLaunchKernelGGL(k_ba_setup, dim3(grid), dim3(BA_NT), 0, s, a);

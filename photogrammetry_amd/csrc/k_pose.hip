@@ -20,17 +20,9 @@
 //
 // One thread per RANSAC sample (the work of a sample is a 9x9 symmetric eigenproblem plus one pass over the pair's
 // match list); a second kernel per image pair picks the first best sample; a third does the pose.
-#include "pgx_internal.h"
+#include "pgx_trackgraph.h"   // splitmix64
 
 namespace {
-
-__device__ __forceinline__ uint64_t splitmix64(uint64_t &s)
-{
-    uint64_t z = (s += 0x9E3779B97F4A7C15ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
 
 // cyclic Jacobi on a symmetric N x N matrix (float64); on return A holds the eigenvalues on its diagonal and the
 // columns of V the eigenvectors

@@ -25,9 +25,7 @@
 //   k_reg_summary  one workgroup: the report, integer sums over the frames
 // Samples run in chunks so that the hypothesis buffer stays bounded; the chunk size changes no result.
 // DESIGN.md section 17 has the measurements.
-#include "pgx_internal.h"
-
-#include <cmath>
+#include "pgx_trackgraph.h"
 
 namespace {
 
@@ -38,15 +36,12 @@ constexpr int REG_HD = 12;          // doubles per hypothesis: R row-major, t_S
 constexpr long long REG_CHUNK_CELLS = 1 << 17;  // (target slots x samples) per chunk, at most (25 MB of hypotheses)
 
 struct RegArgs {
-    const pgx_keypoint *kp;      // [F][stride] by slot
-    const int32_t *frame_ids;    // [F] or nullptr
+    TrackView tv;
     const double *K, *Rt_in;     // [n_frames][4], [n_frames][12]
     const int32_t *reg;          // [n_frames]
-    const int32_t *offsets, *nodes, *track_summary;
     const double *xyz;           // [max_tracks][3]
     const int32_t *track_flags;  // [max_tracks] or nullptr
-    int F, stride, n_frames, max_tracks, n_samples, min_inliers, refine_iters, nblk;
-    long long node_cap;
+    int n_samples, min_inliers, refine_iters, nblk;
     double inlier_px;
     uint64_t seed;
     double *Rt_out, *P_out, *frame_err;
@@ -54,7 +49,7 @@ struct RegArgs {
     int *status;
     // workspace
     int32_t *ctrl;               // [0] tracks to process, [1] targets
-    int32_t *inv, *tnum, *tframe, *cnt, *coff, *nlist;  // [n_frames] each
+    int32_t *tnum, *tframe, *cnt, *coff, *nlist;  // [n_frames] each
     int32_t *cf;                 // [node_cap]: target number of a correspondence node, else -1
     int32_t *corr_node;          // [node_cap]
     double *cx, *cy, *cz, *cu, *cv;  // [node_cap] each, by position coff[target] + j
@@ -65,46 +60,9 @@ struct RegArgs {
     unsigned long long *best;    // [n_frames][nblk]
 };
 
-__device__ __forceinline__ uint64_t splitmix64(uint64_t &s)
-{
-    uint64_t z = (s += 0x9E3779B97F4A7C15ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
-template <int G> __device__ __forceinline__ int gsum_i(int x)
-{
-#pragma unroll
-    for (int m = 1; m < G; m <<= 1) x += __shfl_xor(x, m, G);
-    return x;
-}
-
-__device__ __forceinline__ double wsum(double x)
-{
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) x += __shfl_xor(x, m, 64);
-    return x;
-}
-
-__device__ __forceinline__ double nan_max(double a, double b)
-{
-    if (a != a || b != b) return __builtin_nan("");
-    return a > b ? a : b;
-}
-
 __device__ __forceinline__ bool good_k(const double *K)
 {
     return isfinite(K[0]) && isfinite(K[1]) && isfinite(K[2]) && isfinite(K[3]) && K[0] != 0.0 && K[1] != 0.0;
-}
-
-__device__ __forceinline__ bool track_range(const RegArgs &a, long long t, int &o0, int &n)
-{
-    o0 = a.offsets[t];
-    const int o1 = a.offsets[t + 1];
-    const bool bad = o0 < 0 || o1 < o0 || (long long)o1 > a.node_cap;
-    n = bad ? 0 : o1 - o0;
-    return !bad;
 }
 
 // ---- P3P (Lambda Twist, Persson and Nordberg, ECCV 2018) -----------------------------------------------------------
@@ -394,43 +352,13 @@ __device__ __forceinline__ bool inlier(const double (&R)[9], const double (&t)[3
     return z > 0.0 && pa * pa + pb * pb <= e * e;
 }
 
-// R' = Exp(omega) R (Rodrigues), as k_bundle.hip
-__device__ __forceinline__ void rotate_left(const double *om, const double (&R)[9], double (&Ro)[9])
-{
-    const double th2 = om[0] * om[0] + om[1] * om[1] + om[2] * om[2];
-    double A, B;
-    if (th2 < 1e-8) {
-        A = 1.0 - th2 / 6.0;
-        B = 0.5 - th2 / 24.0;
-    } else {
-        const double th = sqrt(th2);
-        A = sin(th) / th;
-        B = (1.0 - cos(th)) / th2;
-    }
-    const double wx = om[0], wy = om[1], wz = om[2];
-    double E[9];
-    E[0] = 1.0 + B * (wx * wx - th2);
-    E[1] = -A * wz + B * (wx * wy);
-    E[2] = A * wy + B * (wx * wz);
-    E[3] = A * wz + B * (wy * wx);
-    E[4] = 1.0 + B * (wy * wy - th2);
-    E[5] = -A * wx + B * (wy * wz);
-    E[6] = -A * wy + B * (wz * wx);
-    E[7] = A * wx + B * (wz * wy);
-    E[8] = 1.0 + B * (wz * wz - th2);
-#pragma unroll
-    for (int r = 0; r < 3; r++)
-#pragma unroll
-        for (int c = 0; c < 3; c++) Ro[3 * r + c] = (E[3 * r] * R[c] + E[3 * r + 1] * R[3 + c]) + E[3 * r + 2] * R[6 + c];
-}
-
 // ---- kernels -------------------------------------------------------------------------------------------------------
 
 __global__ __launch_bounds__(REG_NT) void k_reg_frames(RegArgs a)
 {
     const double NaN = __builtin_nan("");
-    for (int f = threadIdx.x; f < a.n_frames; f += blockDim.x) {
-        a.inv[f] = -1;
+    for (int f = threadIdx.x; f < a.tv.n_frames; f += blockDim.x) {
+        a.tv.inv[f] = -1;
         a.cnt[f] = 0;
         const double *K = a.K + (size_t)f * 4;
         const bool target = a.reg[f] != 0, kok = good_k(K);
@@ -444,25 +372,16 @@ __global__ __launch_bounds__(REG_NT) void k_reg_frames(RegArgs a)
             known = known && isfinite(r[k]);
         }
         for (int k = 0; k < 12; k++) o[k] = r[k];
-        for (int j = 0; j < 4; j++) {
-            const double c0 = j < 3 ? r[j] : r[9], c1 = j < 3 ? r[3 + j] : r[10], c2 = j < 3 ? r[6 + j] : r[11];
-            P[j] = known ? K[0] * c0 + K[2] * c2 : NaN;
-            P[4 + j] = known ? K[1] * c1 + K[3] * c2 : NaN;
-            P[8 + j] = known ? c2 : NaN;
-        }
+        camera_matrix(K, r, known, P);
         for (int k = 0; k < 4; k++) a.frame_stats[(size_t)f * 4 + k] = -1;
         a.frame_err[2 * f] = NaN;
         a.frame_err[2 * f + 1] = NaN;
     }
     __syncthreads();
-    for (int s = threadIdx.x; s < a.F; s += blockDim.x) {
-        const int f = a.frame_ids ? a.frame_ids[s] : s;
-        if (f < 0 || f >= a.n_frames) continue;
-        if (atomicCAS(&a.inv[f], -1, s) != -1) atomicOr(a.status, (int)PGX_ST_REG_DUP);
-    }
+    build_slot_inverse(a.tv, a.status, PGX_ST_REG_DUP);
     if (threadIdx.x == 0) {
         int n = 0;
-        for (int f = 0; f < a.n_frames; f++) {
+        for (int f = 0; f < a.tv.n_frames; f++) {
             const bool on = a.reg[f] != 0 && good_k(a.K + (size_t)f * 4);
             a.tnum[f] = on ? n : -1;
             if (on) a.tframe[n++] = f;
@@ -479,13 +398,7 @@ __global__ __launch_bounds__(REG_NT) void k_reg_frames(RegArgs a)
                 a.frame_err[2 * f + 1] = NaN;
             }
         }
-        int nt = a.track_summary[0];
-        nt = nt < 0 ? 0 : nt;
-        if (nt > a.max_tracks) {
-            atomicOr(a.status, (int)PGX_ST_REG_CAP);
-            nt = a.max_tracks;
-        }
-        a.ctrl[0] = nt;
+        a.ctrl[0] = clamp_tracks(a.tv, a.status, PGX_ST_REG_CAP);
         a.ctrl[1] = n;
     }
 }
@@ -493,25 +406,23 @@ __global__ __launch_bounds__(REG_NT) void k_reg_frames(RegArgs a)
 __global__ __launch_bounds__(REG_NT) void k_reg_count(RegArgs a)
 {
     const long long nt = a.ctrl[0];
-    const long long gid = ((long long)blockIdx.x * blockDim.x + threadIdx.x) / REG_G;
-    const long long ngroups = (long long)gridDim.x * blockDim.x / REG_G;
-    const int lane = threadIdx.x & (REG_G - 1);
-    for (long long t = gid; t < nt; t += ngroups) {
+    PGX_TRACK_LOOP(REG_G, nt)
+    {
         int o0, n;
-        if (!track_range(a, t, o0, n) && lane == 0) atomicOr(a.status, (int)PGX_ST_REG_NODE);
+        if (!track_range(a.tv, t, o0, n) && lane == 0) atomicOr(a.status, (int)PGX_ST_REG_NODE);
         const bool pt = (!a.track_flags || a.track_flags[t] == 0) && isfinite(a.xyz[3 * t]) && isfinite(a.xyz[3 * t + 1]) &&
                         isfinite(a.xyz[3 * t + 2]);
         int bad = 0, twice = 0;
         for (int i = lane; i < n; i += REG_G) {
             const long long o = (long long)o0 + i;
-            const int f = a.nodes[2 * o], k = a.nodes[2 * o + 1];
+            const int f = a.tv.nodes[2 * o], k = a.tv.nodes[2 * o + 1];
             int c = -1;
-            if (f < 0 || f >= a.n_frames || k < 0 || k >= a.stride || a.inv[f] < 0) {
+            if (!node_ok(a.tv, f, k)) {
                 bad = 1;
             } else if (a.tnum[f] >= 0) {
                 bool dup = false;
                 for (int j = 0; j < n; j++)
-                    if (j != i && a.nodes[2 * ((long long)o0 + j)] == f) dup = true;
+                    if (j != i && a.tv.nodes[2 * ((long long)o0 + j)] == f) dup = true;
                 if (dup) twice = 1;
                 if (!dup && pt) {
                     c = a.tnum[f];
@@ -542,7 +453,7 @@ __global__ __launch_bounds__(REG_NT) void k_reg_csr(RegArgs a)
         long long st = 0;
         for (int b = 0; b < c; b++) st += a.cnt[b];
         const long long end = st + a.cnt[c];
-        const bool fits = end <= a.node_cap;   // overlapping node ranges (malformed offsets) can count a node twice
+        const bool fits = end <= a.tv.node_cap;   // overlapping node ranges (malformed offsets) can count a node twice
         if (!fits) atomicOr(a.status, (int)PGX_ST_REG_NODE);
         a.coff[c] = fits ? (int)st : 0;
         s_base = fits ? (int)st : 0;
@@ -556,7 +467,7 @@ __global__ __launch_bounds__(REG_NT) void k_reg_csr(RegArgs a)
         int node = -1;
         if (t < nt) {
             int o0, n;
-            track_range(a, t, o0, n);
+            track_range(a.tv, t, o0, n);
             for (int i = 0; i < n; i++)
                 if (a.cf[(long long)o0 + i] == c) node = o0 + i;
         }
@@ -567,14 +478,14 @@ __global__ __launch_bounds__(REG_NT) void k_reg_csr(RegArgs a)
         for (int w = 0; w < wave; w++) pos += s_wave[w];
         pos += __popcll(m & ((1ull << ln) - 1ull));
         if (node >= 0 && pos < stop) {
-            const int k = a.nodes[2 * (long long)node + 1];
-            const pgx_keypoint p = a.kp[(size_t)a.inv[f] * a.stride + k];
+            double u, v;
+            node_keypoint(a.tv, f, a.tv.nodes[2 * (long long)node + 1], u, v);
             a.corr_node[pos] = node;
             a.cx[pos] = a.xyz[3 * (long long)t];
             a.cy[pos] = a.xyz[3 * (long long)t + 1];
             a.cz[pos] = a.xyz[3 * (long long)t + 2];
-            a.cu[pos] = a.K[(size_t)f * 4 + 2] - (double)p.x;
-            a.cv[pos] = a.K[(size_t)f * 4 + 3] - (double)p.y;
+            a.cu[pos] = a.K[(size_t)f * 4 + 2] - u;
+            a.cv[pos] = a.K[(size_t)f * 4 + 3] - v;
         }
         __syncthreads();
         if (threadIdx.x == 0) {
@@ -696,7 +607,7 @@ __global__ __launch_bounds__(REG_NT) void k_reg_score(RegArgs a, int s0, int chu
 template <int NV> __device__ __forceinline__ void block_sums(double (&v)[NV], double (*sh)[REG_NT / 64])
 {
 #pragma unroll
-    for (int k = 0; k < NV; k++) v[k] = wsum(v[k]);
+    for (int k = 0; k < NV; k++) v[k] = gsum<64>(v[k]);
     const int w = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0)
 #pragma unroll
@@ -908,8 +819,7 @@ __global__ __launch_bounds__(REG_NT) void k_reg_refine(RegArgs a)
             v[1] += e2;
             mx = nan_max(mx, sqrt(e2));
         }
-#pragma unroll
-        for (int mk = 1; mk < 64; mk <<= 1) mx = nan_max(mx, __shfl_xor(mx, mk, 64));
+        mx = gmax<64>(mx);
         block_sums<2>(v, s_sum);
         if ((threadIdx.x & 63) == 0) s_sum[2][threadIdx.x >> 6] = mx;
         __syncthreads();
@@ -937,12 +847,7 @@ __global__ __launch_bounds__(REG_NT) void k_reg_refine(RegArgs a)
         for (int k = 0; k < 3; k++) r[9 + k] = good ? t[k] - ((R[3 * k] * S0 + R[3 * k + 1] * S1) + R[3 * k + 2] * S2) : NaN;
         double *o = a.Rt_out + (size_t)f * 12, *P = a.P_out + (size_t)f * 12;
         for (int k = 0; k < 12; k++) o[k] = r[k];
-        for (int j = 0; j < 4; j++) {
-            const double c0 = j < 3 ? r[j] : r[9], c1 = j < 3 ? r[3 + j] : r[10], c2 = j < 3 ? r[6 + j] : r[11];
-            P[j] = K[0] * c0 + K[2] * c2;
-            P[4 + j] = K[1] * c1 + K[3] * c2;
-            P[8 + j] = c2;
-        }
+        camera_matrix(K, r, true, P);   // NaN rows come from r itself
         int32_t *st = a.frame_stats + (size_t)f * 4;
         st[0] = n;
         st[1] = fin;
@@ -957,7 +862,7 @@ __global__ __launch_bounds__(REG_NT) void k_reg_summary(RegArgs a)
     if (threadIdx.x < 8) s_acc[threadIdx.x] = 0;
     __syncthreads();
     int acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int f = threadIdx.x; f < a.n_frames; f += blockDim.x) {
+    for (int f = threadIdx.x; f < a.tv.n_frames; f += blockDim.x) {
         if (a.reg[f] == 0) continue;
         const int32_t *st = a.frame_stats + (size_t)f * 4;
         acc[0] += 1;
@@ -974,8 +879,6 @@ __global__ __launch_bounds__(REG_NT) void k_reg_summary(RegArgs a)
     if (threadIdx.x < 8) a.report[threadIdx.x] = s_acc[threadIdx.x];
 }
 
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 int reg_chunk(int n_frames, int n_samples)
 {
     long long ch = REG_CHUNK_CELLS / (n_frames > 0 ? n_frames : 1);
@@ -984,42 +887,42 @@ int reg_chunk(int n_frames, int n_samples)
     return (int)(ch < all ? ch : all);
 }
 
-struct Layout {
-    size_t ctrl, inv, tnum, tframe, cnt, coff, nlist, cf, corr_node, cx, cy, cz, cu, cv, S, win, winfo, hyp, best, total;
-    int chunk, nblk;
-    Layout(int n_frames, long long node_cap, int n_samples)
-    {
-        const size_t N = (size_t)(node_cap > 0 ? node_cap : 1), NF = (size_t)n_frames;
-        chunk = reg_chunk(n_frames, n_samples);
-        nblk = (int)((4ll * n_samples + REG_NT - 1) / REG_NT);
-        size_t at = 0;
-        auto put = [&at](size_t bytes) { const size_t p = at; at += align256(bytes); return p; };
-        ctrl = put(8 * 4);
-        inv = put(NF * 4);
-        tnum = put(NF * 4);
-        tframe = put(NF * 4);
-        cnt = put(NF * 4);
-        coff = put(NF * 4);
-        nlist = put(NF * 4);
-        cf = put(N * 4);
-        corr_node = put(N * 4);
-        cx = put(N * 8);
-        cy = put(N * 8);
-        cz = put(N * 8);
-        cu = put(N * 8);
-        cv = put(N * 8);
-        S = put(NF * 4 * 8);
-        win = put(NF * 16 * 8);
-        winfo = put(NF * 2 * 4);
-        hyp = put(NF * (size_t)chunk * 4 * REG_HD * 8);
-        best = put(NF * (size_t)nblk * 8);
-        total = at;
-    }
-};
+// the workspace, described once: a's workspace pointers (none valid for ws = nullptr) and nblk; the bytes
+size_t reg_carve(RegArgs &a, void *ws, int n_frames, long long node_cap, int n_samples)
+{
+    const size_t N = (size_t)(node_cap > 0 ? node_cap : 1), NF = (size_t)n_frames;
+    const size_t chunk = (size_t)reg_chunk(n_frames, n_samples);
+    a.nblk = (int)((4ll * n_samples + REG_NT - 1) / REG_NT);
+    WsCarver w(ws);
+    a.ctrl = w.take<int32_t>(8 * 4);
+    a.tv.inv = w.take<int32_t>(NF * 4);
+    a.tnum = w.take<int32_t>(NF * 4);
+    a.tframe = w.take<int32_t>(NF * 4);
+    a.cnt = w.take<int32_t>(NF * 4);
+    a.coff = w.take<int32_t>(NF * 4);
+    a.nlist = w.take<int32_t>(NF * 4);
+    a.cf = w.take<int32_t>(N * 4);
+    a.corr_node = w.take<int32_t>(N * 4);
+    a.cx = w.take<double>(N * 8);
+    a.cy = w.take<double>(N * 8);
+    a.cz = w.take<double>(N * 8);
+    a.cu = w.take<double>(N * 8);
+    a.cv = w.take<double>(N * 8);
+    a.S = w.take<double>(NF * 4 * 8);
+    a.win = w.take<double>(NF * 16 * 8);
+    a.winfo = w.take<int32_t>(NF * 2 * 4);
+    a.hyp = w.take<double>(NF * chunk * 4 * REG_HD * 8);
+    a.best = w.take<unsigned long long>(NF * (size_t)a.nblk * 8);
+    return w.total();
+}
 
 } // namespace
 
-size_t pgx_register_ws_bytes(int n_frames, long long node_cap, int n_samples) { return Layout(n_frames, node_cap, n_samples).total; }
+size_t pgx_register_ws_bytes(int n_frames, long long node_cap, int n_samples)
+{
+    RegArgs a;
+    return reg_carve(a, nullptr, n_frames, node_cap, n_samples);
+}
 
 void pgx_launch_register(hipStream_t s, const pgx_keypoint *d_kp, int F, int stride, const int32_t *d_frame_ids, int n_frames,
                          const double *d_K, const double *d_Rt_in, const int32_t *d_register, const int32_t *d_offsets,
@@ -1029,24 +932,15 @@ void pgx_launch_register(hipStream_t s, const pgx_keypoint *d_kp, int F, int str
                          double *d_frame_err, int32_t *d_node_inlier, int32_t *d_report, void *ws, int *status)
 {
     RegArgs a;
-    a.kp = d_kp;
-    a.frame_ids = d_frame_ids;
+    a.tv = TrackView{d_kp, d_frame_ids, d_offsets, d_nodes, d_track_summary, F, stride, n_frames, max_tracks, node_cap, nullptr};
     a.K = d_K;
     a.Rt_in = d_Rt_in;
     a.reg = d_register;
-    a.offsets = d_offsets;
-    a.nodes = d_nodes;
-    a.track_summary = d_track_summary;
     a.xyz = d_xyz;
     a.track_flags = d_track_flags;
-    a.F = F;
-    a.stride = stride;
-    a.n_frames = n_frames;
-    a.max_tracks = max_tracks;
     a.n_samples = n_samples;
     a.min_inliers = min_inliers;
     a.refine_iters = refine_iters;
-    a.node_cap = node_cap;
     a.inlier_px = inlier_px;
     a.seed = seed;
     a.Rt_out = d_Rt_out;
@@ -1056,36 +950,16 @@ void pgx_launch_register(hipStream_t s, const pgx_keypoint *d_kp, int F, int str
     a.node_inlier = d_node_inlier;
     a.report = d_report;
     a.status = status;
-    const Layout L(n_frames, node_cap, n_samples);
-    a.nblk = L.nblk;
-    char *w = static_cast<char *>(ws);
-    a.ctrl = reinterpret_cast<int32_t *>(w + L.ctrl);
-    a.inv = reinterpret_cast<int32_t *>(w + L.inv);
-    a.tnum = reinterpret_cast<int32_t *>(w + L.tnum);
-    a.tframe = reinterpret_cast<int32_t *>(w + L.tframe);
-    a.cnt = reinterpret_cast<int32_t *>(w + L.cnt);
-    a.coff = reinterpret_cast<int32_t *>(w + L.coff);
-    a.nlist = reinterpret_cast<int32_t *>(w + L.nlist);
-    a.cf = reinterpret_cast<int32_t *>(w + L.cf);
-    a.corr_node = reinterpret_cast<int32_t *>(w + L.corr_node);
-    a.cx = reinterpret_cast<double *>(w + L.cx);
-    a.cy = reinterpret_cast<double *>(w + L.cy);
-    a.cz = reinterpret_cast<double *>(w + L.cz);
-    a.cu = reinterpret_cast<double *>(w + L.cu);
-    a.cv = reinterpret_cast<double *>(w + L.cv);
-    a.S = reinterpret_cast<double *>(w + L.S);
-    a.win = reinterpret_cast<double *>(w + L.win);
-    a.winfo = reinterpret_cast<int32_t *>(w + L.winfo);
-    a.hyp = reinterpret_cast<double *>(w + L.hyp);
-    a.best = reinterpret_cast<unsigned long long *>(w + L.best);
+    reg_carve(a, ws, n_frames, node_cap, n_samples);
+    const int chunk = reg_chunk(n_frames, n_samples);
     const long long want = ((long long)max_tracks * REG_G + REG_NT - 1) / REG_NT;
     const int grid = (int)(want < 1 ? 1 : (want > REG_GRID_MAX ? REG_GRID_MAX : want));
     hipLaunchKernelGGL(k_reg_frames, dim3(1), dim3(REG_NT), 0, s, a);
     hipLaunchKernelGGL(k_reg_count, dim3(grid), dim3(REG_NT), 0, s, a);
     hipLaunchKernelGGL(k_reg_csr, dim3(n_frames), dim3(REG_NT), 0, s, a);
-    for (int s0 = 0; s0 < n_samples; s0 += L.chunk) {
-        hipLaunchKernelGGL(k_reg_hyp, dim3((L.chunk + REG_NT - 1) / REG_NT, n_frames), dim3(REG_NT), 0, s, a, s0, L.chunk);
-        hipLaunchKernelGGL(k_reg_score, dim3(4 * L.chunk / REG_NT, n_frames), dim3(REG_NT), 0, s, a, s0, L.chunk);
+    for (int s0 = 0; s0 < n_samples; s0 += chunk) {
+        hipLaunchKernelGGL(k_reg_hyp, dim3((chunk + REG_NT - 1) / REG_NT, n_frames), dim3(REG_NT), 0, s, a, s0, chunk);
+        hipLaunchKernelGGL(k_reg_score, dim3(4 * chunk / REG_NT, n_frames), dim3(REG_NT), 0, s, a, s0, chunk);
     }
     hipLaunchKernelGGL(k_reg_pick, dim3(n_frames), dim3(REG_NT), 0, s, a);
     hipLaunchKernelGGL(k_reg_refine, dim3(n_frames), dim3(REG_NT), 0, s, a);

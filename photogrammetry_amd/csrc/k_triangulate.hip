@@ -4,9 +4,8 @@
 // Utils.CreatePointCloud.  Here every track of pgx_tracks_dev / pgx_tracks_split_dev becomes one point, over all its views.
 //
 // Kernels (three launches, all on the caller's stream; n_tracks is read on the device):
-//   k_tri_frames   one workgroup: per frame the camera's state (centre C = -M^-1 p4, sign det M, ||m3||, known) and the
-//                  inverse of the slot -> frame map (atomicCAS: a second slot naming a frame sets PGX_ST_TRI_DUP); the
-//                  number of tracks to process = min(n_tracks, max_tracks) (more: PGX_ST_TRI_CAP)
+//   k_tri_frames   one workgroup: per frame the camera's state (centre C = -M^-1 p4, sign det M, ||m3||, known), the
+//                  slot -> frame inverse (PGX_ST_TRI_DUP) and the number of tracks to process (PGX_ST_TRI_CAP)
 //   k_tri_tracks   persistent, grid-stride over the tracks in three phases by length: tracks of more than 32 nodes get a
 //                  whole wave (G = 64 lanes), 9..32 nodes a quarter wave (G = 16), 0..8 nodes G = 4 lanes.  Lane l of a
 //                  group takes the observations l, l + G, ...; every per-track sum is a per-lane sum followed by an xor
@@ -18,9 +17,7 @@
 //   k_tri_summary  one workgroup: the per-workgroup counters of k_tri_tracks (no same-address atomics over the grid)
 //                  summed into d_summary.
 // DESIGN.md section 15 has the lane mapping's measurements.
-#include "pgx_internal.h"
-
-#include <cmath>
+#include "pgx_trackgraph.h"
 
 namespace {
 
@@ -30,61 +27,33 @@ constexpr int TRI_JACOBI_SWEEPS = 8; // cyclic sweeps over the 6 pairs of the 4x
 constexpr int CAM_STRIDE = 8;        // doubles per frame in the camera table: C (3), sign det M, ||m3||, known (1 / 0), 2 unused
 
 struct TriArgs {
-    const pgx_keypoint *kp;       // [F][stride] by slot
-    const int32_t *frame_ids;     // [F] slot -> frame, nullptr = identity
+    TrackView tv;
     const double *P;              // [n_frames][12]
-    const int32_t *offsets;       // [n_tracks + 1]
-    const int32_t *nodes;         // [node_cap][2]
-    const int32_t *track_summary; // [0] = n_tracks
-    int F, stride, n_frames, max_tracks, refine_iters;
-    long long node_cap;           // entries of d_nodes (and d_node_err) an offset may reach
+    int refine_iters;
     double min_par, max_reproj;
     double *xyz, *quality;
     int32_t *flags;
     double *node_err;             // or nullptr
     int32_t *summary;
     double *cam;                  // workspace [n_frames][CAM_STRIDE]
-    int32_t *inv;                 // workspace [n_frames] frame -> slot, -1 = none
     int32_t *meta;                // workspace [0] tracks to process
     int32_t *part;                // workspace [grid][8] per-workgroup counters
     int *status;
 };
 
-__device__ __forceinline__ double nan_max(double a, double b)
-{
-    if (a != a || b != b) return __builtin_nan("");
-    return a > b ? a : b;
-}
-
-template <int G> __device__ __forceinline__ double gsum(double x)
-{
-#pragma unroll
-    for (int m = 1; m < G; m <<= 1) x += __shfl_xor(x, m, G);
-    return x;
-}
-template <int G> __device__ __forceinline__ int gsum_i(int x)
-{
-#pragma unroll
-    for (int m = 1; m < G; m <<= 1) x += __shfl_xor(x, m, G);
-    return x;
-}
-template <int G> __device__ __forceinline__ double gmax(double x)
-{
-#pragma unroll
-    for (int m = 1; m < G; m <<= 1) x = nan_max(x, __shfl_xor(x, m, G));
-    return x;
-}
-
-// observation o of d_nodes: true if it is used (valid node, known camera); bad = the node itself is invalid
+// observation o of d_nodes: true if it is used (valid node, known camera); bad = the node itself is invalid.  The node
+// test and the keypoint fetch (and tri_phase's offsets test) stay written out here, not node_ok / node_keypoint /
+// track_range of pgx_trackgraph.h: k_tri_tracks sits at the SGPR limit, and either helper's shape makes the register
+// allocator spill scalars (tests/test_triangulate_codegen.py pins zero spills).
 __device__ __forceinline__ bool tri_obs(const TriArgs &a, long long o, int &f, double &u, double &v, bool &bad)
 {
-    const int fr = a.nodes[2 * o], k = a.nodes[2 * o + 1];
+    const int fr = a.tv.nodes[2 * o], k = a.tv.nodes[2 * o + 1];
     bad = false;
-    if (fr < 0 || fr >= a.n_frames || k < 0 || k >= a.stride) { bad = true; return false; }
-    const int s = a.inv[fr];
+    if (fr < 0 || fr >= a.tv.n_frames || k < 0 || k >= a.tv.stride) { bad = true; return false; }
+    const int s = a.tv.inv[fr];
     if (s < 0) { bad = true; return false; }
     if (a.cam[(size_t)fr * CAM_STRIDE + 5] == 0.0) return false;
-    const pgx_keypoint p = a.kp[(size_t)s * a.stride + k];
+    const pgx_keypoint p = a.tv.kp[(size_t)s * a.tv.stride + k];
     f = fr;
     u = (double)p.x;
     v = (double)p.y;
@@ -154,13 +123,11 @@ __device__ __forceinline__ int len_class(int n) { return n > 32 ? 2 : (n > 8 ? 1
 // every track of length class CLS, G lanes per track
 template <int G, int CLS> __device__ void tri_phase(const TriArgs &a, long long nt, int (&acc)[8])
 {
-    const long long gid = ((long long)blockIdx.x * blockDim.x + threadIdx.x) / G;
-    const long long ngroups = (long long)gridDim.x * blockDim.x / G;
-    const int lane = threadIdx.x & (G - 1);
     const double NaN = __builtin_nan("");
-    for (long long t = gid; t < nt; t += ngroups) {
-        const int o0 = a.offsets[t], o1 = a.offsets[t + 1];
-        const bool malformed = o0 < 0 || o1 < o0 || (long long)o1 > a.node_cap;
+    PGX_TRACK_LOOP(G, nt)
+    {
+        const int o0 = a.tv.offsets[t], o1 = a.tv.offsets[t + 1];
+        const bool malformed = o0 < 0 || o1 < o0 || (long long)o1 > a.tv.node_cap;
         const int n = malformed ? 0 : o1 - o0;
         if (len_class(n) != CLS) continue;
         if (malformed && lane == 0) atomicOr(a.status, (int)PGX_ST_TRI_NODE);
@@ -378,7 +345,7 @@ template <int G, int CLS> __device__ void tri_phase(const TriArgs &a, long long 
 
 __global__ __launch_bounds__(TRI_NT) void k_tri_frames(TriArgs a)
 {
-    for (int f = threadIdx.x; f < a.n_frames; f += blockDim.x) {
+    for (int f = threadIdx.x; f < a.tv.n_frames; f += blockDim.x) {
         const double *p = a.P + (size_t)f * 12;
         bool fin = true;
 #pragma unroll
@@ -399,23 +366,11 @@ __global__ __launch_bounds__(TRI_NT) void k_tri_frames(TriArgs a)
         c[5] = known ? 1.0 : 0.0;
         c[6] = 0.0;
         c[7] = 0.0;
-        a.inv[f] = -1;
+        a.tv.inv[f] = -1;
     }
-    if (threadIdx.x == 0) {
-        int nt = a.track_summary[0];
-        nt = nt < 0 ? 0 : nt;
-        if (nt > a.max_tracks) {
-            atomicOr(a.status, (int)PGX_ST_TRI_CAP);
-            nt = a.max_tracks;
-        }
-        a.meta[0] = nt;
-    }
+    if (threadIdx.x == 0) a.meta[0] = clamp_tracks(a.tv, a.status, PGX_ST_TRI_CAP);
     __syncthreads();
-    for (int s = threadIdx.x; s < a.F; s += blockDim.x) {
-        const int f = a.frame_ids ? a.frame_ids[s] : s;
-        if (f < 0 || f >= a.n_frames) continue;
-        if (atomicCAS(&a.inv[f], -1, s) != -1) atomicOr(a.status, (int)PGX_ST_TRI_DUP);
-    }
+    build_slot_inverse(a.tv, a.status, PGX_ST_TRI_DUP);
 }
 
 __global__ __launch_bounds__(TRI_NT) void k_tri_tracks(TriArgs a)
@@ -456,14 +411,23 @@ int tri_grid(int max_tracks)
     return (int)(want < 1 ? 1 : (want > TRI_GRID_MAX ? TRI_GRID_MAX : want));
 }
 
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+// the workspace, described once: a's workspace pointers (none valid for ws = nullptr) and the bytes
+size_t tri_carve(TriArgs &a, void *ws, int n_frames)
+{
+    WsCarver w(ws);
+    a.cam = w.take<double>((size_t)n_frames * CAM_STRIDE * sizeof(double));
+    a.part = w.take<int32_t>((size_t)TRI_GRID_MAX * 8 * sizeof(int32_t));
+    a.tv.inv = w.take<int32_t>((size_t)n_frames * sizeof(int32_t));
+    a.meta = w.take<int32_t>(256);
+    return w.total();
+}
 
 } // namespace
 
 size_t pgx_triangulate_ws_bytes(int n_frames)
 {
-    return align256((size_t)n_frames * CAM_STRIDE * sizeof(double)) + align256((size_t)TRI_GRID_MAX * 8 * sizeof(int32_t)) +
-           align256((size_t)n_frames * sizeof(int32_t)) + 256;
+    TriArgs a;
+    return tri_carve(a, nullptr, n_frames);
 }
 
 void pgx_launch_triangulate(hipStream_t s, const pgx_keypoint *d_kp, int F, int stride, const int32_t *d_frame_ids, int n_frames,
@@ -473,18 +437,9 @@ void pgx_launch_triangulate(hipStream_t s, const pgx_keypoint *d_kp, int F, int 
                             int32_t *d_summary, void *ws, int *status)
 {
     TriArgs a;
-    a.kp = d_kp;
-    a.frame_ids = d_frame_ids;
+    a.tv = TrackView{d_kp, d_frame_ids, d_offsets, d_nodes, d_track_summary, F, stride, n_frames, max_tracks, node_cap, nullptr};
     a.P = d_P;
-    a.offsets = d_offsets;
-    a.nodes = d_nodes;
-    a.track_summary = d_track_summary;
-    a.F = F;
-    a.stride = stride;
-    a.n_frames = n_frames;
-    a.max_tracks = max_tracks;
     a.refine_iters = refine_iters;
-    a.node_cap = node_cap;
     a.min_par = min_parallax_deg;
     a.max_reproj = max_reproj_px;
     a.xyz = d_xyz;
@@ -492,15 +447,8 @@ void pgx_launch_triangulate(hipStream_t s, const pgx_keypoint *d_kp, int F, int 
     a.flags = d_flags;
     a.node_err = d_node_err;
     a.summary = d_summary;
-    char *w = static_cast<char *>(ws);
-    a.cam = reinterpret_cast<double *>(w);
-    w += align256((size_t)n_frames * CAM_STRIDE * sizeof(double));
-    a.part = reinterpret_cast<int32_t *>(w);
-    w += align256((size_t)TRI_GRID_MAX * 8 * sizeof(int32_t));
-    a.inv = reinterpret_cast<int32_t *>(w);
-    w += align256((size_t)n_frames * sizeof(int32_t));
-    a.meta = reinterpret_cast<int32_t *>(w);
     a.status = status;
+    tri_carve(a, ws, n_frames);
     const int grid = tri_grid(max_tracks);
     hipLaunchKernelGGL(k_tri_frames, dim3(1), dim3(TRI_NT), 0, s, a);
     hipLaunchKernelGGL(k_tri_tracks, dim3(grid), dim3(TRI_NT), 0, s, a);

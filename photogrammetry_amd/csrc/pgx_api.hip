@@ -2,7 +2,7 @@
 // host-buffer entry points (copy in -> kernels -> copy out) and the device-resident batched
 // entry points.  All compute is in the k_*.hip kernels; there is no CPU fallback anywhere:
 // every entry point needs a working gfx950 device and fails with PGX_E_HIP without one.
-#include "pgx_internal.h"
+#include "pgx_trackgraph.h"
 
 #include <atomic>
 #include <cmath>
@@ -1085,9 +1085,88 @@ int pgx_tracks_split_dev(pgx_ctx *c, const pgx_pair *d_matches, const int32_t *d
     return PGX_OK;
 }
 
-// ---- multi-view triangulation of tracks --------------------------------------------------------------------------
+// ---- the consumers of the track graph: triangulation, bundle adjustment, frame registration --------------------------
 
 namespace {
+// the argument checks every device form shares
+int geom_dev_args(pgx_ctx *c, int F, int stride, int n_frames, const int32_t *d_frame_ids, int max_tracks)
+{
+    if (F <= 0 || stride <= 0 || n_frames <= 0) return fail(c, PGX_E_BADARG, "F, stride and n_frames must be positive");
+    if (!d_frame_ids && n_frames != F) return fail(c, PGX_E_BADARG, "without d_frame_ids, n_frames must equal F");
+    if ((long long)n_frames * stride > (1ll << 30)) return fail(c, PGX_E_BADARG, "n_frames * stride must be <= 2^30");
+    if (max_tracks < 0) return fail(c, PGX_E_BADARG, "max_tracks must be >= 0");
+    return PGX_OK;
+}
+
+// the host forms' checks of counts, offsets and nodes (the device then sees no out-of-range node); stride = max(counts, 1)
+int check_host_tracks(pgx_ctx *c, const pgx_keypoint *kps, const int32_t *counts, int n_frames, const int32_t *track_offsets,
+                      const int32_t *nodes, int n_tracks, int *stride_out, long long *n_nodes_out)
+{
+    long long n_kp = 0;
+    int stride = 1;
+    for (int f = 0; f < n_frames; f++) {
+        if (counts[f] < 0) return fail(c, PGX_E_BADARG, "counts[%d] = %d is negative", f, counts[f]);
+        n_kp += counts[f];
+        stride = counts[f] > stride ? counts[f] : stride;
+    }
+    if (n_kp > 0 && !kps) return fail(c, PGX_E_BADARG, "null pointer (kps)");
+    if ((long long)n_frames * stride > (1ll << 30)) return fail(c, PGX_E_BADARG, "n_frames * max(counts) must be <= 2^30");
+    if (track_offsets[0] != 0) return fail(c, PGX_E_BADARG, "track_offsets[0] must be 0");
+    for (int t = 0; t < n_tracks; t++)
+        if (track_offsets[t + 1] < track_offsets[t]) return fail(c, PGX_E_BADARG, "track_offsets decrease at track %d", t);
+    const long long n_nodes = track_offsets[n_tracks];
+    if (n_nodes > 0 && !nodes) return fail(c, PGX_E_BADARG, "null pointer (nodes)");
+    for (long long o = 0; o < n_nodes; o++) {
+        const int f = nodes[2 * o], k = nodes[2 * o + 1];
+        if (f < 0 || f >= n_frames || k < 0 || k >= counts[f])
+            return fail(c, PGX_E_BADARG, "node %lld = (%d, %d) is outside [0, n_frames) x [0, counts[frame])", o, f, k);
+    }
+    *stride_out = stride;
+    *n_nodes_out = n_nodes;
+    return PGX_OK;
+}
+
+// One pinned upload of a host form into st_a, in 256-byte-aligned sections: keypoints [n_frames][stride], the stage's
+// per-frame arrays (frame_src, frame_bytes per frame; nullptr ends the list), offsets, nodes, with per_track the points
+// and flags of the tracks, and the track summary's {n_tracks, n_nodes}.  The section offsets come back in `at`.
+struct HostUpload {
+    size_t frame[3], off, nodes, xyz, flags, ts;
+};
+int stage_host_tracks(pgx_ctx *c, const pgx_keypoint *kps, const int32_t *counts, int n_frames, int stride,
+                      const void *const (&frame_src)[3], const size_t (&frame_bytes)[3], const int32_t *track_offsets,
+                      const int32_t *nodes, int n_tracks, long long n_nodes, bool per_track, const double *xyz,
+                      const int32_t *track_flags, HostUpload &at)
+{
+    const size_t nn = (size_t)(n_nodes > 0 ? n_nodes : 1), nt1 = (size_t)(n_tracks > 0 ? n_tracks : 1);
+    WsCarver w(nullptr);
+    w.put((size_t)n_frames * stride * sizeof(pgx_keypoint));
+    for (int i = 0; i < 3 && frame_src[i]; i++) at.frame[i] = w.put((size_t)n_frames * frame_bytes[i]);
+    at.off = w.put((size_t)(n_tracks + 1) * 4);
+    at.nodes = w.put(nn * 8);
+    if (per_track) {
+        at.xyz = w.put(nt1 * 24);
+        at.flags = w.put(nt1 * 4);
+    }
+    at.ts = w.put(256);
+    HIPCHK(c, c->pin_in.ensure(w.total()));
+    HIPCHK(c, c->st_a.ensure(w.total()));
+    char *h = c->pin_in.as<char>();
+    for (int f = 0, k = 0; f < n_frames; k += counts[f], f++)
+        if (counts[f] > 0) std::memcpy(h + (size_t)f * stride * sizeof(pgx_keypoint), kps + k, (size_t)counts[f] * sizeof(pgx_keypoint));
+    for (int i = 0; i < 3 && frame_src[i]; i++) std::memcpy(h + at.frame[i], frame_src[i], (size_t)n_frames * frame_bytes[i]);
+    std::memcpy(h + at.off, track_offsets, (size_t)(n_tracks + 1) * 4);
+    if (n_nodes > 0) std::memcpy(h + at.nodes, nodes, (size_t)n_nodes * 8);
+    if (per_track && n_tracks > 0) std::memcpy(h + at.xyz, xyz, (size_t)n_tracks * 24);
+    if (per_track && n_tracks > 0 && track_flags) std::memcpy(h + at.flags, track_flags, (size_t)n_tracks * 4);
+    const int32_t ts[8] = {n_tracks, (int32_t)n_nodes};
+    std::memcpy(h + at.ts, ts, sizeof ts);
+    HIPCHK(c, hipMemcpyAsync(c->st_a.p, h, w.total(), hipMemcpyHostToDevice, c->stream));
+    return PGX_OK;
+}
+
+// the uploaded section at `off`
+extern "C++" template <class T> const T *dev_in(pgx_ctx *c, size_t off) { return reinterpret_cast<const T *>(c->st_a.as<char>() + off); }
+
 int tri_args(pgx_ctx *c, double min_parallax_deg, double max_reproj_px, int refine_iters)
 {
     if (refine_iters < 0 || refine_iters > 32) return fail(c, PGX_E_BADARG, "refine_iters = %d, must be in [0, 32]", refine_iters);
@@ -1095,7 +1174,26 @@ int tri_args(pgx_ctx *c, double min_parallax_deg, double max_reproj_px, int refi
     if (!(max_reproj_px > 0.0)) return fail(c, PGX_E_BADARG, "max_reproj_px must be > 0 (and not NaN; +inf disables the test)");
     return PGX_OK;
 }
+
+int ba_args(pgx_ctx *c, int max_iters, double huber_px, double lambda0)
+{
+    if (max_iters < 0 || max_iters > 100) return fail(c, PGX_E_BADARG, "max_iters = %d, must be in [0, 100]", max_iters);
+    if (!(huber_px > 0.0)) return fail(c, PGX_E_BADARG, "huber_px must be > 0 (and not NaN; +inf is plain least squares)");
+    if (!(lambda0 > 0.0) || !std::isfinite(lambda0)) return fail(c, PGX_E_BADARG, "lambda0 must be finite and > 0");
+    return PGX_OK;
+}
+
+int reg_args(pgx_ctx *c, int n_samples, double inlier_px, int min_inliers, int refine_iters)
+{
+    if (n_samples < 1 || n_samples > 65536) return fail(c, PGX_E_BADARG, "n_samples = %d, must be in [1, 65536]", n_samples);
+    if (!(inlier_px > 0.0) || !std::isfinite(inlier_px)) return fail(c, PGX_E_BADARG, "inlier_px must be finite and > 0");
+    if (min_inliers < 3) return fail(c, PGX_E_BADARG, "min_inliers = %d, must be >= 3", min_inliers);
+    if (refine_iters < 0 || refine_iters > 32) return fail(c, PGX_E_BADARG, "refine_iters = %d, must be in [0, 32]", refine_iters);
+    return PGX_OK;
+}
 } // namespace
+
+// ---- multi-view triangulation of tracks --------------------------------------------------------------------------
 
 int pgx_triangulate_tracks_dev(pgx_ctx *c, const pgx_keypoint *d_kp, int F, int stride, const int32_t *d_frame_ids, int n_frames,
                                const double *d_P, const int32_t *d_offsets, const int32_t *d_nodes, const int32_t *d_track_summary,
@@ -1105,11 +1203,8 @@ int pgx_triangulate_tracks_dev(pgx_ctx *c, const pgx_keypoint *d_kp, int F, int 
     if (!c || !d_kp || !d_P || !d_offsets || !d_nodes || !d_track_summary || !d_xyz || !d_quality || !d_flags || !d_summary)
         return c ? fail(c, PGX_E_BADARG, "null pointer") : PGX_E_BADARG;
     Lock l(c);
-    if (F <= 0 || stride <= 0 || n_frames <= 0) return fail(c, PGX_E_BADARG, "F, stride and n_frames must be positive");
-    if (!d_frame_ids && n_frames != F) return fail(c, PGX_E_BADARG, "without d_frame_ids, n_frames must equal F");
-    if ((long long)n_frames * stride > (1ll << 30)) return fail(c, PGX_E_BADARG, "n_frames * stride must be <= 2^30");
-    if (max_tracks < 0) return fail(c, PGX_E_BADARG, "max_tracks must be >= 0");
-    const int rc = tri_args(c, min_parallax_deg, max_reproj_px, refine_iters);
+    int rc = geom_dev_args(c, F, stride, n_frames, d_frame_ids, max_tracks);
+    if (rc == PGX_OK) rc = tri_args(c, min_parallax_deg, max_reproj_px, refine_iters);
     if (rc != PGX_OK) return rc;
     HIPCHK(c, c->ws_tri.ensure(pgx_triangulate_ws_bytes(n_frames)));
     {
@@ -1131,87 +1226,43 @@ int pgx_triangulate_tracks(pgx_ctx *c, const pgx_keypoint *kps, const int32_t *c
         (n_tracks > 0 && (!xyz || !quality || !flags)))
         return c ? fail(c, PGX_E_BADARG, "null pointer or bad size") : PGX_E_BADARG;
     Lock l(c);
-    const int rc = tri_args(c, min_parallax_deg, max_reproj_px, refine_iters);
+    int rc = tri_args(c, min_parallax_deg, max_reproj_px, refine_iters);
+    int stride;
+    long long n_nodes;
+    if (rc == PGX_OK) rc = check_host_tracks(c, kps, counts, n_frames, track_offsets, nodes, n_tracks, &stride, &n_nodes);
     if (rc != PGX_OK) return rc;
-    // the host's checks: counts, offsets, nodes (the device then sees no bad node)
-    long long n_kp = 0;
-    int stride = 1;
-    for (int f = 0; f < n_frames; f++) {
-        if (counts[f] < 0) return fail(c, PGX_E_BADARG, "counts[%d] = %d is negative", f, counts[f]);
-        n_kp += counts[f];
-        stride = counts[f] > stride ? counts[f] : stride;
-    }
-    if (n_kp > 0 && !kps) return fail(c, PGX_E_BADARG, "null pointer (kps)");
-    if ((long long)n_frames * stride > (1ll << 30)) return fail(c, PGX_E_BADARG, "n_frames * max(counts) must be <= 2^30");
-    if (track_offsets[0] != 0) return fail(c, PGX_E_BADARG, "track_offsets[0] must be 0");
-    for (int t = 0; t < n_tracks; t++)
-        if (track_offsets[t + 1] < track_offsets[t]) return fail(c, PGX_E_BADARG, "track_offsets decrease at track %d", t);
-    const long long n_nodes = track_offsets[n_tracks];
-    if (n_nodes > 0 && !nodes) return fail(c, PGX_E_BADARG, "null pointer (nodes)");
-    for (long long o = 0; o < n_nodes; o++) {
-        const int f = nodes[2 * o], k = nodes[2 * o + 1];
-        if (f < 0 || f >= n_frames || k < 0 || k >= counts[f])
-            return fail(c, PGX_E_BADARG, "node %lld = (%d, %d) is outside [0, n_frames) x [0, counts[frame])", o, f, k);
-    }
     for (int i = 0; i < 8; i++) summary[i] = 0;
     if (n_tracks == 0) return PGX_OK;
-    // staging (pinned, one upload): keypoints [n_frames][stride], P, offsets, nodes, the track summary's n_tracks
-    const size_t b_kp = ((size_t)n_frames * stride * sizeof(pgx_keypoint) + 255) & ~(size_t)255;
-    const size_t b_P = ((size_t)n_frames * 12 * sizeof(double) + 255) & ~(size_t)255;
-    const size_t b_off = ((size_t)(n_tracks + 1) * 4 + 255) & ~(size_t)255;
-    const size_t b_nodes = ((size_t)(n_nodes > 0 ? n_nodes : 1) * 8 + 255) & ~(size_t)255;
-    const size_t b_in = b_kp + b_P + b_off + b_nodes + 256;
-    HIPCHK(c, c->pin_in.ensure(b_in));
-    HIPCHK(c, c->st_a.ensure(b_in));
-    char *h = c->pin_in.as<char>();
-    for (int f = 0, at = 0; f < n_frames; at += counts[f], f++)
-        if (counts[f] > 0) std::memcpy(h + (size_t)f * stride * sizeof(pgx_keypoint), kps + at, (size_t)counts[f] * sizeof(pgx_keypoint));
-    std::memcpy(h + b_kp, P, (size_t)n_frames * 12 * sizeof(double));
-    std::memcpy(h + b_kp + b_P, track_offsets, (size_t)(n_tracks + 1) * 4);
-    if (n_nodes > 0) std::memcpy(h + b_kp + b_P + b_off, nodes, (size_t)n_nodes * 8);
-    const int32_t ts[8] = {n_tracks, (int32_t)n_nodes};
-    std::memcpy(h + b_kp + b_P + b_off + b_nodes, ts, sizeof ts);
-    HIPCHK(c, hipMemcpyAsync(c->st_a.p, h, b_in, hipMemcpyHostToDevice, c->stream));
-    char *d = c->st_a.as<char>();
+    HostUpload in;
+    rc = stage_host_tracks(c, kps, counts, n_frames, stride, {P, nullptr, nullptr}, {96, 0, 0}, track_offsets, nodes, n_tracks, n_nodes,
+                           false, nullptr, nullptr, in);
+    if (rc != PGX_OK) return rc;
     // outputs: xyz, quality, node_err, flags, summary
-    const size_t b_xyz = ((size_t)n_tracks * 24 + 255) & ~(size_t)255;
-    const size_t b_err = ((size_t)(n_nodes > 0 ? n_nodes : 1) * 8 + 255) & ~(size_t)255;
-    const size_t b_fl = ((size_t)n_tracks * 4 + 255) & ~(size_t)255;
-    HIPCHK(c, c->st_b.ensure(2 * b_xyz + b_err + b_fl + 256));
+    WsCarver out(nullptr);
+    const size_t p_xyz = out.put((size_t)n_tracks * 24), p_q = out.put((size_t)n_tracks * 24),
+                 p_err = out.put((size_t)(n_nodes > 0 ? n_nodes : 1) * 8), p_fl = out.put((size_t)n_tracks * 4), p_sum = out.put(256);
+    HIPCHK(c, c->st_b.ensure(out.total()));
     char *o = c->st_b.as<char>();
-    double *d_xyz = reinterpret_cast<double *>(o), *d_q = reinterpret_cast<double *>(o + b_xyz);
-    double *d_err = reinterpret_cast<double *>(o + 2 * b_xyz);
-    int32_t *d_fl = reinterpret_cast<int32_t *>(o + 2 * b_xyz + b_err), *d_sum = reinterpret_cast<int32_t *>(o + 2 * b_xyz + b_err + b_fl);
     HIPCHK(c, c->ws_tri.ensure(pgx_triangulate_ws_bytes(n_frames)));
     {
         ProfScope ps(c, "triangulate");
-        pgx_launch_triangulate(c->stream, reinterpret_cast<const pgx_keypoint *>(d), n_frames, stride, nullptr, n_frames,
-                               reinterpret_cast<const double *>(d + b_kp), reinterpret_cast<const int32_t *>(d + b_kp + b_P),
-                               reinterpret_cast<const int32_t *>(d + b_kp + b_P + b_off), n_nodes,
-                               reinterpret_cast<const int32_t *>(d + b_kp + b_P + b_off + b_nodes), n_tracks, min_parallax_deg,
-                               max_reproj_px, refine_iters, d_xyz, d_q, d_fl, node_err ? d_err : nullptr, d_sum, c->ws_tri.p,
-                               c->d_status);
+        pgx_launch_triangulate(c->stream, dev_in<pgx_keypoint>(c, 0), n_frames, stride, nullptr, n_frames, dev_in<double>(c, in.frame[0]),
+                               dev_in<int32_t>(c, in.off), dev_in<int32_t>(c, in.nodes), n_nodes, dev_in<int32_t>(c, in.ts), n_tracks,
+                               min_parallax_deg, max_reproj_px, refine_iters, reinterpret_cast<double *>(o + p_xyz),
+                               reinterpret_cast<double *>(o + p_q), reinterpret_cast<int32_t *>(o + p_fl),
+                               node_err ? reinterpret_cast<double *>(o + p_err) : nullptr, reinterpret_cast<int32_t *>(o + p_sum),
+                               c->ws_tri.p, c->d_status);
     }
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(xyz, d_xyz, (size_t)n_tracks * 24, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(quality, d_q, (size_t)n_tracks * 24, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(flags, d_fl, (size_t)n_tracks * 4, hipMemcpyDeviceToHost, c->stream));
-    if (node_err && n_nodes > 0) HIPCHK(c, hipMemcpyAsync(node_err, d_err, (size_t)n_nodes * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(summary, d_sum, 8 * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(xyz, o + p_xyz, (size_t)n_tracks * 24, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(quality, o + p_q, (size_t)n_tracks * 24, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(flags, o + p_fl, (size_t)n_tracks * 4, hipMemcpyDeviceToHost, c->stream));
+    if (node_err && n_nodes > 0) HIPCHK(c, hipMemcpyAsync(node_err, o + p_err, (size_t)n_nodes * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(summary, o + p_sum, 8 * 4, hipMemcpyDeviceToHost, c->stream));
     return sync_status(c);
 }
 
 // ---- bundle adjustment of cameras and track points ----------------------------------------------------------------
-
-namespace {
-int ba_args(pgx_ctx *c, int max_iters, double huber_px, double lambda0)
-{
-    if (max_iters < 0 || max_iters > 100) return fail(c, PGX_E_BADARG, "max_iters = %d, must be in [0, 100]", max_iters);
-    if (!(huber_px > 0.0)) return fail(c, PGX_E_BADARG, "huber_px must be > 0 (and not NaN; +inf is plain least squares)");
-    if (!(lambda0 > 0.0) || !std::isfinite(lambda0)) return fail(c, PGX_E_BADARG, "lambda0 must be finite and > 0");
-    return PGX_OK;
-}
-} // namespace
 
 int pgx_bundle_adjust_dev(pgx_ctx *c, const pgx_keypoint *d_kp, int F, int stride, const int32_t *d_frame_ids, int n_frames,
                           const double *d_K, const double *d_Rt_in, const int32_t *d_fixed, const int32_t *d_offsets, const int32_t *d_nodes,
@@ -1223,11 +1274,8 @@ int pgx_bundle_adjust_dev(pgx_ctx *c, const pgx_keypoint *d_kp, int F, int strid
         !d_P_out || !d_xyz_out || !d_trace || !d_report)
         return c ? fail(c, PGX_E_BADARG, "null pointer") : PGX_E_BADARG;
     Lock l(c);
-    if (F <= 0 || stride <= 0 || n_frames <= 0) return fail(c, PGX_E_BADARG, "F, stride and n_frames must be positive");
-    if (!d_frame_ids && n_frames != F) return fail(c, PGX_E_BADARG, "without d_frame_ids, n_frames must equal F");
-    if ((long long)n_frames * stride > (1ll << 30)) return fail(c, PGX_E_BADARG, "n_frames * stride must be <= 2^30");
-    if (max_tracks < 0) return fail(c, PGX_E_BADARG, "max_tracks must be >= 0");
-    const int rc = ba_args(c, max_iters, huber_px, lambda0);
+    int rc = geom_dev_args(c, F, stride, n_frames, d_frame_ids, max_tracks);
+    if (rc == PGX_OK) rc = ba_args(c, max_iters, huber_px, lambda0);
     if (rc != PGX_OK) return rc;
     const long long node_cap = (long long)n_frames * stride;
     HIPCHK(c, c->ws_ba.ensure(pgx_bundle_ws_bytes(n_frames, max_tracks, node_cap)));
@@ -1250,71 +1298,35 @@ int pgx_bundle_adjust(pgx_ctx *c, const pgx_keypoint *kps, const int32_t *counts
         n_tracks < 0 || (n_tracks > 0 && (!xyz_in || !xyz_out)))
         return c ? fail(c, PGX_E_BADARG, "null pointer or bad size") : PGX_E_BADARG;
     Lock l(c);
-    const int rc = ba_args(c, max_iters, huber_px, lambda0);
+    int rc = ba_args(c, max_iters, huber_px, lambda0);
+    int stride;
+    long long n_nodes;
+    if (rc == PGX_OK) rc = check_host_tracks(c, kps, counts, n_frames, track_offsets, nodes, n_tracks, &stride, &n_nodes);
+    HostUpload in;
+    if (rc == PGX_OK)
+        rc = stage_host_tracks(c, kps, counts, n_frames, stride, {K, Rt_in, fixed}, {32, 96, 4}, track_offsets, nodes, n_tracks, n_nodes,
+                               true, xyz_in, track_flags, in);
     if (rc != PGX_OK) return rc;
-    // the host's checks: counts, offsets, nodes (the device then sees no out-of-range node)
-    long long n_kp = 0;
-    int stride = 1;
-    for (int f = 0; f < n_frames; f++) {
-        if (counts[f] < 0) return fail(c, PGX_E_BADARG, "counts[%d] = %d is negative", f, counts[f]);
-        n_kp += counts[f];
-        stride = counts[f] > stride ? counts[f] : stride;
-    }
-    if (n_kp > 0 && !kps) return fail(c, PGX_E_BADARG, "null pointer (kps)");
-    if ((long long)n_frames * stride > (1ll << 30)) return fail(c, PGX_E_BADARG, "n_frames * max(counts) must be <= 2^30");
-    if (track_offsets[0] != 0) return fail(c, PGX_E_BADARG, "track_offsets[0] must be 0");
-    for (int t = 0; t < n_tracks; t++)
-        if (track_offsets[t + 1] < track_offsets[t]) return fail(c, PGX_E_BADARG, "track_offsets decrease at track %d", t);
-    const long long n_nodes = track_offsets[n_tracks];
-    if (n_nodes > 0 && !nodes) return fail(c, PGX_E_BADARG, "null pointer (nodes)");
-    for (long long o = 0; o < n_nodes; o++) {
-        const int f = nodes[2 * o], k = nodes[2 * o + 1];
-        if (f < 0 || f >= n_frames || k < 0 || k >= counts[f])
-            return fail(c, PGX_E_BADARG, "node %lld = (%d, %d) is outside [0, n_frames) x [0, counts[frame])", o, f, k);
-    }
-    // staging (pinned, one upload): keypoints [n_frames][stride], K, Rt, fixed, offsets, nodes, xyz, flags, the track summary
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t nn = (size_t)(n_nodes > 0 ? n_nodes : 1), nt1 = (size_t)(n_tracks > 0 ? n_tracks : 1);
-    const size_t b_kp = al((size_t)n_frames * stride * sizeof(pgx_keypoint)), b_K = al((size_t)n_frames * 32),
-                 b_Rt = al((size_t)n_frames * 96), b_fx = al((size_t)n_frames * 4), b_off = al((size_t)(n_tracks + 1) * 4),
-                 b_nodes = al(nn * 8), b_xyz = al(nt1 * 24), b_fl = al(nt1 * 4);
-    const size_t o_K = b_kp, o_Rt = o_K + b_K, o_fx = o_Rt + b_Rt, o_off = o_fx + b_fx, o_nodes = o_off + b_off, o_xyz = o_nodes + b_nodes,
-                 o_fl = o_xyz + b_xyz, o_ts = o_fl + b_fl, b_in = o_ts + 256;
-    HIPCHK(c, c->pin_in.ensure(b_in));
-    HIPCHK(c, c->st_a.ensure(b_in));
-    char *h = c->pin_in.as<char>();
-    for (int f = 0, at = 0; f < n_frames; at += counts[f], f++)
-        if (counts[f] > 0) std::memcpy(h + (size_t)f * stride * sizeof(pgx_keypoint), kps + at, (size_t)counts[f] * sizeof(pgx_keypoint));
-    std::memcpy(h + o_K, K, (size_t)n_frames * 32);
-    std::memcpy(h + o_Rt, Rt_in, (size_t)n_frames * 96);
-    std::memcpy(h + o_fx, fixed, (size_t)n_frames * 4);
-    std::memcpy(h + o_off, track_offsets, (size_t)(n_tracks + 1) * 4);
-    if (n_nodes > 0) std::memcpy(h + o_nodes, nodes, (size_t)n_nodes * 8);
-    if (n_tracks > 0) std::memcpy(h + o_xyz, xyz_in, (size_t)n_tracks * 24);
-    if (n_tracks > 0 && track_flags) std::memcpy(h + o_fl, track_flags, (size_t)n_tracks * 4);
-    const int32_t ts[8] = {n_tracks, (int32_t)n_nodes};
-    std::memcpy(h + o_ts, ts, sizeof ts);
-    HIPCHK(c, hipMemcpyAsync(c->st_a.p, h, b_in, hipMemcpyHostToDevice, c->stream));
-    char *d = c->st_a.as<char>();
     // outputs: Rt, P, xyz, node_err, trace, report
-    const size_t b_tr = al((size_t)(max_iters + 1) * 16);
-    const size_t p_P = b_Rt, p_xyz = 2 * b_Rt, p_err = p_xyz + b_xyz, p_tr = p_err + al(nn * 8), p_rep = p_tr + b_tr;
-    HIPCHK(c, c->st_b.ensure(p_rep + 256));
+    WsCarver out(nullptr);
+    const size_t p_Rt = out.put((size_t)n_frames * 96), p_P = out.put((size_t)n_frames * 96),
+                 p_xyz = out.put((size_t)(n_tracks > 0 ? n_tracks : 1) * 24), p_err = out.put((size_t)(n_nodes > 0 ? n_nodes : 1) * 8),
+                 p_tr = out.put((size_t)(max_iters + 1) * 16), p_rep = out.put(256);
+    HIPCHK(c, c->st_b.ensure(out.total()));
     char *o = c->st_b.as<char>();
     HIPCHK(c, c->ws_ba.ensure(pgx_bundle_ws_bytes(n_frames, n_tracks, n_nodes)));
     {
         ProfScope ps(c, "bundle");
-        pgx_launch_bundle(c->stream, reinterpret_cast<const pgx_keypoint *>(d), n_frames, stride, nullptr, n_frames,
-                          reinterpret_cast<const double *>(d + o_K), reinterpret_cast<const double *>(d + o_Rt),
-                          reinterpret_cast<const int32_t *>(d + o_fx), reinterpret_cast<const int32_t *>(d + o_off),
-                          reinterpret_cast<const int32_t *>(d + o_nodes), n_nodes, reinterpret_cast<const int32_t *>(d + o_ts), n_tracks,
-                          reinterpret_cast<const double *>(d + o_xyz), track_flags ? reinterpret_cast<const int32_t *>(d + o_fl) : nullptr,
-                          max_iters, huber_px, lambda0, reinterpret_cast<double *>(o), reinterpret_cast<double *>(o + p_P),
-                          reinterpret_cast<double *>(o + p_xyz), node_err ? reinterpret_cast<double *>(o + p_err) : nullptr,
-                          reinterpret_cast<double *>(o + p_tr), reinterpret_cast<int32_t *>(o + p_rep), c->ws_ba.p, c->d_status);
+        pgx_launch_bundle(c->stream, dev_in<pgx_keypoint>(c, 0), n_frames, stride, nullptr, n_frames, dev_in<double>(c, in.frame[0]),
+                          dev_in<double>(c, in.frame[1]), dev_in<int32_t>(c, in.frame[2]), dev_in<int32_t>(c, in.off),
+                          dev_in<int32_t>(c, in.nodes), n_nodes, dev_in<int32_t>(c, in.ts), n_tracks, dev_in<double>(c, in.xyz),
+                          track_flags ? dev_in<int32_t>(c, in.flags) : nullptr, max_iters, huber_px, lambda0,
+                          reinterpret_cast<double *>(o + p_Rt), reinterpret_cast<double *>(o + p_P), reinterpret_cast<double *>(o + p_xyz),
+                          node_err ? reinterpret_cast<double *>(o + p_err) : nullptr, reinterpret_cast<double *>(o + p_tr),
+                          reinterpret_cast<int32_t *>(o + p_rep), c->ws_ba.p, c->d_status);
     }
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(Rt_out, o, (size_t)n_frames * 96, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(Rt_out, o + p_Rt, (size_t)n_frames * 96, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(P_out, o + p_P, (size_t)n_frames * 96, hipMemcpyDeviceToHost, c->stream));
     if (n_tracks > 0) HIPCHK(c, hipMemcpyAsync(xyz_out, o + p_xyz, (size_t)n_tracks * 24, hipMemcpyDeviceToHost, c->stream));
     if (node_err && n_nodes > 0) HIPCHK(c, hipMemcpyAsync(node_err, o + p_err, (size_t)n_nodes * 8, hipMemcpyDeviceToHost, c->stream));
@@ -1324,17 +1336,6 @@ int pgx_bundle_adjust(pgx_ctx *c, const pgx_keypoint *kps, const int32_t *counts
 }
 
 // ---- frame registration by P3P RANSAC ------------------------------------------------------------------------------
-
-namespace {
-int reg_args(pgx_ctx *c, int n_samples, double inlier_px, int min_inliers, int refine_iters)
-{
-    if (n_samples < 1 || n_samples > 65536) return fail(c, PGX_E_BADARG, "n_samples = %d, must be in [1, 65536]", n_samples);
-    if (!(inlier_px > 0.0) || !std::isfinite(inlier_px)) return fail(c, PGX_E_BADARG, "inlier_px must be finite and > 0");
-    if (min_inliers < 3) return fail(c, PGX_E_BADARG, "min_inliers = %d, must be >= 3", min_inliers);
-    if (refine_iters < 0 || refine_iters > 32) return fail(c, PGX_E_BADARG, "refine_iters = %d, must be in [0, 32]", refine_iters);
-    return PGX_OK;
-}
-} // namespace
 
 int pgx_register_frames_dev(pgx_ctx *c, const pgx_keypoint *d_kp, int F, int stride, const int32_t *d_frame_ids, int n_frames,
                             const double *d_K, const double *d_Rt_in, const int32_t *d_register, const int32_t *d_offsets,
@@ -1347,11 +1348,8 @@ int pgx_register_frames_dev(pgx_ctx *c, const pgx_keypoint *d_kp, int F, int str
         !d_P_out || !d_frame_stats || !d_frame_err || !d_report)
         return c ? fail(c, PGX_E_BADARG, "null pointer") : PGX_E_BADARG;
     Lock l(c);
-    if (F <= 0 || stride <= 0 || n_frames <= 0) return fail(c, PGX_E_BADARG, "F, stride and n_frames must be positive");
-    if (!d_frame_ids && n_frames != F) return fail(c, PGX_E_BADARG, "without d_frame_ids, n_frames must equal F");
-    if ((long long)n_frames * stride > (1ll << 30)) return fail(c, PGX_E_BADARG, "n_frames * stride must be <= 2^30");
-    if (max_tracks < 0) return fail(c, PGX_E_BADARG, "max_tracks must be >= 0");
-    const int rc = reg_args(c, n_samples, inlier_px, min_inliers, refine_iters);
+    int rc = geom_dev_args(c, F, stride, n_frames, d_frame_ids, max_tracks);
+    if (rc == PGX_OK) rc = reg_args(c, n_samples, inlier_px, min_inliers, refine_iters);
     if (rc != PGX_OK) return rc;
     const long long node_cap = (long long)n_frames * stride;
     HIPCHK(c, c->ws_reg.ensure(pgx_register_ws_bytes(n_frames, node_cap, n_samples)));
@@ -1374,72 +1372,34 @@ int pgx_register_frames(pgx_ctx *c, const pgx_keypoint *kps, const int32_t *coun
         n_frames <= 0 || n_tracks < 0 || (n_tracks > 0 && !xyz))
         return c ? fail(c, PGX_E_BADARG, "null pointer or bad size") : PGX_E_BADARG;
     Lock l(c);
-    const int rc = reg_args(c, n_samples, inlier_px, min_inliers, refine_iters);
+    int rc = reg_args(c, n_samples, inlier_px, min_inliers, refine_iters);
+    int stride;
+    long long n_nodes;
+    if (rc == PGX_OK) rc = check_host_tracks(c, kps, counts, n_frames, track_offsets, nodes, n_tracks, &stride, &n_nodes);
+    HostUpload in;
+    if (rc == PGX_OK)
+        rc = stage_host_tracks(c, kps, counts, n_frames, stride, {K, Rt_in, reg}, {32, 96, 4}, track_offsets, nodes, n_tracks, n_nodes,
+                               true, xyz, track_flags, in);
     if (rc != PGX_OK) return rc;
-    // the host's checks: counts, offsets, nodes (the device then sees no out-of-range node)
-    long long n_kp = 0;
-    int stride = 1;
-    for (int f = 0; f < n_frames; f++) {
-        if (counts[f] < 0) return fail(c, PGX_E_BADARG, "counts[%d] = %d is negative", f, counts[f]);
-        n_kp += counts[f];
-        stride = counts[f] > stride ? counts[f] : stride;
-    }
-    if (n_kp > 0 && !kps) return fail(c, PGX_E_BADARG, "null pointer (kps)");
-    if ((long long)n_frames * stride > (1ll << 30)) return fail(c, PGX_E_BADARG, "n_frames * max(counts) must be <= 2^30");
-    if (track_offsets[0] != 0) return fail(c, PGX_E_BADARG, "track_offsets[0] must be 0");
-    for (int t = 0; t < n_tracks; t++)
-        if (track_offsets[t + 1] < track_offsets[t]) return fail(c, PGX_E_BADARG, "track_offsets decrease at track %d", t);
-    const long long n_nodes = track_offsets[n_tracks];
-    if (n_nodes > 0 && !nodes) return fail(c, PGX_E_BADARG, "null pointer (nodes)");
-    for (long long o = 0; o < n_nodes; o++) {
-        const int f = nodes[2 * o], k = nodes[2 * o + 1];
-        if (f < 0 || f >= n_frames || k < 0 || k >= counts[f])
-            return fail(c, PGX_E_BADARG, "node %lld = (%d, %d) is outside [0, n_frames) x [0, counts[frame])", o, f, k);
-    }
-    // staging (pinned, one upload): keypoints [n_frames][stride], K, Rt, reg, offsets, nodes, xyz, flags, the track summary
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t nn = (size_t)(n_nodes > 0 ? n_nodes : 1), nt1 = (size_t)(n_tracks > 0 ? n_tracks : 1);
-    const size_t b_kp = al((size_t)n_frames * stride * sizeof(pgx_keypoint)), b_K = al((size_t)n_frames * 32),
-                 b_Rt = al((size_t)n_frames * 96), b_rg = al((size_t)n_frames * 4), b_off = al((size_t)(n_tracks + 1) * 4),
-                 b_nodes = al(nn * 8), b_xyz = al(nt1 * 24), b_fl = al(nt1 * 4);
-    const size_t o_K = b_kp, o_Rt = o_K + b_K, o_rg = o_Rt + b_Rt, o_off = o_rg + b_rg, o_nodes = o_off + b_off, o_xyz = o_nodes + b_nodes,
-                 o_fl = o_xyz + b_xyz, o_ts = o_fl + b_fl, b_in = o_ts + 256;
-    HIPCHK(c, c->pin_in.ensure(b_in));
-    HIPCHK(c, c->st_a.ensure(b_in));
-    char *h = c->pin_in.as<char>();
-    for (int f = 0, at = 0; f < n_frames; at += counts[f], f++)
-        if (counts[f] > 0) std::memcpy(h + (size_t)f * stride * sizeof(pgx_keypoint), kps + at, (size_t)counts[f] * sizeof(pgx_keypoint));
-    std::memcpy(h + o_K, K, (size_t)n_frames * 32);
-    std::memcpy(h + o_Rt, Rt_in, (size_t)n_frames * 96);
-    std::memcpy(h + o_rg, reg, (size_t)n_frames * 4);
-    std::memcpy(h + o_off, track_offsets, (size_t)(n_tracks + 1) * 4);
-    if (n_nodes > 0) std::memcpy(h + o_nodes, nodes, (size_t)n_nodes * 8);
-    if (n_tracks > 0) std::memcpy(h + o_xyz, xyz, (size_t)n_tracks * 24);
-    if (n_tracks > 0 && track_flags) std::memcpy(h + o_fl, track_flags, (size_t)n_tracks * 4);
-    const int32_t ts[8] = {n_tracks, (int32_t)n_nodes};
-    std::memcpy(h + o_ts, ts, sizeof ts);
-    HIPCHK(c, hipMemcpyAsync(c->st_a.p, h, b_in, hipMemcpyHostToDevice, c->stream));
-    char *d = c->st_a.as<char>();
     // outputs: Rt, P, stats, err, node_inlier, report
-    const size_t b_st = al((size_t)n_frames * 16), b_er = al((size_t)n_frames * 16);
-    const size_t p_P = b_Rt, p_st = 2 * b_Rt, p_er = p_st + b_st, p_ni = p_er + b_er, p_rep = p_ni + al(nn * 4);
-    HIPCHK(c, c->st_b.ensure(p_rep + 256));
+    WsCarver out(nullptr);
+    const size_t p_Rt = out.put((size_t)n_frames * 96), p_P = out.put((size_t)n_frames * 96), p_st = out.put((size_t)n_frames * 16),
+                 p_er = out.put((size_t)n_frames * 16), p_ni = out.put((size_t)(n_nodes > 0 ? n_nodes : 1) * 4), p_rep = out.put(256);
+    HIPCHK(c, c->st_b.ensure(out.total()));
     char *o = c->st_b.as<char>();
     HIPCHK(c, c->ws_reg.ensure(pgx_register_ws_bytes(n_frames, n_nodes, n_samples)));
     {
         ProfScope ps(c, "register");
-        pgx_launch_register(c->stream, reinterpret_cast<const pgx_keypoint *>(d), n_frames, stride, nullptr, n_frames,
-                            reinterpret_cast<const double *>(d + o_K), reinterpret_cast<const double *>(d + o_Rt),
-                            reinterpret_cast<const int32_t *>(d + o_rg), reinterpret_cast<const int32_t *>(d + o_off),
-                            reinterpret_cast<const int32_t *>(d + o_nodes), n_nodes, reinterpret_cast<const int32_t *>(d + o_ts), n_tracks,
-                            reinterpret_cast<const double *>(d + o_xyz), track_flags ? reinterpret_cast<const int32_t *>(d + o_fl) : nullptr,
-                            n_samples, inlier_px, min_inliers, refine_iters, seed, reinterpret_cast<double *>(o),
-                            reinterpret_cast<double *>(o + p_P), reinterpret_cast<int32_t *>(o + p_st), reinterpret_cast<double *>(o + p_er),
-                            node_inlier ? reinterpret_cast<int32_t *>(o + p_ni) : nullptr, reinterpret_cast<int32_t *>(o + p_rep),
-                            c->ws_reg.p, c->d_status);
+        pgx_launch_register(c->stream, dev_in<pgx_keypoint>(c, 0), n_frames, stride, nullptr, n_frames, dev_in<double>(c, in.frame[0]),
+                            dev_in<double>(c, in.frame[1]), dev_in<int32_t>(c, in.frame[2]), dev_in<int32_t>(c, in.off),
+                            dev_in<int32_t>(c, in.nodes), n_nodes, dev_in<int32_t>(c, in.ts), n_tracks, dev_in<double>(c, in.xyz),
+                            track_flags ? dev_in<int32_t>(c, in.flags) : nullptr, n_samples, inlier_px, min_inliers, refine_iters, seed,
+                            reinterpret_cast<double *>(o + p_Rt), reinterpret_cast<double *>(o + p_P), reinterpret_cast<int32_t *>(o + p_st),
+                            reinterpret_cast<double *>(o + p_er), node_inlier ? reinterpret_cast<int32_t *>(o + p_ni) : nullptr,
+                            reinterpret_cast<int32_t *>(o + p_rep), c->ws_reg.p, c->d_status);
     }
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(Rt_out, o, (size_t)n_frames * 96, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(Rt_out, o + p_Rt, (size_t)n_frames * 96, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(P_out, o + p_P, (size_t)n_frames * 96, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(frame_stats, o + p_st, (size_t)n_frames * 16, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(frame_err, o + p_er, (size_t)n_frames * 16, hipMemcpyDeviceToHost, c->stream));

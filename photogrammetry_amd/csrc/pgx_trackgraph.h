@@ -1,0 +1,184 @@
+// pgx_trackgraph.h -- what every consumer of the track graph shares (k_triangulate.hip, k_bundle.hip, k_register.hip):
+// the read-only view of the graph and the keypoints, its validation and walking on the device, the lane-group
+// reductions, and the workspace carver of the launchers.  Internal to libpgx.so; DESIGN.md section 14a.
+#pragma once
+
+#include "pgx_internal.h"
+
+#include <cmath>
+
+// The shared inputs of a stage, embedded in its kernel-argument struct.
+struct TrackView {
+    const pgx_keypoint *kp;       // [F][stride] by slot
+    const int32_t *frame_ids;     // [F] slot -> frame, nullptr = identity
+    const int32_t *offsets;       // [n_tracks + 1]
+    const int32_t *nodes;         // [node_cap][2] = (frame, keypoint)
+    const int32_t *track_summary; // [0] = n_tracks
+    int F, stride, n_frames, max_tracks;
+    long long node_cap;           // entries of nodes (and of a per-node output) an offset may reach
+    int32_t *inv;                 // workspace [n_frames] frame -> slot, -1 = none (build_slot_inverse)
+};
+
+// Hands out 256-byte-aligned sections of a workspace, so that a stage describes its layout once: the launcher carves
+// the real buffer, *_ws_bytes the null one and reads total().
+struct WsCarver {
+    char *base;
+    size_t at = 0;
+    explicit WsCarver(void *ws) : base(static_cast<char *>(ws)) {}
+    static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+    size_t put(size_t bytes)   // the section's offset
+    {
+        const size_t p = at;
+        at += align256(bytes);
+        return p;
+    }
+    template <class T> T *take(size_t bytes)
+    {
+        const size_t p = put(bytes);
+        return base ? reinterpret_cast<T *>(base + p) : nullptr;
+    }
+    size_t total() const { return at; }
+};
+
+#ifdef __HIPCC__
+
+// ---- the graph --------------------------------------------------------------------------------------------------------
+
+// nodes [o0, o0 + n) of track t; false (and n = 0) for malformed offsets
+__device__ __forceinline__ bool track_range(const TrackView &tv, long long t, int &o0, int &n)
+{
+    o0 = tv.offsets[t];
+    const int o1 = tv.offsets[t + 1];
+    const bool bad = o0 < 0 || o1 < o0 || (long long)o1 > tv.node_cap;
+    n = bad ? 0 : o1 - o0;
+    return !bad;
+}
+
+// node (f, k) names a frame that a slot holds and a keypoint slot of it
+__device__ __forceinline__ bool node_ok(const TrackView &tv, int f, int k)
+{
+    return !(f < 0 || f >= tv.n_frames || k < 0 || k >= tv.stride || tv.inv[f] < 0);
+}
+
+// keypoint of a node that is node_ok
+__device__ __forceinline__ void node_keypoint(const TrackView &tv, int f, int k, double &u, double &v)
+{
+    const pgx_keypoint p = tv.kp[(size_t)tv.inv[f] * tv.stride + k];
+    u = (double)p.x;
+    v = (double)p.y;
+}
+
+// One workgroup, after inv[] = -1 and a barrier: the inverse of the slot -> frame map; a second slot naming a frame
+// raises dup_bit.  The caller places the barrier behind it.
+__device__ __forceinline__ void build_slot_inverse(const TrackView &tv, int *status, unsigned dup_bit)
+{
+    for (int s = threadIdx.x; s < tv.F; s += blockDim.x) {
+        const int f = tv.frame_ids ? tv.frame_ids[s] : s;
+        if (f < 0 || f >= tv.n_frames) continue;
+        if (atomicCAS(&tv.inv[f], -1, s) != -1) atomicOr(status, (int)dup_bit);
+    }
+}
+
+// tracks to process = clamp(n_tracks, 0, max_tracks); more than max_tracks raises cap_bit (one thread calls this)
+__device__ __forceinline__ int clamp_tracks(const TrackView &tv, int *status, unsigned cap_bit)
+{
+    int nt = tv.track_summary[0];
+    nt = nt < 0 ? 0 : nt;
+    if (nt > tv.max_tracks) {
+        atomicOr(status, (int)cap_bit);
+        nt = tv.max_tracks;
+    }
+    return nt;
+}
+
+// Grid-stride loop over the tracks t < nt with G lanes per track (G a power of two <= 64): declares gid, ngroups, lane.
+#define PGX_TRACK_LOOP(G, nt)                                                                \
+    const long long gid = ((long long)blockIdx.x * blockDim.x + threadIdx.x) / (G);         \
+    const long long ngroups = (long long)gridDim.x * blockDim.x / (G);                       \
+    const int lane = threadIdx.x & ((G) - 1);                                                \
+    for (long long t = gid; t < (nt); t += ngroups)
+
+// ---- reductions over the G lanes of a group: xor butterflies, identical bits in every lane ----------------------------
+
+__device__ __forceinline__ double nan_max(double a, double b)
+{
+    if (a != a || b != b) return __builtin_nan("");
+    return a > b ? a : b;
+}
+
+template <int G> __device__ __forceinline__ double gsum(double x)
+{
+#pragma unroll
+    for (int m = 1; m < G; m <<= 1) x += __shfl_xor(x, m, G);
+    return x;
+}
+template <int G> __device__ __forceinline__ int gsum_i(int x)
+{
+#pragma unroll
+    for (int m = 1; m < G; m <<= 1) x += __shfl_xor(x, m, G);
+    return x;
+}
+template <int G> __device__ __forceinline__ double gmax(double x)
+{
+#pragma unroll
+    for (int m = 1; m < G; m <<= 1) x = nan_max(x, __shfl_xor(x, m, G));
+    return x;
+}
+
+// ---- cameras ----------------------------------------------------------------------------------------------------------
+
+// R' = Exp(omega) R (Rodrigues); R, Ro row-major 3x3
+__device__ __forceinline__ void rotate_left(const double *om, const double *R, double *Ro)
+{
+    const double th2 = om[0] * om[0] + om[1] * om[1] + om[2] * om[2];
+    double A, B;
+    if (th2 < 1e-8) {
+        A = 1.0 - th2 / 6.0;
+        B = 0.5 - th2 / 24.0;
+    } else {
+        const double th = sqrt(th2);
+        A = sin(th) / th;
+        B = (1.0 - cos(th)) / th2;
+    }
+    const double wx = om[0], wy = om[1], wz = om[2];
+    // E = I + A [w]x + B [w]x^2, [w]x^2 = w w^T - th2 I
+    double E[9];
+    E[0] = 1.0 + B * (wx * wx - th2);
+    E[1] = -A * wz + B * (wx * wy);
+    E[2] = A * wy + B * (wx * wz);
+    E[3] = A * wz + B * (wy * wx);
+    E[4] = 1.0 + B * (wy * wy - th2);
+    E[5] = -A * wx + B * (wy * wz);
+    E[6] = -A * wy + B * (wz * wx);
+    E[7] = A * wx + B * (wz * wy);
+    E[8] = 1.0 + B * (wz * wz - th2);
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+#pragma unroll
+        for (int c = 0; c < 3; c++) Ro[3 * r + c] = (E[3 * r] * R[c] + E[3 * r + 1] * R[3 + c]) + E[3 * r + 2] * R[6 + c];
+}
+
+// P = K [R | t] of r = (R row-major, t), K = (fx, fy, cx, cy); NaN rows when the camera is not known
+__device__ __forceinline__ void camera_matrix(const double *K, const double (&r)[12], bool known, double *P)
+{
+    const double NaN = __builtin_nan("");
+    // column j of [R | t]: (r[j], r[3 + j], r[6 + j]) for j < 3, (t0, t1, t2) for j = 3
+    for (int j = 0; j < 4; j++) {
+        const double c0 = j < 3 ? r[j] : r[9], c1 = j < 3 ? r[3 + j] : r[10], c2 = j < 3 ? r[6 + j] : r[11];
+        P[j] = known ? K[0] * c0 + K[2] * c2 : NaN;
+        P[4 + j] = known ? K[1] * c1 + K[3] * c2 : NaN;
+        P[8 + j] = known ? c2 : NaN;
+    }
+}
+
+// ---- sampling ---------------------------------------------------------------------------------------------------------
+
+__device__ __forceinline__ uint64_t splitmix64(uint64_t &s)
+{
+    uint64_t z = (s += 0x9E3779B97F4A7C15ull);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+#endif // __HIPCC__
