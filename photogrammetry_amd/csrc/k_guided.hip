@@ -19,7 +19,7 @@
 //      candidate is decided by the exact predicate; admissible ones get the xor + popcount distance and enter the row's top-2
 //      as (distance << 20 | column) keys, and the column side as a global atomic min of (distance << 20 | row).
 // The NN lists reuse k_knn.hip's selection (pgx_launch_knn_select), so the acceptance rules are those of pgx_match_nn_batch_dev.
-#include "pgx_internal.h"
+#include "pgx_pairlist.h"
 
 #include <climits>
 #include <cmath>
@@ -33,8 +33,6 @@ constexpr int COORD_LIM = 1 << 20; // used coordinates must lie in [-2^20, 2^20)
 
 // slot header fields
 enum { H_BAD = 0, H_N, H_MINX, H_MINY, H_MAXX, H_MAXY, H_SHIFT, H_GX, H_GY };
-
-__device__ __forceinline__ int clamp_n(int n, int max_n) { return n < 0 ? 0 : (n > max_n ? max_n : n); }
 
 // the workspace of one chunk (laid out by guided_layout on the host)
 struct GuidedWs {
@@ -98,7 +96,7 @@ __global__ __launch_bounds__(GB) void k_guided_bucket(const pgx_keypoint *__rest
     const int s = blockIdx.x, tid = threadIdx.x;
     if (s >= *w.cnt) return;
     const int f = w.slot_frame[s];
-    const int n = clamp_n(counts[f], max_n);
+    const int n = pgx_clamp_count(counts[f], max_n);
     char *base = w.slots + (size_t)s * w.slot_bytes;
     int *hdr = reinterpret_cast<int *>(base);
     int *off = reinterpret_cast<int *>(base + w.off_offsets);
@@ -212,8 +210,7 @@ __global__ __launch_bounds__(GB) void k_guided_walk(const uint32_t *__restrict__
 #pragma clang fp contract(off) // the predicate of include/pgx.h: one rounding per operation, no FMA
     int m, bx;
     pgx_xcd_map(blockIdx.x, nrb, M, m, bx);
-    const int fa = pairlist[2 * m], fb = pairlist[2 * m + 1];
-    const int n1 = clamp_n(counts[fa], max_n), n2 = clamp_n(counts[fb], max_n);
+    const auto [fa, fb, n1, n2] = pgx_pair_counts(counts, pairlist, m, max_n);
     const int t = bx * GB + threadIdx.x;
     if (t >= n1) return;
     const SlotView A = slot_view(w, w.tab_slot[w.side_pos[2 * m]]);
@@ -300,34 +297,7 @@ __global__ __launch_bounds__(GB) void k_guided_walk(const uint32_t *__restrict__
         }
     }
     const size_t o = ((size_t)m * S + i) * K;
-    out_idx[o] = k1 == PGX_KEY_NONE ? -1 : (int32_t)(k1 & PGX_IDX_MASK);
-    out_dist[o] = k1 == PGX_KEY_NONE ? PGX_DIST_NONE : (int32_t)(k1 >> PGX_IDX_BITS);
-    if (K == 2) {
-        out_idx[o + 1] = k2 == PGX_KEY_NONE ? -1 : (int32_t)(k2 & PGX_IDX_MASK);
-        out_dist[o + 1] = k2 == PGX_KEY_NONE ? PGX_DIST_NONE : (int32_t)(k2 >> PGX_IDX_BITS);
-    }
-}
-
-// column keys: (distance << 20 | row) during the walk, the row index (or -1) after it
-__global__ __launch_bounds__(GB) void k_guided_col_init(const int32_t *__restrict__ counts, const int32_t *__restrict__ pairlist,
-                                                        int S, int max_n, int ncb, int M, uint32_t *__restrict__ colkey)
-{
-    int m, bx;
-    pgx_xcd_map(blockIdx.x, ncb, M, m, bx);
-    const int j = bx * GB + threadIdx.x;
-    if (j < clamp_n(counts[pairlist[2 * m + 1]], max_n)) colkey[(size_t)m * S + j] = PGX_KEY_NONE;
-}
-
-__global__ __launch_bounds__(GB) void k_guided_col_finish(const int32_t *__restrict__ counts, const int32_t *__restrict__ pairlist,
-                                                          int S, int max_n, int ncb, int M, uint32_t *__restrict__ colkey)
-{
-    int m, bx;
-    pgx_xcd_map(blockIdx.x, ncb, M, m, bx);
-    const int j = bx * GB + threadIdx.x;
-    if (j < clamp_n(counts[pairlist[2 * m + 1]], max_n)) {
-        const uint32_t k = colkey[(size_t)m * S + j];
-        colkey[(size_t)m * S + j] = k == PGX_KEY_NONE ? 0xFFFFFFFFu : (k & PGX_IDX_MASK);
-    }
+    pgx_store_keys<K>(k1, k2, out_idx + o, out_dist + o);
 }
 
 int table_size(int E)
@@ -359,26 +329,6 @@ GuidedWs guided_layout(void *ws, int M, int max_n)
     return w;
 }
 
-template <int K, bool COL, int W>
-void launch_walk(hipStream_t s, unsigned grid, const uint32_t *d_desc, const int32_t *d_counts, const int32_t *d_pairlist, int S,
-                 int words, int max_n, int nrb, int M, const float *d_F, double band, double T, const GuidedWs &w, int32_t *d_idx,
-                 int32_t *d_dist, uint32_t *ck)
-{
-    hipLaunchKernelGGL((k_guided_walk<K, COL, W>), dim3(grid), dim3(GB), 0, s, d_desc, d_counts, d_pairlist, S, words, max_n, nrb, M,
-                       d_F, band, T, w, d_idx, d_dist, ck);
-}
-
-template <int W>
-void launch_walk_w(int k, bool col, hipStream_t s, unsigned grid, const uint32_t *d_desc, const int32_t *d_counts,
-                   const int32_t *d_pairlist, int S, int words, int max_n, int nrb, int M, const float *d_F, double band, double T,
-                   const GuidedWs &w, int32_t *d_idx, int32_t *d_dist, uint32_t *ck)
-{
-    if (k == 1 && !col) launch_walk<1, false, W>(s, grid, d_desc, d_counts, d_pairlist, S, words, max_n, nrb, M, d_F, band, T, w, d_idx, d_dist, ck);
-    else if (k == 1) launch_walk<1, true, W>(s, grid, d_desc, d_counts, d_pairlist, S, words, max_n, nrb, M, d_F, band, T, w, d_idx, d_dist, ck);
-    else if (!col) launch_walk<2, false, W>(s, grid, d_desc, d_counts, d_pairlist, S, words, max_n, nrb, M, d_F, band, T, w, d_idx, d_dist, ck);
-    else launch_walk<2, true, W>(s, grid, d_desc, d_counts, d_pairlist, S, words, max_n, nrb, M, d_F, band, T, w, d_idx, d_dist, ck);
-}
-
 } // namespace
 
 size_t pgx_guided_ws_bytes(int M, int max_n)
@@ -400,19 +350,20 @@ void pgx_launch_guided(pgx_ctx *ctx, hipStream_t s, const uint32_t *d_desc, cons
         (void)hipMemsetAsync(w.tab_key, 0xFF, (size_t)w.H * sizeof(int), s);
         hipLaunchKernelGGL(k_guided_slots, dim3((unsigned)((E + GB - 1) / GB)), dim3(GB), 0, s, d_pairlist, E, w);
         hipLaunchKernelGGL(k_guided_bucket, dim3((unsigned)E), dim3(GB), 0, s, d_kp, d_counts, S, max_n, w, status);
-        if (ck) hipLaunchKernelGGL(k_guided_col_init, dim3((unsigned)nb * M), dim3(GB), 0, s, d_counts, d_pairlist, S, max_n, nb, M, ck);
+        if (ck) pgx_launch_colkeys(ctx, s, nullptr, false, d_counts, d_pairlist, M, S, max_n, d_col);
     }
     {
         ProfScope ps(ctx, "guided_walk", s);
         const double bd = (double)band, T = bd * bd;
         const unsigned grid = (unsigned)nb * (unsigned)M;
-        if (words == 8)
-            launch_walk_w<8>(k, ck != nullptr, s, grid, d_desc, d_counts, d_pairlist, S, words, max_n, nb, M, d_F, bd, T, w, d_idx, d_dist, ck);
-        else
-            launch_walk_w<0>(k, ck != nullptr, s, grid, d_desc, d_counts, d_pairlist, S, words, max_n, nb, M, d_F, bd, T, w, d_idx, d_dist, ck);
+        auto walk = [&](auto K, auto COL, auto W) { // W: the descriptor words a thread keeps in registers (0: any width, from memory)
+            hipLaunchKernelGGL((k_guided_walk<decltype(K)::value, decltype(COL)::value, decltype(W)::value>), dim3(grid), dim3(GB), 0, s,
+                               d_desc, d_counts, d_pairlist, S, words, max_n, nb, M, d_F, bd, T, w, d_idx, d_dist, ck);
+        };
+        pgx_dispatch_k_col(k, ck != nullptr, [&](auto K, auto COL) {
+            if (words == 8) walk(K, COL, std::integral_constant<int, 8>{});
+            else walk(K, COL, std::integral_constant<int, 0>{});
+        });
     }
-    if (ck) {
-        ProfScope ps(ctx, "guided_col", s);
-        hipLaunchKernelGGL(k_guided_col_finish, dim3((unsigned)nb * M), dim3(GB), 0, s, d_counts, d_pairlist, S, max_n, nb, M, ck);
-    }
+    if (ck) pgx_launch_colkeys(ctx, s, "guided_col", true, d_counts, d_pairlist, M, S, max_n, d_col);
 }

@@ -3,7 +3,7 @@
 // row) order, and the selection (distance gate, ratio test, cross-check) that makes a match list for the track graph of these.
 //
 // 256-bit descriptors (words == 8) run on the block-scaled FP4 matrix instruction with the arithmetic of k_ham_fp4
-// (k_match_mfma.inc, whose header derives it): acc = F4_BIAS + 8192 * dot + C exactly, dot = 256 - 2 * hamming, and the C input
+// (pgx_fp4.h derives it): acc = F4_BIAS + 8192 * dot + C exactly, dot = 256 - 2 * hamming, and the C input
 // carries a 14-bit key so that every selection is an INTEGER maximum of raw accumulator bits.  What differs from k_ham_fp4:
 //   * a workgroup owns one row block and walks ALL columns of its image pair, in chunks of at most 4096 (the key's 7-bit tile
 //     field): a row's two nearest columns are final inside the workgroup (merged over chunks as distance << 20 | column keys),
@@ -18,7 +18,8 @@
 //     would come back as a second neighbour); row slots past the end repeat the last row as in k_ham_fp4 (a duplicate ties with
 //     its original at a larger row position and never wins a column; its own row results are not written).
 // Other widths: plain xor + popcount, one thread per row (top-2) and one per column (nearest row).  Exact; its speed is no target.
-#include "pgx_internal.h"
+#include "pgx_fp4.h"
+#include "pgx_pairlist.h"
 
 #include <hip/hip_ext.h>
 
@@ -26,33 +27,7 @@
 
 namespace {
 
-using i32x8 = int __attribute__((ext_vector_type(8)));
-using i32x16 = int __attribute__((ext_vector_type(16)));
-using f32x16 = float __attribute__((ext_vector_type(16)));
-
-constexpr int KNN_CHUNK = 4096;            // columns per pass: 128 tiles = the 7-bit tile field of the key
-constexpr int F4_BIAS = (1 << 23) + (1 << 21);
-constexpr int F4_RAW0 = 0x4B000000 + (1 << 21); // raw bits of (float)F4_BIAS
-constexpr int F4_SCALE_A = 140;                 // E8M0: 2^13
-
-// the fp4 expansion of k_match_mfma.inc: bit set -> code of -1 (0xA), clear -> +1 (0x2); with both masks in registers
-// (x & m) | c is one v_and_or_b32
-__device__ __forceinline__ int and_or(uint32_t x, int m, int c) { return (int)((x & (uint32_t)m) | (uint32_t)c); }
-
-__device__ __forceinline__ void expand_fp4(uint32_t w, int km, int kc, int (&d)[4])
-{
-    d[0] = and_or(w, km, kc);
-    d[1] = and_or(w << 1, km, kc);
-    d[2] = and_or(w << 2, km, kc);
-    d[3] = and_or(w << 3, km, kc);
-}
-
-__device__ __forceinline__ int max16i(const i32x16 &v)
-{
-    const int m0 = max(max(v[0], v[1]), v[2]), m1 = max(max(v[3], v[4]), v[5]), m2 = max(max(v[6], v[7]), v[8]);
-    const int m3 = max(max(v[9], v[10]), v[11]), m4 = max(max(v[12], v[13]), v[14]);
-    return max(max(max(m0, m1), m2), max(max(m3, m4), v[15]));
-}
+constexpr int KNN_CHUNK = F4_CHUNK; // columns per pass
 
 // one DPP step of the half-wave merge: (v1 > v2) with the partner lane's pair; lanes of masked-off rows see (INT_MIN, INT_MIN)
 template <int CTRL, int ROWMASK>
@@ -91,8 +66,6 @@ __device__ __forceinline__ void merge_min2(uint32_t &k1, uint32_t &k2, uint32_t 
     k1 = min(k1, n1);
 }
 
-__device__ __forceinline__ int clamp_count(int n, int max_n) { return n < 0 ? 0 : (n > max_n ? max_n : n); }
-
 // ---- 256-bit descriptors on the FP4 matrix instruction -------------------------------------------------------------------
 // idx / dist [M][S][K]; colkey [M][S] (COL): entries j < counts[b] hold PGX_KEY_NONE on entry (k_knn_col_init).
 // Held to 240 registers and two waves per SIMD like k_ham_fp4 (tests/test_knn_codegen.py pins it on the code object).
@@ -107,8 +80,7 @@ __attribute__((amdgpu_num_vgpr(120))) __global__ __launch_bounds__(256, 2) void 
     __shared__ uint32_t rowtop[2][KNN_BM]; // running (distance << 20 | column) keys of every row, min order; row owned by one lane
     int m, bx;
     pgx_xcd_map(blockIdx.x, nrb, M, m, bx); // all row blocks of one image pair on one XCD: they stream the same columns
-    const int fa = pairlist[2 * m], fb = pairlist[2 * m + 1];
-    const int n1 = clamp_count(counts[fa], max_n), n2 = clamp_count(counts[fb], max_n);
+    const auto [fa, fb, n1, n2] = pgx_pair_counts(counts, pairlist, m, max_n);
     const int rb = bx * KNN_BM;
     if (rb >= n1) return;
     const int tid = threadIdx.x;
@@ -273,26 +245,19 @@ __attribute__((amdgpu_num_vgpr(120))) __global__ __launch_bounds__(256, 2) void 
 #pragma unroll
         for (int t = 0; t < RT; t++) {
             const int iloc = wv3 * KNN_WROWS + t * 32 + (g & 3) + 8 * (g >> 2) + 4 * h3, i = rb + iloc;
-            if (i < n1) {
-                const uint32_t kk[2] = {rowtop[0][iloc], rowtop[1][iloc]};
-#pragma unroll
-                for (int e = 0; e < K; e++) {
-                    oidx[(size_t)i * K + e] = kk[e] == PGX_KEY_NONE ? -1 : (int)(kk[e] & PGX_IDX_MASK);
-                    odist[(size_t)i * K + e] = kk[e] == PGX_KEY_NONE ? PGX_DIST_NONE : (int)(kk[e] >> PGX_IDX_BITS);
-                }
-            }
+            if (i < n1) pgx_store_keys<K>(rowtop[0][iloc], rowtop[1][iloc], oidx + (size_t)i * K, odist + (size_t)i * K);
         }
     }
 }
 
-// column output as keys: NONE for j < counts[b] of every pair
+// column output as keys, (distance << 20 | row) while a producer runs (k_knn_fp4, k_guided_walk): NONE for j < counts[b] of every pair
 __global__ __launch_bounds__(256) void k_knn_col_init(const int32_t *__restrict__ counts, const int32_t *__restrict__ pairlist,
                                                       int S, int max_n, int ncb, int M, uint32_t *__restrict__ colkey)
 {
     int m, bx;
     pgx_xcd_map(blockIdx.x, ncb, M, m, bx);
     const int j = bx * 256 + threadIdx.x;
-    if (j < clamp_count(counts[pairlist[2 * m + 1]], max_n)) colkey[(size_t)m * S + j] = PGX_KEY_NONE;
+    if (j < pgx_clamp_count(counts[pairlist[2 * m + 1]], max_n)) colkey[(size_t)m * S + j] = PGX_KEY_NONE;
 }
 
 // keys -> row indices (-1: no row)
@@ -302,7 +267,7 @@ __global__ __launch_bounds__(256) void k_knn_col_finish(const int32_t *__restric
     int m, bx;
     pgx_xcd_map(blockIdx.x, ncb, M, m, bx);
     const int j = bx * 256 + threadIdx.x;
-    if (j < clamp_count(counts[pairlist[2 * m + 1]], max_n)) {
+    if (j < pgx_clamp_count(counts[pairlist[2 * m + 1]], max_n)) {
         const uint32_t k = colkey[(size_t)m * S + j];
         colkey[(size_t)m * S + j] = k == PGX_KEY_NONE ? 0xFFFFFFFFu : (k & PGX_IDX_MASK);
     }
@@ -316,8 +281,7 @@ __global__ __launch_bounds__(256) void k_knn_rows_valu(const uint32_t *__restric
 {
     int m, bx;
     pgx_xcd_map(blockIdx.x, nrb, M, m, bx);
-    const int fa = pairlist[2 * m], fb = pairlist[2 * m + 1];
-    const int n1 = clamp_count(counts[fa], max_n), n2 = clamp_count(counts[fb], max_n);
+    const auto [fa, fb, n1, n2] = pgx_pair_counts(counts, pairlist, m, max_n);
     const int i = bx * 256 + threadIdx.x;
     if (i >= n1) return;
     const uint32_t *a = desc + ((size_t)fa * S + i) * words, *B = desc + (size_t)fb * S * words;
@@ -340,8 +304,7 @@ __global__ __launch_bounds__(256) void k_knn_cols_valu(const uint32_t *__restric
 {
     int m, bx;
     pgx_xcd_map(blockIdx.x, ncb, M, m, bx);
-    const int fa = pairlist[2 * m], fb = pairlist[2 * m + 1];
-    const int n1 = clamp_count(counts[fa], max_n), n2 = clamp_count(counts[fb], max_n);
+    const auto [fa, fb, n1, n2] = pgx_pair_counts(counts, pairlist, m, max_n);
     const int j = bx * 256 + threadIdx.x;
     if (j >= n2) return;
     const uint32_t *b = desc + ((size_t)fb * S + j) * words, *A = desc + (size_t)fa * S * words;
@@ -363,7 +326,7 @@ __global__ __launch_bounds__(256) void k_knn_select(const int32_t *__restrict__ 
 {
     int m, bx;
     pgx_xcd_map(blockIdx.x, nrb, M, m, bx);
-    const int n1 = clamp_count(counts[pairlist[2 * m]], max_n);
+    const int n1 = pgx_clamp_count(counts[pairlist[2 * m]], max_n);
     const int i = bx * 256 + threadIdx.x;
     if (i >= n1) return;
     const size_t o = (size_t)m * S + i;
@@ -400,24 +363,25 @@ void launch_fp4(pgx_ctx *ctx, hipStream_t s, const uint32_t *d_desc, const int32
 
 } // namespace
 
+void pgx_launch_colkeys(pgx_ctx *ctx, hipStream_t s, const char *scope, bool finish, const int32_t *d_counts,
+                        const int32_t *d_pairlist, int M, int S, int max_n, int32_t *d_col)
+{
+    const int nb = (max_n + 255) / 256;
+    ProfScope ps(ctx, scope, s);
+    hipLaunchKernelGGL(finish ? k_knn_col_finish : k_knn_col_init, dim3((unsigned)nb * M), dim3(256), 0, s, d_counts, d_pairlist, S, max_n,
+                       nb, M, reinterpret_cast<uint32_t *>(d_col));
+}
+
 void pgx_launch_knn(pgx_ctx *ctx, hipStream_t s, const uint32_t *d_desc, const int32_t *d_counts, const int32_t *d_pairlist, int M,
                     int S, int words, int max_n, int k, int32_t *d_idx, int32_t *d_dist, int32_t *d_col)
 {
     const int nb = (max_n + 255) / 256; // 256-row blocks (KNN_BM) and 256-column blocks per image pair
     if (words == 8) {
-        uint32_t *ck = reinterpret_cast<uint32_t *>(d_col);
-        if (d_col) {
-            ProfScope ps(ctx, "knn_col", s);
-            hipLaunchKernelGGL(k_knn_col_init, dim3((unsigned)nb * M), dim3(256), 0, s, d_counts, d_pairlist, S, max_n, nb, M, ck);
-        }
-        if (k == 1 && !d_col) launch_fp4<1, false>(ctx, s, d_desc, d_counts, d_pairlist, M, S, max_n, d_idx, d_dist, d_col);
-        else if (k == 1) launch_fp4<1, true>(ctx, s, d_desc, d_counts, d_pairlist, M, S, max_n, d_idx, d_dist, d_col);
-        else if (!d_col) launch_fp4<2, false>(ctx, s, d_desc, d_counts, d_pairlist, M, S, max_n, d_idx, d_dist, d_col);
-        else launch_fp4<2, true>(ctx, s, d_desc, d_counts, d_pairlist, M, S, max_n, d_idx, d_dist, d_col);
-        if (d_col) {
-            ProfScope ps(ctx, "knn_col", s);
-            hipLaunchKernelGGL(k_knn_col_finish, dim3((unsigned)nb * M), dim3(256), 0, s, d_counts, d_pairlist, S, max_n, nb, M, ck);
-        }
+        if (d_col) pgx_launch_colkeys(ctx, s, "knn_col", false, d_counts, d_pairlist, M, S, max_n, d_col);
+        pgx_dispatch_k_col(k, d_col != nullptr, [&](auto K, auto COL) {
+            launch_fp4<decltype(K)::value, decltype(COL)::value>(ctx, s, d_desc, d_counts, d_pairlist, M, S, max_n, d_idx, d_dist, d_col);
+        });
+        if (d_col) pgx_launch_colkeys(ctx, s, "knn_col", true, d_counts, d_pairlist, M, S, max_n, d_col);
         return;
     }
     ProfScope ps(ctx, "knn", s);

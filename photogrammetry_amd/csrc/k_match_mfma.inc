@@ -1,72 +1,11 @@
 // k_match_mfma.inc -- the Hamming distance on the matrix pipe (included by k_match.hip; 256-bit descriptors = 8 words).
-//
-// hamming(a, b) = (K - a.b) / 2 for a, b in {-1,+1}^K (K = 256).  Every descriptor bit is expanded IN THE KERNEL
-// (registers only, never in HBM) to the fp4 code of -+1 and fed to v_mfma_scale_f32_32x32x64_f8f6f4; the C input carries
-// the argmin keys, so that BOTH argmins are plain integer maxima of accumulators -- no per-element masking:
-//   * row side (best column of every row): a lane always holds the same rows and, in tile ct, column ct*32 + (lane & 31);
-//     rbest[reg] = max(rbest[reg], acc[reg]) orders by (dot, smaller ct): ONE v_max per element, lanes are combined once,
-//     after the last tile.
-//   * column side (best row of every column): the 16 registers of a lane are 16 rows of one column; max over them
-//     (v_max3 tree) orders by (dot, smaller row); the winner's tile field is swapped for the wave's row offset and posted
-//     with an LDS atomic max.
-// C/D lane map (cdna_hip_programming.md section 3): col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5).
+// The arithmetic (fp4 expansion, biased accumulators, key fields) is derived in pgx_fp4.h, which k_knn.hip shares.
+#include "pgx_fp4.h"
 
 namespace {
 
-using i32x4 = int __attribute__((ext_vector_type(4)));
-using i32x16 = int __attribute__((ext_vector_type(16)));
-
 constexpr int HAM_PAD = 4;      // pad tiles in front of k_ham_fp4's staged column offsets (its prefetch ring runs four tiles ahead, downwards)
-constexpr int MF_CHUNK = 4096;   // most columns one workgroup walks (LDS column-best array); 128 tiles = the 7-bit ct field
-
-// ---- distance + argmin on the block-scaled FP4 matrix instruction ----------------------------------------------------
-// v_mfma_scale_f32_32x32x64_f8f6f4 with e2m1 operands takes the cycles of the int8 32x32x32 form at twice the K: a
-// descriptor bit becomes the fp4 code of -1 (set, 0xA) or +1 (clear, 0x2), four MFMAs cover the 256 bits, and the A
-// operand's block scale (E8M0 byte 140 = 2^13) puts the dot product above the key field:
-//     acc = 8192 * dot + C      exactly (|8192 * dot| <= 2^21, C < 2^14: all integers below 2^24 in f32)
-// Products and sums of +-1 are exact in any order (tools/probe/fp4_probe.hip checks the instruction against popcounts
-// over the whole distance range).  dot = 256 - 2 * hamming is even, so
-// acc = 16384 * (dot / 2) + C: 14 key bits.  C[reg] of column tile ct = (127 - ct) << 7 | (127 - row position inside the
-// wave's RT x 32 rows); both argmins are maxima of accumulators.
-// Bit -> k-slot assignment: MFMA s takes word s (lanes 0..31) and word 4 + s (lanes 32..63) of the descriptor, so a lane
-// loads ONE 16-byte quarter of its row / column; dword q of a fragment = ((word << q) & 0x88888888) | 0x22222222.
-// No LDS operand staging and no barrier in the loop: every wavefront expands the columns it needs itself (the fp4
-// expansion is 7 VALU per 32 bits; shared staging through LDS costs a workgroup barrier per 32-column tile: 35 % of the
-// wave time of round 2's int8 kernel, which worked that way).  A wavefront keeps RT row tiles (RT x 16 fragment registers); LDS holds the column indices and the column
-// bests of the workgroup.
-using i32x8 = int __attribute__((ext_vector_type(8)));
-using f32x16 = float __attribute__((ext_vector_type(16)));
-
-// (x & m) | c in one instruction: the masks do not fit inline constants and a VOP3 takes no 32-bit literal on gfx9, so
-// with literal masks the compiler emits v_and + v_or; with both constants in registers (made opaque once per kernel) it
-// selects v_and_or_b32.  Plain C rather than inline asm: the hazard recogniser does not look inside an asm statement, and
-// the result feeds an MFMA operand.
-__device__ __forceinline__ int and_or(uint32_t x, int m, int c) { return (int)((x & (uint32_t)m) | (uint32_t)c); }
-
-__device__ __forceinline__ void expand_fp4(uint32_t w, int km, int kc, int &d0, int &d1, int &d2, int &d3)
-{
-    d0 = and_or(w, km, kc);
-    d1 = and_or(w << 1, km, kc);
-    d2 = and_or(w << 2, km, kc);
-    d3 = and_or(w << 3, km, kc);
-}
-
-// Accumulators carry a bias of 2^23 + 2^21, which puts every value into ONE binade, [2^23, 2^24): there f32 has unit spacing, the
-// raw register is F4_RAW0 + (16384 * (dot / 2) + key) -- an affine image of the value -- so all maxima are INTEGER maxima of the
-// raw registers (v_max_i32 / v_max3_i32; fmaxf would cost a canonicalising v_max x, x, x per operand on top: 204 instead of
-// 64 max instructions per step, measured) and key fields are moved with integer adds on the raw bits, no conversions.
-constexpr int F4_BIAS = (1 << 23) + (1 << 21);
-constexpr int F4_RAW0 = 0x4B000000 + (1 << 21); // raw bits of (float)F4_BIAS
-constexpr int F4_SCALE_A = 140; // E8M0: 2^(140 - 127) = 8192
-
-__device__ __forceinline__ int max16i(const i32x16 &v)
-{
-    // 16 values in 8 instructions (7 v_max3 + 1 v_max; the tree of pairs that stood here before took 9)
-    const int m0 = max(max(v[0], v[1]), v[2]), m1 = max(max(v[3], v[4]), v[5]), m2 = max(max(v[6], v[7]), v[8]);
-    const int m3 = max(max(v[9], v[10]), v[11]), m4 = max(max(v[12], v[13]), v[14]);
-    const int n0 = max(max(m0, m1), m2), n1 = max(max(m3, m4), v[15]);
-    return max(n0, n1);
-}
+constexpr int MF_CHUNK = F4_CHUNK; // most columns one workgroup walks (LDS column-best array)
 
 // signed maximum over each half (32 lanes) of a fully active wavefront by DPP row operations: quads, 8, 16 lanes, then
 // row_bcast:15 carries rows 0 and 2 into rows 1 and 3.  Complete in lanes 16..31 and 48..63; no LDS crossbar traffic
@@ -130,10 +69,10 @@ __device__ __forceinline__ void ham_block(const PairWs &p, const uint32_t *__res
         const int row = rb + wv * WROWS + t * 32 + r;
         const uint32_t oi = rows[row < n1 ? row : n1 - 1];
         const uint4 w = *reinterpret_cast<const uint4 *>(dA + (size_t)oi * 8 + 4 * h);
-        expand_fp4(w.x, km, kc, afr[t][0][0], afr[t][0][1], afr[t][0][2], afr[t][0][3]);
-        expand_fp4(w.y, km, kc, afr[t][1][0], afr[t][1][1], afr[t][1][2], afr[t][1][3]);
-        expand_fp4(w.z, km, kc, afr[t][2][0], afr[t][2][1], afr[t][2][2], afr[t][2][3]);
-        expand_fp4(w.w, km, kc, afr[t][3][0], afr[t][3][1], afr[t][3][2], afr[t][3][3]);
+        expand_fp4(w.x, km, kc, afr[t][0]);
+        expand_fp4(w.y, km, kc, afr[t][1]);
+        expand_fp4(w.z, km, kc, afr[t][2]);
+        expand_fp4(w.w, km, kc, afr[t][3]);
     }
     // C input of the LAST tile for row tile 0 (row tile t sits 32 t rows further down).  The tile field of the key, 127 - ct, must
     // fall with ct (equal distances: the smaller column wins); walking the tiles from the last to the first makes its step
@@ -165,10 +104,10 @@ __device__ __forceinline__ void ham_block(const PairWs &p, const uint32_t *__res
     // loads stay in flight over a step (a two-deep rotation made the compiler wait for the newest load at every loop top)
     auto step = [&](int ct, uint4 &slot) {
         int b[4][4];
-        expand_fp4(slot.x, km, kc, b[0][0], b[0][1], b[0][2], b[0][3]);
-        expand_fp4(slot.y, km, kc, b[1][0], b[1][1], b[1][2], b[1][3]);
-        expand_fp4(slot.z, km, kc, b[2][0], b[2][1], b[2][2], b[2][3]);
-        expand_fp4(slot.w, km, kc, b[3][0], b[3][1], b[3][2], b[3][3]);
+        expand_fp4(slot.x, km, kc, b[0]);
+        expand_fp4(slot.y, km, kc, b[1]);
+        expand_fp4(slot.z, km, kc, b[2]);
+        expand_fp4(slot.w, km, kc, b[3]);
         slot = fetch(ct - 4);
         int xm[RT];
         // the next tile's C input, made OUT OF PLACE before this tile's chains start (they read cc): the last chain then runs in
@@ -381,10 +320,10 @@ __global__ __launch_bounds__(256, 2) void k_tail_rows_fp4(uint32_t *ws, const ui
             const uint32_t ww[4] = {~w4.x, ~w4.y, ~w4.z, ~w4.w};
 #pragma unroll
             for (int s = 0; s < 4; s++) {
-                int f0, f1, f2, f3;
-                expand_fp4(ww[s], km, kc, f0, f1, f2, f3);
-                const i32x4 f = {f0, f1, f2, f3};
-                rfrag[rt][s][hh * 32 + sc] = f;
+                int f[4];
+                expand_fp4(ww[s], km, kc, f);
+                const i32x4 fv = {f[0], f[1], f[2], f[3]};
+                rfrag[rt][s][hh * 32 + sc] = fv;
             }
         }
         if (tid < TM_ROWS) rowmin[tid] = 0xFFFFFFFFu;
@@ -401,10 +340,10 @@ __global__ __launch_bounds__(256, 2) void k_tail_rows_fp4(uint32_t *ws, const ui
             const int col = cb + t * 32 + r;
             const uint32_t oj = cols[col < C ? col : 0];
             const uint4 w = *reinterpret_cast<const uint4 *>(dB + (size_t)oj * 8 + 4 * h);
-            expand_fp4(w.x, km, kc, afr[t][0][0], afr[t][0][1], afr[t][0][2], afr[t][0][3]);
-            expand_fp4(w.y, km, kc, afr[t][1][0], afr[t][1][1], afr[t][1][2], afr[t][1][3]);
-            expand_fp4(w.z, km, kc, afr[t][2][0], afr[t][2][1], afr[t][2][2], afr[t][2][3]);
-            expand_fp4(w.w, km, kc, afr[t][3][0], afr[t][3][1], afr[t][3][2], afr[t][3][3]);
+            expand_fp4(w.x, km, kc, afr[t][0]);
+            expand_fp4(w.y, km, kc, afr[t][1]);
+            expand_fp4(w.z, km, kc, afr[t][2]);
+            expand_fp4(w.w, km, kc, afr[t][3]);
         }
         for (int rt = 0; rt < ntr; rt++) {
             i32x4 b[4];

@@ -106,13 +106,23 @@ int sync_status(pgx_ctx *c)
     return decode_status(c, c->h_status[0]);
 }
 
+// image dimensions: PGX_OK, or PGX_E_BADARG with the text `what`
+int dims_ok(pgx_ctx *c, int W, int H, const char *what = "dimensions must fit ushort")
+{
+    return W <= 0 || H <= 0 || W > 65535 || H > 65535 ? fail(c, PGX_E_BADARG, "%s", what) : PGX_OK;
+}
+
+} // namespace
+
+// The next four are also called by pgx_comm.hip (the caller holds the context's mutex).
+
 // every check and workspace allocation of the detect chain (no kernel launch): pgx_sequence_step_dev calls it before its
 // first collective so that no rank can fail locally between two collectives
-int prepare_detect(pgx_ctx *c, int F, int W, int H, int cap)
+int pgx_prepare_detect(pgx_ctx *c, int F, int W, int H, int cap)
 {
     if (!c->params_set) return fail(c, PGX_E_NOT_CONFIGURED, "pgx_set_detect_params not called");
     if (!c->pairs_set) return fail(c, PGX_E_NOT_CONFIGURED, "pgx_set_brief_pairs not called");
-    if (W <= 0 || H <= 0 || W > 65535 || H > 65535) return fail(c, PGX_E_BADARG, "dimensions must fit ushort");
+    if (dims_ok(c, W, H) != PGX_OK) return PGX_E_BADARG;
     if (c->map_set && (c->mapW != W || c->mapH != H))
         return fail(c, PGX_E_DIM_MISMATCH, "image %dx%d vs dewarp map %dx%d (ArgumentException)", W, H, c->mapW, c->mapH);
     if (F <= 0) return PGX_OK;
@@ -133,10 +143,10 @@ int prepare_detect(pgx_ctx *c, int F, int W, int H, int cap)
 }
 
 // detect chain on device-resident frames (enqueue only)
-int enqueue_detect(pgx_ctx *c, const uint16_t *d_rgba, int F, int W, int H, pgx_keypoint *d_kp, uint32_t *d_desc,
-                   int32_t *d_counts, int32_t *d_nraw, int cap)
+int pgx_enqueue_detect(pgx_ctx *c, const uint16_t *d_rgba, int F, int W, int H, pgx_keypoint *d_kp, uint32_t *d_desc,
+                       int32_t *d_counts, int32_t *d_nraw, int cap)
 {
-    const int rcp = prepare_detect(c, F, W, H, cap);
+    const int rcp = pgx_prepare_detect(c, F, W, H, cap);
     if (rcp != PGX_OK) return rcp;
     if (F <= 0) return PGX_OK;
     const int raw_cap = c->raw_cap;
@@ -177,7 +187,7 @@ int enqueue_detect(pgx_ctx *c, const uint16_t *d_rgba, int F, int W, int H, pgx_
 }
 
 // checks and workspace allocation of the matcher for M image pairs of `stride` descriptor slots (no kernel launch)
-int prepare_match(pgx_ctx *c, int stride, int words, int M)
+int pgx_prepare_match(pgx_ctx *c, int stride, int words, int M)
 {
     if (M <= 0) return PGX_OK;
     if (stride <= 0 || stride > (1 << PGX_IDX_BITS)) return fail(c, PGX_E_BADARG, "stride must be in [1, 2^20]");
@@ -189,15 +199,15 @@ int prepare_match(pgx_ctx *c, int stride, int words, int M)
     return PGX_OK;
 }
 
-int enqueue_match(pgx_ctx *c, const uint32_t *d_desc, const int32_t *d_counts, int stride, int words,
-                  const int32_t *d_pairlist, int M, int max_n, pgx_pair *d_out)
+int pgx_enqueue_match(pgx_ctx *c, const uint32_t *d_desc, const int32_t *d_counts, int stride, int words,
+                      const int32_t *d_pairlist, int M, int max_n, pgx_pair *d_out)
 {
     // pgx_gate_match is one shot on the NEXT matcher call, whatever becomes of that call: taken and cleared before any
     // early return, so that a gate never stays armed for some later call (its event belongs to another context)
     hipEvent_t gate = c->match_gate;
     c->match_gate = nullptr;
     if (M <= 0) return PGX_OK;
-    const int rcp = prepare_match(c, stride, words, M);
+    const int rcp = pgx_prepare_match(c, stride, words, M);
     if (rcp != PGX_OK) return rcp;
     // image pairs go through in chunks so the per-pair workspace stays bounded
     const int CHUNK = c->match_chunk;
@@ -291,22 +301,6 @@ int enqueue_match(pgx_ctx *c, const uint32_t *d_desc, const int32_t *d_counts, i
     return PGX_OK;
 }
 
-} // namespace
-
-// used by pgx_comm.hip (the caller holds the context's mutex)
-int pgx_enqueue_detect(pgx_ctx *c, const uint16_t *d_rgba, int F, int W, int H, pgx_keypoint *d_kp, uint32_t *d_desc,
-                       int32_t *d_counts, int32_t *d_nraw, int cap)
-{
-    return enqueue_detect(c, d_rgba, F, W, H, d_kp, d_desc, d_counts, d_nraw, cap);
-}
-int pgx_enqueue_match(pgx_ctx *c, const uint32_t *d_desc, const int32_t *d_counts, int stride, int words,
-                      const int32_t *d_pairlist, int M, int max_n, pgx_pair *d_out)
-{
-    return enqueue_match(c, d_desc, d_counts, stride, words, d_pairlist, M, max_n, d_out);
-}
-int pgx_prepare_detect(pgx_ctx *c, int F, int W, int H, int cap) { return prepare_detect(c, F, W, H, cap); }
-int pgx_prepare_match(pgx_ctx *c, int stride, int words, int M) { return prepare_match(c, stride, words, M); }
-
 extern "C" {
 
 const char *pgx_version(void) { return PGX_VERSION_STR; }
@@ -355,13 +349,13 @@ void pgx_ctx_destroy(pgx_ctx *c)
     for (hipEvent_t ev : c->ev_pool) (void)hipEventDestroy(ev);
     DevBuf *bufs[] = {&c->d_pairs, &c->d_map, &c->ws_gray, &c->ws_seg, &c->ws_segoff, &c->ws_nraw, &c->ws_rawxy,
                       &c->ws_rawscore, &c->ws_nms, &c->ws_order, &c->ws_nkept, &c->st_a, &c->st_b, &c->st_c,
-                      &c->st_d, &c->st_e, &c->st_f, &c->ws_pose, &c->ws_tracks, &c->ws_tracks_split, &c->ws_agree, &c->ws_matchn[0], &c->ws_matchn[1], &c->ws_matchn[2], &c->ws_matchn[3], &c->ws_knn, &c->ws_guided, &c->ws_tri, &c->ws_ba, &c->ws_reg};
+                      &c->st_d, &c->st_e, &c->st_f, &c->ws_pose, &c->ws_tracks, &c->ws_tracks_split, &c->ws_agree, &c->ws_matchn[0], &c->ws_matchn[1], &c->ws_matchn[2], &c->ws_knn, &c->ws_guided, &c->ws_tri, &c->ws_ba, &c->ws_reg};
     for (DevBuf *b : bufs) b->release();
     c->pin_in.release();
     c->pin_out.release();
     if (c->d_status) (void)hipFree(c->d_status);
     if (c->h_status) (void)hipHostFree(c->h_status);
-    for (int k = 0; k < 4; k++) {
+    for (int k = 0; k < 3; k++) {
         if (c->mstream[k]) (void)hipStreamDestroy(c->mstream[k]);
         if (c->ev_wide[k]) (void)hipEventDestroy(c->ev_wide[k]);
         if (c->ev_rows[k]) (void)hipEventDestroy(c->ev_rows[k]);
@@ -409,7 +403,7 @@ int pgx_set_dewarp_map(pgx_ctx *c, const int32_t *uv, int W, int H)
     Lock l(c);
     c->cfg_epoch++;
     if (!uv) { c->map_set = false; c->mapW = c->mapH = 0; return PGX_OK; }
-    if (W <= 0 || H <= 0 || W > 65535 || H > 65535) return fail(c, PGX_E_BADARG, "map dimensions must fit ushort");
+    if (dims_ok(c, W, H, "map dimensions must fit ushort") != PGX_OK) return PGX_E_BADARG;
     const size_t bytes = (size_t)W * H * 8;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, c->d_map.ensure(bytes + 32));
@@ -424,7 +418,7 @@ int pgx_set_dewarp_coeffs(pgx_ctx *c, int W, int H, const double *coeffs, int nc
     Lock l(c);
     c->cfg_epoch++;
     if (ncoeffs != 5) return fail(c, PGX_E_BADARG, "You must pass exactly 5 distortion coefficients (ArgumentException)"); // DeWarp.cs:46-48
-    if (W <= 0 || H <= 0 || W > 65535 || H > 65535) return fail(c, PGX_E_BADARG, "map dimensions must fit ushort");
+    if (dims_ok(c, W, H, "map dimensions must fit ushort") != PGX_OK) return PGX_E_BADARG;
     const size_t bytes = (size_t)W * H * 8;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, c->d_map.ensure(bytes + 32));
@@ -544,7 +538,7 @@ int pgx_gray(pgx_ctx *c, const uint16_t *rgba, int W, int H, float *out)
 {
     if (!c || !rgba || !out) return c ? fail(c, PGX_E_BADARG, "null pointer") : PGX_E_BADARG;
     Lock l(c);
-    if (W <= 0 || H <= 0 || W > 65535 || H > 65535) return fail(c, PGX_E_BADARG, "dimensions must fit ushort");
+    if (dims_ok(c, W, H) != PGX_OK) return PGX_E_BADARG;
     const size_t npix = (size_t)W * H;
     HIPCHK(c, c->st_a.ensure(npix * 8 + 32));
     HIPCHK(c, c->st_b.ensure(npix * 4 + 32));
@@ -561,7 +555,7 @@ int pgx_fast(pgx_ctx *c, const float *gray, int W, int H, pgx_keypoint *out, int
         return c ? fail(c, PGX_E_BADARG, "null pointer") : PGX_E_BADARG;
     Lock l(c);
     if (!c->params_set) return fail(c, PGX_E_NOT_CONFIGURED, "pgx_set_detect_params not called");
-    if (W <= 0 || H <= 0 || W > 65535 || H > 65535) return fail(c, PGX_E_BADARG, "dimensions must fit ushort");
+    if (dims_ok(c, W, H) != PGX_OK) return PGX_E_BADARG;
     const size_t npix = (size_t)W * H, nseg = pgx_fast_seg_count(W, H);
     const int cap = capacity > 0 ? capacity : 1;
     HIPCHK(c, c->st_a.ensure(npix * 4 + 32));
@@ -601,7 +595,7 @@ int pgx_brief(pgx_ctx *c, const float *gray, int W, int H, const pgx_keypoint *k
         return c ? fail(c, PGX_E_BADARG, "null pointer") : PGX_E_BADARG;
     Lock l(c);
     if (!c->pairs_set) return fail(c, PGX_E_NOT_CONFIGURED, "pgx_set_brief_pairs not called");
-    if (W <= 0 || H <= 0 || W > 65535 || H > 65535) return fail(c, PGX_E_BADARG, "dimensions must fit ushort");
+    if (dims_ok(c, W, H) != PGX_OK) return PGX_E_BADARG;
     if (n == 0) return PGX_OK;
     const size_t npix = (size_t)W * H;
     HIPCHK(c, c->st_a.ensure(npix * 4 + 32));
@@ -621,7 +615,7 @@ int pgx_nms(pgx_ctx *c, const pgx_keypoint *kps, int n, int W, int H, int32_t *o
         return c ? fail(c, PGX_E_BADARG, "null pointer") : PGX_E_BADARG;
     Lock l(c);
     if (!c->params_set) return fail(c, PGX_E_NOT_CONFIGURED, "pgx_set_detect_params not called");
-    if (W <= 0 || H <= 0 || W > 65535 || H > 65535) return fail(c, PGX_E_BADARG, "dimensions must fit ushort");
+    if (dims_ok(c, W, H) != PGX_OK) return PGX_E_BADARG;
     *n_out = 0;
     if (n == 0) return PGX_OK;
     std::vector<uint32_t> xy(n);
@@ -653,6 +647,56 @@ int pgx_nms(pgx_ctx *c, const pgx_keypoint *kps, int n, int W, int H, int32_t *o
     return PGX_OK;
 }
 
+namespace {
+
+// The two-set host forms (pgx_match, pgx_knn, pgx_knn_guided) run the batch kernels on two "frames" of S slots: descriptors
+// in st_a, and in st_b the block `meta` = counts[2], pairlist[1][2], F[9]; the guided form (F not null) has keypoints too, in st_d.
+struct TwoSets {
+    int32_t meta[13]; // the upload's source: the caller keeps the struct until its sync_status
+    const uint32_t *desc;
+    const pgx_keypoint *kp;
+    const int32_t *counts, *pairlist;
+    const float *F;
+};
+int stage_two_sets(pgx_ctx *c, const uint32_t *desc1, const pgx_keypoint *kp1, int n1, const uint32_t *desc2, const pgx_keypoint *kp2,
+                   int n2, int S, int words, const float *F, TwoSets &d)
+{
+    HIPCHK(c, c->st_a.ensure((size_t)2 * S * words * 4));
+    HIPCHK(c, c->st_b.ensure(64));
+    if (F) HIPCHK(c, c->st_d.ensure((size_t)2 * S * sizeof(pgx_keypoint)));
+    int32_t(&meta)[13] = d.meta;
+    std::memset(meta, 0, sizeof meta);
+    meta[0] = n1; meta[1] = n2; meta[3] = 1;
+    if (F) std::memcpy(meta + 4, F, 9 * sizeof(float));
+    if (n1 > 0) HIPCHK(c, hipMemcpyAsync(c->st_a.p, desc1, (size_t)n1 * words * 4, hipMemcpyHostToDevice, c->stream));
+    if (n1 > 0 && F) HIPCHK(c, hipMemcpyAsync(c->st_d.p, kp1, (size_t)n1 * sizeof(pgx_keypoint), hipMemcpyHostToDevice, c->stream));
+    if (n2 > 0)
+        HIPCHK(c, hipMemcpyAsync(c->st_a.as<uint32_t>() + (size_t)S * words, desc2, (size_t)n2 * words * 4, hipMemcpyHostToDevice, c->stream));
+    if (n2 > 0 && F)
+        HIPCHK(c, hipMemcpyAsync(c->st_d.as<pgx_keypoint>() + S, kp2, (size_t)n2 * sizeof(pgx_keypoint), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->st_b.p, meta, sizeof meta, hipMemcpyHostToDevice, c->stream));
+    d.desc = c->st_a.as<uint32_t>();
+    d.kp = c->st_d.as<pgx_keypoint>();
+    d.counts = c->st_b.as<int32_t>();
+    d.pairlist = d.counts + 2;
+    d.F = reinterpret_cast<const float *>(d.counts + 4);
+    return PGX_OK;
+}
+
+// the results of pgx_knn and pgx_knn_guided (in st_c: idx [S][k], dist [S][k], col [S]) back to the host; ends the call
+int download_knn(pgx_ctx *c, const int32_t *d_idx, const int32_t *d_dist, const int32_t *d_col, int n1, int n2, int k, int32_t *idx_out,
+                 int32_t *dist_out, int32_t *col_nn_out)
+{
+    if (n1 > 0) {
+        HIPCHK(c, hipMemcpyAsync(idx_out, d_idx, (size_t)n1 * k * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(dist_out, d_dist, (size_t)n1 * k * 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (d_col && n2 > 0) HIPCHK(c, hipMemcpyAsync(col_nn_out, d_col, (size_t)n2 * 4, hipMemcpyDeviceToHost, c->stream));
+    return sync_status(c);
+}
+
+} // namespace
+
 int pgx_match(pgx_ctx *c, const uint32_t *desc1, int n1, const uint32_t *desc2, int n2, int words, pgx_pair *out)
 {
     if (!c || n1 < 0 || n2 < 0 || (n1 > 0 && (!desc1 || !out)) || (n2 > 0 && !desc2))
@@ -663,17 +707,11 @@ int pgx_match(pgx_ctx *c, const uint32_t *desc1, int n1, const uint32_t *desc2, 
     if (words <= 0 || words > 127) return fail(c, PGX_E_BADARG, "words must be in [1, 127]");
     const int S = n1 > n2 ? n1 : n2;
     if (S > (1 << PGX_IDX_BITS)) return fail(c, PGX_E_BADARG, "more than 2^20 keypoints");
-    // two "frames" of S slots
-    HIPCHK(c, c->st_a.ensure((size_t)2 * S * words * 4));
-    HIPCHK(c, c->st_b.ensure(64));
+    TwoSets in;
+    int rc = stage_two_sets(c, desc1, nullptr, n1, desc2, nullptr, n2, S, words, nullptr, in);
+    if (rc != PGX_OK) return rc;
     HIPCHK(c, c->st_c.ensure((size_t)S * sizeof(pgx_pair)));
-    const int32_t meta[4] = {n1, n2, 0, 1}; // counts[2], pairlist[1][2]
-    HIPCHK(c, hipMemcpyAsync(c->st_a.p, desc1, (size_t)n1 * words * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->st_a.as<uint32_t>() + (size_t)S * words, desc2, (size_t)n2 * words * 4,
-                             hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->st_b.p, meta, sizeof meta, hipMemcpyHostToDevice, c->stream));
-    int rc = enqueue_match(c, c->st_a.as<uint32_t>(), c->st_b.as<int32_t>(), S, words, c->st_b.as<int32_t>() + 2, 1,
-                           S, c->st_c.as<pgx_pair>());
+    rc = pgx_enqueue_match(c, in.desc, in.counts, S, words, in.pairlist, 1, S, c->st_c.as<pgx_pair>());
     if (rc != PGX_OK) return rc;
     HIPCHK(c, hipMemcpyAsync(out, c->st_c.p, (size_t)n1 * sizeof(pgx_pair), hipMemcpyDeviceToHost, c->stream));
     return sync_status(c);
@@ -724,7 +762,7 @@ int pgx_match_batch(pgx_ctx *c, const uint32_t *const *descs, const int32_t *cou
     memcpy(hin + desc_bytes + cnt_bytes, pair_list, pl_bytes);
     HIPCHK(c, hipMemcpyAsync(c->st_a.p, hin, in_bytes, hipMemcpyHostToDevice, c->stream));
     uint8_t *din = c->st_a.as<uint8_t>();
-    int rc = enqueue_match(c, reinterpret_cast<const uint32_t *>(din), reinterpret_cast<const int32_t *>(din + desc_bytes), S, words,
+    int rc = pgx_enqueue_match(c, reinterpret_cast<const uint32_t *>(din), reinterpret_cast<const int32_t *>(din + desc_bytes), S, words,
                            reinterpret_cast<const int32_t *>(din + desc_bytes + cnt_bytes), n_pairs, S, c->st_c.as<pgx_pair>());
     if (rc != PGX_OK) return rc;
     HIPCHK(c, hipMemcpyAsync(c->pin_out.p, c->st_c.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
@@ -747,7 +785,7 @@ int pgx_detect(pgx_ctx *c, const uint16_t *rgba, int W, int H, pgx_keypoint *kp_
     if (!c || !rgba || !kp_out || !desc_out || !n_out || capacity <= 0)
         return c ? fail(c, PGX_E_BADARG, "null pointer") : PGX_E_BADARG;
     Lock l(c);
-    if (W <= 0 || H <= 0 || W > 65535 || H > 65535) return fail(c, PGX_E_BADARG, "dimensions must fit ushort");
+    if (dims_ok(c, W, H) != PGX_OK) return PGX_E_BADARG;
     const size_t npix = (size_t)W * H;
     HIPCHK(c, c->st_e.ensure(npix * 8 + 32));
     HIPCHK(c, c->st_f.ensure((size_t)capacity * (sizeof(pgx_keypoint) + (size_t)(c->words ? c->words : 1) * 4) + 64));
@@ -755,7 +793,7 @@ int pgx_detect(pgx_ctx *c, const uint16_t *rgba, int W, int H, pgx_keypoint *kp_
     uint32_t *d_desc = reinterpret_cast<uint32_t *>(d_kp + capacity);
     int32_t *d_cnt = reinterpret_cast<int32_t *>(d_desc + (size_t)capacity * (c->words ? c->words : 1));
     HIPCHK(c, hipMemcpyAsync(c->st_e.p, rgba, npix * (c->src8 ? 4 : 8), hipMemcpyHostToDevice, c->stream));
-    int rc = enqueue_detect(c, c->st_e.as<uint16_t>(), 1, W, H, d_kp, d_desc, d_cnt, d_cnt + 1, capacity);
+    int rc = pgx_enqueue_detect(c, c->st_e.as<uint16_t>(), 1, W, H, d_kp, d_desc, d_cnt, d_cnt + 1, capacity);
     if (rc != PGX_OK) return rc;
     int cnt[2] = {0, 0};
     HIPCHK(c, hipMemcpyAsync(cnt, d_cnt, 8, hipMemcpyDeviceToHost, c->stream));
@@ -777,8 +815,8 @@ int pgx_detect_batch_dev(pgx_ctx *c, const uint16_t *d_rgba, int F, int W, int H
     if (!c || !d_rgba || !d_kp || !d_desc || !d_counts || !d_nraw || capacity <= 0 || F < 0)
         return c ? fail(c, PGX_E_BADARG, "null pointer") : PGX_E_BADARG;
     Lock l(c);
-    if (W <= 0 || H <= 0 || W > 65535 || H > 65535) return fail(c, PGX_E_BADARG, "dimensions must fit ushort");
-    return enqueue_detect(c, d_rgba, F, W, H, d_kp, d_desc, d_counts, d_nraw, capacity);
+    if (dims_ok(c, W, H) != PGX_OK) return PGX_E_BADARG;
+    return pgx_enqueue_detect(c, d_rgba, F, W, H, d_kp, d_desc, d_counts, d_nraw, capacity);
 }
 
 int pgx_match_batch_dev(pgx_ctx *c, const uint32_t *d_desc, const int32_t *d_counts, int stride, int words,
@@ -787,7 +825,7 @@ int pgx_match_batch_dev(pgx_ctx *c, const uint32_t *d_desc, const int32_t *d_cou
     if (!c || !d_desc || !d_counts || !d_pairlist || !d_out || M < 0)
         return c ? fail(c, PGX_E_BADARG, "null pointer") : PGX_E_BADARG;
     Lock l(c);
-    return enqueue_match(c, d_desc, d_counts, stride, words, d_pairlist, M, max_count, d_out);
+    return pgx_enqueue_match(c, d_desc, d_counts, stride, words, d_pairlist, M, max_count, d_out);
 }
 
 // ---- exact nearest-neighbour matching (k_knn.hip) -------------------------------------------------------------------
@@ -804,6 +842,31 @@ int knn_args(pgx_ctx *c, int stride, int words, int M, int k)
 }
 
 int clamp_max_count(int max_count, int stride) { return max_count > stride ? stride : (max_count < 1 ? 1 : max_count); }
+
+// The NN list of every row of M image pairs (pgx_match_nn_batch_dev, pgx_match_guided_batch_dev), in chunks of
+// pgx_set_match_chunk pairs: produce(m0, n, max_n, idx, dist, col) enqueues the top-2 and column nearest of the pairs
+// [m0, m0 + n) into ws_knn (20 bytes per slot) and returns PGX_OK or its error; the shared selection follows it.
+extern "C++" template <class Produce>
+int enqueue_select(pgx_ctx *c, const int32_t *d_counts, int stride, const int32_t *d_pairlist, int M, int max_count, int max_dist,
+                   float ratio, int cross_check, pgx_pair *d_out, Produce &&produce)
+{
+    if (!(ratio <= 1.0f)) return fail(c, PGX_E_BADARG, "ratio must be <= 1 (0 or less: no ratio test)");
+    if (M == 0) return PGX_OK;
+    const int max_n = clamp_max_count(max_count, stride);
+    const int CHUNK = c->match_chunk, mc = M < CHUNK ? M : CHUNK;
+    const size_t slots = (size_t)mc * stride;
+    HIPCHK(c, c->ws_knn.ensure(slots * 5 * sizeof(int32_t)));
+    int32_t *idx = c->ws_knn.as<int32_t>(), *dist = idx + 2 * slots, *col = dist + 2 * slots;
+    for (int m0 = 0; m0 < M; m0 += CHUNK) {
+        const int n = M - m0 < CHUNK ? M - m0 : CHUNK;
+        const int rp = produce(m0, n, max_n, idx, dist, col);
+        if (rp != PGX_OK) return rp;
+        pgx_launch_knn_select(c, c->stream, d_counts, d_pairlist + 2 * (size_t)m0, n, stride, max_n, idx, dist, col, max_dist, ratio,
+                              cross_check ? 1 : 0, d_out + (size_t)m0 * stride);
+    }
+    HIPCHK(c, hipGetLastError());
+    return PGX_OK;
+}
 
 } // namespace
 
@@ -829,23 +892,12 @@ int pgx_match_nn_batch_dev(pgx_ctx *c, const uint32_t *d_desc, const int32_t *d_
     Lock l(c);
     const int rc = knn_args(c, stride, words, M, 2);
     if (rc != PGX_OK) return rc;
-    if (!(ratio <= 1.0f)) return fail(c, PGX_E_BADARG, "ratio must be <= 1 (0 or less: no ratio test)");
-    if (M == 0) return PGX_OK;
-    const int max_n = clamp_max_count(max_count, stride);
-    // the top-2 and column-nearest results of one chunk of image pairs (pgx_set_match_chunk): 20 bytes per slot
-    const int CHUNK = c->match_chunk, mc = M < CHUNK ? M : CHUNK;
-    const size_t slots = (size_t)mc * stride;
-    HIPCHK(c, c->ws_knn.ensure(slots * 5 * sizeof(int32_t)));
-    int32_t *idx = c->ws_knn.as<int32_t>(), *dist = idx + 2 * slots, *col = dist + 2 * slots;
-    for (int m0 = 0; m0 < M; m0 += CHUNK) {
-        const int n = M - m0 < CHUNK ? M - m0 : CHUNK;
-        const int32_t *pl = d_pairlist + 2 * (size_t)m0;
-        pgx_launch_knn(c, c->stream, d_desc, d_counts, pl, n, stride, words, max_n, 2, idx, dist, col);
-        pgx_launch_knn_select(c, c->stream, d_counts, pl, n, stride, max_n, idx, dist, col, max_dist, ratio, cross_check ? 1 : 0,
-                              d_out + (size_t)m0 * stride);
-    }
-    HIPCHK(c, hipGetLastError());
-    return PGX_OK;
+    return enqueue_select(c, d_counts, stride, d_pairlist, M, max_count, max_dist, ratio, cross_check, d_out,
+                          [&](int m0, int n, int max_n, int32_t *idx, int32_t *dist, int32_t *col) {
+                              pgx_launch_knn(c, c->stream, d_desc, d_counts, d_pairlist + 2 * (size_t)m0, n, stride, words, max_n, 2, idx,
+                                             dist, col);
+                              return PGX_OK;
+                          });
 }
 
 int pgx_knn(pgx_ctx *c, const uint32_t *desc1, int n1, const uint32_t *desc2, int n2, int words, int k, int32_t *idx_out,
@@ -859,26 +911,14 @@ int pgx_knn(pgx_ctx *c, const uint32_t *desc1, int n1, const uint32_t *desc2, in
     int rc = knn_args(c, S, words, 1, k);
     if (rc != PGX_OK) return rc;
     if (n1 == 0 && (n2 == 0 || !col_nn_out)) return PGX_OK;
-    // two "frames" of S slots; outputs idx [S][k], dist [S][k], col [S]
-    HIPCHK(c, c->st_a.ensure((size_t)2 * S * words * 4));
-    HIPCHK(c, c->st_b.ensure(64));
+    TwoSets in;
+    rc = stage_two_sets(c, desc1, nullptr, n1, desc2, nullptr, n2, S, words, nullptr, in);
+    if (rc != PGX_OK) return rc;
     HIPCHK(c, c->st_c.ensure((size_t)S * (2 * k + 1) * 4));
-    const int32_t meta[4] = {n1, n2, 0, 1}; // counts[2], pairlist[1][2]
-    if (n1 > 0) HIPCHK(c, hipMemcpyAsync(c->st_a.p, desc1, (size_t)n1 * words * 4, hipMemcpyHostToDevice, c->stream));
-    if (n2 > 0)
-        HIPCHK(c, hipMemcpyAsync(c->st_a.as<uint32_t>() + (size_t)S * words, desc2, (size_t)n2 * words * 4, hipMemcpyHostToDevice,
-                                 c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->st_b.p, meta, sizeof meta, hipMemcpyHostToDevice, c->stream));
     int32_t *d_idx = c->st_c.as<int32_t>(), *d_dist = d_idx + (size_t)S * k, *d_col = col_nn_out ? d_dist + (size_t)S * k : nullptr;
-    pgx_launch_knn(c, c->stream, c->st_a.as<uint32_t>(), c->st_b.as<int32_t>(), c->st_b.as<int32_t>() + 2, 1, S, words, S, k, d_idx,
-                   d_dist, d_col);
+    pgx_launch_knn(c, c->stream, in.desc, in.counts, in.pairlist, 1, S, words, S, k, d_idx, d_dist, d_col);
     HIPCHK(c, hipGetLastError());
-    if (n1 > 0) {
-        HIPCHK(c, hipMemcpyAsync(idx_out, d_idx, (size_t)n1 * k * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(dist_out, d_dist, (size_t)n1 * k * 4, hipMemcpyDeviceToHost, c->stream));
-    }
-    if (d_col && n2 > 0) HIPCHK(c, hipMemcpyAsync(col_nn_out, d_col, (size_t)n2 * 4, hipMemcpyDeviceToHost, c->stream));
-    return sync_status(c);
+    return download_knn(c, d_idx, d_dist, d_col, n1, n2, k, idx_out, dist_out, col_nn_out);
 }
 
 // ---- epipolar-guided exact matching (k_guided.hip) ------------------------------------------------------------------
@@ -934,24 +974,11 @@ int pgx_match_guided_batch_dev(pgx_ctx *c, const uint32_t *d_desc, const pgx_key
     Lock l(c);
     const int rc = guided_args(c, stride, words, M, 2, band);
     if (rc != PGX_OK) return rc;
-    if (!(ratio <= 1.0f)) return fail(c, PGX_E_BADARG, "ratio must be <= 1 (0 or less: no ratio test)");
-    if (M == 0) return PGX_OK;
-    const int max_n = clamp_max_count(max_count, stride);
-    // as pgx_match_nn_batch_dev: the top-2 and column nearest of one chunk (20 bytes per slot), then the shared selection
-    const int CHUNK = c->match_chunk, mc = M < CHUNK ? M : CHUNK;
-    const size_t slots = (size_t)mc * stride;
-    HIPCHK(c, c->ws_knn.ensure(slots * 5 * sizeof(int32_t)));
-    int32_t *idx = c->ws_knn.as<int32_t>(), *dist = idx + 2 * slots, *col = dist + 2 * slots;
-    for (int m0 = 0; m0 < M; m0 += CHUNK) {
-        const int n = M - m0 < CHUNK ? M - m0 : CHUNK;
-        const int32_t *pl = d_pairlist + 2 * (size_t)m0;
-        const int rg = enqueue_guided(c, d_desc, d_kp, d_counts, stride, words, pl, n, max_n, d_F + 9 * (size_t)m0, band, 2, idx, dist, col);
-        if (rg != PGX_OK) return rg;
-        pgx_launch_knn_select(c, c->stream, d_counts, pl, n, stride, max_n, idx, dist, col, max_dist, ratio, cross_check ? 1 : 0,
-                              d_out + (size_t)m0 * stride);
-    }
-    HIPCHK(c, hipGetLastError());
-    return PGX_OK;
+    return enqueue_select(c, d_counts, stride, d_pairlist, M, max_count, max_dist, ratio, cross_check, d_out,
+                          [&](int m0, int n, int max_n, int32_t *idx, int32_t *dist, int32_t *col) {
+                              return enqueue_guided(c, d_desc, d_kp, d_counts, stride, words, d_pairlist + 2 * (size_t)m0, n, max_n,
+                                                    d_F + 9 * (size_t)m0, band, 2, idx, dist, col);
+                          });
 }
 
 int pgx_knn_guided(pgx_ctx *c, const uint32_t *desc1, const pgx_keypoint *kp1, int n1, const uint32_t *desc2, const pgx_keypoint *kp2,
@@ -965,34 +992,14 @@ int pgx_knn_guided(pgx_ctx *c, const uint32_t *desc1, const pgx_keypoint *kp1, i
     const int rc = guided_args(c, S, words, 1, k, band);
     if (rc != PGX_OK) return rc;
     if (n1 == 0 && (n2 == 0 || !col_nn_out)) return PGX_OK;
-    // two "frames" of S slots; st_b: counts[2], pairlist[1][2], F[9]; outputs idx [S][k], dist [S][k], col [S]
-    HIPCHK(c, c->st_a.ensure((size_t)2 * S * words * 4));
-    HIPCHK(c, c->st_b.ensure(64));
-    HIPCHK(c, c->st_c.ensure((size_t)S * (2 * k + 1) * 4));
-    HIPCHK(c, c->st_d.ensure((size_t)2 * S * sizeof(pgx_keypoint)));
-    int32_t meta[13] = {n1, n2, 0, 1};
-    std::memcpy(meta + 4, F, 9 * sizeof(float));
-    if (n1 > 0) {
-        HIPCHK(c, hipMemcpyAsync(c->st_a.p, desc1, (size_t)n1 * words * 4, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->st_d.p, kp1, (size_t)n1 * sizeof(pgx_keypoint), hipMemcpyHostToDevice, c->stream));
-    }
-    if (n2 > 0) {
-        HIPCHK(c, hipMemcpyAsync(c->st_a.as<uint32_t>() + (size_t)S * words, desc2, (size_t)n2 * words * 4, hipMemcpyHostToDevice,
-                                 c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->st_d.as<pgx_keypoint>() + S, kp2, (size_t)n2 * sizeof(pgx_keypoint), hipMemcpyHostToDevice, c->stream));
-    }
-    HIPCHK(c, hipMemcpyAsync(c->st_b.p, meta, sizeof meta, hipMemcpyHostToDevice, c->stream));
-    int32_t *d_idx = c->st_c.as<int32_t>(), *d_dist = d_idx + (size_t)S * k, *d_col = col_nn_out ? d_dist + (size_t)S * k : nullptr;
-    const int32_t *d_meta = c->st_b.as<int32_t>();
-    const int rq = enqueue_guided(c, c->st_a.as<uint32_t>(), c->st_d.as<pgx_keypoint>(), d_meta, S, words, d_meta + 2, 1, S,
-                                  reinterpret_cast<const float *>(d_meta + 4), band, k, d_idx, d_dist, d_col);
+    TwoSets in;
+    int rq = stage_two_sets(c, desc1, kp1, n1, desc2, kp2, n2, S, words, F, in);
     if (rq != PGX_OK) return rq;
-    if (n1 > 0) {
-        HIPCHK(c, hipMemcpyAsync(idx_out, d_idx, (size_t)n1 * k * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(dist_out, d_dist, (size_t)n1 * k * 4, hipMemcpyDeviceToHost, c->stream));
-    }
-    if (d_col && n2 > 0) HIPCHK(c, hipMemcpyAsync(col_nn_out, d_col, (size_t)n2 * 4, hipMemcpyDeviceToHost, c->stream));
-    return sync_status(c);
+    HIPCHK(c, c->st_c.ensure((size_t)S * (2 * k + 1) * 4));
+    int32_t *d_idx = c->st_c.as<int32_t>(), *d_dist = d_idx + (size_t)S * k, *d_col = col_nn_out ? d_dist + (size_t)S * k : nullptr;
+    rq = enqueue_guided(c, in.desc, in.kp, in.counts, S, words, in.pairlist, 1, S, in.F, band, k, d_idx, d_dist, d_col);
+    if (rq != PGX_OK) return rq;
+    return download_knn(c, d_idx, d_dist, d_col, n1, n2, k, idx_out, dist_out, col_nn_out);
 }
 
 // ---- RANSAC fundamental matrix and pose ----------------------------------------------------------
@@ -1031,6 +1038,28 @@ int pgx_pose_dev(pgx_ctx *c, const pgx_keypoint *d_kp, const pgx_pair *d_matches
 
 // ---- the track graph on the device ---------------------------------------------------------------
 
+namespace {
+// the argument checks that the device forms of the track graph and of its consumers share
+int geom_dev_args(pgx_ctx *c, int F, int stride, int n_frames, const int32_t *d_frame_ids, int max_tracks)
+{
+    if (F <= 0 || stride <= 0 || n_frames <= 0) return fail(c, PGX_E_BADARG, "F, stride and n_frames must be positive");
+    if (!d_frame_ids && n_frames != F) return fail(c, PGX_E_BADARG, "without d_frame_ids, n_frames must equal F");
+    if ((long long)n_frames * stride > (1ll << 30)) return fail(c, PGX_E_BADARG, "n_frames * stride must be <= 2^30");
+    if (max_tracks < 0) return fail(c, PGX_E_BADARG, "max_tracks must be >= 0");
+    return PGX_OK;
+}
+
+// ... and those of pgx_tracks_dev and pgx_tracks_split_dev (no track limit; one block per 256 slots of a pair and of a frame)
+int tracks_dev_args(pgx_ctx *c, int M, int F, int stride, int n_frames, const int32_t *d_frame_ids)
+{
+    const int rc = geom_dev_args(c, F, stride, n_frames, d_frame_ids, 0);
+    if (rc != PGX_OK) return rc;
+    if ((long long)M * ((stride + 255) / 256) > 0x7FFFFFFFll || (long long)F * ((stride + 255) / 256) > 0x7FFFFFFFll)
+        return fail(c, PGX_E_BADARG, "too many image pairs for one call");
+    return PGX_OK;
+}
+} // namespace
+
 int pgx_tracks_dev(pgx_ctx *c, const pgx_pair *d_matches, const int32_t *d_counts, const int32_t *d_pairlist, int M, int F,
                    int stride, const int32_t *d_frame_ids, int n_frames, int max_dist, int min_len, int32_t *d_track_of,
                    int32_t *d_offsets, int32_t *d_nodes, int32_t *d_summary)
@@ -1038,11 +1067,8 @@ int pgx_tracks_dev(pgx_ctx *c, const pgx_pair *d_matches, const int32_t *d_count
     if (!c || !d_counts || !d_track_of || !d_offsets || !d_nodes || !d_summary || M < 0 || (M > 0 && (!d_matches || !d_pairlist)))
         return c ? fail(c, PGX_E_BADARG, "null pointer") : PGX_E_BADARG;
     Lock l(c);
-    if (F <= 0 || stride <= 0 || n_frames <= 0) return fail(c, PGX_E_BADARG, "F, stride and n_frames must be positive");
-    if (!d_frame_ids && n_frames != F) return fail(c, PGX_E_BADARG, "without d_frame_ids, n_frames must equal F");
-    if ((long long)n_frames * stride > (1ll << 30)) return fail(c, PGX_E_BADARG, "n_frames * stride must be <= 2^30");
-    if ((long long)M * ((stride + 255) / 256) > 0x7FFFFFFFll || (long long)F * ((stride + 255) / 256) > 0x7FFFFFFFll)
-        return fail(c, PGX_E_BADARG, "too many image pairs for one call");
+    const int rc = tracks_dev_args(c, M, F, stride, n_frames, d_frame_ids);
+    if (rc != PGX_OK) return rc;
     HIPCHK(c, c->ws_tracks.ensure(pgx_tracks_ws_bytes(n_frames, stride)));
     {
         ProfScope ps(c, "tracks");
@@ -1061,11 +1087,8 @@ int pgx_tracks_split_dev(pgx_ctx *c, const pgx_pair *d_matches, const int32_t *d
         (n_gates > 0 && !gates))
         return c ? fail(c, PGX_E_BADARG, "null pointer") : PGX_E_BADARG;
     Lock l(c);
-    if (F <= 0 || stride <= 0 || n_frames <= 0) return fail(c, PGX_E_BADARG, "F, stride and n_frames must be positive");
-    if (!d_frame_ids && n_frames != F) return fail(c, PGX_E_BADARG, "without d_frame_ids, n_frames must equal F");
-    if ((long long)n_frames * stride > (1ll << 30)) return fail(c, PGX_E_BADARG, "n_frames * stride must be <= 2^30");
-    if ((long long)M * ((stride + 255) / 256) > 0x7FFFFFFFll || (long long)F * ((stride + 255) / 256) > 0x7FFFFFFFll)
-        return fail(c, PGX_E_BADARG, "too many image pairs for one call");
+    const int rc = tracks_dev_args(c, M, F, stride, n_frames, d_frame_ids);
+    if (rc != PGX_OK) return rc;
     if (n_gates < 0 || n_gates > 7) return fail(c, PGX_E_BADARG, "n_gates = %d, must be in [0, 7]", n_gates);
     int g[7];
     for (int i = 0; i < n_gates; i++) {
@@ -1088,16 +1111,6 @@ int pgx_tracks_split_dev(pgx_ctx *c, const pgx_pair *d_matches, const int32_t *d
 // ---- the consumers of the track graph: triangulation, bundle adjustment, frame registration --------------------------
 
 namespace {
-// the argument checks every device form shares
-int geom_dev_args(pgx_ctx *c, int F, int stride, int n_frames, const int32_t *d_frame_ids, int max_tracks)
-{
-    if (F <= 0 || stride <= 0 || n_frames <= 0) return fail(c, PGX_E_BADARG, "F, stride and n_frames must be positive");
-    if (!d_frame_ids && n_frames != F) return fail(c, PGX_E_BADARG, "without d_frame_ids, n_frames must equal F");
-    if ((long long)n_frames * stride > (1ll << 30)) return fail(c, PGX_E_BADARG, "n_frames * stride must be <= 2^30");
-    if (max_tracks < 0) return fail(c, PGX_E_BADARG, "max_tracks must be >= 0");
-    return PGX_OK;
-}
-
 // the host forms' checks of counts, offsets and nodes (the device then sees no out-of-range node); stride = max(counts, 1)
 int check_host_tracks(pgx_ctx *c, const pgx_keypoint *kps, const int32_t *counts, int n_frames, const int32_t *track_offsets,
                       const int32_t *nodes, int n_tracks, int *stride_out, long long *n_nodes_out)

@@ -125,8 +125,8 @@ struct pgx_ctx {
     // host-API staging
     DevBuf st_a, st_b, st_c, st_d, st_e, st_f;
     PinBuf pin_in, pin_out; // pgx_match_batch
-    // match workspaces: four, so that with several chunks of image pairs the stages of consecutive chunks run side by side
-    DevBuf ws_matchn[4];
+    // match workspaces: three, so that with several chunks of image pairs the stages of consecutive chunks run side by side
+    DevBuf ws_matchn[3];
     DevBuf ws_pose, ws_tracks;
     DevBuf ws_tracks_split; // pgx_tracks_split_dev: ws_tracks' layout plus the active mask, live counters and frame owners
     DevBuf ws_knn; // pgx_match_nn_batch_dev: top-2 and column nearest of a chunk of image pairs
@@ -134,9 +134,9 @@ struct pgx_ctx {
     DevBuf ws_tri;    // pgx_triangulate_tracks*: camera table, frame -> slot map, per-workgroup counters
     DevBuf ws_ba;     // pgx_bundle_adjust*: control block, cameras, reduced system, per-track and per-node state
     DevBuf ws_reg;    // pgx_register_frames*: target tables, correspondence lists, hypotheses of one chunk, scoring keys
-    hipStream_t mstream[4] = {nullptr, nullptr, nullptr, nullptr}; // [0] wide rounds, [1] residual distance rows, [2], [3] per-pair finishes (alternating)
-    hipEvent_t ev_in = nullptr, ev_wide[4] = {nullptr, nullptr, nullptr, nullptr}, ev_rows[4] = {nullptr, nullptr, nullptr, nullptr},
-               ev_fin[4] = {nullptr, nullptr, nullptr, nullptr}, ev_join[4] = {nullptr, nullptr, nullptr, nullptr};
+    hipStream_t mstream[3] = {nullptr, nullptr, nullptr}; // [0] wide rounds, [1] residual distance rows, [2] per-pair finish
+    hipEvent_t ev_in = nullptr, ev_wide[3] = {nullptr, nullptr, nullptr}, ev_rows[3] = {nullptr, nullptr, nullptr},
+               ev_fin[3] = {nullptr, nullptr, nullptr}, ev_join[3] = {nullptr, nullptr, nullptr};
     // recorded behind the stages of the most recent calls (pgx_wait_stage: another context's work is held back until a stage
     // of this one is done -- e.g. its detect chain until the distance rounds here are over, so that it runs beside the
     // residual rows and the per-pair finish instead); [PGX_STAGE_*]
@@ -201,7 +201,7 @@ struct ProfScope {
     ProfScope(pgx_ctx *ctx, const char *name, hipStream_t s = nullptr, bool attach_to_kernel = false)
         : c(ctx), st(s ? s : ctx->stream), attach(attach_to_kernel)
     {
-        if (!c->prof_on || (!c->prof_only.empty() && c->prof_only != name)) return;
+        if (!name || !c->prof_on || (!c->prof_only.empty() && c->prof_only != name)) return; // no name: brackets nothing
         e = &c->prof[name];
         auto take = [&](hipEvent_t &ev) {
             if (!c->ev_pool.empty()) { ev = c->ev_pool.back(); c->ev_pool.pop_back(); return true; }
@@ -307,6 +307,10 @@ void pgx_launch_match_finish(pgx_ctx *ctx, hipStream_t s, const uint32_t *d_desc
 // d_idx / d_dist [M][S][k], d_col [M][S] or nullptr; max_n in [1, S], k in {1, 2}
 void pgx_launch_knn(pgx_ctx *ctx, hipStream_t s, const uint32_t *d_desc, const int32_t *d_counts, const int32_t *d_pairlist, int M,
                     int S, int words, int max_n, int k, int32_t *d_idx, int32_t *d_dist, int32_t *d_col);
+// the column output of a producer of (distance << 20 | row) keys, d_col [M][S]: finish = false sets the entries j < counts[b] to
+// PGX_KEY_NONE ahead of it, finish = true turns the keys into row indices (-1: no row) behind it.  scope: profiling group or nullptr
+void pgx_launch_colkeys(pgx_ctx *ctx, hipStream_t s, const char *scope, bool finish, const int32_t *d_counts,
+                        const int32_t *d_pairlist, int M, int S, int max_n, int32_t *d_col);
 // the NN list of every row from k = 2 results and the column nearest: d_out [M][S]
 void pgx_launch_knn_select(pgx_ctx *ctx, hipStream_t s, const int32_t *d_counts, const int32_t *d_pairlist, int M, int S, int max_n,
                            const int32_t *d_idx, const int32_t *d_dist, const int32_t *d_col, int max_dist, float ratio,

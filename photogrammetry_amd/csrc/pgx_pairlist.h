@@ -1,0 +1,46 @@
+// pgx_pairlist.h -- what the producers of per-pair neighbour lists share (k_knn.hip, k_guided.hip): the clamped counts of
+// an image pair, the write-out of (distance << 20 | index) keys, and the k in {1, 2} x column side on / off dispatch of
+// their launchers.  The column-key kernels themselves live in k_knn.hip (pgx_launch_colkeys, pgx_internal.h).
+// Internal to libpgx.so; DESIGN.md section 14b.
+#pragma once
+
+#include "pgx_internal.h"
+
+// calls fn(integral_constant<int, k>, bool_constant<col>) for k in {1, 2}: a launcher names its argument list once
+template <class Fn> void pgx_dispatch_k_col(int k, bool col, Fn &&fn)
+{
+    using K1 = std::integral_constant<int, 1>;
+    using K2 = std::integral_constant<int, 2>;
+    if (k == 1 && !col) fn(K1{}, std::false_type{});
+    else if (k == 1) fn(K1{}, std::true_type{});
+    else if (!col) fn(K2{}, std::false_type{});
+    else fn(K2{}, std::true_type{});
+}
+
+#ifdef __HIPCC__
+
+__device__ __forceinline__ int pgx_clamp_count(int n, int max_n) { return n < 0 ? 0 : (n > max_n ? max_n : n); }
+
+// image pair m: its two frames and their counts clamped to [0, max_n]
+struct PairCounts {
+    int fa, fb, n1, n2;
+};
+__device__ __forceinline__ PairCounts pgx_pair_counts(const int32_t *__restrict__ counts, const int32_t *__restrict__ pairlist, int m,
+                                                      int max_n)
+{
+    const int fa = pairlist[2 * m], fb = pairlist[2 * m + 1];
+    return {fa, fb, pgx_clamp_count(counts[fa], max_n), pgx_clamp_count(counts[fb], max_n)};
+}
+
+// a row's K smallest keys (k1 <= k2) as its K entries of idx / dist; no neighbour: (-1, PGX_DIST_NONE)
+template <int K> __device__ __forceinline__ void pgx_store_keys(uint32_t k1, uint32_t k2, int32_t *idx, int32_t *dist)
+{
+    idx[0] = k1 == PGX_KEY_NONE ? -1 : (int32_t)(k1 & PGX_IDX_MASK);
+    dist[0] = k1 == PGX_KEY_NONE ? PGX_DIST_NONE : (int32_t)(k1 >> PGX_IDX_BITS);
+    if (K == 2) {
+        idx[1] = k2 == PGX_KEY_NONE ? -1 : (int32_t)(k2 & PGX_IDX_MASK);
+        dist[1] = k2 == PGX_KEY_NONE ? PGX_DIST_NONE : (int32_t)(k2 >> PGX_IDX_BITS);
+    }
+}
+
+#endif // __HIPCC__

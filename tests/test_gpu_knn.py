@@ -234,6 +234,36 @@ def test_match_nn_grid(words):
                     assert (out[m, n1:] == 77).all()
 
 
+@pytest.mark.parametrize("words", [8, 3])
+def test_match_nn_across_a_chunk_boundary(words):
+    """17 image pairs at 16 pairs per chunk (the smallest): the second chunk of pgx_match_nn_batch_dev holds one pair.  Byte
+    equal to the default chunk's output, equal to the yardstick, and rows at or beyond counts[a] keep the sentinel."""
+    rng = np.random.default_rng(17 + words)
+    base = rand_desc(rng, 150, words)
+    descs = []
+    for n in (150, 97, 0, 133, 1, 64):   # every frame sees a noisy subset of one scene: distances well inside the gate
+        bits = np.unpackbits(base[rng.permutation(150)[:n]].view(np.uint8), axis=1)
+        bits ^= (rng.random(bits.shape) < 0.08).astype(np.uint8)
+        descs.append(np.ascontiguousarray(np.packbits(bits, axis=1).view(np.uint32)).reshape(n, words))
+    stride = 160
+    d_desc, d_counts, counts = to_dev(descs, stride, words)
+    pl = [(i, j) for i in range(6) for j in range(i + 1, 6)] + [(5, 0), (3, 3)]
+    assert len(pl) == 17
+    max_dist = 32 * words // 3
+    whole = run_nn_dev(d_desc, d_counts, stride, words, pl, max_dist, 0.8, True)
+    try:
+        ENGINE.set_match_chunk(16)
+        chunked = run_nn_dev(d_desc, d_counts, stride, words, pl, max_dist, 0.8, True)
+    finally:
+        ENGINE.set_match_chunk(2048)
+    assert chunked.tobytes() == whole.tobytes()
+    for m, (fa, fb) in enumerate(pl):   # pairs 0, 15 and 16 are the ends of the two chunks
+        exp = ref_select(*ref_knn(descs[fa], descs[fb]), max_dist, 0.8, True)
+        assert (chunked[m, :counts[fa]] == exp).all(), m
+        assert (chunked[m, counts[fa]:] == 77).all(), m
+    assert (chunked[0, :, 1] >= 0).sum() > 40 and (chunked[15, :, 1] >= 0).sum() > 20 and (chunked[16, :133, 1] >= 0).all()
+
+
 def test_bad_arguments():
     t = torch.zeros(4096, dtype=torch.int32, device=DEV)
     with pytest.raises(pg.ArgumentException):

@@ -16,7 +16,7 @@ from guided_ref import NONE, loop_guided, ref_guided
 
 LLVM = "/opt/rocm/lib/llvm/bin"
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-KERNELS = ("k_guided_slots", "k_guided_bucket", "k_guided_walk", "k_guided_col_init", "k_guided_col_finish")
+KERNELS = ("k_guided_slots", "k_guided_bucket", "k_guided_walk", "k_knn_col_init", "k_knn_col_finish")
 
 
 @pytest.fixture(scope="module")
