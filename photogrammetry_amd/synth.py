@@ -1,5 +1,6 @@
 """Synthetic inputs for tests and bench.py: corner-rich RGBA64 frames and
-descriptor sets.  Pure data generation on the host, seeded; no reference code or data."""
+descriptor sets.  Pure data generation on the host, seeded; no reference code or data.  device_tracks alone uploads what
+it made, and imports torch when called."""
 import numpy as np
 
 
@@ -166,8 +167,10 @@ def scene_tracks(scene, min_len=2):
 
 def cut_tracks(scene, lengths, seed=0):
     """Tracks of chosen lengths from a make_scene scene: point p's views, in frame order, cut to one contiguous run of
-    min(lengths[p], views of p) nodes at a seeded random start (tools/bench_triangulate.py's shape_a); points left with fewer
-    than 2 nodes give no track.  lengths: [n_points] ints.
+    min(lengths[p], views of p) nodes at a seeded random start; points left with fewer than 2 nodes give no track.
+    lengths: [n_points] ints (tests/test_gpu_geometry_limits.py), or a pair (lo, hi): every seen point's length is then
+    drawn from the same generator as integers(lo, hi), length first, then start -- the scenes of tools/geom_bench.py, whose
+    recorded shapes depend on that order.  seed: an int, or the generator to draw from.
     -> (offsets [n + 1] int32, nodes [n_nodes][2] int32, point [n] (the point of each track))"""
     rng = np.random.default_rng(seed)
     seen = {}
@@ -177,7 +180,7 @@ def cut_tracks(scene, lengths, seed=0):
     tracks, pts = [], []
     for p in sorted(seen):
         v = seen[p]
-        L = min(len(v), int(lengths[p]))
+        L = min(len(v), int(rng.integers(*lengths)) if isinstance(lengths, tuple) else int(lengths[p]))
         if L < 2:
             continue
         a = int(rng.integers(0, len(v) - L + 1))
@@ -186,6 +189,46 @@ def cut_tracks(scene, lengths, seed=0):
     off = np.concatenate([[0], np.cumsum([len(t) for t in tracks])]).astype(np.int32)
     nodes = np.array([n for t in tracks for n in t], dtype=np.int32).reshape(-1, 2)
     return off, nodes, np.array(pts, dtype=np.int64)
+
+
+def slot_layout(kps, slots=None, n_slots=None):
+    """The keypoint buffer of a track-graph consumer on the host.  kps: [nf] of KEYPOINT_DTYPE or of [n][2] (x, y);
+    slots[f] = the slot frame f sits in (default: f) among n_slots (default: nf); other slots are padding: frame id -1, no
+    keypoints.  -> dict(kp [F][stride] KEYPOINT_DTYPE, counts [F], ids [F], slots, F, nf, stride, identity)"""
+    from .api import KEYPOINT_DTYPE
+    nf = len(kps)
+    slots = list(range(nf)) if slots is None else list(slots)
+    F = nf if n_slots is None else n_slots
+    stride = max(1, max(len(k) for k in kps))
+    kp = np.zeros((F, stride), dtype=KEYPOINT_DTYPE)
+    counts = np.zeros(F, np.int32)
+    ids = np.full(F, -1, np.int32)
+    for f, k in enumerate(kps):
+        k = np.asarray(k)
+        if k.dtype == KEYPOINT_DTYPE:
+            kp[slots[f], :len(k)] = k
+        elif len(k):
+            kp["x"][slots[f], :len(k)], kp["y"][slots[f], :len(k)] = k[:, 0], k[:, 1]
+        counts[slots[f]] = len(k)
+        ids[slots[f]] = f
+    return dict(kp=kp, counts=counts, ids=ids, slots=slots, F=F, nf=nf, stride=stride,
+                identity=n_slots is None and slots == list(range(nf)))
+
+
+def device_tracks(kps, off, nodes, slots=None, n_slots=None, device="cuda:0"):
+    """Device buffers of a track-graph consumer's input (triangulation, bundle adjustment, registration; the GPU tests and
+    tools/geom_bench.py): slot_layout's keypoints and frame ids, offsets, nodes and a track summary with n_tracks and
+    n_nodes.  -> dict(kp [F][stride][4] int32, ids, off, nodes, tsum [8] (torch tensors), F, nf, stride, identity, n_tracks,
+    n_nodes)"""
+    import torch
+    lay = slot_layout(kps, slots, n_slots)
+    F, stride, n = lay["F"], lay["stride"], len(off) - 1
+    return dict(kp=torch.from_numpy(lay["kp"].view(np.int32).reshape(F, stride, 4)).to(device),
+                ids=torch.from_numpy(lay["ids"]).to(device), F=F, nf=lay["nf"], stride=stride, identity=lay["identity"],
+                off=torch.from_numpy(np.asarray(off, np.int32)).to(device),
+                nodes=torch.from_numpy(np.ascontiguousarray(nodes, np.int32).reshape(-1, 2)).to(device),
+                tsum=torch.tensor([n, len(nodes), 0, 0, 0, 0, 0, 0], dtype=torch.int32, device=device), n_tracks=n,
+                n_nodes=len(nodes))
 
 
 def perturb(Rt, xyz, seed, rot_deg=0.3, centre_sigma=0.05, point_sigma=0.015, fixed=None):

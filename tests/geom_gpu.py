@@ -1,0 +1,184 @@
+"""What the GPU tests of the track graph and of its three consumers (triangulation, bundle adjustment, registration) share:
+tensor kinds, bit comparison, the device problem, the run wrappers of bundle adjustment and registration with their padded
+inputs and sentinel-filled outputs, the yardstick comparisons that more than one module uses, and the random and constructed
+match lists of the track-graph tests.  A plain helper module: no test module imports another."""
+import numpy as np
+import torch
+
+import triangulate_ref
+from photogrammetry_amd import synth
+
+DEV = "cuda:0"
+I32 = dict(dtype=torch.int32, device=DEV)
+F64 = dict(dtype=torch.float64, device=DEV)
+INF = float("inf")
+INT_MAX = 2**31 - 1
+NS, IP, MIN_IN, ITERS, SEED = 128, 2.0, 12, 10, 7      # registration's defaults: samples, inlier px, min inliers, refinement, seed
+TRI_KEYS = ("xyz", "quality", "flags", "summary")
+BA_KEYS = ("Rt", "P", "xyz", "node_err", "trace", "report")
+REG_KEYS = ("Rt", "P", "frame_stats", "frame_err", "node_inlier", "report")
+
+# keypoints by slot (slots[f] = frame f's slot; other slots padding with frame id -1), offsets, nodes and a track summary
+# with n_tracks, on the device
+device_problem = synth.device_tracks
+
+
+def bits(a):
+    return np.ascontiguousarray(a).view(np.uint8).tobytes()
+
+
+def same_bits(a, b, keys):
+    for k in keys:
+        assert bits(a[k]) == bits(b[k]), k
+
+
+def padded_inputs(d, K, Rt, xyz, flags, max_tracks):
+    """What bundle adjustment and registration read besides the graph: K and Rt per frame, the points in a buffer of
+    max(max_tracks, n_tracks, 1) rows (the rows behind n_tracks hold 3.0) and the optional flags in one of the same length
+    (0 behind n_tracks); Rt_out and P_out filled with 5.0.  -> (max_tracks, dK, dRt, X, flags or None, Rt_out, P_out)"""
+    nf, n = d["nf"], d["n_tracks"]
+    mt = n if max_tracks is None else max_tracks
+    dK = torch.from_numpy(np.ascontiguousarray(K, np.float64).reshape(nf, 4)).to(DEV)
+    dRt = torch.from_numpy(np.ascontiguousarray(Rt, np.float64).reshape(nf, 12)).to(DEV)
+    X = torch.full((max(mt, n, 1), 3), 3.0, **F64)
+    X[:n] = torch.from_numpy(np.ascontiguousarray(xyz, np.float64).reshape(n, 3))
+    fl = None
+    if flags is not None:
+        fl = torch.full((max(mt, n, 1),), 0, **I32)
+        fl[:n] = torch.from_numpy(np.asarray(flags, np.int32))
+    return mt, dK, dRt, X, fl, torch.full((nf, 12), 5.0, **F64), torch.full((nf, 12), 5.0, **F64)
+
+
+def ba_run(engine, d, K, Rt, fixed, xyz, iters=20, huber=INF, lam0=1e-3, max_tracks=None, flags=None):
+    """pgx_bundle_adjust_dev on the context's stream, one sync -> dict of host arrays"""
+    nf, n = d["nf"], d["n_tracks"]
+    mt, dK, dRt, X, fl, Rt_out, P_out = padded_inputs(d, K, Rt, xyz, flags, max_tracks)
+    dfx = torch.from_numpy(np.ascontiguousarray(fixed, np.int32)).to(DEV)
+    X_out = torch.full((max(mt, n, 1), 3), 5.0, **F64)
+    err = torch.full((nf * d["stride"],), 5.0, **F64)
+    trace, report = torch.full((iters + 1, 2), 5.0, **F64), torch.full((8,), 7, **I32)
+    torch.cuda.synchronize()
+    engine.bundle_adjust_dev(d["kp"], d["F"], d["stride"], nf, dK, dRt, dfx, d["off"], d["nodes"], d["tsum"], mt, X, Rt_out, P_out,
+                             X_out, trace, report, iters, huber, lam0, d_track_flags=fl, d_node_err=err,
+                             d_frame_ids=None if d["identity"] else d["ids"])
+    engine.check_status()
+    return dict(Rt=Rt_out.cpu().numpy(), P=P_out.cpu().numpy(), xyz=X_out.cpu().numpy()[:n],
+                node_err=err.cpu().numpy()[:d["n_nodes"]], trace=trace.cpu().numpy(), report=report.cpu().numpy())
+
+
+def reg_run(engine, d, K, Rt, reg, xyz, flags=None, max_tracks=None, n_samples=NS, inlier_px=IP, min_inliers=MIN_IN,
+            refine_iters=ITERS, seed=SEED):
+    """pgx_register_frames_dev on the context's stream, one sync -> dict of host arrays"""
+    nf = d["nf"]
+    mt, dK, dRt, X, fl, Rt_out, P_out = padded_inputs(d, K, Rt, xyz, flags, max_tracks)
+    dreg = torch.from_numpy(np.ascontiguousarray(reg, np.int32)).to(DEV)
+    stats, ferr = torch.full((nf, 4), 9, **I32), torch.full((nf, 2), 5.0, **F64)
+    ni, report = torch.full((nf * d["stride"],), 9, **I32), torch.full((8,), 7, **I32)
+    torch.cuda.synchronize()
+    engine.register_frames_dev(d["kp"], d["F"], d["stride"], nf, dK, dRt, dreg, d["off"], d["nodes"], d["tsum"], mt, X, Rt_out,
+                               P_out, stats, ferr, report, n_samples, inlier_px, min_inliers, refine_iters, seed, d_track_flags=fl,
+                               d_node_inlier=ni, d_frame_ids=None if d["identity"] else d["ids"])
+    engine.check_status()
+    return dict(Rt=Rt_out.cpu().numpy(), P=P_out.cpu().numpy(), frame_stats=stats.cpu().numpy(), frame_err=ferr.cpu().numpy(),
+                node_inlier=ni.cpu().numpy()[:d["n_nodes"]], report=report.cpu().numpy())
+
+
+def decisions(trace, report):
+    """accept / reject per attempted step, read from the trace: lambda falls on acceptance, rises on rejection or a non-PD
+    solve, and stays for the 'small step' stop"""
+    out = []
+    for i in range(1, int(report[0]) + 1):
+        lam0, lam1 = trace[i - 1, 1], trace[i, 1]
+        out.append("accept" if lam1 < lam0 or (trace[i, 0] < trace[i - 1, 0]) else ("small" if lam1 == lam0 else "reject"))
+    return out
+
+
+def yard_decisions(e):
+    return ["reject" if x == "nonpd" else x for x in e["decisions"]]
+
+
+def ba_check_against_yardstick(got, e, scale):
+    """decisions equal wherever the yardstick's cost change is resolved (|C_i - C_i+1| > 1e-12 C_i); the trace to 1e-9
+    relative over the common rows; Rt and xyz to 1e-8 of the scene scale"""
+    dg, de = decisions(got["trace"], got["report"]), yard_decisions(e)
+    C = e["trace"][:, 0]
+    resolved = 0
+    for i in range(len(de)):
+        if not np.isfinite(C[i + 1]) or abs(C[i] - C[i + 1]) <= 1e-12 * C[i]:
+            break
+        resolved += 1
+    assert dg[:resolved] == de[:resolved], (dg, de)
+    assert got["report"][2] in (1, 2, 3) and e["report"][2] in (1, 2, 3)
+    k = min(len(dg), len(de)) + 1
+    assert np.allclose(got["trace"][:k, 0], e["trace"][:k, 0], rtol=1e-9, atol=0), (got["trace"][:k], e["trace"][:k])
+    for k in ("Rt", "xyz"):
+        assert (np.isnan(got[k]) == np.isnan(e[k])).all(), k
+        assert np.nanmax(np.abs(got[k] - e[k])) <= 1e-8 * scale, k
+    assert (got["report"][3:6] == e["report"][3:6]).all()
+    return dg, de
+
+
+def tri_check_against_yardstick(got, kps, P, min_par, max_e, iters, stop_band=False):
+    """stop_band: hold the refined points to max(1e-9 dist, ref.stop_band) (scenes with narrow-baseline tracks; see there)"""
+    ref = triangulate_ref
+    e = ref.triangulate(kps, P, got["offsets"], got["nodes"], min_par, max_e, iters)
+    near = ref.near_threshold(e, min_par, max_e)
+    assert (got["flags"][~near] == e["flags"][~near]).all(), np.flatnonzero((got["flags"] != e["flags"]) & ~near)
+    excluded = np.flatnonzero(near & (got["flags"] != e["flags"]))
+    fin = np.isfinite(e["xyz"]).all(1)
+    assert (np.isfinite(got["xyz"]).all(1) == fin).all()
+    known, C, _, _ = ref.cameras(P)
+    S = np.array([C[[f for f, _ in got["nodes"][a:b] if known[f]]].mean(0) if fin[t] else np.zeros(3)
+                  for t, (a, b) in enumerate(zip(got["offsets"][:-1], got["offsets"][1:]))])
+    dist = np.linalg.norm(e["xyz"] - S, axis=1)
+    ok = fin & (e["parallax"] >= 1.0)
+    dx = np.linalg.norm(got["xyz"] - e["xyz"], axis=1)
+    if iters > 0:
+        tol = 1e-9 * dist
+        if stop_band:
+            tol = np.maximum(tol, ref.stop_band(kps, P, got["offsets"], got["nodes"], e))
+        assert (dx[ok] <= tol[ok]).all(), (dx[ok] / tol[ok]).max()
+        assert np.abs(got["quality"][fin, :2] - e["quality"][fin, :2]).max(initial=0) <= 1e-6
+    else:
+        assert (dx[fin] <= 1e-6 * np.linalg.norm(e["xyz"][fin], axis=1).clip(1.0)).all()
+    assert np.abs(got["quality"][fin, 2] - e["quality"][fin, 2]).max(initial=0) <= 1e-6
+    assert np.allclose(got["node_err"], e["node_err"], rtol=0, atol=1e-6, equal_nan=True)
+    assert (np.isnan(got["node_err"]) == np.isnan(e["node_err"])).all()
+    if not len(excluded):
+        assert (got["summary"] == e["summary"]).all(), (got["summary"], e["summary"])
+    return e, excluded
+
+
+def random_case(seed, F, stride, dmax=60):
+    rng = np.random.default_rng(seed)
+    counts = rng.integers(0, stride + 1, F).astype(np.int32)
+    counts[rng.integers(0, F)] = 0
+    pl = [(a, b) for a in range(F) for b in range(F) if a != b and rng.random() < 0.6]
+    m = np.zeros((len(pl), stride, 3), dtype=np.int32)
+    m[..., 0] = rng.integers(0, stride, m.shape[:2])
+    m[..., 1] = rng.integers(0, stride, m.shape[:2])
+    m[..., 2] = rng.integers(0, dmax, m.shape[:2])
+    m[rng.random(m.shape[:2]) < 0.1] = [0, 0, INT_MAX]
+    return counts, pl, m
+
+
+def constructed_job(F, K, seed, junk=0.3):
+    """F frames x K keypoints with known tracks: ground-truth point g sits at keypoint perm_f[g] of frame f and is visible in
+    a frame with probability 0.8; every ordered pair (a < b) lists true correspondences with a small distance and fills the
+    other entries with junk matches at distances >= 90 (what the greedy matcher's forced assignments look like)."""
+    rng = np.random.default_rng(seed)
+    perm = np.stack([rng.permutation(K) for _ in range(F)])          # perm[f][g] = keypoint index of point g in frame f
+    inv = np.argsort(perm, axis=1)                                     # inv[f][k] = point at keypoint k
+    vis = rng.random((F, K)) < 0.8                                     # vis[f][g]
+    pl = [(a, b) for a in range(F) for b in range(a + 1, F)]
+    m = np.zeros((len(pl), K, 3), dtype=np.int32)
+    for p, (a, b) in enumerate(pl):
+        g = inv[a]                                                     # point of each keypoint of frame a
+        true = vis[a][g] & vis[b][g]
+        m[p, :, 0] = np.arange(K)
+        m[p, :, 1] = np.where(true, perm[b][g], rng.integers(0, K, K))
+        m[p, :, 2] = np.where(true, rng.integers(0, 20, K), rng.integers(90, 140, K))
+        order = rng.permutation(K)                                     # any list order
+        m[p] = m[p][order]
+    counts = np.full(F, K, dtype=np.int32)
+    return counts, pl, m, perm, vis

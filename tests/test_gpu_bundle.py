@@ -8,83 +8,18 @@ import pytest
 import torch
 
 import bundle_ref as ref
+import geom_gpu as g
 import photogrammetry_amd as pg
+from geom_gpu import DEV, F64, I32, INF, bits, device_problem
+from geom_gpu import ba_check_against_yardstick as check_against_yardstick
+from geom_gpu import ba_run as run
 from photogrammetry_amd import synth
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-I32 = dict(dtype=torch.int32, device=DEV)
-F64 = dict(dtype=torch.float64, device=DEV)
-INF = float("inf")
-
-
-def device_problem(kps, off, nodes, slots=None, n_slots=None):
-    """Device buffers: keypoints by slot (slots[f] = frame f's slot; other slots padding with frame id -1), offsets, nodes and
-    a track summary with n_tracks."""
-    nf = len(kps)
-    slots = list(range(nf)) if slots is None else list(slots)
-    F = nf if n_slots is None else n_slots
-    stride = max(1, max(len(k) for k in kps))
-    kp = np.zeros((F, stride), dtype=pg.KEYPOINT_DTYPE)
-    ids = np.full(F, -1, np.int32)
-    for f, k in enumerate(kps):
-        kp[slots[f], :len(k)] = k
-        ids[slots[f]] = f
-    n = len(off) - 1
-    return dict(kp=torch.from_numpy(kp.view(np.int32).reshape(F, stride, 4)).to(DEV), ids=torch.from_numpy(ids).to(DEV), F=F,
-                nf=nf, stride=stride, identity=n_slots is None and slots == list(range(nf)),
-                off=torch.from_numpy(np.asarray(off, np.int32)).to(DEV),
-                nodes=torch.from_numpy(np.ascontiguousarray(nodes, np.int32).reshape(-1, 2)).to(DEV),
-                tsum=torch.tensor([n, len(nodes), 0, 0, 0, 0, 0, 0], **I32), n_tracks=n, n_nodes=len(nodes))
-
-
-def run(engine, d, K, Rt, fixed, xyz, iters=20, huber=INF, lam0=1e-3, max_tracks=None, flags=None):
-    """pgx_bundle_adjust_dev on the context's stream, one sync -> dict of host arrays"""
-    nf, n = d["nf"], d["n_tracks"]
-    mt = n if max_tracks is None else max_tracks
-    dK = torch.from_numpy(np.ascontiguousarray(K, np.float64).reshape(nf, 4)).to(DEV)
-    dRt = torch.from_numpy(np.ascontiguousarray(Rt, np.float64).reshape(nf, 12)).to(DEV)
-    dfx = torch.from_numpy(np.ascontiguousarray(fixed, np.int32)).to(DEV)
-    X = torch.full((max(mt, n, 1), 3), 3.0, **F64)
-    X[:n] = torch.from_numpy(np.ascontiguousarray(xyz, np.float64).reshape(n, 3))
-    fl = None
-    if flags is not None:
-        fl = torch.full((max(mt, n, 1),), 0, **I32)
-        fl[:n] = torch.from_numpy(np.asarray(flags, np.int32))
-    Rt_out, P_out = torch.full((nf, 12), 5.0, **F64), torch.full((nf, 12), 5.0, **F64)
-    X_out = torch.full((max(mt, n, 1), 3), 5.0, **F64)
-    err = torch.full((nf * d["stride"],), 5.0, **F64)
-    trace, report = torch.full((iters + 1, 2), 5.0, **F64), torch.full((8,), 7, **I32)
-    torch.cuda.synchronize()
-    engine.bundle_adjust_dev(d["kp"], d["F"], d["stride"], nf, dK, dRt, dfx, d["off"], d["nodes"], d["tsum"], mt, X, Rt_out, P_out,
-                             X_out, trace, report, iters, huber, lam0, d_track_flags=fl, d_node_err=err,
-                             d_frame_ids=None if d["identity"] else d["ids"])
-    engine.check_status()
-    return dict(Rt=Rt_out.cpu().numpy(), P=P_out.cpu().numpy(), xyz=X_out.cpu().numpy()[:n],
-                node_err=err.cpu().numpy()[:d["n_nodes"]], trace=trace.cpu().numpy(), report=report.cpu().numpy())
-
-
-def decisions(trace, report):
-    """accept / reject per attempted step, read from the trace: lambda falls on acceptance, rises on rejection or a non-PD
-    solve, and stays for the 'small step' stop"""
-    out = []
-    for i in range(1, int(report[0]) + 1):
-        lam0, lam1 = trace[i - 1, 1], trace[i, 1]
-        out.append("accept" if lam1 < lam0 or (trace[i, 0] < trace[i - 1, 0]) else ("small" if lam1 == lam0 else "reject"))
-    return out
-
-
-def yard_decisions(e):
-    return ["reject" if x == "nonpd" else x for x in e["decisions"]]
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint8).tobytes()
 
 
 def same_bits(a, b):
-    for k in ("Rt", "P", "xyz", "node_err", "trace", "report"):
-        assert bits(a[k]) == bits(b[k]), k
+    g.same_bits(a, b, g.BA_KEYS)
 
 
 def problem(n_points=2000, nf=12, seed=5, offset=(0.0, 0.0, 0.0), fixed_frames=(0, 11), perturb_seed=7, pairs=None):
@@ -94,27 +29,6 @@ def problem(n_points=2000, nf=12, seed=5, offset=(0.0, 0.0, 0.0), fixed_frames=(
     fixed[list(fixed_frames)] = 1
     Rt, X = synth.perturb(s["Rt"], s["points"][pid], seed=perturb_seed, fixed=fixed)
     return s, off, nodes, pid, fixed, Rt, X
-
-
-def check_against_yardstick(got, e, scale):
-    """decisions equal wherever the yardstick's cost change is resolved (|C_i - C_i+1| > 1e-12 C_i); the trace to 1e-9
-    relative over the common rows; Rt and xyz to 1e-8 of the scene scale"""
-    dg, de = decisions(got["trace"], got["report"]), yard_decisions(e)
-    C = e["trace"][:, 0]
-    resolved = 0
-    for i in range(len(de)):
-        if not np.isfinite(C[i + 1]) or abs(C[i] - C[i + 1]) <= 1e-12 * C[i]:
-            break
-        resolved += 1
-    assert dg[:resolved] == de[:resolved], (dg, de)
-    assert got["report"][2] in (1, 2, 3) and e["report"][2] in (1, 2, 3)
-    k = min(len(dg), len(de)) + 1
-    assert np.allclose(got["trace"][:k, 0], e["trace"][:k, 0], rtol=1e-9, atol=0), (got["trace"][:k], e["trace"][:k])
-    for k in ("Rt", "xyz"):
-        assert (np.isnan(got[k]) == np.isnan(e[k])).all(), k
-        assert np.nanmax(np.abs(got[k] - e[k])) <= 1e-8 * scale, k
-    assert (got["report"][3:6] == e["report"][3:6]).all()
-    return dg, de
 
 
 def test_against_yardstick_truth_and_offset(engine):

@@ -2,8 +2,8 @@
 arithmetic changes: the wave-per-track phase and several nodes per lane, second grid-stride passes, the largest reduced camera
 system, sample chunks and the scoring tile's edges.  The tracks are cut to exact lengths on the host (synth.cut_tracks) and go
 straight to the *_dev calls with a hand-made track summary, so that their lengths do not depend on the track graph.  Every
-case is held to its stage's numpy yardstick with the comparison helpers and tolerances of tests/test_gpu_{triangulate,bundle,
-register}.py, and to itself bit for bit where only the grid, the slot layout or the chunking changes.  Each test asserts on the
+case is held to its stage's numpy yardstick with the comparison helpers and tolerances that tests/test_gpu_{triangulate,
+bundle,register}.py use (tests/geom_gpu.py), and to itself bit for bit where only the grid, the slot layout or the chunking changes.  Each test asserts on the
 host that its shape reaches the path it names, so that a later change to synth cannot quietly shrink it."""
 import numpy as np
 import pytest
@@ -11,16 +11,12 @@ import torch
 
 import bundle_ref
 import register_ref
-import test_gpu_bundle as gb
-import test_gpu_register as gr
-import test_gpu_triangulate as gt
+import geom_gpu as g
 import triangulate_ref as tref
+from geom_gpu import DEV, F64, I32
 from photogrammetry_amd import synth
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-I32 = dict(dtype=torch.int32, device=DEV)
-F64 = dict(dtype=torch.float64, device=DEV)
 
 # the kernels' launch shapes (k_triangulate.hip, k_bundle.hip, k_register.hip)
 TRI_GROUPS_G64 = 1024 * 256 // 64       # TRI_GRID_MAX workgroups x TRI_NT threads / 64 lanes: wave groups of one pass
@@ -35,7 +31,7 @@ def reg_chunk(n_frames, n_samples):
 
 
 def tri_run(engine, d, P, min_par=1.0, max_e=2.0, iters=10, max_tracks=None):
-    """pgx_triangulate_tracks_dev on gb.device_problem's buffers, one sync -> the dict gt.check_against_yardstick reads"""
+    """pgx_triangulate_tracks_dev on g.device_problem's buffers, one sync -> the dict g.tri_check_against_yardstick reads"""
     nf, n = d["nf"], d["n_tracks"]
     mt = n if max_tracks is None else max_tracks
     xyz, q = torch.full((max(mt, 1), 3), 5.0, **F64), torch.full((max(mt, 1), 3), 5.0, **F64)
@@ -93,10 +89,10 @@ def test_triangulate_every_length_class_in_one_call(engine):
         assert (L == e).sum() >= 150, (e, (L == e).sum())
     assert ((L > 32) & (L <= 64)).any()        # G = 64: one node per lane at most
     assert (L > 64).any() and L.max() == nf    # G = 64: two or three nodes per lane
-    d = gb.device_problem(s["kps"], off, nodes)
+    d = g.device_problem(s["kps"], off, nodes)
     for iters in (10, 0):
         got = tri_run(engine, d, s["P"], 1.0, 2.0, iters)
-        e, excluded = gt.check_against_yardstick(got, s["kps"], s["P"], 1.0, 2.0, iters, stop_band=True)
+        e, excluded = g.tri_check_against_yardstick(got, s["kps"], s["P"], 1.0, 2.0, iters, stop_band=True)
         if iters > 0:
             assert_points_within_1e9(got, e, s["P"], L > 64)
         assert (got["flags"][L > 32] == 0).mean() > 0.9       # the long tracks are valid points, not flagged away
@@ -116,21 +112,21 @@ def test_triangulate_long_tracks_second_grid_pass(engine):
     off, nodes, _ = synth.cut_tracks(s, lengths, seed=2)
     L = np.diff(off)
     assert ((L > 32) & (L <= 64)).sum() > TRI_GROUPS_G64, (L > 32).sum()
-    d = gb.device_problem(s["kps"], off, nodes)
+    d = g.device_problem(s["kps"], off, nodes)
     base = tri_run(engine, d, s["P"], 1.0, 2.0, 10, max_tracks=len(nodes))
-    gt.check_against_yardstick(base, s["kps"], s["P"], 1.0, 2.0, 10)
+    g.tri_check_against_yardstick(base, s["kps"], s["P"], 1.0, 2.0, 10)
     for mt in (d["n_tracks"], d["n_tracks"] + 5000):
         other = tri_run(engine, d, s["P"], 1.0, 2.0, 10, max_tracks=mt)
-        gt.same_bits(base, other)
-        assert gt.bits(base["node_err"]) == gt.bits(other["node_err"])
+        g.same_bits(base, other, g.TRI_KEYS)
+        assert g.bits(base["node_err"]) == g.bits(other["node_err"])
     n1 = 1000
     assert tri_grid(n1) == 250 and tri_grid(n1 + 5000) == 1024 == tri_grid(len(nodes))
-    d1 = gb.device_problem(s["kps"], off[:n1 + 1], nodes[:off[n1]])
+    d1 = g.device_problem(s["kps"], off[:n1 + 1], nodes[:off[n1]])
     for mt in (n1, n1 + 5000):
         sub = tri_run(engine, d1, s["P"], 1.0, 2.0, 10, max_tracks=mt)
         for k in ("xyz", "quality", "flags"):
-            assert gt.bits(sub[k]) == gt.bits(base[k][:n1]), (mt, k)
-        assert gt.bits(sub["node_err"]) == gt.bits(base["node_err"][:off[n1]]), mt
+            assert g.bits(sub[k]) == g.bits(base[k][:n1]), (mt, k)
+        assert g.bits(sub["node_err"]) == g.bits(base["node_err"][:off[n1]]), mt
 
 
 def test_triangulate_bench_shape(engine):
@@ -144,14 +140,14 @@ def test_triangulate_bench_shape(engine):
     off, nodes, _ = synth.cut_tracks(s, rng.integers(2, 65, size=8000), seed=3)
     L = np.diff(off)
     assert len(L) > 7500 and (L <= 8).any() and ((L > 8) & (L <= 32)).any() and (L > 32).any() and L.max() == 64
-    d = gb.device_problem(s["kps"], off, nodes)
+    d = g.device_problem(s["kps"], off, nodes)
     base = tri_run(engine, d, s["P"], 1.0, 2.0, 10)
-    e, _ = gt.check_against_yardstick(base, s["kps"], s["P"], 1.0, 2.0, 10, stop_band=True)
+    e, _ = g.tri_check_against_yardstick(base, s["kps"], s["P"], 1.0, 2.0, 10, stop_band=True)
     assert_points_within_1e9(base, e, s["P"], L > 32)
     slots, F = padded_slots(nf, 5, 4)
-    perm = tri_run(engine, gb.device_problem(s["kps"], off, nodes, slots=slots, n_slots=F), s["P"], 1.0, 2.0, 10)
-    gt.same_bits(base, perm)
-    assert gt.bits(base["node_err"]) == gt.bits(perm["node_err"])
+    perm = tri_run(engine, g.device_problem(s["kps"], off, nodes, slots=slots, n_slots=F), s["P"], 1.0, 2.0, 10)
+    g.same_bits(base, perm, g.TRI_KEYS)
+    assert g.bits(base["node_err"]) == g.bits(perm["node_err"])
 
 
 # ------------------------------------------------------------------------------------------------------------ bundle adjustment
@@ -166,10 +162,10 @@ def ba_problem(n_points, nf, lengths, seed, perturb_seed=7):
 
 
 def ba_check(engine, s, off, nodes, fixed, Rt, X, d=None):
-    d = d or gb.device_problem(s["kps"], off, nodes)
-    got = gb.run(engine, d, s["K"], Rt, fixed, X)
+    d = d or g.device_problem(s["kps"], off, nodes)
+    got = g.ba_run(engine, d, s["K"], Rt, fixed, X)
     e = bundle_ref.bundle_adjust(s["kps"], s["K"], Rt, fixed, off, nodes, X, max_iters=20)
-    dg, de = gb.check_against_yardstick(got, e, 5.0)
+    dg, de = g.ba_check_against_yardstick(got, e, 5.0)
     print("gpu", dg, got["report"].tolist(), "yardstick", de, e["report"].tolist())
     assert got["report"][1] >= 2         # steps were taken and accepted
     return d, got
@@ -187,9 +183,10 @@ def test_bundle_62_free_cameras_layouts_and_capacity(engine):
     assert (L > BA_G).any() and (L > 2 * BA_G).any() and L.max() == nf
     d, got = ba_check(engine, s, off, nodes, fixed, Rt, X)
     assert got["report"][3] == 62
-    gb.same_bits(got, gb.run(engine, d, s["K"], Rt, fixed, X, max_tracks=d["n_tracks"] + 3000))
+    g.same_bits(got, g.ba_run(engine, d, s["K"], Rt, fixed, X, max_tracks=d["n_tracks"] + 3000), g.BA_KEYS)
     slots, F = padded_slots(nf, 7, 5)
-    gb.same_bits(got, gb.run(engine, gb.device_problem(s["kps"], off, nodes, slots=slots, n_slots=F), s["K"], Rt, fixed, X))
+    g.same_bits(got, g.ba_run(engine, g.device_problem(s["kps"], off, nodes, slots=slots, n_slots=F), s["K"], Rt, fixed, X),
+                g.BA_KEYS)
 
 
 def test_bundle_128_free_cameras(engine):
@@ -272,20 +269,20 @@ def test_register_sample_chunks_change_no_result(engine, n_samples):
     ch = reg_chunk(big, n_samples)
     n_chunks = -(-n_samples // ch)
     assert ch == 64 and n_chunks == {100: 2, 128: 2, 3000: 47}[n_samples]
-    e = register_ref.register(kps, s["K"], s["Rt"], reg, off, nodes, xyz, None, n_samples, ip, gr.MIN_IN, gr.ITERS, gr.SEED)
+    e = register_ref.register(kps, s["K"], s["Rt"], reg, off, nodes, xyz, None, n_samples, ip, g.MIN_IN, g.ITERS, g.SEED)
     assert (e["frame_stats"][2:, 2] >= ch).all(), e["frame_stats"][2:, 2]       # every winner lies past the first chunk
-    a = gr.run(engine, gr.device_problem(kps, off, nodes), s["K"], s["Rt"], reg, xyz, n_samples=n_samples, inlier_px=ip)
+    a = g.reg_run(engine, g.device_problem(kps, off, nodes), s["K"], s["Rt"], reg, xyz, n_samples=n_samples, inlier_px=ip)
     check_register(a, e)
     assert a["report"][1] == 2
     K2 = np.concatenate([s["K"], np.tile(s["K"][:1], (big - nf, 1))])
     Rt2 = np.concatenate([s["Rt"], np.tile(s["Rt"][:1], (big - nf, 1))])
     reg2 = np.concatenate([reg, np.zeros(big - nf, np.int32)])
     kps2 = kps + [kps[0][:0]] * (big - nf)
-    b = gr.run(engine, gr.device_problem(kps2, off, nodes), K2, Rt2, reg2, xyz, n_samples=n_samples, inlier_px=ip)
+    b = g.reg_run(engine, g.device_problem(kps2, off, nodes), K2, Rt2, reg2, xyz, n_samples=n_samples, inlier_px=ip)
     for k in ("Rt", "P", "frame_stats", "frame_err"):
-        assert gt.bits(a[k]) == gt.bits(b[k][:nf]), k
-    assert gt.bits(a["node_inlier"]) == gt.bits(b["node_inlier"]) and gt.bits(a["report"]) == gt.bits(b["report"])
-    assert (b["frame_stats"][nf:] == -1).all() and gt.bits(b["Rt"][nf:]) == gt.bits(Rt2[nf:])
+        assert g.bits(a[k]) == g.bits(b[k][:nf]), k
+    assert g.bits(a["node_inlier"]) == g.bits(b["node_inlier"]) and g.bits(a["report"]) == g.bits(b["report"])
+    assert (b["frame_stats"][nf:] == -1).all() and g.bits(b["Rt"][nf:]) == g.bits(Rt2[nf:])
     print("winning samples", a["frame_stats"][2:, 2].tolist(), "chunk", ch)
 
 
@@ -299,8 +296,8 @@ def test_register_bench_like_scene(engine):
     xyz = s["points"][pid]
     L = np.diff(off)
     assert (L > REG_G).any() and (L > 3 * REG_G).any()
-    got = gr.run(engine, gr.device_problem(kps, off, nodes), s["K"], s["Rt"], reg, xyz)
-    e = register_ref.register(kps, s["K"], s["Rt"], reg, off, nodes, xyz, None, gr.NS, gr.IP, gr.MIN_IN, gr.ITERS, gr.SEED)
+    got = g.reg_run(engine, g.device_problem(kps, off, nodes), s["K"], s["Rt"], reg, xyz)
+    e = register_ref.register(kps, s["K"], s["Rt"], reg, off, nodes, xyz, None, g.NS, g.IP, g.MIN_IN, g.ITERS, g.SEED)
     check_register(got, e)
     assert got["report"][0] == 62 and got["report"][1] == 62, got["report"]
 
@@ -402,7 +399,7 @@ def test_register_scoring_tile_edges(engine):
     s, kps, off, nodes, xyz, reg = tile_scene()
     corr, _ = register_ref.correspondences(kps, reg, s["K"], off, nodes, xyz)
     assert {f: len(corr[f][0]) for f in corr} == TILE_COUNTS
-    H = hypothesis_inliers(kps, s["K"], reg, off, nodes, xyz, gr.NS, gr.IP, gr.SEED)
+    H = hypothesis_inliers(kps, s["K"], reg, off, nodes, xyz, g.NS, g.IP, g.SEED)
     for f, (M, valid) in H.items():
         n = M.shape[1]
         w = winning_hypothesis(M, valid, np.ones(n, bool))
@@ -411,8 +408,8 @@ def test_register_scoring_tile_edges(engine):
         assert M[w].sum() == (n + 1) // 2, (f, M[w].sum())                 # the winner is a P hypothesis
         for name, keep in miscounts(n).items():
             assert winning_hypothesis(M, valid, keep) != w, (n, name)
-    got = gr.run(engine, gr.device_problem(kps, off, nodes), s["K"], s["Rt"], reg, xyz)
-    e = register_ref.register(kps, s["K"], s["Rt"], reg, off, nodes, xyz, None, gr.NS, gr.IP, gr.MIN_IN, gr.ITERS, gr.SEED)
+    got = g.reg_run(engine, g.device_problem(kps, off, nodes), s["K"], s["Rt"], reg, xyz)
+    e = register_ref.register(kps, s["K"], s["Rt"], reg, off, nodes, xyz, None, g.NS, g.IP, g.MIN_IN, g.ITERS, g.SEED)
     check_register(got, e)
     win = [winning_hypothesis(*H[f], np.ones(TILE_COUNTS[f], bool)) // 4 for f in range(3, 7)]
     assert (e["frame_stats"][3:, 2] == win).all()

@@ -9,69 +9,19 @@ import numpy as np
 import pytest
 import torch
 
+import geom_gpu as g
 import photogrammetry_amd as pg
 import register_ref as ref
 import triangulate_ref as tri
+from geom_gpu import DEV, F64, I32, INF, IP, ITERS, MIN_IN, NS, SEED, bits, device_problem
+from geom_gpu import reg_run as run
 from photogrammetry_amd import synth
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-I32 = dict(dtype=torch.int32, device=DEV)
-F64 = dict(dtype=torch.float64, device=DEV)
-INF = float("inf")
-NS, IP, MIN_IN, ITERS, SEED = 128, 2.0, 12, 10, 7
-
-
-def device_problem(kps, off, nodes, slots=None, n_slots=None):
-    nf = len(kps)
-    slots = list(range(nf)) if slots is None else list(slots)
-    F = nf if n_slots is None else n_slots
-    stride = max(1, max(len(k) for k in kps))
-    kp = np.zeros((F, stride), dtype=pg.KEYPOINT_DTYPE)
-    ids = np.full(F, -1, np.int32)
-    for f, k in enumerate(kps):
-        kp[slots[f], :len(k)] = k
-        ids[slots[f]] = f
-    n = len(off) - 1
-    return dict(kp=torch.from_numpy(kp.view(np.int32).reshape(F, stride, 4)).to(DEV), ids=torch.from_numpy(ids).to(DEV), F=F,
-                nf=nf, stride=stride, identity=n_slots is None and slots == list(range(nf)),
-                off=torch.from_numpy(np.asarray(off, np.int32)).to(DEV),
-                nodes=torch.from_numpy(np.ascontiguousarray(nodes, np.int32).reshape(-1, 2)).to(DEV),
-                tsum=torch.tensor([n, len(nodes), 0, 0, 0, 0, 0, 0], **I32), n_tracks=n, n_nodes=len(nodes))
-
-
-def run(engine, d, K, Rt, reg, xyz, flags=None, max_tracks=None, n_samples=NS, inlier_px=IP, min_inliers=MIN_IN,
-        refine_iters=ITERS, seed=SEED):
-    nf, n = d["nf"], d["n_tracks"]
-    mt = n if max_tracks is None else max_tracks
-    dK = torch.from_numpy(np.ascontiguousarray(K, np.float64).reshape(nf, 4)).to(DEV)
-    dRt = torch.from_numpy(np.ascontiguousarray(Rt, np.float64).reshape(nf, 12)).to(DEV)
-    dreg = torch.from_numpy(np.ascontiguousarray(reg, np.int32)).to(DEV)
-    X = torch.full((max(mt, n, 1), 3), 3.0, **F64)
-    X[:n] = torch.from_numpy(np.ascontiguousarray(xyz, np.float64).reshape(n, 3))
-    fl = None
-    if flags is not None:
-        fl = torch.full((max(mt, n, 1),), 0, **I32)
-        fl[:n] = torch.from_numpy(np.asarray(flags, np.int32))
-    Rt_out, P_out = torch.full((nf, 12), 5.0, **F64), torch.full((nf, 12), 5.0, **F64)
-    stats, ferr = torch.full((nf, 4), 9, **I32), torch.full((nf, 2), 5.0, **F64)
-    ni, report = torch.full((nf * d["stride"],), 9, **I32), torch.full((8,), 7, **I32)
-    torch.cuda.synchronize()
-    engine.register_frames_dev(d["kp"], d["F"], d["stride"], nf, dK, dRt, dreg, d["off"], d["nodes"], d["tsum"], mt, X, Rt_out,
-                               P_out, stats, ferr, report, n_samples, inlier_px, min_inliers, refine_iters, seed, d_track_flags=fl,
-                               d_node_inlier=ni, d_frame_ids=None if d["identity"] else d["ids"])
-    engine.check_status()
-    return dict(Rt=Rt_out.cpu().numpy(), P=P_out.cpu().numpy(), frame_stats=stats.cpu().numpy(), frame_err=ferr.cpu().numpy(),
-                node_inlier=ni.cpu().numpy()[:d["n_nodes"]], report=report.cpu().numpy())
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint8).tobytes()
 
 
 def same_bits(a, b):
-    for k in ("Rt", "P", "frame_stats", "frame_err", "node_inlier", "report"):
-        assert bits(a[k]) == bits(b[k]), k
+    g.same_bits(a, b, g.REG_KEYS)
 
 
 def problem(n_points=2000, nf=12, seed=5, offset=(0.0, 0.0, 0.0), outlier_frame=6, outlier_rate=0.2):

@@ -14,10 +14,9 @@ import torch
 
 from oracle import tracks_np
 import photogrammetry_amd as pg
+from geom_gpu import DEV, INT_MAX, constructed_job, random_case
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-INT_MAX = 2**31 - 1
 
 
 @pytest.fixture(scope="module")
@@ -94,24 +93,11 @@ def test_hand_built_conflict_tail_and_empty_frames(engine):
     assert exp == []
 
 
-def _random_case(seed, F, stride, dmax=60):
-    rng = np.random.default_rng(seed)
-    counts = rng.integers(0, stride + 1, F).astype(np.int32)
-    counts[rng.integers(0, F)] = 0
-    pl = [(a, b) for a in range(F) for b in range(F) if a != b and rng.random() < 0.6]
-    m = np.zeros((len(pl), stride, 3), dtype=np.int32)
-    m[..., 0] = rng.integers(0, stride, m.shape[:2])
-    m[..., 1] = rng.integers(0, stride, m.shape[:2])
-    m[..., 2] = rng.integers(0, dmax, m.shape[:2])
-    m[rng.random(m.shape[:2]) < 0.1] = [0, 0, INT_MAX]
-    return counts, pl, m
-
-
 @pytest.mark.parametrize("seed", range(6))
 def test_random_lists_equal_oracle(engine, seed):
     """Random lists: most components are inconsistent at a loose gate, few at a tight one; both sides of the drop rule."""
     F, stride = 5 + seed, [7, 64, 300, 257, 33, 1024][seed]
-    counts, pl, m = _random_case(seed, F, stride)
+    counts, pl, m = random_case(seed, F, stride)
     for max_dist, min_len in ((0, 2), (1, 2), (4, 1), (30, 3)):
         check_against_oracle(engine, counts, pl, m, stride, max_dist, min_len)
 
@@ -121,7 +107,7 @@ def test_slot_permutation_padding_and_frame_subset(engine):
     build the graph for a subset of the frames.  d_frame_ids maps slots to frame numbers; -1 slots and every image pair
     touching one are skipped."""
     F, stride = 7, 96
-    counts, pl, m = _random_case(42, F, stride, dmax=40)
+    counts, pl, m = random_case(42, F, stride, dmax=40)
     exp, exp_tof, exp_s = tracks_np.tracks(counts, pl, m, 3, 2)
     assert exp_s["n_tracks"] > 3
     # 3 "ranks", 3 slots each: slot of frame f = (f % 3) * 3 + f // 3; slots 5 and 8 are padding
@@ -148,35 +134,13 @@ def test_slot_permutation_padding_and_frame_subset(engine):
     assert as_lists(off, nodes) == exp2 and summ == exp2_s
 
 
-def _constructed_job(F, K, seed, junk=0.3):
-    """F frames x K keypoints with known tracks: ground-truth point g sits at keypoint perm_f[g] of frame f and is visible in
-    a frame with probability 0.8; every ordered pair (a < b) lists true correspondences with a small distance and fills the
-    other entries with junk matches at distances >= 90 (what the greedy matcher's forced assignments look like)."""
-    rng = np.random.default_rng(seed)
-    perm = np.stack([rng.permutation(K) for _ in range(F)])          # perm[f][g] = keypoint index of point g in frame f
-    inv = np.argsort(perm, axis=1)                                     # inv[f][k] = point at keypoint k
-    vis = rng.random((F, K)) < 0.8                                     # vis[f][g]
-    pl = [(a, b) for a in range(F) for b in range(a + 1, F)]
-    m = np.zeros((len(pl), K, 3), dtype=np.int32)
-    for p, (a, b) in enumerate(pl):
-        g = inv[a]                                                     # point of each keypoint of frame a
-        true = vis[a][g] & vis[b][g]
-        m[p, :, 0] = np.arange(K)
-        m[p, :, 1] = np.where(true, perm[b][g], rng.integers(0, K, K))
-        m[p, :, 2] = np.where(true, rng.integers(0, 20, K), rng.integers(90, 140, K))
-        order = rng.permutation(K)                                     # any list order
-        m[p] = m[p][order]
-    counts = np.full(F, K, dtype=np.int32)
-    return counts, pl, m, perm, vis
-
-
 def test_bench_size_known_tracks_and_invariances(engine):
     """64 frames x 4096 keypoints, all 2016 pairs = 8.3 M match entries (the bench job's size).  By construction the tracks at
     max_dist = 64 are exactly the ground-truth points seen in >= 2 frames, one node per frame where visible; the result is
     the same for any order of the image pairs and when the call is repeated on the same buffers; the vectorised oracle
     (scipy connected components) agrees array for array."""
     F, K = 64, 4096
-    counts, pl, m, perm, vis = _constructed_job(F, K, 7)
+    counts, pl, m, perm, vis = constructed_job(F, K, 7)
     off, nodes, tof, summ = run_dev(engine, counts, pl, m, K, 64, 2)
     nvis = vis.sum(0)
     assert summ["n_tracks"] == int((nvis >= 2).sum()) and summ["n_nodes"] == int(nvis[nvis >= 2].sum())

@@ -12,10 +12,10 @@ import torch
 
 import photogrammetry_amd as pg
 import tracks_split_ref as ref
+from geom_gpu import constructed_job, random_case
 from oracle import tracks_np
 from photogrammetry_amd import dist as pdist
 from photogrammetry_amd import synth
-from test_gpu_tracks import _constructed_job, _random_case
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -91,7 +91,7 @@ def test_hand_built_case(engine):
 @pytest.mark.parametrize("seed", range(6))
 def test_random_lists_equal_reference(engine, seed):
     F, stride = 5 + seed, [7, 64, 300, 257, 33, 1024][seed]
-    counts, pl, m = _random_case(seed, F, stride)
+    counts, pl, m = random_case(seed, F, stride)
     for max_dist, gates, min_len in ((59, [40, 20, 10, 5, 2, 1, 0], 2), (30, [8], 1), (45, [30, 12, 3], 3), (20, [], 2)):
         check(engine, counts, pl, m, stride, max_dist, gates, min_len, host=stride <= 300)
 
@@ -101,7 +101,7 @@ def test_no_gates_is_tracks_dev_and_kept_tracks_survive(engine, seed):
     """n_gates = 0 is pgx_tracks_dev bit for bit (slots [0..7]); with gates every track pgx_tracks_dev keeps is kept unchanged
     (level-0 groups are the same) and dropped_nodes never grows."""
     F, stride = 6 + seed, [64, 257, 1024][seed]
-    counts, pl, m = _random_case(10 + seed, F, stride)
+    counts, pl, m = random_case(10 + seed, F, stride)
     for max_dist in (3, 30, 59):
         p_off, p_nodes, p_tof, p_s = run_plain(engine, counts, pl, m, stride, max_dist)
         off, nodes, tof, s = run_split(engine, counts, pl, m, stride, max_dist, [])
@@ -116,7 +116,7 @@ def test_no_gates_is_tracks_dev_and_kept_tracks_survive(engine, seed):
 
 def test_pair_order_slot_permutation_padding_and_frame_subset(engine):
     F, stride = 7, 96
-    counts, pl, m = _random_case(42, F, stride, dmax=40)
+    counts, pl, m = random_case(42, F, stride, dmax=40)
     max_dist, gates = 30, [20, 6, 2]
     e_off, e_nodes, e_tof, e_s = ref.arrays(counts, pl, m, stride, max_dist, gates)
     assert e_s["per_level"][1:] != [0, 0, 0]         # the case exercises the refinement levels
@@ -150,7 +150,7 @@ def test_bench_size_recovers_the_tracks_of_the_giant_component(engine):
     component, which pgx_tracks_dev drops (test_gpu_tracks.py).  Split at the gate 64, it falls apart into exactly the
     ground-truth tracks -- pgx_tracks_dev's result at max_dist = 64 -- all of them at level 1."""
     F, K = 64, 4096
-    counts, pl, m, perm, vis = _constructed_job(F, K, 7)
+    counts, pl, m, perm, vis = constructed_job(F, K, 7)
     _, _, _, p_s = run_plain(engine, counts, pl, m, K, 200)
     assert p_s[2] >= 1 and p_s[6] > 1000
     off, nodes, tof, s = run_split(engine, counts, pl, m, K, 200, [64])

@@ -8,51 +8,35 @@ import numpy as np
 import pytest
 import torch
 
+import geom_gpu
 import photogrammetry_amd as pg
 import triangulate_ref as ref
+from geom_gpu import DEV, F64, I32, bits
+from geom_gpu import tri_check_against_yardstick as check_against_yardstick
 from photogrammetry_amd import synth
 from photogrammetry_amd._lib import PGX_DIST_NONE
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-I32 = dict(dtype=torch.int32, device=DEV)
-F64 = dict(dtype=torch.float64, device=DEV)
 
 
-def _kp_array(kps):
-    k = np.asarray(kps)
-    if k.dtype == pg.KEYPOINT_DTYPE:
-        return k
-    out = np.zeros(len(k), dtype=pg.KEYPOINT_DTYPE)
-    if len(k):
-        out["x"], out["y"] = k[:, 0], k[:, 1]
-    return out
+def same_bits(x, y):
+    geom_gpu.same_bits(x, y, geom_gpu.TRI_KEYS)
 
 
 def device_graph(kps, pairs, lists, slots=None, n_slots=None):
     """Device buffers of the graph's inputs.  slots[f] = the slot frame f sits in (default: f); other slots are padding
     (frame id -1, no keypoints).  -> dict of tensors and sizes"""
-    nf = len(kps)
-    slots = list(range(nf)) if slots is None else list(slots)
-    F = nf if n_slots is None else n_slots
-    kps = [_kp_array(k) for k in kps]
-    stride = max(1, max(len(k) for k in kps))
-    kp = np.zeros((F, stride), dtype=pg.KEYPOINT_DTYPE)
-    counts = np.zeros(F, np.int32)
-    ids = np.full(F, -1, np.int32)
-    for f, k in enumerate(kps):
-        kp[slots[f], :len(k)] = k
-        counts[slots[f]] = len(k)
-        ids[slots[f]] = f
+    lay = synth.slot_layout(kps, slots, n_slots)
+    slots, F, nf, stride = lay["slots"], lay["F"], lay["nf"], lay["stride"]
     M = max(1, len(pairs))
     m = np.zeros((M, stride, 3), np.int32)
     m[:, :, 2] = PGX_DIST_NONE
     for i, ((a, _), rows) in enumerate(zip(pairs, lists)):
         m[i, :len(rows)] = np.stack([rows["k1"], rows["k2"], rows["dist"]], 1)
     pl = np.array([(slots[a], slots[b]) for a, b in pairs], np.int32).reshape(-1, 2) if pairs else np.zeros((1, 2), np.int32)
-    return dict(kp=torch.from_numpy(kp.view(np.int32).reshape(F, stride, 4)).to(DEV), counts=torch.from_numpy(counts).to(DEV),
-                pl=torch.from_numpy(pl).to(DEV), m=torch.from_numpy(m).to(DEV), ids=torch.from_numpy(ids).to(DEV), F=F, nf=nf,
-                stride=stride, M=len(pairs), identity=n_slots is None and slots == list(range(nf)))
+    return dict(kp=torch.from_numpy(lay["kp"].view(np.int32).reshape(F, stride, 4)).to(DEV),
+                counts=torch.from_numpy(lay["counts"]).to(DEV), pl=torch.from_numpy(pl).to(DEV), m=torch.from_numpy(m).to(DEV),
+                ids=torch.from_numpy(lay["ids"]).to(DEV), F=F, nf=nf, stride=stride, M=len(pairs), identity=lay["identity"])
 
 
 def run(engine, g, P, min_par=1.0, max_e=float("inf"), iters=10, max_tracks=None, split=False, node_err=True):
@@ -88,45 +72,6 @@ def run(engine, g, P, min_par=1.0, max_e=float("inf"), iters=10, max_tracks=None
 
 def chain_pairs(nf, skip=(1, 2)):
     return [(a, a + s) for s in skip for a in range(nf - s)]
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint8).tobytes()
-
-
-def same_bits(x, y):
-    for k in ("xyz", "quality", "flags", "summary"):
-        assert bits(x[k]) == bits(y[k]), k
-
-
-def check_against_yardstick(got, kps, P, min_par, max_e, iters, stop_band=False):
-    """stop_band: hold the refined points to max(1e-9 dist, ref.stop_band) (scenes with narrow-baseline tracks; see there)"""
-    e = ref.triangulate(kps, P, got["offsets"], got["nodes"], min_par, max_e, iters)
-    near = ref.near_threshold(e, min_par, max_e)
-    assert (got["flags"][~near] == e["flags"][~near]).all(), np.flatnonzero((got["flags"] != e["flags"]) & ~near)
-    excluded = np.flatnonzero(near & (got["flags"] != e["flags"]))
-    fin = np.isfinite(e["xyz"]).all(1)
-    assert (np.isfinite(got["xyz"]).all(1) == fin).all()
-    known, C, _, _ = ref.cameras(P)
-    S = np.array([C[[f for f, _ in got["nodes"][a:b] if known[f]]].mean(0) if fin[t] else np.zeros(3)
-                  for t, (a, b) in enumerate(zip(got["offsets"][:-1], got["offsets"][1:]))])
-    dist = np.linalg.norm(e["xyz"] - S, axis=1)
-    ok = fin & (e["parallax"] >= 1.0)
-    dx = np.linalg.norm(got["xyz"] - e["xyz"], axis=1)
-    if iters > 0:
-        tol = 1e-9 * dist
-        if stop_band:
-            tol = np.maximum(tol, ref.stop_band(kps, P, got["offsets"], got["nodes"], e))
-        assert (dx[ok] <= tol[ok]).all(), (dx[ok] / tol[ok]).max()
-        assert np.abs(got["quality"][fin, :2] - e["quality"][fin, :2]).max(initial=0) <= 1e-6
-    else:
-        assert (dx[fin] <= 1e-6 * np.linalg.norm(e["xyz"][fin], axis=1).clip(1.0)).all()
-    assert np.abs(got["quality"][fin, 2] - e["quality"][fin, 2]).max(initial=0) <= 1e-6
-    assert np.allclose(got["node_err"], e["node_err"], rtol=0, atol=1e-6, equal_nan=True)
-    assert (np.isnan(got["node_err"]) == np.isnan(e["node_err"])).all()
-    if not len(excluded):
-        assert (got["summary"] == e["summary"]).all(), (got["summary"], e["summary"])
-    return e, excluded
 
 
 @pytest.mark.parametrize("offset", [(0.0, 0.0, 0.0), (1e4, -5e3, 2e4)])

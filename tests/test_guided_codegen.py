@@ -3,53 +3,17 @@
   * the compiler's listing of the band walk has no v_fma_f64: the predicate of include/pgx.h is one rounding per operation;
   * the yardstick of tests/guided_ref.py (used by tests/test_gpu_guided.py) equals a literal Python double loop.
 """
-import os
-import re
-import shutil
-import subprocess
-
 import numpy as np
-import pytest
 
-import photogrammetry_amd._lib as L
+from codeobj import instructions, kernels, listing
 from guided_ref import NONE, loop_guided, ref_guided
 
-LLVM = "/opt/rocm/lib/llvm/bin"
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 KERNELS = ("k_guided_slots", "k_guided_bucket", "k_guided_walk", "k_knn_col_init", "k_knn_col_finish")
 
 
-@pytest.fixture(scope="module")
-def code_objects(tmp_path_factory):
-    if not os.path.exists(os.path.join(LLVM, "llvm-readelf")):
-        pytest.skip("llvm-readelf not found")
-    L.build()
-    d = str(tmp_path_factory.mktemp("guided_co"))
-    so = os.path.join(d, "libpgx.so")
-    shutil.copy(L.LIB_PATH, so)
-    subprocess.run([os.path.join(LLVM, "llvm-objdump"), "--offloading", so], cwd=d, check=True, capture_output=True)
-    return [os.path.join(d, f) for f in sorted(os.listdir(d)) if "amdgcn" in f]
-
-
-def _kernels(objs, needle):
-    out = []
-    for o in objs:
-        notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", o], check=True, capture_output=True, text=True).stdout
-        for item in re.split(r"\n  - (?=\.)", notes):
-            m = re.search(r"\.name:\s+(\S+)", item)
-            if m and needle in m.group(1) and not m.group(1).endswith(".kd"):
-                md = {"name": m.group(1)}
-                for key in ("vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size"):
-                    mm = re.search(r"\.%s:\s+(\d+)" % key, item)
-                    if mm:
-                        md[key] = int(mm.group(1))
-                out.append(md)
-    return out
-
-
-def test_guided_kernels_exist_without_scratch(code_objects):
+def test_guided_kernels_exist_without_scratch():
     for needle in KERNELS:
-        mds = _kernels(code_objects, needle)
+        mds = kernels(needle)
         # the walk: k in {1, 2} x column side on / off x (256-bit descriptors in registers, any width)
         assert len({md["name"] for md in mds}) == (8 if needle == "k_guided_walk" else 1), (needle, [md["name"] for md in mds])
         for md in mds:
@@ -57,21 +21,11 @@ def test_guided_kernels_exist_without_scratch(code_objects):
             assert md["vgpr_spill_count"] == 0 and md["sgpr_spill_count"] == 0, md
 
 
-def test_walk_predicate_is_not_contracted(tmp_path):
-    hipcc = "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not found")
-    out = os.path.join(str(tmp_path), "k_guided.s")
-    subprocess.run([hipcc, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-fast-math",
-                    "--cuda-device-only", "-S", os.path.join(ROOT, "photogrammetry_amd", "csrc", "k_guided.hip"), "-o", out],
-                   check=True, capture_output=True)
-    lines = open(out).read().split("\n")
-    starts = [i for i, l in enumerate(lines) if re.match(r"^_ZN.*k_guided_walk.*:", l)]
+def test_walk_predicate_is_not_contracted():
+    lines, starts = listing("k_guided.hip", "k_guided_walk")
     assert len(starts) == 8
     for start in starts:
-        end = next(i for i in range(start, len(lines)) if lines[i].startswith(".Lfunc_end"))
-        body = [l.strip().split(";")[0].strip() for l in lines[start:end]
-                if l.startswith("\t") and not l.startswith("\t.") and not l.strip().startswith(";")]
+        body = instructions(lines, start)
         assert any(i.startswith("v_mul_f64") for i in body) and any(i.startswith("v_add_f64") for i in body), lines[start]
         assert not [i for i in body if i.startswith("v_fma_f64")], lines[start]
         assert not [i for i in body if i.startswith("scratch_")], lines[start]

@@ -23,15 +23,12 @@ record load (global_load_dwordx4) nothing touches the exec mask until the wave-u
 suppression store itself.  The round-3 listing of k_nms_phase_c<2, false> is kept as the checker's positive control."""
 import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-import photogrammetry_amd._lib as L
+from codeobj import function_lines
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
 SC1_LOAD = re.compile(r"\b(global|flat)_load_\w+\b.*\bsc1\b")
 
 
@@ -101,40 +98,9 @@ def exec_ops_between_load_and_use(window):
     return bad
 
 
-def _device_disassembly(tmp_path):
-    if not os.path.exists(OBJDUMP):
-        pytest.skip("llvm-objdump not found")
-    L.build()
-    so = os.path.join(str(tmp_path), "libpgx.so")
-    shutil.copy(L.LIB_PATH, so)
-    subprocess.run([OBJDUMP, "--offloading", so], cwd=str(tmp_path), check=True, capture_output=True)   # unbundles next to the copy
-    text = []
-    for f in sorted(os.listdir(str(tmp_path))):
-        if "amdgcn" in f:
-            text.append(subprocess.run([OBJDUMP, "-d", "--no-show-raw-insn", os.path.join(str(tmp_path), f)], check=True,
-                                       capture_output=True, text=True).stdout)
-    return "\n".join(text)
-
-
-def _function(dis, needle):
-    """Instruction lines of the one function whose symbol contains `needle`."""
-    out, on = [], False
-    for ln in dis.splitlines():
-        m = re.match(r"^[0-9a-f]+ <(.+)>:$", ln)
-        if m:
-            if on:
-                break
-            on = needle in m.group(1)
-            continue
-        if on:
-            out.append(re.sub(r"//.*$", "", ln))
-    return out
-
-
 @pytest.mark.parametrize("rr", [2, 3])
-def test_shipped_round_reads_mutable_state_only_while_staging(tmp_path, rr):
-    dis = _device_disassembly(tmp_path)
-    fn = _function(dis, "k_nmsm_roundILi%dE" % rr)
+def test_shipped_round_reads_mutable_state_only_while_staging(rr):
+    fn = function_lines("k_nmsm_roundILi%dE" % rr)
     assert len(fn) > 500, "k_nmsm_round<%d> not found in libpgx.so" % rr
     ok, why = mutable_loads_confined_to_staging(fn)
     assert ok, why
@@ -163,13 +129,12 @@ RECORD_ROUND_KERNELS = ["k_nms_phase_cILi2ELb1E", "k_nms_phase_cILi2ELb0E", "k_n
                         "10k_nms_pushE", "k_nms_phase_aE"]
 
 
-def test_record_rounds_load_under_full_exec_and_evaluate_branch_free(tmp_path):
+def test_record_rounds_load_under_full_exec_and_evaluate_branch_free():
     """k_nms_tail is not in the list on purpose: it runs the same phase_c_wave code (checked here through k_nms_phase_c) and,
     besides it, the general path's serial leftovers, whose phases are separated by block barriers inside ONE workgroup --
     no other workgroup's stores are in flight there."""
-    dis = _device_disassembly(tmp_path)
     for needle in RECORD_ROUND_KERNELS:
-        fn = _function(dis, needle)
+        fn = function_lines(needle)
         assert len(fn) > 300, needle + " not found in libpgx.so"
         wins = record_load_windows(_instructions(fn))
         assert len(wins) >= 1, needle + ": no record loads found, re-derive the check"

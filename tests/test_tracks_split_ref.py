@@ -8,10 +8,6 @@
   * the new kernels are in libpgx.so's code object with no private segment, no spills and at most 32 VGPRs.
 """
 import ctypes as C
-import os
-import re
-import shutil
-import subprocess
 import time
 
 import numpy as np
@@ -20,10 +16,10 @@ import pytest
 import photogrammetry_amd as pg
 import photogrammetry_amd._lib as L
 import tracks_split_ref as ref
+from codeobj import kernels
 from oracle import tracks_np
 
 INT_MAX = 2**31 - 1
-LLVM = "/opt/rocm/lib/llvm/bin"
 
 
 def random_case(seed, F, stride, dmax=60):
@@ -177,37 +173,9 @@ def test_host_form_builds_in_linear_time(lib):
     assert dt < 3.0, dt
 
 
-@pytest.fixture(scope="module")
-def code_objects(tmp_path_factory):
-    if not os.path.exists(os.path.join(LLVM, "llvm-readelf")):
-        pytest.skip("llvm-readelf not found")
-    L.build()
-    d = str(tmp_path_factory.mktemp("split_co"))
-    so = os.path.join(d, "libpgx.so")
-    shutil.copy(L.LIB_PATH, so)
-    subprocess.run([os.path.join(LLVM, "llvm-objdump"), "--offloading", so], cwd=d, check=True, capture_output=True)
-    return [os.path.join(d, f) for f in sorted(os.listdir(d)) if "amdgcn" in f]
-
-
-def _kernels(objs, needle):
-    out = []
-    for o in objs:
-        notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", o], check=True, capture_output=True, text=True).stdout
-        for item in re.split(r"\n  - (?=\.)", notes):
-            m = re.search(r"\.name:\s+(\S+)", item)
-            if m and needle in m.group(1) and not m.group(1).endswith(".kd"):
-                md = {"name": m.group(1)}
-                for key in ("vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size", "vgpr_count"):
-                    mm = re.search(r"\.%s:\s+(\d+)" % key, item)
-                    if mm:
-                        md[key] = int(mm.group(1))
-                out.append(md)
-    return out
-
-
-def test_split_kernels_exist_without_scratch(code_objects):
+def test_split_kernels_exist_without_scratch():
     for needle in ("k_trks_prep", "k_trks_mark", "k_trks_reset", "k_trks_union", "k_trks_flatten"):
-        mds = _kernels(code_objects, needle)
+        mds = kernels(needle)
         assert len({md["name"] for md in mds}) == 1, (needle, [md["name"] for md in mds])
         for md in mds:
             assert md["private_segment_fixed_size"] == 0, md

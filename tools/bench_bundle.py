@@ -6,7 +6,6 @@ tests (the iterations after the stop cost only their early-exit launches).  The 
 the median of the same call with max_iters = 0) / the iterations it attempted.  Writes profiles/bundle_<shape>.json (or
 --out DIR).  For the kernel split run it under `rocprofv3 --kernel-trace --stats -- python tools/bench_bundle.py`."""
 import argparse
-import json
 import os
 import sys
 import time
@@ -16,74 +15,30 @@ import torch
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT)
+import geom_bench as gb  # noqa: E402
 import photogrammetry_amd as pg  # noqa: E402
+from geom_bench import F64, I32  # noqa: E402
 from photogrammetry_amd import synth  # noqa: E402
-
-DEV = "cuda:0"
 
 
 def make_shape(rng, nf, n_points=8000):
-    s = synth.make_scene(n_points, nf, seed=1, arc_deg=120.0)
-    seen = {}
-    for f, pid in enumerate(s["point_id"]):
-        for k, p in enumerate(pid):
-            seen.setdefault(int(p), []).append((f, k))
-    tracks, pts = [], []
-    for p in sorted(seen):
-        v = seen[p]
-        L = min(len(v), int(rng.integers(2, 65)))
-        if L < 2:
-            continue
-        a = int(rng.integers(0, len(v) - L + 1))
-        tracks.append(v[a:a + L])
-        pts.append(p)
+    s, off, nodes, pts = gb.cut_scene(rng, nf, n_points)
     fixed = np.zeros(nf, np.int32)
     fixed[[0, nf - 1]] = 1
     Rt, X = synth.perturb(s["Rt"], s["points"][pts], seed=3, fixed=fixed)
-    return s, tracks, fixed, Rt, X
-
-
-def device_inputs(s, tracks, fixed, Rt, X):
-    off = np.concatenate([[0], np.cumsum([len(t) for t in tracks])])
-    nodes = np.array([n for t in tracks for n in t])
-    nf = len(s["kps"])
-    stride = max(len(k) for k in s["kps"])
-    buf = np.zeros((nf, stride), dtype=pg.KEYPOINT_DTYPE)
-    for f, k in enumerate(s["kps"]):
-        buf[f, :len(k)] = k
-    i32, f64 = dict(dtype=torch.int32, device=DEV), dict(dtype=torch.float64, device=DEV)
-    return dict(kp=torch.from_numpy(buf.view(np.int32).reshape(nf, stride, 4)).to(DEV), K=torch.from_numpy(s["K"]).to(DEV),
-                Rt=torch.from_numpy(Rt).to(DEV), fixed=torch.from_numpy(fixed).to(DEV), X=torch.from_numpy(X).to(DEV),
-                off=torch.from_numpy(off.astype(np.int32)).to(DEV), nodes=torch.from_numpy(nodes.astype(np.int32)).to(DEV),
-                tsum=torch.tensor([len(off) - 1, len(nodes), 0, 0, 0, 0, 0, 0], **i32), nf=nf, stride=stride, n_tracks=len(off) - 1,
-                n_nodes=len(nodes), lengths=np.diff(off), f64=f64, i32=i32)
+    return gb.device_inputs(s["kps"], off, nodes, K=s["K"], Rt=Rt, fixed=fixed, X=X)
 
 
 def bench(eng, d, steps, warmup, iters):
-    nt, nf, f64, i32 = d["n_tracks"], d["nf"], d["f64"], d["i32"]
-    Rt_out, P_out, X_out = torch.empty((nf, 12), **f64), torch.empty((nf, 12), **f64), torch.empty((nt, 3), **f64)
-    err, trace, report = torch.empty(nf * d["stride"], **f64), torch.empty((iters + 1, 2), **f64), torch.empty(8, **i32)
+    nt, nf = d["n_tracks"], d["nf"]
+    Rt_out, P_out, X_out = torch.empty((nf, 12), **F64), torch.empty((nf, 12), **F64), torch.empty((nt, 3), **F64)
+    err, trace, report = torch.empty(nf * d["stride"], **F64), torch.empty((iters + 1, 2), **F64), torch.empty(8, **I32)
     torch.cuda.synchronize()
 
     def call():
         eng.bundle_adjust_dev(d["kp"], nf, d["stride"], nf, d["K"], d["Rt"], d["fixed"], d["off"], d["nodes"], d["tsum"], nt, d["X"],
                               Rt_out, P_out, X_out, trace, report, iters, float("inf"), 1e-3, d_node_err=err)
-    for _ in range(warmup):
-        call()
-    eng.check_status()
-    stream = torch.cuda.Stream()
-    eng.set_stream(stream.cuda_stream)
-    times = []
-    for _ in range(steps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(stream)
-        call()
-        b.record(stream)
-        b.synchronize()
-        times.append(a.elapsed_time(b))
-    eng.set_stream(0)
-    eng.check_status()
-    return np.array(times), report.cpu().tolist(), trace.cpu().numpy()
+    return gb.time_on_stream(eng, call, steps, warmup), report.cpu().tolist(), trace.cpu().numpy()
 
 
 def main():
@@ -94,12 +49,11 @@ def main():
     ap.add_argument("--shapes", default="a,b")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles"))
     args = ap.parse_args()
-    os.makedirs(args.out, exist_ok=True)
     eng = pg.Engine(0)
     for name in args.shapes.split(","):
         rng = np.random.default_rng(0)
         t0 = time.time()
-        d = device_inputs(*make_shape(rng, 64 if name == "a" else 130))
+        d = make_shape(rng, 64 if name == "a" else 130)
         gen_s = time.time() - t0
         ms, report, trace = bench(eng, d, args.steps, args.warmup, args.iters)
         # the same call with max_iters = 0: setup, first linearisation and outputs, so that the per-iteration cost is the rest
@@ -113,9 +67,7 @@ def main():
                    ms_max=float(ms.max()), ms_setup_median=float(np.median(ms0)),
                    ms_per_iteration=float((np.median(ms) - np.median(ms0)) / its), input_generation_s=round(gen_s, 1),
                    target_ms_per_iteration=1.0 if name == "a" else None)
-        print(json.dumps(rec))
-        with open(os.path.join(args.out, "bundle_%s.json" % name), "w") as fh:
-            json.dump(rec, fh, indent=1)
+        gb.write_record(rec, args.out, "bundle")
     eng.close()
 
 

@@ -5,7 +5,6 @@ Tracks are true tracks of synthetic scenes (synth.make_scene's cameras; rounded 
 every refinement step runs.  Writes profiles/triangulate_<shape>.json (or --out DIR).  For the kernel split run it under
 `rocprofv3 --kernel-trace --stats -- python tools/bench_triangulate.py`."""
 import argparse
-import json
 import os
 import sys
 import time
@@ -15,28 +14,15 @@ import torch
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT)
+import geom_bench as gb  # noqa: E402
 import photogrammetry_amd as pg  # noqa: E402
+from geom_bench import F64, I32  # noqa: E402
 from photogrammetry_amd import synth  # noqa: E402
-
-DEV = "cuda:0"
 
 
 def shape_a(rng, nf=64, n_points=8000):
-    s = synth.make_scene(n_points, nf, seed=1, arc_deg=120.0)
-    seen = {}
-    for f, pid in enumerate(s["point_id"]):
-        for k, p in enumerate(pid):
-            seen.setdefault(int(p), []).append((f, k))
-    tracks = []
-    for p in sorted(seen):
-        v = seen[p]
-        L = min(len(v), int(rng.integers(2, 65)))
-        if L < 2:
-            continue
-        a = int(rng.integers(0, len(v) - L + 1))
-        tracks.append(v[a:a + L])
-    kp = [np.stack([k["x"], k["y"]], 1) for k in s["kps"]]
-    return kp, s["P"], tracks
+    s, off, nodes, _ = gb.cut_scene(rng, nf, n_points)
+    return s["kps"], s["P"], (off, nodes)
 
 
 def shape_b(rng, nf=64, n_tracks=1 << 20):
@@ -63,52 +49,17 @@ def shape_b(rng, nf=64, n_tracks=1 << 20):
     return kp, s["P"], (off, nodes)
 
 
-def device_inputs(kp, P, tracks):
-    if isinstance(tracks, tuple):
-        off, nodes = tracks
-    else:
-        off = np.concatenate([[0], np.cumsum([len(t) for t in tracks])])
-        nodes = np.array([n for t in tracks for n in t])
-    nf = len(kp)
-    stride = max(len(k) for k in kp)
-    buf = np.zeros((nf, stride, 4), np.int32)
-    for f, k in enumerate(kp):
-        buf[f, :len(k), :2] = k
-    i32 = dict(dtype=torch.int32, device=DEV)
-    return dict(kp=torch.from_numpy(buf).to(DEV), P=torch.from_numpy(np.ascontiguousarray(P, np.float64)).to(DEV),
-                off=torch.from_numpy(off.astype(np.int32)).to(DEV), nodes=torch.from_numpy(nodes.astype(np.int32)).to(DEV),
-                tsum=torch.tensor([len(off) - 1, len(nodes), 0, 0, 0, 0, 0, 0], **i32), nf=nf, stride=stride, n_tracks=len(off) - 1,
-                n_nodes=len(nodes), lengths=np.diff(off))
-
-
 def bench(eng, d, steps, warmup, iters, min_par, max_e):
     nt = d["n_tracks"]
-    f64 = dict(dtype=torch.float64, device=DEV)
-    xyz, q = torch.empty((nt, 3), **f64), torch.empty((nt, 3), **f64)
-    fl, summ = torch.empty(nt, dtype=torch.int32, device=DEV), torch.empty(8, dtype=torch.int32, device=DEV)
-    err = torch.empty(d["n_nodes"], **f64)
-
+    xyz, q = torch.empty((nt, 3), **F64), torch.empty((nt, 3), **F64)
+    fl, summ = torch.empty(nt, **I32), torch.empty(8, **I32)
+    err = torch.empty(d["n_nodes"], **F64)
     torch.cuda.synchronize()
 
     def call():
         eng.triangulate_tracks_dev(d["kp"], d["nf"], d["stride"], d["nf"], d["P"], d["off"], d["nodes"], d["tsum"], nt, xyz, q, fl,
                                    summ, min_par, max_e, iters, d_node_err=err)
-    for _ in range(warmup):
-        call()
-    eng.check_status()
-    stream = torch.cuda.Stream()     # a stream of its own: handle 0 would mean the context's own stream again
-    eng.set_stream(stream.cuda_stream)
-    times = []
-    for _ in range(steps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(stream)
-        call()
-        b.record(stream)
-        b.synchronize()
-        times.append(a.elapsed_time(b))
-    eng.set_stream(0)
-    eng.check_status()
-    return np.array(times), summ.cpu().tolist()
+    return gb.time_on_stream(eng, call, steps, warmup), summ.cpu().tolist()
 
 
 def main():
@@ -119,13 +70,12 @@ def main():
     ap.add_argument("--shapes", default="a,b")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles"))
     args = ap.parse_args()
-    os.makedirs(args.out, exist_ok=True)
     rng = np.random.default_rng(0)
     eng = pg.Engine(0)
     for name in args.shapes.split(","):
         t0 = time.time()
-        kp, P, tracks = (shape_a if name == "a" else shape_b)(rng)
-        d = device_inputs(kp, P, tracks)
+        kp, P, (off, nodes) = (shape_a if name == "a" else shape_b)(rng)
+        d = gb.device_inputs(kp, off, nodes, P=P)
         gen_s = time.time() - t0
         ms, summary = bench(eng, d, args.steps, args.warmup, args.iters, 1.0, 2.0)
         lens = d["lengths"]
@@ -135,9 +85,7 @@ def main():
                    refine_iters=args.iters, min_parallax_deg=1.0, max_reproj_px=2.0, steps=args.steps,
                    ms_median=float(np.median(ms)), ms_min=float(ms.min()), ms_max=float(ms.max()), summary=summary,
                    input_generation_s=round(gen_s, 1), target_ms=0.05 if name == "a" else 1.0)
-        print(json.dumps(rec))
-        with open(os.path.join(args.out, "triangulate_%s.json" % name), "w") as fh:
-            json.dump(rec, fh, indent=1)
+        gb.write_record(rec, args.out, "triangulate")
     eng.close()
 
 
