@@ -1,6 +1,6 @@
-"""Synthetic inputs for tests and bench.py: corner-rich RGBA64 frames and
-descriptor sets.  Pure data generation on the host, seeded; no reference code or data.  device_tracks alone uploads what
-it made, and imports torch when called."""
+"""Synthetic inputs for tests, tools and bench.py: corner-rich RGBA64 frames, descriptor sets, the two-view scene
+with its fundamental matrix, and multi-view scenes with tracks.  Pure data generation on the host, seeded; no reference code
+or data.  device_tracks alone uploads what it made, and imports torch when called."""
 import numpy as np
 
 
@@ -71,6 +71,34 @@ def true_match_descriptors(n, words, seed, flip=0.15):
     perm = rng.permutation(n)
     d2 = np.packbits(bits ^ noise, axis=1).view(np.uint32)[perm]
     return d1, np.ascontiguousarray(d2), perm
+
+
+def rot_y(a):
+    return np.array([[np.cos(a), 0, np.sin(a)], [0, 1, 0], [-np.sin(a), 0, np.cos(a)]])
+
+
+def skew(t):
+    return np.array([[0, -t[2], t[1]], [t[2], 0, -t[0]], [-t[1], t[0], 0]])
+
+
+def fundamental_from_pose(K, R, t):
+    """F with h_a^T F h_b = 0 (include/pgx.h) for x_a ~ K X, x_b ~ K (R X + t); unit Frobenius norm, float32 [3][3]."""
+    Ki = np.linalg.inv(K)
+    F = (Ki.T @ skew(t) @ R @ Ki).T
+    return (F / np.linalg.norm(F)).astype(np.float32)
+
+
+def two_view_pixels(rng, n, K, R, t, W=3000, H=4000):
+    """The two-view scene of the matcher and pose tests: n points drawn from rng in [-3, 3] x [-4, 4] x [4, 9], seen as
+    x1 ~ K X and x2 ~ K (R X + t); kept are those whose rounded pixels are inside the W x H window in both views.
+    -> (p1, p2) int32 [kept][2], in the order drawn"""
+    X = np.stack([rng.uniform(-3, 3, n), rng.uniform(-4, 4, n), rng.uniform(4, 9, n)], 1)
+    x1 = (K @ X.T).T
+    x2 = (K @ (R @ X.T + t[:, None])).T
+    p1 = np.rint(x1[:, :2] / x1[:, 2:3]).astype(np.int32)
+    p2 = np.rint(x2[:, :2] / x2[:, 2:3]).astype(np.int32)
+    ok = (p1 >= 0).all(1) & (p2 >= 0).all(1) & (p1[:, 0] < W) & (p2[:, 0] < W) & (p1[:, 1] < H) & (p2[:, 1] < H)
+    return p1[ok], p2[ok]
 
 
 def look_at_camera(centre, target, f=1200.0, W=1920, H=1080):

@@ -1,11 +1,13 @@
 """What the GPU tests of the track graph and of its three consumers (triangulation, bundle adjustment, registration) share:
 tensor kinds, bit comparison, the device problem, the run wrappers of bundle adjustment and registration with their padded
-inputs and sentinel-filled outputs, the yardstick comparisons that more than one module uses, and the random and constructed
-match lists of the track-graph tests.  A plain helper module: no test module imports another."""
+inputs and sentinel-filled outputs, the yardstick comparisons that more than one module uses, the random and constructed
+match lists of the track-graph tests (the CPU ones included) and the runners of pgx_tracks_dev and pgx_tracks_split_dev.
+A plain helper module: no test module imports another."""
 import numpy as np
 import torch
 
 import triangulate_ref
+from tracks_split_ref import KEYS as TRACK_KEYS
 from photogrammetry_amd import synth
 
 DEV = "cuda:0"
@@ -149,14 +151,16 @@ def tri_check_against_yardstick(got, kps, P, min_par, max_e, iters, stop_band=Fa
     return e, excluded
 
 
-def random_case(seed, F, stride, dmax=60):
+def random_case(seed, F, stride, dmax=60, p_pair=0.6, k2_lo=0):
+    """Random match lists: every ordered pair with probability p_pair, k2 from k2_lo (-1: the rejected rows of NN lists), a
+    tenth of the rows (0, 0, int.MaxValue) -> (counts [F], pair list, matches [M][stride][3])"""
     rng = np.random.default_rng(seed)
     counts = rng.integers(0, stride + 1, F).astype(np.int32)
     counts[rng.integers(0, F)] = 0
-    pl = [(a, b) for a in range(F) for b in range(F) if a != b and rng.random() < 0.6]
+    pl = [(a, b) for a in range(F) for b in range(F) if a != b and rng.random() < p_pair]
     m = np.zeros((len(pl), stride, 3), dtype=np.int32)
     m[..., 0] = rng.integers(0, stride, m.shape[:2])
-    m[..., 1] = rng.integers(0, stride, m.shape[:2])
+    m[..., 1] = rng.integers(k2_lo, stride, m.shape[:2])
     m[..., 2] = rng.integers(0, dmax, m.shape[:2])
     m[rng.random(m.shape[:2]) < 0.1] = [0, 0, INT_MAX]
     return counts, pl, m
@@ -182,3 +186,46 @@ def constructed_job(F, K, seed, junk=0.3):
         m[p] = m[p][order]
     counts = np.full(F, K, dtype=np.int32)
     return counts, pl, m, perm, vis
+
+
+def as_lists(offsets, nodes):
+    return [[(int(f), int(k)) for f, k in nodes[offsets[t]:offsets[t + 1]]] for t in range(len(offsets) - 1)]
+
+
+def summary_dict(s):
+    """the 8 summary slots of pgx_tracks_dev as the oracle's dict"""
+    assert s[7] == 0
+    return dict(zip(TRACK_KEYS, s))
+
+
+def tracks_buffers(counts, pair_list, matches, stride, frame_ids, nf):
+    """counts [F] by slot, pair_list [M][2] slots, matches [M][stride][3], frame_ids [F] or None
+    -> (d_matches, d_counts, d_pairs, d_frame_ids, (track_of, offsets, nodes) filled with 77)"""
+    M = len(pair_list)
+    d_m = torch.from_numpy(np.ascontiguousarray(matches, dtype=np.int32).reshape(max(M, 1), stride, 3)).to(DEV)
+    d_c = torch.tensor(np.asarray(counts, dtype=np.int32), **I32)
+    d_pl = torch.tensor(np.asarray(pair_list, dtype=np.int32).reshape(-1, 2) if M else np.zeros((1, 2), np.int32), **I32)
+    d_ids = None if frame_ids is None else torch.tensor(np.asarray(frame_ids, dtype=np.int32), **I32)
+    outs = (torch.full((nf, stride), 77, **I32), torch.full((nf * stride + 1,), 77, **I32), torch.full((nf * stride, 2), 77, **I32))
+    return d_m, d_c, d_pl, d_ids, outs
+
+
+def run_tracks_split(engine, counts, pair_list, matches, stride, max_dist, gates, min_len=2, frame_ids=None, n_frames=None):
+    """pgx_tracks_split_dev, or pgx_tracks_dev with gates = None -> (offsets, nodes, track_of, summary list of 16 or 8)"""
+    nf = len(counts) if n_frames is None else n_frames
+    d_m, d_c, d_pl, d_ids, (track_of, offsets, nodes) = tracks_buffers(counts, pair_list, matches, stride, frame_ids, nf)
+    summary = torch.full((8 if gates is None else 16,), 77, **I32)
+    torch.cuda.synchronize()
+    if gates is None:
+        engine.tracks_dev(d_m, d_c, d_pl, len(pair_list), len(counts), stride, nf, max_dist, min_len, track_of, offsets, nodes,
+                          summary, d_frame_ids=d_ids)
+    else:
+        engine.tracks_split_dev(d_m, d_c, d_pl, len(pair_list), len(counts), stride, nf, max_dist, gates, min_len, track_of,
+                                offsets, nodes, summary, d_frame_ids=d_ids)
+    engine.check_status()
+    s = summary.cpu().tolist()
+    return offsets.cpu().numpy()[:s[0] + 1], nodes.cpu().numpy()[:s[1]], track_of.cpu().numpy(), s
+
+
+def run_tracks(engine, counts, pair_list, matches, stride, max_dist, min_len=2, frame_ids=None, n_frames=None):
+    return run_tracks_split(engine, counts, pair_list, matches, stride, max_dist, None, min_len, frame_ids, n_frames)

@@ -1,5 +1,5 @@
-"""Helpers shared by tests/test_pose_ref.py (CPU) and tests/test_gpu_pose_limits.py (GPU): the two-view scene with exact entry
-counts, the per-sample stream seed, the conditioning of a sample's 8-point system, and the inlier-count interval.
+"""Helpers shared by tests/test_pose_ref.py (CPU) and the GPU tests of RANSAC and pose (tests/test_gpu_pose.py,
+tests/test_gpu_pose_limits.py, tests/test_gpu_chain.py): the two-view scene with exact entry counts, the per-sample stream seed, the conditioning of a sample's 8-point system, and the inlier-count interval.
 
 The interval.  k_fund_score's inlier test is `res <= threshold` with res = sum_ij F_ij ha_i hb_j, ha = (x1, y1, 1),
 hb = (x2, y2, 1): nine products and eight additions of which the ones with a homogeneous 1 are exact, i.e. 12 float32
@@ -10,6 +10,7 @@ and the sum is good to 2^-50 mag).  So  #(res <= thr - g)  <=  count  <=  #(res 
 import numpy as np
 
 from oracle import pose_np
+from photogrammetry_amd import synth
 
 MASK = (1 << 64) - 1
 STREAM_MUL = 0xD1B54A32D192ED03
@@ -21,23 +22,17 @@ def stream_seed(seed, m, s):
     return (seed ^ ((m & 0xFFFFFFFF) << 32) ^ (((s & 0xFFFFFFFF) * STREAM_MUL) & MASK)) & MASK
 
 
-def two_views(n_true, n_out, seed, dup=1):
-    """Exactly n_true true correspondences (rounded pixels) of a synthetic scene seen by two cameras with the reference's K,
-    then n_out random wrong ones -> (p1, p2, R, t) with p1, p2 int32 [n_true + n_out][2].  dup > 1 repeats every entry."""
+def two_views(n_true, n_out, seed, dup=1, exact=True):
+    """True correspondences (rounded pixels) of synth.two_view_pixels' scene seen by two cameras with the reference's K, then
+    n_out random wrong ones -> (p1, p2, R, t) with p1, p2 int32 [true + n_out][2].  exact: 2 n_true + 64 points are drawn and
+    exactly n_true of those seen in both views kept; otherwise n_true are drawn and what is seen is kept.  dup > 1 repeats
+    every entry."""
     rng = np.random.default_rng(seed)
-    K = pose_np.K.astype(np.float64)
-    a = 0.07
-    R = np.array([[np.cos(a), 0, np.sin(a)], [0, 1, 0], [-np.sin(a), 0, np.cos(a)]])
-    t = np.array([0.6, 0.05, 0.1])
-    n_gen = 2 * n_true + 64
-    X = np.stack([rng.uniform(-3, 3, n_gen), rng.uniform(-4, 4, n_gen), rng.uniform(4, 9, n_gen)], 1)
-    x1 = (K @ X.T).T
-    x2 = (K @ (R @ X.T + t[:, None])).T
-    p1 = np.rint(x1[:, :2] / x1[:, 2:3]).astype(np.int32)
-    p2 = np.rint(x2[:, :2] / x2[:, 2:3]).astype(np.int32)
-    ok = (p1 >= 0).all(1) & (p2 >= 0).all(1) & (p1[:, 0] < 3000) & (p2[:, 0] < 3000) & (p1[:, 1] < 4000) & (p2[:, 1] < 4000)
-    p1, p2 = p1[ok][:n_true], p2[ok][:n_true]
-    assert len(p1) == n_true
+    R, t = synth.rot_y(0.07), np.array([0.6, 0.05, 0.1])
+    p1, p2 = synth.two_view_pixels(rng, 2 * n_true + 64 if exact else n_true, pose_np.K.astype(np.float64), R, t)
+    if exact:
+        p1, p2 = p1[:n_true], p2[:n_true]
+        assert len(p1) == n_true
     o1 = np.stack([rng.integers(0, 3000, n_out), rng.integers(0, 4000, n_out)], 1).astype(np.int32)
     o2 = np.stack([rng.integers(0, 3000, n_out), rng.integers(0, 4000, n_out)], 1).astype(np.int32)
     p1, p2 = np.concatenate([p1, o1]), np.concatenate([p2, o2])

@@ -6,12 +6,12 @@ import numpy as np
 import pytest
 import torch
 
+from match_gpu import DEV, oracle_detect, pairs_equal, run_match
 from oracle import cref
 from photogrammetry_amd import synth
 import photogrammetry_amd as pg
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 
 
 @pytest.fixture(scope="module")
@@ -20,14 +20,6 @@ def engine():
     e = pg.Engine(0)
     yield e
     e.close()
-
-
-def _oracle_detect(frame, dmap, pairs, T, radius, cap):
-    src = cref.apply_distortion(frame, dmap) if dmap is not None else frame
-    g = cref.gray(src)
-    raw = cref.detect(g, T)
-    kept = raw[cref.nms(raw, radius)][:cap]
-    return kept, cref.brief(g, np.stack([kept["x"], kept["y"]], 1), pairs), len(raw)
 
 
 @pytest.mark.parametrize("F,radius,with_map", [(3, 9, True), (8, 16, False), (11, 20, True)])
@@ -55,7 +47,7 @@ def test_detect_batch_matches_oracle(engine, F, radius, with_map):
     counts, nraw = d_counts.cpu().numpy(), d_nraw.cpu().numpy()
     assert counts[F - 1] == 0 and nraw[F - 1] == 0
     for f in range(F):
-        kept, edesc, n_raw = _oracle_detect(frames[f], dmap, pairs, T, radius, CAP)
+        kept, edesc, n_raw = oracle_detect(frames[f], dmap, pairs, T, radius, CAP)
         assert nraw[f] == n_raw and counts[f] == len(kept), f
         n = len(kept)
         assert (kp[f, :n, 0] == kept["x"]).all() and (kp[f, :n, 1] == kept["y"]).all()
@@ -65,28 +57,13 @@ def test_detect_batch_matches_oracle(engine, F, radius, with_map):
     engine.set_dewarp_map(None)
 
 
-def _match_batch(engine, descs, counts, pairlist, stride, max_count=None):
-    F = len(descs)
-    d = np.zeros((F, stride, 8), dtype=np.uint32)
-    for f in range(F):
-        d[f, :len(descs[f])] = descs[f]
-    d_desc = torch.from_numpy(d.view(np.int32)).to(DEV)
-    d_counts = torch.tensor(counts, dtype=torch.int32, device=DEV)
-    d_pl = torch.tensor(pairlist, dtype=torch.int32, device=DEV)
-    d_out = torch.full((len(pairlist), stride, 3), -7, dtype=torch.int32, device=DEV)
-    torch.cuda.synchronize()   # see pgx.h: "_dev" buffers must be ready on, or ordered against, the context's stream
-    engine.match_batch_dev(d_desc, d_counts, stride, 8, d_pl, len(pairlist), d_out, max_count=max_count)
-    _match_batch.keepalive = (d_desc, d_counts, d_pl)   # the launch is asynchronous: inputs must outlive it
-    return d_out
-
-
 def test_match_batch_ragged_counts_and_order(engine):
     rng = np.random.default_rng(5)
     sizes = [1500, 40, 2300, 1024, 1025, 0, 700]
     descs = [rng.integers(0, 2**32, (n, 8), dtype=np.uint32) for n in sizes]
     descs[3] = descs[0][:1024].copy()                      # frame 3 is a prefix of frame 0: exact matches exist
     pl = [(0, 2), (2, 0), (1, 4), (4, 1), (3, 0), (0, 3), (5, 6), (6, 6), (1, 1)]
-    d_out = _match_batch(engine, descs, sizes, pl, 2304)
+    d_out = run_match(engine, descs, pl, 2304, wait=False)
     engine.check_status()          # synchronises the engine's stream; results are not defined before it
     out = d_out.cpu().numpy()
     for m, (a, b) in enumerate(pl):
@@ -94,7 +71,7 @@ def test_match_batch_ragged_counts_and_order(engine):
             continue
         exp = cref.match_sorted(descs[a], descs[b])
         got = out[m][:sizes[a]]
-        assert (got[:, 0] == exp["k1"]).all() and (got[:, 1] == exp["k2"]).all() and (got[:, 2] == exp["dist"]).all(), (a, b)
+        assert pairs_equal(got, exp), (a, b)
 
 
 def test_match_batch_host_buffers(engine):
@@ -137,7 +114,7 @@ def test_match_batch_host_buffers_other_descriptor_lengths(engine, words, mask):
 def test_match_batch_empty_second_set_raises(engine):
     rng = np.random.default_rng(6)
     descs = [rng.integers(0, 2**32, (30, 8), dtype=np.uint32), np.zeros((0, 8), np.uint32)]
-    out = _match_batch(engine, descs, [30, 0], [(0, 1), (0, 0)], 64)
+    out = run_match(engine, descs, [(0, 1), (0, 0)], 64, wait=False)
     with pytest.raises(pg.ArgumentOutOfRangeException):     # KeypointMatching.cs:61
         engine.check_status()
     o = out.cpu().numpy()
@@ -149,13 +126,13 @@ def test_match_batch_empty_second_set_raises(engine):
 def test_match_batch_max_count_truncates(engine):
     rng = np.random.default_rng(7)
     descs = [rng.integers(0, 2**32, (900, 8), dtype=np.uint32), rng.integers(0, 2**32, (1300, 8), dtype=np.uint32)]
-    d_out = _match_batch(engine, descs, [900, 1300], [(0, 1), (1, 0)], 1536, max_count=512)
+    d_out = run_match(engine, descs, [(0, 1), (1, 0)], 1536, max_count=512, wait=False)
     engine.check_status()
     out = d_out.cpu().numpy()
     for m, (a, b) in enumerate([(0, 1), (1, 0)]):
         exp = cref.match_sorted(descs[a][:512], descs[b][:512])   # lists are cut to their first max_count entries
         got = out[m][:512]
-        assert (got[:, 0] == exp["k1"]).all() and (got[:, 1] == exp["k2"]).all() and (got[:, 2] == exp["dist"]).all()
+        assert pairs_equal(got, exp)
 
 
 def test_match_batch_more_pairs_than_one_chunk(engine):
@@ -172,14 +149,14 @@ def test_match_batch_more_pairs_than_one_chunk(engine):
     pl = [(a, b) for a in range(F) for b in range(a + 1, F)]
     assert len(pl) == 300
     engine.set_match_chunk(128)
-    d_out = _match_batch(engine, descs, sizes, pl, 400)
+    d_out = run_match(engine, descs, pl, 400, wait=False)
     engine.check_status()
     engine.set_match_chunk(2048)
     out = d_out.cpu().numpy()
     for m, (a, b) in enumerate(pl):
         exp = cref.match_sorted(descs[a], descs[b])
         got = out[m][:sizes[a]]
-        assert (got[:, 0] == exp["k1"]).all() and (got[:, 1] == exp["k2"]).all() and (got[:, 2] == exp["dist"]).all(), (a, b)
+        assert pairs_equal(got, exp), (a, b)
 
 
 def test_profile_hooks_and_stats(engine):
@@ -187,7 +164,7 @@ def test_profile_hooks_and_stats(engine):
     descs = [rng.integers(0, 2**32, (3000, 8), dtype=np.uint32) for _ in range(2)]   # > PGX_TAIL_MAX: a wide round runs
     engine.profile_reset()
     engine.profile_enable(True)
-    _match_batch(engine, descs, [3000, 3000], [(0, 1)], 3072)
+    run_match(engine, descs, [(0, 1)], 3072, wait=False)
     engine.check_status()
     engine.profile_enable(False)
     n, ms = engine.profile_get("ham_argmin")
@@ -229,7 +206,7 @@ def test_detect_full_size_frames_vs_oracle(engine, radius):
     desc = d_desc.cpu().numpy().view(np.uint32)
     counts, nraw = d_counts.cpu().numpy(), d_nraw.cpu().numpy()
     for f in range(F):
-        kept, edesc, n_raw = _oracle_detect(frames[f], dmap, pairs, T, radius, CAP)
+        kept, edesc, n_raw = oracle_detect(frames[f], dmap, pairs, T, radius, CAP)
         assert n_raw > 30000 and nraw[f] == n_raw
         assert counts[f] == len(kept), (f, counts[f], len(kept))
         n = len(kept)
@@ -259,7 +236,7 @@ def test_detect_4k_frame_vs_oracle(engine):
     torch.cuda.synchronize()
     engine.detect_batch_dev(d_frames, 1, W, H, d_kp, d_desc, d_counts, d_nraw, CAP)
     engine.check_status()
-    kept, edesc, n_raw = _oracle_detect(frame, dmap, pairs, T, radius, CAP)
+    kept, edesc, n_raw = oracle_detect(frame, dmap, pairs, T, radius, CAP)
     n = len(kept)
     assert n > 8192 and int(d_nraw[0]) == n_raw and int(d_counts[0]) == n
     kp = d_kp.cpu().numpy()[0]
@@ -290,7 +267,7 @@ def test_detect_dense_noise_frame_vs_oracle(engine, radius):
     torch.cuda.synchronize()
     engine.detect_batch_dev(d_frames, 1, W, H, d_kp, d_desc, d_counts, d_nraw, CAP)
     engine.check_status()
-    kept, edesc, n_raw = _oracle_detect(frame, None, pairs, T, radius, CAP)
+    kept, edesc, n_raw = oracle_detect(frame, None, pairs, T, radius, CAP)
     n = len(kept)
     assert n_raw > 20000 and int(d_nraw[0]) == n_raw and int(d_counts[0]) == n
     kp = d_kp.cpu().numpy()[0]
@@ -331,13 +308,13 @@ def test_two_contexts_in_flight_are_independent():
         counts = o["counts"].cpu().numpy()
         desc = o["desc"].cpu().numpy().view(np.uint32)
         res = o["out"].cpu().numpy()
-        exp = [_oracle_detect(frames[f], None, c["pairs"], T, c["radius"], CAP) for f in range(4)]
+        exp = [oracle_detect(frames[f], None, c["pairs"], T, c["radius"], CAP) for f in range(4)]
         for f in range(4):
             assert counts[f] == len(exp[f][0]) and (desc[f, :counts[f]] == exp[f][1]).all()
         for m, (a, b) in enumerate([(0, 1), (2, 3), (3, 0)]):
             em = cref.match_sorted(exp[a][1], exp[b][1])
             got = res[m][:counts[a]]
-            assert (got[:, 0] == em["k1"]).all() and (got[:, 1] == em["k2"]).all() and (got[:, 2] == em["dist"]).all()
+            assert pairs_equal(got, em)
     for e in engs:
         e.close()
 

@@ -23,6 +23,7 @@ import torch
 from oracle import cref, pose_np
 from photogrammetry_amd import synth, dist as pdist
 import photogrammetry_amd as pg
+from pose_ref import normed, system
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -35,11 +36,6 @@ def _frames():
     fr = [synth.shift_frame(base, 5 * i, 2 * i) for i in range(F - 1)]
     fr.append(synth.shift_frame(synth.make_frame(W, H, seed=4243, n_shapes=150), 3, 1))   # the sparse one
     return np.stack(fr)
-
-
-def _normed(Fm):
-    Fm = np.asarray(Fm, dtype=np.float64).reshape(3, 3)
-    return Fm / np.linalg.norm(Fm)
 
 
 def test_configs4_chain_every_stage_against_its_oracle():
@@ -119,11 +115,11 @@ def test_configs4_chain_every_stage_against_its_oracle():
             idx = pose_np.sample_indices(SEED, m, int(bs[m]), PPS, n)
             if tail[m]:
                 assert max(idx) < n       # positions of the whole list: tail entries can be drawn
-            A = _system(p1[idx], p2[idx])
+            A = system(p1[idx], p2[idx])
             sv = np.linalg.svd(A, compute_uv=False)
             if sv[-2] > 50 * sv[-1] and sv[-2] > 1e-6 * sv[0]:     # a clear null vector: the two solvers must agree on it
                 Fs = pose_np.estimate_fundamental(p1[idx], p2[idx])
-                assert np.abs(_normed(Fg[m]) - _normed(Fs)).max() < 2e-3, m
+                assert np.abs(normed(Fg[m]) - normed(Fs)).max() < 2e-3, m
                 checked_F += 1
             assert abs(int(pose_np.score(Fg[m].reshape(3, 3), p1, p2, THR).sum()) - int(cnt[m])) <= tol, m
         # single samples on the real lists (n_samples = 1: sample 0 of every image pair is the winner by definition), so that
@@ -137,14 +133,14 @@ def test_configs4_chain_every_stage_against_its_oracle():
             for m in [0, 5, 12, pl.index((7, 0)), pl.index((7, 3))]:
                 p1, p2 = corr[m]
                 idx = pose_np.sample_indices(seed, m, 0, PPS, len(p1))
-                sv = np.linalg.svd(_system(p1[idx], p2[idx]), compute_uv=False)
+                sv = np.linalg.svd(system(p1[idx], p2[idx]), compute_uv=False)
                 if sv[-2] > 50 * sv[-1] and sv[-2] > 1e-6 * sv[0]:
                     Fs = pose_np.estimate_fundamental(p1[idx], p2[idx])
                     co1 = int(pose_np.score(Fs, p1, p2, THR).sum())
                     if int(c1[m]) < 0:      # no sample with an inlier: bestF stays null (CameraPoseEstimation.cs:79-89), -1 here
                         assert co1 <= max(3, len(p1) // 100), (seed, m, co1)
                         continue
-                    assert np.abs(_normed(F1[m]) - _normed(Fs)).max() < 2e-3, (seed, m)
+                    assert np.abs(normed(F1[m]) - normed(Fs)).max() < 2e-3, (seed, m)
                     assert abs(co1 - int(c1[m])) <= max(3, len(p1) // 100), (seed, m)
                     checked_F += 1
         assert checked_F >= 8
@@ -174,11 +170,3 @@ def test_configs4_chain_every_stage_against_its_oracle():
     finally:
         eng.set_stream(0)
         eng.close()
-
-
-def _system(p1, p2):
-    """The 8-point system of pose_np.estimate_fundamental (centred coordinates), for its conditioning only."""
-    c1, c2 = p1.astype(np.float64).mean(0), p2.astype(np.float64).mean(0)
-    x1, y1 = p1[:, 0] - c1[0], p1[:, 1] - c1[1]
-    x2, y2 = p2[:, 0] - c2[0], p2[:, 1] - c2[1]
-    return np.stack([x1 * x2, x1 * y2, x1, y1 * x2, y1 * y2, y1, x2, y2, np.ones_like(x1)], 1)

@@ -9,13 +9,15 @@ import numpy as np
 import pytest
 import torch
 
-from guided_ref import NONE, admissible, ref_guided, ref_select
+from geom_gpu import run_tracks
+from guided_ref import admissible, ref_guided
+from knn_ref import NONE, ref_select
+from match_gpu import DEV, run_knn, run_nn, upload
 from oracle import pose_np, tracks_np
 import photogrammetry_amd as pg
 from photogrammetry_amd import synth
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 ENGINE = None
 
 
@@ -33,33 +35,13 @@ K = pose_np.K.astype(np.float64)
 F_AXIS = np.array([[0, 0, 0], [0, 0, -1], [0, 1, 0]], dtype=np.float32)   # the line of row (x, y) is v = y
 
 
-def skew(t):
-    return np.array([[0, -t[2], t[1]], [t[2], 0, -t[0]], [-t[1], t[0], 0]])
-
-
-def true_F(R, t):
-    """F with h_a^T F h_b = 0 for x_a ~ K X, x_b ~ K (R X + t); unit Frobenius norm, float32."""
-    Ki = np.linalg.inv(K)
-    F = (Ki.T @ skew(t) @ R @ Ki).T
-    return (F / np.linalg.norm(F)).astype(np.float32)
-
-
-def rot_y(a):
-    return np.array([[np.cos(a), 0, np.sin(a)], [0, 1, 0], [-np.sin(a), 0, np.cos(a)]])
-
-
 def two_views(n, n_out, seed, words, flip=0.12, a=0.07, t=(0.6, 0.05, 0.1)):
-    """As test_gpu_pose._two_views: n true correspondences of one scene and n_out distractors per frame.  Column j < n_true of
-    frame b is the view of row perm[j] of frame a.  -> (da, kpa, db, kpb, F, truth) with truth[j] = true row of column j or -1."""
+    """The pose tests' scene (synth.two_view_pixels) with descriptors: n points drawn, those seen in both views kept, and n_out
+    distractors per frame.  Column j < n_true of frame b is the view of row perm[j] of frame a.
+    -> (da, kpa, db, kpb, F, truth) with truth[j] = true row of column j or -1."""
     rng = np.random.default_rng(seed)
-    X = np.stack([rng.uniform(-3, 3, n), rng.uniform(-4, 4, n), rng.uniform(4, 9, n)], 1)
-    R, tt = rot_y(a), np.asarray(t, dtype=np.float64)
-    x1 = (K @ X.T).T
-    x2 = (K @ (R @ X.T + tt[:, None])).T
-    p1 = np.rint(x1[:, :2] / x1[:, 2:3]).astype(np.int32)
-    p2 = np.rint(x2[:, :2] / x2[:, 2:3]).astype(np.int32)
-    ok = (p1 >= 0).all(1) & (p2 >= 0).all(1) & (p1[:, 0] < 3000) & (p2[:, 0] < 3000) & (p1[:, 1] < 4000) & (p2[:, 1] < 4000)
-    p1, p2 = p1[ok], p2[ok]
+    R, tt = synth.rot_y(a), np.asarray(t, dtype=np.float64)
+    p1, p2 = synth.two_view_pixels(rng, n, K, R, tt)
     nt = len(p1)
     d1, d2, perm = synth.true_match_descriptors(nt, words, seed + 1000, flip=flip)
     pts = lambda m: np.stack([rng.integers(0, 3000, m), rng.integers(0, 4000, m)], 1).astype(np.int32)   # noqa: E731
@@ -67,59 +49,18 @@ def two_views(n, n_out, seed, words, flip=0.12, a=0.07, t=(0.6, 0.05, 0.1)):
     kpa, da = np.concatenate([p1, pts(n_out)]), np.concatenate([d1, rnd(n_out)])
     kpb, db = np.concatenate([p2[perm], pts(n_out)]), np.concatenate([d2, rnd(n_out)])
     truth = np.concatenate([perm, np.full(n_out, -1)]).astype(np.int64)
-    return da, kpa, db, kpb, true_F(R, tt), truth
-
-
-def upload(frames, stride, words):
-    """frames: [(desc [n][words], kp [n][2])] -> (d_desc, d_kp, d_counts, counts)."""
-    Fn = len(frames)
-    desc = np.zeros((Fn, stride, words), dtype=np.uint32)
-    kp = np.zeros((Fn, stride), dtype=pg.KEYPOINT_DTYPE)
-    for f, (d, p) in enumerate(frames):
-        desc[f, :len(d)] = d
-        kp["x"][f, :len(p)] = p[:, 0]
-        kp["y"][f, :len(p)] = p[:, 1]
-    counts = np.array([len(d) for d, _ in frames], dtype=np.int32)
-    t = lambda a: torch.from_numpy(a).to(DEV)   # noqa: E731
-    return t(desc.view(np.int32)), t(kp.view(np.int32).reshape(Fn, stride, 4)), t(counts), counts
-
-
-def run_knn(dev, stride, words, pl, Fs, band, k, col, sentinel=77, max_count=None):
-    d_desc, d_kp, d_counts, _ = dev
-    M = len(pl)
-    i32 = dict(dtype=torch.int32, device=DEV)
-    d_pl = torch.tensor(np.asarray(pl, dtype=np.int32).reshape(-1, 2), device=DEV)
-    d_F = torch.from_numpy(np.stack([np.asarray(f, dtype=np.float32).reshape(9) for f in Fs])).to(DEV)
-    idx = torch.full((M, stride, k), sentinel, **i32)
-    dist = torch.full((M, stride, k), sentinel, **i32)
-    cnn = torch.full((M, stride), sentinel, **i32) if col else None
-    torch.cuda.synchronize()
-    ENGINE.knn_guided_batch_dev(d_desc, d_kp, d_counts, stride, words, d_pl, M, d_F, band, k, idx, dist, cnn, max_count=max_count)
-    ENGINE.check_status()
-    return idx.cpu().numpy(), dist.cpu().numpy(), (cnn.cpu().numpy() if col else None)
-
-
-def run_match(dev, stride, words, pl, Fs, band, max_dist, ratio, cross, sentinel=77):
-    d_desc, d_kp, d_counts, _ = dev
-    M = len(pl)
-    d_pl = torch.tensor(np.asarray(pl, dtype=np.int32).reshape(-1, 2), device=DEV)
-    d_F = torch.from_numpy(np.stack([np.asarray(f, dtype=np.float32).reshape(9) for f in Fs])).to(DEV)
-    out = torch.full((M, stride, 3), sentinel, dtype=torch.int32, device=DEV)
-    torch.cuda.synchronize()
-    ENGINE.match_guided_batch_dev(d_desc, d_kp, d_counts, stride, words, d_pl, M, d_F, band, out, max_dist, ratio, cross)
-    ENGINE.check_status()
-    return out.cpu().numpy()
+    return da, kpa, db, kpb, synth.fundamental_from_pose(K, R, tt), truth
 
 
 def check_knn(frames, stride, words, pl, Fs, band, refs=None):
     """Every k and column-side combination of one batch against the yardstick; returns the refs."""
-    dev = upload(frames, stride, words)
+    dev = upload(stride, words, *zip(*frames))
     counts = dev[3]
     if refs is None:
         refs = [ref_guided(frames[a][0], frames[b][0], frames[a][1], frames[b][1], Fs[m], band) for m, (a, b) in enumerate(pl)]
     for k in (1, 2):
         for col in (False, True):
-            idx, dist, cnn = run_knn(dev, stride, words, pl, Fs, band, k, col)
+            idx, dist, cnn = run_knn(ENGINE, dev, stride, words, pl, k, col, guide=(Fs, band))
             for m, (a, b) in enumerate(pl):
                 r_idx, r_dist, r_col = refs[m]
                 n1, n2 = counts[a], counts[b]
@@ -164,20 +105,14 @@ def test_huge_band_equals_knn(words):
     for m, (a, b) in enumerate(pl):   # well conditioned: every row has a line
         assert admissible(frames[a][1], frames[b][1], Fs[m], 1e30).all()
     stride = 4096
-    dev = upload(frames, stride, words)
-    d_pl = torch.tensor(pl, dtype=torch.int32, device=DEV)
-    i32 = dict(dtype=torch.int32, device=DEV)
-    idx, dist, cnn = (torch.full((3, stride, 2), 5, **i32), torch.full((3, stride, 2), 5, **i32), torch.full((3, stride), 5, **i32))
-    ENGINE.knn_batch_dev(dev[0], dev[2], stride, words, d_pl, 3, 2, idx, dist, cnn)
-    ENGINE.check_status()
-    g = run_knn(dev, stride, words, pl, Fs, 1e30, 2, True, sentinel=5)
-    assert (g[0] == idx.cpu().numpy()).all() and (g[1] == dist.cpu().numpy()).all() and (g[2] == cnn.cpu().numpy()).all()
+    dev = upload(stride, words, *zip(*frames))
+    u = run_knn(ENGINE, dev, stride, words, pl, 2, True, sentinel=5)
+    g = run_knn(ENGINE, dev, stride, words, pl, 2, True, sentinel=5, guide=(Fs, 1e30))
+    assert (g[0] == u[0]).all() and (g[1] == u[1]).all() and (g[2] == u[2]).all()
     for ratio, cross in ((0.8, True), (0.0, False)):
-        nn = torch.full((3, stride, 3), 5, **i32)
-        ENGINE.match_nn_batch_dev(dev[0], dev[2], stride, words, d_pl, 3, nn, 32 * words // 3, ratio, cross)
-        ENGINE.check_status()
-        gm = run_match(dev, stride, words, pl, Fs, 1e30, 32 * words // 3, ratio, cross, sentinel=5)
-        assert (gm == nn.cpu().numpy()).all(), (ratio, cross)
+        nn = run_nn(ENGINE, dev, stride, words, pl, 32 * words // 3, ratio, cross, sentinel=5)
+        gm = run_nn(ENGINE, dev, stride, words, pl, 32 * words // 3, ratio, cross, sentinel=5, guide=(Fs, 1e30))
+        assert (gm == nn).all(), (ratio, cross)
 
 
 # ---- 3. boundary cases --------------------------------------------------------------------------------------------------------
@@ -243,8 +178,8 @@ def test_shapes_padded_repeated_swapped_untouched(words):
     refs = check_knn(frames, stride, words, pl, Fs, 12.0)
     assert sum(int((r[0][:, 0] >= 0).sum()) for r in refs) > 500
     # max_count below the stride, the host form, the NN lists
-    dev = upload(frames, stride, words)
-    idx, dist, _ = run_knn(dev, stride, words, pl, Fs, 12.0, 2, False, max_count=5000)
+    dev = upload(stride, words, *zip(*frames))
+    idx, dist, _ = run_knn(ENGINE, dev, stride, words, pl, 2, False, max_count=5000, guide=(Fs, 12.0))
     for m, (a, b) in enumerate(pl):
         assert (idx[m, :len(frames[a][0])] == refs[m][0]).all()
     for m in (0, 3, 4, 10):
@@ -254,7 +189,7 @@ def test_shapes_padded_repeated_swapped_untouched(words):
         h1 = ENGINE.knn_guided(frames[a][0], kp_array(frames[a][1]), frames[b][0], kp_array(frames[b][1]), Fs[m], 12.0, k=1)
         assert (h1[0] == refs[m][0][:, :1]).all() and (h1[1] == refs[m][1][:, :1]).all()
     for max_dist, ratio, cross in ((32 * words, 0.0, False), (32 * words // 3, 0.8, True), (0, 1.0, False)):
-        out = run_match(dev, stride, words, pl, Fs, 12.0, max_dist, ratio, cross)
+        out = run_nn(ENGINE, dev, stride, words, pl, max_dist, ratio, cross, guide=(Fs, 12.0))
         for m, (a, b) in enumerate(pl):
             n1 = len(frames[a][0])
             assert (out[m, :n1] == ref_select(*refs[m], max_dist, ratio, cross)).all(), (m, max_dist, ratio, cross)
@@ -274,14 +209,14 @@ def test_chunk_size_and_repeatability():
     pl = [(i, j) for i in range(Fn) for j in range(Fn) if i != j][:40]
     Fs = [rng.normal(size=9).astype(np.float32) for _ in pl]
     stride = 900
-    dev = upload(frames, stride, words)
-    base = run_knn(dev, stride, words, pl, Fs, 6.0, 2, True)
-    again = run_knn(dev, stride, words, pl, Fs, 6.0, 2, True)
-    m0 = run_match(dev, stride, words, pl, Fs, 6.0, 80, 0.8, True)
+    dev = upload(stride, words, *zip(*frames))
+    base = run_knn(ENGINE, dev, stride, words, pl, 2, True, guide=(Fs, 6.0))
+    again = run_knn(ENGINE, dev, stride, words, pl, 2, True, guide=(Fs, 6.0))
+    m0 = run_nn(ENGINE, dev, stride, words, pl, 80, 0.8, True, guide=(Fs, 6.0))
     try:
         ENGINE.set_match_chunk(16)
-        small = run_knn(dev, stride, words, pl, Fs, 6.0, 2, True)
-        m1 = run_match(dev, stride, words, pl, Fs, 6.0, 80, 0.8, True)
+        small = run_knn(ENGINE, dev, stride, words, pl, 2, True, guide=(Fs, 6.0))
+        m1 = run_nn(ENGINE, dev, stride, words, pl, 80, 0.8, True, guide=(Fs, 6.0))
     finally:
         ENGINE.set_match_chunk(2048)
     for x, y, z in zip(base, again, small):
@@ -331,7 +266,7 @@ def test_out_of_range_coordinate_rejects_its_pairs_and_reports():
     stride = 320
     pl = [(0, 1), (3, 1), (1, 3), (1, 0)]
     Fs = [rng.normal(size=9).astype(np.float32) for _ in pl]
-    dev = upload(frames, stride, words)
+    dev = upload(stride, words, *zip(*frames))
     d_pl = torch.tensor(pl, dtype=torch.int32, device=DEV)
     d_F = torch.from_numpy(np.stack(Fs)).to(DEV)
     idx = torch.full((4, stride, 2), 77, dtype=torch.int32, device=DEV)
@@ -363,7 +298,7 @@ def sequence(n_frames, n_pts, seed, words, flip=0.1):
     rng = np.random.default_rng(seed)
     X = np.stack([rng.uniform(-3, 3, n_pts), rng.uniform(-4, 4, n_pts), rng.uniform(5, 10, n_pts)], 1)
     base = rng.integers(0, 2**32, size=(n_pts, words), dtype=np.uint32)
-    poses = [(rot_y(0.02 * f), np.array([0.25 * f, 0.02 * f, 0.0])) for f in range(n_frames)]
+    poses = [(synth.rot_y(0.02 * f), np.array([0.25 * f, 0.02 * f, 0.0])) for f in range(n_frames)]
     frames, ids = [], []
     for R, t in poses:
         x = (K @ (R @ X.T + t[:, None])).T
@@ -378,7 +313,7 @@ def sequence(n_frames, n_pts, seed, words, flip=0.1):
     def F_of(a, b):   # x_a ~ K (Ra X + ta), x_b ~ K (Rb X + tb): relative motion a -> b
         (Ra, ta), (Rb, tb) = poses[a], poses[b]
         R = Rb @ Ra.T
-        return true_F(R, tb - R @ ta)
+        return synth.fundamental_from_pose(K, R, tb - R @ ta)
     return frames, ids, F_of
 
 
@@ -386,26 +321,16 @@ def test_nn_lists_feed_the_track_graph():
     words, Fn = 8, 6
     frames, _, F_of = sequence(Fn, 700, 21, words)
     stride = max(len(f[0]) for f in frames)
-    dev = upload(frames, stride, words)
+    dev = upload(stride, words, *zip(*frames))
     counts = dev[3]
     pl = [(i, j) for i in range(Fn) for j in range(i + 1, Fn)]
     Fs = [F_of(a, b) for a, b in pl]
-    m = run_match(dev, stride, words, pl, Fs, 2.0, 70, 0.8, True)
+    m = run_nn(ENGINE, dev, stride, words, pl, 70, 0.8, True, guide=(Fs, 2.0))
     for q in (0, len(pl) - 1):
         a, b = pl[q]
         r = ref_guided(frames[a][0], frames[b][0], frames[a][1], frames[b][1], Fs[q], 2.0)
         assert (m[q, :counts[a]] == ref_select(*r, 70, 0.8, True)).all()
-    M = len(pl)
-    i32 = dict(dtype=torch.int32, device=DEV)
-    track_of = torch.full((Fn, stride), 77, **i32)
-    offsets = torch.full((Fn * stride + 1,), 77, **i32)
-    nodes = torch.full((Fn * stride, 2), 77, **i32)
-    summary = torch.full((8,), 77, **i32)
-    ENGINE.tracks_dev(torch.from_numpy(m).to(DEV), dev[2], torch.tensor(pl, **i32), M, Fn, stride, Fn, 70, 2, track_of, offsets,
-                      nodes, summary)
-    ENGINE.check_status()
-    s = summary.cpu().tolist()
-    off, nod, tof = offsets.cpu().numpy()[:s[0] + 1], nodes.cpu().numpy()[:s[1]], track_of.cpu().numpy()
+    off, nod, tof, s = run_tracks(ENGINE, counts, pl, m, stride, 70, 2)
     e_off, e_nodes, e_tof, e_s = tracks_np.tracks_arrays(counts, pl, m, stride, 70, 2)
     assert (off == e_off).all() and (nod == e_nodes).all() and (tof == e_tof).all()
     assert s[0] == e_s["n_tracks"] > 100 and s[1] == e_s["n_nodes"]
@@ -421,7 +346,7 @@ def test_ransac_F_is_accepted_as_is():
     j = np.nonzero(truth >= 0)[0]
     stride = n
     frames = [(da, kpa), (db, kpb)]
-    dev = upload(frames, stride, words)
+    dev = upload(stride, words, *zip(*frames))
     ml = np.zeros((1, stride, 3), dtype=np.int32)
     ml[0, :len(j), 0], ml[0, :len(j), 1] = truth[j], j          # the true list: (row, column, 0)
     d_pl = torch.tensor([[0, 1]], dtype=torch.int32, device=DEV)
@@ -468,13 +393,9 @@ def test_guided_lists_hold_more_correct_and_fewer_wrong_matches():
     assert (truth[inv] == np.arange(nt)).all()
     frames = [(da, kpa), (db, kpb)]
     stride = nt
-    dev = upload(frames, stride, words)
-    d_pl = torch.tensor([[0, 1]], dtype=torch.int32, device=DEV)
-    nn = torch.full((1, stride, 3), 77, dtype=torch.int32, device=DEV)
-    ENGINE.match_nn_batch_dev(dev[0], dev[2], stride, words, d_pl, 1, nn, 60, 0.8, False)
-    ENGINE.check_status()
-    nn = nn.cpu().numpy()[0]
-    gd = run_match(dev, stride, words, [(0, 1)], [F], 2.0, 60, 0.8, False)[0]
+    dev = upload(stride, words, *zip(*frames))
+    nn = run_nn(ENGINE, dev, stride, words, [(0, 1)], 60, 0.8, False)[0]
+    gd = run_nn(ENGINE, dev, stride, words, [(0, 1)], 60, 0.8, False, guide=([F], 2.0))[0]
     r = ref_guided(da, db, kpa, kpb, F, 2.0)
     assert (gd == ref_select(*r, 60, 0.8, False)).all()
 

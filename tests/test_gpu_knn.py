@@ -1,9 +1,8 @@
 """GPU tests of the exact nearest-neighbour mode (pgx_knn_batch_dev, pgx_match_nn_batch_dev, pgx_knn; include/pgx.h).
 
-Everything is an exact integer result, so every check is entry by entry.  The yardstick is a numpy brute force that lives
-here (a popcount table over uint8 views, then lexsort((j, d)) per row; the column side a first-occurrence argmin), itself
-checked against a literal Python loop over bin(x ^ y).count("1") -- the hamming_distance of the reference's Python
-prototype (python_src/photogrammetry/image_processing/keypoint_matching.py).  Two checks tie the mode to paths that
+Everything is an exact integer result, so every check is entry by entry.  The yardstick is the numpy brute force of
+tests/knn_ref.py (a popcount table over uint8 views, then lexsort((j, d)) per row; the column side a first-occurrence argmin),
+itself checked here against its literal Python loop over bin(x ^ y).count("1").  Two checks tie the mode to paths that
 already exist: a mutual nearest pair under the (d, index) order is always taken by the greedy assignment
 (pgx_match_batch_dev), and NN lists go through the track graph (pgx_tracks_dev) like the oracle's and the host form's.
 """
@@ -11,14 +10,14 @@ import numpy as np
 import pytest
 import torch
 
+from geom_gpu import as_lists, run_tracks
+from knn_ref import NONE, loop_knn, rand_desc, ref_knn, ref_select
+from match_gpu import DEV, run_knn, run_nn, upload
 from oracle import tracks_np
 import photogrammetry_amd as pg
 from photogrammetry_amd import synth
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-NONE = 2**31 - 1
-POP8 = np.array([bin(x).count("1") for x in range(256)], dtype=np.uint16)
 
 ENGINE = None
 
@@ -30,69 +29,6 @@ def _engine():
     yield
     ENGINE.close()
     ENGINE = None
-
-
-# ---- the numpy yardstick ------------------------------------------------------------------------------------------------
-def dist_matrix(a, b, i0=0, i1=None):
-    """[i1 - i0][n2] hamming distances of rows i0..i1 of a against b (uint32 [n][words])."""
-    a8 = np.ascontiguousarray(a[i0:i1]).view(np.uint8)
-    b8 = np.ascontiguousarray(b).view(np.uint8)
-    return POP8[a8[:, None, :] ^ b8[None, :, :]].sum(-1, dtype=np.int32)
-
-
-def ref_knn(a, b, block=128):
-    """-> idx [n1][2], dist [n1][2] (ascending (d, j), missing = (-1, NONE)), col [n2] (smallest (d, i), -1 without rows)."""
-    n1, n2 = len(a), len(b)
-    idx = np.full((n1, 2), -1, dtype=np.int32)
-    dist = np.full((n1, 2), NONE, dtype=np.int32)
-    cbest = np.full(n2, NONE, dtype=np.int64)
-    col = np.full(n2, -1, dtype=np.int32)
-    if n2 == 0:
-        return idx, dist, col
-    for i0 in range(0, n1, block):
-        d = dist_matrix(a, b, i0, i0 + block)
-        j = np.broadcast_to(np.arange(n2, dtype=np.int32), d.shape)
-        order = np.lexsort((j, d), axis=-1)[:, :2]
-        kk = order.shape[1]
-        idx[i0:i0 + len(d), :kk] = order
-        dist[i0:i0 + len(d), :kk] = np.take_along_axis(d, order, axis=1)
-        mn, am = d.min(0), d.argmin(0)           # argmin: the first (smallest) row of a tie
-        better = mn < cbest                      # strict: an earlier block keeps a tie
-        cbest[better] = mn[better]
-        col[better] = am[better] + i0
-    return idx, dist, col
-
-
-def ref_select(idx, dist, col, max_dist, ratio, cross):
-    n1 = len(idx)
-    i = np.arange(n1)
-    j1, d1, j2, d2 = idx[:, 0], dist[:, 0].astype(np.int64), idx[:, 1], dist[:, 1].astype(np.int64)
-    ok = (j1 >= 0) & (d1 <= max_dist)
-    if ratio > 0:
-        ok &= (j2 < 0) | (d1.astype(np.float64) < np.float64(np.float32(ratio)) * d2.astype(np.float64))
-    if cross and len(col):   # no column: no row was accepted anyway
-        ok &= col[np.where(j1 >= 0, j1, 0)] == i
-    out = np.zeros((n1, 3), dtype=np.int32)
-    out[:, 0] = i
-    out[:, 1] = np.where(ok, j1, -1)
-    out[:, 2] = np.where(ok, dist[:, 0], NONE)
-    return out
-
-
-def loop_knn(a, b):
-    """Literal loops, tiny inputs only."""
-    ints = lambda d: [int("".join("%08x" % w for w in row[::-1]), 16) for row in d]   # noqa: E731
-    A, B = ints(a), ints(b)
-    rows = []
-    for x in A:
-        ds = sorted((bin(x ^ y).count("1"), j) for j, y in enumerate(B))
-        rows.append(ds[:2])
-    cols = [min(((bin(x ^ y).count("1"), i) for i, x in enumerate(A)), default=(NONE, -1))[1] for y in B]
-    return rows, cols
-
-
-def rand_desc(rng, n, words):
-    return rng.integers(0, 2**32, size=(n, words), dtype=np.uint32)
 
 
 def check_host(a, b, k, col):
@@ -153,49 +89,19 @@ def test_tie_heavy_pool(words):
 
 
 # ---- device batch ---------------------------------------------------------------------------------------------------------
-def to_dev(descs, stride, words):
-    F = len(descs)
-    buf = np.zeros((F, stride, words), dtype=np.uint32)
-    for f, d in enumerate(descs):
-        buf[f, :len(d)] = d
-    counts = np.array([len(d) for d in descs], dtype=np.int32)
-    return torch.from_numpy(buf.view(np.int32)).to(DEV), torch.from_numpy(counts).to(DEV), counts
-
-
-def run_knn_dev(d_desc, d_counts, stride, words, pl, k, col, sentinel=77, max_count=None):
-    M = len(pl)
-    d_pl = torch.tensor(np.asarray(pl, dtype=np.int32).reshape(-1, 2), device=DEV)
-    idx = torch.full((M, stride, k), sentinel, dtype=torch.int32, device=DEV)
-    dist = torch.full((M, stride, k), sentinel, dtype=torch.int32, device=DEV)
-    cnn = torch.full((M, stride), sentinel, dtype=torch.int32, device=DEV) if col else None
-    torch.cuda.synchronize()
-    ENGINE.knn_batch_dev(d_desc, d_counts, stride, words, d_pl, M, k, idx, dist, cnn, max_count=max_count)
-    ENGINE.check_status()
-    return idx.cpu().numpy(), dist.cpu().numpy(), (cnn.cpu().numpy() if col else None)
-
-
-def run_nn_dev(d_desc, d_counts, stride, words, pl, max_dist, ratio, cross, sentinel=77):
-    M = len(pl)
-    d_pl = torch.tensor(np.asarray(pl, dtype=np.int32).reshape(-1, 2), device=DEV)
-    out = torch.full((M, stride, 3), sentinel, dtype=torch.int32, device=DEV)
-    torch.cuda.synchronize()
-    ENGINE.match_nn_batch_dev(d_desc, d_counts, stride, words, d_pl, M, out, max_dist, ratio, cross)
-    ENGINE.check_status()
-    return out.cpu().numpy()
-
-
 @pytest.mark.parametrize("words", [8, 3])
 def test_batch_padded_repeated_swapped_and_untouched(words):
     rng = np.random.default_rng(11)
     sizes = [300, 0, 1000, 77, 2, 513]
     descs = [rand_desc(rng, n, words) for n in sizes]
     stride = 1100
-    d_desc, d_counts, counts = to_dev(descs, stride, words)
+    dev = upload(stride, words, descs)
+    counts = dev[3]
     pl = [(0, 2), (2, 0), (0, 2), (3, 5), (5, 3), (2, 1), (1, 2), (4, 0), (0, 4), (5, 5)]
     refs = {p: ref_knn(descs[p[0]], descs[p[1]]) for p in set(pl)}
     for k in (1, 2):
         for col in (False, True):
-            idx, dist, cnn = run_knn_dev(d_desc, d_counts, stride, words, pl, k, col)
+            idx, dist, cnn = run_knn(ENGINE, dev, stride, words, pl, k, col)
             for m, (a, b) in enumerate(pl):
                 r_idx, r_dist, r_col = refs[(a, b)]
                 n1, n2 = counts[a], counts[b]
@@ -207,7 +113,7 @@ def test_batch_padded_repeated_swapped_and_untouched(words):
                     h = ENGINE.knn(descs[a], descs[b], k=2, col=True)
                     assert (h[0] == idx[m, :n1]).all() and (h[1] == dist[m, :n1]).all() and (h[2] == cnn[m, :n2]).all()
     # max_count below the stride still covers every count
-    idx, dist, _ = run_knn_dev(d_desc, d_counts, stride, words, pl, 2, False, max_count=int(counts.max()))
+    idx, dist, _ = run_knn(ENGINE, dev, stride, words, pl, 2, False, max_count=int(counts.max()))
     for m, (a, b) in enumerate(pl):
         assert (idx[m, :counts[a]] == refs[(a, b)][0]).all()
 
@@ -219,14 +125,15 @@ def test_match_nn_grid(words):
     descs = [a, b[:650], rand_desc(rng, 400, words), np.zeros((0, words), np.uint32)]
     descs.append(descs[0][rng.integers(0, 700, 300)])   # duplicates: equal nearest distances, ratio 1.0 rejects them
     stride = 704
-    d_desc, d_counts, counts = to_dev(descs, stride, words)
+    dev = upload(stride, words, descs)
+    counts = dev[3]
     pl = [(0, 1), (1, 0), (0, 2), (2, 3), (4, 0), (0, 4)]
     refs = {p: ref_knn(descs[p[0]], descs[p[1]]) for p in set(pl)}
     dmax = 32 * words
     for max_dist in (0, dmax // 5, dmax // 3, dmax):
         for ratio in (0.0, 0.6, 0.8, 1.0):
             for cross in (False, True):
-                out = run_nn_dev(d_desc, d_counts, stride, words, pl, max_dist, ratio, cross)
+                out = run_nn(ENGINE, dev, stride, words, pl, max_dist, ratio, cross)
                 for m, (fa, fb) in enumerate(pl):
                     exp = ref_select(*refs[(fa, fb)], max_dist, ratio, cross)
                     n1 = counts[fa]
@@ -246,14 +153,15 @@ def test_match_nn_across_a_chunk_boundary(words):
         bits ^= (rng.random(bits.shape) < 0.08).astype(np.uint8)
         descs.append(np.ascontiguousarray(np.packbits(bits, axis=1).view(np.uint32)).reshape(n, words))
     stride = 160
-    d_desc, d_counts, counts = to_dev(descs, stride, words)
+    dev = upload(stride, words, descs)
+    counts = dev[3]
     pl = [(i, j) for i in range(6) for j in range(i + 1, 6)] + [(5, 0), (3, 3)]
     assert len(pl) == 17
     max_dist = 32 * words // 3
-    whole = run_nn_dev(d_desc, d_counts, stride, words, pl, max_dist, 0.8, True)
+    whole = run_nn(ENGINE, dev, stride, words, pl, max_dist, 0.8, True)
     try:
         ENGINE.set_match_chunk(16)
-        chunked = run_nn_dev(d_desc, d_counts, stride, words, pl, max_dist, 0.8, True)
+        chunked = run_nn(ENGINE, dev, stride, words, pl, max_dist, 0.8, True)
     finally:
         ENGINE.set_match_chunk(2048)
     assert chunked.tobytes() == whole.tobytes()
@@ -291,11 +199,11 @@ def test_mutual_nearest_pairs_are_taken_by_the_greedy():
     a, b, _ = synth.true_match_descriptors(4096, 8, 9, flip=0.2)
     descs = [rand_desc(rng, 4096, 8), rand_desc(rng, 4096, 8), a, b]
     stride = 4096
-    d_desc, d_counts, counts = to_dev(descs, stride, 8)
+    dev = upload(stride, 8, descs)
     pl = [(0, 1), (2, 3)]
-    out = run_nn_dev(d_desc, d_counts, stride, 8, pl, 10**6, 0.0, True)
+    out = run_nn(ENGINE, dev, stride, 8, pl, 10**6, 0.0, True)
     greedy = torch.zeros((len(pl), stride, 3), dtype=torch.int32, device=DEV)
-    ENGINE.match_batch_dev(d_desc, d_counts, stride, 8, torch.tensor(pl, dtype=torch.int32, device=DEV), len(pl), greedy)
+    ENGINE.match_batch_dev(dev[0], dev[2], stride, 8, torch.tensor(pl, dtype=torch.int32, device=DEV), len(pl), greedy)
     ENGINE.check_status()
     greedy = greedy.cpu().numpy()
     for m in range(len(pl)):
@@ -315,25 +223,17 @@ def test_nn_lists_feed_the_track_graph():
         bits = np.unpackbits(base[keep].view(np.uint8), axis=1)
         bits ^= (rng.random(bits.shape) < 0.08).astype(np.uint8)
         descs.append(np.ascontiguousarray(np.packbits(bits, axis=1).view(np.uint32)))
-    d_desc, d_counts, counts = to_dev(descs, stride, 8)
+    dev = upload(stride, 8, descs)
+    counts = dev[3]
     pl = [(i, j) for i in range(F) for j in range(i + 1, F)]
-    m = run_nn_dev(d_desc, d_counts, stride, 8, pl, 60, 0.8, True)
+    m = run_nn(ENGINE, dev, stride, 8, pl, 60, 0.8, True)
     M = len(pl)
-    i32 = dict(dtype=torch.int32, device=DEV)
-    track_of = torch.full((F, stride), 77, **i32)
-    offsets = torch.full((F * stride + 1,), 77, **i32)
-    nodes = torch.full((F * stride, 2), 77, **i32)
-    summary = torch.full((8,), 77, **i32)
-    ENGINE.tracks_dev(torch.from_numpy(m).to(DEV), d_counts, torch.tensor(pl, **i32), M, F, stride, F, 60, 2, track_of, offsets,
-                      nodes, summary)
-    ENGINE.check_status()
-    s = summary.cpu().tolist()
-    off, nod, tof = offsets.cpu().numpy()[:s[0] + 1], nodes.cpu().numpy()[:s[1]], track_of.cpu().numpy()
+    off, nod, tof, s = run_tracks(ENGINE, counts, pl, m, stride, 60, 2)
     e_off, e_nodes, e_tof, e_s = tracks_np.tracks_arrays(counts, pl, m, stride, 60, 2)
     assert (off == e_off).all() and (nod == e_nodes).all() and (tof == e_tof).all()
     assert s[0] == e_s["n_tracks"] > 100 and s[1] == e_s["n_nodes"]
     host, dropped, dropped_nodes = pg.tracks_host(counts, pl, [m[p] for p in range(M)], 60, 2)
-    assert host == [[(int(f), int(k)) for f, k in nod[off[t]:off[t + 1]]] for t in range(s[0])]
+    assert host == as_lists(off, nod)
     assert (dropped, dropped_nodes) == (s[2], s[3])
 
 
@@ -342,11 +242,10 @@ def test_bench_size_sample_and_repeatability():
     F, N = 64, 4096
     rng = np.random.default_rng(64)
     desc = rng.integers(0, 2**32, size=(F, N, 8), dtype=np.uint32)
-    d_desc = torch.from_numpy(desc.view(np.int32)).to(DEV)
-    d_counts = torch.full((F,), N, dtype=torch.int32, device=DEV)
+    dev = upload(N, 8, desc)
     pl = [(i, j) for i in range(F) for j in range(i + 1, F)]
-    r1 = run_knn_dev(d_desc, d_counts, N, 8, pl, 2, True)
-    r2 = run_knn_dev(d_desc, d_counts, N, 8, pl, 2, True)
+    r1 = run_knn(ENGINE, dev, N, 8, pl, 2, True)
+    r2 = run_knn(ENGINE, dev, N, 8, pl, 2, True)
     for x, y in zip(r1, r2):
         assert x.tobytes() == y.tobytes()
     for m in rng.choice(len(pl), 16, replace=False):

@@ -9,6 +9,7 @@ import torch
 
 from oracle import pose_np
 import photogrammetry_amd as pg
+from pose_ref import normed, two_views
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -22,22 +23,8 @@ def engine():
 
 
 def _two_views(n, n_out, seed):
-    """n true correspondences of a synthetic scene seen by two cameras with the reference's K, plus n_out wrong ones."""
-    rng = np.random.default_rng(seed)
-    K = pose_np.K.astype(np.float64)
-    X = np.stack([rng.uniform(-3, 3, n), rng.uniform(-4, 4, n), rng.uniform(4, 9, n)], 1)
-    a = 0.07
-    R = np.array([[np.cos(a), 0, np.sin(a)], [0, 1, 0], [-np.sin(a), 0, np.cos(a)]])
-    t = np.array([0.6, 0.05, 0.1])
-    x1 = (K @ X.T).T
-    x2 = (K @ (R @ X.T + t[:, None])).T
-    p1 = np.rint(x1[:, :2] / x1[:, 2:3]).astype(np.int32)
-    p2 = np.rint(x2[:, :2] / x2[:, 2:3]).astype(np.int32)
-    ok = (p1 >= 0).all(1) & (p2 >= 0).all(1) & (p1[:, 0] < 3000) & (p2[:, 0] < 3000) & (p1[:, 1] < 4000) & (p2[:, 1] < 4000)
-    p1, p2 = p1[ok], p2[ok]
-    o1 = np.stack([rng.integers(0, 3000, n_out), rng.integers(0, 4000, n_out)], 1).astype(np.int32)
-    o2 = np.stack([rng.integers(0, 3000, n_out), rng.integers(0, 4000, n_out)], 1).astype(np.int32)
-    return np.concatenate([p1, o1]), np.concatenate([p2, o2])
+    """Of n points drawn, the true correspondences seen by both cameras (pose_ref.two_views), plus n_out wrong ones."""
+    return two_views(n, n_out, seed, exact=False)[:2]
 
 
 def _upload(sets, stride):
@@ -58,11 +45,6 @@ def _upload(sets, stride):
             torch.tensor([[2 * m, 2 * m + 1] for m in range(M)], dtype=torch.int32, device=DEV))
 
 
-def _normed(F):
-    F = np.asarray(F, dtype=np.float64).reshape(3, 3)
-    return F / np.linalg.norm(F)
-
-
 def test_single_samples_match_the_oracle(engine):
     sets = [_two_views(300, 60, 1), _two_views(500, 0, 2), _two_views(40, 200, 3)]
     stride = 1024
@@ -80,7 +62,7 @@ def test_single_samples_match_the_oracle(engine):
             for m, (p1, p2) in enumerate(sets):
                 idx = pose_np.sample_indices(seed, m, 0, P, len(p1))
                 Fo = pose_np.estimate_fundamental(p1[idx], p2[idx])
-                assert np.abs(_normed(F[m]) - _normed(Fo)).max() < 2e-3, (P, seed, m)
+                assert np.abs(normed(F[m]) - normed(Fo)).max() < 2e-3, (P, seed, m)
                 co = int(pose_np.score(Fo, p1, p2, 0.001).sum())
                 assert abs(int(cnt[m]) - co) <= max(3, co // 100), (P, seed, m, cnt[m], co)
 
@@ -103,7 +85,7 @@ def test_ransac_picks_the_first_best_sample_and_argument_errors(engine):
         # the GPU's winner, re-scored by the oracle, really has that many inliers, and it is that sample's matrix
         idx = pose_np.sample_indices(77, m, got_s, P, len(p1))
         Fs = pose_np.estimate_fundamental(p1[idx], p2[idx])
-        assert np.abs(_normed(d_F[m].cpu().numpy()) - _normed(Fs)).max() < 2e-3
+        assert np.abs(normed(d_F[m].cpu().numpy()) - normed(Fs)).max() < 2e-3
         assert abs(int(pose_np.score(Fs, p1, p2, 0.001).sum()) - got_c) <= max(3, co // 100)
     with pytest.raises(pg.ArgumentException):          # CameraPoseEstimation.cs:28-29
         engine.fundamental_ransac_dev(d_kp, d_ml, d_counts, d_pl, M, stride, S, 7, 0.001, d_F, d_in, d_bs)

@@ -12,13 +12,13 @@ import numpy as np
 import pytest
 import torch
 
+from match_gpu import DEV, oracle_detect, pairs_equal, run_match
 from oracle import cref, tracks_np
 from photogrammetry_amd import dist as pdist
 from photogrammetry_amd import synth
 import photogrammetry_amd as pg
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 T = np.float32(0.1)
 
 
@@ -27,18 +27,6 @@ def engine():
     e = pg.Engine(0)
     yield e
     e.close()
-
-
-def _oracle_detect(frame, dmap, pairs, radius, cap):
-    src = cref.apply_distortion(frame, dmap) if dmap is not None else frame
-    g = cref.gray(src)
-    raw = cref.detect(g, T)
-    kept = raw[cref.nms(raw, radius)][:cap]
-    return kept, cref.brief(g, np.stack([kept["x"], kept["y"]], 1), pairs), len(raw)
-
-
-def _same(got, exp):
-    return bool((got[:, 0] == exp["k1"]).all() and (got[:, 1] == exp["k2"]).all() and (got[:, 2] == exp["dist"]).all())
 
 
 def test_sharded_sequence_world1_config3_shape(engine):
@@ -69,7 +57,7 @@ def test_sharded_sequence_world1_config3_shape(engine):
     desc = [job.descriptors(f).cpu().numpy().view(np.uint32)[:counts[f]] for f in range(F)]
     frames_h = d_frames.cpu().numpy()
     for f in (0, 5):
-        kept, edesc, n_raw = _oracle_detect(frames_h[f], dmap, pairs, radius, NKP)
+        kept, edesc, n_raw = oracle_detect(frames_h[f], dmap, pairs, T, radius, NKP)
         n = len(kept)
         assert n == counts[f] and int(job.nraw_l[f]) == n_raw
         kp = job.kp_l[f].cpu().numpy()
@@ -77,7 +65,7 @@ def test_sharded_sequence_world1_config3_shape(engine):
         assert (desc[f] == edesc).all()
     for m, (a, b) in enumerate(pl):
         got = job.matches(m).cpu().numpy()[:counts[a]]
-        assert _same(got, cref.match_sorted(desc[a], desc[b])), (a, b)
+        assert pairs_equal(got, cref.match_sorted(desc[a], desc[b])), (a, b)
     # the track graph the step built on the device from these 28 lists (pgx_tracks_dev; parity unpinned by
     # construction -- the reference has no track graph) against the sequential oracle: same tracks, order, per-node ids
     lists = np.stack([job.matches(m).cpu().numpy() for m in range(len(pl))])
@@ -91,21 +79,6 @@ def test_sharded_sequence_world1_config3_shape(engine):
     engine.set_capacity(1 << 17, 1 << 20)
 
 
-def _match_dev(engine, descs, pl, stride, max_count=None):
-    F = len(descs)
-    d = np.zeros((F, stride, 8), dtype=np.uint32)
-    for f in range(F):
-        d[f, :len(descs[f])] = descs[f]
-    d_desc = torch.from_numpy(d.view(np.int32)).to(DEV)
-    d_counts = torch.tensor([len(x) for x in descs], dtype=torch.int32, device=DEV)
-    d_pl = torch.tensor(pl, dtype=torch.int32, device=DEV)
-    d_out = torch.full((len(pl), stride, 3), -7, dtype=torch.int32, device=DEV)
-    torch.cuda.synchronize()
-    engine.match_batch_dev(d_desc, d_counts, stride, 8, d_pl, len(pl), d_out, max_count=max_count)
-    engine.check_status()
-    return d_out.cpu().numpy()
-
-
 def test_match_8192_squared_vs_oracle(engine):
     """BASELINE configs[3]'s list length: uniform-random (tie-heavy: distances ~ Binomial(256, 1/2)) and a
     true-correspondence pair (permuted copy with 15 % of the bits flipped), both directions."""
@@ -113,10 +86,10 @@ def test_match_8192_squared_vs_oracle(engine):
     a = synth.random_descriptors(N, 8, 81)
     b = synth.random_descriptors(N, 8, 82)
     t1, t2, _ = synth.true_match_descriptors(N, 8, 83)
-    out = _match_dev(engine, [a, b, t1, t2], [(0, 1), (1, 0), (2, 3), (3, 2)], N)
+    out = run_match(engine, [a, b, t1, t2], [(0, 1), (1, 0), (2, 3), (3, 2)], N)
     sets = [a, b, t1, t2]
     for m, (x, y) in enumerate([(0, 1), (1, 0), (2, 3), (3, 2)]):
-        assert _same(out[m][:N], cref.match_sorted(sets[x], sets[y])), (x, y)
+        assert pairs_equal(out[m][:N], cref.match_sorted(sets[x], sets[y])), (x, y)
     rounds, evals, evals0 = engine.match_stats()
     assert rounds >= 3 and evals0 == 4 * N * N
 
@@ -144,14 +117,14 @@ def test_detect_and_match_4k_pair_end_to_end(engine):
     engine.match_batch_dev(d_desc, d_counts, NKP, 8, d_pl, 1, d_out, max_count=NKP)
     engine.check_status()
     desc = d_desc.cpu().numpy().view(np.uint32)
-    exp = [_oracle_detect(frames[f], dmap, pairs, radius, NKP) for f in range(2)]
+    exp = [oracle_detect(frames[f], dmap, pairs, T, radius, NKP) for f in range(2)]
     for f in range(2):
         kept, edesc, n_raw = exp[f]
         assert len(kept) == NKP and int(d_counts[f]) == NKP and int(d_nraw[f]) == n_raw
         kp = d_kp[f].cpu().numpy()
         assert (kp[:, 0] == kept["x"]).all() and (kp[:, 1] == kept["y"]).all() and (kp[:, 2] == kept["fast_score"]).all()
         assert (desc[f] == edesc).all()
-    assert _same(d_out[0].cpu().numpy(), cref.match_sorted(exp[0][1], exp[1][1]))
+    assert pairs_equal(d_out[0].cpu().numpy(), cref.match_sorted(exp[0][1], exp[1][1]))
     engine.set_dewarp_map(None)
     engine.set_capacity(1 << 17, 1 << 20)
 
@@ -175,7 +148,7 @@ def test_match_three_chunks_with_wide_rounds(engine):
     engine.profile_reset()
     engine.profile_enable(True)
     engine.set_match_chunk(128)
-    out = _match_dev(engine, descs, pl, 2560)
+    out = run_match(engine, descs, pl, 2560)
     engine.set_match_chunk(2048)
     engine.profile_enable(False)
     n_wide, _ = engine.profile_get("ham_argmin")
@@ -185,7 +158,7 @@ def test_match_three_chunks_with_wide_rounds(engine):
     assert rounds >= 1 and evals0 == sum(sizes[a] * sizes[b] for a, b in pl)
     for m, (a, b) in enumerate(pl):
         if m % 2 == 0 or m % 128 in (0, 1, 126, 127):
-            assert _same(out[m][:sizes[a]], cref.match_sorted(descs[a], descs[b])), (a, b)
+            assert pairs_equal(out[m][:sizes[a]], cref.match_sorted(descs[a], descs[b])), (a, b)
 
 
 @pytest.mark.parametrize("W,H,F", [(451, 383, 5), (333, 77, 6), (127, 129, 9)])
@@ -209,7 +182,7 @@ def test_detect_batch_odd_frame_sizes(engine, W, H, F):
     engine.check_status()
     desc = d_desc.cpu().numpy().view(np.uint32)
     for f in range(F):
-        kept, edesc, n_raw = _oracle_detect(frames[f], dmap, pairs, radius, CAP)
+        kept, edesc, n_raw = oracle_detect(frames[f], dmap, pairs, T, radius, CAP)
         n = len(kept)
         assert int(d_nraw[f]) == n_raw and int(d_counts[f]) == n, f
         kp = d_kp[f].cpu().numpy()
@@ -227,7 +200,7 @@ def test_survivor_limit_cuts_silently_and_capacity_still_raises(engine):
     engine.set_detect_params(T, radius)
     engine.set_dewarp_map(None)
     frame = synth.make_frame(W, H, seed=33, n_shapes=1500)
-    kept, edesc, _ = _oracle_detect(frame, None, pairs, radius, 1 << 20)
+    kept, edesc, _ = oracle_detect(frame, None, pairs, T, radius, 1 << 20)
     assert len(kept) > 300
     engine.set_capacity(1 << 17, 200)
     kp, desc, _ = engine.detect(frame, capacity=4096)
@@ -273,7 +246,7 @@ def test_c_abi_communicator_world1_and_sequence_step(engine):
         a, b = pl[m]
         da = jb.descriptors(a).cpu().numpy().view(np.uint32)[:counts[a]]
         db = jb.descriptors(b).cpu().numpy().view(np.uint32)[:counts[b]]
-        assert _same(jb.matches(m).cpu().numpy()[:counts[a]], cref.match_sorted(da, db))
+        assert pairs_equal(jb.matches(m).cpu().numpy()[:counts[a]], cref.match_sorted(da, db))
     engine.comm_destroy()
     engine.comm_destroy()                           # idempotent
     engine.set_stream(0)
@@ -294,11 +267,11 @@ def test_tail_fallback_distance_256_and_oversized_residual(engine):
     ident2[::7, 3] ^= 1                                        # a few at distance 1
     sets = [a, np.ascontiguousarray(b), ident1, ident2]
     pl = [(0, 1), (1, 0), (2, 3)]
-    out = _match_dev(engine, sets, pl, 2304)
+    out = run_match(engine, sets, pl, 2304)
     bits = lambda d: np.unpackbits(d.view(np.uint8), axis=1).astype(np.int32)
     assert ((bits(a)[:, None, :] != bits(sets[1])[None, :, :]).sum(2) == 256).any()   # the byte matrix would overflow
     for m, (x, y) in enumerate(pl):
-        assert _same(out[m][:len(sets[x])], cref.match_sorted(sets[x], sets[y])), (x, y)
+        assert pairs_equal(out[m][:len(sets[x])], cref.match_sorted(sets[x], sets[y])), (x, y)
 
 
 def _two_rank_worker(rank, world, port, q):
@@ -532,7 +505,7 @@ def test_match_many_pairs_with_sets_above_4096(engine):
     pl = [(a, b) for a in range(F) for b in range(a + 1, F)]
     assert len(pl) == 561
     engine.set_match_chunk(2048)
-    out = _match_dev(engine, descs, pl, 4736)
+    out = run_match(engine, descs, pl, 4736)
     for m in (0, 1, 255, 256, 511, 512, 560):
         a, b = pl[m]
-        assert _same(out[m][:sizes[a]], cref.match_sorted(descs[a], descs[b])), (a, b)
+        assert pairs_equal(out[m][:sizes[a]], cref.match_sorted(descs[a], descs[b])), (a, b)

@@ -14,7 +14,7 @@ import torch
 
 from oracle import tracks_np
 import photogrammetry_amd as pg
-from geom_gpu import DEV, INT_MAX, constructed_job, random_case
+from geom_gpu import DEV, INT_MAX, as_lists, constructed_job, random_case, run_tracks, summary_dict
 
 pytestmark = pytest.mark.gpu
 
@@ -26,32 +26,10 @@ def engine():
     e.close()
 
 
-def run_dev(engine, counts, pair_list, matches, stride, max_dist, min_len=2, frame_ids=None, n_frames=None):
-    """counts [F] by slot, pair_list [M][2] slots, matches [M][stride][3] -> (offsets, nodes, track_of, summary dict)."""
-    i32 = dict(dtype=torch.int32, device=DEV)
-    F = len(counts)
-    nf = F if n_frames is None else n_frames
-    M = len(pair_list)
-    d_m = torch.from_numpy(np.ascontiguousarray(matches, dtype=np.int32).reshape(max(M, 1), stride, 3)).to(DEV)
-    d_c = torch.tensor(np.asarray(counts, dtype=np.int32), **i32)
-    d_pl = torch.tensor(np.asarray(pair_list, dtype=np.int32).reshape(-1, 2) if M else np.zeros((1, 2), np.int32), **i32)
-    d_ids = None if frame_ids is None else torch.tensor(np.asarray(frame_ids, dtype=np.int32), **i32)
-    track_of = torch.full((nf, stride), 77, **i32)
-    offsets = torch.full((nf * stride + 1,), 77, **i32)
-    nodes = torch.full((nf * stride, 2), 77, **i32)
-    summary = torch.full((8,), 77, **i32)
-    torch.cuda.synchronize()
-    engine.tracks_dev(d_m, d_c, d_pl, M, F, stride, nf, max_dist, min_len, track_of, offsets, nodes, summary, d_frame_ids=d_ids)
-    engine.check_status()
-    s = summary.cpu().tolist()
-    summ = {"n_tracks": s[0], "n_nodes": s[1], "dropped": s[2], "dropped_nodes": s[3], "edges": s[4], "longest": s[5],
-            "largest_dropped": s[6]}
-    assert s[7] == 0
-    return offsets.cpu().numpy()[:s[0] + 1], nodes.cpu().numpy()[:s[1]], track_of.cpu().numpy(), summ
-
-
-def as_lists(offsets, nodes):
-    return [[(int(f), int(k)) for f, k in nodes[offsets[t]:offsets[t + 1]]] for t in range(len(offsets) - 1)]
+def run_dev(engine, *args, **kwargs):
+    """geom_gpu.run_tracks with the summary as the oracle's dict -> (offsets, nodes, track_of, summary dict)."""
+    off, nodes, tof, s = run_tracks(engine, *args, **kwargs)
+    return off, nodes, tof, summary_dict(s)
 
 
 def check_against_oracle(engine, counts, pl, m, stride, max_dist, min_len=2):

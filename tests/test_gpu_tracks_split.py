@@ -12,14 +12,13 @@ import torch
 
 import photogrammetry_amd as pg
 import tracks_split_ref as ref
-from geom_gpu import constructed_job, random_case
+from geom_gpu import DEV, INT_MAX, as_lists, constructed_job, random_case, run_tracks, run_tracks_split, tracks_buffers
+from match_gpu import run_nn, upload
 from oracle import tracks_np
 from photogrammetry_amd import dist as pdist
 from photogrammetry_amd import synth
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-INT_MAX = 2**31 - 1
 
 
 @pytest.fixture(scope="module")
@@ -29,46 +28,8 @@ def engine():
     e.close()
 
 
-def _buffers(counts, pair_list, matches, stride, frame_ids, nf):
-    i32 = dict(dtype=torch.int32, device=DEV)
-    M = len(pair_list)
-    d_m = torch.from_numpy(np.ascontiguousarray(matches, dtype=np.int32).reshape(max(M, 1), stride, 3)).to(DEV)
-    d_c = torch.tensor(np.asarray(counts, dtype=np.int32), **i32)
-    d_pl = torch.tensor(np.asarray(pair_list, dtype=np.int32).reshape(-1, 2) if M else np.zeros((1, 2), np.int32), **i32)
-    d_ids = None if frame_ids is None else torch.tensor(np.asarray(frame_ids, dtype=np.int32), **i32)
-    outs = (torch.full((nf, stride), 77, **i32), torch.full((nf * stride + 1,), 77, **i32), torch.full((nf * stride, 2), 77, **i32))
-    return d_m, d_c, d_pl, d_ids, outs
-
-
-def run_split(engine, counts, pair_list, matches, stride, max_dist, gates, min_len=2, frame_ids=None, n_frames=None):
-    """-> (offsets, nodes, track_of, summary [16] list)"""
-    nf = len(counts) if n_frames is None else n_frames
-    d_m, d_c, d_pl, d_ids, (track_of, offsets, nodes) = _buffers(counts, pair_list, matches, stride, frame_ids, nf)
-    summary = torch.full((16,), 77, dtype=torch.int32, device=DEV)
-    torch.cuda.synchronize()
-    engine.tracks_split_dev(d_m, d_c, d_pl, len(pair_list), len(counts), stride, nf, max_dist, gates, min_len, track_of, offsets,
-                            nodes, summary, d_frame_ids=d_ids)
-    engine.check_status()
-    s = summary.cpu().tolist()
-    return offsets.cpu().numpy()[:s[0] + 1], nodes.cpu().numpy()[:s[1]], track_of.cpu().numpy(), s
-
-
-def run_plain(engine, counts, pair_list, matches, stride, max_dist, min_len=2):
-    nf = len(counts)
-    d_m, d_c, d_pl, d_ids, (track_of, offsets, nodes) = _buffers(counts, pair_list, matches, stride, None, nf)
-    summary = torch.full((8,), 77, dtype=torch.int32, device=DEV)
-    engine.tracks_dev(d_m, d_c, d_pl, len(pair_list), nf, stride, nf, max_dist, min_len, track_of, offsets, nodes, summary)
-    engine.check_status()
-    s = summary.cpu().tolist()
-    return offsets.cpu().numpy()[:s[0] + 1], nodes.cpu().numpy()[:s[1]], track_of.cpu().numpy(), s
-
-
-def as_lists(offsets, nodes):
-    return [[(int(f), int(k)) for f, k in nodes[offsets[t]:offsets[t + 1]]] for t in range(len(offsets) - 1)]
-
-
 def check(engine, counts, pl, m, stride, max_dist, gates, min_len=2, host=True):
-    off, nodes, tof, s = run_split(engine, counts, pl, m, stride, max_dist, gates, min_len)
+    off, nodes, tof, s = run_tracks_split(engine, counts, pl, m, stride, max_dist, gates, min_len)
     e_off, e_nodes, e_tof, e_s = ref.arrays(counts, pl, m, stride, max_dist, gates, min_len)
     assert (off == e_off).all() and (nodes == e_nodes).all() and (tof == e_tof).all()
     assert s == ref.summary16(e_s), (s, e_s)
@@ -84,7 +45,7 @@ def test_hand_built_case(engine):
     assert as_lists(off, nodes) == exp and s[8:10] == [0, 10] and s[2:4] == [1, 3]
     assert tof[6, 1] == -1 and tof[4, 0] == tof[4, 1] == tof[5, 0] == -2
     # the same lists through today's graph: every component dropped
-    _, _, _, s0 = run_plain(engine, counts, pl, m, stride, max_dist)
+    _, _, _, s0 = run_tracks(engine, counts, pl, m, stride, max_dist)
     assert s0[0] == 0 and s0[2] == 3
 
 
@@ -103,13 +64,13 @@ def test_no_gates_is_tracks_dev_and_kept_tracks_survive(engine, seed):
     F, stride = 6 + seed, [64, 257, 1024][seed]
     counts, pl, m = random_case(10 + seed, F, stride)
     for max_dist in (3, 30, 59):
-        p_off, p_nodes, p_tof, p_s = run_plain(engine, counts, pl, m, stride, max_dist)
-        off, nodes, tof, s = run_split(engine, counts, pl, m, stride, max_dist, [])
+        p_off, p_nodes, p_tof, p_s = run_tracks(engine, counts, pl, m, stride, max_dist)
+        off, nodes, tof, s = run_tracks_split(engine, counts, pl, m, stride, max_dist, [])
         assert (off == p_off).all() and (nodes == p_nodes).all() and (tof == p_tof).all()
         assert s[:8] == p_s and s[8] == p_s[1] and s[9:] == [0] * 7
         kept = {tuple(t) for t in as_lists(p_off, p_nodes)}
         for gates in ([max_dist - 1], [max_dist - 1, max_dist // 2, 0]):
-            off, nodes, tof, s = run_split(engine, counts, pl, m, stride, max_dist, gates)
+            off, nodes, tof, s = run_tracks_split(engine, counts, pl, m, stride, max_dist, gates)
             assert kept <= {tuple(t) for t in as_lists(off, nodes)}
             assert s[3] <= p_s[3] and s[8] == p_s[1]
 
@@ -121,7 +82,7 @@ def test_pair_order_slot_permutation_padding_and_frame_subset(engine):
     e_off, e_nodes, e_tof, e_s = ref.arrays(counts, pl, m, stride, max_dist, gates)
     assert e_s["per_level"][1:] != [0, 0, 0]         # the case exercises the refinement levels
     o = np.random.default_rng(3).permutation(len(pl))
-    off, nodes, tof, s = run_split(engine, counts, [pl[i] for i in o], m[o], stride, max_dist, gates)
+    off, nodes, tof, s = run_tracks_split(engine, counts, [pl[i] for i in o], m[o], stride, max_dist, gates)
     assert (off == e_off).all() and (nodes == e_nodes).all() and (tof == e_tof).all() and s == ref.summary16(e_s)
     G, fs = 3, 3
     slot = [(f % G) * fs + f // G for f in range(F)]
@@ -133,7 +94,7 @@ def test_pair_order_slot_permutation_padding_and_frame_subset(engine):
     c_s[ids < 0] = 50
     pl_s = [(slot[a], slot[b]) for a, b in pl] + [(8, 0), (-1, -1)]
     m_s = np.concatenate([m, np.zeros((2, stride, 3), dtype=np.int32)])
-    off, nodes, tof, s = run_split(engine, c_s, pl_s, m_s, stride, max_dist, gates, frame_ids=ids, n_frames=F)
+    off, nodes, tof, s = run_tracks_split(engine, c_s, pl_s, m_s, stride, max_dist, gates, frame_ids=ids, n_frames=F)
     assert (off == e_off).all() and (nodes == e_nodes).all() and (tof == e_tof).all() and s == ref.summary16(e_s)
     sub = [1, 2, 4, 6]
     ids2 = -np.ones(G * fs, dtype=np.int32)
@@ -141,7 +102,7 @@ def test_pair_order_slot_permutation_padding_and_frame_subset(engine):
         ids2[slot[f]] = i
     keep = [p for p, (a, b) in enumerate(pl) if a in sub and b in sub]
     e2 = ref.arrays(counts[sub], [(sub.index(pl[p][0]), sub.index(pl[p][1])) for p in keep], m[keep], stride, max_dist, gates)
-    off, nodes, tof, s = run_split(engine, c_s, pl_s, m_s, stride, max_dist, gates, frame_ids=ids2, n_frames=len(sub))
+    off, nodes, tof, s = run_tracks_split(engine, c_s, pl_s, m_s, stride, max_dist, gates, frame_ids=ids2, n_frames=len(sub))
     assert (off == e2[0]).all() and (nodes == e2[1]).all() and (tof == e2[2]).all() and s == ref.summary16(e2[3])
 
 
@@ -151,10 +112,10 @@ def test_bench_size_recovers_the_tracks_of_the_giant_component(engine):
     ground-truth tracks -- pgx_tracks_dev's result at max_dist = 64 -- all of them at level 1."""
     F, K = 64, 4096
     counts, pl, m, perm, vis = constructed_job(F, K, 7)
-    _, _, _, p_s = run_plain(engine, counts, pl, m, K, 200)
+    _, _, _, p_s = run_tracks(engine, counts, pl, m, K, 200)
     assert p_s[2] >= 1 and p_s[6] > 1000
-    off, nodes, tof, s = run_split(engine, counts, pl, m, K, 200, [64])
-    t_off, t_nodes, t_tof, t_s = run_plain(engine, counts, pl, m, K, 64)
+    off, nodes, tof, s = run_tracks_split(engine, counts, pl, m, K, 200, [64])
+    t_off, t_nodes, t_tof, t_s = run_tracks(engine, counts, pl, m, K, 64)
     assert (off == t_off).all() and (nodes == t_nodes).all() and (tof == t_tof).all()
     nvis = vis.sum(0)
     assert s[0] == int((nvis >= 2).sum()) and s[1] == int(nvis[nvis >= 2].sum()) and s[2] == 0
@@ -162,7 +123,7 @@ def test_bench_size_recovers_the_tracks_of_the_giant_component(engine):
     e_off, e_nodes, e_tof, e_s = ref.arrays(counts, pl, m, K, 200, [64])
     assert (off == e_off).all() and (nodes == e_nodes).all() and (tof == e_tof).all() and s == ref.summary16(e_s)
     # four gates, as in the measurements; the levels below 64 find nothing left to split
-    off4, nodes4, tof4, s4 = run_split(engine, counts, pl, m, K, 200, [64, 48, 32, 16])
+    off4, nodes4, tof4, s4 = run_tracks_split(engine, counts, pl, m, K, 200, [64, 48, 32, 16])
     assert (off4 == off).all() and (nodes4 == nodes).all() and (tof4 == tof).all() and s4[:10] == s[:10] and s4[10:] == [0] * 6
 
 
@@ -171,22 +132,16 @@ def test_nn_lists_are_accepted(engine):
     rng = np.random.default_rng(8)
     base, _, _ = synth.true_match_descriptors(600, 8, 4, flip=0.0)
     F, stride = 6, 640
-    buf = np.zeros((F, stride, 8), dtype=np.uint32)
-    counts = np.zeros(F, dtype=np.int32)
+    descs = []
     for f in range(F):
         keep = rng.permutation(600)[: 450 + 30 * f]
         bits = np.unpackbits(base[keep].view(np.uint8), axis=1)
         bits ^= (rng.random(bits.shape) < 0.15).astype(np.uint8)
-        buf[f, :len(keep)] = np.packbits(bits, axis=1).view(np.uint32)
-        counts[f] = len(keep)
-    d_desc = torch.from_numpy(buf.view(np.int32)).to(DEV)
-    d_counts = torch.from_numpy(counts).to(DEV)
+        descs.append(np.packbits(bits, axis=1).view(np.uint32))
+    dev = upload(stride, 8, descs)
+    counts = dev[3]
     pl = [(i, j) for i in range(F) for j in range(i + 1, F)]
-    out = torch.full((len(pl), stride, 3), 77, dtype=torch.int32, device=DEV)
-    engine.match_nn_batch_dev(d_desc, d_counts, stride, 8, torch.tensor(pl, dtype=torch.int32, device=DEV), len(pl), out, 120,
-                              0.95, False)
-    engine.check_status()
-    m = out.cpu().numpy()
+    m = run_nn(engine, dev, stride, 8, pl, 120, 0.95, False)
     assert (m[..., 1] == -1).any() and (m[m[..., 1] == -1][:, 2] == INT_MAX).all()
     off, nodes, tof, s = check(engine, counts, pl, m, stride, 120, [80, 60, 40])
     assert s[0] > 100
@@ -204,12 +159,12 @@ def test_bad_arguments_and_duplicate_frames(engine):
     ids = np.arange(8, dtype=np.int32)
     ids[5] = 0
     nf = 8
-    d_m, d_c, d_pl, d_ids, (track_of, offsets, nodes) = _buffers(counts, pl, m, stride, ids, nf)
+    d_m, d_c, d_pl, d_ids, (track_of, offsets, nodes) = tracks_buffers(counts, pl, m, stride, ids, nf)
     engine.tracks_split_dev(d_m, d_c, d_pl, len(pl), 8, stride, nf, max_dist, gates, 2, track_of, offsets, nodes, s16,
                             d_frame_ids=d_ids)
     with pytest.raises(pg.ArgumentException):
         engine.check_status()
-    off, nodes, tof, s = run_split(engine, counts, pl, m, stride, max_dist, gates)
+    off, nodes, tof, s = run_tracks_split(engine, counts, pl, m, stride, max_dist, gates)
     assert as_lists(off, nodes) == exp
 
 

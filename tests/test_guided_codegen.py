@@ -6,7 +6,8 @@
 import numpy as np
 
 from codeobj import instructions, kernels, listing
-from guided_ref import NONE, loop_guided, ref_guided
+from guided_ref import loop_guided, ref_guided
+from knn_ref import NONE
 
 KERNELS = ("k_guided_slots", "k_guided_bucket", "k_guided_walk", "k_knn_col_init", "k_knn_col_finish")
 

@@ -8,6 +8,7 @@
   * the new kernels are in libpgx.so's code object with no private segment, no spills and at most 32 VGPRs.
 """
 import ctypes as C
+import functools
 import time
 
 import numpy as np
@@ -15,6 +16,7 @@ import pytest
 
 import photogrammetry_amd as pg
 import photogrammetry_amd._lib as L
+import geom_gpu
 import tracks_split_ref as ref
 from codeobj import kernels
 from oracle import tracks_np
@@ -22,21 +24,8 @@ from oracle import tracks_np
 INT_MAX = 2**31 - 1
 
 
-def random_case(seed, F, stride, dmax=60):
-    rng = np.random.default_rng(seed)
-    counts = rng.integers(0, stride + 1, F).astype(np.int32)
-    counts[rng.integers(0, F)] = 0
-    pl = [(a, b) for a in range(F) for b in range(F) if a != b and rng.random() < 0.5]
-    m = np.zeros((len(pl), stride, 3), dtype=np.int32)
-    m[..., 0] = rng.integers(0, stride, m.shape[:2])
-    m[..., 1] = rng.integers(-1, stride, m.shape[:2])          # -1: the rejected rows of NN lists
-    m[..., 2] = rng.integers(0, dmax, m.shape[:2])
-    m[rng.random(m.shape[:2]) < 0.1] = [0, 0, INT_MAX]
-    return counts, pl, m
-
-
-def lists_of(offsets, nodes):
-    return [[(int(f), int(k)) for f, k in nodes[offsets[t]:offsets[t + 1]]] for t in range(len(offsets) - 1)]
+# geom_gpu's lists with sparser pairs and with the rejected rows of NN lists (k2 = -1)
+random_case = functools.partial(geom_gpu.random_case, p_pair=0.5, k2_lo=-1)
 
 
 def check_all(counts, pl, m, stride, max_dist, gates, min_len):
@@ -44,7 +33,7 @@ def check_all(counts, pl, m, stride, max_dist, gates, min_len):
     b = ref.sequential(counts, pl, m, max_dist, gates, min_len)
     assert a[0] == b[0] and a[2] == b[2] and (a[1] == b[1]).all()
     off, nodes, tof, s = ref.arrays(counts, pl, m, stride, max_dist, gates, min_len)
-    assert lists_of(off, nodes) == a[0] and s == a[2]
+    assert geom_gpu.as_lists(off, nodes) == a[0] and s == a[2]
     w = a[1].shape[1]
     assert (tof[:, :w] == a[1]).all() and (tof[:, w:] == -1).all()
     assert sum(s["per_level"]) == s["n_nodes"] and len(s["per_level"]) == len(gates) + 1

@@ -17,17 +17,10 @@ import torch
 
 sys.path.insert(0, os.path.abspath(os.path.join(os.path.dirname(__file__), "..")))
 import photogrammetry_amd as pg
+from photogrammetry_amd.synth import fundamental_from_pose, rot_y
 
 W, H = 1920, 1080
 K = np.array([[1000.0, 0, W / 2], [0, 1000.0, H / 2], [0, 0, 1]])
-
-
-def rot_y(a):
-    return np.array([[np.cos(a), 0, np.sin(a)], [0, 1, 0], [-np.sin(a), 0, np.cos(a)]])
-
-
-def skew(t):
-    return np.array([[0, -t[2], t[1]], [t[2], 0, -t[0]], [-t[1], t[0], 0]])
 
 
 def scene(F, N, words, flip, seed):
@@ -59,10 +52,7 @@ def true_F(poses, a, b):
     """h_a^T F h_b = 0 (include/pgx.h), unit Frobenius norm."""
     (Ra, ta), (Rb, tb) = poses[a], poses[b]
     R = Rb @ Ra.T
-    t = tb - R @ ta
-    Ki = np.linalg.inv(K)
-    Fm = (Ki.T @ skew(t) @ R @ Ki).T
-    return (Fm / np.linalg.norm(Fm)).astype(np.float32).reshape(9)
+    return fundamental_from_pose(K, R, tb - R @ ta).reshape(9)
 
 
 def main():
