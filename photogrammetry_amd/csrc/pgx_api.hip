@@ -3,6 +3,7 @@
 // entry points.  All compute is in the k_*.hip kernels; there is no CPU fallback anywhere:
 // every entry point needs a working gfx950 device and fails with PGX_E_HIP without one.
 #include "pgx_trackgraph.h"
+#include "pgx_brief_plan.h"
 
 #include <atomic>
 #include <cmath>
@@ -178,7 +179,7 @@ int pgx_enqueue_detect(pgx_ctx *c, const uint16_t *d_rgba, int F, int W, int H, 
     {
         ProfScope ps(c, "brief");
         pgx_launch_brief(c->stream, gray, F, W, H, c->ws_rawxy.as<uint32_t>(), c->ws_rawscore.as<int32_t>(), raw_cap,
-                         c->ws_order.as<uint32_t>(), c->ws_nkept.as<int32_t>(), kp_eff, c->d_pairs.as<int32_t>(), c->P,
+                         c->ws_order.as<uint32_t>(), c->ws_nkept.as<int32_t>(), kp_eff, c->d_pairs.as<int32_t>(), c->d_plan.as<int32_t>(), c->P,
                          d_kp, d_desc, d_counts, cap);
     }
     HIPCHK(c, hipEventRecord(c->ev_stage[PGX_STAGE_DETECT], c->stream));
@@ -347,7 +348,7 @@ void pgx_ctx_destroy(pgx_ctx *c)
     for (auto &kv : c->prof)
         for (auto &ev : kv.second.pending) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
     for (hipEvent_t ev : c->ev_pool) (void)hipEventDestroy(ev);
-    DevBuf *bufs[] = {&c->d_pairs, &c->d_map, &c->ws_gray, &c->ws_seg, &c->ws_segoff, &c->ws_nraw, &c->ws_rawxy,
+    DevBuf *bufs[] = {&c->d_pairs, &c->d_plan, &c->d_map, &c->ws_gray, &c->ws_seg, &c->ws_segoff, &c->ws_nraw, &c->ws_rawxy,
                       &c->ws_rawscore, &c->ws_nms, &c->ws_order, &c->ws_nkept, &c->st_a, &c->st_b, &c->st_c,
                       &c->st_d, &c->st_e, &c->st_f, &c->ws_pose, &c->ws_tracks, &c->ws_tracks_split, &c->ws_agree, &c->ws_matchn[0], &c->ws_matchn[1], &c->ws_matchn[2], &c->ws_knn, &c->ws_guided, &c->ws_tri, &c->ws_ba, &c->ws_reg};
     for (DevBuf *b : bufs) b->release();
@@ -448,6 +449,12 @@ int pgx_set_brief_pairs(pgx_ctx *c, const int32_t *pairs, int P)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, c->d_pairs.ensure((size_t)P * 16));
     HIPCHK(c, hipMemcpy(c->d_pairs.p, pairs, (size_t)P * 16, hipMemcpyHostToDevice));
+    if (P == PGX_PLAN_PAIRS) { // brief_256 reads the table through its row-sorted sample plan (pgx_brief_plan.h)
+        int32_t plan[PGX_PLAN_WORDS];
+        pgx_build_brief_plan(pairs, plan);
+        HIPCHK(c, c->d_plan.ensure(sizeof plan));
+        HIPCHK(c, hipMemcpy(c->d_plan.p, plan, sizeof plan, hipMemcpyHostToDevice));
+    }
     c->P = P; c->words = (P + 31) / 32; c->pairs_set = true;
     return PGX_OK;
 }
@@ -604,7 +611,7 @@ int pgx_brief(pgx_ctx *c, const float *gray, int W, int H, const pgx_keypoint *k
     HIPCHK(c, hipMemcpyAsync(c->st_a.p, gray, npix * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->st_b.p, kps, (size_t)n * sizeof(pgx_keypoint), hipMemcpyHostToDevice, c->stream));
     pgx_launch_brief_list(c->stream, c->st_a.as<float>(), W, H, c->st_b.as<pgx_keypoint>(), n,
-                          c->d_pairs.as<int32_t>(), c->P, c->st_c.as<uint32_t>());
+                          c->d_pairs.as<int32_t>(), c->d_plan.as<int32_t>(), c->P, c->st_c.as<uint32_t>());
     HIPCHK(c, hipMemcpyAsync(desc_out, c->st_c.p, (size_t)n * c->words * 4, hipMemcpyDeviceToHost, c->stream));
     return sync_status(c);
 }

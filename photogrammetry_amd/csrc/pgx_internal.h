@@ -104,6 +104,7 @@ struct pgx_ctx {
     int P = 0, words = 0;
     bool pairs_set = false;
     DevBuf d_pairs;
+    DevBuf d_plan; // P == 256 only: the table's row-sorted sample plan (pgx_brief_plan.h), rebuilt with every table
     int mapW = 0, mapH = 0;
     bool map_set = false;
     DevBuf d_map;
@@ -255,11 +256,11 @@ hipError_t pgx_launch_nms_sync(hipStream_t s, const uint32_t *raw_xy, const int3
 void pgx_launch_brief(hipStream_t s, const float *gray, int F, int W, int H,
                       const uint32_t *raw_xy, const int32_t *raw_score, int raw_cap,
                       const uint32_t *order, const int32_t *n_kept, int kp_cap /* order stride and list bound */,
-                      const int32_t *pairs, int P,
+                      const int32_t *pairs, const int32_t *plan /* pgx_brief_plan.h; read when P == 256 */, int P,
                       pgx_keypoint *kp_out, uint32_t *desc_out, int32_t *counts_out, int out_stride /* slots per frame in kp_out/desc_out */);
 // descriptors for an explicit keypoint list (stage API)
 void pgx_launch_brief_list(hipStream_t s, const float *gray, int W, int H, const pgx_keypoint *kps, int n,
-                           const int32_t *pairs, int P, uint32_t *desc_out);
+                           const int32_t *pairs, const int32_t *plan, int P, uint32_t *desc_out);
 
 // k_pose.hip
 size_t pgx_pose_ws_bytes(int M, int n_samples);
