@@ -93,8 +93,11 @@ int pgx_get_dewarp_map(pgx_ctx *ctx, int32_t *uv_out, int W, int H);
 int pgx_set_brief_pairs(pgx_ctx *ctx, const int32_t *pairs, int P);
 /* KeypointDetectionOptions.Threshold, RedundantKeypointEliminationOptions.SuppressionRadius. */
 int pgx_set_detect_params(pgx_ctx *ctx, float threshold, int suppression_radius);
-/* Per-frame limits of the fused detect path.  max_raw_per_frame: raw FAST hits kept for NMS (more raise
- * PGX_E_CAPACITY).  max_keypoints_per_frame: survivor LIMIT -- a frame's list is cut to its first
+/* Per-frame limits of the fused detect path.  max_raw_per_frame: raw FAST hits kept for NMS.  A frame with more raises
+ * PGX_E_CAPACITY at the next status check (which clears it); its d_nraw is still the true total, and its lists are those
+ * of the first max_raw_per_frame hits in raster order (NMS, the survivors' order and the descriptors as if the later hits
+ * did not exist), at every radius; the other frames of the call are unaffected, and rows at and beyond counts[f] are
+ * not written.  max_keypoints_per_frame: survivor LIMIT -- a frame's list is cut to its first
  * max_keypoints_per_frame entries in NMS order without an error (a harness-side truncation: the reference has
  * no cap; default 2^20 = none).  Survivors beyond a call's own `capacity` still raise
  * PGX_E_CAPACITY. */

@@ -36,6 +36,7 @@ namespace {
 constexpr int NT = 1024;
 constexpr int WIDE_ROUNDS = 8; // champion path: 3..10 measure the same on 128 1080p frames (r = 16); 8..10 are best on 4K frames at r = 30
 constexpr uint32_t SORT_LDS_MAX = 16384; // u64 keys -> 128 KiB
+constexpr uint32_t MT_SORT_LDS = 8192;   // the mask-round tail's (k_nmsm_tail): u64 keys -> 64 KiB
 
 struct NmsLayout {
     int gw, gh, cs, ncell;
@@ -81,7 +82,8 @@ __host__ __device__ inline NmsLayout nms_layout(int W, int H, int radius, int n_
         const size_t npc = (size_t)L.cgw * (L.gh + 2 * L.R);
         L.off_cellstart = L.off_cellfill = L.off_cellund = L.off_rec = 0;
         L.off_counters = take(64);
-        L.off_accflag = take(n_cap > (1 << 20) ? (size_t)n_cap : 0); // only the output order of > 1M raw hits uses it
+        // only tail_order's per-score compaction uses it: k_nmsm_tail leaves the rank bitmaps above 64 * MT_SORT_LDS raw hits
+        L.off_accflag = take(n_cap > (int)(64 * MT_SORT_LDS) ? (size_t)n_cap : 0);
         L.off_alive = take(npc * 8);
         L.off_planes = take(npc * 24);
         L.off_champ = take(npc * 4);
@@ -1536,7 +1538,6 @@ __global__ __launch_bounds__(NT) void k_nms_tail(const int32_t *raw_score_all,
 // workgroups waiting: the whole detect chain of a second job in flight stalled here until that launch had drained (2.5 ms
 // instead of 0.1).  The rounds work on a few hundred listed cells, the order pass on 15 k bitmap words: alone it is as fast.
 constexpr int MT_NT = 512;
-constexpr uint32_t MT_SORT_LDS = 8192; // u64 keys -> 64 KiB
 template <int RR>
 __global__ __launch_bounds__(MT_NT) void k_nmsm_tail(const int32_t *raw_score_all, const int32_t *__restrict__ n_raw_all, int n_cap,
                                                   NmsLayout L, int radius, unsigned char *ws_all, size_t ws_stride,

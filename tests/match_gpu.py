@@ -91,13 +91,41 @@ def run_match(engine, descs, pl, stride, max_count=None, sentinel=-7, wait=True)
     return d_out.cpu().numpy()
 
 
-def oracle_detect(frame, dmap, pairs, T, radius, cap):
-    """dewarp (dmap or None) -> gray -> detect -> NMS -> BRIEF by the oracle -> (kept keypoints, descriptors, raw hits)"""
+def oracle_detect(frame, dmap, pairs, T, radius, cap, raw_cap=None):
+    """dewarp (dmap or None) -> gray -> detect -> NMS -> BRIEF by the oracle -> (kept keypoints, descriptors, raw hits).
+    raw_cap: pgx_set_capacity's max_raw_per_frame -- NMS sees the first raw_cap hits in raster order; the count is the true one."""
     src = cref.apply_distortion(frame, dmap) if dmap is not None else frame
     g = cref.gray(src)
     raw = cref.detect(g, T)
+    n_raw = len(raw)
+    raw = raw[:raw_cap]
     kept = raw[cref.nms(raw, radius)][:cap]
-    return kept, cref.brief(g, np.stack([kept["x"], kept["y"]], 1), pairs), len(raw)
+    return kept, cref.brief(g, np.stack([kept["x"], kept["y"]], 1), pairs), n_raw
+
+
+def run_detect(engine, frames, cap, sentinel=-7):
+    """pgx_detect_batch_dev on host frames [F][H][W][4] with the engine's current parameters, nothing synchronised: the caller's
+    check_status does that -> device (d_kp [F][cap][4], d_desc [F][cap][8], d_counts [F], d_nraw [F]), sentinel-filled"""
+    F, H, W = frames.shape[:3]
+    d_frames = torch.from_numpy(frames).to(DEV)
+    out = (torch.full((F, cap, 4), sentinel, **I32), torch.full((F, cap, 8), sentinel, **I32),
+           torch.full((F,), sentinel, **I32), torch.full((F,), sentinel, **I32))
+    torch.cuda.synchronize()
+    engine.detect_batch_dev(d_frames, F, W, H, *out, cap)
+    run_detect.keepalive = d_frames
+    return out
+
+
+def detect_equal(out, f, kept, edesc, n_raw, sentinel=-7):
+    """frame f of run_detect's buffers against oracle_detect's triple, every field exact; the rows behind the list untouched"""
+    kp, desc = out[0][f].cpu().numpy(), out[1][f].cpu().numpy()
+    n = len(kept)
+    assert int(out[3][f]) == n_raw and int(out[2][f]) == n, (f, int(out[3][f]), n_raw, int(out[2][f]), n)
+    assert (kp[:n, 0] == kept["x"]).all() and (kp[:n, 1] == kept["y"]).all(), f
+    assert (kp[:n, 2] == kept["fast_score"]).all(), f
+    assert kp[:n, 3].view(np.float32).tobytes() == kept["value"].tobytes(), f
+    assert (desc[:n].view(np.uint32) == edesc).all(), f
+    assert (kp[n:] == sentinel).all() and (desc[n:] == sentinel).all(), f
 
 
 def pairs_equal(got, exp):

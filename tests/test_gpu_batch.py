@@ -181,8 +181,9 @@ def test_profile_hooks_and_stats(engine):
 @pytest.mark.parametrize("radius", [16, 20, 25, 45, 100])
 def test_detect_full_size_frames_vs_oracle(engine, radius):
     """The bench workload's frame shape: 1920x1080, ~1e5 raw hits per frame, dewarp map on, two frames per launch
-    (one of them a shifted copy), every stage compared bit-exactly with the oracle.  The radii cover every cell
-    size / reach combination of the NMS champion rounds (8 px: reach 2 and 3; 16 px; 32 px; 64 px)."""
+    (one of them a shifted copy), every stage compared bit-exactly with the oracle.  The radii run the NMS champion rounds at
+    (cell size, reach) = (8, 2), (8, 3), (16, 2), (32, 2) and (64, 2); reach 3 at 16-, 32- and 64-px cells, both sides of every
+    switch radius and the other limits of the path are tests/test_gpu_nms_limits.py's."""
     W, H, CAP, RAW = 1920, 1080, 16384, 1 << 18
     T = np.float32(0.1)
     base = synth.make_frame(W, H, seed=11, n_shapes=12000)
