@@ -493,6 +493,7 @@ class Engine:
                                                 _dptr(d_out_all)))
 
     def debug_counters(self):
+        """The eight diagnostic counters of the match tail, summed over the calls since the last read: reading clears them."""
         out = np.zeros(8, dtype=np.int64)
         self._chk(self._L.pgx_debug_counters(self._h, _ptr(out)))
         return out.tolist()

@@ -73,6 +73,56 @@ def true_match_descriptors(n, words, seed, flip=0.15):
     return d1, np.ascontiguousarray(d2), perm
 
 
+def flip_bits(rng, d, k):
+    """d (uint32 [n][words]) with k (an int, or [n] ints) distinct random bits of every row flipped"""
+    bits = np.unpackbits(np.ascontiguousarray(d).view(np.uint8), axis=1)
+    rank = rng.random(bits.shape).argsort(1).argsort(1)
+    mask = rank < np.broadcast_to(np.asarray(k), (len(d),))[:, None]
+    return np.ascontiguousarray(np.packbits(bits ^ mask.astype(np.uint8), axis=1).view(np.uint32))
+
+
+def far_descriptors(n1, n2, lo, hi, seed):
+    """(set1, set2) of 256-bit descriptors in which every row's nearest column and every column's nearest row is FAR: rows are
+    one prototype with every bit flipped at rate q, column j is the bit-complement of row perm[j] with 1..3 more bits
+    flipped, so distance(i, j) = 256 - hamming(row i, copy j) and the nearest column is the least similar copy.  q is chosen
+    so that the expected largest of n hamming distances (mean + sqrt(2 ln n) sd) is 256 - (lo + hi) / 2; callers check the
+    range they need.  lo == hi pins EVERY distance at that value (255, 256, ...): identical rows, columns their complement
+    with 256 - lo random bits flipped back, so every distance ties as well."""
+    rng = np.random.default_rng(seed)
+    proto = rng.integers(0, 2**32, size=(1, 8), dtype=np.uint32)
+    if lo == hi:
+        cols = ~np.repeat(proto, n2, axis=0)
+        return np.repeat(proto, n1, axis=0), (flip_bits(rng, cols, 256 - lo) if lo < 256 else cols)
+    n, want = max(n1, n2), 256.0 - (lo + hi) / 2.0
+    qs = np.linspace(0.005, 0.5, 400)
+    p = 2 * qs * (1 - qs)
+    q = qs[np.argmin(np.abs(256 * p + np.sqrt(2 * np.log(n) * 256 * p * (1 - p)) - want))]
+    bits = np.unpackbits(np.repeat(proto, n, axis=0).view(np.uint8), axis=1) ^ (rng.random((n, 256)) < q).astype(np.uint8)
+    rows = np.ascontiguousarray(np.packbits(bits, axis=1).view(np.uint32))
+    perm = rng.permutation(n)[:n2]
+    return rows[:n1].copy(), ~flip_bits(rng, rows[perm], rng.integers(1, 4, n2))
+
+
+def repeat_blocks(d, period):
+    """In place: entry j + period holds the descriptor of entry j, for j in every other block of `period` entries (blocks
+    0, 2, 4, ... are copied over blocks 1, 3, 5, ...; the last copy is cut at the end of the set)."""
+    for b in range(0, len(d) - period, 2 * period):
+        m = min(period, len(d) - b - period)
+        d[b + period:b + period + m] = d[b:b + m]
+    return d
+
+
+def tiled_ties(n1, n2, period, seed, row_period=96):
+    """(set1, set2) whose minima tie across the blockings of a matcher: column j + period repeats column j (repeat_blocks),
+    every row is a copy of a random column with 0..2 bits flipped -- its minimum is attained at that column and at its repeat
+    -- and row i + row_period repeats row i in the same way, so a column's minimum ties between rows as well.  Half of the
+    columns stay distinct, so mutual-nearest rounds still take most rows."""
+    rng = np.random.default_rng(seed)
+    cols = repeat_blocks(rng.integers(0, 2**32, size=(n2, 8), dtype=np.uint32), period)
+    rows = flip_bits(rng, cols[rng.integers(0, n2, n1)], rng.integers(0, 3, n1))
+    return repeat_blocks(rows, row_period), cols
+
+
 def rot_y(a):
     return np.array([[np.cos(a), 0, np.sin(a)], [0, 1, 0], [-np.sin(a), 0, np.cos(a)]])
 
