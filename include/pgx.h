@@ -91,6 +91,34 @@ int pgx_get_dewarp_map(pgx_ctx *ctx, int32_t *uv_out, int W, int H);
 /* KeypointDetection ctor's _gaussianKeypairs (KeypointDetection.cs:35-39): host int32 [P][4] =
  * (x1, y1, x2, y2).  The table is an INPUT because the reference draws it unseeded. */
 int pgx_set_brief_pairs(pgx_ctx *ctx, const int32_t *pairs, int P);
+/* Steered BRIEF: rotation-invariant descriptors by patch orientation (k_steer.hip).  Not in the C# reference, whose BRIEF
+ * applies one table upright at every keypoint; this is ORB's remedy for camera roll, stated in integers so that the mode is
+ * bit-identical to a CPU restatement (tests/steered_ref.py) with no tolerance anywhere.  Off by default; with it off nothing
+ * changes.
+ *
+ * A steering table has B directions, with 4 <= B <= 64 and B % 4 == 0.  It holds:
+ *   - dirs int32 [B][2] = (cx, cy), every component in [-32767, 32767];
+ *   - pairs_rot int32 [B][P][4] in the layout of pgx_set_brief_pairs, with P = the context's current P;
+ *   - a disc radius R, 1 <= R <= 31.
+ * Steps 1-4 apply to a keypoint at (x, y) on a float32 grey image:
+ *   1. q(g).  NaN -> 0; clamp to [0, 1]; ONE float32 multiplication by 65535.0f; round to nearest even; convert to int.  In
+ *      numpy: np.rint(np.float32(clipped) * np.float32(65535)).  For the pipeline's own grey (sum / 196605) this is the channel
+ *      mean in 16 bits.
+ *   2. Moments.  m10 = sum of dx * q(pixel(x+dx, y+dy)) and m01 = sum of dy * q(...), over all integer (dx, dy) with
+ *      dx^2 + dy^2 <= R^2.  A pixel outside the image contributes 0.  Each moment is below 2^31 in magnitude for R <= 31: the
+ *      sum over dx > 0 of dx * 65535 on the R = 31 disc is 1 290 253 080.  Every partial sum lies between the negative part
+ *      and the positive part of the total.  int32 accumulation in any order is therefore exact.
+ *   3. Direction.  s_k = (int64)m10 * dirs[k][0] + (int64)m01 * dirs[k][1], and |s_k| < 2^46.  bin = the smallest k with the
+ *      largest s_k.  A flat patch, with all s_k = 0, gets bin 0.
+ *   4. Descriptor.  Exactly the existing rule (bit order, the "either end point outside -> bit 0" rule, the < on the original
+ *      float32 values) applied with the table pairs_rot[bin].
+ *
+ * pgx_set_brief_steering uploads the tables and, when P == 256, builds one row-sorted sample plan per direction.
+ * pairs_rot == NULL turns the mode off.  It needs pgx_set_brief_pairs first (PGX_E_NOT_CONFIGURED), and a later
+ * pgx_set_brief_pairs turns the mode off, because the turned tables belong to the old table.  Bad B, radius or dirs:
+ * PGX_E_BADARG.  With the mode on, pgx_brief, pgx_detect, pgx_detect_batch_dev and pgx_sequence_step_dev write steered
+ * descriptors; keypoints, counts and order are unchanged. */
+int pgx_set_brief_steering(pgx_ctx *ctx, const int32_t *pairs_rot, const int32_t *dirs, int B, int radius);
 /* KeypointDetectionOptions.Threshold, RedundantKeypointEliminationOptions.SuppressionRadius. */
 int pgx_set_detect_params(pgx_ctx *ctx, float threshold, int suppression_radius);
 /* Per-frame limits of the fused detect path.  max_raw_per_frame: raw FAST hits kept for NMS.  A frame with more raises
@@ -122,6 +150,10 @@ int pgx_fast(pgx_ctx *ctx, const float *gray, int W, int H,
 /* Keypoint.GetBriefDescriptor (Keypoint.cs:29-57) for n keypoints -> desc [n][ceil(P/32)]. */
 int pgx_brief(pgx_ctx *ctx, const float *gray, int W, int H,
               const pgx_keypoint *kps, int n, uint32_t *desc_out);
+/* Steps 1-3 of steered BRIEF for n keypoints -> bins_out [n] (not in the C# reference); PGX_E_NOT_CONFIGURED when the mode
+ * is off.  A keypoint may lie anywhere: pixels outside the image contribute 0. */
+int pgx_orient(pgx_ctx *ctx, const float *gray, int W, int H,
+               const pgx_keypoint *kps, int n, int32_t *bins_out);
 /* RedundantKeypointEliminator.EliminateRedundantKeypoints (:16-35): order_out[k] = index into
  * kps of the k-th accepted keypoint; *n_out = accepted count (order_out holds n entries). */
 int pgx_nms(pgx_ctx *ctx, const pgx_keypoint *kps, int n, int W, int H,
@@ -160,6 +192,11 @@ int pgx_detect(pgx_ctx *ctx, const uint16_t *rgba64, int W, int H,
 int pgx_detect_batch_dev(pgx_ctx *ctx, const uint16_t *d_rgba64, int F, int W, int H,
                          pgx_keypoint *d_kp, uint32_t *d_desc, int32_t *d_counts,
                          int32_t *d_nraw, int capacity);
+/* The same chain in steered mode (PGX_E_NOT_CONFIGURED when it is off); it also writes each survivor's direction bin,
+ * d_bins [F][capacity].  Not in the C# reference. */
+int pgx_detect_batch_steered_dev(pgx_ctx *ctx, const uint16_t *d_rgba64, int F, int W, int H,
+                                 pgx_keypoint *d_kp, uint32_t *d_desc, int32_t *d_counts,
+                                 int32_t *d_nraw, int capacity, int32_t *d_bins);
 /* M image pairs: d_pairlist [M][2] = (frame_a, frame_b) indexes descriptor sets
  * d_desc [F][stride][words] with d_counts [F].  d_out [M][stride]: the first counts[a] entries of
  * row m are the reference's match list for (a, b).  Pairs with counts[b] == 0 < counts[a] raise
@@ -619,6 +656,13 @@ int pgx_debug_counters(pgx_ctx *ctx, int64_t *out8);
 /* ---- host-side helpers (no GPU work) -------------------------------------------------- */
 /* Utils.NextGaussianPair (Utils.cs:14-38) on a seeded splitmix64 stream; out [P][4]. */
 int pgx_make_brief_pairs(uint64_t seed, int sigma, int P, int32_t *out);
+/* The steering table of a pair table (steered BRIEF above; not in the C# reference): pairs_rot_out [B][P][4], dirs_out [B][2].
+ * For k < B / 4, theta = 2 pi k / B in double: dirs[k] = (rint(16384 cos theta), rint(16384 sin theta)), and every end point
+ * (dx, dy) becomes (rint(c dx - s dy), rint(s dx + c dy)), in image coordinates (x right, y down).  For k >= B / 4 the
+ * entries are the EXACT quarter turn (x, y) -> (-y, x) of direction k - B / 4, both end points and dirs; no libm is used
+ * again.  The quarter-turn relation is what makes the 90-degree invariance exact.  Direction 0 is the input table.  Input
+ * offsets beyond +-2^20, B outside {4, 8, ..., 64}: PGX_E_BADARG. */
+int pgx_make_steering(const int32_t *pairs, int P, int B, int32_t *pairs_rot_out, int32_t *dirs_out);
 /* DeWarp.GetDistortionMatrix (DeWarp.cs:39-107) in float64 on the host; out [H][W][2].
  * MathNet's Cubic.RealRoots is restated from its published algorithm (parity unpinned). */
 int pgx_build_dewarp_map(int W, int H, const double *coeffs, int ncoeffs, int32_t *out);

@@ -39,6 +39,9 @@ internal static unsafe class PgxNative
     [DllImport(Lib)] public static extern int pgx_set_dewarp_coeffs(IntPtr ctx, int w, int h, double* coeffs, int ncoeffs);
     [DllImport(Lib)] public static extern int pgx_get_dewarp_map(IntPtr ctx, int* uvOut, int w, int h);
     [DllImport(Lib)] public static extern int pgx_set_brief_pairs(IntPtr ctx, int* pairs, int p);
+    // steered BRIEF (not in the reference): pairsRot [b][p][4] and dirs [b][2] from pgx_make_steering; pairsRot = null turns it off
+    [DllImport(Lib)] public static extern int pgx_set_brief_steering(IntPtr ctx, int* pairsRot, int* dirs, int b, int radius);
+    [DllImport(Lib)] public static extern int pgx_make_steering(int* pairs, int p, int b, int* pairsRotOut, int* dirsOut);
     [DllImport(Lib)] public static extern int pgx_set_detect_params(IntPtr ctx, float threshold, int suppressionRadius);
     [DllImport(Lib)] public static extern int pgx_set_capacity(IntPtr ctx, int maxRaw, int maxKeypoints);
     [DllImport(Lib)] public static extern int pgx_set_source_format(IntPtr ctx, int format); // 0 = Rgba64, 1 = Rgba32 bytes (widened x257 on the device)
@@ -49,6 +52,7 @@ internal static unsafe class PgxNative
     [DllImport(Lib)] public static extern int pgx_gray(IntPtr ctx, ushort* rgba64, int w, int h, float* outGray);
     [DllImport(Lib)] public static extern int pgx_fast(IntPtr ctx, float* gray, int w, int h, PgxKeypoint* o, int capacity, out int n);
     [DllImport(Lib)] public static extern int pgx_brief(IntPtr ctx, float* gray, int w, int h, PgxKeypoint* kps, int n, uint* desc);
+    [DllImport(Lib)] public static extern int pgx_orient(IntPtr ctx, float* gray, int w, int h, PgxKeypoint* kps, int n, int* bins);
     [DllImport(Lib)] public static extern int pgx_nms(IntPtr ctx, PgxKeypoint* kps, int n, int w, int h, int* order, out int nOut);
     [DllImport(Lib)] public static extern int pgx_match(IntPtr ctx, uint* d1, int n1, uint* d2, int n2, int words, PgxPair* o);
     // many image pairs, managed arrays, one call: descs[f] -> frame f's descriptors, pairList [m][2], lists back to back in `o`
@@ -67,6 +71,9 @@ internal static unsafe class PgxNative
     // batched, device-resident entry points and the multi-GPU / pose / track-graph additions (include/pgx.h)
     [DllImport(Lib)] public static extern int pgx_detect_batch_dev(IntPtr ctx, void* dRgba64, int f, int w, int h, void* dKp, void* dDesc,
                                                                    void* dCounts, void* dNraw, int capacity);
+    [DllImport(Lib)] public static extern int pgx_detect_batch_steered_dev(IntPtr ctx, void* dRgba64, int f, int w, int h, void* dKp,
+                                                                           void* dDesc, void* dCounts, void* dNraw, int capacity,
+                                                                           void* dBins);
     [DllImport(Lib)] public static extern int pgx_match_batch_dev(IntPtr ctx, void* dDesc, void* dCounts, int stride, int words,
                                                                   void* dPairlist, int m, int maxCount, void* dOut);
     [DllImport(Lib)] public static extern int pgx_knn_batch_dev(IntPtr ctx, void* dDesc, void* dCounts, int stride, int words,

@@ -35,6 +35,7 @@ EXPORTS = [
     "pgx_triangulate_tracks_dev", "pgx_triangulate_tracks",
     "pgx_bundle_adjust_dev", "pgx_bundle_adjust",
     "pgx_register_frames_dev", "pgx_register_frames",
+    "pgx_set_brief_steering", "pgx_orient", "pgx_detect_batch_steered_dev", "pgx_make_steering",
 ]
 
 

@@ -140,6 +140,19 @@ class Engine:
         self.P = p.shape[0]
         self.words = (self.P + 31) // 32
 
+    def set_brief_steering(self, pairs_rot, dirs=None, radius=15):
+        """Steered BRIEF (pgx.h): pairs_rot [B][P][4] and dirs [B][2] from make_steering, disc radius of the orientation
+        pass.  pairs_rot=None turns the mode off."""
+        if pairs_rot is None:
+            self._chk(self._L.pgx_set_brief_steering(self._h, None, None, 0, 0))
+            return
+        t = np.ascontiguousarray(pairs_rot, dtype=np.int32)
+        d = np.ascontiguousarray(dirs, dtype=np.int32).reshape(-1, 2)
+        B = d.shape[0]
+        if 4 <= B <= 64 and B % 4 == 0 and t.size != B * self.P * 4:   # the library reads B x P x 4 values; it rejects any other B itself
+            raise ValueError("pairs_rot has %d values; %d directions of the current table need %d" % (t.size, B, B * self.P * 4))
+        self._chk(self._L.pgx_set_brief_steering(self._h, _ptr(t), _ptr(d), int(B), int(radius)))
+
     def set_detect_params(self, threshold, suppression_radius):
         self._chk(self._L.pgx_set_detect_params(self._h, C.c_float(threshold), int(suppression_radius)))
 
@@ -189,6 +202,14 @@ class Engine:
         k = np.ascontiguousarray(kps, dtype=KEYPOINT_DTYPE)
         out = np.zeros((len(k), self.words), dtype=np.uint32)
         self._chk(self._L.pgx_brief(self._h, _ptr(g), g.shape[1], g.shape[0], _ptr(k), len(k), _ptr(out)))
+        return out
+
+    def orient(self, gray, kps):
+        """The direction bin of every keypoint (steered mode on), int32 [n]."""
+        g = np.ascontiguousarray(gray, dtype=np.float32)
+        k = np.ascontiguousarray(kps, dtype=KEYPOINT_DTYPE)
+        out = np.zeros(len(k), dtype=np.int32)
+        self._chk(self._L.pgx_orient(self._h, _ptr(g), g.shape[1], g.shape[0], _ptr(k), len(k), _ptr(out)))
         return out
 
     def nms(self, kps, W, H):
@@ -243,6 +264,11 @@ class Engine:
     def detect_batch_dev(self, d_rgba64, F, W, H, d_kp, d_desc, d_counts, d_nraw, capacity):
         self._chk(self._L.pgx_detect_batch_dev(self._h, _dptr(d_rgba64), int(F), int(W), int(H), _dptr(d_kp),
                                                _dptr(d_desc), _dptr(d_counts), _dptr(d_nraw), int(capacity)))
+
+    def detect_batch_steered_dev(self, d_rgba64, F, W, H, d_kp, d_desc, d_counts, d_nraw, capacity, d_bins):
+        self._chk(self._L.pgx_detect_batch_steered_dev(self._h, _dptr(d_rgba64), int(F), int(W), int(H), _dptr(d_kp),
+                                                       _dptr(d_desc), _dptr(d_counts), _dptr(d_nraw), int(capacity),
+                                                       _dptr(d_bins)))
 
     def match_batch_dev(self, d_desc, d_counts, stride, words, d_pairlist, M, d_out, max_count=None):
         self._chk(self._L.pgx_match_batch_dev(self._h, _dptr(d_desc), _dptr(d_counts), int(stride), int(words),
@@ -581,6 +607,18 @@ def make_brief_pairs(seed, sigma, P):
     if rc != PGX_OK:
         raise PgxError(rc, "pgx_make_brief_pairs")
     return out
+
+
+def make_steering(pairs, B):
+    """The steering table of a pair table (pgx_make_steering) -> (pairs_rot int32 [B][P][4], dirs int32 [B][2])."""
+    p = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 4)
+    B = int(B)
+    rot = np.zeros((max(B, 0), p.shape[0], 4), dtype=np.int32)
+    dirs = np.zeros((max(B, 0), 2), dtype=np.int32)
+    rc = _lib.lib().pgx_make_steering(_ptr(p), p.shape[0], B, _ptr(rot), _ptr(dirs))
+    if rc != PGX_OK:
+        raise ArgumentException(rc, "B must be a multiple of 4 in [4, 64] and every offset within +-2^20")
+    return rot, dirs
 
 
 def build_dewarp_map(W, H, coeffs):

@@ -143,9 +143,18 @@ int pgx_prepare_detect(pgx_ctx *c, int F, int W, int H, int cap)
     return PGX_OK;
 }
 
-// detect chain on device-resident frames (enqueue only)
-int pgx_enqueue_detect(pgx_ctx *c, const uint16_t *d_rgba, int F, int W, int H, pgx_keypoint *d_kp, uint32_t *d_desc,
-                       int32_t *d_counts, int32_t *d_nraw, int cap)
+namespace {
+
+// the context's steering tables as the BRIEF launchers take them
+PgxSteer steer_of(const pgx_ctx *c, int32_t *d_bins = nullptr)
+{
+    return PgxSteer{c->d_steer_pairs.as<int32_t>(), c->d_steer_plans.as<int32_t>(), c->d_steer_dirs.as<int32_t>(), c->steer_B,
+                    c->steer_R, d_bins};
+}
+
+// detect chain on device-resident frames (enqueue only); d_bins (steered mode only, optional): each survivor's direction
+int enqueue_detect_bins(pgx_ctx *c, const uint16_t *d_rgba, int F, int W, int H, pgx_keypoint *d_kp, uint32_t *d_desc,
+                        int32_t *d_counts, int32_t *d_nraw, int cap, int32_t *d_bins)
 {
     const int rcp = pgx_prepare_detect(c, F, W, H, cap);
     if (rcp != PGX_OK) return rcp;
@@ -178,13 +187,22 @@ int pgx_enqueue_detect(pgx_ctx *c, const uint16_t *d_rgba, int F, int W, int H, 
     }
     {
         ProfScope ps(c, "brief");
+        const PgxSteer st = steer_of(c, d_bins);
         pgx_launch_brief(c->stream, gray, F, W, H, c->ws_rawxy.as<uint32_t>(), c->ws_rawscore.as<int32_t>(), raw_cap,
                          c->ws_order.as<uint32_t>(), c->ws_nkept.as<int32_t>(), kp_eff, c->d_pairs.as<int32_t>(), c->d_plan.as<int32_t>(), c->P,
-                         d_kp, d_desc, d_counts, cap);
+                         d_kp, d_desc, d_counts, cap, c->steer_on ? &st : nullptr);
     }
     HIPCHK(c, hipEventRecord(c->ev_stage[PGX_STAGE_DETECT], c->stream));
     HIPCHK(c, hipGetLastError());
     return PGX_OK;
+}
+
+} // namespace
+
+int pgx_enqueue_detect(pgx_ctx *c, const uint16_t *d_rgba, int F, int W, int H, pgx_keypoint *d_kp, uint32_t *d_desc,
+                       int32_t *d_counts, int32_t *d_nraw, int cap)
+{
+    return enqueue_detect_bins(c, d_rgba, F, W, H, d_kp, d_desc, d_counts, d_nraw, cap, nullptr);
 }
 
 // checks and workspace allocation of the matcher for M image pairs of `stride` descriptor slots (no kernel launch)
@@ -348,7 +366,7 @@ void pgx_ctx_destroy(pgx_ctx *c)
     for (auto &kv : c->prof)
         for (auto &ev : kv.second.pending) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
     for (hipEvent_t ev : c->ev_pool) (void)hipEventDestroy(ev);
-    DevBuf *bufs[] = {&c->d_pairs, &c->d_plan, &c->d_map, &c->ws_gray, &c->ws_seg, &c->ws_segoff, &c->ws_nraw, &c->ws_rawxy,
+    DevBuf *bufs[] = {&c->d_pairs, &c->d_plan, &c->d_steer_pairs, &c->d_steer_plans, &c->d_steer_dirs, &c->d_map, &c->ws_gray, &c->ws_seg, &c->ws_segoff, &c->ws_nraw, &c->ws_rawxy,
                       &c->ws_rawscore, &c->ws_nms, &c->ws_order, &c->ws_nkept, &c->st_a, &c->st_b, &c->st_c,
                       &c->st_d, &c->st_e, &c->st_f, &c->ws_pose, &c->ws_tracks, &c->ws_tracks_split, &c->ws_agree, &c->ws_matchn[0], &c->ws_matchn[1], &c->ws_matchn[2], &c->ws_knn, &c->ws_guided, &c->ws_tri, &c->ws_ba, &c->ws_reg};
     for (DevBuf *b : bufs) b->release();
@@ -456,6 +474,36 @@ int pgx_set_brief_pairs(pgx_ctx *c, const int32_t *pairs, int P)
         HIPCHK(c, hipMemcpy(c->d_plan.p, plan, sizeof plan, hipMemcpyHostToDevice));
     }
     c->P = P; c->words = (P + 31) / 32; c->pairs_set = true;
+    c->steer_on = false; // turned tables belong to the table they were turned from
+    return PGX_OK;
+}
+
+int pgx_set_brief_steering(pgx_ctx *c, const int32_t *pairs_rot, const int32_t *dirs, int B, int radius)
+{
+    if (!c) return PGX_E_BADARG;
+    Lock l(c);
+    c->cfg_epoch++;
+    if (!pairs_rot) { c->steer_on = false; return PGX_OK; }
+    if (!c->pairs_set) return fail(c, PGX_E_NOT_CONFIGURED, "pgx_set_brief_pairs not called");
+    if (!dirs) return fail(c, PGX_E_BADARG, "null pointer");
+    if (B < 4 || B > 64 || B % 4 != 0) return fail(c, PGX_E_BADARG, "B must be a multiple of 4 in [4, 64]");
+    if (radius < 1 || radius > 31) return fail(c, PGX_E_BADARG, "radius must be in [1, 31]");
+    for (int i = 0; i < 2 * B; i++)
+        if (dirs[i] < -32767 || dirs[i] > 32767) return fail(c, PGX_E_BADARG, "dirs components must be in [-32767, 32767]");
+    const size_t tbytes = (size_t)B * c->P * 16;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->steer_on = false; // until everything below is in place
+    HIPCHK(c, c->d_steer_pairs.ensure(tbytes));
+    HIPCHK(c, hipMemcpy(c->d_steer_pairs.p, pairs_rot, tbytes, hipMemcpyHostToDevice));
+    HIPCHK(c, c->d_steer_dirs.ensure((size_t)B * 8));
+    HIPCHK(c, hipMemcpy(c->d_steer_dirs.p, dirs, (size_t)B * 8, hipMemcpyHostToDevice));
+    if (c->P == PGX_PLAN_PAIRS) { // one row-sorted sample plan per direction: brief_256 as it is
+        std::vector<int32_t> plans((size_t)B * PGX_PLAN_WORDS);
+        for (int k = 0; k < B; k++) pgx_build_brief_plan(pairs_rot + (size_t)k * PGX_PLAN_PAIRS * 4, plans.data() + (size_t)k * PGX_PLAN_WORDS);
+        HIPCHK(c, c->d_steer_plans.ensure(plans.size() * 4));
+        HIPCHK(c, hipMemcpy(c->d_steer_plans.p, plans.data(), plans.size() * 4, hipMemcpyHostToDevice));
+    }
+    c->steer_B = B; c->steer_R = radius; c->steer_on = true;
     return PGX_OK;
 }
 
@@ -610,9 +658,29 @@ int pgx_brief(pgx_ctx *c, const float *gray, int W, int H, const pgx_keypoint *k
     HIPCHK(c, c->st_c.ensure((size_t)n * c->words * 4));
     HIPCHK(c, hipMemcpyAsync(c->st_a.p, gray, npix * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->st_b.p, kps, (size_t)n * sizeof(pgx_keypoint), hipMemcpyHostToDevice, c->stream));
+    const PgxSteer st = steer_of(c);
     pgx_launch_brief_list(c->stream, c->st_a.as<float>(), W, H, c->st_b.as<pgx_keypoint>(), n,
-                          c->d_pairs.as<int32_t>(), c->d_plan.as<int32_t>(), c->P, c->st_c.as<uint32_t>());
+                          c->d_pairs.as<int32_t>(), c->d_plan.as<int32_t>(), c->P, c->st_c.as<uint32_t>(), c->steer_on ? &st : nullptr);
     HIPCHK(c, hipMemcpyAsync(desc_out, c->st_c.p, (size_t)n * c->words * 4, hipMemcpyDeviceToHost, c->stream));
+    return sync_status(c);
+}
+
+int pgx_orient(pgx_ctx *c, const float *gray, int W, int H, const pgx_keypoint *kps, int n, int32_t *bins_out)
+{
+    if (!c || !gray || n < 0 || (n > 0 && (!kps || !bins_out)))
+        return c ? fail(c, PGX_E_BADARG, "null pointer") : PGX_E_BADARG;
+    Lock l(c);
+    if (!c->steer_on) return fail(c, PGX_E_NOT_CONFIGURED, "pgx_set_brief_steering not called");
+    if (dims_ok(c, W, H) != PGX_OK) return PGX_E_BADARG;
+    if (n == 0) return PGX_OK;
+    const size_t npix = (size_t)W * H;
+    HIPCHK(c, c->st_a.ensure(npix * 4 + 32));
+    HIPCHK(c, c->st_b.ensure((size_t)n * sizeof(pgx_keypoint)));
+    HIPCHK(c, c->st_c.ensure((size_t)n * 4));
+    HIPCHK(c, hipMemcpyAsync(c->st_a.p, gray, npix * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->st_b.p, kps, (size_t)n * sizeof(pgx_keypoint), hipMemcpyHostToDevice, c->stream));
+    pgx_launch_orient_list(c->stream, c->st_a.as<float>(), W, H, c->st_b.as<pgx_keypoint>(), n, steer_of(c), c->st_c.as<int32_t>());
+    HIPCHK(c, hipMemcpyAsync(bins_out, c->st_c.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     return sync_status(c);
 }
 
@@ -824,6 +892,17 @@ int pgx_detect_batch_dev(pgx_ctx *c, const uint16_t *d_rgba, int F, int W, int H
     Lock l(c);
     if (dims_ok(c, W, H) != PGX_OK) return PGX_E_BADARG;
     return pgx_enqueue_detect(c, d_rgba, F, W, H, d_kp, d_desc, d_counts, d_nraw, capacity);
+}
+
+int pgx_detect_batch_steered_dev(pgx_ctx *c, const uint16_t *d_rgba, int F, int W, int H, pgx_keypoint *d_kp,
+                                 uint32_t *d_desc, int32_t *d_counts, int32_t *d_nraw, int capacity, int32_t *d_bins)
+{
+    if (!c || !d_rgba || !d_kp || !d_desc || !d_counts || !d_nraw || !d_bins || capacity <= 0 || F < 0)
+        return c ? fail(c, PGX_E_BADARG, "null pointer") : PGX_E_BADARG;
+    Lock l(c);
+    if (!c->steer_on) return fail(c, PGX_E_NOT_CONFIGURED, "pgx_set_brief_steering not called");
+    if (dims_ok(c, W, H) != PGX_OK) return PGX_E_BADARG;
+    return enqueue_detect_bins(c, d_rgba, F, W, H, d_kp, d_desc, d_counts, d_nraw, capacity, d_bins);
 }
 
 int pgx_match_batch_dev(pgx_ctx *c, const uint32_t *d_desc, const int32_t *d_counts, int stride, int words,

@@ -5,6 +5,8 @@
 //                        draws from an unseeded System.Random, so its table cannot be
 //                        reproduced; the formula (Marsaglia polar on y1,y2 in [0,1), truncation)
 //                        is kept so synthetic tables have the reference's shape: all offsets >= 0.
+// pgx_make_steering    : the B turned copies of a BRIEF pair table and their direction vectors (steered BRIEF, pgx.h; not in
+//                        the C# reference).  libm only in the first quadrant; the other three are exact quarter turns.
 // pgx_build_dewarp_map : DeWarp.GetDistortionMatrix (ImageProcessing/DeWarp.cs:39-107) in float64.
 //                        MathNet.Numerics 5.0.0 Cubic.RealRoots (third party, absent) is restated
 //                        from its published algorithm: parity unpinned, see DESIGN.md.
@@ -87,6 +89,38 @@ extern "C" int pgx_make_brief_pairs(uint64_t seed, int sigma, int P, int32_t *ou
     for (int p = 0; p < P; p++) {
         gaussian_coordinate(rng, sigma, out + 4 * p);
         gaussian_coordinate(rng, sigma, out + 4 * p + 2);
+    }
+    return PGX_OK;
+}
+
+extern "C" int pgx_make_steering(const int32_t *pairs, int P, int B, int32_t *pairs_rot_out, int32_t *dirs_out)
+{
+    if (!pairs || !pairs_rot_out || !dirs_out || P <= 0 || B < 4 || B > 64 || B % 4 != 0) return PGX_E_BADARG;
+    for (size_t i = 0; i < (size_t)P * 4; i++)
+        if (pairs[i] < -(1 << 20) || pairs[i] > (1 << 20)) return PGX_E_BADARG;
+    const int Q = B / 4;
+    const size_t n = (size_t)P * 2; // end points per table
+    for (int k = 0; k < Q; k++) {
+        const double theta = 2.0 * 3.14159265358979323846 * k / B;
+        const double c = std::cos(theta), s = std::sin(theta);
+        dirs_out[2 * k] = (int32_t)std::rint(16384.0 * c);
+        dirs_out[2 * k + 1] = (int32_t)std::rint(16384.0 * s);
+        int32_t *t = pairs_rot_out + (size_t)k * n * 2;
+        for (size_t e = 0; e < n; e++) { // image coordinates: x right, y down
+            const double dx = pairs[2 * e], dy = pairs[2 * e + 1];
+            t[2 * e] = (int32_t)std::rint(c * dx - s * dy);
+            t[2 * e + 1] = (int32_t)std::rint(s * dx + c * dy);
+        }
+    }
+    for (int k = Q; k < B; k++) { // the exact quarter turn (x, y) -> (-y, x) of direction k - B / 4
+        dirs_out[2 * k] = -dirs_out[2 * (k - Q) + 1];
+        dirs_out[2 * k + 1] = dirs_out[2 * (k - Q)];
+        const int32_t *src = pairs_rot_out + (size_t)(k - Q) * n * 2;
+        int32_t *t = pairs_rot_out + (size_t)k * n * 2;
+        for (size_t e = 0; e < n; e++) {
+            t[2 * e] = -src[2 * e + 1];
+            t[2 * e + 1] = src[2 * e];
+        }
     }
     return PGX_OK;
 }

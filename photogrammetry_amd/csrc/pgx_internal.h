@@ -105,6 +105,11 @@ struct pgx_ctx {
     bool pairs_set = false;
     DevBuf d_pairs;
     DevBuf d_plan; // P == 256 only: the table's row-sorted sample plan (pgx_brief_plan.h), rebuilt with every table
+    // steered BRIEF (pgx_set_brief_steering; off by default and after every pgx_set_brief_pairs): B turned tables, their
+    // sample plans when P == 256 (B x PGX_PLAN_WORDS), the B direction vectors and the disc radius of the orientation pass
+    bool steer_on = false;
+    int steer_B = 0, steer_R = 0;
+    DevBuf d_steer_pairs, d_steer_plans, d_steer_dirs;
     int mapW = 0, mapH = 0;
     bool map_set = false;
     DevBuf d_map;
@@ -252,15 +257,34 @@ hipError_t pgx_launch_nms_sync(hipStream_t s, const uint32_t *raw_xy, const int3
                                int n_cap, int W, int H, int radius, void *ws, size_t ws_stride, uint32_t *order,
                                int32_t *n_kept, int kp_cap, int *status);
 
-// k_brief.hip
+// steered BRIEF: what the launchers of k_brief.hip hand to k_steer.hip's when the mode is on (device pointers)
+struct PgxSteer {
+    const int32_t *pairs_rot; // [B][P][4]
+    const int32_t *plans;     // [B][PGX_PLAN_WORDS]; read when P == 256
+    const int32_t *dirs;      // [B][2]
+    int B, R;
+    int32_t *bins_out;        // fused path only, optional: [F][out_stride]
+};
+
+// k_brief.hip; steer != nullptr: the steered kernels of k_steer.hip on the same arguments
 void pgx_launch_brief(hipStream_t s, const float *gray, int F, int W, int H,
                       const uint32_t *raw_xy, const int32_t *raw_score, int raw_cap,
                       const uint32_t *order, const int32_t *n_kept, int kp_cap /* order stride and list bound */,
                       const int32_t *pairs, const int32_t *plan /* pgx_brief_plan.h; read when P == 256 */, int P,
-                      pgx_keypoint *kp_out, uint32_t *desc_out, int32_t *counts_out, int out_stride /* slots per frame in kp_out/desc_out */);
+                      pgx_keypoint *kp_out, uint32_t *desc_out, int32_t *counts_out, int out_stride /* slots per frame in kp_out/desc_out */,
+                      const PgxSteer *steer = nullptr);
 // descriptors for an explicit keypoint list (stage API)
 void pgx_launch_brief_list(hipStream_t s, const float *gray, int W, int H, const pgx_keypoint *kps, int n,
-                           const int32_t *pairs, const int32_t *plan, int P, uint32_t *desc_out);
+                           const int32_t *pairs, const int32_t *plan, int P, uint32_t *desc_out, const PgxSteer *steer = nullptr);
+
+// k_steer.hip
+void pgx_launch_steer(hipStream_t s, const float *gray, int F, int W, int H, const uint32_t *raw_xy, const int32_t *raw_score,
+                      int raw_cap, const uint32_t *order, const int32_t *n_kept, int kp_cap, const PgxSteer &st, int P,
+                      pgx_keypoint *kp_out, uint32_t *desc_out, int32_t *counts_out, int out_stride);
+void pgx_launch_steer_list(hipStream_t s, const float *gray, int W, int H, const pgx_keypoint *kps, int n, const PgxSteer &st,
+                           int P, uint32_t *desc_out);
+void pgx_launch_orient_list(hipStream_t s, const float *gray, int W, int H, const pgx_keypoint *kps, int n, const PgxSteer &st,
+                            int32_t *bins_out);
 
 // k_pose.hip
 size_t pgx_pose_ws_bytes(int M, int n_samples);

@@ -143,6 +143,28 @@ class KeypointDetection {
         for (const auto &p : gaussianKeypairs) { flat.push_back(p.first.X); flat.push_back(p.first.Y); flat.push_back(p.second.X); flat.push_back(p.second.Y); }
         ctx_.check(pgx_set_brief_pairs(ctx_.get(), flat.data(), (int)gaussianKeypairs.size()));
         words_ = ((int)gaussianKeypairs.size() + 31) / 32;
+        pairs_ = std::move(flat);
+    }
+    // Steered BRIEF (pgx.h; not in the reference): Detect then writes the descriptors of each keypoint's own direction.
+    // directions: a multiple of 4 in [4, 64]; radius of the orientation disc in [1, 31].
+    void SetSteering(int directions, int radius)
+    {
+        const int P = (int)pairs_.size() / 4;
+        std::vector<int32_t> rot((size_t)(directions > 0 ? directions : 0) * P * 4 + 1), dirs((size_t)(directions > 0 ? directions : 0) * 2 + 1);
+        if (pgx_make_steering(pairs_.data(), P, directions, rot.data(), dirs.data()) != PGX_OK)
+            throw ArgumentException("SetSteering: directions must be a multiple of 4 in [4, 64], offsets within +-2^20");
+        ctx_.check(pgx_set_brief_steering(ctx_.get(), rot.data(), dirs.data(), directions, radius));
+    }
+    void ClearSteering() { ctx_.check(pgx_set_brief_steering(ctx_.get(), nullptr, nullptr, 0, 0)); }
+    // the direction bin of every keypoint (steering on)
+    std::vector<int32_t> Orient(const Matrix<float> &image, const std::vector<Keypoint> &keypoints) const
+    {
+        std::vector<pgx_keypoint> in(keypoints.size());
+        for (size_t i = 0; i < keypoints.size(); i++)
+            in[i] = {keypoints[i].Coordinate_.X, keypoints[i].Coordinate_.Y, keypoints[i].FastScore, keypoints[i].Value};
+        std::vector<int32_t> bins(keypoints.size());
+        ctx_.check(pgx_orient(ctx_.get(), image.data.data(), image.Width, image.Height, in.data(), (int)in.size(), bins.data()));
+        return bins;
     }
     static std::vector<GaussianPair> MakeGaussianKeypairs(uint64_t seed, const KeypointDetectionOptions &o)
     {
@@ -176,6 +198,7 @@ class KeypointDetection {
     Context &ctx_;
     KeypointDetectionOptions o_;
     int words_ = 0;
+    std::vector<int32_t> pairs_; // the table as set, for SetSteering
 };
 
 class RedundantKeypointEliminator {
