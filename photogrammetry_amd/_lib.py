@@ -18,25 +18,85 @@ PGX_DIST_NONE = 2**31 - 1
 PGX_SRC_RGBA64, PGX_SRC_RGBA8 = 0, 1
 PGX_STAGE_DETECT, PGX_STAGE_MATCH_WIDE, PGX_STAGE_MATCH_ROWS, PGX_STAGE_MATCH_DONE = 0, 1, 2, 3
 
-# every symbol include/pgx.h declares (tests/test_abi_symbols.py checks the header against this)
-EXPORTS = [
-    "pgx_ctx_create", "pgx_ctx_destroy", "pgx_last_error", "pgx_version", "pgx_set_stream",
-    "pgx_check_status", "pgx_set_dewarp_map", "pgx_set_dewarp_coeffs", "pgx_get_dewarp_map", "pgx_set_brief_pairs",
-    "pgx_set_detect_params",
-    "pgx_set_capacity", "pgx_set_source_format", "pgx_set_match_chunk", "pgx_dewarp", "pgx_gray", "pgx_fast", "pgx_brief", "pgx_nms", "pgx_match", "pgx_match_batch",
-    "pgx_detect", "pgx_detect_batch_dev", "pgx_match_batch_dev", "pgx_wait_stage", "pgx_gate_match", "pgx_profile_enable",
-    "pgx_profile_get", "pgx_profile_filter", "pgx_profile_reset", "pgx_profile_serialize", "pgx_match_stats", "pgx_debug_counters", "pgx_make_brief_pairs",
-    "pgx_build_dewarp_map", "pgx_comm_unique_id", "pgx_comm_init", "pgx_comm_destroy", "pgx_comm_info",
-    "pgx_allgather_dev", "pgx_sequence_step_dev", "pgx_tracks_create", "pgx_tracks_destroy", "pgx_tracks_add_pair",
-    "pgx_tracks_finish", "pgx_tracks_get", "pgx_tracks_dropped", "pgx_tracks_dev", "pgx_fundamental_ransac_dev", "pgx_pose_dev",
-    "pgx_knn_batch_dev", "pgx_match_nn_batch_dev", "pgx_knn",
-    "pgx_knn_guided_batch_dev", "pgx_match_guided_batch_dev", "pgx_knn_guided",
-    "pgx_tracks_split_dev", "pgx_tracks_finish_split",
-    "pgx_triangulate_tracks_dev", "pgx_triangulate_tracks",
-    "pgx_bundle_adjust_dev", "pgx_bundle_adjust",
-    "pgx_register_frames_dev", "pgx_register_frames",
-    "pgx_set_brief_steering", "pgx_orient", "pgx_detect_batch_steered_dev", "pgx_make_steering",
-]
+# Every export of include/pgx.h with its signature, in the header's order: name -> (restype, [argtypes]).  lib() applies
+# the table, so a call site passes plain Python values: ctypes converts each to the declared width (a 64-bit seed or a
+# device address stays 64 bits) and refuses the wrong kind with ctypes.ArgumentError before the library is entered.  The
+# kinds are coarse on purpose: every pointer, handle and out-parameter is P (numpy and device addresses, byref(...), ctypes
+# arrays and None all pass), a `const char *` is S.  Adding an export means three things: the prototype in pgx.h, one line
+# here, and a [DllImport] or an OMITTED entry in integration/csharp/PgxNative.cs; the CPU suite fails until all three agree
+# (tests/test_abi_symbols.py holds this table to the header, tests/test_csharp_binding.py the C# side).
+I, F, D, U64, SZ, P, S = C.c_int, C.c_float, C.c_double, C.c_uint64, C.c_size_t, C.c_void_p, C.c_char_p
+SIGNATURES = {
+    "pgx_ctx_create": (I, [I, P]),
+    "pgx_ctx_destroy": (None, [P]),
+    "pgx_last_error": (S, [P]),
+    "pgx_version": (S, []),
+    "pgx_set_stream": (I, [P, P]),
+    "pgx_check_status": (I, [P]),
+    "pgx_set_source_format": (I, [P, I]),
+    "pgx_set_dewarp_map": (I, [P, P, I, I]),
+    "pgx_set_dewarp_coeffs": (I, [P, I, I, P, I]),
+    "pgx_get_dewarp_map": (I, [P, P, I, I]),
+    "pgx_set_brief_pairs": (I, [P, P, I]),
+    "pgx_set_brief_steering": (I, [P, P, P, I, I]),
+    "pgx_set_detect_params": (I, [P, F, I]),
+    "pgx_set_capacity": (I, [P, I, I]),
+    "pgx_set_match_chunk": (I, [P, I]),
+    "pgx_dewarp": (I, [P, P, I, I, P]),
+    "pgx_gray": (I, [P, P, I, I, P]),
+    "pgx_fast": (I, [P, P, I, I, P, I, P]),
+    "pgx_brief": (I, [P, P, I, I, P, I, P]),
+    "pgx_orient": (I, [P, P, I, I, P, I, P]),
+    "pgx_nms": (I, [P, P, I, I, I, P, P]),
+    "pgx_match": (I, [P, P, I, P, I, I, P]),
+    "pgx_match_batch": (I, [P, P, P, I, I, P, I, P, P]),
+    "pgx_detect": (I, [P, P, I, I, P, P, I, P, P]),
+    "pgx_detect_batch_dev": (I, [P, P, I, I, I, P, P, P, P, I]),
+    "pgx_detect_batch_steered_dev": (I, [P, P, I, I, I, P, P, P, P, I, P]),
+    "pgx_match_batch_dev": (I, [P, P, P, I, I, P, I, I, P]),
+    "pgx_wait_stage": (I, [P, P, I]),
+    "pgx_gate_match": (I, [P, P, I]),
+    "pgx_knn_batch_dev": (I, [P, P, P, I, I, P, I, I, I, P, P, P]),
+    "pgx_match_nn_batch_dev": (I, [P, P, P, I, I, P, I, I, I, F, I, P]),
+    "pgx_knn": (I, [P, P, I, P, I, I, I, P, P, P]),
+    "pgx_knn_guided_batch_dev": (I, [P, P, P, P, I, I, P, I, I, P, F, I, P, P, P]),
+    "pgx_match_guided_batch_dev": (I, [P, P, P, P, I, I, P, I, I, P, F, I, F, I, P]),
+    "pgx_knn_guided": (I, [P, P, P, I, P, P, I, I, P, F, I, P, P, P]),
+    "pgx_fundamental_ransac_dev": (I, [P, P, P, P, P, I, I, I, I, F, I, U64, P, P, P]),
+    "pgx_pose_dev": (I, [P, P, P, P, P, I, I, P, P, P, P, P]),
+    "pgx_comm_unique_id": (I, [P]),
+    "pgx_comm_init": (I, [P, I, I, P]),
+    "pgx_comm_destroy": (I, [P]),
+    "pgx_comm_info": (I, [P, P, P]),
+    "pgx_allgather_dev": (I, [P, P, SZ]),
+    "pgx_sequence_step_dev": (I, [P, P, I, I, I, I, P, P, P, P, I, P, I, I, P]),
+    "pgx_tracks_dev": (I, [P, P, P, P, I, I, I, P, I, I, I, P, P, P, P]),
+    "pgx_tracks_split_dev": (I, [P, P, P, P, I, I, I, P, I, I, P, I, I, P, P, P, P]),
+    "pgx_tracks_create": (I, [P, I, P]),
+    "pgx_tracks_destroy": (None, [P]),
+    "pgx_tracks_add_pair": (I, [P, I, I, P, I, I]),
+    "pgx_tracks_finish": (I, [P, I, P, P]),
+    "pgx_tracks_get": (I, [P, P, P]),
+    "pgx_tracks_finish_split": (I, [P, P, I, I, P, P, P]),
+    "pgx_tracks_dropped": (I, [P, P, P]),
+    "pgx_triangulate_tracks_dev": (I, [P, P, I, I, P, I, P, P, P, P, I, D, D, I, P, P, P, P, P]),
+    "pgx_triangulate_tracks": (I, [P, P, P, I, P, P, P, I, D, D, I, P, P, P, P, P]),
+    "pgx_bundle_adjust_dev": (I, [P, P, I, I, P, I, P, P, P, P, P, P, I, P, P, I, D, D, P, P, P, P, P, P]),
+    "pgx_bundle_adjust": (I, [P, P, P, I, P, P, P, P, P, I, P, P, I, D, D, P, P, P, P, P, P]),
+    "pgx_register_frames_dev": (I, [P, P, I, I, P, I, P, P, P, P, P, P, I, P, P, I, D, I, I, U64, P, P, P, P, P, P]),
+    "pgx_register_frames": (I, [P, P, P, I, P, P, P, P, P, I, P, P, I, D, I, I, U64, P, P, P, P, P, P]),
+    "pgx_profile_enable": (I, [P, I]),
+    "pgx_profile_filter": (I, [P, S]),
+    "pgx_profile_get": (I, [P, S, P, P]),
+    "pgx_profile_reset": (I, [P]),
+    "pgx_profile_serialize": (I, [P, I]),
+    "pgx_match_stats": (I, [P, P, P, P]),
+    "pgx_debug_counters": (I, [P, P]),
+    "pgx_make_brief_pairs": (I, [U64, I, I, P]),
+    "pgx_make_steering": (I, [P, I, I, P, P]),
+    "pgx_build_dewarp_map": (I, [I, I, P, I, P]),
+}
+EXPORTS = list(SIGNATURES)
 
 
 def build(force=False):
@@ -61,11 +121,8 @@ def lib():
             raise OSError("%s is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                           "(there is no CPU fallback)" % LIB_PATH)
         L = C.CDLL(LIB_PATH)
-        L.pgx_last_error.restype = C.c_char_p
-        L.pgx_version.restype = C.c_char_p
-        L.pgx_ctx_destroy.restype = None
-        L.pgx_tracks_destroy.restype = None
-        for name in EXPORTS:
-            getattr(L, name)  # AttributeError if the ABI lost a symbol
+        for name, (restype, argtypes) in SIGNATURES.items():
+            f = getattr(L, name)  # AttributeError if the ABI lost a symbol
+            f.restype, f.argtypes = restype, argtypes
         _lib = L
     return _lib

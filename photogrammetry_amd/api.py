@@ -55,12 +55,14 @@ _EXC[_lib.PGX_E_RCCL] = RcclError
 
 
 def _ptr(a):
-    return C.c_void_p(a.ctypes.data) if a is not None else None
+    """A pointer argument: the address of a numpy array, the device pointer of a torch tensor, a raw int as it is; None is
+    NULL.  _lib.SIGNATURES declares every such parameter as c_void_p, so the plain int keeps its 64 bits."""
+    if a is None or isinstance(a, int):
+        return a
+    return a.ctypes.data if isinstance(a, np.ndarray) else a.data_ptr()
 
 
-def _dptr(t):
-    """Device pointer of a torch tensor (or a raw int)."""
-    return C.c_void_p(t if isinstance(t, int) else t.data_ptr())
+_dptr = _ptr   # the name the device-resident call sites use
 
 
 def _host_tracks(kps_per_frame, track_offsets, nodes):
@@ -76,6 +78,30 @@ def _host_tracks(kps_per_frame, track_offsets, nodes):
     counts = np.array([len(k) for k in kp], dtype=np.int32)
     flat = np.ascontiguousarray(np.concatenate(kp) if len(kp) else np.zeros(0, KEYPOINT_DTYPE))
     return off, nd, kp, counts, flat
+
+
+def _host_problem(kps_per_frame, K, Rt, sel, track_offsets, nodes, xyz, track_flags):
+    """What the host forms of bundle adjustment and registration share: their arguments kps .. track_flags in the C order (arrays
+    for pointers, None for NULL; sel = the per-frame int32 array, `fixed` or `reg`) -> (those arguments, n_frames, n_tracks,
+    n_nodes)."""
+    off, nd, kp, counts, flat = _host_tracks(kps_per_frame, track_offsets, nodes)
+    nf, n = len(kp), len(off) - 1
+    Kc = np.ascontiguousarray(K, dtype=np.float64).reshape(nf, 4)
+    Rc = np.ascontiguousarray(Rt, dtype=np.float64).reshape(nf, 12)
+    sl = np.ascontiguousarray(sel, dtype=np.int32).reshape(nf)
+    X = np.ascontiguousarray(xyz, dtype=np.float64).reshape(n, 3)
+    fl = None if track_flags is None else np.ascontiguousarray(track_flags, dtype=np.int32).reshape(n)
+    head = (flat if len(flat) else None, counts, nf, Kc, Rc, sl, off, nd if len(nd) else None, n, X if n else None, fl if n else None)
+    return head, nf, n, len(nd)
+
+
+def _desc_pair(desc1, desc2):
+    """The two descriptor sets of a one-pair host call -> (d1, d2, words): words from the first set that has rows, 8 when
+    neither has."""
+    d1 = np.ascontiguousarray(desc1, dtype=np.uint32)
+    d2 = np.ascontiguousarray(desc2, dtype=np.uint32)
+    words = d1.shape[1] if d1.ndim == 2 and d1.shape[0] else (d2.shape[1] if d2.ndim == 2 and d2.shape[0] else 8)
+    return d1, d2, words
 
 
 class Engine:
@@ -111,7 +137,7 @@ class Engine:
 
     # -- configuration ------------------------------------------------------------------
     def set_stream(self, stream_handle):
-        self._chk(self._L.pgx_set_stream(self._h, C.c_void_p(stream_handle)))
+        self._chk(self._L.pgx_set_stream(self._h, stream_handle))
 
     def check_status(self):
         self._chk(self._L.pgx_check_status(self._h))
@@ -154,7 +180,7 @@ class Engine:
         self._chk(self._L.pgx_set_brief_steering(self._h, _ptr(t), _ptr(d), int(B), int(radius)))
 
     def set_detect_params(self, threshold, suppression_radius):
-        self._chk(self._L.pgx_set_detect_params(self._h, C.c_float(threshold), int(suppression_radius)))
+        self._chk(self._L.pgx_set_detect_params(self._h, threshold, int(suppression_radius)))
 
     def set_capacity(self, max_raw_per_frame, max_keypoints_per_frame):
         self._chk(self._L.pgx_set_capacity(self._h, int(max_raw_per_frame), int(max_keypoints_per_frame)))
@@ -220,11 +246,9 @@ class Engine:
         return order[:n.value].copy()
 
     def match(self, desc1, desc2):
-        d1 = np.ascontiguousarray(desc1, dtype=np.uint32)
-        d2 = np.ascontiguousarray(desc2, dtype=np.uint32)
-        words = d1.shape[1] if d1.ndim == 2 and d1.shape[0] else (d2.shape[1] if d2.ndim == 2 and d2.shape[0] else 8)
+        d1, d2, words = _desc_pair(desc1, desc2)
         out = np.zeros(max(1, len(d1)), dtype=PAIR_DTYPE)
-        self._chk(self._L.pgx_match(self._h, _ptr(d1), len(d1), _ptr(d2), len(d2), int(words), _ptr(out)))
+        self._chk(self._L.pgx_match(self._h, _ptr(d1), len(d1), _ptr(d2), len(d2), words, _ptr(out)))
         return out[:len(d1)].copy()
 
     def match_batch(self, descs, pair_list):
@@ -267,28 +291,29 @@ class Engine:
 
     def detect_batch_steered_dev(self, d_rgba64, F, W, H, d_kp, d_desc, d_counts, d_nraw, capacity, d_bins):
         self._chk(self._L.pgx_detect_batch_steered_dev(self._h, _dptr(d_rgba64), int(F), int(W), int(H), _dptr(d_kp),
-                                                       _dptr(d_desc), _dptr(d_counts), _dptr(d_nraw), int(capacity),
-                                                       _dptr(d_bins)))
+                                                       _dptr(d_desc), _dptr(d_counts), _dptr(d_nraw), int(capacity), _dptr(d_bins)))
 
     def match_batch_dev(self, d_desc, d_counts, stride, words, d_pairlist, M, d_out, max_count=None):
         self._chk(self._L.pgx_match_batch_dev(self._h, _dptr(d_desc), _dptr(d_counts), int(stride), int(words),
-                                              _dptr(d_pairlist), int(M),
-                                              int(stride if max_count is None else max_count), _dptr(d_out)))
+                                              _dptr(d_pairlist), int(M), int(stride if max_count is None else max_count), _dptr(d_out)))
 
     # -- exact nearest-neighbour matching (include/pgx.h, "exact nearest-neighbour matching") --------------
     def knn(self, desc1, desc2, k=2, col=False):
         """pgx_knn: the k (1 or 2) nearest columns of every row of desc1 in desc2, ascending in (distance, column).
         Returns (idx [n1][k], dist [n1][k]) int32 arrays, and col_nn [n2] (the nearest row of every column, -1 when desc1 is
         empty) as a third array when col=True.  Missing neighbours are (-1, PGX_DIST_NONE)."""
-        d1 = np.ascontiguousarray(desc1, dtype=np.uint32)
-        d2 = np.ascontiguousarray(desc2, dtype=np.uint32)
-        words = d1.shape[1] if d1.ndim == 2 and d1.shape[0] else (d2.shape[1] if d2.ndim == 2 and d2.shape[0] else 8)
-        n1, n2 = len(d1), len(d2)
+        d1, d2, words = _desc_pair(desc1, desc2)
+        return self._knn_out(len(d1), len(d2), k, col, lambda *out: self._L.pgx_knn(
+            self._h, _ptr(d1), len(d1), _ptr(d2), len(d2), words, int(k), *out))
+
+    def _knn_out(self, n1, n2, k, col, call):
+        """The output side of knn / knn_guided: buffers of at least one row (no NULL for an empty set), call(idx, dist, col_nn)
+        on their addresses, the results cut to n1 rows and n2 columns."""
         kk = max(1, int(k))
         idx = np.zeros((max(1, n1), kk), dtype=np.int32)
         dist = np.zeros((max(1, n1), kk), dtype=np.int32)
         cnn = np.zeros(max(1, n2), dtype=np.int32) if col else None
-        self._chk(self._L.pgx_knn(self._h, _ptr(d1), n1, _ptr(d2), n2, int(words), int(k), _ptr(idx), _ptr(dist), _ptr(cnn)))
+        self._chk(call(_ptr(idx), _ptr(dist), _ptr(cnn)))
         if col:
             return idx[:n1].copy(), dist[:n1].copy(), cnn[:n2].copy()
         return idx[:n1].copy(), dist[:n1].copy()
@@ -297,7 +322,7 @@ class Engine:
         """pgx_knn_batch_dev: d_idx, d_dist [M][stride][k] int32, d_col_nn [M][stride] int32 or None (device tensors)."""
         self._chk(self._L.pgx_knn_batch_dev(self._h, _dptr(d_desc), _dptr(d_counts), int(stride), int(words), _dptr(d_pairlist),
                                             int(M), int(stride if max_count is None else max_count), int(k), _dptr(d_idx),
-                                            _dptr(d_dist), None if d_col_nn is None else _dptr(d_col_nn)))
+                                            _dptr(d_dist), _dptr(d_col_nn)))
 
     def match_nn_batch_dev(self, d_desc, d_counts, stride, words, d_pairlist, M, d_out, max_dist, ratio=0.0, cross_check=False,
                            max_count=None):
@@ -305,31 +330,22 @@ class Engine:
         (i, -1, PGX_DIST_NONE); feeds tracks_dev as it is."""
         self._chk(self._L.pgx_match_nn_batch_dev(self._h, _dptr(d_desc), _dptr(d_counts), int(stride), int(words), _dptr(d_pairlist),
                                                  int(M), int(stride if max_count is None else max_count), int(max_dist),
-                                                 C.c_float(ratio), 1 if cross_check else 0, _dptr(d_out)))
+                                                 ratio, 1 if cross_check else 0, _dptr(d_out)))
 
     # -- epipolar-guided exact matching (include/pgx.h, "epipolar-guided exact matching") ----------------
     def knn_guided(self, desc1, kp1, desc2, kp2, F, band, k=2, col=False):
         """pgx_knn_guided: knn() restricted to the columns within `band` pixels of each row's epipolar line.  kp1, kp2:
         KEYPOINT_DTYPE arrays (or int32 [n][4]) of the same lengths as desc1, desc2; F: 9 float32 values, row-major,
         h1^T F h2 = 0.  Returns (idx [n1][k], dist [n1][k]) and col_nn [n2] as a third array when col=True."""
-        d1 = np.ascontiguousarray(desc1, dtype=np.uint32)
-        d2 = np.ascontiguousarray(desc2, dtype=np.uint32)
+        d1, d2, words = _desc_pair(desc1, desc2)
         k1 = np.ascontiguousarray(np.asarray(kp1).view(np.int32).reshape(-1, 4) if len(kp1) else np.zeros((0, 4), np.int32))
         k2 = np.ascontiguousarray(np.asarray(kp2).view(np.int32).reshape(-1, 4) if len(kp2) else np.zeros((0, 4), np.int32))
         f = np.ascontiguousarray(np.asarray(F, dtype=np.float32).reshape(9))
-        words = d1.shape[1] if d1.ndim == 2 and d1.shape[0] else (d2.shape[1] if d2.ndim == 2 and d2.shape[0] else 8)
         n1, n2 = len(d1), len(d2)
         if len(k1) != n1 or len(k2) != n2:
             raise ValueError("keypoint and descriptor counts differ")
-        kk = max(1, int(k))
-        idx = np.zeros((max(1, n1), kk), dtype=np.int32)
-        dist = np.zeros((max(1, n1), kk), dtype=np.int32)
-        cnn = np.zeros(max(1, n2), dtype=np.int32) if col else None
-        self._chk(self._L.pgx_knn_guided(self._h, _ptr(d1), _ptr(k1), n1, _ptr(d2), _ptr(k2), n2, int(words), _ptr(f),
-                                         C.c_float(band), int(k), _ptr(idx), _ptr(dist), _ptr(cnn)))
-        if col:
-            return idx[:n1].copy(), dist[:n1].copy(), cnn[:n2].copy()
-        return idx[:n1].copy(), dist[:n1].copy()
+        return self._knn_out(n1, n2, k, col, lambda *out: self._L.pgx_knn_guided(
+            self._h, _ptr(d1), _ptr(k1), n1, _ptr(d2), _ptr(k2), n2, words, _ptr(f), band, int(k), *out))
 
     def knn_guided_batch_dev(self, d_desc, d_kp, d_counts, stride, words, d_pairlist, M, d_F, band, k, d_idx, d_dist,
                              d_col_nn=None, max_count=None):
@@ -337,29 +353,25 @@ class Engine:
         d_col_nn [M][stride] int32 or None (device tensors)."""
         self._chk(self._L.pgx_knn_guided_batch_dev(self._h, _dptr(d_desc), _dptr(d_kp), _dptr(d_counts), int(stride), int(words),
                                                    _dptr(d_pairlist), int(M), int(stride if max_count is None else max_count),
-                                                   _dptr(d_F), C.c_float(band), int(k), _dptr(d_idx), _dptr(d_dist),
-                                                   None if d_col_nn is None else _dptr(d_col_nn)))
+                                                   _dptr(d_F), band, int(k), _dptr(d_idx), _dptr(d_dist), _dptr(d_col_nn)))
 
     def match_guided_batch_dev(self, d_desc, d_kp, d_counts, stride, words, d_pairlist, M, d_F, band, d_out, max_dist, ratio=0.0,
                                cross_check=False, max_count=None):
         """pgx_match_guided_batch_dev: the guided NN lists, d_out [M][stride] PAIR_DTYPE as match_nn_batch_dev's."""
         self._chk(self._L.pgx_match_guided_batch_dev(self._h, _dptr(d_desc), _dptr(d_kp), _dptr(d_counts), int(stride), int(words),
                                                      _dptr(d_pairlist), int(M), int(stride if max_count is None else max_count),
-                                                     _dptr(d_F), C.c_float(band), int(max_dist), C.c_float(ratio),
-                                                     1 if cross_check else 0, _dptr(d_out)))
+                                                     _dptr(d_F), band, int(max_dist), ratio, 1 if cross_check else 0, _dptr(d_out)))
 
     # -- RANSAC fundamental matrix / pose (device tensors) ------------------------------------------
     def fundamental_ransac_dev(self, d_kp, d_matches, d_counts, d_pairlist, M, stride, n_samples, pairs_per_sample, threshold,
                                d_F, d_inliers, d_best_sample, rank_check=False, seed=0):
         self._chk(self._L.pgx_fundamental_ransac_dev(self._h, _dptr(d_kp), _dptr(d_matches), _dptr(d_counts), _dptr(d_pairlist),
-                                                     int(M), int(stride), int(n_samples), int(pairs_per_sample),
-                                                     C.c_float(threshold), 1 if rank_check else 0, C.c_uint64(seed),
-                                                     _dptr(d_F), _dptr(d_inliers), _dptr(d_best_sample)))
+                                                     int(M), int(stride), int(n_samples), int(pairs_per_sample), threshold,
+                                                     1 if rank_check else 0, seed, _dptr(d_F), _dptr(d_inliers), _dptr(d_best_sample)))
 
     def pose_dev(self, d_kp, d_matches, d_counts, d_pairlist, M, stride, d_F, d_Rt, d_votes, d_best, d_points=None):
         self._chk(self._L.pgx_pose_dev(self._h, _dptr(d_kp), _dptr(d_matches), _dptr(d_counts), _dptr(d_pairlist), int(M),
-                                       int(stride), _dptr(d_F), _dptr(d_Rt), _dptr(d_votes), _dptr(d_best),
-                                       _dptr(d_points) if d_points is not None else None))
+                                       int(stride), _dptr(d_F), _dptr(d_Rt), _dptr(d_votes), _dptr(d_best), _dptr(d_points)))
 
     # -- the track graph on the device (pgx_tracks_dev) ----------------------------------------------
     def tracks_dev(self, d_matches, d_counts, d_pairlist, M, F, stride, n_frames, max_dist, min_len, d_track_of, d_offsets,
@@ -367,8 +379,8 @@ class Engine:
         """Connected components over the gated match lists where they sit in HBM (pgx.h: order-independent semantics).
         d_track_of [n_frames][stride], d_offsets [n_frames * stride + 1], d_nodes [n_frames * stride][2], d_summary [8]."""
         self._chk(self._L.pgx_tracks_dev(self._h, _dptr(d_matches), _dptr(d_counts), _dptr(d_pairlist), int(M), int(F), int(stride),
-                                         _dptr(d_frame_ids) if d_frame_ids is not None else None, int(n_frames), int(max_dist),
-                                         int(min_len), _dptr(d_track_of), _dptr(d_offsets), _dptr(d_nodes), _dptr(d_summary)))
+                                         _dptr(d_frame_ids), int(n_frames), int(max_dist), int(min_len), _dptr(d_track_of),
+                                         _dptr(d_offsets), _dptr(d_nodes), _dptr(d_summary)))
 
     def tracks_split_dev(self, d_matches, d_counts, d_pairlist, M, F, stride, n_frames, max_dist, gates, min_len, d_track_of,
                          d_offsets, d_nodes, d_summary, d_frame_ids=None):
@@ -377,8 +389,8 @@ class Engine:
         Layouts as tracks_dev, but d_summary [16]: [8 + l] = nodes in tracks resolved at level l (level 0 = max_dist)."""
         g = np.ascontiguousarray(list(gates), dtype=np.int32)
         self._chk(self._L.pgx_tracks_split_dev(self._h, _dptr(d_matches), _dptr(d_counts), _dptr(d_pairlist), int(M), int(F),
-                                               int(stride), _dptr(d_frame_ids) if d_frame_ids is not None else None,
-                                               int(n_frames), int(max_dist), _ptr(g) if len(g) else None, len(g), int(min_len),
+                                               int(stride), _dptr(d_frame_ids), int(n_frames), int(max_dist),
+                                               _ptr(g) if len(g) else None, len(g), int(min_len),
                                                _dptr(d_track_of), _dptr(d_offsets), _dptr(d_nodes), _dptr(d_summary)))
 
     # -- multi-view triangulation of tracks (pgx_triangulate_tracks*) -----------------------------------
@@ -389,10 +401,9 @@ class Engine:
         float64 by frame number; d_xyz / d_quality [max_tracks][3] float64, d_flags [max_tracks] int32, d_summary [8] int32,
         d_node_err [n_frames * stride] float64 or None.  n_tracks is read on the device: no sync."""
         self._chk(self._L.pgx_triangulate_tracks_dev(
-            self._h, _dptr(d_kp), int(F), int(stride), _dptr(d_frame_ids) if d_frame_ids is not None else None, int(n_frames),
-            _dptr(d_P), _dptr(d_offsets), _dptr(d_nodes), _dptr(d_track_summary), int(max_tracks), C.c_double(min_parallax_deg),
-            C.c_double(max_reproj_px), int(refine_iters), _dptr(d_xyz), _dptr(d_quality), _dptr(d_flags),
-            _dptr(d_node_err) if d_node_err is not None else None, _dptr(d_summary)))
+            self._h, _dptr(d_kp), int(F), int(stride), _dptr(d_frame_ids), int(n_frames), _dptr(d_P), _dptr(d_offsets),
+            _dptr(d_nodes), _dptr(d_track_summary), int(max_tracks), min_parallax_deg, max_reproj_px, int(refine_iters),
+            _dptr(d_xyz), _dptr(d_quality), _dptr(d_flags), _dptr(d_node_err), _dptr(d_summary)))
 
     def triangulate_tracks(self, kps_per_frame, cameras, track_offsets, nodes=None, min_parallax_deg=1.0,
                            max_reproj_px=float("inf"), refine_iters=10):
@@ -408,8 +419,7 @@ class Engine:
         summary = np.zeros(8, dtype=np.int32)
         self._chk(self._L.pgx_triangulate_tracks(
             self._h, _ptr(flat) if len(flat) else None, _ptr(counts), len(kp), _ptr(P), _ptr(off), _ptr(nd) if len(nd) else None, n,
-            C.c_double(min_parallax_deg), C.c_double(max_reproj_px), int(refine_iters), _ptr(xyz), _ptr(q), _ptr(flags), _ptr(err),
-            _ptr(summary)))
+            min_parallax_deg, max_reproj_px, int(refine_iters), _ptr(xyz), _ptr(q), _ptr(flags), _ptr(err), _ptr(summary)))
         return dict(xyz=xyz[:n], quality=q[:n], flags=flags[:n], node_err=err[:len(nd)], summary=summary)
 
     # -- bundle adjustment of cameras and track points (pgx_bundle_adjust*) ------------------------------
@@ -420,12 +430,11 @@ class Engine:
         adjustment).  d_K [n_frames][4], d_Rt_in / d_Rt_out / d_P_out [n_frames][12] float64, d_fixed [n_frames] int32,
         d_xyz_in / d_xyz_out [max_tracks][3] float64, d_track_flags [max_tracks] int32 or None, d_trace [max_iters + 1][2]
         float64, d_report [8] int32, d_node_err [n_frames * stride] float64 or None.  n_tracks is read on the device: no sync."""
-        opt = lambda t: _dptr(t) if t is not None else None  # noqa: E731
         self._chk(self._L.pgx_bundle_adjust_dev(
-            self._h, _dptr(d_kp), int(F), int(stride), opt(d_frame_ids), int(n_frames), _dptr(d_K), _dptr(d_Rt_in), _dptr(d_fixed),
-            _dptr(d_offsets), _dptr(d_nodes), _dptr(d_track_summary), int(max_tracks), _dptr(d_xyz_in), opt(d_track_flags),
-            int(max_iters), C.c_double(huber_px), C.c_double(lambda0), _dptr(d_Rt_out), _dptr(d_P_out), _dptr(d_xyz_out),
-            opt(d_node_err), _dptr(d_trace), _dptr(d_report)))
+            self._h, _dptr(d_kp), int(F), int(stride), _dptr(d_frame_ids), int(n_frames), _dptr(d_K), _dptr(d_Rt_in), _dptr(d_fixed),
+            _dptr(d_offsets), _dptr(d_nodes), _dptr(d_track_summary), int(max_tracks), _dptr(d_xyz_in), _dptr(d_track_flags),
+            int(max_iters), huber_px, lambda0, _dptr(d_Rt_out), _dptr(d_P_out), _dptr(d_xyz_out), _dptr(d_node_err), _dptr(d_trace),
+            _dptr(d_report)))
 
     def bundle_adjust(self, kps_per_frame, K, Rt, fixed, track_offsets, nodes, xyz, track_flags=None, max_iters=20,
                       huber_px=float("inf"), lambda0=1e-3):
@@ -433,23 +442,14 @@ class Engine:
         [n_frames][12] float64; fixed [n_frames]; tracks as pgx_tracks_get gives them (track_offsets [n_tracks + 1], nodes
         [n_nodes][2]) or, with nodes=None, the `tracks` list of tracks_host; xyz [n_tracks][3]; track_flags [n_tracks] or None.
         -> dict(Rt [F][12], P [F][12], xyz [n][3], node_err [n_nodes], trace [max_iters + 1][2], report [8])"""
-        off, nd, kp, counts, flat = _host_tracks(kps_per_frame, track_offsets, nodes)
-        nf = len(kp)
-        Kc = np.ascontiguousarray(K, dtype=np.float64).reshape(nf, 4)
-        Rc = np.ascontiguousarray(Rt, dtype=np.float64).reshape(nf, 12)
-        fx = np.ascontiguousarray(fixed, dtype=np.int32).reshape(nf)
-        n = len(off) - 1
-        X = np.ascontiguousarray(xyz, dtype=np.float64).reshape(n, 3)
-        fl = None if track_flags is None else np.ascontiguousarray(track_flags, dtype=np.int32).reshape(n)
+        head, nf, n, n_nodes = _host_problem(kps_per_frame, K, Rt, fixed, track_offsets, nodes, xyz, track_flags)
         Rt_out, P_out = np.zeros((nf, 12)), np.zeros((nf, 12))
-        xyz_out, err = np.zeros((max(n, 1), 3)), np.zeros(max(len(nd), 1))
+        xyz_out, err = np.zeros((max(n, 1), 3)), np.zeros(max(n_nodes, 1))
         trace, report = np.zeros((int(max_iters) + 1, 2)), np.zeros(8, dtype=np.int32)
         self._chk(self._L.pgx_bundle_adjust(
-            self._h, _ptr(flat) if len(flat) else None, _ptr(counts), nf, _ptr(Kc), _ptr(Rc), _ptr(fx), _ptr(off),
-            _ptr(nd) if len(nd) else None, n, _ptr(X) if n else None, _ptr(fl) if fl is not None and n else None, int(max_iters),
-            C.c_double(huber_px), C.c_double(lambda0), _ptr(Rt_out), _ptr(P_out), _ptr(xyz_out), _ptr(err), _ptr(trace),
-            _ptr(report)))
-        return dict(Rt=Rt_out, P=P_out, xyz=xyz_out[:n], node_err=err[:len(nd)], trace=trace, report=report)
+            self._h, *map(_ptr, head), int(max_iters), huber_px, lambda0, _ptr(Rt_out), _ptr(P_out), _ptr(xyz_out), _ptr(err),
+            _ptr(trace), _ptr(report)))
+        return dict(Rt=Rt_out, P=P_out, xyz=xyz_out[:n], node_err=err[:n_nodes], trace=trace, report=report)
 
     # -- frame registration by P3P RANSAC against track points (pgx_register_frames*) ------------------
     def register_frames_dev(self, d_kp, F, stride, n_frames, d_K, d_Rt_in, d_register, d_offsets, d_nodes, d_track_summary,
@@ -461,12 +461,11 @@ class Engine:
         d_xyz [max_tracks][3] float64, d_track_flags [max_tracks] int32 or None, d_frame_stats [n_frames][4] int32,
         d_frame_err [n_frames][2] float64, d_node_inlier [n_frames * stride] int32 or None, d_report [8] int32.  n_tracks is
         read on the device: no sync."""
-        opt = lambda t: _dptr(t) if t is not None else None  # noqa: E731
         self._chk(self._L.pgx_register_frames_dev(
-            self._h, _dptr(d_kp), int(F), int(stride), opt(d_frame_ids), int(n_frames), _dptr(d_K), _dptr(d_Rt_in),
+            self._h, _dptr(d_kp), int(F), int(stride), _dptr(d_frame_ids), int(n_frames), _dptr(d_K), _dptr(d_Rt_in),
             _dptr(d_register), _dptr(d_offsets), _dptr(d_nodes), _dptr(d_track_summary), int(max_tracks), _dptr(d_xyz),
-            opt(d_track_flags), int(n_samples), C.c_double(inlier_px), int(min_inliers), int(refine_iters), C.c_uint64(seed),
-            _dptr(d_Rt_out), _dptr(d_P_out), _dptr(d_frame_stats), _dptr(d_frame_err), opt(d_node_inlier), _dptr(d_report)))
+            _dptr(d_track_flags), int(n_samples), inlier_px, int(min_inliers), int(refine_iters), seed,
+            _dptr(d_Rt_out), _dptr(d_P_out), _dptr(d_frame_stats), _dptr(d_frame_err), _dptr(d_node_inlier), _dptr(d_report)))
 
     def register_frames(self, kps_per_frame, K, Rt, reg, track_offsets, nodes, xyz, track_flags=None, n_samples=1024,
                         inlier_px=2.0, min_inliers=12, refine_iters=10, seed=0):
@@ -474,23 +473,14 @@ class Engine:
         [n_frames][12] float64; reg [n_frames]; tracks as pgx_tracks_get gives them (track_offsets [n_tracks + 1], nodes
         [n_nodes][2]) or, with nodes=None, the `tracks` list of tracks_host; xyz [n_tracks][3]; track_flags [n_tracks] or None.
         -> dict(Rt [F][12], P [F][12], frame_stats [F][4], frame_err [F][2], node_inlier [n_nodes], report [8])"""
-        off, nd, kp, counts, flat = _host_tracks(kps_per_frame, track_offsets, nodes)
-        nf = len(kp)
-        Kc = np.ascontiguousarray(K, dtype=np.float64).reshape(nf, 4)
-        Rc = np.ascontiguousarray(Rt, dtype=np.float64).reshape(nf, 12)
-        rg = np.ascontiguousarray(reg, dtype=np.int32).reshape(nf)
-        n = len(off) - 1
-        X = np.ascontiguousarray(xyz, dtype=np.float64).reshape(n, 3)
-        fl = None if track_flags is None else np.ascontiguousarray(track_flags, dtype=np.int32).reshape(n)
+        head, nf, n, n_nodes = _host_problem(kps_per_frame, K, Rt, reg, track_offsets, nodes, xyz, track_flags)
         Rt_out, P_out = np.zeros((nf, 12)), np.zeros((nf, 12))
         stats, ferr = np.zeros((nf, 4), dtype=np.int32), np.zeros((nf, 2))
-        ni, report = np.zeros(max(len(nd), 1), dtype=np.int32), np.zeros(8, dtype=np.int32)
+        ni, report = np.zeros(max(n_nodes, 1), dtype=np.int32), np.zeros(8, dtype=np.int32)
         self._chk(self._L.pgx_register_frames(
-            self._h, _ptr(flat) if len(flat) else None, _ptr(counts), nf, _ptr(Kc), _ptr(Rc), _ptr(rg), _ptr(off),
-            _ptr(nd) if len(nd) else None, n, _ptr(X) if n else None, _ptr(fl) if fl is not None and n else None, int(n_samples),
-            C.c_double(inlier_px), int(min_inliers), int(refine_iters), C.c_uint64(seed), _ptr(Rt_out), _ptr(P_out), _ptr(stats),
-            _ptr(ferr), _ptr(ni), _ptr(report)))
-        return dict(Rt=Rt_out, P=P_out, frame_stats=stats, frame_err=ferr, node_inlier=ni[:len(nd)], report=report)
+            self._h, *map(_ptr, head), int(n_samples), inlier_px, int(min_inliers), int(refine_iters), seed, _ptr(Rt_out),
+            _ptr(P_out), _ptr(stats), _ptr(ferr), _ptr(ni), _ptr(report)))
+        return dict(Rt=Rt_out, P=P_out, frame_stats=stats, frame_err=ferr, node_inlier=ni[:n_nodes], report=report)
 
     # -- multi-GPU: the context's own RCCL communicator (pgx_comm_*) ------------------------------
     def comm_init(self, rank, world, unique_id):
@@ -508,7 +498,7 @@ class Engine:
 
     def allgather_dev(self, d_buf, bytes_per_rank):
         """In-place all-gather of fixed-size records on the context's stream (rank-major buffer)."""
-        self._chk(self._L.pgx_allgather_dev(self._h, _dptr(d_buf), C.c_size_t(int(bytes_per_rank))))
+        self._chk(self._L.pgx_allgather_dev(self._h, _dptr(d_buf), int(bytes_per_rank)))
 
     def sequence_step_dev(self, d_frames_local, n_local_frames, frame_slots, W, H, d_kp_local, d_desc_all, d_counts_all,
                           d_nraw_local, capacity, d_pairlist_local, n_local_pairs, pair_slots, d_out_all):
@@ -603,7 +593,7 @@ def tracks_host(counts, pair_list, lists, max_dist, min_len=2, gates=None):
 def make_brief_pairs(seed, sigma, P):
     """Seeded table with the reference's generator formula (Utils.cs:14-38)."""
     out = np.zeros((P, 4), dtype=np.int32)
-    rc = _lib.lib().pgx_make_brief_pairs(C.c_uint64(seed), int(sigma), int(P), _ptr(out))
+    rc = _lib.lib().pgx_make_brief_pairs(seed, int(sigma), int(P), _ptr(out))
     if rc != PGX_OK:
         raise PgxError(rc, "pgx_make_brief_pairs")
     return out
