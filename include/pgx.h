@@ -119,6 +119,41 @@ int pgx_set_brief_pairs(pgx_ctx *ctx, const int32_t *pairs, int P);
  * PGX_E_BADARG.  With the mode on, pgx_brief, pgx_detect, pgx_detect_batch_dev and pgx_sequence_step_dev write steered
  * descriptors; keypoints, counts and order are unchanged. */
 int pgx_set_brief_steering(pgx_ctx *ctx, const int32_t *pairs_rot, const int32_t *dirs, int B, int radius);
+/* Scale pyramid: scale-invariant keypoints by running the detect chain on a ladder of shrunk grey images (k_pyramid.hip).  Not
+ * in the C# reference, whose chain is single-scale; this is ORB's remedy for a camera that moves toward or away from the
+ * scene.  Everything below is integer arithmetic or single IEEE float32 operations, so the mode is bit-identical to a CPU
+ * restatement (tests/pyramid_ref.py) with no tolerance anywhere.  Off by default; with it off nothing changes.
+ *
+ * pgx_set_pyramid(ctx, n_levels, step_q16): 1 <= n_levels <= 8; step_q16 is the scale step between neighbouring levels in
+ * 16.16 fixed point, 69632 <= step_q16 <= 131072 (1.0625 ... 2.0; 78643 ~ 1.2, 92682 ~ sqrt 2).  Anything else is
+ * PGX_E_BADARG.  n_levels == 1 turns the mode off.
+ *
+ *   1. Sizes.  W_0 = W, H_0 = H; W_l = (W_{l-1} * 65536) / step and H_l likewise, int64 floor division.  A level with
+ *      W_l < 16 or H_l < 16 is empty (no keypoints), and so is every level after it; that is not an error.
+ *   2. Scale back to level 0.  S_0 = 65536, S_l = (S_{l-1} * step + 32768) >> 16 in uint64.
+ *   3. Resampling.  Level l is built from level l - 1; level 0 is the chain's grey.  For destination column x:
+ *      q = ((2x + 1) * step - 65536) >> 1 in int64, x0 = q >> 16, x1 = min(x0 + 1, W_{l-1} - 1),
+ *      fx = (float)(q & 65535) * 2^-16 (exact).  Rows alike give y0, y1, fy.  With a = src[y0][x0], b = src[y0][x1],
+ *      c = src[y1][x0], d = src[y1][x1]:  t = a + fx * (b - a);  u = c + fx * (d - c);  out = t + fy * (u - t) -- nine
+ *      float32 operations in that order, none contracted.  q >= 0 and x0 <= W_{l-1} - 1 hold for every size from 16 to
+ *      65535 and every step in range.  At step 2.0 this is the 2 x 2 mean; at smaller steps it is the 2-tap bilinear filter
+ *      ORB implementations use between neighbouring levels.
+ *   4. Per level, on the level image of size (W_l, H_l), the existing chain runs unchanged: FAST at the context's
+ *      threshold, NMS at the context's radius, then BRIEF or steered BRIEF.  pgx_set_capacity's raw limit and survivor
+ *      limit apply to each level separately, with their usual meaning at that level.
+ *   5. Merged list of a frame.  Levels follow each other in the order 0, 1, ..., each level's entries in its NMS order.
+ *      An entry from level l at (x_l, y_l) carries pgx_keypoint.x = min(((2 x_l + 1) * S_l) >> 17, W - 1) and y likewise
+ *      with H, so the geometry stages keep reading level-0 pixels; fast_score and value are the level image's, and the
+ *      descriptor is evaluated on the level image.  d_counts[f] = min(total, capacity); a total above capacity raises
+ *      PGX_E_CAPACITY at the next status check, with the first `capacity` entries intact.  d_nraw[f] is the sum over the
+ *      levels.  Every entry's slot follows from the level counts alone: no atomic decides a placement.
+ *
+ * With the mode on, pgx_detect, pgx_detect_batch_dev, pgx_detect_batch_steered_dev (bins merged too) and
+ * pgx_sequence_step_dev write the merged lists of rule 5. */
+int pgx_set_pyramid(pgx_ctx *ctx, int n_levels, int step_q16);
+/* Rules 1 and 2 on the host (no GPU work): dims_out [n_levels][2] = (W_l, H_l), (0, 0) for an empty level; scale_out
+ * [n_levels] = S_l.  Either output may be NULL.  W or H outside [1, 65535], bad n_levels or step: PGX_E_BADARG. */
+int pgx_pyramid_dims(int W, int H, int n_levels, int step_q16, int32_t *dims_out /*[n_levels][2]*/, int32_t *scale_out /*[n_levels]*/);
 /* KeypointDetectionOptions.Threshold, RedundantKeypointEliminationOptions.SuppressionRadius. */
 int pgx_set_detect_params(pgx_ctx *ctx, float threshold, int suppression_radius);
 /* Per-frame limits of the fused detect path.  max_raw_per_frame: raw FAST hits kept for NMS.  A frame with more raises
@@ -154,6 +189,11 @@ int pgx_brief(pgx_ctx *ctx, const float *gray, int W, int H,
  * is off.  A keypoint may lie anywhere: pixels outside the image contribute 0. */
 int pgx_orient(pgx_ctx *ctx, const float *gray, int W, int H,
                const pgx_keypoint *kps, int n, int32_t *bins_out);
+/* Level `level` of a host grey image under the context's pyramid step (rule 3 of pgx_set_pyramid, applied `level` times;
+ * level 0 is a copy).  out [H_l][W_l], sized by the caller from pgx_pyramid_dims.  Not in the C# reference.
+ * PGX_E_NOT_CONFIGURED when the mode is off; PGX_E_BADARG when level is negative, at or beyond n_levels, or names an
+ * empty level. */
+int pgx_pyramid_level(pgx_ctx *ctx, const float *gray, int W, int H, int level, float *out);
 /* RedundantKeypointEliminator.EliminateRedundantKeypoints (:16-35): order_out[k] = index into
  * kps of the k-th accepted keypoint; *n_out = accepted count (order_out holds n entries). */
 int pgx_nms(pgx_ctx *ctx, const pgx_keypoint *kps, int n, int W, int H,
@@ -197,6 +237,13 @@ int pgx_detect_batch_dev(pgx_ctx *ctx, const uint16_t *d_rgba64, int F, int W, i
 int pgx_detect_batch_steered_dev(pgx_ctx *ctx, const uint16_t *d_rgba64, int F, int W, int H,
                                  pgx_keypoint *d_kp, uint32_t *d_desc, int32_t *d_counts,
                                  int32_t *d_nraw, int capacity, int32_t *d_bins);
+/* The same chain in pyramid mode (PGX_E_NOT_CONFIGURED when it is off), with where every entry of the merged lists came
+ * from: d_origin [F][capacity][3] = (level, x_l, y_l) on the level image; d_level_stats [F][n_levels][2] = (entries of the
+ * level in the frame's list, raw FAST hits of the level), (0, 0) for an empty level.  d_bins [F][capacity] or NULL; a
+ * non-NULL d_bins needs steering on (PGX_E_NOT_CONFIGURED).  Not in the C# reference. */
+int pgx_detect_batch_pyramid_dev(pgx_ctx *ctx, const uint16_t *d_rgba64, int F, int W, int H,
+                                 pgx_keypoint *d_kp, uint32_t *d_desc, int32_t *d_counts,
+                                 int32_t *d_nraw, int capacity, int32_t *d_origin, int32_t *d_level_stats, int32_t *d_bins);
 /* M image pairs: d_pairlist [M][2] = (frame_a, frame_b) indexes descriptor sets
  * d_desc [F][stride][words] with d_counts [F].  d_out [M][stride]: the first counts[a] entries of
  * row m are the reference's match list for (a, b).  Pairs with counts[b] == 0 < counts[a] raise
@@ -635,7 +682,7 @@ int pgx_profile_enable(pgx_ctx *ctx, int on);
  * of device time each way on a busy stream (0.6 ms per step of the bench job with every launch bracketed): the timed
  * region of bench.py brackets the dominant kernel only, the untimed stand-alone pass brackets everything. */
 int pgx_profile_filter(pgx_ctx *ctx, const char *name);
-/* Sums since the last reset for kernel `name` ("dewarp_gray", "fast", "ham_argmin", ...):
+/* Sums since the last reset for kernel `name` ("dewarp_gray", "fast", "pyramid", "pyramid_append", "ham_argmin", ...):
  * launches and total milliseconds.  Synchronises the stream. */
 int pgx_profile_get(pgx_ctx *ctx, const char *name, int *launches, double *total_ms);
 int pgx_profile_reset(pgx_ctx *ctx);

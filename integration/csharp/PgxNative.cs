@@ -42,6 +42,10 @@ internal static unsafe class PgxNative
     // steered BRIEF (not in the reference): pairsRot [b][p][4] and dirs [b][2] from pgx_make_steering; pairsRot = null turns it off
     [DllImport(Lib)] public static extern int pgx_set_brief_steering(IntPtr ctx, int* pairsRot, int* dirs, int b, int radius);
     [DllImport(Lib)] public static extern int pgx_make_steering(int* pairs, int p, int b, int* pairsRotOut, int* dirsOut);
+    // scale pyramid (not in the reference): nLevels in [1, 8] (1 = off), stepQ16 in [69632, 131072]; rules in include/pgx.h
+    [DllImport(Lib)] public static extern int pgx_set_pyramid(IntPtr ctx, int nLevels, int stepQ16);
+    [DllImport(Lib)] public static extern int pgx_pyramid_level(IntPtr ctx, float* gray, int w, int h, int level, float* levelOut);
+    [DllImport(Lib)] public static extern int pgx_pyramid_dims(int w, int h, int nLevels, int stepQ16, int* dimsOut, int* scaleOut);
     [DllImport(Lib)] public static extern int pgx_set_detect_params(IntPtr ctx, float threshold, int suppressionRadius);
     [DllImport(Lib)] public static extern int pgx_set_capacity(IntPtr ctx, int maxRaw, int maxKeypoints);
     [DllImport(Lib)] public static extern int pgx_set_source_format(IntPtr ctx, int format); // 0 = Rgba64, 1 = Rgba32 bytes (widened x257 on the device)
@@ -74,6 +78,10 @@ internal static unsafe class PgxNative
     [DllImport(Lib)] public static extern int pgx_detect_batch_steered_dev(IntPtr ctx, void* dRgba64, int f, int w, int h, void* dKp,
                                                                            void* dDesc, void* dCounts, void* dNraw, int capacity,
                                                                            void* dBins);
+    // pyramid mode: dOrigin [f][capacity][3] = (level, x_l, y_l), dLevelStats [f][nLevels][2]; dBins may be null
+    [DllImport(Lib)] public static extern int pgx_detect_batch_pyramid_dev(IntPtr ctx, void* dRgba64, int f, int w, int h, void* dKp,
+                                                                           void* dDesc, void* dCounts, void* dNraw, int capacity,
+                                                                           void* dOrigin, void* dLevelStats, void* dBins);
     [DllImport(Lib)] public static extern int pgx_match_batch_dev(IntPtr ctx, void* dDesc, void* dCounts, int stride, int words,
                                                                   void* dPairlist, int m, int maxCount, void* dOut);
     [DllImport(Lib)] public static extern int pgx_knn_batch_dev(IntPtr ctx, void* dDesc, void* dCounts, int stride, int words,

@@ -39,6 +39,8 @@ SIGNATURES = {
     "pgx_get_dewarp_map": (I, [P, P, I, I]),
     "pgx_set_brief_pairs": (I, [P, P, I]),
     "pgx_set_brief_steering": (I, [P, P, P, I, I]),
+    "pgx_set_pyramid": (I, [P, I, I]),
+    "pgx_pyramid_dims": (I, [I, I, I, I, P, P]),
     "pgx_set_detect_params": (I, [P, F, I]),
     "pgx_set_capacity": (I, [P, I, I]),
     "pgx_set_match_chunk": (I, [P, I]),
@@ -47,12 +49,14 @@ SIGNATURES = {
     "pgx_fast": (I, [P, P, I, I, P, I, P]),
     "pgx_brief": (I, [P, P, I, I, P, I, P]),
     "pgx_orient": (I, [P, P, I, I, P, I, P]),
+    "pgx_pyramid_level": (I, [P, P, I, I, I, P]),
     "pgx_nms": (I, [P, P, I, I, I, P, P]),
     "pgx_match": (I, [P, P, I, P, I, I, P]),
     "pgx_match_batch": (I, [P, P, P, I, I, P, I, P, P]),
     "pgx_detect": (I, [P, P, I, I, P, P, I, P, P]),
     "pgx_detect_batch_dev": (I, [P, P, I, I, I, P, P, P, P, I]),
     "pgx_detect_batch_steered_dev": (I, [P, P, I, I, I, P, P, P, P, I, P]),
+    "pgx_detect_batch_pyramid_dev": (I, [P, P, I, I, I, P, P, P, P, I, P, P, P]),
     "pgx_match_batch_dev": (I, [P, P, P, I, I, P, I, I, P]),
     "pgx_wait_stage": (I, [P, P, I]),
     "pgx_gate_match": (I, [P, P, I]),

@@ -179,6 +179,12 @@ class Engine:
             raise ValueError("pairs_rot has %d values; %d directions of the current table need %d" % (t.size, B, B * self.P * 4))
         self._chk(self._L.pgx_set_brief_steering(self._h, _ptr(t), _ptr(d), int(B), int(radius)))
 
+    def set_pyramid(self, n_levels, step_q16=92682):
+        """Scale pyramid (pgx.h): n_levels in [1, 8] (1 = off), step_q16 = the scale step between levels in 16.16 fixed
+        point, 69632 ... 131072 (92682 ~ sqrt 2).  With it on the detect entry points write merged multi-level lists."""
+        self._chk(self._L.pgx_set_pyramid(self._h, int(n_levels), int(step_q16)))
+        self._pyramid = (int(n_levels), int(step_q16))
+
     def set_detect_params(self, threshold, suppression_radius):
         self._chk(self._L.pgx_set_detect_params(self._h, threshold, int(suppression_radius)))
 
@@ -238,6 +244,16 @@ class Engine:
         self._chk(self._L.pgx_orient(self._h, _ptr(g), g.shape[1], g.shape[0], _ptr(k), len(k), _ptr(out)))
         return out
 
+    def pyramid_level(self, gray, level):
+        """Level `level` of a float32 grey image under the context's pyramid step, float32 [H_l][W_l]."""
+        g = np.ascontiguousarray(gray, dtype=np.float32)
+        n_levels, step = getattr(self, "_pyramid", (1, 0))
+        dims = pyramid_dims(g.shape[1], g.shape[0], n_levels, step)[0] if n_levels > 1 else np.zeros((1, 2), np.int32)
+        w, h = (int(v) for v in dims[level]) if 0 <= level < len(dims) else (0, 0)
+        out = np.empty((max(h, 1), max(w, 1)), dtype=np.float32)
+        self._chk(self._L.pgx_pyramid_level(self._h, _ptr(g), g.shape[1], g.shape[0], int(level), _ptr(out)))
+        return out
+
     def nms(self, kps, W, H):
         k = np.ascontiguousarray(kps, dtype=KEYPOINT_DTYPE)
         order = np.zeros(max(1, len(k)), dtype=np.int32)
@@ -284,6 +300,41 @@ class Engine:
                                      C.byref(n), C.byref(nraw)))
         return kp[:n.value].copy(), desc[:n.value].copy(), nraw.value
 
+    def detect_pyramid(self, rgba64, capacity=8192, bins=False):
+        """The chain in pyramid mode for one host image -> (keypoints, descriptors, origin [n][3] = (level, x_l, y_l),
+        level stats [n_levels][2] = (entries, raw hits), nraw[, bins with bins=True; steering on]).  The frame and the
+        outputs go through torch device tensors (pgx_detect_batch_pyramid_dev has no host form); the call waits."""
+        import torch
+        a = np.ascontiguousarray(rgba64, dtype=getattr(self, "_src_dtype", np.uint16))
+        H, W = a.shape[:2]
+        n_levels = getattr(self, "_pyramid", (1, 0))[0]
+        dev = torch.device("cuda", self.device)
+        words = max(1, self.words)
+        d_frame = torch.from_numpy(a.view(np.int16 if a.dtype == np.uint16 else np.uint8)).to(dev)
+        i32 = dict(dtype=torch.int32, device=dev)
+        d_kp, d_desc = torch.zeros((capacity, 4), **i32), torch.zeros((capacity, words), **i32)
+        d_cnt, d_origin = torch.zeros(2, **i32), torch.zeros((capacity, 3), **i32)
+        d_stats = torch.zeros((max(1, n_levels), 2), **i32)
+        d_bins = torch.zeros(capacity, **i32) if bins else None
+        torch.cuda.synchronize(dev)   # torch's fills run on its own stream; the context's stream does not order against it
+        self._chk(self._L.pgx_detect_batch_pyramid_dev(self._h, _dptr(d_frame), 1, W, H, _dptr(d_kp), _dptr(d_desc), _dptr(d_cnt),
+                                                       d_cnt.data_ptr() + 4, int(capacity), _dptr(d_origin), _dptr(d_stats),
+                                                       _dptr(d_bins)))
+        err = None
+        try:
+            self.check_status()
+        except CapacityError as e:   # the first `capacity` entries are intact: hand them over with the error
+            err = e
+        n, nraw = (int(v) for v in d_cnt.cpu().numpy())
+        kp = np.ascontiguousarray(d_kp[:n].cpu().numpy()).view(KEYPOINT_DTYPE).reshape(-1)
+        out = (kp, d_desc[:n].cpu().numpy().view(np.uint32), d_origin[:n].cpu().numpy(), d_stats.cpu().numpy(), nraw)
+        if bins:
+            out += (d_bins[:n].cpu().numpy(),)
+        if err is not None:
+            err.partial = out
+            raise err
+        return out
+
     # -- device-resident batched API (torch tensors or raw device pointers) -------------------
     def detect_batch_dev(self, d_rgba64, F, W, H, d_kp, d_desc, d_counts, d_nraw, capacity):
         self._chk(self._L.pgx_detect_batch_dev(self._h, _dptr(d_rgba64), int(F), int(W), int(H), _dptr(d_kp),
@@ -292,6 +343,14 @@ class Engine:
     def detect_batch_steered_dev(self, d_rgba64, F, W, H, d_kp, d_desc, d_counts, d_nraw, capacity, d_bins):
         self._chk(self._L.pgx_detect_batch_steered_dev(self._h, _dptr(d_rgba64), int(F), int(W), int(H), _dptr(d_kp),
                                                        _dptr(d_desc), _dptr(d_counts), _dptr(d_nraw), int(capacity), _dptr(d_bins)))
+
+    def detect_batch_pyramid_dev(self, d_rgba64, F, W, H, d_kp, d_desc, d_counts, d_nraw, capacity, d_origin, d_level_stats,
+                                 d_bins=None):
+        """pgx_detect_batch_pyramid_dev: the merged lists plus d_origin [F][capacity][3] and d_level_stats [F][n_levels][2];
+        d_bins [F][capacity] only with steering on."""
+        self._chk(self._L.pgx_detect_batch_pyramid_dev(self._h, _dptr(d_rgba64), int(F), int(W), int(H), _dptr(d_kp), _dptr(d_desc),
+                                                       _dptr(d_counts), _dptr(d_nraw), int(capacity), _dptr(d_origin),
+                                                       _dptr(d_level_stats), _dptr(d_bins)))
 
     def match_batch_dev(self, d_desc, d_counts, stride, words, d_pairlist, M, d_out, max_count=None):
         self._chk(self._L.pgx_match_batch_dev(self._h, _dptr(d_desc), _dptr(d_counts), int(stride), int(words),
@@ -609,6 +668,17 @@ def make_steering(pairs, B):
     if rc != PGX_OK:
         raise ArgumentException(rc, "B must be a multiple of 4 in [4, 64] and every offset within +-2^20")
     return rot, dirs
+
+
+def pyramid_dims(W, H, n_levels, step_q16):
+    """Rules 1 and 2 of the scale pyramid (pgx.h; host only) -> (dims int32 [n_levels][2] = (W_l, H_l), (0, 0) for an empty
+    level; scale int32 [n_levels] = S_l)."""
+    n = int(n_levels)
+    dims, scale = np.zeros((max(n, 1), 2), dtype=np.int32), np.zeros(max(n, 1), dtype=np.int32)
+    rc = _lib.lib().pgx_pyramid_dims(int(W), int(H), n, int(step_q16), _ptr(dims), _ptr(scale))
+    if rc != PGX_OK:
+        raise _EXC.get(rc, PgxError)(rc, "pgx_pyramid_dims(%d, %d, %d, %d)" % (W, H, n, step_q16))
+    return dims, scale
 
 
 def build_dewarp_map(W, H, coeffs):

@@ -117,8 +117,31 @@ int dims_ok(pgx_ctx *c, int W, int H, const char *what = "dimensions must fit us
 
 // The next four are also called by pgx_comm.hip (the caller holds the context's mutex).
 
+namespace {
+
+// the levels of a W x H frame under the context's pyramid (rules 1 and 2 of pgx_set_pyramid); mode off: level 0 alone
+struct PyrPlan {
+    int n_levels = 1, n_run = 1; // levels of the mode; those of them that are not empty
+    int32_t dims[8][2] = {};
+    int32_t scale[8] = {};
+};
+
+PyrPlan pyr_plan(const pgx_ctx *c, int W, int H)
+{
+    PyrPlan p;
+    p.dims[0][0] = W; p.dims[0][1] = H; p.scale[0] = 65536;
+    if (c->pyr_levels <= 1) return p;
+    p.n_levels = c->pyr_levels;
+    (void)pgx_pyramid_dims(W, H, p.n_levels, c->pyr_step, &p.dims[0][0], p.scale); // the caller has checked W and H
+    while (p.n_run < p.n_levels && p.dims[p.n_run][0] > 0) p.n_run++;
+    return p;
+}
+
+} // namespace
+
 // every check and workspace allocation of the detect chain (no kernel launch): pgx_sequence_step_dev calls it before its
-// first collective so that no rank can fail locally between two collectives
+// first collective so that no rank can fail locally between two collectives.  In pyramid mode every workspace holds the
+// largest requirement over the levels, and the level images and per-level lists are allocated here too.
 int pgx_prepare_detect(pgx_ctx *c, int F, int W, int H, int cap)
 {
     if (!c->params_set) return fail(c, PGX_E_NOT_CONFIGURED, "pgx_set_detect_params not called");
@@ -127,19 +150,36 @@ int pgx_prepare_detect(pgx_ctx *c, int F, int W, int H, int cap)
     if (c->map_set && (c->mapW != W || c->mapH != H))
         return fail(c, PGX_E_DIM_MISMATCH, "image %dx%d vs dewarp map %dx%d (ArgumentException)", W, H, c->mapW, c->mapH);
     if (F <= 0) return PGX_OK;
+    const PyrPlan pl = pyr_plan(c, W, H);
     const size_t npix = (size_t)W * H;
-    const size_t nseg = pgx_fast_seg_count(W, H);
     const int raw_cap = c->raw_cap;
+    size_t nseg = 0, nms_stride = 0; // neither is assumed monotone in the frame size
+    for (int l = 0; l < pl.n_run; l++) {
+        const size_t sg = pgx_fast_seg_count(pl.dims[l][0], pl.dims[l][1]);
+        const size_t ns = pgx_nms_ws_bytes(pl.dims[l][0], pl.dims[l][1], c->radius, raw_cap, true);
+        nseg = sg > nseg ? sg : nseg;
+        nms_stride = ns > nms_stride ? ns : nms_stride;
+    }
     HIPCHK(c, c->ws_gray.ensure((size_t)F * npix * 4));
     HIPCHK(c, c->ws_seg.ensure((size_t)F * nseg * 32));
     HIPCHK(c, c->ws_segoff.ensure((size_t)F * nseg * 4));
     HIPCHK(c, c->ws_rawxy.ensure((size_t)F * raw_cap * 4));
     HIPCHK(c, c->ws_rawscore.ensure((size_t)F * raw_cap * 4));
-    const size_t nms_stride = pgx_nms_ws_bytes(W, H, c->radius, raw_cap, true);
     HIPCHK(c, c->ws_nms.ensure((size_t)F * nms_stride));
     const int kp_eff = c->kp_cap <= cap ? c->kp_cap : cap;
     HIPCHK(c, c->ws_order.ensure((size_t)F * kp_eff * 4));
     HIPCHK(c, c->ws_nkept.ensure((size_t)F * 4));
+    if (pl.n_levels > 1) {
+        HIPCHK(c, c->ws_pyr_cnt.ensure((size_t)16 * F * 4));
+        if (pl.n_run > 1) {
+            const size_t slots = (size_t)(pl.n_run - 1) * F * kp_eff;
+            HIPCHK(c, c->ws_pyr_a.ensure((size_t)F * pl.dims[1][0] * pl.dims[1][1] * 4));
+            if (pl.n_run > 2) HIPCHK(c, c->ws_pyr_b.ensure((size_t)F * pl.dims[2][0] * pl.dims[2][1] * 4));
+            HIPCHK(c, c->ws_pyr_kp.ensure(slots * sizeof(pgx_keypoint)));
+            HIPCHK(c, c->ws_pyr_desc.ensure(slots * c->words * 4));
+            if (c->steer_on) HIPCHK(c, c->ws_pyr_bins.ensure(slots * 4));
+        }
+    }
     return PGX_OK;
 }
 
@@ -152,26 +192,13 @@ PgxSteer steer_of(const pgx_ctx *c, int32_t *d_bins = nullptr)
                     c->steer_R, d_bins};
 }
 
-// detect chain on device-resident frames (enqueue only); d_bins (steered mode only, optional): each survivor's direction
-int enqueue_detect_bins(pgx_ctx *c, const uint16_t *d_rgba, int F, int W, int H, pgx_keypoint *d_kp, uint32_t *d_desc,
-                        int32_t *d_counts, int32_t *d_nraw, int cap, int32_t *d_bins)
+// the chain behind the grey image, FAST -> NMS -> BRIEF, on F grey images of W x H (enqueue only): survivor lists of
+// out_stride slots per frame
+void enqueue_from_gray(pgx_ctx *c, const float *gray, int F, int W, int H, int kp_eff, bool kp_soft, pgx_keypoint *d_kp,
+                       uint32_t *d_desc, int32_t *d_counts, int32_t *d_nraw, int out_stride, int32_t *d_bins)
 {
-    const int rcp = pgx_prepare_detect(c, F, W, H, cap);
-    if (rcp != PGX_OK) return rcp;
-    if (F <= 0) return PGX_OK;
     const int raw_cap = c->raw_cap;
     const size_t nms_stride = pgx_nms_ws_bytes(W, H, c->radius, raw_cap, true);
-    // pgx_set_capacity's survivor limit: lists are cut to their first kp_cap entries (NMS order) without an error;
-    // only an overflow of the caller's own `cap` raises PGX_E_CAPACITY
-    const bool kp_soft = c->kp_cap <= cap;
-    const int kp_eff = kp_soft ? c->kp_cap : cap;
-
-    float *gray = c->ws_gray.as<float>();
-    {
-        ProfScope ps(c, "dewarp_gray");
-        pgx_launch_dewarp_gray(c->stream, d_rgba, c->src8, c->map_set ? c->d_map.as<int32_t>() : nullptr, F, W, H, gray,
-                               nullptr, c->d_status);
-    }
     {
         ProfScope ps(c, "fast");
         pgx_launch_fast(c->stream, gray, F, W, H, c->threshold, c->ws_seg.as<unsigned long long>(),
@@ -190,7 +217,59 @@ int enqueue_detect_bins(pgx_ctx *c, const uint16_t *d_rgba, int F, int W, int H,
         const PgxSteer st = steer_of(c, d_bins);
         pgx_launch_brief(c->stream, gray, F, W, H, c->ws_rawxy.as<uint32_t>(), c->ws_rawscore.as<int32_t>(), raw_cap,
                          c->ws_order.as<uint32_t>(), c->ws_nkept.as<int32_t>(), kp_eff, c->d_pairs.as<int32_t>(), c->d_plan.as<int32_t>(), c->P,
-                         d_kp, d_desc, d_counts, cap, c->steer_on ? &st : nullptr);
+                         d_kp, d_desc, d_counts, out_stride, c->steer_on ? &st : nullptr);
+    }
+}
+
+// detect chain on device-resident frames (enqueue only); d_bins (steered mode only, optional): each survivor's direction.
+// Pyramid mode: the chain behind the grey image runs once per level, level 0 straight into the caller's buffers, and
+// k_pyr_append merges the rest behind it; d_origin / d_stats (optional) as pgx_detect_batch_pyramid_dev describes them.
+int enqueue_detect_bins(pgx_ctx *c, const uint16_t *d_rgba, int F, int W, int H, pgx_keypoint *d_kp, uint32_t *d_desc,
+                        int32_t *d_counts, int32_t *d_nraw, int cap, int32_t *d_bins, int32_t *d_origin = nullptr,
+                        int32_t *d_stats = nullptr)
+{
+    const int rcp = pgx_prepare_detect(c, F, W, H, cap);
+    if (rcp != PGX_OK) return rcp;
+    if (F <= 0) return PGX_OK;
+    // pgx_set_capacity's survivor limit: lists are cut to their first kp_cap entries (NMS order) without an error;
+    // only an overflow of the caller's own `cap` raises PGX_E_CAPACITY
+    const bool kp_soft = c->kp_cap <= cap;
+    const int kp_eff = kp_soft ? c->kp_cap : cap;
+
+    float *gray = c->ws_gray.as<float>();
+    {
+        ProfScope ps(c, "dewarp_gray");
+        pgx_launch_dewarp_gray(c->stream, d_rgba, c->src8, c->map_set ? c->d_map.as<int32_t>() : nullptr, F, W, H, gray,
+                               nullptr, c->d_status);
+    }
+    if (c->pyr_levels <= 1) {
+        enqueue_from_gray(c, gray, F, W, H, kp_eff, kp_soft, d_kp, d_desc, d_counts, d_nraw, cap, d_bins);
+    } else {
+        const PyrPlan pl = pyr_plan(c, W, H);
+        int32_t *lvl_counts = c->ws_pyr_cnt.as<int32_t>(), *lvl_nraw = lvl_counts + (size_t)8 * F;
+        const size_t lvl_slots = (size_t)F * kp_eff;
+        int32_t *tmp_bins = d_bins ? c->ws_pyr_bins.as<int32_t>() : nullptr;
+        enqueue_from_gray(c, gray, F, W, H, kp_eff, kp_soft, d_kp, d_desc, lvl_counts, lvl_nraw, cap, d_bins);
+        const float *src = gray;
+        for (int l = 1; l < pl.n_run; l++) {
+            float *dst = (l & 1) ? c->ws_pyr_a.as<float>() : c->ws_pyr_b.as<float>();
+            {
+                ProfScope ps(c, "pyramid");
+                pgx_launch_pyr_down(c->stream, src, F, pl.dims[l - 1][0], pl.dims[l - 1][1], dst, pl.dims[l][0], pl.dims[l][1],
+                                    c->pyr_step);
+            }
+            enqueue_from_gray(c, dst, F, pl.dims[l][0], pl.dims[l][1], kp_eff, kp_soft,
+                              c->ws_pyr_kp.as<pgx_keypoint>() + (l - 1) * lvl_slots,
+                              c->ws_pyr_desc.as<uint32_t>() + (l - 1) * lvl_slots * c->words, lvl_counts + (size_t)l * F,
+                              lvl_nraw + (size_t)l * F, kp_eff, tmp_bins ? tmp_bins + (l - 1) * lvl_slots : nullptr);
+            src = dst;
+        }
+        {
+            ProfScope ps(c, "pyramid_append");
+            pgx_launch_pyr_append(c->stream, c->ws_pyr_kp.as<pgx_keypoint>(), c->ws_pyr_desc.as<uint32_t>(), tmp_bins, lvl_counts,
+                                  lvl_nraw, F, kp_eff, c->words, pl.n_levels, pl.n_run, W, H, pl.scale, d_kp, d_desc, d_bins,
+                                  d_counts, d_nraw, d_origin, d_stats, cap, c->d_status);
+        }
     }
     HIPCHK(c, hipEventRecord(c->ev_stage[PGX_STAGE_DETECT], c->stream));
     HIPCHK(c, hipGetLastError());
@@ -368,7 +447,8 @@ void pgx_ctx_destroy(pgx_ctx *c)
     for (hipEvent_t ev : c->ev_pool) (void)hipEventDestroy(ev);
     DevBuf *bufs[] = {&c->d_pairs, &c->d_plan, &c->d_steer_pairs, &c->d_steer_plans, &c->d_steer_dirs, &c->d_map, &c->ws_gray, &c->ws_seg, &c->ws_segoff, &c->ws_nraw, &c->ws_rawxy,
                       &c->ws_rawscore, &c->ws_nms, &c->ws_order, &c->ws_nkept, &c->st_a, &c->st_b, &c->st_c,
-                      &c->st_d, &c->st_e, &c->st_f, &c->ws_pose, &c->ws_tracks, &c->ws_tracks_split, &c->ws_agree, &c->ws_matchn[0], &c->ws_matchn[1], &c->ws_matchn[2], &c->ws_knn, &c->ws_guided, &c->ws_tri, &c->ws_ba, &c->ws_reg};
+                      &c->st_d, &c->st_e, &c->st_f, &c->ws_pose, &c->ws_tracks, &c->ws_tracks_split, &c->ws_agree, &c->ws_matchn[0], &c->ws_matchn[1], &c->ws_matchn[2], &c->ws_knn, &c->ws_guided, &c->ws_tri, &c->ws_ba, &c->ws_reg,
+                      &c->ws_pyr_a, &c->ws_pyr_b, &c->ws_pyr_kp, &c->ws_pyr_desc, &c->ws_pyr_bins, &c->ws_pyr_cnt};
     for (DevBuf *b : bufs) b->release();
     c->pin_in.release();
     c->pin_out.release();
@@ -504,6 +584,17 @@ int pgx_set_brief_steering(pgx_ctx *c, const int32_t *pairs_rot, const int32_t *
         HIPCHK(c, hipMemcpy(c->d_steer_plans.p, plans.data(), plans.size() * 4, hipMemcpyHostToDevice));
     }
     c->steer_B = B; c->steer_R = radius; c->steer_on = true;
+    return PGX_OK;
+}
+
+int pgx_set_pyramid(pgx_ctx *c, int n_levels, int step_q16)
+{
+    if (!c) return PGX_E_BADARG;
+    Lock l(c);
+    c->cfg_epoch++;
+    if (n_levels < 1 || n_levels > 8) return fail(c, PGX_E_BADARG, "n_levels must be in [1, 8]");
+    if (step_q16 < 69632 || step_q16 > 131072) return fail(c, PGX_E_BADARG, "step_q16 must be in [69632, 131072] (1.0625 ... 2.0)");
+    c->pyr_levels = n_levels; c->pyr_step = step_q16;
     return PGX_OK;
 }
 
@@ -681,6 +772,31 @@ int pgx_orient(pgx_ctx *c, const float *gray, int W, int H, const pgx_keypoint *
     HIPCHK(c, hipMemcpyAsync(c->st_b.p, kps, (size_t)n * sizeof(pgx_keypoint), hipMemcpyHostToDevice, c->stream));
     pgx_launch_orient_list(c->stream, c->st_a.as<float>(), W, H, c->st_b.as<pgx_keypoint>(), n, steer_of(c), c->st_c.as<int32_t>());
     HIPCHK(c, hipMemcpyAsync(bins_out, c->st_c.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    return sync_status(c);
+}
+
+int pgx_pyramid_level(pgx_ctx *c, const float *gray, int W, int H, int level, float *out)
+{
+    if (!c || !gray || !out) return c ? fail(c, PGX_E_BADARG, "null pointer") : PGX_E_BADARG;
+    Lock l(c);
+    if (c->pyr_levels <= 1) return fail(c, PGX_E_NOT_CONFIGURED, "pgx_set_pyramid not called (or called with one level)");
+    if (dims_ok(c, W, H) != PGX_OK) return PGX_E_BADARG;
+    const PyrPlan pl = pyr_plan(c, W, H);
+    if (level < 0 || level >= pl.n_levels) return fail(c, PGX_E_BADARG, "level %d outside [0, %d)", level, pl.n_levels);
+    if (level >= pl.n_run) return fail(c, PGX_E_BADARG, "level %d of a %dx%d image is empty", level, W, H);
+    const size_t npix = (size_t)W * H;
+    HIPCHK(c, c->st_a.ensure(npix * 4 + 32));
+    if (level >= 1) HIPCHK(c, c->st_b.ensure((size_t)pl.dims[1][0] * pl.dims[1][1] * 4 + 32));
+    if (level >= 2) HIPCHK(c, c->st_c.ensure((size_t)pl.dims[2][0] * pl.dims[2][1] * 4 + 32));
+    HIPCHK(c, hipMemcpyAsync(c->st_a.p, gray, npix * 4, hipMemcpyHostToDevice, c->stream));
+    const float *src = c->st_a.as<float>();
+    for (int k = 1; k <= level; k++) {
+        float *dst = (k & 1) ? c->st_b.as<float>() : c->st_c.as<float>();
+        ProfScope ps(c, "pyramid");
+        pgx_launch_pyr_down(c->stream, src, 1, pl.dims[k - 1][0], pl.dims[k - 1][1], dst, pl.dims[k][0], pl.dims[k][1], c->pyr_step);
+        src = dst;
+    }
+    HIPCHK(c, hipMemcpyAsync(out, src, (size_t)pl.dims[level][0] * pl.dims[level][1] * 4, hipMemcpyDeviceToHost, c->stream));
     return sync_status(c);
 }
 
@@ -903,6 +1019,19 @@ int pgx_detect_batch_steered_dev(pgx_ctx *c, const uint16_t *d_rgba, int F, int 
     if (!c->steer_on) return fail(c, PGX_E_NOT_CONFIGURED, "pgx_set_brief_steering not called");
     if (dims_ok(c, W, H) != PGX_OK) return PGX_E_BADARG;
     return enqueue_detect_bins(c, d_rgba, F, W, H, d_kp, d_desc, d_counts, d_nraw, capacity, d_bins);
+}
+
+int pgx_detect_batch_pyramid_dev(pgx_ctx *c, const uint16_t *d_rgba, int F, int W, int H, pgx_keypoint *d_kp, uint32_t *d_desc,
+                                 int32_t *d_counts, int32_t *d_nraw, int capacity, int32_t *d_origin, int32_t *d_level_stats,
+                                 int32_t *d_bins)
+{
+    if (!c || !d_rgba || !d_kp || !d_desc || !d_counts || !d_nraw || !d_origin || !d_level_stats || capacity <= 0 || F < 0)
+        return c ? fail(c, PGX_E_BADARG, "null pointer") : PGX_E_BADARG;
+    Lock l(c);
+    if (c->pyr_levels <= 1) return fail(c, PGX_E_NOT_CONFIGURED, "pgx_set_pyramid not called (or called with one level)");
+    if (d_bins && !c->steer_on) return fail(c, PGX_E_NOT_CONFIGURED, "d_bins given but pgx_set_brief_steering not called");
+    if (dims_ok(c, W, H) != PGX_OK) return PGX_E_BADARG;
+    return enqueue_detect_bins(c, d_rgba, F, W, H, d_kp, d_desc, d_counts, d_nraw, capacity, d_bins, d_origin, d_level_stats);
 }
 
 int pgx_match_batch_dev(pgx_ctx *c, const uint32_t *d_desc, const int32_t *d_counts, int stride, int words,

@@ -152,3 +152,24 @@ extern "C" int pgx_build_dewarp_map(int W, int H, const double *k, int ncoeffs, 
     }
     return PGX_OK;
 }
+
+// rules 1 and 2 of pgx_set_pyramid (include/pgx.h): level sizes and each level's scale back to level 0
+extern "C" int pgx_pyramid_dims(int W, int H, int n_levels, int step_q16, int32_t *dims_out, int32_t *scale_out)
+{
+    if (W <= 0 || H <= 0 || W > 65535 || H > 65535 || n_levels < 1 || n_levels > 8 || step_q16 < 69632 || step_q16 > 131072)
+        return PGX_E_BADARG;
+    int64_t w = W, h = H;
+    uint64_t s = 65536;
+    bool empty = false;
+    for (int l = 0; l < n_levels; l++) {
+        if (l > 0) {
+            w = (w * 65536) / step_q16;
+            h = (h * 65536) / step_q16;
+            s = (s * (uint64_t)step_q16 + 32768) >> 16;
+            if (w < 16 || h < 16) empty = true;
+        }
+        if (dims_out) { dims_out[2 * l] = empty ? 0 : (int32_t)w; dims_out[2 * l + 1] = empty ? 0 : (int32_t)h; }
+        if (scale_out) scale_out[l] = (int32_t)s;
+    }
+    return PGX_OK;
+}

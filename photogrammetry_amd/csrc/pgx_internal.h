@@ -110,6 +110,8 @@ struct pgx_ctx {
     bool steer_on = false;
     int steer_B = 0, steer_R = 0;
     DevBuf d_steer_pairs, d_steer_plans, d_steer_dirs;
+    // scale pyramid (pgx_set_pyramid; off = 1 level): levels and the 16.16 step between them
+    int pyr_levels = 1, pyr_step = 0;
     int mapW = 0, mapH = 0;
     bool map_set = false;
     DevBuf d_map;
@@ -128,6 +130,10 @@ struct pgx_ctx {
 
     // detect workspaces
     DevBuf ws_gray, ws_seg, ws_segoff, ws_nraw, ws_rawxy, ws_rawscore, ws_nms, ws_order, ws_nkept;
+    // pyramid mode: two level images per frame (level l reads one and writes the other), the lists of levels >= 1
+    // ([levels - 1][F][list stride] keypoints, descriptors and, in steered mode, bins) and the level counts ([8][F] survivors,
+    // [8][F] raw hits)
+    DevBuf ws_pyr_a, ws_pyr_b, ws_pyr_kp, ws_pyr_desc, ws_pyr_bins, ws_pyr_cnt;
     // host-API staging
     DevBuf st_a, st_b, st_c, st_d, st_e, st_f;
     PinBuf pin_in, pin_out; // pgx_match_batch
@@ -285,6 +291,18 @@ void pgx_launch_steer_list(hipStream_t s, const float *gray, int W, int H, const
                            int P, uint32_t *desc_out);
 void pgx_launch_orient_list(hipStream_t s, const float *gray, int W, int H, const pgx_keypoint *kps, int n, const PgxSteer &st,
                             int32_t *bins_out);
+
+// k_pyramid.hip (scale pyramid; pgx_set_pyramid's rules, include/pgx.h)
+// level l of F frames from level l - 1: src [F][Hs][Ws] -> dst [F][Hd][Wd]
+void pgx_launch_pyr_down(hipStream_t s, const float *src, int F, int Ws, int Hs, float *dst, int Wd, int Hd, int step_q16);
+// the merge of rule 5.  Level 0 is already in kp / desc / bins ([F][cap]); levels 1 .. n_run - 1 come from tmp_kp / tmp_desc /
+// tmp_bins ([n_levels - 1][F][tmp_stride]); lvl_counts / lvl_nraw [.][F] hold the levels' survivors and raw hits (level-major,
+// read for levels < n_run); scale [n_levels] = S_l (host).  origin [F][cap][3], stats [F][n_levels][2], bins: optional.
+// A total above cap sets PGX_ST_KP_CAP.
+void pgx_launch_pyr_append(hipStream_t s, const pgx_keypoint *tmp_kp, const uint32_t *tmp_desc, const int32_t *tmp_bins,
+                           const int32_t *lvl_counts, const int32_t *lvl_nraw, int F, int tmp_stride, int words, int n_levels,
+                           int n_run, int W, int H, const int32_t *scale, pgx_keypoint *kp, uint32_t *desc, int32_t *bins,
+                           int32_t *counts, int32_t *nraw, int32_t *origin, int32_t *stats, int cap, int *status);
 
 // k_pose.hip
 size_t pgx_pose_ws_bytes(int M, int n_samples);
