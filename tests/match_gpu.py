@@ -59,7 +59,7 @@ def run_knn(engine, dev, stride, words, pl, k, col, sentinel=77, max_count=None,
     return idx.cpu().numpy(), dist.cpu().numpy(), (cnn.cpu().numpy() if col else None)
 
 
-def run_nn(engine, dev, stride, words, pl, max_dist, ratio, cross, sentinel=77, guide=None):
+def run_nn(engine, dev, stride, words, pl, max_dist, ratio, cross, sentinel=77, guide=None, max_count=None):
     """pgx_match_nn_batch_dev, or pgx_match_guided_batch_dev with guide = (F per pair, band) -> lists [M][stride][3]"""
     d_desc, d_kp, d_counts, _ = dev
     M = len(pl)
@@ -68,9 +68,10 @@ def run_nn(engine, dev, stride, words, pl, max_dist, ratio, cross, sentinel=77, 
     d_F, band = _guide(guide)
     torch.cuda.synchronize()
     if guide is None:
-        engine.match_nn_batch_dev(d_desc, d_counts, stride, words, d_pl, M, out, max_dist, ratio, cross)
+        engine.match_nn_batch_dev(d_desc, d_counts, stride, words, d_pl, M, out, max_dist, ratio, cross, max_count=max_count)
     else:
-        engine.match_guided_batch_dev(d_desc, d_kp, d_counts, stride, words, d_pl, M, d_F, band, out, max_dist, ratio, cross)
+        engine.match_guided_batch_dev(d_desc, d_kp, d_counts, stride, words, d_pl, M, d_F, band, out, max_dist, ratio, cross,
+                                      max_count=max_count)
     engine.check_status()
     return out.cpu().numpy()
 
