@@ -675,6 +675,67 @@ int pgx_register_frames(pgx_ctx *ctx, const pgx_keypoint *kps, const int32_t *co
                         int refine_iters, uint64_t seed, double *Rt_out, double *P_out, int32_t *frame_stats, double *frame_err,
                         int32_t *node_inlier, int32_t *report);
 
+/* ---- two-view geometric verification of match lists by epipolar RANSAC ----------------- */
+/* The stage between a matcher and the track graph: per image pair a robust fundamental matrix, the match list with
+ * everything but its inliers rejected (ready for pgx_tracks_dev), and F in the guided matcher's convention (d_F32 is
+ * accepted by pgx_match_guided_batch_dev as it is).  Not in the C# reference.
+ * Inputs: d_kp, d_matches, d_counts, d_pairlist, M, stride and max_dist as for pgx_tracks_dev; (a, b) = d_pairlist[m].
+ * Values.  Every value is a double, every operation one IEEE double operation in the order written, nothing is contracted
+ * into a fused multiply-add.
+ * Candidates.  Entry e < clamp(counts[a], 0, stride) of list m is a candidate when 0 <= k1 < counts[a], 0 <= k2 < counts[b]
+ * (both counts clamped to [0, stride]), dist <= max_dist and dist != PGX_DIST_NONE: pgx_tracks_dev's filters of an edge.
+ * Candidates keep their list order and get positions 0 .. n-1; with (x, y) = kp_a[k1] and (u, v) = kp_b[k2] a candidate gives
+ * h_a = (x, y, 1) and h_b = (u, v, 1).  n < 8: PGX_VER_FEWMATCHES (and no other flag).
+ * Samples.  For s in [0, n_samples): state = seed ^ ((uint64)(uint32)a << 32) ^ (uint64)(uint32)b * 0x9E3779B97F4A7C15 ^
+ * (uint64)s * 0xD1B54A32D192ED03; draw splitmix64(state) % n until there are 8 distinct positions (k_pose.hip's generator).
+ * The stream depends on the pair's slots, not on its place in the list.
+ * Fit: the normalised 8-point algorithm with rank 2 enforced, on a set S of correspondences.  Per image, c = the mean point
+ * and dbar = the mean of sqrt((x - cx)^2 + (y - cy)^2) (sums in the set's order for a sample, in a fixed launch-independent
+ * order for a refit); sc = sqrt(2) / dbar, dbar == 0 makes the set invalid; T = [[sc, 0, -sc cx], [0, sc, -sc cy], [0, 0, 1]],
+ * hh = T h (hh0 = sc x + (-(sc cx))); the row of a correspondence is r = (hha0 hhb0, hha0 hhb1, hha0, hha1 hhb0, hha1 hhb1,
+ * hha1, hhb0, hhb1, 1); G = sum r r^T; f = the eigenvector of G's smallest eigenvalue (cyclic Jacobi, sign: largest
+ * component positive); Fh = f row-major; v3 = the same of Fh^T Fh; Fh' = Fh - (Fh v3) v3^T; F = Ta^T Fh' Tb divided by its
+ * Frobenius norm.  A non-finite entry makes the fit invalid; an invalid sample has count -1 and a NaN F.
+ * Inlier predicate (the Sampson distance with no division and no square root), evaluated in this order:
+ *   m0 = (F00 u + F01 v) + F02;  m1 = (F10 u + F11 v) + F12;  m2 = (F20 u + F21 v) + F22;  e = (x m0 + y m1) + m2
+ *   l0 = (F00 x + F10 y) + F20;  l1 = (F01 x + F11 y) + F21;  d = ((l0 l0 + l1 l1) + m0 m0) + m1 m1;  T = inlier_px inlier_px
+ *   inlier iff d > 0 and e e <= T d
+ * Winner: the valid sample with the most inliers over all n candidates, ties to the smallest s (integers only: the grid
+ * does not matter).  No valid sample: PGX_VER_NOMODEL.
+ * Refit, up to refit_iters times: the fit on the whole current inlier set if it has at least 8 members; the new F is kept
+ * only if the fit is valid and its inlier count is strictly greater, otherwise the refits stop.
+ * Final inliers < min_inliers: PGX_VER_FEWINLIERS.  A pair that carries any flag is rejected whole.
+ * Outputs:
+ *   d_out [M][stride]  for e < clamp(counts[a], 0, stride): the input entry if it is a candidate, a final inlier and the pair
+ *           is accepted, (k1 of the input entry, -1, PGX_DIST_NONE) otherwise (never linked by the track graph); entries at
+ *           and beyond that are not written.  d_out may alias d_matches.
+ *   d_F [M][9]         the final F row-major: NaN for FEWMATCHES and NOMODEL, kept for FEWINLIERS
+ *   d_F32 [M][9] or NULL  d_F rounded to float32
+ *   d_stats [M][8] int32: n candidates, the winner's count, the final count, the winning sample or -1, the flags, refits
+ *           kept, valid samples, 0 (counts are 0 without a winner)
+ *   d_inlier [M][stride] or NULL, for the entries d_out writes: 1 candidate and final inlier (of the final F, also in a
+ *           rejected pair), 0 candidate and outlier, -1 not a candidate
+ *   d_sample_F [M][n_samples][9], d_sample_count [M][n_samples], each or NULL: every sample's F (NaN when invalid) and count
+ *   d_report [8] int32: pairs, accepted pairs, pairs with FEWMATCHES, with NOMODEL, with FEWINLIERS, candidates of all
+ *           pairs, final inliers of accepted pairs, 0
+ * Returned at once (PGX_E_BADARG): n_samples outside [1, 65536], inlier_px <= 0 or not finite, min_inliers < 8, refit_iters
+ * outside [0, 8], M < 0, stride outside [1, 2^20], a null required pointer.  A pair with counts[a] == 0 is FEWMATCHES.
+ * Results depend on the inputs only: the same bits from run to run, for any order of the pair list, for any
+ * pgx_set_match_chunk, and from the host form below.  Asynchronous on the context's stream. */
+#define PGX_VER_FEWMATCHES 1   /* fewer than 8 candidate entries */
+#define PGX_VER_NOMODEL    2   /* no sample gave a finite F */
+#define PGX_VER_FEWINLIERS 4   /* final inliers < min_inliers */
+int pgx_verify_pairs_dev(pgx_ctx *ctx, const pgx_keypoint *d_kp, const pgx_pair *d_matches, const int32_t *d_counts,
+                         const int32_t *d_pairlist, int M, int stride, int max_dist, int n_samples, double inlier_px,
+                         int min_inliers, int refit_iters, uint64_t seed, pgx_pair *d_out, double *d_F, float *d_F32,
+                         int32_t *d_stats, int32_t *d_inlier, double *d_sample_F, int32_t *d_sample_count, int32_t *d_report);
+/* Host form: one pair on host arrays, the same kernels with frame a in slot 1 and frame b in slot 2 (so the bits are those
+ * of the device form for the pair (1, 2)).  matches, out and inlier hold n1 entries; F [9], stats [8]; inlier may be NULL.
+ * n1 or n2 < 0 or above 2^20: PGX_E_BADARG.  Returns when the outputs are in the caller's buffers. */
+int pgx_verify_pair(pgx_ctx *ctx, const pgx_keypoint *kp1, int n1, const pgx_keypoint *kp2, int n2, const pgx_pair *matches,
+                    int max_dist, int n_samples, double inlier_px, int min_inliers, int refit_iters, uint64_t seed, pgx_pair *out,
+                    double *F, int32_t *stats, int32_t *inlier);
+
 /* ---- measurement hooks (bench.py) ---------------------------------------------------- */
 /* When on, the named hot kernels are bracketed by HIP events on the launch stream. */
 int pgx_profile_enable(pgx_ctx *ctx, int on);

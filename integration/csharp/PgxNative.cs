@@ -24,6 +24,7 @@ internal static unsafe class PgxNative
     public const int CommIdBytes = 128;                                                   // PGX_COMM_ID_BYTES
     public const int TriFewViews = 1, TriDegenerate = 2, TriBehind = 4, TriParallax = 8, TriReproj = 16;   // PGX_TRI_* (0 = valid)
     public const int RegBadK = 1, RegFewPoints = 2, RegNoSolution = 4, RegFewInliers = 8;   // PGX_REG_* (0 = registered)
+    public const int VerFewMatches = 1, VerNoModel = 2, VerFewInliers = 4;                 // PGX_VER_* (0 = accepted)
 
     // Exports of include/pgx.h that this binding deliberately leaves out (tests/test_csharp_binding.py holds the list to the
     // header): the caller's-HIP-stream hook and the measurement hooks (a managed host owns no hipStream_t and reads no HIP event
@@ -169,6 +170,20 @@ internal static unsafe class PgxNative
                                                                   int minInliers, int refineIters, ulong seed, double* rtOut,
                                                                   double* pOut, int* frameStats, double* frameErr, int* nodeInlier,
                                                                   int* report);
+
+    // two-view verification of match lists by epipolar RANSAC, between a matcher and pgx_tracks_dev: dOut [m][stride] (may be
+    // dMatches), dF [m][9] float64, dF32 [m][9] float32 or null (what pgx_match_guided_batch_dev takes), dStats [m][8],
+    // dInlier [m][stride] or null, dSampleF [m][nSamples][9] and dSampleCount [m][nSamples] or null, dReport [8]; the host form
+    // runs one pair (matches, output and inlier hold n1 entries)
+    [DllImport(Lib)] public static extern int pgx_verify_pairs_dev(IntPtr ctx, void* dKp, void* dMatches, void* dCounts, void* dPairlist,
+                                                                   int m, int stride, int maxDist, int nSamples, double inlierPx,
+                                                                   int minInliers, int refitIters, ulong seed, void* dOut, void* dF,
+                                                                   void* dF32, void* dStats, void* dInlier, void* dSampleF,
+                                                                   void* dSampleCount, void* dReport);
+    [DllImport(Lib)] public static extern int pgx_verify_pair(IntPtr ctx, PgxKeypoint* kp1, int n1, PgxKeypoint* kp2, int n2,
+                                                              PgxPair* matches, int maxDist, int nSamples, double inlierPx,
+                                                              int minInliers, int refitIters, ulong seed, PgxPair* output, double* f,
+                                                              int* stats, int* inlier);
 
     /// <summary>Maps a status code back to the exception type the managed implementation throws.</summary>
     public static void Check(IntPtr ctx, int rc)

@@ -89,6 +89,8 @@ SIGNATURES = {
     "pgx_bundle_adjust": (I, [P, P, P, I, P, P, P, P, P, I, P, P, I, D, D, P, P, P, P, P, P]),
     "pgx_register_frames_dev": (I, [P, P, I, I, P, I, P, P, P, P, P, P, I, P, P, I, D, I, I, U64, P, P, P, P, P, P]),
     "pgx_register_frames": (I, [P, P, P, I, P, P, P, P, P, I, P, P, I, D, I, I, U64, P, P, P, P, P, P]),
+    "pgx_verify_pairs_dev": (I, [P, P, P, P, P, I, I, I, I, D, I, I, U64, P, P, P, P, P, P, P, P]),
+    "pgx_verify_pair": (I, [P, P, I, P, I, P, I, I, D, I, I, U64, P, P, P, P]),
     "pgx_profile_enable": (I, [P, I]),
     "pgx_profile_filter": (I, [P, S]),
     "pgx_profile_get": (I, [P, S, P, P]),

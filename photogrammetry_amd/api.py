@@ -541,6 +541,38 @@ class Engine:
             _ptr(P_out), _ptr(stats), _ptr(ferr), _ptr(ni), _ptr(report)))
         return dict(Rt=Rt_out, P=P_out, frame_stats=stats, frame_err=ferr, node_inlier=ni[:n_nodes], report=report)
 
+    # -- two-view verification of match lists by epipolar RANSAC (pgx_verify_pair*) ------------------------
+    def verify_pairs_dev(self, d_kp, d_matches, d_counts, d_pairlist, M, stride, max_dist, d_out, d_F, d_stats, d_report,
+                         n_samples=256, inlier_px=1.5, min_inliers=24, refit_iters=2, seed=0, d_F32=None, d_inlier=None,
+                         d_sample_F=None, d_sample_count=None):
+        """A robust fundamental matrix per image pair and the match lists with everything but its inliers rejected, where they
+        sit in HBM (pgx.h: two-view geometric verification).  d_matches / d_out [M][stride] PAIR_DTYPE (d_out may be
+        d_matches), d_F [M][9] float64, d_F32 [M][9] float32 or None (what match_guided_batch_dev takes), d_stats [M][8] int32,
+        d_inlier [M][stride] int32 or None, d_sample_F [M][n_samples][9] float64 and d_sample_count [M][n_samples] int32 or
+        None, d_report [8] int32.  No sync."""
+        self._chk(self._L.pgx_verify_pairs_dev(
+            self._h, _dptr(d_kp), _dptr(d_matches), _dptr(d_counts), _dptr(d_pairlist), int(M), int(stride), int(max_dist),
+            int(n_samples), inlier_px, int(min_inliers), int(refit_iters), seed, _dptr(d_out), _dptr(d_F), _dptr(d_F32),
+            _dptr(d_stats), _dptr(d_inlier), _dptr(d_sample_F), _dptr(d_sample_count), _dptr(d_report)))
+
+    def verify_pair(self, kp1, kp2, matches, max_dist, n_samples=256, inlier_px=1.5, min_inliers=24, refit_iters=2, seed=0):
+        """The host form (pgx_verify_pair): one pair, frame a in slot 1 and frame b in slot 2.  kp1, kp2: KEYPOINT_DTYPE
+        arrays; matches: PAIR_DTYPE array (or int32 [n1][3]) of len(kp1) entries.
+        -> dict(out [n1] PAIR_DTYPE, F [9], stats [8], inlier [n1])"""
+        k1 = np.ascontiguousarray(kp1, dtype=KEYPOINT_DTYPE)
+        k2 = np.ascontiguousarray(kp2, dtype=KEYPOINT_DTYPE)
+        n1, n2 = len(k1), len(k2)
+        ml = np.ascontiguousarray(matches)
+        ml = ml if ml.dtype == PAIR_DTYPE else np.ascontiguousarray(ml, dtype=np.int32).reshape(-1, 3).view(PAIR_DTYPE).reshape(-1)
+        if len(ml) != n1:
+            raise ValueError("the match list must hold one entry per keypoint of the first frame")
+        out, inl = np.zeros(max(n1, 1), dtype=PAIR_DTYPE), np.zeros(max(n1, 1), dtype=np.int32)
+        F, stats = np.zeros(9), np.zeros(8, dtype=np.int32)
+        self._chk(self._L.pgx_verify_pair(
+            self._h, _ptr(k1) if n1 else None, n1, _ptr(k2) if n2 else None, n2, _ptr(ml) if n1 else None, int(max_dist),
+            int(n_samples), inlier_px, int(min_inliers), int(refit_iters), seed, _ptr(out), _ptr(F), _ptr(stats), _ptr(inl)))
+        return dict(out=out[:n1], F=F, stats=stats, inlier=inl[:n1])
+
     # -- multi-GPU: the context's own RCCL communicator (pgx_comm_*) ------------------------------
     def comm_init(self, rank, world, unique_id):
         """Collective: every rank calls this with the 128 bytes rank 0 got from comm_unique_id()."""

@@ -30,6 +30,7 @@
 namespace {
 
 constexpr int REG_NT = 256;         // threads per workgroup of every kernel here
+static_assert(REG_NT == 256, "block_sums (pgx_trackgraph.h) adds up four waves");
 constexpr int REG_G = 16;           // lanes per track in k_reg_count
 constexpr int REG_GRID_MAX = 1024;  // workgroups of k_reg_count, at most
 constexpr int REG_HD = 12;          // doubles per hypothesis: R row-major, t_S
@@ -601,21 +602,6 @@ __global__ __launch_bounds__(REG_NT) void k_reg_score(RegArgs a, int s0, int chu
         for (int w = 1; w < REG_NT / 64; w++) k = s_key[w] > k ? s_key[w] : k;
         a.best[(size_t)c * a.nblk + (4 * s0) / REG_NT + blockIdx.x] = k;
     }
-}
-
-// fixed-shape workgroup sum of NV values per thread: xor butterflies per wave, then the four waves in a fixed order
-template <int NV> __device__ __forceinline__ void block_sums(double (&v)[NV], double (*sh)[REG_NT / 64])
-{
-#pragma unroll
-    for (int k = 0; k < NV; k++) v[k] = gsum<64>(v[k]);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-        for (int k = 0; k < NV; k++) sh[k][w] = v[k];
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < NV; k++) v[k] = (sh[k][0] + sh[k][1]) + (sh[k][2] + sh[k][3]);
-    __syncthreads();
 }
 
 // cost of the pose over the inliers of (R0, t0): sum of squared pixel errors, division form

@@ -447,7 +447,7 @@ void pgx_ctx_destroy(pgx_ctx *c)
     for (hipEvent_t ev : c->ev_pool) (void)hipEventDestroy(ev);
     DevBuf *bufs[] = {&c->d_pairs, &c->d_plan, &c->d_steer_pairs, &c->d_steer_plans, &c->d_steer_dirs, &c->d_map, &c->ws_gray, &c->ws_seg, &c->ws_segoff, &c->ws_nraw, &c->ws_rawxy,
                       &c->ws_rawscore, &c->ws_nms, &c->ws_order, &c->ws_nkept, &c->st_a, &c->st_b, &c->st_c,
-                      &c->st_d, &c->st_e, &c->st_f, &c->ws_pose, &c->ws_tracks, &c->ws_tracks_split, &c->ws_agree, &c->ws_matchn[0], &c->ws_matchn[1], &c->ws_matchn[2], &c->ws_knn, &c->ws_guided, &c->ws_tri, &c->ws_ba, &c->ws_reg,
+                      &c->st_d, &c->st_e, &c->st_f, &c->ws_pose, &c->ws_tracks, &c->ws_tracks_split, &c->ws_agree, &c->ws_matchn[0], &c->ws_matchn[1], &c->ws_matchn[2], &c->ws_knn, &c->ws_guided, &c->ws_tri, &c->ws_ba, &c->ws_reg, &c->ws_ver,
                       &c->ws_pyr_a, &c->ws_pyr_b, &c->ws_pyr_kp, &c->ws_pyr_desc, &c->ws_pyr_bins, &c->ws_pyr_cnt};
     for (DevBuf *b : bufs) b->release();
     c->pin_in.release();
@@ -1419,6 +1419,39 @@ int reg_args(pgx_ctx *c, int n_samples, double inlier_px, int min_inliers, int r
     if (refine_iters < 0 || refine_iters > 32) return fail(c, PGX_E_BADARG, "refine_iters = %d, must be in [0, 32]", refine_iters);
     return PGX_OK;
 }
+
+int ver_args(pgx_ctx *c, int M, int stride, int n_samples, double inlier_px, int min_inliers, int refit_iters)
+{
+    if (M < 0) return fail(c, PGX_E_BADARG, "M = %d, must be >= 0", M);
+    if (stride < 1 || stride > (1 << PGX_IDX_BITS)) return fail(c, PGX_E_BADARG, "stride must be in [1, 2^20]");
+    if (n_samples < 1 || n_samples > 65536) return fail(c, PGX_E_BADARG, "n_samples = %d, must be in [1, 65536]", n_samples);
+    if (!(inlier_px > 0.0) || !std::isfinite(inlier_px)) return fail(c, PGX_E_BADARG, "inlier_px must be finite and > 0");
+    if (min_inliers < 8) return fail(c, PGX_E_BADARG, "min_inliers = %d, must be >= 8", min_inliers);
+    if (refit_iters < 0 || refit_iters > 8) return fail(c, PGX_E_BADARG, "refit_iters = %d, must be in [0, 8]", refit_iters);
+    return PGX_OK;
+}
+
+// the M pairs of a call in chunks of pgx_set_match_chunk pairs that share ws_ver, then the report
+int enqueue_verify(pgx_ctx *c, const pgx_keypoint *d_kp, const pgx_pair *d_matches, const int32_t *d_counts, const int32_t *d_pairlist,
+                   int M, int stride, int max_dist, int n_samples, double inlier_px, int min_inliers, int refit_iters, uint64_t seed,
+                   pgx_pair *d_out, double *d_F, float *d_F32, int32_t *d_stats, int32_t *d_inlier, double *d_sample_F,
+                   int32_t *d_sample_count, int32_t *d_report)
+{
+    const int CHUNK = c->match_chunk < 65535 ? c->match_chunk : 65535, mc = M < CHUNK ? M : CHUNK;
+    const int chunk = pgx_verify_chunk(mc, n_samples);   // one value for every launch: a shorter last chunk of pairs fits too
+    HIPCHK(c, c->ws_ver.ensure(pgx_verify_ws_bytes(mc, stride, n_samples, chunk)));
+    ProfScope ps(c, "verify");
+    for (int m0 = 0; m0 < M; m0 += CHUNK) {
+        const int n = M - m0 < CHUNK ? M - m0 : CHUNK;
+        const size_t o = (size_t)m0 * stride, os = (size_t)m0 * n_samples;
+        pgx_launch_verify(c->stream, d_kp, d_matches + o, d_counts, d_pairlist + 2 * (size_t)m0, n, stride, max_dist, n_samples,
+                          inlier_px, min_inliers, refit_iters, seed, d_out + o, d_F + 9 * (size_t)m0,
+                          d_F32 ? d_F32 + 9 * (size_t)m0 : nullptr, d_stats + 8 * (size_t)m0, d_inlier ? d_inlier + o : nullptr,
+                          d_sample_F ? d_sample_F + 9 * os : nullptr, d_sample_count ? d_sample_count + os : nullptr, chunk, c->ws_ver.p);
+    }
+    pgx_launch_verify_summary(c->stream, d_stats, M, d_report);
+    return PGX_OK;
+}
 } // namespace
 
 // ---- multi-view triangulation of tracks --------------------------------------------------------------------------
@@ -1633,6 +1666,71 @@ int pgx_register_frames(pgx_ctx *c, const pgx_keypoint *kps, const int32_t *coun
     HIPCHK(c, hipMemcpyAsync(frame_err, o + p_er, (size_t)n_frames * 16, hipMemcpyDeviceToHost, c->stream));
     if (node_inlier && n_nodes > 0) HIPCHK(c, hipMemcpyAsync(node_inlier, o + p_ni, (size_t)n_nodes * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(report, o + p_rep, 8 * 4, hipMemcpyDeviceToHost, c->stream));
+    return sync_status(c);
+}
+
+// ---- two-view verification by epipolar RANSAC ----------------------------------------------------------------------
+
+int pgx_verify_pairs_dev(pgx_ctx *c, const pgx_keypoint *d_kp, const pgx_pair *d_matches, const int32_t *d_counts,
+                         const int32_t *d_pairlist, int M, int stride, int max_dist, int n_samples, double inlier_px, int min_inliers,
+                         int refit_iters, uint64_t seed, pgx_pair *d_out, double *d_F, float *d_F32, int32_t *d_stats,
+                         int32_t *d_inlier, double *d_sample_F, int32_t *d_sample_count, int32_t *d_report)
+{
+    if (!c || !d_kp || !d_matches || !d_counts || !d_pairlist || !d_out || !d_F || !d_stats || !d_report)
+        return c ? fail(c, PGX_E_BADARG, "null pointer") : PGX_E_BADARG;
+    Lock l(c);
+    const int rc = ver_args(c, M, stride, n_samples, inlier_px, min_inliers, refit_iters);
+    if (rc != PGX_OK) return rc;
+    const int rq = enqueue_verify(c, d_kp, d_matches, d_counts, d_pairlist, M, stride, max_dist, n_samples, inlier_px, min_inliers,
+                                  refit_iters, seed, d_out, d_F, d_F32, d_stats, d_inlier, d_sample_F, d_sample_count, d_report);
+    if (rq != PGX_OK) return rq;
+    HIPCHK(c, hipGetLastError());
+    return PGX_OK;
+}
+
+int pgx_verify_pair(pgx_ctx *c, const pgx_keypoint *kp1, int n1, const pgx_keypoint *kp2, int n2, const pgx_pair *matches, int max_dist,
+                    int n_samples, double inlier_px, int min_inliers, int refit_iters, uint64_t seed, pgx_pair *out, double *F,
+                    int32_t *stats, int32_t *inlier)
+{
+    if (!c || !F || !stats || n1 < 0 || n2 < 0 || n1 > (1 << PGX_IDX_BITS) || n2 > (1 << PGX_IDX_BITS) ||
+        (n1 > 0 && (!kp1 || !matches || !out)) || (n2 > 0 && !kp2))
+        return c ? fail(c, PGX_E_BADARG, "null pointer or bad size") : PGX_E_BADARG;
+    Lock l(c);
+    const int S = n1 > n2 ? n1 : (n2 > 0 ? n2 : 1);
+    const int rc = ver_args(c, 1, S, n_samples, inlier_px, min_inliers, refit_iters);
+    if (rc != PGX_OK) return rc;
+    // inputs in st_a: keypoints [3][S] (slot 0 unused), the list [S], counts [3], the pair (1, 2); outputs in st_b
+    WsCarver in(nullptr), ot(nullptr);
+    const size_t i_kp = in.put((size_t)3 * S * sizeof(pgx_keypoint)), i_ml = in.put((size_t)S * sizeof(pgx_pair)), i_meta = in.put(64);
+    const size_t o_out = ot.put((size_t)S * sizeof(pgx_pair)), o_F = ot.put(72), o_st = ot.put(32), o_in = ot.put((size_t)S * 4),
+                 o_rep = ot.put(32);
+    HIPCHK(c, c->st_a.ensure(in.total()));
+    HIPCHK(c, c->st_b.ensure(ot.total()));
+    char *di = c->st_a.as<char>(), *dout = c->st_b.as<char>();
+    const int32_t meta[5] = {0, n1, n2, 1, 2};
+    HIPCHK(c, hipMemsetAsync(di, 0, in.total(), c->stream));
+    if (n1 > 0) {
+        HIPCHK(c, hipMemcpyAsync(di + i_kp + (size_t)S * sizeof(pgx_keypoint), kp1, (size_t)n1 * sizeof(pgx_keypoint), hipMemcpyHostToDevice,
+                                 c->stream));
+        HIPCHK(c, hipMemcpyAsync(di + i_ml, matches, (size_t)n1 * sizeof(pgx_pair), hipMemcpyHostToDevice, c->stream));
+    }
+    if (n2 > 0)
+        HIPCHK(c, hipMemcpyAsync(di + i_kp + (size_t)2 * S * sizeof(pgx_keypoint), kp2, (size_t)n2 * sizeof(pgx_keypoint), hipMemcpyHostToDevice,
+                                 c->stream));
+    HIPCHK(c, hipMemcpyAsync(di + i_meta, meta, sizeof meta, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));   // meta is on this call's stack
+    const int32_t *d_meta = reinterpret_cast<const int32_t *>(di + i_meta);
+    const int rq = enqueue_verify(c, reinterpret_cast<const pgx_keypoint *>(di + i_kp), reinterpret_cast<const pgx_pair *>(di + i_ml), d_meta,
+                                  d_meta + 3, 1, S, max_dist, n_samples, inlier_px, min_inliers, refit_iters, seed,
+                                  reinterpret_cast<pgx_pair *>(dout + o_out), reinterpret_cast<double *>(dout + o_F), nullptr,
+                                  reinterpret_cast<int32_t *>(dout + o_st), inlier ? reinterpret_cast<int32_t *>(dout + o_in) : nullptr,
+                                  nullptr, nullptr, reinterpret_cast<int32_t *>(dout + o_rep));
+    if (rq != PGX_OK) return rq;
+    HIPCHK(c, hipGetLastError());
+    if (n1 > 0) HIPCHK(c, hipMemcpyAsync(out, dout + o_out, (size_t)n1 * sizeof(pgx_pair), hipMemcpyDeviceToHost, c->stream));
+    if (inlier && n1 > 0) HIPCHK(c, hipMemcpyAsync(inlier, dout + o_in, (size_t)n1 * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(F, dout + o_F, 72, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(stats, dout + o_st, 32, hipMemcpyDeviceToHost, c->stream));
     return sync_status(c);
 }
 

@@ -146,6 +146,7 @@ struct pgx_ctx {
     DevBuf ws_tri;    // pgx_triangulate_tracks*: camera table, frame -> slot map, per-workgroup counters
     DevBuf ws_ba;     // pgx_bundle_adjust*: control block, cameras, reduced system, per-track and per-node state
     DevBuf ws_reg;    // pgx_register_frames*: target tables, correspondence lists, hypotheses of one chunk, scoring keys
+    DevBuf ws_ver;    // pgx_verify_pair*: candidate lists of a chunk of image pairs, hypotheses of one chunk of samples, keys
     hipStream_t mstream[3] = {nullptr, nullptr, nullptr}; // [0] wide rounds, [1] residual distance rows, [2] per-pair finish
     hipEvent_t ev_in = nullptr, ev_wide[3] = {nullptr, nullptr, nullptr}, ev_rows[3] = {nullptr, nullptr, nullptr},
                ev_fin[3] = {nullptr, nullptr, nullptr}, ev_join[3] = {nullptr, nullptr, nullptr};
@@ -394,3 +395,15 @@ void pgx_launch_register(hipStream_t s, const pgx_keypoint *d_kp, int F, int str
                          const double *d_xyz, const int32_t *d_track_flags, int n_samples, double inlier_px, int min_inliers,
                          int refine_iters, uint64_t seed, double *d_Rt_out, double *d_P_out, int32_t *d_frame_stats,
                          double *d_frame_err, int32_t *d_node_inlier, int32_t *d_report, void *ws, int *status);
+
+// k_verify.hip (two-view verification by epipolar RANSAC; pgx_verify_pairs_dev semantics, include/pgx.h)
+// samples per chunk for a workspace of M pairs (a multiple of 256), and the bytes of that workspace: not less for more pairs
+int pgx_verify_chunk(int M, int n_samples);
+size_t pgx_verify_ws_bytes(int M, int stride, int n_samples, int chunk);
+// M <= 65535 pairs that share the workspace; every pointer is the first of those pairs' rows.  chunk: the workspace's
+void pgx_launch_verify(hipStream_t s, const pgx_keypoint *d_kp, const pgx_pair *d_matches, const int32_t *d_counts,
+                       const int32_t *d_pairlist, int M, int stride, int max_dist, int n_samples, double inlier_px, int min_inliers,
+                       int refit_iters, uint64_t seed, pgx_pair *d_out, double *d_F, float *d_F32, int32_t *d_stats,
+                       int32_t *d_inlier, double *d_sample_F, int32_t *d_sample_count, int chunk, void *ws);
+// d_report from the d_stats rows of all M pairs of a call
+void pgx_launch_verify_summary(hipStream_t s, const int32_t *d_stats, int M, int32_t *d_report);

@@ -1,6 +1,6 @@
 // pgx_trackgraph.h -- what every consumer of the track graph shares (k_triangulate.hip, k_bundle.hip, k_register.hip):
-// the read-only view of the graph and the keypoints, its validation and walking on the device, the lane-group
-// reductions, and the workspace carver of the launchers.  Internal to libpgx.so; DESIGN.md section 14a.
+// the read-only view of the graph and the keypoints, its validation and walking on the device, the lane-group and
+// workgroup reductions (k_verify.hip uses those too), and the workspace carver of the launchers.  Internal to libpgx.so; DESIGN.md section 14a.
 #pragma once
 
 #include "pgx_internal.h"
@@ -123,6 +123,22 @@ template <int G> __device__ __forceinline__ double gmax(double x)
 #pragma unroll
     for (int m = 1; m < G; m <<= 1) x = nan_max(x, __shfl_xor(x, m, G));
     return x;
+}
+
+// Fixed-shape sum over a workgroup of 256 threads of NV values per thread: xor butterflies per wave, then the four waves in a
+// fixed order; identical bits in every thread.  sh: NV rows of LDS.
+template <int NV> __device__ __forceinline__ void block_sums(double (&v)[NV], double (*sh)[4])
+{
+#pragma unroll
+    for (int k = 0; k < NV; k++) v[k] = gsum<64>(v[k]);
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0)
+#pragma unroll
+        for (int k = 0; k < NV; k++) sh[k][w] = v[k];
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < NV; k++) v[k] = (sh[k][0] + sh[k][1]) + (sh[k][2] + sh[k][3]);
+    __syncthreads();
 }
 
 // ---- cameras ----------------------------------------------------------------------------------------------------------
