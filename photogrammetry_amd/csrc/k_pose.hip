@@ -20,8 +20,8 @@
 //
 // One thread per RANSAC sample (the work of a sample is a 9x9 symmetric eigenproblem plus one pass over the pair's
 // match list); a second kernel per image pair picks the first best sample; a third does the pose.
-#include "pgx_trackgraph.h"   // splitmix64
-#include "pgx_eig.h"          // jacobi_eig, smallest_eigvec
+#include "pgx_ransac.h"   // the sampler, the "first best sample" key and its reductions
+#include "pgx_eig.h"      // jacobi_eig, smallest_eigvec
 
 namespace {
 
@@ -59,16 +59,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
     int *outc = reinterpret_cast<int *>(out + 9);
     if (pv.n < P) { *outc = -1; return; } // CameraPoseEstimation.cs:31-32 (InvalidOperationException)
     // the subset: P distinct positions of the match list (OrderBy(random).Take(P), :42)
-    uint64_t st = seed ^ ((uint64_t)(uint32_t)m << 32) ^ (uint64_t)(uint32_t)s * 0xD1B54A32D192ED03ull;
+    uint64_t st = ransac_stream(seed, m, s);
     int idx[64];
-    for (int k = 0; k < P; k++) {
-        while (true) {
-            const int c = (int)(splitmix64(st) % (uint64_t)pv.n);
-            bool dup = false;
-            for (int j = 0; j < k; j++) dup |= idx[j] == c;
-            if (!dup) { idx[k] = c; break; }
-        }
-    }
+    ransac_draw(st, pv.n, P, idx);
     // CalculateCentroid / CalculateTransformationMatrix (:252-288): float64 sums, float32 matrix entries, scale == 1
     double c1x = 0, c1y = 0, c2x = 0, c2y = 0;
     for (int k = 0; k < P; k++) {
@@ -179,28 +172,23 @@ __global__ __launch_bounds__(256) void k_fund_score(const pgx_keypoint *__restri
 __global__ __launch_bounds__(256) void k_fund_pick(const float *__restrict__ rec, int n_samples, float *__restrict__ F_out,
                                                    int32_t *__restrict__ inliers, int32_t *__restrict__ best_sample)
 {
-    __shared__ unsigned long long best;
+    __shared__ unsigned long long s_key[256 / 64];
     const int m = blockIdx.x;
-    if (threadIdx.x == 0) best = 0ull;
-    __syncthreads();
-    unsigned long long k = 0ull;
+    unsigned long long best = 0ull;
     for (int s = threadIdx.x; s < n_samples; s += 256) {
         const int c = *reinterpret_cast<const int *>(rec + ((size_t)m * n_samples + s) * REC + 9);
-        if (c > 0) { // bestSample starts empty: a sample needs at least one inlier to replace it
-            const unsigned long long key = ((unsigned long long)(uint32_t)c << 32) | (uint32_t)(0x7FFFFFFF - s);
-            k = key > k ? key : k;
-        }
+        const unsigned long long key = ransac_key(c > 0, c, s); // bestSample starts empty: a sample needs at least one inlier to replace it
+        best = key > best ? key : best;
     }
-    atomicMax(&best, k);
-    __syncthreads();
+    best = ransac_block_max<256>(best, s_key);
     if (threadIdx.x == 0) {
         if (best == 0ull) { // every sample skipped or without inliers: the reference throws (:88-89); the library reports -1
             inliers[m] = -1;
             best_sample[m] = -1;
             for (int i = 0; i < 9; i++) F_out[(size_t)m * 9 + i] = 0.f;
         } else {
-            const int s = 0x7FFFFFFF - (int)(uint32_t)(best & 0xFFFFFFFFull);
-            inliers[m] = (int32_t)(best >> 32);
+            const int s = ransac_key_index(best);
+            inliers[m] = ransac_key_count(best);
             best_sample[m] = s;
             for (int i = 0; i < 9; i++) F_out[(size_t)m * 9 + i] = rec[((size_t)m * n_samples + s) * REC + i];
         }
@@ -219,6 +207,29 @@ __device__ float det3(const float (&A)[3][3])
 {
     return A[0][0] * (A[1][1] * A[2][2] - A[1][2] * A[2][1]) - A[0][1] * (A[1][0] * A[2][2] - A[1][2] * A[2][0]) +
            A[0][2] * (A[1][0] * A[2][1] - A[1][1] * A[2][0]);
+}
+
+// linear triangulation of one correspondence (normalised points n1, n2) under P1 = [I | 0], P2 = [R | t] (:143-173) -> X
+__device__ __forceinline__ void triangulate_pair(const PoseCand &pc, float n1x, float n1y, float n2x, float n2y, float &sx, float &sy,
+                                                 float &sz)
+{
+    float D[4][4];
+    D[0][0] = 1.f; D[0][1] = 0.f; D[0][2] = -n1x; D[0][3] = 0.f;                                   // P1.Row(0) - P1.Row(2) * n1x
+    D[1][0] = 0.f; D[1][1] = -1.f; D[1][2] = n1y; D[1][3] = 0.f;                                   // P1.Row(2) * n1y - P1.Row(1)
+    for (int j = 0; j < 3; j++) {
+        D[2][j] = pc.R[0][j] - pc.R[2][j] * n2x;
+        D[3][j] = pc.R[2][j] * n2y - pc.R[1][j];
+    }
+    D[2][3] = pc.t[0] - pc.t[2] * n2x;
+    D[3][3] = pc.t[2] * n2y - pc.t[1];
+    double G[4][4], X[4];
+    for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) {
+        double acc = 0;
+        for (int k = 0; k < 4; k++) acc += (double)D[k][i] * (double)D[k][j];
+        G[i][j] = acc;
+    }
+    smallest_eigvec<4>(G, X);                                                                   // V.Column(3) of the SVD (:170-171)
+    sx = (float)(X[0] / X[3]); sy = (float)(X[1] / X[3]); sz = (float)(X[2] / X[3]);            // :173
 }
 
 __global__ __launch_bounds__(256) void k_pose(const pgx_keypoint *__restrict__ kp, const pgx_pair *__restrict__ matches,
@@ -296,24 +307,8 @@ __global__ __launch_bounds__(256) void k_pose(const pgx_keypoint *__restrict__ k
         const float n2x = Ki[0][0] * x2 + Ki[0][2], n2y = Ki[1][1] * y2 + Ki[1][2];
         for (int c = 0; c < 4; c++) {
             const PoseCand &pc = cand[c];
-            float D[4][4];
-            // P1 = [I | 0], P2 = [R | t]
-            D[0][0] = 1.f; D[0][1] = 0.f; D[0][2] = -n1x; D[0][3] = 0.f;                                   // P1.Row(0) - P1.Row(2) * n1x
-            D[1][0] = 0.f; D[1][1] = -1.f; D[1][2] = n1y; D[1][3] = 0.f;                                   // P1.Row(2) * n1y - P1.Row(1)
-            for (int j = 0; j < 3; j++) {
-                D[2][j] = pc.R[0][j] - pc.R[2][j] * n2x;
-                D[3][j] = pc.R[2][j] * n2y - pc.R[1][j];
-            }
-            D[2][3] = pc.t[0] - pc.t[2] * n2x;
-            D[3][3] = pc.t[2] * n2y - pc.t[1];
-            double G[4][4], X[4];
-            for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) {
-                double acc = 0;
-                for (int k = 0; k < 4; k++) acc += (double)D[k][i] * (double)D[k][j];
-                G[i][j] = acc;
-            }
-            smallest_eigvec<4>(G, X);                                                                   // V.Column(3) of the SVD (:170-171)
-            const float sx = (float)(X[0] / X[3]), sy = (float)(X[1] / X[3]), sz = (float)(X[2] / X[3]); // :173
+            float sx, sy, sz;
+            triangulate_pair(pc, n1x, n1y, n2x, n2y, sx, sy, sz);
             const float pz = pc.R[2][0] * sx + pc.R[2][1] * sy + pc.R[2][2] * sz + pc.t[2];             // :174 (z of R * X + t)
             if (pz >= 0.f) atomicAdd(&cnt[c], 1);                                                        // :181-184
         }
@@ -337,23 +332,8 @@ __global__ __launch_bounds__(256) void k_pose(const pgx_keypoint *__restrict__ k
         const float x2 = (float)pv.kpb[pr.k2].x, y2 = (float)pv.kpb[pr.k2].y;
         const float n1x = Ki[0][0] * x1 + Ki[0][2], n1y = Ki[1][1] * y1 + Ki[1][2];
         const float n2x = Ki[0][0] * x2 + Ki[0][2], n2y = Ki[1][1] * y2 + Ki[1][2];
-        float D[4][4];
-        D[0][0] = 1.f; D[0][1] = 0.f; D[0][2] = -n1x; D[0][3] = 0.f;
-        D[1][0] = 0.f; D[1][1] = -1.f; D[1][2] = n1y; D[1][3] = 0.f;
-        for (int j = 0; j < 3; j++) {
-            D[2][j] = pc.R[0][j] - pc.R[2][j] * n2x;
-            D[3][j] = pc.R[2][j] * n2y - pc.R[1][j];
-        }
-        D[2][3] = pc.t[0] - pc.t[2] * n2x;
-        D[3][3] = pc.t[2] * n2y - pc.t[1];
-        double G[4][4], X[4];
-        for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) {
-            double acc = 0;
-            for (int k = 0; k < 4; k++) acc += (double)D[k][i] * (double)D[k][j];
-            G[i][j] = acc;
-        }
-        smallest_eigvec<4>(G, X);
-        const float sx = (float)(X[0] / X[3]), sy = (float)(X[1] / X[3]), sz = (float)(X[2] / X[3]);
+        float sx, sy, sz;
+        triangulate_pair(pc, n1x, n1y, n2x, n2y, sx, sy, sz);
         float *o = points + ((size_t)m * stride + e) * 3;
         o[0] = pc.R[0][0] * sx + pc.R[0][1] * sy + pc.R[0][2] * sz + pc.t[0];
         o[1] = pc.R[1][0] * sx + pc.R[1][1] * sy + pc.R[1][2] * sz + pc.t[1];

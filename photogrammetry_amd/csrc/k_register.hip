@@ -17,7 +17,7 @@
 //   k_reg_score    the hot path: one thread per hypothesis, a workgroup covers 256 hypotheses of one target and walks the
 //                  target's correspondences through LDS (every lane reads the same address: a broadcast).  The predicate
 //                  has no division and no square root; the counts are integers in registers; the workgroup's best key
-//                  (inliers, then the smallest h) goes to its own slot, no atomics
+//                  (pgx_ransac.h: inliers, then the smallest h) goes to its own slot, no atomics
 //   k_reg_pick     one workgroup per target: the winner (a max over the per-workgroup keys) and its hypothesis again (the
 //                  same device code as k_reg_hyp, so the same bits)
 //   k_reg_refine   one workgroup per target: Gauss-Newton on the winner's inliers (6x6 normal equations summed per lane,
@@ -286,21 +286,9 @@ __device__ void p3p(const double (&y)[3][3], const double (&X)[3][3], double (&R
 __device__ bool hypothesis(const RegArgs &a, int frame, int base, int n, double fx, double fy, int s, int rank, double (&Ro)[9],
                            double (&to)[3])
 {
-    uint64_t st = a.seed ^ ((uint64_t)(uint32_t)frame << 32) ^ (uint64_t)(uint32_t)s * 0xD1B54A32D192ED03ull;
+    uint64_t st = ransac_stream(a.seed, frame, s);
     int id[3];
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        while (true) {
-            const int c = (int)(splitmix64(st) % (uint64_t)n);
-            bool dup = false;
-#pragma unroll
-            for (int j = 0; j < k; j++) dup |= id[j] == c;
-            if (!dup) {
-                id[k] = c;
-                break;
-            }
-        }
-    }
+    ransac_draw(st, n, 3, id);
     double y[3][3], X[3][3];
 #pragma unroll
     for (int k = 0; k < 3; k++) {
@@ -588,20 +576,8 @@ __global__ __launch_bounds__(REG_NT) void k_reg_score(RegArgs a, int s0, int chu
         }
         __syncthreads();
     }
-    // key: (inliers + 1) << 32 | ~h for a hypothesis, 0 for none; the largest wins
-    unsigned long long key = valid ? ((unsigned long long)(cnt + 1) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)h) : 0ull;
-#pragma unroll
-    for (int mk = 1; mk < 64; mk <<= 1) {
-        const unsigned long long o = __shfl_xor(key, mk, 64);
-        key = o > key ? o : key;
-    }
-    if ((threadIdx.x & 63) == 0) s_key[threadIdx.x >> 6] = key;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long k = s_key[0];
-        for (int w = 1; w < REG_NT / 64; w++) k = s_key[w] > k ? s_key[w] : k;
-        a.best[(size_t)c * a.nblk + (4 * s0) / REG_NT + blockIdx.x] = k;
-    }
+    const unsigned long long key = ransac_block_max<REG_NT>(ransac_key(valid, cnt, h), s_key);
+    if (threadIdx.x == 0) a.best[(size_t)c * a.nblk + (4 * s0) / REG_NT + blockIdx.x] = key;
 }
 
 // cost of the pose over the inliers of (R0, t0): sum of squared pixel errors, division form
@@ -628,21 +604,8 @@ __global__ __launch_bounds__(REG_NT) void k_reg_pick(RegArgs a)
     __shared__ unsigned long long s_key[REG_NT / 64];
     const int c = blockIdx.x;
     if (c >= a.ctrl[1]) return;
-    unsigned long long key = 0;
-    for (int b = threadIdx.x; b < a.nblk; b += REG_NT) {
-        const unsigned long long k = a.best[(size_t)c * a.nblk + b];
-        key = k > key ? k : key;
-    }
-#pragma unroll
-    for (int mk = 1; mk < 64; mk <<= 1) {
-        const unsigned long long o = __shfl_xor(key, mk, 64);
-        key = o > key ? o : key;
-    }
-    if ((threadIdx.x & 63) == 0) s_key[threadIdx.x >> 6] = key;
-    __syncthreads();
+    const unsigned long long key = ransac_block_max<REG_NT>(ransac_row_max<REG_NT>(a.best, c, a.nblk, 0, a.nblk), s_key);
     if (threadIdx.x != 0) return;
-    key = s_key[0];
-    for (int w = 1; w < REG_NT / 64; w++) key = s_key[w] > key ? s_key[w] : key;
     const int f = a.tframe[c], n = a.nlist[c];
     double *out = a.win + (size_t)c * 16;
     int win = -1, flags = 0;
@@ -652,7 +615,7 @@ __global__ __launch_bounds__(REG_NT) void k_reg_pick(RegArgs a)
     } else if (key == 0ull) {
         flags = PGX_REG_NOSOLUTION;
     } else {
-        const int h = (int)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull));
+        const int h = ransac_key_index(key);
         if (hypothesis(a, f, a.coff[c], n, a.K[(size_t)f * 4], a.K[(size_t)f * 4 + 1], h >> 2, h & 3, R, t))
             win = h >> 2;
         else
@@ -867,10 +830,7 @@ __global__ __launch_bounds__(REG_NT) void k_reg_summary(RegArgs a)
 
 int reg_chunk(int n_frames, int n_samples)
 {
-    long long ch = REG_CHUNK_CELLS / (n_frames > 0 ? n_frames : 1);
-    ch = ch < 64 ? 64 : ch & ~63ll;   // a multiple of 64: a chunk is whole scoring workgroups
-    const long long all = ((long long)n_samples + 63) & ~63ll;
-    return (int)(ch < all ? ch : all);
+    return ransac_chunk(REG_CHUNK_CELLS, n_frames, 64, n_samples);   // 64 samples = 256 hypotheses: one scoring workgroup
 }
 
 // the workspace, described once: a's workspace pointers (none valid for ws = nullptr) and nblk; the bytes

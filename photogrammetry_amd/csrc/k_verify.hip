@@ -14,7 +14,7 @@
 //   k_ver_score    the hot path: one thread per hypothesis, a workgroup covers 256 hypotheses of one pair and walks the
 //                  pair's candidates through LDS (every lane reads the same address: a broadcast).  The predicate has no
 //                  division and no square root (18 multiplications, 15 additions); the counts are integers in registers; the
-//                  workgroup's best key (inliers, then the smallest s) and its number of valid samples go to its own slot,
+//                  workgroup's best key (pgx_ransac.h: inliers, then the smallest s) and its number of valid samples go to its own slot,
 //                  no atomics
 //   k_ver_pick     one workgroup per pair: the chunk's best key against the pair's running best (keys are distinct per
 //                  sample, so the order of the chunks does not matter); a better one brings its F along
@@ -203,22 +203,9 @@ __global__ __launch_bounds__(VER_SNT) void k_ver_samples(VerArgs a, int s0, int 
     bool ok = n >= 8;
     if (ok) {
         const int fa = a.pairlist[2 * m], fb = a.pairlist[2 * m + 1];
-        uint64_t st = a.seed ^ ((uint64_t)(uint32_t)fa << 32) ^ (uint64_t)(uint32_t)fb * 0x9E3779B97F4A7C15ull ^
-                      (uint64_t)(uint32_t)s * 0xD1B54A32D192ED03ull;
+        uint64_t st = ransac_stream(a.seed, fa, s) ^ (uint64_t)(uint32_t)fb * 0x9E3779B97F4A7C15ull;   // the pair is (fa, fb)
         int id[8];
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            while (true) {
-                const int c = (int)(splitmix64(st) % (uint64_t)n);
-                bool dup = false;
-#pragma unroll
-                for (int j = 0; j < k; j++) dup |= id[j] == c;
-                if (!dup) {
-                    id[k] = c;
-                    break;
-                }
-            }
-        }
+        ransac_draw(st, n, 8, id);
         double px[8], py[8], pu[8], pv[8];
         double cax = 0.0, cay = 0.0, cbx = 0.0, cby = 0.0;
 #pragma unroll
@@ -319,28 +306,12 @@ __global__ __launch_bounds__(VER_NT) void k_ver_score(VerArgs a, int s0, int chu
         __syncthreads();
     }
     if (live && a.sample_count) a.sample_count[(size_t)m * a.n_samples + s] = valid ? cnt : -1;
-    // key: (inliers + 1) << 32 | ~s for a valid sample, 0 for none; the largest wins
-    unsigned long long key = valid ? ((unsigned long long)(cnt + 1) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)s) : 0ull;
-#pragma unroll
-    for (int mk = 1; mk < 64; mk <<= 1) {
-        const unsigned long long o = __shfl_xor(key, mk, 64);
-        key = o > key ? o : key;
-    }
     const int nv = __popcll(__ballot(valid));
-    if ((threadIdx.x & 63) == 0) {
-        s_key[threadIdx.x >> 6] = key;
-        s_nv[threadIdx.x >> 6] = nv;
-    }
-    __syncthreads();
+    if ((threadIdx.x & 63) == 0) s_nv[threadIdx.x >> 6] = nv;
+    const unsigned long long key = ransac_block_max<VER_NT>(ransac_key(valid, cnt, s), s_key);   // its barrier covers s_nv
     if (threadIdx.x == 0) {
-        unsigned long long k = s_key[0];
-        int v = s_nv[0];
-        for (int w = 1; w < VER_NT / 64; w++) {
-            k = s_key[w] > k ? s_key[w] : k;
-            v += s_nv[w];
-        }
-        a.best[(size_t)m * a.nblk + gb] = k;
-        a.nvalid[(size_t)m * a.nblk + gb] = v;
+        a.best[(size_t)m * a.nblk + gb] = key;
+        a.nvalid[(size_t)m * a.nblk + gb] = (s_nv[0] + s_nv[1]) + (s_nv[2] + s_nv[3]);
     }
 }
 
@@ -355,16 +326,12 @@ __global__ __launch_bounds__(VER_NT) void k_ver_pick(VerArgs a, int s0, int chun
     b1 = b1 < a.nblk ? b1 : a.nblk;
     unsigned long long key = 0;
     int nv = 0;
-    for (int b = b0 + threadIdx.x; b < b1; b += VER_NT) {
+    for (int b = b0 + threadIdx.x; b < b1; b += VER_NT) {   // ransac_row_max written out: the valid counts ride along
         const unsigned long long k = a.best[(size_t)m * a.nblk + b];
         key = k > key ? k : key;
         nv += a.nvalid[(size_t)m * a.nblk + b];
     }
-#pragma unroll
-    for (int mk = 1; mk < 64; mk <<= 1) {
-        const unsigned long long o = __shfl_xor(key, mk, 64);
-        key = o > key ? o : key;
-    }
+    key = ransac_wave_max(key);
     nv = gsum_i<64>(nv);
     if ((threadIdx.x & 63) == 0) {
         s_key[threadIdx.x >> 6] = key;
@@ -372,27 +339,17 @@ __global__ __launch_bounds__(VER_NT) void k_ver_pick(VerArgs a, int s0, int chun
     }
     __syncthreads();
     if (threadIdx.x != 0) return;
-    for (int w = 1; w < VER_NT / 64; w++) {
+    for (int w = 1; w < VER_NT / 64; w++) {   // ransac_block_max written out, like the scan
         key = s_key[w] > key ? s_key[w] : key;
         nv += s_nv[w];
     }
     a.run_valid[m] += nv;
     if (key > a.run[m]) {
         a.run[m] = key;
-        const int s = (int)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull));
+        const int s = ransac_key_index(key);
         const double *hp = a.hyp + ((size_t)m * chunk + (s - s0)) * 9;
         for (int k = 0; k < 9; k++) a.win[(size_t)m * 9 + k] = hp[k];
     }
-}
-
-__device__ __forceinline__ int block_count(int c, int *sh)
-{
-    c = gsum_i<64>(c);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = c;
-    __syncthreads();
-    c = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-    __syncthreads();
-    return c;
 }
 
 __global__ __launch_bounds__(VER_NT) void k_ver_refit(VerArgs a)
@@ -414,8 +371,8 @@ __global__ __launch_bounds__(VER_NT) void k_ver_refit(VerArgs a)
     } else if (key == 0ull) {
         flags = PGX_VER_NOMODEL;
     } else {
-        win = (int)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull));
-        wcount = (int)(key >> 32) - 1;
+        win = ransac_key_index(key);
+        wcount = ransac_key_count(key);
     }
     // F through LDS: it then lives in vector registers
     if (threadIdx.x < 9) s_F[threadIdx.x] = a.win[(size_t)m * 9 + threadIdx.x];
@@ -493,7 +450,7 @@ __global__ __launch_bounds__(VER_NT) void k_ver_refit(VerArgs a)
             if (ok)
                 for (int j = threadIdx.x; j < n; j += VER_NT)
                     c += inlier(Fn, T, a.x[base + j], a.y[base + j], a.u[base + j], a.v[base + j]) ? 1 : 0;
-            c = block_count(c, s_cnt);
+            c = block_sum_i(c, s_cnt);
             if (!ok || c <= cur) break;
             cur = c;
             kept++;
@@ -584,10 +541,7 @@ __global__ __launch_bounds__(VER_NT) void k_ver_summary(const int32_t *stats, in
 // this one value (a shorter last chunk of pairs would otherwise get a longer chunk of samples than the workspace holds)
 int pgx_verify_chunk(int M, int n_samples)
 {
-    long long ch = VER_CHUNK_CELLS / (M > 0 ? M : 1);
-    ch = ch < VER_NT ? VER_NT : ch & ~(long long)(VER_NT - 1);   // a multiple of 256: a chunk is whole scoring workgroups
-    const long long all = ((long long)n_samples + VER_NT - 1) & ~(long long)(VER_NT - 1);
-    return (int)(ch < all ? ch : all);
+    return ransac_chunk(VER_CHUNK_CELLS, M, VER_NT, n_samples);   // 256 samples: one scoring workgroup
 }
 
 namespace {

@@ -1,9 +1,11 @@
 // pgx_trackgraph.h -- what every consumer of the track graph shares (k_triangulate.hip, k_bundle.hip, k_register.hip):
 // the read-only view of the graph and the keypoints, its validation and walking on the device, the lane-group and
-// workgroup reductions (k_verify.hip uses those too), and the workspace carver of the launchers.  Internal to libpgx.so; DESIGN.md section 14a.
+// workgroup reductions (k_verify.hip uses those too), and the workspace carver of the launchers.  It brings pgx_ransac.h along,
+// the sampler and the keys of the RANSAC stages among its consumers.  Internal to libpgx.so; DESIGN.md section 14a.
 #pragma once
 
 #include "pgx_internal.h"
+#include "pgx_ransac.h"
 
 #include <cmath>
 
@@ -141,6 +143,17 @@ template <int NV> __device__ __forceinline__ void block_sums(double (&v)[NV], do
     __syncthreads();
 }
 
+// block_sums' integer sibling: the sum of one count per thread over the workgroup of 256 threads, in every thread.  sh: 4 ints.
+__device__ __forceinline__ int block_sum_i(int c, int *sh)
+{
+    c = gsum_i<64>(c);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = c;
+    __syncthreads();
+    c = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+    __syncthreads();
+    return c;
+}
+
 // ---- cameras ----------------------------------------------------------------------------------------------------------
 
 // R' = Exp(omega) R (Rodrigues); R, Ro row-major 3x3
@@ -185,16 +198,6 @@ __device__ __forceinline__ void camera_matrix(const double *K, const double (&r)
         P[4 + j] = known ? K[1] * c1 + K[3] * c2 : NaN;
         P[8 + j] = known ? c2 : NaN;
     }
-}
-
-// ---- sampling ---------------------------------------------------------------------------------------------------------
-
-__device__ __forceinline__ uint64_t splitmix64(uint64_t &s)
-{
-    uint64_t z = (s += 0x9E3779B97F4A7C15ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
 }
 
 #endif // __HIPCC__

@@ -11,15 +11,10 @@ import numpy as np
 
 from oracle import pose_np
 from photogrammetry_amd import synth
+# stream_seed(seed, m, s): the seed under which slot 0 / sample 0 of a call runs the stream of sample s of image pair m
+from ransac_ref import M64 as MASK, STREAM_MUL, stream_seed
 
-MASK = (1 << 64) - 1
-STREAM_MUL = 0xD1B54A32D192ED03
 CH = 1024            # k_fund_score's LDS tile: list entries per chunk
-
-
-def stream_seed(seed, m, s):
-    """The seed under which slot 0 / sample 0 of a call runs the stream of sample s of image pair m under `seed`."""
-    return (seed ^ ((m & 0xFFFFFFFF) << 32) ^ (((s & 0xFFFFFFFF) * STREAM_MUL) & MASK)) & MASK
 
 
 def two_views(n_true, n_out, seed, dup=1, exact=True):

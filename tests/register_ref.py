@@ -7,29 +7,14 @@ import math
 
 import numpy as np
 
+from ransac_ref import M64, draw, splitmix64, stream_seed
+
 BADK, FEWPOINTS, NOSOLUTION, FEWINLIERS = 1, 2, 4, 8
-M64 = (1 << 64) - 1
-
-
-def splitmix64(state):
-    """-> (new state, output), as k_pose.hip"""
-    state = (state + 0x9E3779B97F4A7C15) & M64
-    z = state
-    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & M64
-    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & M64
-    return state, z ^ (z >> 31)
 
 
 def sample(seed, frame, s, n):
     """the three distinct positions of sample s of a frame with n correspondences"""
-    st = (seed ^ ((frame & 0xFFFFFFFF) << 32) ^ ((s & 0xFFFFFFFF) * 0xD1B54A32D192ED03)) & M64
-    ids = []
-    while len(ids) < 3:
-        st, z = splitmix64(st)
-        c = z % n
-        if c not in ids:
-            ids.append(c)
-    return ids
+    return draw(stream_seed(seed, frame, s), n, 3)
 
 
 def _det3c(a, b, c):

@@ -1,11 +1,11 @@
 """float64 restatement of two-view verification by epipolar RANSAC (include/pgx.h, "two-view geometric verification"): the
-yardstick of tests/test_gpu_verify.py.  Candidates, the sampler (register_ref.splitmix64), the normalised 8-point fit with
+yardstick of tests/test_gpu_verify.py.  Candidates, the sampler (ransac_ref), the normalised 8-point fit with
 rank 2 enforced (numpy's eigh in place of the kernel's Jacobi solver, the same sign rule), the inlier predicate in exactly
 the header's order of operations (numpy float64 reproduces the device's bits from the same F), winner, refit and outputs.
 tests/test_verify_ref.py ties this file to the truth."""
 import numpy as np
 
-from register_ref import M64, splitmix64
+from ransac_ref import M64, draw, splitmix64, stream_seed
 
 FEWMATCHES, NOMODEL, FEWINLIERS = 1, 2, 4
 DIST_NONE = 2**31 - 1
@@ -25,15 +25,7 @@ def candidates(kpa, kpb, ca, cb, ml, stride, max_dist):
 
 def sample(seed, a, b, s, n):
     """the 8 distinct positions of sample s of the pair in slots (a, b) with n candidates"""
-    st = (seed ^ ((a & 0xFFFFFFFF) << 32) ^ (((b & 0xFFFFFFFF) * 0x9E3779B97F4A7C15) & M64) ^
-          (((s & 0xFFFFFFFF) * 0xD1B54A32D192ED03) & M64)) & M64
-    ids = []
-    while len(ids) < 8:
-        st, z = splitmix64(st)
-        c = z % n
-        if c not in ids:
-            ids.append(c)
-    return ids
+    return draw(stream_seed(seed, a, s) ^ (((b & 0xFFFFFFFF) * 0x9E3779B97F4A7C15) & M64), n, 8)
 
 
 def _smallest(A, gaps=None):
