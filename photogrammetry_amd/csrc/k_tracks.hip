@@ -50,6 +50,7 @@ constexpr int TRK_UNION_GRID = 256;
 constexpr int TRKS_UNION_GRID = 256;
 static_assert(TRK_ECNT <= SCAN_NT, "k_trk_scan_sums adds the edge-counter slots up in one block scan");
 constexpr int FL_SLOTS = 512;        // LDS aggregation table of k_trk_flatten (>= 2 * TRK_NT)
+constexpr int TRK_INIT_GRID_MAX = 4096;   // workgroups of the grid-stride kernels over the nodes and the tables (trk_init_grid)
 
 struct TrkArgs {
     const pgx_pair *matches;   // [M][stride]
@@ -545,7 +546,7 @@ unsigned trk_init_grid(const TrkArgs &a)
 {
     const long long init_items = a.N > (long long)a.n_frames * a.T ? a.N : (long long)a.n_frames * a.T;
     long long gi = (init_items + TRK_NT - 1) / TRK_NT;
-    if (gi > 4096) gi = 4096;
+    if (gi > TRK_INIT_GRID_MAX) gi = TRK_INIT_GRID_MAX;
     if (gi < 1) gi = 1;
     return (unsigned)gi;
 }
