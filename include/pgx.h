@@ -736,6 +736,88 @@ int pgx_verify_pair(pgx_ctx *ctx, const pgx_keypoint *kp1, int n1, const pgx_key
                     int max_dist, int n_samples, double inlier_px, int min_inliers, int refit_iters, uint64_t seed, pgx_pair *out,
                     double *F, int32_t *stats, int32_t *inlier);
 
+/* ---- relative pose per image pair and the choice of the initial pair ------------------- */
+/* The start of a reconstruction: turns verification's F and the intrinsics into the first two cameras, so that the chain
+ * pgx_verify_pairs_dev -> pgx_tracks_dev -> this -> pgx_triangulate_tracks_dev -> pgx_bundle_adjust_dev ->
+ * pgx_register_frames_dev runs on one stream with no host round trip.  No RANSAC of its own (verification ran one) and no
+ * refinement (bundle adjustment with one fixed frame does that).  Not in the C# reference.
+ * Inputs: d_kp [F][stride], d_matches [M][stride] (meant: verification's d_out), d_counts [F], d_pairlist [M][2] (slots), M,
+ * F, stride, d_frame_ids [F] or NULL, n_frames and max_dist as for pgx_tracks_dev; (a, b) = d_pairlist[m];
+ *   d_F [M][9]          float64, verification's d_F: h_a^T F h_b = 0
+ *   d_K [n_frames][4]   fx, fy, cx, cy by frame NUMBER, as pgx_bundle_adjust_dev takes it
+ *   min_angle_deg in [0, 90), min_front_frac in (0, 1], min_points >= 1.
+ * Values.  Every value is a double, every operation one IEEE double operation in the order written, nothing is contracted
+ * into a fused multiply-add; dot products are summed as ((.0 + .1) + .2).
+ * Per pair m:
+ *   1 flags   (PGX_INIT_*, bits; 0 = eligible)
+ *             SKIPPED     a slot outside [0, F), a == b, or a slot whose frame number is -1 (or otherwise outside
+ *                         [0, n_frames)); no other flag is set with it and nothing else of the pair is read
+ *             BADINPUT    an entry of F, K_a or K_b is not finite, or some fx or fy is 0; no other flag is set with it
+ *             DEGENERATE  step 4 failed; no other flag is set with it
+ *             FEWFRONT, FEWPOINTS  step 6; both can be set on one pair
+ *   2 candidates  exactly pgx_verify_pairs_dev's: entry e < clamp(counts[a], 0, stride) with 0 <= k1 < counts[a], 0 <= k2 <
+ *             counts[b] (both clamped to [0, stride]), dist <= max_dist and dist != PGX_DIST_NONE, in list order; there are n.
+ *             With (x, y) = kp_a[k1], (u, v) = kp_b[k2] the unnormalised bearings are g_a = ((x - cx_a) fy_a, (y - cy_a) fx_a,
+ *             fx_a fy_a) with s_a = fx_a fy_a, and g_b, s_b alike: no division.
+ *   3 E = K_a^T F K_b: the rows of A = K_a^T F are fx_a F[0], fy_a F[1], (cx_a F[0] + cy_a F[1]) + F[2]; the columns of E are
+ *             A[:,0] fx_b, A[:,1] fy_b, (A[:,0] cx_b + A[:,1] cy_b) + A[:,2].  G = E^T, so that g_b^T G g_a = 0 and G is
+ *             proportional to [t]x R for x_b = R x_a + t.  Gh = G / sqrt(the sum of its squares, row-major from 0).
+ *   4 decomposition  B = Gh^T Gh (B[i][j] = the dot product of columns i and j); its eigenpairs by cyclic Jacobi
+ *             (pgx_verify_pairs_dev's solver, N = 3), ordered by eigenvalue descending, ties to the lower column;
+ *             sigma_i = sqrt(max(lambda_i, 0)).  DEGENERATE if an entry of Gh, an eigenvalue or an entry of a candidate is not
+ *             finite, or sigma_2 <= 1e-6 sigma_1.  u1 = (Gh v1) / sigma_1; w = Gh v2, u2 = (w - (u1 . w) u1) / its norm;
+ *             v3 = v1 x v2, u3 = u1 x u2.  R1[i][j] = (u2[i] v1[j] - u1[i] v2[j]) + u3[i] v3[j] (= U W V^T, W = [[0, -1, 0],
+ *             [1, 0, 0], [0, 0, 1]]), R2[i][j] = (u1[i] v2[j] - u2[i] v1[j]) + u3[i] v3[j] (= U W^T V^T), t = u3, |t| = 1.
+ *             Candidates c = 0..3 = (R1, t), (R1, -t), (R2, t), (R2, -t).
+ *   5 score of a candidate (R, t) on one match, with no division and no square root:
+ *             p = R g_a;  a11 = p . p;  c = p . g_b;  a12 = -c;  a22 = g_b . g_b;  r1 = -(p . t);  r2 = g_b . t
+ *             det = a11 a22 - a12 a12;  na = r1 a22 - a12 r2;  nb = a11 r2 - a12 r1
+ *             front  iff det > 0 and na s_a > 0 and nb s_b > 0 (both depths positive)
+ *             wide   iff front and ((c s_a) s_b <= 0 or c c <= cos2 (a11 a22)): the angle between the two rays is at least
+ *                    min_angle_deg; cos2 = the square of the host C library's cos(min_angle_deg * (M_PI / 180)).
+ *             The ray angle does not depend on t: a pair related by a pure rotation has no wide point, whatever its t.
+ *   6 winner  the candidate with the most front points, ties to the smallest c.  FEWFRONT if (double)front <
+ *             min_front_frac * (double)n; FEWPOINTS if the winner's wide count < min_points.  Only integers are summed: the
+ *             grid and the order of the sums do not matter.
+ * Choice.  Among the pairs with flags 0 the largest wide count; ties to the smaller frame number of a, then of b, then the
+ * smaller m (integer keys; with distinct pairs the choice does not depend on the order of the pair list).  Call it m*, its
+ * frames a*, b*.
+ * Outputs, per pair:
+ *   d_Rt_pair [M][12]      the winner, R row-major then t; NaN for SKIPPED, BADINPUT and DEGENERATE
+ *   d_pair_stats [M][8]    int32: n, front[0..3], the winner's wide count, the winner c or -1, the flags.  n is counted for
+ *                          every pair but a SKIPPED one; the other counts are 0 without a winner
+ *   d_sigma [M] or NULL    sigma_2 / sigma_1; NaN when it was not computed (SKIPPED, BADINPUT, a non-finite Gh or eigenvalue)
+ *   d_cand_Rt [M][4][12] or NULL  the four candidates; NaN where d_Rt_pair is
+ * per frame number, ready for the next calls (NaN and 0 throughout when no pair is eligible, which is no error):
+ *   d_Rt_out, d_P_out [n_frames][12]  frame a* = [I | 0], frame b* = [R | t] of m*, every other frame NaN; P = K [R | t] with
+ *                          the rows (fx r0 + cx r2, fy r1 + cy r2, r2), as pgx_bundle_adjust_dev writes them
+ *   d_fixed_out [n_frames]     int32: 1 for a*, else 0
+ *   d_register_out [n_frames]  int32: 1 for every frame that some slot names other than a* and b*, else 0
+ *   d_report [8] int32: pairs, pairs with flags 0, SKIPPED or BADINPUT, DEGENERATE, FEWFRONT, FEWPOINTS, m* or -1, the wide
+ *                          count of m* (0 without one)
+ * Returned at once (PGX_E_BADARG): min_angle_deg outside [0, 90), min_front_frac outside (0, 1], either NaN, min_points < 1,
+ * M < 0, stride outside [1, 2^20], F or n_frames not positive, no d_frame_ids and n_frames != F, n_frames * stride > 2^30, a
+ * null required pointer.
+ * Results depend on the inputs only: the same bits from run to run, for any order of the pair list (the choice then names the
+ * same pair), any slot layout of the same frames, any n_frames that holds them, and from the host form below.  The workspace
+ * is 304 bytes per pair, so pgx_set_match_chunk plays no part.  Asynchronous on the context's stream, no host sync. */
+#define PGX_INIT_SKIPPED    1
+#define PGX_INIT_BADINPUT   2
+#define PGX_INIT_DEGENERATE 4
+#define PGX_INIT_FEWFRONT   8
+#define PGX_INIT_FEWPOINTS  16
+int pgx_init_pair_dev(pgx_ctx *ctx, const pgx_keypoint *d_kp, const pgx_pair *d_matches, const int32_t *d_counts,
+                      const int32_t *d_pairlist, int M, int F, int stride, const int32_t *d_frame_ids, int n_frames, int max_dist,
+                      const double *d_F, const double *d_K, double min_angle_deg, double min_front_frac, int min_points,
+                      double *d_Rt_pair, int32_t *d_pair_stats, double *d_sigma, double *d_cand_Rt, double *d_Rt_out,
+                      double *d_P_out, int32_t *d_fixed_out, int32_t *d_register_out, int32_t *d_report);
+/* Host form: one pair on host arrays, the same kernels with frame a in slot 1 and frame b in slot 2, like pgx_verify_pair (so
+ * the bits are those of the device form).  matches holds n1 entries; F [9]; K_a, K_b [4]; Rt [12], stats [8], sigma [1],
+ * cand_Rt [48] or NULL.  n1 or n2 < 0 or above 2^20: PGX_E_BADARG.  Returns when the outputs are in the caller's buffers. */
+int pgx_relative_pose(pgx_ctx *ctx, const pgx_keypoint *kp1, int n1, const pgx_keypoint *kp2, int n2, const pgx_pair *matches,
+                      int max_dist, const double *F, const double *K_a, const double *K_b, double min_angle_deg,
+                      double min_front_frac, int min_points, double *Rt, int32_t *stats, double *sigma, double *cand_Rt);
+
 /* ---- measurement hooks (bench.py) ---------------------------------------------------- */
 /* When on, the named hot kernels are bracketed by HIP events on the launch stream. */
 int pgx_profile_enable(pgx_ctx *ctx, int on);

@@ -25,6 +25,7 @@ internal static unsafe class PgxNative
     public const int TriFewViews = 1, TriDegenerate = 2, TriBehind = 4, TriParallax = 8, TriReproj = 16;   // PGX_TRI_* (0 = valid)
     public const int RegBadK = 1, RegFewPoints = 2, RegNoSolution = 4, RegFewInliers = 8;   // PGX_REG_* (0 = registered)
     public const int VerFewMatches = 1, VerNoModel = 2, VerFewInliers = 4;                 // PGX_VER_* (0 = accepted)
+    public const int InitSkipped = 1, InitBadInput = 2, InitDegenerate = 4, InitFewFront = 8, InitFewPoints = 16;   // PGX_INIT_* (0 = eligible)
 
     // Exports of include/pgx.h that this binding deliberately leaves out (tests/test_csharp_binding.py holds the list to the
     // header): the caller's-HIP-stream hook and the measurement hooks (a managed host owns no hipStream_t and reads no HIP event
@@ -184,6 +185,22 @@ internal static unsafe class PgxNative
                                                               PgxPair* matches, int maxDist, int nSamples, double inlierPx,
                                                               int minInliers, int refitIters, ulong seed, PgxPair* output, double* f,
                                                               int* stats, int* inlier);
+
+    // the start of a reconstruction, between pgx_tracks_dev and the first pgx_triangulate_tracks_dev: per image pair the
+    // relative pose from verification's dF [m][9] and dK [nFrames][4] (dRtPair [m][12], dPairStats [m][8], dSigma [m] or null,
+    // dCandRt [m][4][12] or null), and for the chosen pair dRtOut, dPOut [nFrames][12], dFixedOut and dRegisterOut [nFrames]
+    // as the next stages take them, dReport [8]; the host form runs one pair (f [9], kA and kB [4], rt [12], stats [8],
+    // sigma [1], candRt [48] or null)
+    [DllImport(Lib)] public static extern int pgx_init_pair_dev(IntPtr ctx, void* dKp, void* dMatches, void* dCounts, void* dPairlist,
+                                                                int m, int f, int stride, void* dFrameIds, int nFrames, int maxDist,
+                                                                void* dF, void* dK, double minAngleDeg, double minFrontFrac,
+                                                                int minPoints, void* dRtPair, void* dPairStats, void* dSigma,
+                                                                void* dCandRt, void* dRtOut, void* dPOut, void* dFixedOut,
+                                                                void* dRegisterOut, void* dReport);
+    [DllImport(Lib)] public static extern int pgx_relative_pose(IntPtr ctx, PgxKeypoint* kp1, int n1, PgxKeypoint* kp2, int n2,
+                                                                PgxPair* matches, int maxDist, double* f, double* kA, double* kB,
+                                                                double minAngleDeg, double minFrontFrac, int minPoints, double* rt,
+                                                                int* stats, double* sigma, double* candRt);
 
     /// <summary>Maps a status code back to the exception type the managed implementation throws.</summary>
     public static void Check(IntPtr ctx, int rc)

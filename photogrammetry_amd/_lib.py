@@ -91,6 +91,8 @@ SIGNATURES = {
     "pgx_register_frames": (I, [P, P, P, I, P, P, P, P, P, I, P, P, I, D, I, I, U64, P, P, P, P, P, P]),
     "pgx_verify_pairs_dev": (I, [P, P, P, P, P, I, I, I, I, D, I, I, U64, P, P, P, P, P, P, P, P]),
     "pgx_verify_pair": (I, [P, P, I, P, I, P, I, I, D, I, I, U64, P, P, P, P]),
+    "pgx_init_pair_dev": (I, [P, P, P, P, P, I, I, I, P, I, I, P, P, D, D, I, P, P, P, P, P, P, P, P, P]),
+    "pgx_relative_pose": (I, [P, P, I, P, I, P, I, P, P, P, D, D, I, P, P, P, P]),
     "pgx_profile_enable": (I, [P, I]),
     "pgx_profile_filter": (I, [P, S]),
     "pgx_profile_get": (I, [P, S, P, P]),

@@ -573,6 +573,43 @@ class Engine:
             int(n_samples), inlier_px, int(min_inliers), int(refit_iters), seed, _ptr(out), _ptr(F), _ptr(stats), _ptr(inl)))
         return dict(out=out[:n1], F=F, stats=stats, inlier=inl[:n1])
 
+    # -- relative pose per image pair and the choice of the initial pair (pgx_init_pair_dev, pgx_relative_pose) ------
+    def init_pair_dev(self, d_kp, d_matches, d_counts, d_pairlist, M, F, stride, n_frames, max_dist, d_F, d_K, d_Rt_pair,
+                      d_pair_stats, d_Rt_out, d_P_out, d_fixed_out, d_register_out, d_report, min_angle_deg=2.0,
+                      min_front_frac=0.7, min_points=30, d_sigma=None, d_cand_Rt=None, d_frame_ids=None):
+        """The first two cameras of a reconstruction from verification's F and the intrinsics, where they sit in HBM (pgx.h:
+        relative pose per image pair).  d_matches [M][stride] PAIR_DTYPE (verify_pairs_dev's d_out), d_F [M][9] and d_K
+        [n_frames][4] float64; d_Rt_pair [M][12] float64, d_pair_stats [M][8] int32, d_sigma [M] float64 or None, d_cand_Rt
+        [M][4][12] float64 or None; d_Rt_out / d_P_out [n_frames][12] float64 and d_fixed_out / d_register_out [n_frames]
+        int32, as triangulate_tracks_dev, bundle_adjust_dev and register_frames_dev take them; d_report [8] int32.  No sync."""
+        self._chk(self._L.pgx_init_pair_dev(
+            self._h, _dptr(d_kp), _dptr(d_matches), _dptr(d_counts), _dptr(d_pairlist), int(M), int(F), int(stride),
+            _dptr(d_frame_ids), int(n_frames), int(max_dist), _dptr(d_F), _dptr(d_K), min_angle_deg, min_front_frac,
+            int(min_points), _dptr(d_Rt_pair), _dptr(d_pair_stats), _dptr(d_sigma), _dptr(d_cand_Rt), _dptr(d_Rt_out),
+            _dptr(d_P_out), _dptr(d_fixed_out), _dptr(d_register_out), _dptr(d_report)))
+
+    def relative_pose(self, kp1, kp2, matches, max_dist, F, K_a, K_b, min_angle_deg=2.0, min_front_frac=0.7, min_points=30,
+                      candidates=True):
+        """The host form (pgx_relative_pose): one pair, frame a in slot 1 and frame b in slot 2.  kp1, kp2: KEYPOINT_DTYPE
+        arrays; matches: PAIR_DTYPE array (or int32 [n1][3]) of len(kp1) entries; F [9] with h_a^T F h_b = 0; K_a, K_b
+        (fx, fy, cx, cy).  -> dict(Rt [12], stats [8], sigma, cand_Rt [4][12] or None)"""
+        k1 = np.ascontiguousarray(kp1, dtype=KEYPOINT_DTYPE)
+        k2 = np.ascontiguousarray(kp2, dtype=KEYPOINT_DTYPE)
+        n1, n2 = len(k1), len(k2)
+        ml = np.ascontiguousarray(matches)
+        ml = ml if ml.dtype == PAIR_DTYPE else np.ascontiguousarray(ml, dtype=np.int32).reshape(-1, 3).view(PAIR_DTYPE).reshape(-1)
+        if len(ml) != n1:
+            raise ValueError("the match list must hold one entry per keypoint of the first frame")
+        Fm = np.ascontiguousarray(F, dtype=np.float64).reshape(9)
+        Ka, Kb = np.ascontiguousarray(K_a, dtype=np.float64).reshape(4), np.ascontiguousarray(K_b, dtype=np.float64).reshape(4)
+        Rt, stats, sigma = np.zeros(12), np.zeros(8, dtype=np.int32), np.zeros(1)
+        cand = np.zeros((4, 12)) if candidates else None
+        self._chk(self._L.pgx_relative_pose(
+            self._h, _ptr(k1) if n1 else None, n1, _ptr(k2) if n2 else None, n2, _ptr(ml) if n1 else None, int(max_dist),
+            _ptr(Fm), _ptr(Ka), _ptr(Kb), min_angle_deg, min_front_frac, int(min_points), _ptr(Rt), _ptr(stats), _ptr(sigma),
+            _ptr(cand) if candidates else None))
+        return dict(Rt=Rt, stats=stats, sigma=float(sigma[0]), cand_Rt=cand)
+
     # -- multi-GPU: the context's own RCCL communicator (pgx_comm_*) ------------------------------
     def comm_init(self, rank, world, unique_id):
         """Collective: every rank calls this with the 128 bytes rank 0 got from comm_unique_id()."""

@@ -447,7 +447,7 @@ void pgx_ctx_destroy(pgx_ctx *c)
     for (hipEvent_t ev : c->ev_pool) (void)hipEventDestroy(ev);
     DevBuf *bufs[] = {&c->d_pairs, &c->d_plan, &c->d_steer_pairs, &c->d_steer_plans, &c->d_steer_dirs, &c->d_map, &c->ws_gray, &c->ws_seg, &c->ws_segoff, &c->ws_nraw, &c->ws_rawxy,
                       &c->ws_rawscore, &c->ws_nms, &c->ws_order, &c->ws_nkept, &c->st_a, &c->st_b, &c->st_c,
-                      &c->st_d, &c->st_e, &c->st_f, &c->ws_pose, &c->ws_tracks, &c->ws_tracks_split, &c->ws_agree, &c->ws_matchn[0], &c->ws_matchn[1], &c->ws_matchn[2], &c->ws_knn, &c->ws_guided, &c->ws_tri, &c->ws_ba, &c->ws_reg, &c->ws_ver,
+                      &c->st_d, &c->st_e, &c->st_f, &c->ws_pose, &c->ws_tracks, &c->ws_tracks_split, &c->ws_agree, &c->ws_matchn[0], &c->ws_matchn[1], &c->ws_matchn[2], &c->ws_knn, &c->ws_guided, &c->ws_tri, &c->ws_ba, &c->ws_reg, &c->ws_ver, &c->ws_init,
                       &c->ws_pyr_a, &c->ws_pyr_b, &c->ws_pyr_kp, &c->ws_pyr_desc, &c->ws_pyr_bins, &c->ws_pyr_cnt};
     for (DevBuf *b : bufs) b->release();
     c->pin_in.release();
@@ -1731,6 +1731,106 @@ int pgx_verify_pair(pgx_ctx *c, const pgx_keypoint *kp1, int n1, const pgx_keypo
     if (inlier && n1 > 0) HIPCHK(c, hipMemcpyAsync(inlier, dout + o_in, (size_t)n1 * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(F, dout + o_F, 72, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(stats, dout + o_st, 32, hipMemcpyDeviceToHost, c->stream));
+    return sync_status(c);
+}
+
+// ---- relative pose per image pair and the choice of the initial pair ------------------------------------------------
+
+namespace {
+// cos^2 of the angle gate through *cos2
+int init_args(pgx_ctx *c, int M, int stride, double min_angle_deg, double min_front_frac, int min_points, double *cos2)
+{
+    if (M < 0) return fail(c, PGX_E_BADARG, "M = %d, must be >= 0", M);
+    if (stride < 1 || stride > (1 << PGX_IDX_BITS)) return fail(c, PGX_E_BADARG, "stride must be in [1, 2^20]");
+    if (!(min_angle_deg >= 0.0 && min_angle_deg < 90.0)) return fail(c, PGX_E_BADARG, "min_angle_deg must be in [0, 90) (and not NaN)");
+    if (!(min_front_frac > 0.0 && min_front_frac <= 1.0)) return fail(c, PGX_E_BADARG, "min_front_frac must be in (0, 1] (and not NaN)");
+    if (min_points < 1) return fail(c, PGX_E_BADARG, "min_points = %d, must be >= 1", min_points);
+    const double cs = std::cos(min_angle_deg * (M_PI / 180));
+    *cos2 = cs * cs;
+    return PGX_OK;
+}
+} // namespace
+
+int pgx_init_pair_dev(pgx_ctx *c, const pgx_keypoint *d_kp, const pgx_pair *d_matches, const int32_t *d_counts,
+                      const int32_t *d_pairlist, int M, int F, int stride, const int32_t *d_frame_ids, int n_frames, int max_dist,
+                      const double *d_F, const double *d_K, double min_angle_deg, double min_front_frac, int min_points,
+                      double *d_Rt_pair, int32_t *d_pair_stats, double *d_sigma, double *d_cand_Rt, double *d_Rt_out, double *d_P_out,
+                      int32_t *d_fixed_out, int32_t *d_register_out, int32_t *d_report)
+{
+    if (!c || !d_kp || !d_matches || !d_counts || !d_pairlist || !d_F || !d_K || !d_Rt_pair || !d_pair_stats || !d_Rt_out || !d_P_out ||
+        !d_fixed_out || !d_register_out || !d_report)
+        return c ? fail(c, PGX_E_BADARG, "null pointer") : PGX_E_BADARG;
+    Lock l(c);
+    double cos2 = 0.0;
+    int rc = init_args(c, M, stride, min_angle_deg, min_front_frac, min_points, &cos2);
+    if (rc == PGX_OK) rc = geom_dev_args(c, F, stride, n_frames, d_frame_ids, 0);
+    if (rc != PGX_OK) return rc;
+    HIPCHK(c, c->ws_init.ensure(pgx_init_pair_ws_bytes(M)));
+    {
+        ProfScope ps(c, "init_pair");
+        pgx_launch_init_pair(c->stream, d_kp, d_matches, d_counts, d_pairlist, M, F, stride, d_frame_ids, n_frames, max_dist, d_F, d_K,
+                             cos2, min_front_frac, min_points, d_Rt_pair, d_pair_stats, d_sigma, d_cand_Rt, d_Rt_out, d_P_out,
+                             d_fixed_out, d_register_out, d_report, c->ws_init.p);
+    }
+    HIPCHK(c, hipGetLastError());
+    return PGX_OK;
+}
+
+int pgx_relative_pose(pgx_ctx *c, const pgx_keypoint *kp1, int n1, const pgx_keypoint *kp2, int n2, const pgx_pair *matches, int max_dist,
+                      const double *F, const double *K_a, const double *K_b, double min_angle_deg, double min_front_frac,
+                      int min_points, double *Rt, int32_t *stats, double *sigma, double *cand_Rt)
+{
+    if (!c || !F || !K_a || !K_b || !Rt || !stats || !sigma || n1 < 0 || n2 < 0 || n1 > (1 << PGX_IDX_BITS) ||
+        n2 > (1 << PGX_IDX_BITS) || (n1 > 0 && (!kp1 || !matches)) || (n2 > 0 && !kp2))
+        return c ? fail(c, PGX_E_BADARG, "null pointer or bad size") : PGX_E_BADARG;
+    Lock l(c);
+    const int S = n1 > n2 ? n1 : (n2 > 0 ? n2 : 1);
+    double cos2 = 0.0;
+    const int rc = init_args(c, 1, S, min_angle_deg, min_front_frac, min_points, &cos2);
+    if (rc != PGX_OK) return rc;
+    // inputs in st_a: keypoints [3][S] (slot 0 unused), the list [S], F [9], K [3][4] (row 0 unused), counts [3] and the pair
+    // (1, 2); outputs in st_b
+    WsCarver in(nullptr), ot(nullptr);
+    const size_t i_kp = in.put((size_t)3 * S * sizeof(pgx_keypoint)), i_ml = in.put((size_t)S * sizeof(pgx_pair)), i_F = in.put(72),
+                 i_K = in.put(96), i_meta = in.put(64);
+    const size_t o_Rt = ot.put(96), o_st = ot.put(32), o_sg = ot.put(8), o_cand = ot.put(384), o_fr = ot.put(2 * 3 * 96),
+                 o_fi = ot.put(2 * 3 * 4 + 64), o_rep = ot.put(32);
+    HIPCHK(c, c->st_a.ensure(in.total()));
+    HIPCHK(c, c->st_b.ensure(ot.total()));
+    HIPCHK(c, c->ws_init.ensure(pgx_init_pair_ws_bytes(1)));
+    char *di = c->st_a.as<char>(), *dout = c->st_b.as<char>();
+    const int32_t meta[5] = {0, n1, n2, 1, 2};
+    HIPCHK(c, hipMemsetAsync(di, 0, in.total(), c->stream));
+    if (n1 > 0) {
+        HIPCHK(c, hipMemcpyAsync(di + i_kp + (size_t)S * sizeof(pgx_keypoint), kp1, (size_t)n1 * sizeof(pgx_keypoint), hipMemcpyHostToDevice,
+                                 c->stream));
+        HIPCHK(c, hipMemcpyAsync(di + i_ml, matches, (size_t)n1 * sizeof(pgx_pair), hipMemcpyHostToDevice, c->stream));
+    }
+    if (n2 > 0)
+        HIPCHK(c, hipMemcpyAsync(di + i_kp + (size_t)2 * S * sizeof(pgx_keypoint), kp2, (size_t)n2 * sizeof(pgx_keypoint), hipMemcpyHostToDevice,
+                                 c->stream));
+    HIPCHK(c, hipMemcpyAsync(di + i_F, F, 72, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(di + i_K + 32, K_a, 32, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(di + i_K + 64, K_b, 32, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(di + i_meta, meta, sizeof meta, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));   // meta is on this call's stack
+    const int32_t *d_meta = reinterpret_cast<const int32_t *>(di + i_meta);
+    {
+        ProfScope ps(c, "init_pair");
+        pgx_launch_init_pair(c->stream, reinterpret_cast<const pgx_keypoint *>(di + i_kp), reinterpret_cast<const pgx_pair *>(di + i_ml),
+                             d_meta, d_meta + 3, 1, 3, S, nullptr, 3, max_dist, reinterpret_cast<const double *>(di + i_F),
+                             reinterpret_cast<const double *>(di + i_K), cos2, min_front_frac, min_points,
+                             reinterpret_cast<double *>(dout + o_Rt), reinterpret_cast<int32_t *>(dout + o_st),
+                             reinterpret_cast<double *>(dout + o_sg), cand_Rt ? reinterpret_cast<double *>(dout + o_cand) : nullptr,
+                             reinterpret_cast<double *>(dout + o_fr), reinterpret_cast<double *>(dout + o_fr + 3 * 96),
+                             reinterpret_cast<int32_t *>(dout + o_fi), reinterpret_cast<int32_t *>(dout + o_fi + 32),
+                             reinterpret_cast<int32_t *>(dout + o_rep), c->ws_init.p);
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(Rt, dout + o_Rt, 96, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(stats, dout + o_st, 32, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(sigma, dout + o_sg, 8, hipMemcpyDeviceToHost, c->stream));
+    if (cand_Rt) HIPCHK(c, hipMemcpyAsync(cand_Rt, dout + o_cand, 384, hipMemcpyDeviceToHost, c->stream));
     return sync_status(c);
 }
 

@@ -147,6 +147,7 @@ struct pgx_ctx {
     DevBuf ws_ba;     // pgx_bundle_adjust*: control block, cameras, reduced system, per-track and per-node state
     DevBuf ws_reg;    // pgx_register_frames*: target tables, correspondence lists, hypotheses of one chunk, scoring keys
     DevBuf ws_ver;    // pgx_verify_pair*: candidate lists of a chunk of image pairs, hypotheses of one chunk of samples, keys
+    DevBuf ws_init;   // pgx_init_pair_dev, pgx_relative_pose: per image pair the two rotations, t, the intrinsics and the counters
     hipStream_t mstream[3] = {nullptr, nullptr, nullptr}; // [0] wide rounds, [1] residual distance rows, [2] per-pair finish
     hipEvent_t ev_in = nullptr, ev_wide[3] = {nullptr, nullptr, nullptr}, ev_rows[3] = {nullptr, nullptr, nullptr},
                ev_fin[3] = {nullptr, nullptr, nullptr}, ev_join[3] = {nullptr, nullptr, nullptr};
@@ -407,3 +408,12 @@ void pgx_launch_verify(hipStream_t s, const pgx_keypoint *d_kp, const pgx_pair *
                        int32_t *d_inlier, double *d_sample_F, int32_t *d_sample_count, int chunk, void *ws);
 // d_report from the d_stats rows of all M pairs of a call
 void pgx_launch_verify_summary(hipStream_t s, const int32_t *d_stats, int M, int32_t *d_report);
+
+// k_initpair.hip (relative pose per image pair and the choice of the initial pair; pgx_init_pair_dev semantics, include/pgx.h)
+size_t pgx_init_pair_ws_bytes(int M);
+// all M pairs of a call; cos2 = the square of the cosine of min_angle_deg; d_sigma and d_cand_Rt may be null
+void pgx_launch_init_pair(hipStream_t s, const pgx_keypoint *d_kp, const pgx_pair *d_matches, const int32_t *d_counts,
+                          const int32_t *d_pairlist, int M, int F, int stride, const int32_t *d_frame_ids, int n_frames, int max_dist,
+                          const double *d_F, const double *d_K, double cos2, double min_front_frac, int min_points, double *d_Rt_pair,
+                          int32_t *d_pair_stats, double *d_sigma, double *d_cand_Rt, double *d_Rt_out, double *d_P_out,
+                          int32_t *d_fixed_out, int32_t *d_register_out, int32_t *d_report, void *ws);
