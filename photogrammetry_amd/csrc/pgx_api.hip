@@ -1328,7 +1328,7 @@ int pgx_tracks_split_dev(pgx_ctx *c, const pgx_pair *d_matches, const int32_t *d
 namespace {
 // the host forms' checks of counts, offsets and nodes (the device then sees no out-of-range node); stride = max(counts, 1)
 int check_host_tracks(pgx_ctx *c, const pgx_keypoint *kps, const int32_t *counts, int n_frames, const int32_t *track_offsets,
-                      const int32_t *nodes, int n_tracks, int *stride_out, long long *n_nodes_out)
+                      const int32_t *nodes, int n_tracks, HostTracks *out)
 {
     long long n_kp = 0;
     int stride = 1;
@@ -1349,55 +1349,47 @@ int check_host_tracks(pgx_ctx *c, const pgx_keypoint *kps, const int32_t *counts
         if (f < 0 || f >= n_frames || k < 0 || k >= counts[f])
             return fail(c, PGX_E_BADARG, "node %lld = (%d, %d) is outside [0, n_frames) x [0, counts[frame])", o, f, k);
     }
-    *stride_out = stride;
-    *n_nodes_out = n_nodes;
+    *out = {kps, counts, track_offsets, nodes, n_frames, n_tracks, stride, n_nodes};
     return PGX_OK;
 }
 
-// One pinned upload of a host form into st_a, in 256-byte-aligned sections: keypoints [n_frames][stride], the stage's
-// per-frame arrays (frame_src, frame_bytes per frame; nullptr ends the list), offsets, nodes, with per_track the points
-// and flags of the tracks, and the track summary's {n_tracks, n_nodes}.  The section offsets come back in `at`.
-struct HostUpload {
-    size_t frame[3], off, nodes, xyz, flags, ts;
-};
-int stage_host_tracks(pgx_ctx *c, const pgx_keypoint *kps, const int32_t *counts, int n_frames, int stride,
-                      const void *const (&frame_src)[3], const size_t (&frame_bytes)[3], const int32_t *track_offsets,
-                      const int32_t *nodes, int n_tracks, long long n_nodes, bool per_track, const double *xyz,
-                      const int32_t *track_flags, HostUpload &at)
+// A host form's images (pgx_hoststage.h) onto the device: the inputs packed in pin_in and uploaded to st_a in one copy,
+// the outputs in st_b
+int stage_images(pgx_ctx *c, HostImage &in, HostImage &out)
 {
-    const size_t nn = (size_t)(n_nodes > 0 ? n_nodes : 1), nt1 = (size_t)(n_tracks > 0 ? n_tracks : 1);
-    WsCarver w(nullptr);
-    w.put((size_t)n_frames * stride * sizeof(pgx_keypoint));
-    for (int i = 0; i < 3 && frame_src[i]; i++) at.frame[i] = w.put((size_t)n_frames * frame_bytes[i]);
-    at.off = w.put((size_t)(n_tracks + 1) * 4);
-    at.nodes = w.put(nn * 8);
-    if (per_track) {
-        at.xyz = w.put(nt1 * 24);
-        at.flags = w.put(nt1 * 4);
-    }
-    at.ts = w.put(256);
-    HIPCHK(c, c->pin_in.ensure(w.total()));
-    HIPCHK(c, c->st_a.ensure(w.total()));
-    char *h = c->pin_in.as<char>();
-    for (int f = 0, k = 0; f < n_frames; k += counts[f], f++)
-        if (counts[f] > 0) std::memcpy(h + (size_t)f * stride * sizeof(pgx_keypoint), kps + k, (size_t)counts[f] * sizeof(pgx_keypoint));
-    for (int i = 0; i < 3 && frame_src[i]; i++) std::memcpy(h + at.frame[i], frame_src[i], (size_t)n_frames * frame_bytes[i]);
-    std::memcpy(h + at.off, track_offsets, (size_t)(n_tracks + 1) * 4);
-    if (n_nodes > 0) std::memcpy(h + at.nodes, nodes, (size_t)n_nodes * 8);
-    if (per_track && n_tracks > 0) std::memcpy(h + at.xyz, xyz, (size_t)n_tracks * 24);
-    if (per_track && n_tracks > 0 && track_flags) std::memcpy(h + at.flags, track_flags, (size_t)n_tracks * 4);
-    const int32_t ts[8] = {n_tracks, (int32_t)n_nodes};
-    std::memcpy(h + at.ts, ts, sizeof ts);
-    HIPCHK(c, hipMemcpyAsync(c->st_a.p, h, w.total(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, c->pin_in.ensure(in.total()));
+    HIPCHK(c, c->st_a.ensure(in.total()));
+    HIPCHK(c, c->st_b.ensure(out.total()));
+    in.pack(c->pin_in.as<char>());
+    in.base = c->st_a.as<char>();
+    out.base = c->st_b.as<char>();
+    HIPCHK(c, hipMemcpyAsync(c->st_a.p, c->pin_in.p, in.total(), hipMemcpyHostToDevice, c->stream));
     return PGX_OK;
 }
 
-// the uploaded section at `off`
-extern "C++" template <class T> const T *dev_in(pgx_ctx *c, size_t off) { return reinterpret_cast<const T *>(c->st_a.as<char>() + off); }
+// ... and back: one copy per output section that has a destination, then the call's status
+int download_images(pgx_ctx *c, const HostImage &out)
+{
+    for (const HostImage::Move &m : out.moves) HIPCHK(c, hipMemcpyAsync(m.host, out.base + m.off, m.bytes, hipMemcpyDeviceToHost, c->stream));
+    return sync_status(c);
+}
+
+// the range checks that the stages share: PGX_OK, or PGX_E_BADARG with the one text
+int samples_ok(pgx_ctx *c, int n) { return n < 1 || n > 65536 ? fail(c, PGX_E_BADARG, "n_samples = %d, must be in [1, 65536]", n) : PGX_OK; }
+int inlier_px_ok(pgx_ctx *c, double px) { return px > 0.0 && std::isfinite(px) ? PGX_OK : fail(c, PGX_E_BADARG, "inlier_px must be finite and > 0"); }
+int iters_ok(pgx_ctx *c, const char *name, int n, int most)
+{
+    return n < 0 || n > most ? fail(c, PGX_E_BADARG, "%s = %d, must be in [0, %d]", name, n, most) : PGX_OK;
+}
+int pairs_ok(pgx_ctx *c, int M, int stride)
+{
+    if (M < 0) return fail(c, PGX_E_BADARG, "M = %d, must be >= 0", M);
+    return stride < 1 || stride > (1 << PGX_IDX_BITS) ? fail(c, PGX_E_BADARG, "stride must be in [1, 2^20]") : PGX_OK;
+}
 
 int tri_args(pgx_ctx *c, double min_parallax_deg, double max_reproj_px, int refine_iters)
 {
-    if (refine_iters < 0 || refine_iters > 32) return fail(c, PGX_E_BADARG, "refine_iters = %d, must be in [0, 32]", refine_iters);
+    if (iters_ok(c, "refine_iters", refine_iters, 32) != PGX_OK) return PGX_E_BADARG;
     if (!(min_parallax_deg >= 0.0)) return fail(c, PGX_E_BADARG, "min_parallax_deg must be >= 0 (and not NaN)");
     if (!(max_reproj_px > 0.0)) return fail(c, PGX_E_BADARG, "max_reproj_px must be > 0 (and not NaN; +inf disables the test)");
     return PGX_OK;
@@ -1405,7 +1397,7 @@ int tri_args(pgx_ctx *c, double min_parallax_deg, double max_reproj_px, int refi
 
 int ba_args(pgx_ctx *c, int max_iters, double huber_px, double lambda0)
 {
-    if (max_iters < 0 || max_iters > 100) return fail(c, PGX_E_BADARG, "max_iters = %d, must be in [0, 100]", max_iters);
+    if (iters_ok(c, "max_iters", max_iters, 100) != PGX_OK) return PGX_E_BADARG;
     if (!(huber_px > 0.0)) return fail(c, PGX_E_BADARG, "huber_px must be > 0 (and not NaN; +inf is plain least squares)");
     if (!(lambda0 > 0.0) || !std::isfinite(lambda0)) return fail(c, PGX_E_BADARG, "lambda0 must be finite and > 0");
     return PGX_OK;
@@ -1413,22 +1405,16 @@ int ba_args(pgx_ctx *c, int max_iters, double huber_px, double lambda0)
 
 int reg_args(pgx_ctx *c, int n_samples, double inlier_px, int min_inliers, int refine_iters)
 {
-    if (n_samples < 1 || n_samples > 65536) return fail(c, PGX_E_BADARG, "n_samples = %d, must be in [1, 65536]", n_samples);
-    if (!(inlier_px > 0.0) || !std::isfinite(inlier_px)) return fail(c, PGX_E_BADARG, "inlier_px must be finite and > 0");
+    if (samples_ok(c, n_samples) != PGX_OK || inlier_px_ok(c, inlier_px) != PGX_OK) return PGX_E_BADARG;
     if (min_inliers < 3) return fail(c, PGX_E_BADARG, "min_inliers = %d, must be >= 3", min_inliers);
-    if (refine_iters < 0 || refine_iters > 32) return fail(c, PGX_E_BADARG, "refine_iters = %d, must be in [0, 32]", refine_iters);
-    return PGX_OK;
+    return iters_ok(c, "refine_iters", refine_iters, 32);
 }
 
 int ver_args(pgx_ctx *c, int M, int stride, int n_samples, double inlier_px, int min_inliers, int refit_iters)
 {
-    if (M < 0) return fail(c, PGX_E_BADARG, "M = %d, must be >= 0", M);
-    if (stride < 1 || stride > (1 << PGX_IDX_BITS)) return fail(c, PGX_E_BADARG, "stride must be in [1, 2^20]");
-    if (n_samples < 1 || n_samples > 65536) return fail(c, PGX_E_BADARG, "n_samples = %d, must be in [1, 65536]", n_samples);
-    if (!(inlier_px > 0.0) || !std::isfinite(inlier_px)) return fail(c, PGX_E_BADARG, "inlier_px must be finite and > 0");
+    if (pairs_ok(c, M, stride) != PGX_OK || samples_ok(c, n_samples) != PGX_OK || inlier_px_ok(c, inlier_px) != PGX_OK) return PGX_E_BADARG;
     if (min_inliers < 8) return fail(c, PGX_E_BADARG, "min_inliers = %d, must be >= 8", min_inliers);
-    if (refit_iters < 0 || refit_iters > 8) return fail(c, PGX_E_BADARG, "refit_iters = %d, must be in [0, 8]", refit_iters);
-    return PGX_OK;
+    return iters_ok(c, "refit_iters", refit_iters, 8);
 }
 
 // the M pairs of a call in chunks of pgx_set_match_chunk pairs that share ws_ver, then the report
@@ -1488,39 +1474,27 @@ int pgx_triangulate_tracks(pgx_ctx *c, const pgx_keypoint *kps, const int32_t *c
         return c ? fail(c, PGX_E_BADARG, "null pointer or bad size") : PGX_E_BADARG;
     Lock l(c);
     int rc = tri_args(c, min_parallax_deg, max_reproj_px, refine_iters);
-    int stride;
-    long long n_nodes;
-    if (rc == PGX_OK) rc = check_host_tracks(c, kps, counts, n_frames, track_offsets, nodes, n_tracks, &stride, &n_nodes);
+    HostTracks t;
+    if (rc == PGX_OK) rc = check_host_tracks(c, kps, counts, n_frames, track_offsets, nodes, n_tracks, &t);
     if (rc != PGX_OK) return rc;
     for (int i = 0; i < 8; i++) summary[i] = 0;
     if (n_tracks == 0) return PGX_OK;
-    HostUpload in;
-    rc = stage_host_tracks(c, kps, counts, n_frames, stride, {P, nullptr, nullptr}, {96, 0, 0}, track_offsets, nodes, n_tracks, n_nodes,
-                           false, nullptr, nullptr, in);
-    if (rc != PGX_OK) return rc;
-    // outputs: xyz, quality, node_err, flags, summary
-    WsCarver out(nullptr);
-    const size_t p_xyz = out.put((size_t)n_tracks * 24), p_q = out.put((size_t)n_tracks * 24),
-                 p_err = out.put((size_t)(n_nodes > 0 ? n_nodes : 1) * 8), p_fl = out.put((size_t)n_tracks * 4), p_sum = out.put(256);
-    HIPCHK(c, c->st_b.ensure(out.total()));
-    char *o = c->st_b.as<char>();
+    HostImage in, out;
+    const TracksIn i = tracks_in(in, t, {P, nullptr, nullptr}, {96, 0, 0}, false, nullptr, nullptr);
+    const int o_xyz = out.add(xyz, n_tracks, 24), o_q = out.add(quality, n_tracks, 24),
+              o_err = out.add(node_err, t.n_nodes, 8, 1, node_err != nullptr), o_fl = out.add(flags, n_tracks, 4),
+              o_sum = out.add(summary, 8, 4, 64);
+    if ((rc = stage_images(c, in, out)) != PGX_OK) return rc;
     HIPCHK(c, c->ws_tri.ensure(pgx_triangulate_ws_bytes(n_frames)));
     {
         ProfScope ps(c, "triangulate");
-        pgx_launch_triangulate(c->stream, dev_in<pgx_keypoint>(c, 0), n_frames, stride, nullptr, n_frames, dev_in<double>(c, in.frame[0]),
-                               dev_in<int32_t>(c, in.off), dev_in<int32_t>(c, in.nodes), n_nodes, dev_in<int32_t>(c, in.ts), n_tracks,
-                               min_parallax_deg, max_reproj_px, refine_iters, reinterpret_cast<double *>(o + p_xyz),
-                               reinterpret_cast<double *>(o + p_q), reinterpret_cast<int32_t *>(o + p_fl),
-                               node_err ? reinterpret_cast<double *>(o + p_err) : nullptr, reinterpret_cast<int32_t *>(o + p_sum),
-                               c->ws_tri.p, c->d_status);
+        pgx_launch_triangulate(c->stream, in.dev<pgx_keypoint>(i.kp), n_frames, t.stride, nullptr, n_frames, in.dev<double>(i.frame[0]),
+                               in.dev<int32_t>(i.off), in.dev<int32_t>(i.nodes), t.n_nodes, in.dev<int32_t>(i.ts), n_tracks,
+                               min_parallax_deg, max_reproj_px, refine_iters, out.dev<double>(o_xyz), out.dev<double>(o_q),
+                               out.dev<int32_t>(o_fl), out.dev<double>(o_err), out.dev<int32_t>(o_sum), c->ws_tri.p, c->d_status);
     }
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(xyz, o + p_xyz, (size_t)n_tracks * 24, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(quality, o + p_q, (size_t)n_tracks * 24, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(flags, o + p_fl, (size_t)n_tracks * 4, hipMemcpyDeviceToHost, c->stream));
-    if (node_err && n_nodes > 0) HIPCHK(c, hipMemcpyAsync(node_err, o + p_err, (size_t)n_nodes * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(summary, o + p_sum, 8 * 4, hipMemcpyDeviceToHost, c->stream));
-    return sync_status(c);
+    return download_images(c, out);
 }
 
 // ---- bundle adjustment of cameras and track points ----------------------------------------------------------------
@@ -1560,40 +1534,26 @@ int pgx_bundle_adjust(pgx_ctx *c, const pgx_keypoint *kps, const int32_t *counts
         return c ? fail(c, PGX_E_BADARG, "null pointer or bad size") : PGX_E_BADARG;
     Lock l(c);
     int rc = ba_args(c, max_iters, huber_px, lambda0);
-    int stride;
-    long long n_nodes;
-    if (rc == PGX_OK) rc = check_host_tracks(c, kps, counts, n_frames, track_offsets, nodes, n_tracks, &stride, &n_nodes);
-    HostUpload in;
-    if (rc == PGX_OK)
-        rc = stage_host_tracks(c, kps, counts, n_frames, stride, {K, Rt_in, fixed}, {32, 96, 4}, track_offsets, nodes, n_tracks, n_nodes,
-                               true, xyz_in, track_flags, in);
+    HostTracks t;
+    if (rc == PGX_OK) rc = check_host_tracks(c, kps, counts, n_frames, track_offsets, nodes, n_tracks, &t);
     if (rc != PGX_OK) return rc;
-    // outputs: Rt, P, xyz, node_err, trace, report
-    WsCarver out(nullptr);
-    const size_t p_Rt = out.put((size_t)n_frames * 96), p_P = out.put((size_t)n_frames * 96),
-                 p_xyz = out.put((size_t)(n_tracks > 0 ? n_tracks : 1) * 24), p_err = out.put((size_t)(n_nodes > 0 ? n_nodes : 1) * 8),
-                 p_tr = out.put((size_t)(max_iters + 1) * 16), p_rep = out.put(256);
-    HIPCHK(c, c->st_b.ensure(out.total()));
-    char *o = c->st_b.as<char>();
-    HIPCHK(c, c->ws_ba.ensure(pgx_bundle_ws_bytes(n_frames, n_tracks, n_nodes)));
+    HostImage in, out;
+    const TracksIn i = tracks_in(in, t, {K, Rt_in, fixed}, {32, 96, 4}, true, xyz_in, track_flags);
+    const int o_Rt = out.add(Rt_out, n_frames, 96), o_P = out.add(P_out, n_frames, 96), o_xyz = out.add(xyz_out, n_tracks, 24, 1),
+              o_err = out.add(node_err, t.n_nodes, 8, 1, node_err != nullptr), o_tr = out.add(trace, max_iters + 1, 16),
+              o_rep = out.add(report, 8, 4, 64);
+    if ((rc = stage_images(c, in, out)) != PGX_OK) return rc;
+    HIPCHK(c, c->ws_ba.ensure(pgx_bundle_ws_bytes(n_frames, n_tracks, t.n_nodes)));
     {
         ProfScope ps(c, "bundle");
-        pgx_launch_bundle(c->stream, dev_in<pgx_keypoint>(c, 0), n_frames, stride, nullptr, n_frames, dev_in<double>(c, in.frame[0]),
-                          dev_in<double>(c, in.frame[1]), dev_in<int32_t>(c, in.frame[2]), dev_in<int32_t>(c, in.off),
-                          dev_in<int32_t>(c, in.nodes), n_nodes, dev_in<int32_t>(c, in.ts), n_tracks, dev_in<double>(c, in.xyz),
-                          track_flags ? dev_in<int32_t>(c, in.flags) : nullptr, max_iters, huber_px, lambda0,
-                          reinterpret_cast<double *>(o + p_Rt), reinterpret_cast<double *>(o + p_P), reinterpret_cast<double *>(o + p_xyz),
-                          node_err ? reinterpret_cast<double *>(o + p_err) : nullptr, reinterpret_cast<double *>(o + p_tr),
-                          reinterpret_cast<int32_t *>(o + p_rep), c->ws_ba.p, c->d_status);
+        pgx_launch_bundle(c->stream, in.dev<pgx_keypoint>(i.kp), n_frames, t.stride, nullptr, n_frames, in.dev<double>(i.frame[0]),
+                          in.dev<double>(i.frame[1]), in.dev<int32_t>(i.frame[2]), in.dev<int32_t>(i.off), in.dev<int32_t>(i.nodes),
+                          t.n_nodes, in.dev<int32_t>(i.ts), n_tracks, in.dev<double>(i.xyz), in.dev<int32_t>(i.flags), max_iters, huber_px,
+                          lambda0, out.dev<double>(o_Rt), out.dev<double>(o_P), out.dev<double>(o_xyz), out.dev<double>(o_err),
+                          out.dev<double>(o_tr), out.dev<int32_t>(o_rep), c->ws_ba.p, c->d_status);
     }
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(Rt_out, o + p_Rt, (size_t)n_frames * 96, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(P_out, o + p_P, (size_t)n_frames * 96, hipMemcpyDeviceToHost, c->stream));
-    if (n_tracks > 0) HIPCHK(c, hipMemcpyAsync(xyz_out, o + p_xyz, (size_t)n_tracks * 24, hipMemcpyDeviceToHost, c->stream));
-    if (node_err && n_nodes > 0) HIPCHK(c, hipMemcpyAsync(node_err, o + p_err, (size_t)n_nodes * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(trace, o + p_tr, (size_t)(max_iters + 1) * 16, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(report, o + p_rep, 8 * 4, hipMemcpyDeviceToHost, c->stream));
-    return sync_status(c);
+    return download_images(c, out);
 }
 
 // ---- frame registration by P3P RANSAC ------------------------------------------------------------------------------
@@ -1634,39 +1594,26 @@ int pgx_register_frames(pgx_ctx *c, const pgx_keypoint *kps, const int32_t *coun
         return c ? fail(c, PGX_E_BADARG, "null pointer or bad size") : PGX_E_BADARG;
     Lock l(c);
     int rc = reg_args(c, n_samples, inlier_px, min_inliers, refine_iters);
-    int stride;
-    long long n_nodes;
-    if (rc == PGX_OK) rc = check_host_tracks(c, kps, counts, n_frames, track_offsets, nodes, n_tracks, &stride, &n_nodes);
-    HostUpload in;
-    if (rc == PGX_OK)
-        rc = stage_host_tracks(c, kps, counts, n_frames, stride, {K, Rt_in, reg}, {32, 96, 4}, track_offsets, nodes, n_tracks, n_nodes,
-                               true, xyz, track_flags, in);
+    HostTracks t;
+    if (rc == PGX_OK) rc = check_host_tracks(c, kps, counts, n_frames, track_offsets, nodes, n_tracks, &t);
     if (rc != PGX_OK) return rc;
-    // outputs: Rt, P, stats, err, node_inlier, report
-    WsCarver out(nullptr);
-    const size_t p_Rt = out.put((size_t)n_frames * 96), p_P = out.put((size_t)n_frames * 96), p_st = out.put((size_t)n_frames * 16),
-                 p_er = out.put((size_t)n_frames * 16), p_ni = out.put((size_t)(n_nodes > 0 ? n_nodes : 1) * 4), p_rep = out.put(256);
-    HIPCHK(c, c->st_b.ensure(out.total()));
-    char *o = c->st_b.as<char>();
-    HIPCHK(c, c->ws_reg.ensure(pgx_register_ws_bytes(n_frames, n_nodes, n_samples)));
+    HostImage in, out;
+    const TracksIn i = tracks_in(in, t, {K, Rt_in, reg}, {32, 96, 4}, true, xyz, track_flags);
+    const int o_Rt = out.add(Rt_out, n_frames, 96), o_P = out.add(P_out, n_frames, 96), o_st = out.add(frame_stats, n_frames, 16),
+              o_er = out.add(frame_err, n_frames, 16), o_ni = out.add(node_inlier, t.n_nodes, 4, 1, node_inlier != nullptr),
+              o_rep = out.add(report, 8, 4, 64);
+    if ((rc = stage_images(c, in, out)) != PGX_OK) return rc;
+    HIPCHK(c, c->ws_reg.ensure(pgx_register_ws_bytes(n_frames, t.n_nodes, n_samples)));
     {
         ProfScope ps(c, "register");
-        pgx_launch_register(c->stream, dev_in<pgx_keypoint>(c, 0), n_frames, stride, nullptr, n_frames, dev_in<double>(c, in.frame[0]),
-                            dev_in<double>(c, in.frame[1]), dev_in<int32_t>(c, in.frame[2]), dev_in<int32_t>(c, in.off),
-                            dev_in<int32_t>(c, in.nodes), n_nodes, dev_in<int32_t>(c, in.ts), n_tracks, dev_in<double>(c, in.xyz),
-                            track_flags ? dev_in<int32_t>(c, in.flags) : nullptr, n_samples, inlier_px, min_inliers, refine_iters, seed,
-                            reinterpret_cast<double *>(o + p_Rt), reinterpret_cast<double *>(o + p_P), reinterpret_cast<int32_t *>(o + p_st),
-                            reinterpret_cast<double *>(o + p_er), node_inlier ? reinterpret_cast<int32_t *>(o + p_ni) : nullptr,
-                            reinterpret_cast<int32_t *>(o + p_rep), c->ws_reg.p, c->d_status);
+        pgx_launch_register(c->stream, in.dev<pgx_keypoint>(i.kp), n_frames, t.stride, nullptr, n_frames, in.dev<double>(i.frame[0]),
+                            in.dev<double>(i.frame[1]), in.dev<int32_t>(i.frame[2]), in.dev<int32_t>(i.off), in.dev<int32_t>(i.nodes),
+                            t.n_nodes, in.dev<int32_t>(i.ts), n_tracks, in.dev<double>(i.xyz), in.dev<int32_t>(i.flags), n_samples, inlier_px,
+                            min_inliers, refine_iters, seed, out.dev<double>(o_Rt), out.dev<double>(o_P), out.dev<int32_t>(o_st),
+                            out.dev<double>(o_er), out.dev<int32_t>(o_ni), out.dev<int32_t>(o_rep), c->ws_reg.p, c->d_status);
     }
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(Rt_out, o + p_Rt, (size_t)n_frames * 96, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(P_out, o + p_P, (size_t)n_frames * 96, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(frame_stats, o + p_st, (size_t)n_frames * 16, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(frame_err, o + p_er, (size_t)n_frames * 16, hipMemcpyDeviceToHost, c->stream));
-    if (node_inlier && n_nodes > 0) HIPCHK(c, hipMemcpyAsync(node_inlier, o + p_ni, (size_t)n_nodes * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(report, o + p_rep, 8 * 4, hipMemcpyDeviceToHost, c->stream));
-    return sync_status(c);
+    return download_images(c, out);
 }
 
 // ---- two-view verification by epipolar RANSAC ----------------------------------------------------------------------
@@ -1699,39 +1646,19 @@ int pgx_verify_pair(pgx_ctx *c, const pgx_keypoint *kp1, int n1, const pgx_keypo
     const int S = n1 > n2 ? n1 : (n2 > 0 ? n2 : 1);
     const int rc = ver_args(c, 1, S, n_samples, inlier_px, min_inliers, refit_iters);
     if (rc != PGX_OK) return rc;
-    // inputs in st_a: keypoints [3][S] (slot 0 unused), the list [S], counts [3], the pair (1, 2); outputs in st_b
-    WsCarver in(nullptr), ot(nullptr);
-    const size_t i_kp = in.put((size_t)3 * S * sizeof(pgx_keypoint)), i_ml = in.put((size_t)S * sizeof(pgx_pair)), i_meta = in.put(64);
-    const size_t o_out = ot.put((size_t)S * sizeof(pgx_pair)), o_F = ot.put(72), o_st = ot.put(32), o_in = ot.put((size_t)S * 4),
-                 o_rep = ot.put(32);
-    HIPCHK(c, c->st_a.ensure(in.total()));
-    HIPCHK(c, c->st_b.ensure(ot.total()));
-    char *di = c->st_a.as<char>(), *dout = c->st_b.as<char>();
-    const int32_t meta[5] = {0, n1, n2, 1, 2};
-    HIPCHK(c, hipMemsetAsync(di, 0, in.total(), c->stream));
-    if (n1 > 0) {
-        HIPCHK(c, hipMemcpyAsync(di + i_kp + (size_t)S * sizeof(pgx_keypoint), kp1, (size_t)n1 * sizeof(pgx_keypoint), hipMemcpyHostToDevice,
-                                 c->stream));
-        HIPCHK(c, hipMemcpyAsync(di + i_ml, matches, (size_t)n1 * sizeof(pgx_pair), hipMemcpyHostToDevice, c->stream));
-    }
-    if (n2 > 0)
-        HIPCHK(c, hipMemcpyAsync(di + i_kp + (size_t)2 * S * sizeof(pgx_keypoint), kp2, (size_t)n2 * sizeof(pgx_keypoint), hipMemcpyHostToDevice,
-                                 c->stream));
-    HIPCHK(c, hipMemcpyAsync(di + i_meta, meta, sizeof meta, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));   // meta is on this call's stack
-    const int32_t *d_meta = reinterpret_cast<const int32_t *>(di + i_meta);
-    const int rq = enqueue_verify(c, reinterpret_cast<const pgx_keypoint *>(di + i_kp), reinterpret_cast<const pgx_pair *>(di + i_ml), d_meta,
-                                  d_meta + 3, 1, S, max_dist, n_samples, inlier_px, min_inliers, refit_iters, seed,
-                                  reinterpret_cast<pgx_pair *>(dout + o_out), reinterpret_cast<double *>(dout + o_F), nullptr,
-                                  reinterpret_cast<int32_t *>(dout + o_st), inlier ? reinterpret_cast<int32_t *>(dout + o_in) : nullptr,
-                                  nullptr, nullptr, reinterpret_cast<int32_t *>(dout + o_rep));
+    HostImage in, ot;
+    const PairIn i = pair_in(in, kp1, n1, kp2, n2, matches, S);
+    // the report is the device form's: carved, not downloaded
+    const int o_out = ot.add(out, n1, sizeof(pgx_pair), S), o_F = ot.add(F, 9, 8), o_st = ot.add(stats, 8, 4),
+              o_in = ot.add(inlier, n1, 4, S, inlier != nullptr), o_rep = ot.add(nullptr, 0, 4, 8);
+    if (const int rs = stage_images(c, in, ot); rs != PGX_OK) return rs;
+    const int32_t *d_meta = in.dev<int32_t>(i.meta);
+    const int rq = enqueue_verify(c, in.dev<pgx_keypoint>(i.kp), in.dev<pgx_pair>(i.list), d_meta, d_meta + 3, 1, S, max_dist, n_samples,
+                                  inlier_px, min_inliers, refit_iters, seed, ot.dev<pgx_pair>(o_out), ot.dev<double>(o_F), nullptr,
+                                  ot.dev<int32_t>(o_st), ot.dev<int32_t>(o_in), nullptr, nullptr, ot.dev<int32_t>(o_rep));
     if (rq != PGX_OK) return rq;
     HIPCHK(c, hipGetLastError());
-    if (n1 > 0) HIPCHK(c, hipMemcpyAsync(out, dout + o_out, (size_t)n1 * sizeof(pgx_pair), hipMemcpyDeviceToHost, c->stream));
-    if (inlier && n1 > 0) HIPCHK(c, hipMemcpyAsync(inlier, dout + o_in, (size_t)n1 * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(F, dout + o_F, 72, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(stats, dout + o_st, 32, hipMemcpyDeviceToHost, c->stream));
-    return sync_status(c);
+    return download_images(c, ot);
 }
 
 // ---- relative pose per image pair and the choice of the initial pair ------------------------------------------------
@@ -1740,8 +1667,7 @@ namespace {
 // cos^2 of the angle gate through *cos2
 int init_args(pgx_ctx *c, int M, int stride, double min_angle_deg, double min_front_frac, int min_points, double *cos2)
 {
-    if (M < 0) return fail(c, PGX_E_BADARG, "M = %d, must be >= 0", M);
-    if (stride < 1 || stride > (1 << PGX_IDX_BITS)) return fail(c, PGX_E_BADARG, "stride must be in [1, 2^20]");
+    if (pairs_ok(c, M, stride) != PGX_OK) return PGX_E_BADARG;
     if (!(min_angle_deg >= 0.0 && min_angle_deg < 90.0)) return fail(c, PGX_E_BADARG, "min_angle_deg must be in [0, 90) (and not NaN)");
     if (!(min_front_frac > 0.0 && min_front_frac <= 1.0)) return fail(c, PGX_E_BADARG, "min_front_frac must be in (0, 1] (and not NaN)");
     if (min_points < 1) return fail(c, PGX_E_BADARG, "min_points = %d, must be >= 1", min_points);
@@ -1788,50 +1714,28 @@ int pgx_relative_pose(pgx_ctx *c, const pgx_keypoint *kp1, int n1, const pgx_key
     double cos2 = 0.0;
     const int rc = init_args(c, 1, S, min_angle_deg, min_front_frac, min_points, &cos2);
     if (rc != PGX_OK) return rc;
-    // inputs in st_a: keypoints [3][S] (slot 0 unused), the list [S], F [9], K [3][4] (row 0 unused), counts [3] and the pair
-    // (1, 2); outputs in st_b
-    WsCarver in(nullptr), ot(nullptr);
-    const size_t i_kp = in.put((size_t)3 * S * sizeof(pgx_keypoint)), i_ml = in.put((size_t)S * sizeof(pgx_pair)), i_F = in.put(72),
-                 i_K = in.put(96), i_meta = in.put(64);
-    const size_t o_Rt = ot.put(96), o_st = ot.put(32), o_sg = ot.put(8), o_cand = ot.put(384), o_fr = ot.put(2 * 3 * 96),
-                 o_fi = ot.put(2 * 3 * 4 + 64), o_rep = ot.put(32);
-    HIPCHK(c, c->st_a.ensure(in.total()));
-    HIPCHK(c, c->st_b.ensure(ot.total()));
+    // the pair (1, 2) of three frames, then F [9] and K [3][4] by frame (row 0 unused)
+    HostImage in, ot;
+    const PairIn i = pair_in(in, kp1, n1, kp2, n2, matches, S);
+    const int i_F = in.add(F, 9, 8), i_K = in.add(nullptr, 0, 32, 3);
+    in.put_at(32, K_a, 32);
+    in.put_at(64, K_b, 32);
+    // carved, not downloaded: the frames' Rt_out then P_out [3][12], fixed_out [3] then, 8 words in, register_out [3], the report
+    const int o_Rt = ot.add(Rt, 12, 8), o_st = ot.add(stats, 8, 4), o_sg = ot.add(sigma, 1, 8), o_cand = ot.add(cand_Rt, 48, 8, 0, cand_Rt != nullptr),
+              o_fr = ot.add(nullptr, 0, 96, 2 * 3), o_fi = ot.add(nullptr, 0, 4, 2 * 3 + 16), o_rep = ot.add(nullptr, 0, 4, 8);
+    if (const int rs = stage_images(c, in, ot); rs != PGX_OK) return rs;
     HIPCHK(c, c->ws_init.ensure(pgx_init_pair_ws_bytes(1)));
-    char *di = c->st_a.as<char>(), *dout = c->st_b.as<char>();
-    const int32_t meta[5] = {0, n1, n2, 1, 2};
-    HIPCHK(c, hipMemsetAsync(di, 0, in.total(), c->stream));
-    if (n1 > 0) {
-        HIPCHK(c, hipMemcpyAsync(di + i_kp + (size_t)S * sizeof(pgx_keypoint), kp1, (size_t)n1 * sizeof(pgx_keypoint), hipMemcpyHostToDevice,
-                                 c->stream));
-        HIPCHK(c, hipMemcpyAsync(di + i_ml, matches, (size_t)n1 * sizeof(pgx_pair), hipMemcpyHostToDevice, c->stream));
-    }
-    if (n2 > 0)
-        HIPCHK(c, hipMemcpyAsync(di + i_kp + (size_t)2 * S * sizeof(pgx_keypoint), kp2, (size_t)n2 * sizeof(pgx_keypoint), hipMemcpyHostToDevice,
-                                 c->stream));
-    HIPCHK(c, hipMemcpyAsync(di + i_F, F, 72, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(di + i_K + 32, K_a, 32, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(di + i_K + 64, K_b, 32, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(di + i_meta, meta, sizeof meta, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));   // meta is on this call's stack
-    const int32_t *d_meta = reinterpret_cast<const int32_t *>(di + i_meta);
+    const int32_t *d_meta = in.dev<int32_t>(i.meta);
     {
         ProfScope ps(c, "init_pair");
-        pgx_launch_init_pair(c->stream, reinterpret_cast<const pgx_keypoint *>(di + i_kp), reinterpret_cast<const pgx_pair *>(di + i_ml),
-                             d_meta, d_meta + 3, 1, 3, S, nullptr, 3, max_dist, reinterpret_cast<const double *>(di + i_F),
-                             reinterpret_cast<const double *>(di + i_K), cos2, min_front_frac, min_points,
-                             reinterpret_cast<double *>(dout + o_Rt), reinterpret_cast<int32_t *>(dout + o_st),
-                             reinterpret_cast<double *>(dout + o_sg), cand_Rt ? reinterpret_cast<double *>(dout + o_cand) : nullptr,
-                             reinterpret_cast<double *>(dout + o_fr), reinterpret_cast<double *>(dout + o_fr + 3 * 96),
-                             reinterpret_cast<int32_t *>(dout + o_fi), reinterpret_cast<int32_t *>(dout + o_fi + 32),
-                             reinterpret_cast<int32_t *>(dout + o_rep), c->ws_init.p);
+        pgx_launch_init_pair(c->stream, in.dev<pgx_keypoint>(i.kp), in.dev<pgx_pair>(i.list), d_meta, d_meta + 3, 1, 3, S, nullptr, 3,
+                             max_dist, in.dev<double>(i_F), in.dev<double>(i_K), cos2, min_front_frac, min_points, ot.dev<double>(o_Rt),
+                             ot.dev<int32_t>(o_st), ot.dev<double>(o_sg), ot.dev<double>(o_cand), ot.dev<double>(o_fr),
+                             ot.dev<double>(o_fr) + 3 * 12, ot.dev<int32_t>(o_fi), ot.dev<int32_t>(o_fi) + 8, ot.dev<int32_t>(o_rep),
+                             c->ws_init.p);
     }
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(Rt, dout + o_Rt, 96, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(stats, dout + o_st, 32, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(sigma, dout + o_sg, 8, hipMemcpyDeviceToHost, c->stream));
-    if (cand_Rt) HIPCHK(c, hipMemcpyAsync(cand_Rt, dout + o_cand, 384, hipMemcpyDeviceToHost, c->stream));
-    return sync_status(c);
+    return download_images(c, ot);
 }
 
 // ---- measurement hooks ---------------------------------------------------------------------

@@ -1,0 +1,115 @@
+// pgx_hoststage.h -- buffers laid out in 256-byte-aligned sections: the workspace carver of the launchers and, on it, the
+// image that a host form uploads or downloads in (HostImage), with the input lists that the geometry host forms share.
+// Host code without HIP: tests/hoststage_driver.cpp builds it with g++ under sanitizers, and pgx_api.hip puts the copies
+// around it (stage_images, download_images).  Internal to libpgx.so; DESIGN.md section 14g.
+#pragma once
+
+#include "../../include/pgx.h"
+
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+// Hands out 256-byte-aligned sections of a workspace, so that a stage describes its layout once: the launcher carves
+// the real buffer, *_ws_bytes the null one and reads total().
+struct WsCarver {
+    char *base;
+    size_t at = 0;
+    explicit WsCarver(void *ws) : base(static_cast<char *>(ws)) {}
+    static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+    size_t put(size_t bytes)   // the section's offset
+    {
+        const size_t p = at;
+        at += align256(bytes);
+        return p;
+    }
+    template <class T> T *take(size_t bytes)
+    {
+        const size_t p = put(bytes);
+        return base ? reinterpret_cast<T *>(base + p) : nullptr;
+    }
+    size_t total() const { return at; }
+};
+
+// The inputs or the outputs of a host form as one image.  A section is declared once, add(host, n, elem, at_least, present):
+// max(n, at_least) elements of `elem` bytes, the first n of which travel from the host source (pack) or to the host
+// destination (moves, after the launch); none travel with host null or n 0.  An absent section is carved like any
+// other, but dev() is null and nothing travels.  The sources are only read: `host` is not const for the outputs' sake.
+struct HostImage {
+    struct Sec { size_t off; bool present; };
+    struct Move { size_t off; void *host; size_t bytes; };   // off: from the image's start
+    std::vector<Sec> secs;
+    std::vector<Move> moves;
+    WsCarver w{nullptr};
+    char *base = nullptr;                      // where the image lies on the device
+    std::vector<std::vector<int32_t>> words;   // add_words' blocks: `moves` points into them, so an image is not copied
+    HostImage() = default; HostImage(const HostImage &) = delete; HostImage &operator=(const HostImage &) = delete;
+
+    int add(const void *host, size_t n, size_t elem, size_t at_least = 0, bool present = true)
+    {
+        secs.push_back({w.put(std::max(n, at_least) * elem), present});
+        if (present) put_at(0, host, n * elem);
+        return (int)secs.size() - 1;
+    }
+    void put_at(size_t at, const void *host, size_t bytes)   // one more source inside the section declared last, `at` bytes in
+    {
+        if (host && bytes) moves.push_back({secs.back().off + at, const_cast<void *>(host), bytes});
+    }
+    int add_words(std::initializer_list<int32_t> v, size_t at_least)   // a few words held by value
+    {
+        words.emplace_back(v);
+        return add(words.back().data(), v.size(), 4, at_least);
+    }
+    // keypoints by slot: counts[f] elements of frame f, frame behind frame in src, to slot f of `stride` elements
+    int add_slots(const void *src, const int32_t *counts, size_t n_slots, size_t stride, size_t elem)
+    {
+        const int s = add(nullptr, 0, elem, n_slots * stride);
+        for (size_t f = 0, k = 0; f < n_slots; k += counts[f], f++)
+            put_at(f * stride * elem, static_cast<const char *>(src) + k * elem, counts[f] * elem);
+        return s;
+    }
+    size_t total() const { return w.total(); }
+    void pack(char *dst) const   // all total() bytes: zero wherever no source lies
+    {
+        std::memset(dst, 0, total());
+        for (const Move &m : moves) std::memcpy(dst + m.off, m.host, m.bytes);
+    }
+    template <class T> T *dev(int s) const { return secs[s].present ? reinterpret_cast<T *>(base + secs[s].off) : nullptr; }
+};
+
+// The keypoints and the track graph of a host form, checked: stride = max(counts, 1), n_nodes = track_offsets[n_tracks].
+struct HostTracks {
+    const pgx_keypoint *kps; const int32_t *counts, *track_offsets, *nodes; int n_frames, n_tracks, stride; long long n_nodes;
+};
+
+// triangulation, bundle adjustment, registration: keypoints [n_frames][stride], the stage's per-frame arrays (frame_src,
+// frame_bytes per frame; nullptr ends the list), offsets, nodes, with per_track the points and flags of the tracks, and
+// the track summary's {n_tracks, n_nodes}
+struct TracksIn { int kp, frame[3], off, nodes, xyz, flags, ts; };
+inline TracksIn tracks_in(HostImage &in, const HostTracks &t, const void *const (&frame_src)[3], const size_t (&frame_bytes)[3],
+                          bool per_track, const double *xyz, const int32_t *track_flags)
+{
+    TracksIn s{};
+    s.kp = in.add_slots(t.kps, t.counts, t.n_frames, t.stride, sizeof(pgx_keypoint));
+    for (int i = 0; i < 3 && frame_src[i]; i++) s.frame[i] = in.add(frame_src[i], t.n_frames, frame_bytes[i]);
+    s.off = in.add(t.track_offsets, t.n_tracks + 1, 4);
+    s.nodes = in.add(t.nodes, t.n_nodes, 8, 1);
+    if (per_track) {
+        s.xyz = in.add(xyz, t.n_tracks, 24, 1);
+        s.flags = in.add(track_flags, t.n_tracks, 4, 1, track_flags != nullptr);
+    }
+    s.ts = in.add_words({t.n_tracks, (int32_t)t.n_nodes}, 64);
+    return s;
+}
+
+// verification, relative pose: two keypoint sets as the image pair (1, 2) of three slots of S: keypoints [3][S] (slot 0
+// unused), the list [S], and meta = the counts {0, n1, n2} with the pair list {1, 2} behind them
+struct PairIn { int kp, list, meta; };
+inline PairIn pair_in(HostImage &in, const pgx_keypoint *kp1, int n1, const pgx_keypoint *kp2, int n2, const pgx_pair *matches, int S)
+{
+    const size_t K = sizeof(pgx_keypoint);
+    const int kp = in.add(nullptr, 0, K, 3 * S);
+    in.put_at(S * K, kp1, n1 * K);
+    in.put_at(2 * S * K, kp2, n2 * K);
+    return {kp, in.add(matches, n1, sizeof(pgx_pair), S), in.add_words({0, n1, n2, 1, 2}, 16)};   // in this order
+}

@@ -5,6 +5,7 @@
 #pragma once
 
 #include "pgx_internal.h"
+#include "pgx_hoststage.h"   // WsCarver, the workspace carver of the launchers
 #include "pgx_ransac.h"
 
 #include <cmath>
@@ -19,27 +20,6 @@ struct TrackView {
     int F, stride, n_frames, max_tracks;
     long long node_cap;           // entries of nodes (and of a per-node output) an offset may reach
     int32_t *inv;                 // workspace [n_frames] frame -> slot, -1 = none (build_slot_inverse)
-};
-
-// Hands out 256-byte-aligned sections of a workspace, so that a stage describes its layout once: the launcher carves
-// the real buffer, *_ws_bytes the null one and reads total().
-struct WsCarver {
-    char *base;
-    size_t at = 0;
-    explicit WsCarver(void *ws) : base(static_cast<char *>(ws)) {}
-    static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-    size_t put(size_t bytes)   // the section's offset
-    {
-        const size_t p = at;
-        at += align256(bytes);
-        return p;
-    }
-    template <class T> T *take(size_t bytes)
-    {
-        const size_t p = put(bytes);
-        return base ? reinterpret_cast<T *>(base + p) : nullptr;
-    }
-    size_t total() const { return at; }
 };
 
 #ifdef __HIPCC__

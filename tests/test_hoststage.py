@@ -1,0 +1,42 @@
+"""CPU test of the staging images of the geometry host forms (photogrammetry_amd/csrc/pgx_hoststage.h): the input image that
+pgx_triangulate_tracks, pgx_bundle_adjust, pgx_register_frames, pgx_verify_pair and pgx_relative_pose pack and upload in one
+copy, and the output image they download from.
+
+The header is plain host C++; tests/hoststage_driver.cpp is a stand-alone program around it, built here with
+-fsanitize=address,undefined and run once per host form.  It hands the packer a buffer of exactly total() bytes and sources
+of exactly their sizes, so every run is also a sanitizer run of the packer.
+
+A limit of this test: only the input lists that the forms share (tracks_in, pair_in) are the header's own code.  Each form
+declares its outputs, and pgx_relative_pose its F and K, inside pgx_api.hip, which needs HIP; the driver repeats those
+declarations word for word, so a size edited in pgx_api.hip alone is caught by tests/test_gpu_host_forms.py (every output bit
+for bit against the device form), not here.
+
+Checked per form, for its section lists as the form declares them: every offset is 256-aligned, the sections are disjoint and
+in declaration order and the total is the sum of the aligned sizes; the packed image equals one laid out naively in the
+driver, byte for byte, with every byte that no source covers zero; an absent section gives a null device pointer and an
+absent output no download; an output with nothing to download gives none.
+
+Sizes: n_frames 1 and 3 with counts {0, 5, 2} (stride from the largest count); n_tracks 0, 1 and 7 with n_nodes 0 and 19;
+(n1, n2) in (0, 0), (0, 4), (4, 0), (5, 3); max_iters 0 and 20; every optional section once present and once absent."""
+import os
+import subprocess
+
+import pytest
+
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+
+
+@pytest.fixture(scope="module")
+def driver(tmp_path_factory):
+    exe = str(tmp_path_factory.mktemp("hoststage") / "hoststage_driver")
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined",
+                    "-fno-sanitize-recover=all", "-o", exe, os.path.join(ROOT, "tests", "hoststage_driver.cpp")],
+                   check=True, capture_output=True, text=True, timeout=300)
+    return exe
+
+
+@pytest.mark.parametrize("form", ["triangulate_tracks", "bundle_adjust", "register_frames", "verify_pair", "relative_pose"])
+def test_images_match_the_naive_layout(driver, form):
+    run = subprocess.run([driver, form], capture_output=True, text=True, timeout=60)
+    assert run.returncode == 0 and not run.stderr, run.stderr[-2000:]
+    assert run.stdout.startswith("ok ") and int(run.stdout.split()[1]) > 50
