@@ -840,49 +840,23 @@ int pgx_nms(pgx_ctx *c, const pgx_keypoint *kps, int n, int W, int H, int32_t *o
 
 namespace {
 
-// The two-set host forms (pgx_match, pgx_knn, pgx_knn_guided) run the batch kernels on two "frames" of S slots: descriptors
-// in st_a, and in st_b the block `meta` = counts[2], pairlist[1][2], F[9]; the guided form (F not null) has keypoints too, in st_d.
-struct TwoSets {
-    int32_t meta[13]; // the upload's source: the caller keeps the struct until its sync_status
-    const uint32_t *desc;
-    const pgx_keypoint *kp;
-    const int32_t *counts, *pairlist;
-    const float *F;
-};
-int stage_two_sets(pgx_ctx *c, const uint32_t *desc1, const pgx_keypoint *kp1, int n1, const uint32_t *desc2, const pgx_keypoint *kp2,
-                   int n2, int S, int words, const float *F, TwoSets &d)
+// A host form's images (pgx_hoststage.h) onto the device: inputs packed in pin_in and uploaded to st_a in one copy, outputs in st_b
+int stage_images(pgx_ctx *c, HostImage &in, HostImage &out)
 {
-    HIPCHK(c, c->st_a.ensure((size_t)2 * S * words * 4));
-    HIPCHK(c, c->st_b.ensure(64));
-    if (F) HIPCHK(c, c->st_d.ensure((size_t)2 * S * sizeof(pgx_keypoint)));
-    int32_t(&meta)[13] = d.meta;
-    std::memset(meta, 0, sizeof meta);
-    meta[0] = n1; meta[1] = n2; meta[3] = 1;
-    if (F) std::memcpy(meta + 4, F, 9 * sizeof(float));
-    if (n1 > 0) HIPCHK(c, hipMemcpyAsync(c->st_a.p, desc1, (size_t)n1 * words * 4, hipMemcpyHostToDevice, c->stream));
-    if (n1 > 0 && F) HIPCHK(c, hipMemcpyAsync(c->st_d.p, kp1, (size_t)n1 * sizeof(pgx_keypoint), hipMemcpyHostToDevice, c->stream));
-    if (n2 > 0)
-        HIPCHK(c, hipMemcpyAsync(c->st_a.as<uint32_t>() + (size_t)S * words, desc2, (size_t)n2 * words * 4, hipMemcpyHostToDevice, c->stream));
-    if (n2 > 0 && F)
-        HIPCHK(c, hipMemcpyAsync(c->st_d.as<pgx_keypoint>() + S, kp2, (size_t)n2 * sizeof(pgx_keypoint), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->st_b.p, meta, sizeof meta, hipMemcpyHostToDevice, c->stream));
-    d.desc = c->st_a.as<uint32_t>();
-    d.kp = c->st_d.as<pgx_keypoint>();
-    d.counts = c->st_b.as<int32_t>();
-    d.pairlist = d.counts + 2;
-    d.F = reinterpret_cast<const float *>(d.counts + 4);
+    HIPCHK(c, c->pin_in.ensure(in.total()));
+    HIPCHK(c, c->st_a.ensure(in.total()));
+    HIPCHK(c, c->st_b.ensure(out.total()));
+    in.pack(c->pin_in.as<char>());
+    in.base = c->st_a.as<char>();
+    out.base = c->st_b.as<char>();
+    HIPCHK(c, hipMemcpyAsync(c->st_a.p, c->pin_in.p, in.total(), hipMemcpyHostToDevice, c->stream));
     return PGX_OK;
 }
 
-// the results of pgx_knn and pgx_knn_guided (in st_c: idx [S][k], dist [S][k], col [S]) back to the host; ends the call
-int download_knn(pgx_ctx *c, const int32_t *d_idx, const int32_t *d_dist, const int32_t *d_col, int n1, int n2, int k, int32_t *idx_out,
-                 int32_t *dist_out, int32_t *col_nn_out)
+// ... and back: one copy per output section that has a destination, then the call's status
+int download_images(pgx_ctx *c, const HostImage &out)
 {
-    if (n1 > 0) {
-        HIPCHK(c, hipMemcpyAsync(idx_out, d_idx, (size_t)n1 * k * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(dist_out, d_dist, (size_t)n1 * k * 4, hipMemcpyDeviceToHost, c->stream));
-    }
-    if (d_col && n2 > 0) HIPCHK(c, hipMemcpyAsync(col_nn_out, d_col, (size_t)n2 * 4, hipMemcpyDeviceToHost, c->stream));
+    for (const HostImage::Move &m : out.moves) HIPCHK(c, hipMemcpyAsync(m.host, out.base + m.off, m.bytes, hipMemcpyDeviceToHost, c->stream));
     return sync_status(c);
 }
 
@@ -898,14 +872,14 @@ int pgx_match(pgx_ctx *c, const uint32_t *desc1, int n1, const uint32_t *desc2, 
     if (words <= 0 || words > 127) return fail(c, PGX_E_BADARG, "words must be in [1, 127]");
     const int S = n1 > n2 ? n1 : n2;
     if (S > (1 << PGX_IDX_BITS)) return fail(c, PGX_E_BADARG, "more than 2^20 keypoints");
-    TwoSets in;
-    int rc = stage_two_sets(c, desc1, nullptr, n1, desc2, nullptr, n2, S, words, nullptr, in);
+    HostImage in, ot;
+    const TwoSetsIn i = two_sets_in(in, desc1, nullptr, n1, desc2, nullptr, n2, S, words, nullptr);
+    const int o_out = ot.add(out, n1, sizeof(pgx_pair), S);
+    if (const int rs = stage_images(c, in, ot); rs != PGX_OK) return rs;
+    const int32_t *d_meta = in.dev<int32_t>(i.meta);
+    const int rc = pgx_enqueue_match(c, in.dev<uint32_t>(i.desc), d_meta, S, words, d_meta + 2, 1, S, ot.dev<pgx_pair>(o_out));
     if (rc != PGX_OK) return rc;
-    HIPCHK(c, c->st_c.ensure((size_t)S * sizeof(pgx_pair)));
-    rc = pgx_enqueue_match(c, in.desc, in.counts, S, words, in.pairlist, 1, S, c->st_c.as<pgx_pair>());
-    if (rc != PGX_OK) return rc;
-    HIPCHK(c, hipMemcpyAsync(out, c->st_c.p, (size_t)n1 * sizeof(pgx_pair), hipMemcpyDeviceToHost, c->stream));
-    return sync_status(c);
+    return download_images(c, ot);
 }
 
 int pgx_match_batch(pgx_ctx *c, const uint32_t *const *descs, const int32_t *counts, int n_frames, int words,
@@ -938,25 +912,18 @@ int pgx_match_batch(pgx_ctx *c, const uint32_t *const *descs, const int32_t *cou
     if (out_offsets) out_offsets[n_pairs] = total;
     if (n_pairs == 0 || total == 0) return PGX_OK;
     if (!out) return fail(c, PGX_E_BADARG, "null pointer");
-    // stage: [F][S][words] descriptors + counts + pair list in one pinned block, one upload
-    const size_t desc_bytes = (size_t)n_frames * S * words * 4, cnt_bytes = ((size_t)n_frames * 4 + 15) & ~(size_t)15;
-    const size_t pl_bytes = (size_t)n_pairs * 8, in_bytes = desc_bytes + cnt_bytes + pl_bytes;
+    // one upload (an unreferenced frame's count is never read on the device); the lists [n_pairs][S] are carved and come back
+    // in ONE copy to pin_out, not one per image pair, and are scattered to `out` from there
+    HostImage in, ot;
+    const BatchIn i = batch_in(in, descs, counts, used.data(), n_frames, S, words, pair_list, n_pairs);
+    const int o_out = ot.add(nullptr, 0, sizeof(pgx_pair), (size_t)n_pairs * S);
     const size_t out_bytes = (size_t)n_pairs * S * sizeof(pgx_pair);
-    HIPCHK(c, c->pin_in.ensure(in_bytes));
     HIPCHK(c, c->pin_out.ensure(out_bytes));
-    HIPCHK(c, c->st_a.ensure(in_bytes));
-    HIPCHK(c, c->st_c.ensure(out_bytes));
-    uint8_t *hin = c->pin_in.as<uint8_t>();
-    for (int f = 0; f < n_frames; f++)
-        if (counts[f] > 0 && used[(size_t)f]) memcpy(hin + (size_t)f * S * words * 4, descs[f], (size_t)counts[f] * words * 4);
-    memcpy(hin + desc_bytes, counts, (size_t)n_frames * 4); // an unreferenced frame's count is never read on the device
-    memcpy(hin + desc_bytes + cnt_bytes, pair_list, pl_bytes);
-    HIPCHK(c, hipMemcpyAsync(c->st_a.p, hin, in_bytes, hipMemcpyHostToDevice, c->stream));
-    uint8_t *din = c->st_a.as<uint8_t>();
-    int rc = pgx_enqueue_match(c, reinterpret_cast<const uint32_t *>(din), reinterpret_cast<const int32_t *>(din + desc_bytes), S, words,
-                           reinterpret_cast<const int32_t *>(din + desc_bytes + cnt_bytes), n_pairs, S, c->st_c.as<pgx_pair>());
+    if (const int rs = stage_images(c, in, ot); rs != PGX_OK) return rs;
+    int rc = pgx_enqueue_match(c, in.dev<uint32_t>(i.desc), in.dev<int32_t>(i.counts), S, words, in.dev<int32_t>(i.pairs), n_pairs, S,
+                               ot.dev<pgx_pair>(o_out));
     if (rc != PGX_OK) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->pin_out.p, c->st_c.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->pin_out.p, ot.dev<pgx_pair>(o_out), out_bytes, hipMemcpyDeviceToHost, c->stream));
     rc = sync_status(c);
     if (rc != PGX_OK && rc != PGX_E_EMPTY_SET) return rc;
     const pgx_pair *hout = c->pin_out.as<pgx_pair>();
@@ -1126,14 +1093,15 @@ int pgx_knn(pgx_ctx *c, const uint32_t *desc1, int n1, const uint32_t *desc2, in
     int rc = knn_args(c, S, words, 1, k);
     if (rc != PGX_OK) return rc;
     if (n1 == 0 && (n2 == 0 || !col_nn_out)) return PGX_OK;
-    TwoSets in;
-    rc = stage_two_sets(c, desc1, nullptr, n1, desc2, nullptr, n2, S, words, nullptr, in);
-    if (rc != PGX_OK) return rc;
-    HIPCHK(c, c->st_c.ensure((size_t)S * (2 * k + 1) * 4));
-    int32_t *d_idx = c->st_c.as<int32_t>(), *d_dist = d_idx + (size_t)S * k, *d_col = col_nn_out ? d_dist + (size_t)S * k : nullptr;
-    pgx_launch_knn(c, c->stream, in.desc, in.counts, in.pairlist, 1, S, words, S, k, d_idx, d_dist, d_col);
+    HostImage in, ot;
+    const TwoSetsIn i = two_sets_in(in, desc1, nullptr, n1, desc2, nullptr, n2, S, words, nullptr);
+    const KnnOut o = knn_out(ot, n1, n2, S, k, idx_out, dist_out, col_nn_out);
+    if ((rc = stage_images(c, in, ot)) != PGX_OK) return rc;
+    const int32_t *d_meta = in.dev<int32_t>(i.meta);
+    pgx_launch_knn(c, c->stream, in.dev<uint32_t>(i.desc), d_meta, d_meta + 2, 1, S, words, S, k, ot.dev<int32_t>(o.idx),
+                   ot.dev<int32_t>(o.dist), ot.dev<int32_t>(o.col));
     HIPCHK(c, hipGetLastError());
-    return download_knn(c, d_idx, d_dist, d_col, n1, n2, k, idx_out, dist_out, col_nn_out);
+    return download_images(c, ot);
 }
 
 // ---- epipolar-guided exact matching (k_guided.hip) ------------------------------------------------------------------
@@ -1207,14 +1175,15 @@ int pgx_knn_guided(pgx_ctx *c, const uint32_t *desc1, const pgx_keypoint *kp1, i
     const int rc = guided_args(c, S, words, 1, k, band);
     if (rc != PGX_OK) return rc;
     if (n1 == 0 && (n2 == 0 || !col_nn_out)) return PGX_OK;
-    TwoSets in;
-    int rq = stage_two_sets(c, desc1, kp1, n1, desc2, kp2, n2, S, words, F, in);
+    HostImage in, ot;
+    const TwoSetsIn i = two_sets_in(in, desc1, kp1, n1, desc2, kp2, n2, S, words, F);
+    const KnnOut o = knn_out(ot, n1, n2, S, k, idx_out, dist_out, col_nn_out);
+    if (const int rs = stage_images(c, in, ot); rs != PGX_OK) return rs;
+    const int32_t *d_meta = in.dev<int32_t>(i.meta);
+    const int rq = enqueue_guided(c, in.dev<uint32_t>(i.desc), in.dev<pgx_keypoint>(i.kp), d_meta, S, words, d_meta + 2, 1, S,
+                                  in.dev<float>(i.F), band, k, ot.dev<int32_t>(o.idx), ot.dev<int32_t>(o.dist), ot.dev<int32_t>(o.col));
     if (rq != PGX_OK) return rq;
-    HIPCHK(c, c->st_c.ensure((size_t)S * (2 * k + 1) * 4));
-    int32_t *d_idx = c->st_c.as<int32_t>(), *d_dist = d_idx + (size_t)S * k, *d_col = col_nn_out ? d_dist + (size_t)S * k : nullptr;
-    rq = enqueue_guided(c, in.desc, in.kp, in.counts, S, words, in.pairlist, 1, S, in.F, band, k, d_idx, d_dist, d_col);
-    if (rq != PGX_OK) return rq;
-    return download_knn(c, d_idx, d_dist, d_col, n1, n2, k, idx_out, dist_out, col_nn_out);
+    return download_images(c, ot);
 }
 
 // ---- RANSAC fundamental matrix and pose ----------------------------------------------------------
@@ -1351,27 +1320,6 @@ int check_host_tracks(pgx_ctx *c, const pgx_keypoint *kps, const int32_t *counts
     }
     *out = {kps, counts, track_offsets, nodes, n_frames, n_tracks, stride, n_nodes};
     return PGX_OK;
-}
-
-// A host form's images (pgx_hoststage.h) onto the device: the inputs packed in pin_in and uploaded to st_a in one copy,
-// the outputs in st_b
-int stage_images(pgx_ctx *c, HostImage &in, HostImage &out)
-{
-    HIPCHK(c, c->pin_in.ensure(in.total()));
-    HIPCHK(c, c->st_a.ensure(in.total()));
-    HIPCHK(c, c->st_b.ensure(out.total()));
-    in.pack(c->pin_in.as<char>());
-    in.base = c->st_a.as<char>();
-    out.base = c->st_b.as<char>();
-    HIPCHK(c, hipMemcpyAsync(c->st_a.p, c->pin_in.p, in.total(), hipMemcpyHostToDevice, c->stream));
-    return PGX_OK;
-}
-
-// ... and back: one copy per output section that has a destination, then the call's status
-int download_images(pgx_ctx *c, const HostImage &out)
-{
-    for (const HostImage::Move &m : out.moves) HIPCHK(c, hipMemcpyAsync(m.host, out.base + m.off, m.bytes, hipMemcpyDeviceToHost, c->stream));
-    return sync_status(c);
 }
 
 // the range checks that the stages share: PGX_OK, or PGX_E_BADARG with the one text

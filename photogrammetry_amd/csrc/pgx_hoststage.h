@@ -1,5 +1,7 @@
 // pgx_hoststage.h -- buffers laid out in 256-byte-aligned sections: the workspace carver of the launchers and, on it, the
-// image that a host form uploads or downloads in (HostImage), with the input lists that the geometry host forms share.
+// image that a host form uploads or downloads in (HostImage), with the section lists that the nine host forms on it share:
+// tracks_in (triangulation, bundle adjustment, registration), pair_in (verification, relative pose), two_sets_in and knn_out
+// (pgx_match, pgx_knn, pgx_knn_guided), batch_in (pgx_match_batch).
 // Host code without HIP: tests/hoststage_driver.cpp builds it with g++ under sanitizers, and pgx_api.hip puts the copies
 // around it (stage_images, download_images).  Internal to libpgx.so; DESIGN.md section 14g.
 #pragma once
@@ -42,6 +44,7 @@ struct HostImage {
     std::vector<Move> moves;
     WsCarver w{nullptr};
     char *base = nullptr;                      // where the image lies on the device
+    bool ascending = true;                     // no source so far begins before the end of the one declared before it
     std::vector<std::vector<int32_t>> words;   // add_words' blocks: `moves` points into them, so an image is not copied
     HostImage() = default; HostImage(const HostImage &) = delete; HostImage &operator=(const HostImage &) = delete;
 
@@ -53,7 +56,9 @@ struct HostImage {
     }
     void put_at(size_t at, const void *host, size_t bytes)   // one more source inside the section declared last, `at` bytes in
     {
-        if (host && bytes) moves.push_back({secs.back().off + at, const_cast<void *>(host), bytes});
+        if (!host || !bytes) return;
+        ascending &= moves.empty() || moves.back().off + moves.back().bytes <= secs.back().off + at;
+        moves.push_back({secs.back().off + at, const_cast<void *>(host), bytes});
     }
     int add_words(std::initializer_list<int32_t> v, size_t at_least)   // a few words held by value
     {
@@ -69,10 +74,15 @@ struct HostImage {
         return s;
     }
     size_t total() const { return w.total(); }
-    void pack(char *dst) const   // all total() bytes: zero wherever no source lies
+    void pack(char *dst) const   // all total() bytes: zero wherever no source lies (sources in ascending order: only there)
     {
-        std::memset(dst, 0, total());
-        for (const Move &m : moves) std::memcpy(dst + m.off, m.host, m.bytes);
+        size_t at = 0;
+        if (!ascending) std::memset(dst, 0, at = total());
+        for (const Move &m : moves) {
+            if (ascending) std::memset(dst + at, 0, m.off - at), at = m.off + m.bytes;
+            std::memcpy(dst + m.off, m.host, m.bytes);
+        }
+        std::memset(dst + at, 0, total() - at);
     }
     template <class T> T *dev(int s) const { return secs[s].present ? reinterpret_cast<T *>(base + secs[s].off) : nullptr; }
 };
@@ -112,4 +122,46 @@ inline PairIn pair_in(HostImage &in, const pgx_keypoint *kp1, int n1, const pgx_
     in.put_at(S * K, kp1, n1 * K);
     in.put_at(2 * S * K, kp2, n2 * K);
     return {kp, in.add(matches, n1, sizeof(pgx_pair), S), in.add_words({0, n1, n2, 1, 2}, 16)};   // in this order
+}
+
+// the matchers.  No loader of k_match.hip, k_match_mfma.inc, k_knn.hip or k_guided.hip reads a descriptor or keypoint row
+// at or past a frame's count, so neither list below needs slack behind its last slot.
+// pgx_match, pgx_knn, pgx_knn_guided: two sets as the image pair (0, 1) of two slots of S: descriptors [2][S][words], the
+// counts {n1, n2} with the pair list {0, 1} behind them, and for the guided form (F given) keypoints [2][S] and F [9]; the
+// other two forms carry empty absent sections in their place
+struct TwoSetsIn { int desc, kp, meta, F; };
+inline TwoSetsIn two_sets_in(HostImage &in, const uint32_t *desc1, const pgx_keypoint *kp1, int n1, const uint32_t *desc2,
+                             const pgx_keypoint *kp2, int n2, int S, int words, const float *F)
+{
+    const size_t D = (size_t)words * 4, K = sizeof(pgx_keypoint);
+    TwoSetsIn s{};
+    s.desc = in.add(nullptr, 0, D, 2 * (size_t)S);
+    in.put_at(0, desc1, n1 * D);
+    in.put_at(S * D, desc2, n2 * D);
+    s.kp = in.add(nullptr, 0, K, F ? 2 * (size_t)S : 0, F != nullptr);
+    if (F) in.put_at(0, kp1, n1 * K), in.put_at(S * K, kp2, n2 * K);
+    s.meta = in.add_words({n1, n2, 0, 1}, 16);
+    s.F = in.add(F, F ? 9 : 0, sizeof(float), 0, F != nullptr);
+    return s;
+}
+
+// ... and the outputs of pgx_knn and pgx_knn_guided: idx [S][k], dist [S][k], and col_nn [S], absent with a null col_nn_out
+struct KnnOut { int idx, dist, col; };
+inline KnnOut knn_out(HostImage &out, int n1, int n2, int S, int k, int32_t *idx_out, int32_t *dist_out, int32_t *col_nn_out)
+{
+    const size_t rows = (size_t)n1 * k, slots = (size_t)S * k;
+    return {out.add(idx_out, rows, 4, slots), out.add(dist_out, rows, 4, slots), out.add(col_nn_out, n2, 4, S, col_nn_out != nullptr)};
+}
+
+// pgx_match_batch: descriptors [n_frames][S][words], of which only the frames that some pair references (used[f]) are
+// read from the caller, then counts [n_frames] and pair_list [n_pairs][2]
+struct BatchIn { int desc, counts, pairs; };
+inline BatchIn batch_in(HostImage &in, const uint32_t *const *descs, const int32_t *counts, const char *used, int n_frames, int S,
+                        int words, const int32_t *pair_list, int n_pairs)
+{
+    const size_t D = (size_t)words * 4;
+    const int desc = in.add(nullptr, 0, D, (size_t)n_frames * S);
+    for (int f = 0; f < n_frames; f++)
+        if (used[f]) in.put_at((size_t)f * S * D, descs[f], counts[f] * D);
+    return {desc, in.add(counts, n_frames, 4), in.add(pair_list, n_pairs, 8)};   // in this order
 }

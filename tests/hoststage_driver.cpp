@@ -1,7 +1,8 @@
 // Stand-alone driver of the host forms' staging images (photogrammetry_amd/csrc/pgx_hoststage.h) for tests/test_hoststage.py:
 // argv[1] names a host form, whose section lists are checked at every size of the test's docstring against images laid out
-// naively here.  The input lists are the header's own (tracks_in, pair_in); the output lists, and F and K of
-// pgx_relative_pose, are declared here word for word as the form in pgx_api.hip declares them.  Host code only; the test
+// naively here.  The input lists are the header's own (tracks_in, pair_in, two_sets_in, batch_in), and so is knn_out; the
+// other output lists, F and K of pgx_relative_pose, and S and `used` of pgx_match_batch are declared or computed here word
+// for word as the form in pgx_api.hip does.  Host code only; the test
 // builds it with -fsanitize=address,undefined, and every buffer has its exact size, so a read or write past an end is a
 // sanitizer report.  Exit status 0 and "ok <checks>" on stdout, or 1 and the first failure on stderr.
 #include <cstdio>
@@ -217,16 +218,113 @@ void pair_form(int kind)
         }
 }
 
+Bytes words_of(std::initializer_list<int32_t> v)
+{
+    const char *b = reinterpret_cast<const char *>(v.begin());
+    return Bytes(b, b + 4 * v.size());
+}
+
+// kind 5: pgx_match, 6: pgx_knn, 7: pgx_knn_guided (the only one with keypoints and F)
+void two_sets_form(int kind)
+{
+    const int N[3][2] = {{0, 4}, {4, 0}, {5, 3}};
+    const bool guided = kind == 7;
+    for (const int(&n)[2] : N)
+        for (int words : {1, 8})
+            for (int k : {1, 2})
+                for (int col = 0; col < 2; col++) {
+                    if (kind == 5 && (k == 2 || col)) continue;   // pgx_match has neither
+                    const int n1 = n[0], n2 = n[1], S = n1 > n2 ? n1 : n2;
+                    const size_t D = (size_t)words * 4;
+                    Src<uint32_t> d1((size_t)n1 * words, 1), d2((size_t)n2 * words, 2);
+                    Src<pgx_keypoint> kp1(guided ? n1 : 0, 3), kp2(guided ? n2 : 0, 4);
+                    Src<float> F(guided ? 9 : 0, 5);
+                    Bytes desc, kp;
+                    place(desc, 0, d1.bytes());
+                    place(desc, S * D, d2.bytes());
+                    place(kp, 0, kp1.bytes());
+                    if (guided) place(kp, (size_t)S * 16, kp2.bytes());
+                    HostImage in;
+                    const TwoSetsIn i = two_sets_in(in, d1.p(), kp1.p(), n1, d2.p(), kp2.p(), n2, S, words, F.p());
+                    check_in(in, {i.desc, i.kp, i.meta, i.F},
+                             {in_sec(2 * S * D, desc), in_sec(guided ? (size_t)2 * S * 16 : 0, kp, guided), in_sec(64, words_of({n1, n2, 0, 1})),
+                              in_sec(guided ? 36 : 0, F.bytes(), guided)});
+                    int32_t w[3];
+                    pgx_pair pr[1];
+                    HostImage out;
+                    if (kind == 5) {
+                        check_out(out, {out.add(pr, n1, sizeof(pgx_pair), S)}, {out_sec((size_t)S * 12, pr, (size_t)n1 * 12)});
+                    } else {
+                        int32_t *const cn = col ? w + 2 : nullptr;
+                        const KnnOut o = knn_out(out, n1, n2, S, k, w, w + 1, cn);
+                        check_out(out, {o.idx, o.dist, o.col},
+                                  {out_sec((size_t)S * k * 4, w, (size_t)n1 * k * 4), out_sec((size_t)S * k * 4, w + 1, (size_t)n1 * k * 4),
+                                   out_sec((size_t)S * 4, cn, (size_t)n2 * 4, col)});
+                    }
+                }
+}
+
+// kind 8: pgx_match_batch; S and `used` as the form computes them.  The last case has a fourth frame of 9 rows that no pair
+// names: its source is null, so that reading it is a crash, and it must not widen S.
+void batch_form()
+{
+    const int32_t counts[4] = {0, 5, 2, 9};
+    const std::vector<std::vector<int32_t>> LISTS = {{}, {1, 2}, {1, 2, 2, 1}};
+    for (int n_frames : {3, 4})
+        for (const std::vector<int32_t> &pl : LISTS)
+            for (int words : {1, 8}) {
+                if (n_frames == 4 && pl.size() != 4) continue;
+                const int n_pairs = (int)pl.size() / 2;
+                const size_t D = (size_t)words * 4;
+                int S = 1;
+                char used[4] = {0, 0, 0, 0};
+                for (int32_t f : pl) used[f] = 1, S = counts[f] > S ? counts[f] : S;
+                CHECK(S == (n_pairs ? 5 : 1));
+                std::vector<Src<uint32_t>> src;
+                const uint32_t *descs[4];
+                Bytes desc;
+                for (int f = 0; f < n_frames; f++) {
+                    src.emplace_back(f < 3 ? (size_t)counts[f] * words : 0, 10 + f);
+                    if (used[f]) place(desc, (size_t)f * S * D, src[f].bytes());
+                }
+                for (int f = 0; f < n_frames; f++) descs[f] = src[f].p();
+                const Bytes counts_b(reinterpret_cast<const char *>(counts), reinterpret_cast<const char *>(counts) + 4 * n_frames);
+                const Bytes pl_b(reinterpret_cast<const char *>(pl.data()), reinterpret_cast<const char *>(pl.data()) + 4 * pl.size());
+                HostImage in;
+                const BatchIn i = batch_in(in, descs, counts, used, n_frames, S, words, pl.empty() ? nullptr : pl.data(), n_pairs);
+                check_in(in, {i.desc, i.counts, i.pairs}, {in_sec((size_t)n_frames * S * D, desc), in_sec(4 * n_frames, counts_b), in_sec(8 * n_pairs, pl_b)});
+                HostImage out;   // carved, not downloaded: the form copies all lists to its pinned buffer in one piece
+                check_out(out, {out.add(nullptr, 0, sizeof(pgx_pair), (size_t)n_pairs * S)}, {out_sec((size_t)n_pairs * S * 12, nullptr, 0)});
+            }
+}
+
+// sources declared out of order (no form does that): pack() still zeroes every byte that none of them covers
+void out_of_order()
+{
+    Src<int32_t> a(3, 1), b(2, 2);
+    HostImage in;
+    const int s = in.add(nullptr, 0, 4, 100);
+    in.put_at(200, a.p(), 12);
+    in.put_at(40, b.p(), 8);
+    Bytes naive;
+    place(naive, 40, b.bytes());
+    place(naive, 200, a.bytes());
+    check_in(in, {s}, {in_sec(400, naive)});
+    CHECK(!in.ascending);
+}
+
 } // namespace
 
 int main(int argc, char **argv)
 {
-    static const char *const FORMS[5] = {"triangulate_tracks", "bundle_adjust", "register_frames", "verify_pair", "relative_pose"};
+    static const char *const FORMS[9] = {"triangulate_tracks", "bundle_adjust", "register_frames", "verify_pair", "relative_pose",
+                                         "match", "knn", "knn_guided", "match_batch"};
     int kind = -1;
-    for (int k = 0; k < 5; k++)
+    for (int k = 0; k < 9; k++)
         if (argc == 2 && argv[1] == std::string(FORMS[k])) kind = k;
     if (kind < 0) return 2;
-    kind < 3 ? tracks_form(kind) : pair_form(kind);
+    out_of_order();
+    kind < 3 ? tracks_form(kind) : kind < 5 ? pair_form(kind) : kind < 8 ? two_sets_form(kind) : batch_form();
     std::printf("ok %d\n", n_checks);
     return 0;
 }

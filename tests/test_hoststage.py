@@ -1,15 +1,15 @@
-"""CPU test of the staging images of the geometry host forms (photogrammetry_amd/csrc/pgx_hoststage.h): the input image that
-pgx_triangulate_tracks, pgx_bundle_adjust, pgx_register_frames, pgx_verify_pair and pgx_relative_pose pack and upload in one
-copy, and the output image they download from.
+"""CPU test of the staging images of the nine host forms on photogrammetry_amd/csrc/pgx_hoststage.h: the input image that
+pgx_triangulate_tracks, pgx_bundle_adjust, pgx_register_frames, pgx_verify_pair, pgx_relative_pose, pgx_match, pgx_knn,
+pgx_knn_guided and pgx_match_batch pack and upload in one copy, and the output image they download from.
 
 The header is plain host C++; tests/hoststage_driver.cpp is a stand-alone program around it, built here with
 -fsanitize=address,undefined and run once per host form.  It hands the packer a buffer of exactly total() bytes and sources
 of exactly their sizes, so every run is also a sanitizer run of the packer.
 
-A limit of this test: only the input lists that the forms share (tracks_in, pair_in) are the header's own code.  Each form
-declares its outputs, and pgx_relative_pose its F and K, inside pgx_api.hip, which needs HIP; the driver repeats those
-declarations word for word, so a size edited in pgx_api.hip alone is caught by tests/test_gpu_host_forms.py (every output bit
-for bit against the device form), not here.
+A limit of this test: only the lists that the forms share (tracks_in, pair_in, two_sets_in, batch_in, knn_out) are the
+header's own code.  Every other form declares its outputs, pgx_relative_pose its F and K, and pgx_match_batch computes its S
+and its referenced frames, inside pgx_api.hip, which needs HIP; the driver repeats those word for word, so a size edited in
+pgx_api.hip alone is caught by tests/test_gpu_host_forms.py (every output bit for bit against the device form), not here.
 
 Checked per form, for its section lists as the form declares them: every offset is 256-aligned, the sections are disjoint and
 in declaration order and the total is the sum of the aligned sizes; the packed image equals one laid out naively in the
@@ -17,7 +17,11 @@ driver, byte for byte, with every byte that no source covers zero; an absent sec
 absent output no download; an output with nothing to download gives none.
 
 Sizes: n_frames 1 and 3 with counts {0, 5, 2} (stride from the largest count); n_tracks 0, 1 and 7 with n_nodes 0 and 19;
-(n1, n2) in (0, 0), (0, 4), (4, 0), (5, 3); max_iters 0 and 20; every optional section once present and once absent."""
+(n1, n2) in (0, 0), (0, 4), (4, 0), (5, 3); max_iters 0 and 20; every optional section once present and once absent.
+The matchers: (n1, n2) in (0, 4), (4, 0), (5, 3) with words 1 and 8, k 1 and 2, col_nn present and absent, the keypoints and
+F present (pgx_knn_guided) and absent (pgx_match, pgx_knn); the batch with 3 frames of {0, 5, 2} rows and the pair lists {},
+{(1, 2)}, {(1, 2), (2, 1)}, and with a fourth frame of 9 rows that no pair names, whose source is null and which must
+leave S at 5."""
 import os
 import subprocess
 
@@ -35,7 +39,8 @@ def driver(tmp_path_factory):
     return exe
 
 
-@pytest.mark.parametrize("form", ["triangulate_tracks", "bundle_adjust", "register_frames", "verify_pair", "relative_pose"])
+@pytest.mark.parametrize("form", ["triangulate_tracks", "bundle_adjust", "register_frames", "verify_pair", "relative_pose",
+                                  "match", "knn", "knn_guided", "match_batch"])
 def test_images_match_the_naive_layout(driver, form):
     run = subprocess.run([driver, form], capture_output=True, text=True, timeout=60)
     assert run.returncode == 0 and not run.stderr, run.stderr[-2000:]
