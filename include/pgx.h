@@ -675,6 +675,90 @@ int pgx_register_frames(pgx_ctx *ctx, const pgx_keypoint *kps, const int32_t *co
                         int refine_iters, uint64_t seed, double *Rt_out, double *P_out, int32_t *frame_stats, double *frame_err,
                         int32_t *node_inlier, int32_t *report);
 
+/* ---- track consensus: drop outlier observations from tracks ----------------------------- */
+/* A track with one wrong observation is otherwise lost whole: the triangulation can only flag it (PGX_TRI_REPROJ), and bundle
+ * adjustment and registration skip flagged tracks.  This stage sits between either graph call and the triangulation (tracks
+ * -> consensus -> triangulate -> BA -> register -> triangulate -> consensus -> ...), needs cameras but no points, and
+ * writes a graph with fewer nodes: per track a small deterministic RANSAC over pairs of views, then an ordered compaction.
+ * Not in the reference.
+ * Inputs: d_kp, F, stride, d_frame_ids, n_frames, d_P, d_offsets, d_nodes, d_track_summary and max_tracks as for
+ * pgx_triangulate_tracks_dev (n_tracks = d_track_summary[0], read on the device).
+ * Values.  Every value is a double, every operation one IEEE double operation in the order written; a sum of three terms is
+ * ((a + b) + c), a dot product ((x0 y0 + x1 y1) + x2 y2); nothing is contracted into a fused multiply-add.
+ * Frames.  A frame is KNOWN by the triangulation's test: all 12 entries finite and det M != 0, det M = (m00 k00 + m01 k01) +
+ * m02 k02 over the cofactors k of M's first row.  Per known frame Minv = adj(M) / det (every entry divided), C = -(Minv p4),
+ * each component -((Minv[r][0] p4[0] + Minv[r][1] p4[1]) + Minv[r][2] p4[2]), and sgn = +1 for det M > 0, else -1.
+ * Observations.  The known observations of a track are its nodes in known frames, in d_nodes order, at positions
+ * 0 .. n_k - 1.  The ray of observation i = (u, v) is d_i = sgn * ((Minv[:,0] u + Minv[:,1] v) + Minv[:,2]).  Nodes in unknown
+ * frames are never judged and always carried over (registration needs them later).
+ * Hypotheses.  n_p = n_k (n_k - 1) / 2.  If n_p <= max_hyp, hypothesis h is the h-th pair (i, j), i < j, in lexicographic
+ * order (exhaustive).  Otherwise, for h < max_hyp: state = seed ^ ((uint64)(uint32)t << 32) ^ (uint64)(uint32)h *
+ * 0xD1B54A32D192ED03 (t the track's index in the input), draw splitmix64(state) % n_k until there are 2 distinct positions
+ * (registration's generator); i is the smaller, j the larger.  With w0 = C_i - C_j, a = d_i.d_i, b = d_i.d_j, c = d_j.d_j,
+ * dd = d_i.w0, e = d_j.w0, den = a c - b b, a hypothesis is VALID unless it is rejected, in this order:
+ *   1 b > 0 and b b >= cos2 (a c), cos2 = the square of cos(min_parallax_deg pi / 180), computed once on the host;
+ *   2 not den > 0;
+ *   3 s = (b e - c dd) / den, tt = (a e - b dd) / den: not (s > 0 and tt > 0).
+ * Its point relative to C_i is X' = 0.5 (s d_i + (tt d_j - w0)): the midpoint of the two rays' closest points.
+ * Score.  Known observation m = (u, v) is an inlier of a hypothesis with y = X' + (C_i - C_m), h = M_m y (rows in order),
+ * w = h2, a' = h0 - u w, b' = h1 - v w, e' = inlier_px w: inlier iff sgn_m w > 0 and a' a' + b' b' <= e' e'.  No division and
+ * no p4: a translated scene decides the same way.  A camera with det M < 0 is read as the negative of a proper camera, as the
+ * triangulation's depth does: -P decides exactly as P, and a mirrored K (fx < 0) has its points behind it.
+ * Winner: the valid hypothesis with the most inliers, ties to the smallest h (an integer key: the grid, the lane mapping and
+ * the summation order cannot matter).
+ * Per track (PGX_CNS_* bits in d_track_stats):
+ *   FEWVIEWS     n_k < 2: the track passes through unchanged
+ *   LOWPARALLAX  no valid hypothesis: passes through unchanged (a track that cannot be judged yet is not a wrong track)
+ *   NOCONSENSUS  the winner has fewer than min_inliers inliers: the whole track is removed
+ *   otherwise    every known observation that is not an inlier of the winner is removed.
+ *   SHORT        (with any of the above but NOCONSENSUS) fewer than min_len nodes are left, counting the nodes in unknown
+ *                frames: the track is removed.  min_len < 1 counts as 1.
+ * Order.  Surviving tracks keep their relative order, surviving nodes theirs.  Once a track's first node is removed the
+ * output is NO LONGER SORTED by first node (pgx_tracks_dev's order); the triangulation, bundle adjustment and registration
+ * walk tracks by index and nodes by position and do not rely on it.
+ * Outputs (none may alias an input: d_offsets_out == d_offsets, d_nodes_out == d_nodes or d_summary_out == d_track_summary
+ * is PGX_E_BADARG), for t < min(n_tracks, max_tracks):
+ *   d_offsets_out [max_tracks + 1], d_nodes_out [n_frames * stride][2], d_summary_out [8]  the layout of pgx_tracks_dev, so the
+ *           triangulation, BA and registration take them unchanged: [0] tracks, [1] nodes, [5] the longest track; [2], [3],
+ *           [4], [6] copied from d_track_summary; [7] = 0
+ *   d_track_map [max_tracks]     old index -> new index, or -1
+ *   d_xyz_out [max_tracks][3], d_flags_out [max_tracks]  by the NEW index: the winner's point in world coordinates, each
+ *           component X' + C_i, and flag 0; NaN and PGX_TRI_FEWVIEWS for a track that passed through.  Registration or BA
+ *           can follow directly without a triangulation in between
+ *   d_track_stats [max_tracks][4] by the OLD index: known observations, the winner's inliers, the winning h or -1, PGX_CNS_*
+ *   d_track_of [n_frames][stride] or NULL, in place, for the nodes of the processed tracks: a node of a removed track
+ *           becomes -1, a removed node of a surviving track -3, any other node its track's new index
+ *   d_report [8]  tracks in, tracks out, nodes in, nodes out, outlier observations removed (of the tracks that reached a
+ *           consensus), NOCONSENSUS tracks, SHORT tracks, tracks that passed through undecided (FEWVIEWS or LOWPARALLAX)
+ * Errors through pgx_check_status: n_tracks > max_tracks (PGX_E_CAPACITY; the first max_tracks tracks are processed); a node
+ * outside [0, n_frames) x [0, stride) or in a frame no slot names (PGX_E_BADARG; the node is dropped from the output),
+ * malformed offsets (the track counts as empty) or two slots naming one frame, as in the triangulation.  Returned at once
+ * (PGX_E_BADARG): inlier_px not positive or not finite, min_parallax_deg outside [0, 90), min_inliers < 2, max_hyp outside
+ * [1, 4096], null required pointers, aliased outputs, and the size checks of pgx_triangulate_tracks_dev.
+ * Results depend on the inputs only: the same bits for any max_tracks >= n_tracks, any slot layout, from run to run, and
+ * from the host form below.  Asynchronous on the context's stream. */
+#define PGX_CNS_FEWVIEWS    1
+#define PGX_CNS_LOWPARALLAX 2
+#define PGX_CNS_NOCONSENSUS 4
+#define PGX_CNS_SHORT       8
+int pgx_track_consensus_dev(pgx_ctx *ctx, const pgx_keypoint *d_kp, int F, int stride, const int32_t *d_frame_ids, int n_frames,
+                            const double *d_P, const int32_t *d_offsets, const int32_t *d_nodes, const int32_t *d_track_summary,
+                            int max_tracks, double inlier_px, double min_parallax_deg, int min_inliers, int min_len, int max_hyp,
+                            uint64_t seed, int32_t *d_offsets_out, int32_t *d_nodes_out, int32_t *d_summary_out,
+                            int32_t *d_track_map, double *d_xyz_out, int32_t *d_flags_out, int32_t *d_track_stats,
+                            int32_t *d_track_of, int32_t *d_report);
+/* Host form (what a host calls after pgx_tracks_get): the same kernels on host arrays (the conventions of
+ * pgx_triangulate_tracks: kps concatenated by frame, tracks as pgx_tracks_get writes them; a node outside [0, n_frames) x
+ * [0, counts[frame]) or offsets that are not non-decreasing from 0: PGX_E_BADARG before any GPU work).  offsets_out
+ * [n_tracks + 1], nodes_out [n_nodes][2], summary_out [8] (slots 2, 3, 4 and 6 are 0) and report [8] are required; track_map
+ * [n_tracks], xyz_out [n_tracks][3], flags_out [n_tracks] and track_stats [n_tracks][4] may be NULL.  Returns when the
+ * outputs are in the caller's buffers. */
+int pgx_track_consensus(pgx_ctx *ctx, const pgx_keypoint *kps, const int32_t *counts, int n_frames, const double *P,
+                        const int32_t *track_offsets, const int32_t *nodes, int n_tracks, double inlier_px, double min_parallax_deg,
+                        int min_inliers, int min_len, int max_hyp, uint64_t seed, int32_t *offsets_out, int32_t *nodes_out,
+                        int32_t *summary_out, int32_t *track_map, double *xyz_out, int32_t *flags_out, int32_t *track_stats,
+                        int32_t *report);
+
 /* ---- two-view geometric verification of match lists by epipolar RANSAC ----------------- */
 /* The stage between a matcher and the track graph: per image pair a robust fundamental matrix, the match list with
  * everything but its inliers rejected (ready for pgx_tracks_dev), and F in the guided matcher's convention (d_F32 is

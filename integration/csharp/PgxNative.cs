@@ -24,6 +24,7 @@ internal static unsafe class PgxNative
     public const int CommIdBytes = 128;                                                   // PGX_COMM_ID_BYTES
     public const int TriFewViews = 1, TriDegenerate = 2, TriBehind = 4, TriParallax = 8, TriReproj = 16;   // PGX_TRI_* (0 = valid)
     public const int RegBadK = 1, RegFewPoints = 2, RegNoSolution = 4, RegFewInliers = 8;   // PGX_REG_* (0 = registered)
+    public const int CnsFewViews = 1, CnsLowParallax = 2, CnsNoConsensus = 4, CnsShort = 8;   // PGX_CNS_* (0 = a consensus, kept)
     public const int VerFewMatches = 1, VerNoModel = 2, VerFewInliers = 4;                 // PGX_VER_* (0 = accepted)
     public const int InitSkipped = 1, InitBadInput = 2, InitDegenerate = 4, InitFewFront = 8, InitFewPoints = 16;   // PGX_INIT_* (0 = eligible)
 
@@ -170,6 +171,23 @@ internal static unsafe class PgxNative
                                                                   double* xyz, int* trackFlags, int nSamples, double inlierPx,
                                                                   int minInliers, int refineIters, ulong seed, double* rtOut,
                                                                   double* pOut, int* frameStats, double* frameErr, int* nodeInlier,
+                                                                  int* report);
+    // track consensus, between either graph call and the triangulation: per track a two-view RANSAC over its observations
+    // (p [nFrames][12] float64) and the compacted graph without the observations its winner rejects (offsetsOut, nodesOut,
+    // summaryOut in the graph's layout; they must not be the inputs), trackMap old -> new index, xyzOut and flagsOut by the new
+    // index, trackStats [.][4] by the old index, report [8]; dTrackOf [nFrames][stride] or null is rewritten in place
+    [DllImport(Lib)] public static extern int pgx_track_consensus_dev(IntPtr ctx, void* dKp, int f, int stride, void* dFrameIds, int nFrames,
+                                                                      void* dP, void* dOffsets, void* dNodes, void* dTrackSummary,
+                                                                      int maxTracks, double inlierPx, double minParallaxDeg,
+                                                                      int minInliers, int minLen, int maxHyp, ulong seed,
+                                                                      void* dOffsetsOut, void* dNodesOut, void* dSummaryOut,
+                                                                      void* dTrackMap, void* dXyzOut, void* dFlagsOut,
+                                                                      void* dTrackStats, void* dTrackOf, void* dReport);
+    [DllImport(Lib)] public static extern int pgx_track_consensus(IntPtr ctx, PgxKeypoint* kps, int* counts, int nFrames, double* p,
+                                                                  int* trackOffsets, int* nodes, int nTracks, double inlierPx,
+                                                                  double minParallaxDeg, int minInliers, int minLen, int maxHyp,
+                                                                  ulong seed, int* offsetsOut, int* nodesOut, int* summaryOut,
+                                                                  int* trackMap, double* xyzOut, int* flagsOut, int* trackStats,
                                                                   int* report);
 
     // two-view verification of match lists by epipolar RANSAC, between a matcher and pgx_tracks_dev: dOut [m][stride] (may be

@@ -89,7 +89,9 @@ SIGNATURES = {
     "pgx_bundle_adjust": (I, [P, P, P, I, P, P, P, P, P, I, P, P, I, D, D, P, P, P, P, P, P]),
     "pgx_register_frames_dev": (I, [P, P, I, I, P, I, P, P, P, P, P, P, I, P, P, I, D, I, I, U64, P, P, P, P, P, P]),
     "pgx_register_frames": (I, [P, P, P, I, P, P, P, P, P, I, P, P, I, D, I, I, U64, P, P, P, P, P, P]),
-    "pgx_verify_pairs_dev": (I, [P, P, P, P, P, I, I, I, I, D, I, I, U64, P, P, P, P, P, P, P, P]),
+    "pgx_track_consensus_dev": (I, [P, P, I, I, P, I, P, P, P, P, I, D, D, I, I, I, U64, P, P, P, P, P, P, P, P, P]),
+    "pgx_track_consensus": (I, [P, P, P, I, P, P, P, I, D, D, I, I, I, U64, P, P, P, P, P, P, P, P]),
+    "pgx_verify_pairs_dev":(I, [P, P, P, P, P, I, I, I, I, D, I, I, U64, P, P, P, P, P, P, P, P]),
     "pgx_verify_pair": (I, [P, P, I, P, I, P, I, I, D, I, I, U64, P, P, P, P]),
     "pgx_init_pair_dev": (I, [P, P, P, P, P, I, I, I, P, I, I, P, P, D, D, I, P, P, P, P, P, P, P, P, P]),
     "pgx_relative_pose": (I, [P, P, I, P, I, P, I, P, P, P, D, D, I, P, P, P, P]),

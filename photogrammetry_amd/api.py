@@ -541,6 +541,44 @@ class Engine:
             _ptr(P_out), _ptr(stats), _ptr(ferr), _ptr(ni), _ptr(report)))
         return dict(Rt=Rt_out, P=P_out, frame_stats=stats, frame_err=ferr, node_inlier=ni[:n_nodes], report=report)
 
+    # -- track consensus: outlier observations dropped from tracks (pgx_track_consensus*) ------------------
+    def track_consensus_dev(self, d_kp, F, stride, n_frames, d_P, d_offsets, d_nodes, d_track_summary, max_tracks, d_offsets_out,
+                            d_nodes_out, d_summary_out, d_track_map, d_xyz_out, d_flags_out, d_track_stats, d_report, inlier_px=4.0,
+                            min_parallax_deg=1.0, min_inliers=2, min_len=2, max_hyp=256, seed=0, d_track_of=None, d_frame_ids=None):
+        """A deterministic two-view RANSAC per track of the graph, where it sits in HBM, and the compacted graph without the
+        observations its winner rejects (pgx.h: track consensus).  It sits between tracks_dev and triangulate_tracks_dev.
+        d_P [n_frames][12] float64; d_offsets_out [max_tracks + 1], d_nodes_out [n_frames * stride][2], d_summary_out [8] int32 in
+        tracks_dev's layout (they must not be the inputs); d_track_map [max_tracks] int32; d_xyz_out [max_tracks][3] float64
+        and d_flags_out [max_tracks] int32 by the new index; d_track_stats [max_tracks][4] int32 by the old index; d_report [8]
+        int32; d_track_of [n_frames][stride] int32 or None, rewritten in place.  n_tracks is read on the device: no sync."""
+        self._chk(self._L.pgx_track_consensus_dev(
+            self._h, _dptr(d_kp), int(F), int(stride), _dptr(d_frame_ids), int(n_frames), _dptr(d_P), _dptr(d_offsets),
+            _dptr(d_nodes), _dptr(d_track_summary), int(max_tracks), inlier_px, min_parallax_deg, int(min_inliers), int(min_len),
+            int(max_hyp), seed, _dptr(d_offsets_out), _dptr(d_nodes_out), _dptr(d_summary_out), _dptr(d_track_map), _dptr(d_xyz_out),
+            _dptr(d_flags_out), _dptr(d_track_stats), _dptr(d_track_of), _dptr(d_report)))
+
+    def track_consensus(self, kps_per_frame, cameras, track_offsets, nodes=None, inlier_px=4.0, min_parallax_deg=1.0,
+                        min_inliers=2, min_len=2, max_hyp=256, seed=0):
+        """The host form (pgx_track_consensus).  kps_per_frame: one KEYPOINT_DTYPE array per frame; cameras [n_frames][3][4]
+        (or [n_frames][12]) float64, NaN rows for frames without a pose.  Tracks as pgx_tracks_get gives them (track_offsets
+        [n_tracks + 1], nodes [n_nodes][2]) or, with nodes=None, the `tracks` list of tracks_host.
+        -> dict(offsets [n_out + 1], nodes [nodes_out][2], summary [8], map [n], xyz [n_out][3], flags [n_out], stats [n][4],
+                report [8])"""
+        off, nd, kp, counts, flat = _host_tracks(kps_per_frame, track_offsets, nodes)
+        P = np.ascontiguousarray(cameras, dtype=np.float64).reshape(len(kp), 12)
+        n = len(off) - 1
+        off_out, nd_out = np.zeros(n + 1, dtype=np.int32), np.zeros((max(len(nd), 1), 2), dtype=np.int32)
+        summary, report = np.zeros(8, dtype=np.int32), np.zeros(8, dtype=np.int32)
+        tmap, stats = np.zeros(max(n, 1), dtype=np.int32), np.zeros((max(n, 1), 4), dtype=np.int32)
+        xyz, flags = np.zeros((max(n, 1), 3)), np.zeros(max(n, 1), dtype=np.int32)
+        self._chk(self._L.pgx_track_consensus(
+            self._h, _ptr(flat) if len(flat) else None, _ptr(counts), len(kp), _ptr(P), _ptr(off), _ptr(nd) if len(nd) else None, n,
+            inlier_px, min_parallax_deg, int(min_inliers), int(min_len), int(max_hyp), seed, _ptr(off_out), _ptr(nd_out),
+            _ptr(summary), _ptr(tmap), _ptr(xyz), _ptr(flags), _ptr(stats), _ptr(report)))
+        n_out = int(summary[0])
+        return dict(offsets=off_out[:n_out + 1], nodes=nd_out[:int(summary[1])], summary=summary, map=tmap[:n], xyz=xyz[:n_out],
+                    flags=flags[:n_out], stats=stats[:n], report=report)
+
     # -- two-view verification of match lists by epipolar RANSAC (pgx_verify_pair*) ------------------------
     def verify_pairs_dev(self, d_kp, d_matches, d_counts, d_pairlist, M, stride, max_dist, d_out, d_F, d_stats, d_report,
                          n_samples=256, inlier_px=1.5, min_inliers=24, refit_iters=2, seed=0, d_F32=None, d_inlier=None,

@@ -94,6 +94,12 @@ int decode_status(pgx_ctx *c, int bits)
     if (bits & PGX_ST_REG_DUP) return fail(c, PGX_E_BADARG, "registration: two slots of d_frame_ids name the same frame");
     if (bits & PGX_ST_REG_TWICE)
         return fail(c, PGX_E_BADARG, "registration: a track has two nodes in one target frame (those nodes were skipped)");
+    if (bits & PGX_ST_CNS_CAP)
+        return fail(c, PGX_E_CAPACITY, "track consensus: n_tracks exceeds max_tracks (only the first max_tracks were processed)");
+    if (bits & PGX_ST_CNS_NODE)
+        return fail(c, PGX_E_BADARG, "track consensus: a node outside the frames / keypoint slots, or malformed offsets (those nodes "
+                                     "were dropped)");
+    if (bits & PGX_ST_CNS_DUP) return fail(c, PGX_E_BADARG, "track consensus: two slots of d_frame_ids name the same frame");
     return PGX_OK;
 }
 
@@ -447,7 +453,7 @@ void pgx_ctx_destroy(pgx_ctx *c)
     for (hipEvent_t ev : c->ev_pool) (void)hipEventDestroy(ev);
     DevBuf *bufs[] = {&c->d_pairs, &c->d_plan, &c->d_steer_pairs, &c->d_steer_plans, &c->d_steer_dirs, &c->d_map, &c->ws_gray, &c->ws_seg, &c->ws_segoff, &c->ws_nraw, &c->ws_rawxy,
                       &c->ws_rawscore, &c->ws_nms, &c->ws_order, &c->ws_nkept, &c->st_a, &c->st_b, &c->st_c,
-                      &c->st_d, &c->st_e, &c->st_f, &c->ws_pose, &c->ws_tracks, &c->ws_tracks_split, &c->ws_agree, &c->ws_matchn[0], &c->ws_matchn[1], &c->ws_matchn[2], &c->ws_knn, &c->ws_guided, &c->ws_tri, &c->ws_ba, &c->ws_reg, &c->ws_ver, &c->ws_init,
+                      &c->st_d, &c->st_e, &c->st_f, &c->ws_pose, &c->ws_tracks, &c->ws_tracks_split, &c->ws_agree, &c->ws_matchn[0], &c->ws_matchn[1], &c->ws_matchn[2], &c->ws_knn, &c->ws_guided, &c->ws_tri, &c->ws_ba, &c->ws_reg, &c->ws_ver, &c->ws_init, &c->ws_cns,
                       &c->ws_pyr_a, &c->ws_pyr_b, &c->ws_pyr_kp, &c->ws_pyr_desc, &c->ws_pyr_bins, &c->ws_pyr_cnt};
     for (DevBuf *b : bufs) b->release();
     c->pin_in.release();
@@ -1358,6 +1364,18 @@ int reg_args(pgx_ctx *c, int n_samples, double inlier_px, int min_inliers, int r
     return iters_ok(c, "refine_iters", refine_iters, 32);
 }
 
+// *cos2 = the square of the cosine of min_parallax_deg
+int cns_args(pgx_ctx *c, double inlier_px, double min_parallax_deg, int min_inliers, int max_hyp, double *cos2)
+{
+    if (inlier_px_ok(c, inlier_px) != PGX_OK) return PGX_E_BADARG;
+    if (!(min_parallax_deg >= 0.0 && min_parallax_deg < 90.0)) return fail(c, PGX_E_BADARG, "min_parallax_deg must be in [0, 90)");
+    if (min_inliers < 2) return fail(c, PGX_E_BADARG, "min_inliers = %d, must be >= 2", min_inliers);
+    if (max_hyp < 1 || max_hyp > 4096) return fail(c, PGX_E_BADARG, "max_hyp = %d, must be in [1, 4096]", max_hyp);
+    const double cs = std::cos(min_parallax_deg * M_PI / 180.0);
+    *cos2 = cs * cs;
+    return PGX_OK;
+}
+
 int ver_args(pgx_ctx *c, int M, int stride, int n_samples, double inlier_px, int min_inliers, int refit_iters)
 {
     if (pairs_ok(c, M, stride) != PGX_OK || samples_ok(c, n_samples) != PGX_OK || inlier_px_ok(c, inlier_px) != PGX_OK) return PGX_E_BADARG;
@@ -1559,6 +1577,75 @@ int pgx_register_frames(pgx_ctx *c, const pgx_keypoint *kps, const int32_t *coun
                             t.n_nodes, in.dev<int32_t>(i.ts), n_tracks, in.dev<double>(i.xyz), in.dev<int32_t>(i.flags), n_samples, inlier_px,
                             min_inliers, refine_iters, seed, out.dev<double>(o_Rt), out.dev<double>(o_P), out.dev<int32_t>(o_st),
                             out.dev<double>(o_er), out.dev<int32_t>(o_ni), out.dev<int32_t>(o_rep), c->ws_reg.p, c->d_status);
+    }
+    HIPCHK(c, hipGetLastError());
+    return download_images(c, out);
+}
+
+// ---- track consensus: outlier observations dropped from tracks ------------------------------------------------------
+
+int pgx_track_consensus_dev(pgx_ctx *c, const pgx_keypoint *d_kp, int F, int stride, const int32_t *d_frame_ids, int n_frames,
+                            const double *d_P, const int32_t *d_offsets, const int32_t *d_nodes, const int32_t *d_track_summary,
+                            int max_tracks, double inlier_px, double min_parallax_deg, int min_inliers, int min_len, int max_hyp,
+                            uint64_t seed, int32_t *d_offsets_out, int32_t *d_nodes_out, int32_t *d_summary_out, int32_t *d_track_map,
+                            double *d_xyz_out, int32_t *d_flags_out, int32_t *d_track_stats, int32_t *d_track_of, int32_t *d_report)
+{
+    if (!c || !d_kp || !d_P || !d_offsets || !d_nodes || !d_track_summary || !d_offsets_out || !d_nodes_out || !d_summary_out ||
+        !d_track_map || !d_xyz_out || !d_flags_out || !d_track_stats || !d_report)
+        return c ? fail(c, PGX_E_BADARG, "null pointer") : PGX_E_BADARG;
+    Lock l(c);
+    int rc = geom_dev_args(c, F, stride, n_frames, d_frame_ids, max_tracks);
+    double cos2 = 0.0;
+    if (rc == PGX_OK) rc = cns_args(c, inlier_px, min_parallax_deg, min_inliers, max_hyp, &cos2);
+    if (rc != PGX_OK) return rc;
+    if (d_offsets_out == d_offsets || d_nodes_out == d_nodes || d_summary_out == d_track_summary)
+        return fail(c, PGX_E_BADARG, "the output graph must not alias the input graph");
+    const long long node_cap = (long long)n_frames * stride;
+    HIPCHK(c, c->ws_cns.ensure(pgx_consensus_ws_bytes(n_frames, max_tracks, node_cap)));
+    {
+        ProfScope ps(c, "consensus");
+        pgx_launch_consensus(c, c->stream, d_kp, F, stride, d_frame_ids, n_frames, d_P, d_offsets, d_nodes, node_cap, d_track_summary,
+                             max_tracks, inlier_px, cos2, min_inliers, min_len, max_hyp, seed, d_offsets_out, d_nodes_out, d_summary_out,
+                             d_track_map, d_xyz_out, d_flags_out, d_track_stats, d_track_of, d_report, c->ws_cns.p, c->d_status);
+    }
+    HIPCHK(c, hipGetLastError());
+    return PGX_OK;
+}
+
+int pgx_track_consensus(pgx_ctx *c, const pgx_keypoint *kps, const int32_t *counts, int n_frames, const double *P,
+                        const int32_t *track_offsets, const int32_t *nodes, int n_tracks, double inlier_px, double min_parallax_deg,
+                        int min_inliers, int min_len, int max_hyp, uint64_t seed, int32_t *offsets_out, int32_t *nodes_out,
+                        int32_t *summary_out, int32_t *track_map, double *xyz_out, int32_t *flags_out, int32_t *track_stats,
+                        int32_t *report)
+{
+    if (!c || !counts || !P || !track_offsets || !offsets_out || !summary_out || !report || n_frames <= 0 || n_tracks < 0)
+        return c ? fail(c, PGX_E_BADARG, "null pointer or bad size") : PGX_E_BADARG;
+    Lock l(c);
+    double cos2 = 0.0;
+    int rc = cns_args(c, inlier_px, min_parallax_deg, min_inliers, max_hyp, &cos2);
+    HostTracks t;
+    if (rc == PGX_OK) rc = check_host_tracks(c, kps, counts, n_frames, track_offsets, nodes, n_tracks, &t);
+    if (rc != PGX_OK) return rc;
+    if (t.n_nodes > 0 && !nodes_out) return fail(c, PGX_E_BADARG, "null pointer (nodes_out)");
+    if (offsets_out == track_offsets || (nodes_out && nodes_out == nodes))
+        return fail(c, PGX_E_BADARG, "the output graph must not alias the input graph");
+    for (int i = 0; i < 8; i++) summary_out[i] = report[i] = 0;
+    offsets_out[0] = 0;
+    if (n_tracks == 0) return PGX_OK;
+    HostImage in, out;
+    const TracksIn i = tracks_in(in, t, {P, nullptr, nullptr}, {96, 0, 0}, false, nullptr, nullptr);
+    const int o_off = out.add(offsets_out, n_tracks + 1, 4), o_nd = out.add(nodes_out, t.n_nodes, 8, 1),
+              o_sum = out.add(summary_out, 8, 4, 64), o_map = out.add(track_map, n_tracks, 4), o_xyz = out.add(xyz_out, n_tracks, 24),
+              o_fl = out.add(flags_out, n_tracks, 4), o_st = out.add(track_stats, n_tracks, 16), o_rep = out.add(report, 8, 4, 64);
+    if ((rc = stage_images(c, in, out)) != PGX_OK) return rc;
+    HIPCHK(c, c->ws_cns.ensure(pgx_consensus_ws_bytes(n_frames, n_tracks, t.n_nodes)));
+    {
+        ProfScope ps(c, "consensus");
+        pgx_launch_consensus(c, c->stream, in.dev<pgx_keypoint>(i.kp), n_frames, t.stride, nullptr, n_frames, in.dev<double>(i.frame[0]),
+                             in.dev<int32_t>(i.off), in.dev<int32_t>(i.nodes), t.n_nodes, in.dev<int32_t>(i.ts), n_tracks, inlier_px, cos2,
+                             min_inliers, min_len, max_hyp, seed, out.dev<int32_t>(o_off), out.dev<int32_t>(o_nd), out.dev<int32_t>(o_sum),
+                             out.dev<int32_t>(o_map), out.dev<double>(o_xyz), out.dev<int32_t>(o_fl), out.dev<int32_t>(o_st), nullptr,
+                             out.dev<int32_t>(o_rep), c->ws_cns.p, c->d_status);
     }
     HIPCHK(c, hipGetLastError());
     return download_images(c, out);

@@ -34,6 +34,9 @@
 #define PGX_ST_REG_NODE   131072u /* pgx_register_frames_dev: a node outside the frames / keypoint slots, or malformed offsets */
 #define PGX_ST_REG_DUP    262144u /* pgx_register_frames_dev: two slots of d_frame_ids name the same frame */
 #define PGX_ST_REG_TWICE  524288u /* pgx_register_frames_dev: a track with two nodes in one target frame */
+#define PGX_ST_CNS_CAP    1048576u /* pgx_track_consensus_dev: n_tracks > max_tracks */
+#define PGX_ST_CNS_NODE   2097152u /* pgx_track_consensus_dev: a node outside the frames / keypoint slots, or malformed offsets */
+#define PGX_ST_CNS_DUP    4194304u /* pgx_track_consensus_dev: two slots of d_frame_ids name the same frame */
 
 // key = (distance << PGX_IDX_BITS) | index ; limits: index < 2^20, distance < 2^12
 #define PGX_IDX_BITS 20
@@ -146,6 +149,7 @@ struct pgx_ctx {
     DevBuf ws_tri;    // pgx_triangulate_tracks*: camera table, frame -> slot map, per-workgroup counters
     DevBuf ws_ba;     // pgx_bundle_adjust*: control block, cameras, reduced system, per-track and per-node state
     DevBuf ws_reg;    // pgx_register_frames*: target tables, correspondence lists, hypotheses of one chunk, scoring keys
+    DevBuf ws_cns;    // pgx_track_consensus*: frame table, ray records and keep flags per node, per-track state, scan block sums
     DevBuf ws_ver;    // pgx_verify_pair*: candidate lists of a chunk of image pairs, hypotheses of one chunk of samples, keys
     DevBuf ws_init;   // pgx_init_pair_dev, pgx_relative_pose: per image pair the two rotations, t, the intrinsics and the counters
     hipStream_t mstream[3] = {nullptr, nullptr, nullptr}; // [0] wide rounds, [1] residual distance rows, [2] per-pair finish
@@ -396,6 +400,17 @@ void pgx_launch_register(hipStream_t s, const pgx_keypoint *d_kp, int F, int str
                          const double *d_xyz, const int32_t *d_track_flags, int n_samples, double inlier_px, int min_inliers,
                          int refine_iters, uint64_t seed, double *d_Rt_out, double *d_P_out, int32_t *d_frame_stats,
                          double *d_frame_err, int32_t *d_node_inlier, int32_t *d_report, void *ws, int *status);
+
+// k_consensus.hip (track consensus; pgx_track_consensus_dev semantics, include/pgx.h)
+size_t pgx_consensus_ws_bytes(int n_frames, int max_tracks, long long node_cap);
+// node_cap: entries of d_nodes / d_nodes_out an offset may reach; cos2 = the square of the cosine of min_parallax_deg;
+// PGX_ST_CNS_* bits go to *status; ctx: the profiling groups consensus_frames / _score / _scan / _write
+void pgx_launch_consensus(pgx_ctx *ctx, hipStream_t s, const pgx_keypoint *d_kp, int F, int stride, const int32_t *d_frame_ids, int n_frames,
+                          const double *d_P, const int32_t *d_offsets, const int32_t *d_nodes, long long node_cap,
+                          const int32_t *d_track_summary, int max_tracks, double inlier_px, double cos2, int min_inliers, int min_len,
+                          int max_hyp, uint64_t seed, int32_t *d_offsets_out, int32_t *d_nodes_out, int32_t *d_summary_out,
+                          int32_t *d_track_map, double *d_xyz_out, int32_t *d_flags_out, int32_t *d_track_stats, int32_t *d_track_of,
+                          int32_t *d_report, void *ws, int *status);
 
 // k_verify.hip (two-view verification by epipolar RANSAC; pgx_verify_pairs_dev semantics, include/pgx.h)
 // samples per chunk for a workspace of M pairs (a multiple of 256), and the bytes of that workspace: not less for more pairs

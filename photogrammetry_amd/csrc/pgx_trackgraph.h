@@ -1,4 +1,4 @@
-// pgx_trackgraph.h -- what every consumer of the track graph shares (k_triangulate.hip, k_bundle.hip, k_register.hip):
+// pgx_trackgraph.h -- what every consumer of the track graph shares (k_triangulate.hip, k_bundle.hip, k_register.hip, k_consensus.hip):
 // the read-only view of the graph and the keypoints, its validation and walking on the device, the lane-group and
 // workgroup reductions (k_verify.hip uses those too), and the workspace carver of the launchers.  It brings pgx_ransac.h along,
 // the sampler and the keys of the RANSAC stages among its consumers.  Internal to libpgx.so; DESIGN.md section 14a.
