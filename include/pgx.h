@@ -902,6 +902,69 @@ int pgx_relative_pose(pgx_ctx *ctx, const pgx_keypoint *kp1, int n1, const pgx_k
                       int max_dist, const double *F, const double *K_a, const double *K_b, double min_angle_deg,
                       double min_front_frac, int min_points, double *Rt, int32_t *stats, double *sigma, double *cand_Rt);
 
+/* ---- image-pair selection on a binary visual vocabulary ------------------------------ */
+/* Which pairs of an unordered collection are worth matching: every matcher, verification and the track graph take
+ * d_pairlist [M][2] from the caller, and all pairs stop scaling at a few dozen frames.  This is image retrieval as SfM
+ * packages do it (quantise the descriptors against a vocabulary, score frames by their word histograms, match the best
+ * partners), stated in integers so that it is bit-identical to a CPU restatement (tests/pairs_ref.py).  Not in the C#
+ * reference.  k_vocab.hip.
+ * Shared definitions.  Descriptors are 256-bit: 8 words each, descriptor bit t = bit t % 32 of word t / 32.
+ *   d_desc [F][stride][8], d_counts [F]; slots f < F, n_f = clamp(d_counts[f], 0, stride); 1 <= stride <= 65535,
+ *   1 <= F <= 4096, 1 <= V <= 65536, anything else PGX_E_BADARG.  A slot with n_f == 0 takes part in nothing.
+ *   d(x, y) = popcount(x ^ y) over the 8 words.
+ *   word(f, i) = argmin over j < V of (d(desc[f][i], vocab[j]), j): a tie goes to the smaller j.
+ *
+ * pgx_vocab_quantize_dev: d_word[f][i] = word(f, i) and, with d_wdist not NULL, d_wdist[f][i] = its distance, for i < n_f;
+ * entries i >= n_f are not written.  The exact Hamming argmin on the block-scaled FP4 matrix instruction; no workspace. */
+int pgx_vocab_quantize_dev(pgx_ctx *ctx, const uint32_t *d_desc, const int32_t *d_counts, int F, int stride,
+                           const uint32_t *d_vocab /*[V][8]*/, int V, int32_t *d_word /*[F][stride]*/,
+                           int32_t *d_wdist /*[F][stride] or NULL*/);
+/* pgx_vocab_train_dev: k-majority, the Hamming form of k-means; integers only, deterministic.
+ *   N = the sum of n_f; rank g enumerates the valid descriptors by (f, i) ascending.
+ *   Initialisation, in uint64: lo_j = (j N) / V, hi_j = ((j + 1) N) / V, state = seed ^ (uint64_t)j * 0xD1B54A32D192ED03,
+ *     r_j = lo_j + splitmix64(state) % (hi_j - lo_j) (the splitmix64 of the RANSAC stages: state += 0x9E3779B97F4A7C15, then
+ *     the two multiply-xorshift rounds); vocab[j] = the descriptor of rank r_j.
+ *   One iteration: every valid descriptor gets its word by the rule above; for word j with c_j members of which ones_j[t]
+ *     have bit t set, the new bit t is 1 if 2 ones > c, 0 if 2 ones < c, the old bit on equality; c_j == 0 leaves the word
+ *     as it is.  All `iters` iterations run: no early stop, no host round trip.
+ *   d_report [4] int32: N; words without a member in the last assignment (-1 at iters == 0); bits changed by the last
+ *     iteration (-1 at iters == 0); 0.
+ * iters outside [0, 64]: PGX_E_BADARG at once.  N < V is known on the device only: d_report[0] = N, d_vocab is not written
+ * and pgx_check_status reports PGX_E_BADARG.  Workspace: 8 bytes per descriptor slot (F * stride) + 8 bytes per word.
+ * The same bits for any stride layout of the same descriptors. */
+int pgx_vocab_train_dev(pgx_ctx *ctx, const uint32_t *d_desc, const int32_t *d_counts, int F, int stride, int V, int iters,
+                        uint64_t seed, uint32_t *d_vocab /*out [V][8]*/, int32_t *d_report /*[4]*/);
+/* pgx_select_pairs_dev: the pair list of a collection.
+ * Histograms and weights.  h_f[w] = the number of entries i < n_f with word(f, i) == w; Fv = the slots with n_f > 0;
+ *   df[w] = the slots with h_f[w] > 0.  weighting == 0: q[w] = 1.  weighting == 1, an integer log2 of the inverse document
+ *   frequency with a linear mantissa: q[w] = 0 where df[w] == 0, else x = (Fv 2^16) / df[w] in 64 bits, e = the index of the
+ *   highest set bit of x, m = (x 2^8) / 2^e - 256, q[w] = 256 (e - 16) + m (a word in every frame weighs 0).  Any other
+ *   weighting: PGX_E_BADARG.
+ * Scores, in int64: self_f = sum_w q[w] h_f[w]; s(a, b) = sum_w q[w] min(h_a[w], h_b[w]);
+ *   sn(a, b) = (s(a, b) 2^20) / max(1, min(self_a, self_b)), in [0, 2^20], symmetric.
+ *   d_scores[a][b] = sn(a, b) for non-empty a != b, -1 on the diagonal and wherever a slot is empty.
+ * Selection.  Slot a nominates the first min(top_k, .) of its candidates: the b != a with n_b > 0 and sn >= min_score, in
+ *   (sn descending, b ascending) order.  A pair a < b of non-empty slots is selected when a nominates b, or b nominates a,
+ *   or b - a <= window.  top_k >= 0, window >= 0 (else PGX_E_BADARG); top_k = 0 with window = w is the sliding-window list.
+ * Output.  The selected pairs in lexicographic (a, b) order in d_pairlist [max_pairs][2], each with its sn in d_pair_score
+ *   [max_pairs]; rows from the count to max_pairs hold (-1, -1) and -1.  More than max_pairs pairs: the first max_pairs are
+ *   written and pgx_check_status reports PGX_E_CAPACITY.  A prefix of the list is what every d_pairlist consumer takes.
+ *   d_summary [8] int32: pairs selected (the full count); Fv; words with df == 0; words with df == Fv; pairs selected by
+ *   the window alone; the smallest sn among nominated pairs (-1: none); 0; 0.
+ * Workspace: per slot 4 stride + 2 V + 32 bytes, per word 4 bytes, 8 F^2 bytes of raw scores, and 4 F^2 more when d_scores is
+ * NULL. */
+int pgx_select_pairs_dev(pgx_ctx *ctx, const uint32_t *d_desc, const int32_t *d_counts, int F, int stride,
+                         const uint32_t *d_vocab, int V, int weighting, int top_k, int window, int min_score, int max_pairs,
+                         int32_t *d_pairlist /*[max_pairs][2]*/, int32_t *d_pair_score /*[max_pairs]*/,
+                         int32_t *d_scores /*[F][F] or NULL*/, int32_t *d_summary /*[8]*/);
+/* Host forms: host arrays in the layouts above in, host arrays out, the same kernels; they return when the results are in the
+ * caller's buffers.  pgx_vocab_train answers N < V with PGX_E_BADARG at once.  scores may be NULL. */
+int pgx_vocab_train(pgx_ctx *ctx, const uint32_t *desc, const int32_t *counts, int F, int stride, int V, int iters,
+                    uint64_t seed, uint32_t *vocab, int32_t *report);
+int pgx_select_pairs(pgx_ctx *ctx, const uint32_t *desc, const int32_t *counts, int F, int stride, const uint32_t *vocab,
+                     int V, int weighting, int top_k, int window, int min_score, int max_pairs, int32_t *pairlist,
+                     int32_t *pair_score, int32_t *scores, int32_t *summary);
+
 /* ---- measurement hooks (bench.py) ---------------------------------------------------- */
 /* When on, the named hot kernels are bracketed by HIP events on the launch stream. */
 int pgx_profile_enable(pgx_ctx *ctx, int on);

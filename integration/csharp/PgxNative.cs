@@ -220,6 +220,24 @@ internal static unsafe class PgxNative
                                                                 double minAngleDeg, double minFrontFrac, int minPoints, double* rt,
                                                                 int* stats, double* sigma, double* candRt);
 
+    // image-pair selection on a binary visual vocabulary (256-bit descriptors): dDesc [f][stride][8], dVocab [v][8]; dWord and
+    // dWdist [f][stride] (dWdist or null); dPairlist [maxPairs][2] is what every dPairlist parameter above takes, dPairScore
+    // [maxPairs], dScores [f][f] or null, dSummary [8], dReport [4].  The host forms take host arrays in the same layouts.
+    [DllImport(Lib)] public static extern int pgx_vocab_quantize_dev(IntPtr ctx, void* dDesc, void* dCounts, int f, int stride,
+                                                                     void* dVocab, int v, void* dWord, void* dWdist);
+    [DllImport(Lib)] public static extern int pgx_vocab_train_dev(IntPtr ctx, void* dDesc, void* dCounts, int f, int stride, int v,
+                                                                  int iters, ulong seed, void* dVocab, void* dReport);
+    [DllImport(Lib)] public static extern int pgx_select_pairs_dev(IntPtr ctx, void* dDesc, void* dCounts, int f, int stride,
+                                                                   void* dVocab, int v, int weighting, int topK, int window,
+                                                                   int minScore, int maxPairs, void* dPairlist, void* dPairScore,
+                                                                   void* dScores, void* dSummary);
+    [DllImport(Lib)] public static extern int pgx_vocab_train(IntPtr ctx, uint* desc, int* counts, int f, int stride, int v, int iters,
+                                                              ulong seed, uint* vocab, int* report);
+    [DllImport(Lib)] public static extern int pgx_select_pairs(IntPtr ctx, uint* desc, int* counts, int f, int stride, uint* vocab,
+                                                               int v, int weighting, int topK, int window, int minScore,
+                                                               int maxPairs, int* pairlist, int* pairScore, int* scores,
+                                                               int* summary);
+
     /// <summary>Maps a status code back to the exception type the managed implementation throws.</summary>
     public static void Check(IntPtr ctx, int rc)
     {

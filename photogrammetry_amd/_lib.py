@@ -95,6 +95,11 @@ SIGNATURES = {
     "pgx_verify_pair": (I, [P, P, I, P, I, P, I, I, D, I, I, U64, P, P, P, P]),
     "pgx_init_pair_dev": (I, [P, P, P, P, P, I, I, I, P, I, I, P, P, D, D, I, P, P, P, P, P, P, P, P, P]),
     "pgx_relative_pose": (I, [P, P, I, P, I, P, I, P, P, P, D, D, I, P, P, P, P]),
+    "pgx_vocab_quantize_dev": (I, [P, P, P, I, I, P, I, P, P]),
+    "pgx_vocab_train_dev": (I, [P, P, P, I, I, I, I, U64, P, P]),
+    "pgx_select_pairs_dev": (I, [P, P, P, I, I, P, I, I, I, I, I, I, P, P, P, P]),
+    "pgx_vocab_train": (I, [P, P, P, I, I, I, I, U64, P, P]),
+    "pgx_select_pairs": (I, [P, P, P, I, I, P, I, I, I, I, I, I, P, P, P, P]),
     "pgx_profile_enable": (I, [P, I]),
     "pgx_profile_filter": (I, [P, S]),
     "pgx_profile_get": (I, [P, S, P, P]),

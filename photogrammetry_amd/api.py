@@ -648,6 +648,59 @@ class Engine:
             _ptr(cand) if candidates else None))
         return dict(Rt=Rt, stats=stats, sigma=float(sigma[0]), cand_Rt=cand)
 
+    # -- image-pair selection on a binary visual vocabulary (pgx_vocab_*, pgx_select_pairs*) -----------------------
+    def vocab_quantize_dev(self, d_desc, d_counts, F, stride, d_vocab, V, d_word, d_wdist=None):
+        """pgx_vocab_quantize_dev: d_desc [F][stride][8] uint32, d_vocab [V][8] uint32; d_word and d_wdist [F][stride] int32
+        (d_wdist or None): the nearest word of every valid descriptor, ties to the smaller word.  No sync."""
+        self._chk(self._L.pgx_vocab_quantize_dev(self._h, _dptr(d_desc), _dptr(d_counts), int(F), int(stride), _dptr(d_vocab),
+                                                 int(V), _dptr(d_word), _dptr(d_wdist)))
+
+    def vocab_train_dev(self, d_desc, d_counts, F, stride, V, d_vocab, d_report, iters=2, seed=0):
+        """pgx_vocab_train_dev: k-majority on the device; d_vocab [V][8] uint32 out, d_report [4] int32.  No sync."""
+        self._chk(self._L.pgx_vocab_train_dev(self._h, _dptr(d_desc), _dptr(d_counts), int(F), int(stride), int(V), int(iters),
+                                              seed, _dptr(d_vocab), _dptr(d_report)))
+
+    def select_pairs_dev(self, d_desc, d_counts, F, stride, d_vocab, V, max_pairs, d_pairlist, d_pair_score, d_summary,
+                         weighting=1, top_k=10, window=0, min_score=1, d_scores=None):
+        """pgx_select_pairs_dev: d_pairlist [max_pairs][2] int32 (rows past the count hold -1), d_pair_score [max_pairs] int32,
+        d_scores [F][F] int32 or None, d_summary [8] int32 ([0] = the pairs selected).  No sync."""
+        self._chk(self._L.pgx_select_pairs_dev(self._h, _dptr(d_desc), _dptr(d_counts), int(F), int(stride), _dptr(d_vocab),
+                                               int(V), int(weighting), int(top_k), int(window), int(min_score), int(max_pairs),
+                                               _dptr(d_pairlist), _dptr(d_pair_score), _dptr(d_scores), _dptr(d_summary)))
+
+    @staticmethod
+    def _host_slots(desc, counts):
+        d = np.ascontiguousarray(desc, dtype=np.uint32)
+        if d.ndim != 3 or d.shape[2] != 8:
+            raise ValueError("descriptors must be [F][stride][8] uint32 (256-bit)")
+        cn = np.ascontiguousarray(counts, dtype=np.int32).reshape(-1)
+        if len(cn) != d.shape[0]:
+            raise ValueError("one count per slot")
+        return d, cn
+
+    def vocab_train(self, desc, counts, V, iters=2, seed=0):
+        """The host form (pgx_vocab_train): desc [F][stride][8] uint32, counts [F] -> (vocab [V][8] uint32, report [4])."""
+        d, cn = self._host_slots(desc, counts)
+        vocab, report = np.zeros((max(int(V), 1), 8), dtype=np.uint32), np.zeros(4, dtype=np.int32)
+        self._chk(self._L.pgx_vocab_train(self._h, _ptr(d), _ptr(cn), d.shape[0], d.shape[1], int(V), int(iters), seed,
+                                          _ptr(vocab), _ptr(report)))
+        return vocab, report
+
+    def select_pairs(self, desc, counts, vocab, weighting=1, top_k=10, window=0, min_score=1, max_pairs=None, scores=False):
+        """The host form (pgx_select_pairs) -> dict(pairs [n][2] trimmed to summary[0], pair_score [n], scores [F][F] or None,
+        summary [8]).  max_pairs defaults to all F (F - 1) / 2; a smaller one that cuts the list raises CapacityError."""
+        d, cn = self._host_slots(desc, counts)
+        vc = np.ascontiguousarray(vocab, dtype=np.uint32).reshape(-1, 8)
+        F = d.shape[0]
+        cap = F * (F - 1) // 2 if max_pairs is None else int(max_pairs)
+        pl, ps = np.zeros((max(cap, 1), 2), dtype=np.int32), np.zeros(max(cap, 1), dtype=np.int32)
+        sc = np.zeros((F, F), dtype=np.int32) if scores else None
+        summary = np.zeros(8, dtype=np.int32)
+        self._chk(self._L.pgx_select_pairs(self._h, _ptr(d), _ptr(cn), F, d.shape[1], _ptr(vc), len(vc), int(weighting), int(top_k),
+                                           int(window), int(min_score), cap, _ptr(pl), _ptr(ps), _ptr(sc), _ptr(summary)))
+        n = min(int(summary[0]), cap)
+        return dict(pairs=pl[:n], pair_score=ps[:n], scores=sc, summary=summary)
+
     # -- multi-GPU: the context's own RCCL communicator (pgx_comm_*) ------------------------------
     def comm_init(self, rank, world, unique_id):
         """Collective: every rank calls this with the 128 bytes rank 0 got from comm_unique_id()."""

@@ -100,6 +100,10 @@ int decode_status(pgx_ctx *c, int bits)
         return fail(c, PGX_E_BADARG, "track consensus: a node outside the frames / keypoint slots, or malformed offsets (those nodes "
                                      "were dropped)");
     if (bits & PGX_ST_CNS_DUP) return fail(c, PGX_E_BADARG, "track consensus: two slots of d_frame_ids name the same frame");
+    if (bits & PGX_ST_VOC_FEW)
+        return fail(c, PGX_E_BADARG, "vocabulary training: fewer valid descriptors than words (d_vocab was not written)");
+    if (bits & PGX_ST_SEL_CAP)
+        return fail(c, PGX_E_CAPACITY, "pair selection: more than max_pairs pairs were selected (the first max_pairs were written)");
     return PGX_OK;
 }
 
@@ -453,7 +457,7 @@ void pgx_ctx_destroy(pgx_ctx *c)
     for (hipEvent_t ev : c->ev_pool) (void)hipEventDestroy(ev);
     DevBuf *bufs[] = {&c->d_pairs, &c->d_plan, &c->d_steer_pairs, &c->d_steer_plans, &c->d_steer_dirs, &c->d_map, &c->ws_gray, &c->ws_seg, &c->ws_segoff, &c->ws_nraw, &c->ws_rawxy,
                       &c->ws_rawscore, &c->ws_nms, &c->ws_order, &c->ws_nkept, &c->st_a, &c->st_b, &c->st_c,
-                      &c->st_d, &c->st_e, &c->st_f, &c->ws_pose, &c->ws_tracks, &c->ws_tracks_split, &c->ws_agree, &c->ws_matchn[0], &c->ws_matchn[1], &c->ws_matchn[2], &c->ws_knn, &c->ws_guided, &c->ws_tri, &c->ws_ba, &c->ws_reg, &c->ws_ver, &c->ws_init, &c->ws_cns,
+                      &c->st_d, &c->st_e, &c->st_f, &c->ws_pose, &c->ws_tracks, &c->ws_tracks_split, &c->ws_agree, &c->ws_matchn[0], &c->ws_matchn[1], &c->ws_matchn[2], &c->ws_knn, &c->ws_guided, &c->ws_tri, &c->ws_ba, &c->ws_reg, &c->ws_ver, &c->ws_init, &c->ws_cns, &c->ws_vocab,
                       &c->ws_pyr_a, &c->ws_pyr_b, &c->ws_pyr_kp, &c->ws_pyr_desc, &c->ws_pyr_bins, &c->ws_pyr_cnt};
     for (DevBuf *b : bufs) b->release();
     c->pin_in.release();
@@ -1648,6 +1652,110 @@ int pgx_track_consensus(pgx_ctx *c, const pgx_keypoint *kps, const int32_t *coun
                              out.dev<int32_t>(o_rep), c->ws_cns.p, c->d_status);
     }
     HIPCHK(c, hipGetLastError());
+    return download_images(c, out);
+}
+
+// ---- binary visual vocabulary and image-pair selection ---------------------------------------------------------------
+
+namespace {
+
+int vocab_args(pgx_ctx *c, int F, int stride, int V)
+{
+    if (F < 1 || F > 4096) return fail(c, PGX_E_BADARG, "F must be in [1, 4096]");
+    if (stride < 1 || stride > 65535) return fail(c, PGX_E_BADARG, "stride must be in [1, 65535]");
+    if (V < 1 || V > 65536) return fail(c, PGX_E_BADARG, "V must be in [1, 65536]");
+    return PGX_OK;
+}
+
+int select_args(pgx_ctx *c, int F, int stride, int V, int weighting, int top_k, int window, int max_pairs)
+{
+    if (const int rc = vocab_args(c, F, stride, V); rc != PGX_OK) return rc;
+    if (weighting != 0 && weighting != 1) return fail(c, PGX_E_BADARG, "weighting must be 0 or 1");
+    if (top_k < 0 || window < 0 || max_pairs < 0) return fail(c, PGX_E_BADARG, "top_k, window and max_pairs must not be negative");
+    return PGX_OK;
+}
+
+} // namespace
+
+int pgx_vocab_quantize_dev(pgx_ctx *c, const uint32_t *d_desc, const int32_t *d_counts, int F, int stride, const uint32_t *d_vocab,
+                           int V, int32_t *d_word, int32_t *d_wdist)
+{
+    if (!c || !d_desc || !d_counts || !d_vocab || !d_word) return c ? fail(c, PGX_E_BADARG, "null pointer") : PGX_E_BADARG;
+    Lock l(c);
+    if (const int rc = vocab_args(c, F, stride, V); rc != PGX_OK) return rc;
+    pgx_launch_vocab_quantize(c, c->stream, d_desc, d_counts, F, stride, d_vocab, V, d_word, d_wdist);
+    HIPCHK(c, hipGetLastError());
+    return PGX_OK;
+}
+
+int pgx_vocab_train_dev(pgx_ctx *c, const uint32_t *d_desc, const int32_t *d_counts, int F, int stride, int V, int iters,
+                        uint64_t seed, uint32_t *d_vocab, int32_t *d_report)
+{
+    if (!c || !d_desc || !d_counts || !d_vocab || !d_report) return c ? fail(c, PGX_E_BADARG, "null pointer") : PGX_E_BADARG;
+    Lock l(c);
+    if (const int rc = vocab_args(c, F, stride, V); rc != PGX_OK) return rc;
+    if (iters < 0 || iters > 64) return fail(c, PGX_E_BADARG, "iters must be in [0, 64]");
+    HIPCHK(c, c->ws_vocab.ensure(pgx_vocab_train_ws_bytes(F, stride, V)));
+    pgx_launch_vocab_train(c, c->stream, d_desc, d_counts, F, stride, V, iters, seed, d_vocab, d_report, c->ws_vocab.p, c->d_status);
+    HIPCHK(c, hipGetLastError());
+    return PGX_OK;
+}
+
+int pgx_select_pairs_dev(pgx_ctx *c, const uint32_t *d_desc, const int32_t *d_counts, int F, int stride, const uint32_t *d_vocab, int V,
+                         int weighting, int top_k, int window, int min_score, int max_pairs, int32_t *d_pairlist,
+                         int32_t *d_pair_score, int32_t *d_scores, int32_t *d_summary)
+{
+    if (!c || !d_desc || !d_counts || !d_vocab || !d_summary || (max_pairs > 0 && (!d_pairlist || !d_pair_score)))
+        return c ? fail(c, PGX_E_BADARG, "null pointer") : PGX_E_BADARG;
+    Lock l(c);
+    if (const int rc = select_args(c, F, stride, V, weighting, top_k, window, max_pairs); rc != PGX_OK) return rc;
+    HIPCHK(c, c->ws_vocab.ensure(pgx_select_pairs_ws_bytes(F, stride, V, d_scores == nullptr)));
+    pgx_launch_select_pairs(c, c->stream, d_desc, d_counts, F, stride, d_vocab, V, weighting, top_k, window, min_score, max_pairs,
+                            d_pairlist, d_pair_score, d_scores, d_summary, c->ws_vocab.p, c->d_status);
+    HIPCHK(c, hipGetLastError());
+    return PGX_OK;
+}
+
+int pgx_vocab_train(pgx_ctx *c, const uint32_t *desc, const int32_t *counts, int F, int stride, int V, int iters, uint64_t seed,
+                    uint32_t *vocab, int32_t *report)
+{
+    if (!c || !desc || !counts || !vocab || !report) return c ? fail(c, PGX_E_BADARG, "null pointer") : PGX_E_BADARG;
+    Lock l(c);
+    if (const int rc = vocab_args(c, F, stride, V); rc != PGX_OK) return rc;
+    if (iters < 0 || iters > 64) return fail(c, PGX_E_BADARG, "iters must be in [0, 64]");
+    long long N = 0;
+    for (int f = 0; f < F; f++) N += counts[f] < 0 ? 0 : (counts[f] > stride ? stride : counts[f]);
+    if (N < V) return fail(c, PGX_E_BADARG, "fewer valid descriptors (%lld) than words (%d)", N, V);
+    HostImage in, out;
+    const int i_desc = in.add(desc, (size_t)F * stride, 32), i_cnt = in.add(counts, F, 4);
+    const int o_voc = out.add(vocab, V, 32), o_rep = out.add(report, 4, 4, 16);
+    if (const int rs = stage_images(c, in, out); rs != PGX_OK) return rs;
+    HIPCHK(c, c->ws_vocab.ensure(pgx_vocab_train_ws_bytes(F, stride, V)));
+    pgx_launch_vocab_train(c, c->stream, in.dev<uint32_t>(i_desc), in.dev<int32_t>(i_cnt), F, stride, V, iters, seed,
+                           out.dev<uint32_t>(o_voc), out.dev<int32_t>(o_rep), c->ws_vocab.p, c->d_status);
+    HIPCHK(c, hipGetLastError());
+    return download_images(c, out);
+}
+
+int pgx_select_pairs(pgx_ctx *c, const uint32_t *desc, const int32_t *counts, int F, int stride, const uint32_t *vocab, int V,
+                     int weighting, int top_k, int window, int min_score, int max_pairs, int32_t *pairlist, int32_t *pair_score,
+                     int32_t *scores, int32_t *summary)
+{
+    if (!c || !desc || !counts || !vocab || !summary || (max_pairs > 0 && (!pairlist || !pair_score)))
+        return c ? fail(c, PGX_E_BADARG, "null pointer") : PGX_E_BADARG;
+    Lock l(c);
+    if (const int rc = select_args(c, F, stride, V, weighting, top_k, window, max_pairs); rc != PGX_OK) return rc;
+    HostImage in, out;
+    const int i_desc = in.add(desc, (size_t)F * stride, 32), i_cnt = in.add(counts, F, 4), i_voc = in.add(vocab, V, 32);
+    const int o_pl = out.add(pairlist, max_pairs, 8, 1), o_ps = out.add(pair_score, max_pairs, 4, 1),
+              o_sc = out.add(scores, (size_t)F * F, 4, 0, scores != nullptr), o_sum = out.add(summary, 8, 4, 16);
+    if (const int rs = stage_images(c, in, out); rs != PGX_OK) return rs;
+    HIPCHK(c, c->ws_vocab.ensure(pgx_select_pairs_ws_bytes(F, stride, V, scores == nullptr)));
+    pgx_launch_select_pairs(c, c->stream, in.dev<uint32_t>(i_desc), in.dev<int32_t>(i_cnt), F, stride, in.dev<uint32_t>(i_voc), V,
+                            weighting, top_k, window, min_score, max_pairs, out.dev<int32_t>(o_pl), out.dev<int32_t>(o_ps),
+                            out.dev<int32_t>(o_sc), out.dev<int32_t>(o_sum), c->ws_vocab.p, c->d_status);
+    HIPCHK(c, hipGetLastError());
+    // the outputs travel even when the list was cut: PGX_E_CAPACITY leaves the first max_pairs pairs in the caller's buffers
     return download_images(c, out);
 }
 

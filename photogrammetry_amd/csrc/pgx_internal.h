@@ -37,6 +37,8 @@
 #define PGX_ST_CNS_CAP    1048576u /* pgx_track_consensus_dev: n_tracks > max_tracks */
 #define PGX_ST_CNS_NODE   2097152u /* pgx_track_consensus_dev: a node outside the frames / keypoint slots, or malformed offsets */
 #define PGX_ST_CNS_DUP    4194304u /* pgx_track_consensus_dev: two slots of d_frame_ids name the same frame */
+#define PGX_ST_VOC_FEW    8388608u  /* pgx_vocab_train_dev: fewer valid descriptors than words */
+#define PGX_ST_SEL_CAP    16777216u /* pgx_select_pairs_dev: more than max_pairs pairs selected */
 
 // key = (distance << PGX_IDX_BITS) | index ; limits: index < 2^20, distance < 2^12
 #define PGX_IDX_BITS 20
@@ -151,6 +153,7 @@ struct pgx_ctx {
     DevBuf ws_reg;    // pgx_register_frames*: target tables, correspondence lists, hypotheses of one chunk, scoring keys
     DevBuf ws_cns;    // pgx_track_consensus*: frame table, ray records and keep flags per node, per-track state, scan block sums
     DevBuf ws_ver;    // pgx_verify_pair*: candidate lists of a chunk of image pairs, hypotheses of one chunk of samples, keys
+    DevBuf ws_vocab;  // pgx_vocab_train*, pgx_select_pairs*: words per descriptor, members by word, histograms, weights, scores
     DevBuf ws_init;   // pgx_init_pair_dev, pgx_relative_pose: per image pair the two rotations, t, the intrinsics and the counters
     hipStream_t mstream[3] = {nullptr, nullptr, nullptr}; // [0] wide rounds, [1] residual distance rows, [2] per-pair finish
     hipEvent_t ev_in = nullptr, ev_wide[3] = {nullptr, nullptr, nullptr}, ev_rows[3] = {nullptr, nullptr, nullptr},
@@ -432,3 +435,19 @@ void pgx_launch_init_pair(hipStream_t s, const pgx_keypoint *d_kp, const pgx_pai
                           const double *d_F, const double *d_K, double cos2, double min_front_frac, int min_points, double *d_Rt_pair,
                           int32_t *d_pair_stats, double *d_sigma, double *d_cand_Rt, double *d_Rt_out, double *d_P_out,
                           int32_t *d_fixed_out, int32_t *d_register_out, int32_t *d_report, void *ws);
+
+// k_vocab.hip (binary visual vocabulary and image-pair selection; pgx_vocab_quantize_dev, pgx_vocab_train_dev and
+// pgx_select_pairs_dev semantics, include/pgx.h).  256-bit descriptors; F in [1, 4096], S in [1, 65535], V in [1, 65536]
+// d_word / d_wdist [F][S], d_wdist or nullptr
+void pgx_launch_vocab_quantize(pgx_ctx *ctx, hipStream_t s, const uint32_t *d_desc, const int32_t *d_counts, int F, int S,
+                               const uint32_t *d_vocab, int V, int32_t *d_word, int32_t *d_wdist);
+size_t pgx_vocab_train_ws_bytes(int F, int S, int V);
+// fewer valid descriptors than words: PGX_ST_VOC_FEW in *status, d_vocab untouched
+void pgx_launch_vocab_train(pgx_ctx *ctx, hipStream_t s, const uint32_t *d_desc, const int32_t *d_counts, int F, int S, int V, int iters,
+                            uint64_t seed, uint32_t *d_vocab, int32_t *d_report, void *ws, int *status);
+// own_scores: the [F][F] score matrix lives in the workspace (the caller passes no d_scores)
+size_t pgx_select_pairs_ws_bytes(int F, int S, int V, bool own_scores);
+// more than max_pairs pairs: PGX_ST_SEL_CAP in *status
+void pgx_launch_select_pairs(pgx_ctx *ctx, hipStream_t s, const uint32_t *d_desc, const int32_t *d_counts, int F, int S,
+                             const uint32_t *d_vocab, int V, int weighting, int top_k, int window, int min_score, int max_pairs,
+                             int32_t *d_pairlist, int32_t *d_pair_score, int32_t *d_scores, int32_t *d_summary, void *ws, int *status);
