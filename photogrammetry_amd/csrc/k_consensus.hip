@@ -353,40 +353,18 @@ __global__ __launch_bounds__(CNS_NT) void k_cns_scan_reduce(CnsArgs a)
     }
 }
 
-// the exclusive prefix of (x, y) over the workgroup's 256 threads in thread order, and the totals
-__device__ __forceinline__ void block_excl2(int &x, int &y, int &tx, int &ty, int (*sh)[2])
-{
-    const int ln = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int ix = x, iy = y;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int ox = __shfl_up(ix, d, 64), oy = __shfl_up(iy, d, 64);
-        if (ln >= d) { ix += ox; iy += oy; }
-    }
-    if (ln == 63) { sh[w][0] = ix; sh[w][1] = iy; }
-    __syncthreads();
-    int bx = 0, by = 0;
-    tx = 0;
-    ty = 0;
-#pragma unroll
-    for (int k = 0; k < CNS_NT / 64; k++) {
-        if (k < w) { bx += sh[k][0]; by += sh[k][1]; }
-        tx += sh[k][0];
-        ty += sh[k][1];
-    }
-    x = bx + ix - x;
-    y = by + iy - y;
-    __syncthreads();
-}
-
+// The surviving tracks and their nodes are scanned one after the other, not packed into one 64-bit value as the track graph's
+// are: tracks whose offsets overlap (malformed, reported, but not rejected) can keep more than 2^32 nodes between them, and a
+// carry out of the node count must not reach the track index that off_out and map are written at.
 __global__ __launch_bounds__(CNS_NT) void k_cns_scan_sums(CnsArgs a, int nblk)
 {
-    __shared__ int sh[CNS_NT / 64][2];
+    __shared__ int sh[CNS_NT / 64];
     int cx = 0, cy = 0;   // the carry: everything before this chunk of CNS_NT block sums
     for (int b0 = 0; b0 < nblk; b0 += CNS_NT) {
         const int b = b0 + threadIdx.x;
-        int x = b < nblk ? a.bsum[2 * (size_t)b] : 0, y = b < nblk ? a.bsum[2 * (size_t)b + 1] : 0, tx, ty;
-        block_excl2(x, y, tx, ty, sh);
+        int tx, ty;
+        const int x = block_excl_scan<int, CNS_NT>(b < nblk ? a.bsum[2 * (size_t)b] : 0, sh, tx);
+        const int y = block_excl_scan<int, CNS_NT>(b < nblk ? a.bsum[2 * (size_t)b + 1] : 0, sh, ty);
         if (b < nblk) {
             a.bsum[2 * (size_t)b] = cx + x;
             a.bsum[2 * (size_t)b + 1] = cy + y;
@@ -418,13 +396,12 @@ __global__ __launch_bounds__(CNS_NT) void k_cns_scan_sums(CnsArgs a, int nblk)
 
 __global__ __launch_bounds__(CNS_NT) void k_cns_scan_apply(CnsArgs a)
 {
-    __shared__ int sh[CNS_NT / 64][2];
+    __shared__ int sh[CNS_NT / 64];
     const long long nt = a.meta[0];
-    int kp[CNS_SCAN_PER_THREAD], x, y, tx, ty;
+    int kp[CNS_SCAN_PER_THREAD], x, y, tot;
     scan_items(a, nt, kp, x, y);
-    block_excl2(x, y, tx, ty, sh);
-    x += a.bsum[2 * (size_t)blockIdx.x];
-    y += a.bsum[2 * (size_t)blockIdx.x + 1];
+    x = a.bsum[2 * (size_t)blockIdx.x] + block_excl_scan<int, CNS_NT>(x, sh, tot);
+    y = a.bsum[2 * (size_t)blockIdx.x + 1] + block_excl_scan<int, CNS_NT>(y, sh, tot);
     const long long t0 = (long long)blockIdx.x * CNS_SCAN_ITEMS + (long long)threadIdx.x * CNS_SCAN_PER_THREAD;
 #pragma unroll
     for (int i = 0; i < CNS_SCAN_PER_THREAD; i++) {

@@ -7,20 +7,6 @@ namespace {
 constexpr int HAM_PAD = 4;      // pad tiles in front of k_ham_fp4's staged column offsets (its prefetch ring runs four tiles ahead, downwards)
 constexpr int MF_CHUNK = F4_CHUNK; // most columns one workgroup walks (LDS column-best array)
 
-// signed maximum over each half (32 lanes) of a fully active wavefront by DPP row operations: quads, 8, 16 lanes, then
-// row_bcast:15 carries rows 0 and 2 into rows 1 and 3.  Complete in lanes 16..31 and 48..63; no LDS crossbar traffic
-// (the publishing step of k_ham_fp4 made 160 ds_bpermute round trips per wavefront before).
-__device__ __forceinline__ int half_max_i32(int v)
-{
-    const int id = (int)0x80000000;
-    v = max(v, __builtin_amdgcn_update_dpp(id, v, 0xB1, 0xF, 0xF, false));  // quad_perm [1,0,3,2]
-    v = max(v, __builtin_amdgcn_update_dpp(id, v, 0x4E, 0xF, 0xF, false));  // quad_perm [2,3,0,1]
-    v = max(v, __builtin_amdgcn_update_dpp(id, v, 0x141, 0xF, 0xF, false)); // row_half_mirror
-    v = max(v, __builtin_amdgcn_update_dpp(id, v, 0x140, 0xF, 0xF, false)); // row_mirror
-    v = max(v, __builtin_amdgcn_update_dpp(id, v, 0x142, 0xA, 0xF, false)); // row_bcast:15 into rows 1, 3
-    return v;
-}
-
 // One row block of one image pair against its column chunk, RT row tiles per wavefront (4 * RT * 32 rows).  The kernel below
 // owns the LDS and the block map and picks RT by the rows the block really has: the LAST row block of a pair is usually ragged
 // (4096 rows = 10 blocks of 384 + 256), and 256 rows are exactly four waves x two tiles -- with three tiles per wave the

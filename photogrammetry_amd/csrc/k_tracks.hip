@@ -31,7 +31,7 @@
 //                  segments are short: <= n_frames)
 // Same-address atomics serialise at about 10 ns each on this part: one global counter of the edges used cost 1.3 ms per launch
 // (130 k wavefront atomics), per-node atomicAdds on the junk component's root 0.56 ms -- hence the LDS stages and TRK_ECNT.
-#include "pgx_internal.h"
+#include "pgx_trackgraph.h"   // block_excl_scan
 
 namespace {
 
@@ -243,30 +243,6 @@ __device__ __forceinline__ unsigned long long kept_item(const TrkArgs &a, int r)
     return (1ull << 32) | (unsigned)sz;
 }
 
-// block-wide exclusive scan of one value per thread (SCAN_NT threads); returns the exclusive prefix, *total = block sum
-__device__ __forceinline__ unsigned long long block_excl_scan(unsigned long long v, unsigned long long *lds /*[16]*/, unsigned long long *total)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    unsigned long long inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned long long o = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += o;
-    }
-    if (lane == 63) lds[w] = inc;
-    __syncthreads();
-    unsigned long long base = 0, tot = 0;
-#pragma unroll
-    for (int i = 0; i < SCAN_NT / 64; i++) {
-        const unsigned long long s = lds[i];
-        if (i < w) base += s;
-        tot += s;
-    }
-    __syncthreads();
-    *total = tot;
-    return base + inc - v;
-}
-
 __global__ __launch_bounds__(SCAN_NT) void k_trk_scan_reduce(TrkArgs a)
 {
     __shared__ unsigned long long lds[SCAN_NT / 64];
@@ -288,7 +264,7 @@ __global__ __launch_bounds__(SCAN_NT) void k_trk_scan_reduce(TrkArgs a)
     __shared__ int agg[4];   // dropped components, their nodes, longest kept, largest dropped: one global atomic each per workgroup
     if (threadIdx.x < 4) agg[threadIdx.x] = 0;
     unsigned long long tot;
-    (void)block_excl_scan(s, lds, &tot);   // (its barriers order the zeroing above before the adds below)
+    (void)block_excl_scan<unsigned long long, SCAN_NT>(s, lds, tot);   // (its barriers order the zeroing above before the adds below)
     if (threadIdx.x == 0) a.bsum[blockIdx.x] = tot;
     if (dropped) { atomicAdd(&agg[0], dropped); atomicAdd(&agg[1], dropped_nodes); atomicMax(&agg[3], largest_dropped); }
     if (longest) atomicMax(&agg[2], longest);
@@ -308,12 +284,12 @@ __global__ __launch_bounds__(SCAN_NT) void k_trk_scan_sums(TrkArgs a, int nb)
         const int b = b0 + threadIdx.x;
         const unsigned long long v = b < nb ? a.bsum[b] : 0ull;
         unsigned long long tot;
-        const unsigned long long ex = block_excl_scan(v, lds, &tot);
+        const unsigned long long ex = block_excl_scan<unsigned long long, SCAN_NT>(v, lds, tot);
         if (b < nb) a.bsum[b] = carry + ex;
         carry += tot;
     }
     unsigned long long etot;
-    (void)block_excl_scan(threadIdx.x < TRK_ECNT ? (unsigned long long)a.ecnt[threadIdx.x] : 0ull, lds, &etot);
+    (void)block_excl_scan<unsigned long long, SCAN_NT>(threadIdx.x < TRK_ECNT ? (unsigned long long)a.ecnt[threadIdx.x] : 0ull, lds, etot);
     if (threadIdx.x == 0) {
         const int nt = (int)(carry >> 32), nn = (int)(unsigned)carry;
         a.summary[0] = nt;
@@ -332,7 +308,7 @@ __global__ __launch_bounds__(SCAN_NT) void k_trk_scan_apply(TrkArgs a)
 #pragma unroll
     for (int i = 0; i < 4; i++) { rr[i] = trk_named_here(a, x0 + i); it[i] = kept_item(a, rr[i]); s += it[i]; }
     unsigned long long tot;
-    unsigned long long ex = a.bsum[blockIdx.x] + block_excl_scan(s, lds, &tot);
+    unsigned long long ex = a.bsum[blockIdx.x] + block_excl_scan<unsigned long long, SCAN_NT>(s, lds, tot);
 #pragma unroll
     for (int i = 0; i < 4; i++) {
         if (it[i]) {

@@ -1,12 +1,9 @@
 // k_vocab.hip -- image retrieval on a binary visual vocabulary (include/pgx.h: pgx_vocab_quantize_dev, pgx_vocab_train_dev,
 // pgx_select_pairs_dev): which image pairs of an unordered collection are worth matching.
 //
-// The quantiser (k_vocab_fp4) is the exact Hamming argmin of k_knn_fp4<1, false, 2> (k_knn.hip) with other addressing: the
-// rows are the valid descriptors of one slot, the columns are the vocabulary, a buffer of its own walked in chunks of
-// F4_CHUNK; a row's best is merged over the chunks as distance << 20 | word in LDS.  The arithmetic is pgx_fp4.h's: bits
-// expanded to fp4 -+1 in registers, acc = F4_BIAS + 8192 * dot + C exactly, the 14-bit key in the C input, every selection an
-// integer maximum of raw accumulator bits.  Padding as in k_knn_fp4: columns past the end of the ragged LAST tile of a chunk
-// are masked; row slots past the end repeat the last row and are not written.
+// The quantiser (k_vocab_fp4) is the exact Hamming argmin on the FP4 matrix instruction: the rows are the valid descriptors of
+// one slot, the columns are the vocabulary, a buffer of its own, and the work is fp4_nn_block<1, false, VOC_RT> (pgx_fp4_nn.h),
+// the body of k_knn_fp4 (k_knn.hip): the nearest word of a row is the k = 1 nearest column, ties to the smaller word.
 //
 // Training (k-majority) and the pair selection are integer kernels around it; every sum is an integer sum, so no order of
 // evaluation changes a bit of the result:
@@ -23,8 +20,7 @@
 //                      staged in LDS, the raw min-plus sums added up in int64; k_sel_norm: the normalised matrix, mirrored
 //   k_sel_topk         per slot: the key of its top_k-th candidate, found bit by bit on (score << 12 | 4095 - b) keys in LDS
 //   k_sel_count / _scan / _write / _fill   the selected pairs compacted in (a, b) order
-#include "pgx_fp4.h"
-#include "pgx_pairlist.h"
+#include "pgx_fp4_nn.h"
 #include "pgx_trackgraph.h"
 
 #include <climits>
@@ -38,175 +34,23 @@ constexpr int SEL_WC = 256;                     // words per staged histogram ch
 constexpr int SEL_PAD = SEL_WC + 2;             // row pitch in uint16: 129 dwords, so 16 rows fall into 16 different banks
 constexpr int SEL_MAXF = 4096;
 
-// the largest over each half (32 lanes) of a fully active wavefront, complete in lanes 16..31 and 48..63 (k_knn.hip's half_top<1>)
-__device__ __forceinline__ void voc_half_max(int &v1)
-{
-    v1 = max(v1, __builtin_amdgcn_update_dpp(INT_MIN, v1, 0xB1, 0xF, 0xF, false));
-    v1 = max(v1, __builtin_amdgcn_update_dpp(INT_MIN, v1, 0x4E, 0xF, 0xF, false));
-    v1 = max(v1, __builtin_amdgcn_update_dpp(INT_MIN, v1, 0x141, 0xF, 0xF, false));
-    v1 = max(v1, __builtin_amdgcn_update_dpp(INT_MIN, v1, 0x140, 0xF, 0xF, false));
-    v1 = max(v1, __builtin_amdgcn_update_dpp(INT_MIN, v1, 0x142, 0xA, 0xF, false));
-}
-
-// ---- the quantiser: 256-bit descriptors against V words on the FP4 matrix instruction ------------------------------------
-// out_word / out_dist [F][S]; entries i < clamp(counts[f], 0, S) are written.  Held to 240 registers and two waves per SIMD like
-// k_knn_fp4 (tests/test_vocab_codegen.py pins it on the code object).
+// ---- the quantiser: 256-bit descriptors against V >= 1 words on the FP4 matrix instruction -------------------------------
+// out_word / out_dist [F][S]; entries i < clamp(counts[f], 0, S) are written; out_dist may be null.  Held to 240 registers and
+// two waves per SIMD like k_knn_fp4 (tests/test_vocab_codegen.py pins it on the code object).
 __attribute__((amdgpu_num_vgpr(120))) __global__ __launch_bounds__(256, 2) void k_vocab_fp4(
     const uint32_t *__restrict__ desc, const int32_t *__restrict__ counts, int S, int nrb, int F, const uint32_t *__restrict__ vocab,
     int V, int32_t *__restrict__ out_word, int32_t *__restrict__ out_dist)
 {
-    __shared__ uint32_t rowtop[VOC_BM]; // running (distance << 20 | word) key of every row, min order; row owned by one lane
     int f, bx;
     pgx_xcd_map(blockIdx.x, nrb, F, f, bx);
     const int n1 = pgx_clamp_count(counts[f], S);
     const int rb = bx * VOC_BM;
     if (rb >= n1) return;
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, wv = tid >> 6, r = lane & 31, h = lane >> 5;
-    int km = (int)0x88888888, kc = 0x22222222;
-    asm volatile("" : "+v"(km), "+v"(kc)); // pin the two expansion constants in vector registers
-
-    // row operand: this lane's row of each 32-row tile, its 16-byte quarter-pair (words 4h .. 4h+3) expanded
-    const uint32_t *dA = desc + (size_t)f * S * 8;
-    int afr[VOC_RT][4][4];
-#pragma unroll
-    for (int t = 0; t < VOC_RT; t++) {
-        const int row = rb + wv * (VOC_RT * 32) + t * 32 + r;
-        const uint4 w = *reinterpret_cast<const uint4 *>(dA + (size_t)(row < n1 ? row : n1 - 1) * 8 + 4 * h);
-        expand_fp4(w.x, km, kc, afr[t][0]);
-        expand_fp4(w.y, km, kc, afr[t][1]);
-        expand_fp4(w.z, km, kc, afr[t][2]);
-        expand_fp4(w.w, km, kc, afr[t][3]);
-    }
-
-    for (int cb = 0; cb < V; cb += F4_CHUNK) {
-        const int ncol = V - cb < F4_CHUNK ? V - cb : F4_CHUNK, ntile = (ncol + 31) / 32;
-        const char *dB = reinterpret_cast<const char *>(vocab + (size_t)cb * 8);
-        auto fetch = [&](int ct) -> uint4 { // this lane's quarter-pair of word ct * 32 + r, clamped into the chunk
-            int c = (ct > 0 ? ct : 0) * 32 + r;
-            c = c < ncol ? c : ncol - 1;
-            return *reinterpret_cast<const uint4 *>(dB + (uint32_t)c * 32u + 16u * (uint32_t)h);
-        };
-        // C input of the LAST tile (the loop walks the tiles downwards; a tile step adds 128 on the matrix pipe, see k_ham_fp4):
-        // (127 - ct) << 7 | (127 - row position inside the wave's tile)
-        f32x16 cc;
-        int b1[VOC_RT][16];
-#pragma unroll
-        for (int g = 0; g < 16; g++) {
-            cc[g] = (float)(F4_BIAS + (((127 - (ntile - 1)) << 7) | (127 - ((g & 3) + 8 * (g >> 2) + 4 * h))));
-#pragma unroll
-            for (int t = 0; t < VOC_RT; t++) b1[t][g] = 0; // below every real value (raw bits of a float >= 2^23)
-        }
-        // one column tile; `slot` holds its raw words (loaded four tiles ago) and is refilled for tile ct - 4
-        auto step = [&](int ct, uint4 &slot, bool ragged) {
-            int b[4][4];
-            expand_fp4(slot.x, km, kc, b[0]);
-            expand_fp4(slot.y, km, kc, b[1]);
-            expand_fp4(slot.z, km, kc, b[2]);
-            expand_fp4(slot.w, km, kc, b[3]);
-            slot = fetch(ct - 4);
-            const i32x8 onesv = {kc, kc, kc, kc, 0, 0, 0, 0}; // the fp4 code of +1 in every nibble
-            const f32x16 ccn = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(onesv, onesv, cc, 4, 4, 0, 128, 0, 127);
-            const bool valid = !ragged || ct * 32 + r < ncol;
-#pragma unroll
-            for (int t = 0; t < VOC_RT; t++) {
-                f32x16 acc = cc;
-#pragma unroll
-                for (int s4 = 0; s4 < 4; s4++) {
-                    const i32x8 av = {afr[t][s4][0], afr[t][s4][1], afr[t][s4][2], afr[t][s4][3], 0, 0, 0, 0};
-                    const i32x8 bv = {b[s4][0], b[s4][1], b[s4][2], b[s4][3], 0, 0, 0, 0};
-                    acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(av, bv, acc, 4, 4, 0, F4_SCALE_A, 0, 127);
-                }
-#pragma unroll
-                for (int g = 0; g < 16; g++) {
-                    const int x = valid ? __float_as_int(acc[g]) : 0;
-                    b1[t][g] = max(b1[t][g], x);
-                }
-            }
-            cc = ccn;
-        };
-        uint4 w0 = fetch(ntile - 1), w1 = fetch(ntile - 2), w2 = fetch(ntile - 3), w3 = fetch(ntile - 4);
-        int ct = ntile - 1;
-        step(ct, w0, true); // the only tile that can be ragged
-        ct--;
-        for (; ct >= 3; ct -= 4) {
-            step(ct, w1, false);
-            step(ct - 1, w2, false);
-            step(ct - 2, w3, false);
-            step(ct - 3, w0, false);
-        }
-        if (ct >= 0) { step(ct, w1, false); ct--; }
-        if (ct >= 0) { step(ct, w2, false); ct--; }
-        if (ct >= 0) { step(ct, w3, false); ct--; }
-
-        // rebuild each value's column position (key = 8191 - position: the smaller word wins a tie), merge the 32 lanes of a
-        // row set; value g of a tile ends in lane 16 + g (h = 0) / 48 + g (h = 1)
-        int tid2 = threadIdx.x;
-        asm volatile("" : "+v"(tid2));
-        const int r2 = tid2 & 31;
-        uint32_t nk[VOC_RT];
-#pragma unroll
-        for (int t = 0; t < VOC_RT; t++) {
-            int mine = INT_MIN;
-#pragma unroll
-            for (int g = 0; g < 16; g++) {
-                const int x = b1[t][g], raw = x - F4_RAW0;
-                const int cpos = (127 - ((raw >> 7) & 127)) * 32 + r2;
-                int v = x == 0 ? INT_MIN : (raw & ~0x3FFF) | (8191 - cpos);
-                voc_half_max(v);
-                if (r2 == 16 + g) mine = v;
-            }
-            nk[t] = mine == INT_MIN ? PGX_KEY_NONE
-                                    : ((uint32_t)(128 - (mine >> 14)) << PGX_IDX_BITS) | (uint32_t)(cb + 8191 - (mine & 0x3FFF));
-        }
-        if (r2 >= 16) { // the lane owns row value g = r2 - 16 of each of its tiles (in LDS: no registers held across the chunks)
-            const int g = r2 - 16, h2 = (tid2 >> 5) & 1, wv2 = tid2 >> 6;
-#pragma unroll
-            for (int t = 0; t < VOC_RT; t++) {
-                const int iloc = wv2 * (VOC_RT * 32) + t * 32 + (g & 3) + 8 * (g >> 2) + 4 * h2;
-                const uint32_t k1 = cb ? rowtop[iloc] : PGX_KEY_NONE;
-                rowtop[iloc] = min(k1, nk[t]);
-            }
-        }
-    }
-
-    int tid3 = threadIdx.x;
-    asm volatile("" : "+v"(tid3));
-    const int r3 = tid3 & 31, h3 = (tid3 >> 5) & 1, wv3 = tid3 >> 6;
-    if (r3 >= 16) {
-        const int g = r3 - 16;
-#pragma unroll
-        for (int t = 0; t < VOC_RT; t++) {
-            const int iloc = wv3 * (VOC_RT * 32) + t * 32 + (g & 3) + 8 * (g >> 2) + 4 * h3, i = rb + iloc;
-            if (i < n1) {
-                const uint32_t k = rowtop[iloc];
-                out_word[(size_t)f * S + i] = (int32_t)(k & PGX_IDX_MASK);
-                if (out_dist) out_dist[(size_t)f * S + i] = (int32_t)(k >> PGX_IDX_BITS);
-            }
-        }
-    }
+    fp4_nn_block<1, false, VOC_RT>(desc + (size_t)f * S * 8, n1, vocab, 0, V, rb, out_word + (size_t)f * S,
+                                   out_dist ? out_dist + (size_t)f * S : nullptr, nullptr);
 }
 
 // ---- scans ------------------------------------------------------------------------------------------------------------------
-
-// exclusive prefix of one value per thread over the workgroup of 256 threads, in thread order, and the total; sh: 4 ints
-__device__ __forceinline__ int block_excl_scan(int v, int *sh, int &total)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += o;
-    }
-    if (lane == 63) sh[w] = inc;
-    __syncthreads();
-    int base = 0;
-    for (int k = 0; k < w; k++) base += sh[k];
-    total = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-    __syncthreads();
-    return base + inc - v;
-}
 
 // one workgroup of 256: out[i] = in[0] + .. + in[i - 1] for i <= n (out may be in); clamp_to >= 0 clamps the inputs to [0, clamp_to]
 __device__ __forceinline__ void scan_array(const int32_t *in, int32_t *out, int n, int clamp_to, int *sh)
@@ -217,7 +61,7 @@ __device__ __forceinline__ void scan_array(const int32_t *in, int32_t *out, int 
         int v = i < n ? in[i] : 0;
         if (clamp_to >= 0) v = pgx_clamp_count(v, clamp_to);
         int tot;
-        const int e = block_excl_scan(v, sh, tot);
+        const int e = block_excl_scan<int, 256>(v, sh, tot);
         if (i < n) out[i] = carry + e;
         carry += tot;
     }
@@ -553,7 +397,7 @@ __global__ __launch_bounds__(256) void k_sel_write(SelArgs a)
         int sc = -1;
         const int on = sb < a.F && sel_state(a, sa, sb, sc) != 0;
         int tot;
-        const int p = at + block_excl_scan(on, sh, tot);
+        const int p = at + block_excl_scan<int, 256>(on, sh, tot);
         if (on && p < a.max_pairs) {
             a.pairlist[2 * (size_t)p] = sa;
             a.pairlist[2 * (size_t)p + 1] = sb;

@@ -1667,6 +1667,13 @@ int vocab_args(pgx_ctx *c, int F, int stride, int V)
     return PGX_OK;
 }
 
+int train_args(pgx_ctx *c, int F, int stride, int V, int iters)
+{
+    if (const int rc = vocab_args(c, F, stride, V); rc != PGX_OK) return rc;
+    if (iters < 0 || iters > 64) return fail(c, PGX_E_BADARG, "iters must be in [0, 64]");
+    return PGX_OK;
+}
+
 int select_args(pgx_ctx *c, int F, int stride, int V, int weighting, int top_k, int window, int max_pairs)
 {
     if (const int rc = vocab_args(c, F, stride, V); rc != PGX_OK) return rc;
@@ -1693,8 +1700,7 @@ int pgx_vocab_train_dev(pgx_ctx *c, const uint32_t *d_desc, const int32_t *d_cou
 {
     if (!c || !d_desc || !d_counts || !d_vocab || !d_report) return c ? fail(c, PGX_E_BADARG, "null pointer") : PGX_E_BADARG;
     Lock l(c);
-    if (const int rc = vocab_args(c, F, stride, V); rc != PGX_OK) return rc;
-    if (iters < 0 || iters > 64) return fail(c, PGX_E_BADARG, "iters must be in [0, 64]");
+    if (const int rc = train_args(c, F, stride, V, iters); rc != PGX_OK) return rc;
     HIPCHK(c, c->ws_vocab.ensure(pgx_vocab_train_ws_bytes(F, stride, V)));
     pgx_launch_vocab_train(c, c->stream, d_desc, d_counts, F, stride, V, iters, seed, d_vocab, d_report, c->ws_vocab.p, c->d_status);
     HIPCHK(c, hipGetLastError());
@@ -1721,8 +1727,7 @@ int pgx_vocab_train(pgx_ctx *c, const uint32_t *desc, const int32_t *counts, int
 {
     if (!c || !desc || !counts || !vocab || !report) return c ? fail(c, PGX_E_BADARG, "null pointer") : PGX_E_BADARG;
     Lock l(c);
-    if (const int rc = vocab_args(c, F, stride, V); rc != PGX_OK) return rc;
-    if (iters < 0 || iters > 64) return fail(c, PGX_E_BADARG, "iters must be in [0, 64]");
+    if (const int rc = train_args(c, F, stride, V, iters); rc != PGX_OK) return rc;
     long long N = 0;
     for (int f = 0; f < F; f++) N += counts[f] < 0 ? 0 : (counts[f] > stride ? stride : counts[f]);
     if (N < V) return fail(c, PGX_E_BADARG, "fewer valid descriptors (%lld) than words (%d)", N, V);

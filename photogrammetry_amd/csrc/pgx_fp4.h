@@ -1,5 +1,6 @@
 // pgx_fp4.h -- the Hamming distance of 256-bit descriptors (8 words) on the matrix pipe: the arithmetic that k_ham_fp4 and
-// the residual-rows kernel (k_match_mfma.inc) and k_knn_fp4 (k_knn.hip) share.  Internal to libpgx.so; device code only.
+// the residual-rows kernel (k_match_mfma.inc) and the nearest-column body of k_knn_fp4 and k_vocab_fp4 (pgx_fp4_nn.h) share.
+// Internal to libpgx.so; device code only.
 //
 // hamming(a, b) = (K - a.b) / 2 for a, b in {-1,+1}^K (K = 256).  Every descriptor bit is expanded IN THE KERNEL
 // (registers only, never in HBM) to the fp4 code of -+1 and fed to v_mfma_scale_f32_32x32x64_f8f6f4; the C input carries
@@ -69,4 +70,18 @@ __device__ __forceinline__ int max16i(const i32x16 &v)
     const int m3 = max(max(v[9], v[10]), v[11]), m4 = max(max(v[12], v[13]), v[14]);
     const int n0 = max(max(m0, m1), m2), n1 = max(max(m3, m4), v[15]);
     return max(n0, n1);
+}
+
+// signed maximum over each half (32 lanes) of a fully active wavefront by DPP row operations: quads, 8, 16 lanes, then
+// row_bcast:15 carries rows 0 and 2 into rows 1 and 3.  Complete in lanes 16..31 and 48..63; no LDS crossbar traffic
+// (the publishing step of k_ham_fp4 made 160 ds_bpermute round trips per wavefront before).
+__device__ __forceinline__ int half_max_i32(int v)
+{
+    const int id = (int)0x80000000;
+    v = max(v, __builtin_amdgcn_update_dpp(id, v, 0xB1, 0xF, 0xF, false));  // quad_perm [1,0,3,2]
+    v = max(v, __builtin_amdgcn_update_dpp(id, v, 0x4E, 0xF, 0xF, false));  // quad_perm [2,3,0,1]
+    v = max(v, __builtin_amdgcn_update_dpp(id, v, 0x141, 0xF, 0xF, false)); // row_half_mirror
+    v = max(v, __builtin_amdgcn_update_dpp(id, v, 0x140, 0xF, 0xF, false)); // row_mirror
+    v = max(v, __builtin_amdgcn_update_dpp(id, v, 0x142, 0xA, 0xF, false)); // row_bcast:15 into rows 1, 3
+    return v;
 }

@@ -1,6 +1,7 @@
-// pgx_pairlist.h -- what the producers of per-pair neighbour lists share (k_knn.hip, k_guided.hip): the clamped counts of
-// an image pair, the write-out of (distance << 20 | index) keys, and the k in {1, 2} x column side on / off dispatch of
-// their launchers.  The column-key kernels themselves live in k_knn.hip (pgx_launch_colkeys, pgx_internal.h).
+// pgx_pairlist.h -- what the producers of per-pair neighbour lists share (k_knn.hip, k_guided.hip, and through pgx_fp4_nn.h
+// the quantiser of k_vocab.hip): the clamped counts of an image pair, the write-out of (distance << 20 | index) keys, and the
+// k in {1, 2} x column side on / off dispatch of their launchers.  The column-key kernels themselves live in k_knn.hip
+// (pgx_launch_colkeys, pgx_internal.h).
 // Internal to libpgx.so; DESIGN.md section 14b.
 #pragma once
 
@@ -32,14 +33,14 @@ __device__ __forceinline__ PairCounts pgx_pair_counts(const int32_t *__restrict_
     return {fa, fb, pgx_clamp_count(counts[fa], max_n), pgx_clamp_count(counts[fb], max_n)};
 }
 
-// a row's K smallest keys (k1 <= k2) as its K entries of idx / dist; no neighbour: (-1, PGX_DIST_NONE)
+// a row's K smallest keys (k1 <= k2) as its K entries of idx / dist; no neighbour: (-1, PGX_DIST_NONE).  dist may be null
 template <int K> __device__ __forceinline__ void pgx_store_keys(uint32_t k1, uint32_t k2, int32_t *idx, int32_t *dist)
 {
-    idx[0] = k1 == PGX_KEY_NONE ? -1 : (int32_t)(k1 & PGX_IDX_MASK);
-    dist[0] = k1 == PGX_KEY_NONE ? PGX_DIST_NONE : (int32_t)(k1 >> PGX_IDX_BITS);
-    if (K == 2) {
-        idx[1] = k2 == PGX_KEY_NONE ? -1 : (int32_t)(k2 & PGX_IDX_MASK);
-        dist[1] = k2 == PGX_KEY_NONE ? PGX_DIST_NONE : (int32_t)(k2 >> PGX_IDX_BITS);
+    const uint32_t k[2] = {k1, k2};
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+        idx[j] = k[j] == PGX_KEY_NONE ? -1 : (int32_t)(k[j] & PGX_IDX_MASK);
+        if (dist) dist[j] = k[j] == PGX_KEY_NONE ? PGX_DIST_NONE : (int32_t)(k[j] >> PGX_IDX_BITS);
     }
 }
 

@@ -1,6 +1,7 @@
 // pgx_trackgraph.h -- what every consumer of the track graph shares (k_triangulate.hip, k_bundle.hip, k_register.hip, k_consensus.hip):
 // the read-only view of the graph and the keypoints, its validation and walking on the device, the lane-group and
-// workgroup reductions (k_verify.hip uses those too), and the workspace carver of the launchers.  It brings pgx_ransac.h along,
+// workgroup reductions (k_verify.hip uses those too), the workgroup scan (k_tracks.hip, k_consensus.hip and k_vocab.hip compact
+// with it), and the workspace carver of the launchers.  It brings pgx_ransac.h along,
 // the sampler and the keys of the RANSAC stages among its consumers.  Internal to libpgx.so; DESIGN.md section 14a.
 #pragma once
 
@@ -132,6 +133,32 @@ __device__ __forceinline__ int block_sum_i(int c, int *sh)
     c = (sh[0] + sh[1]) + (sh[2] + sh[3]);
     __syncthreads();
     return c;
+}
+
+// The exclusive prefix of one value per thread over a workgroup of NT threads, in thread order (shuffle-up scan per wave, then the
+// waves in order), and the workgroup's total in every thread.  lds: NT / 64 values.  Two counts whose SUMS stay below 2^32 scan
+// as one 64-bit value (hi << 32 | lo), as k_tracks.hip's (tracks, nodes) do: no carry crosses.
+template <class T, int NT> __device__ __forceinline__ T block_excl_scan(T v, T *lds, T &total)
+{
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    T inc = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const T o = __shfl_up(inc, d, 64);
+        if (lane >= d) inc += o;
+    }
+    if (lane == 63) lds[w] = inc;
+    __syncthreads();
+    T base = 0, tot = 0;
+#pragma unroll
+    for (int i = 0; i < NT / 64; i++) {
+        const T s = lds[i];
+        if (i < w) base += s;
+        tot += s;
+    }
+    __syncthreads();
+    total = tot;
+    return base + inc - v;
 }
 
 // ---- cameras ----------------------------------------------------------------------------------------------------------
