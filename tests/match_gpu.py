@@ -104,12 +104,12 @@ def oracle_detect(frame, dmap, pairs, T, radius, cap, raw_cap=None):
     return kept, cref.brief(g, np.stack([kept["x"], kept["y"]], 1), pairs), n_raw
 
 
-def run_detect(engine, frames, cap, sentinel=-7):
+def run_detect(engine, frames, cap, sentinel=-7, words=8):
     """pgx_detect_batch_dev on host frames [F][H][W][4] with the engine's current parameters, nothing synchronised: the caller's
-    check_status does that -> device (d_kp [F][cap][4], d_desc [F][cap][8], d_counts [F], d_nraw [F]), sentinel-filled"""
+    check_status does that -> device (d_kp [F][cap][4], d_desc [F][cap][words], d_counts [F], d_nraw [F]), sentinel-filled"""
     F, H, W = frames.shape[:3]
     d_frames = torch.from_numpy(frames).to(DEV)
-    out = (torch.full((F, cap, 4), sentinel, **I32), torch.full((F, cap, 8), sentinel, **I32),
+    out = (torch.full((F, cap, 4), sentinel, **I32), torch.full((F, cap, words), sentinel, **I32),
            torch.full((F,), sentinel, **I32), torch.full((F,), sentinel, **I32))
     torch.cuda.synchronize()
     engine.detect_batch_dev(d_frames, F, W, H, *out, cap)

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import front_limits_cases as fc
 import photogrammetry_amd as pg
 import steered_ref as sr
 from match_gpu import DEV
@@ -145,6 +146,31 @@ def test_a_bright_pixel_along_each_direction_gets_that_bin(eng, B, R, reach):
         g[70 + dy, 80 + dx] = 1.0
         assert sr.bins(g, c, dirs, R).tolist() == [k]
         assert eng.orient(g, _kps(c)).tolist() == [k]
+
+
+@pytest.mark.parametrize("turns", [0, 1, 2, 3])
+def test_half_plane_at_full_scale(eng, turns):
+    """R = 31, B = 64 and a half plane of 1.0 through the keypoint: the largest |s_k| the rule can produce with make_steering's
+    directions, 1.2 * 2^44 against the 2^46 the packed key allows (asserted on the restatement); the bin and the descriptor still come out as restated"""
+    rot, dirs = _set(eng, _table(256), 64, 31)
+    c = np.array([(80, 70)], np.int32)
+    g = fc.half_plane(W, H, 80, 70, turns)
+    s = sr.scores(g, c, dirs, 31)[0]
+    assert 2 ** 44 < int(np.abs(s).max()) < 2 ** 46
+    _check_list(eng, g, c, rot, dirs, 31)
+    assert eng.orient(g, _kps(c)).tolist() == [int(s.argmax())]
+
+
+def test_orient_of_keypoints_outside_the_image(eng, image):
+    pts, _ = fc.outside_points(W, H)
+    for R, B in [(15, 32), (31, 64)]:
+        rot, dirs = _set(eng, _table(256), B, R)
+        eb = sr.bins(image, pts, dirs, R)
+        assert eng.orient(image, _kps(pts)).tolist() == eb.tolist()
+        dx = np.maximum(np.maximum(-pts[:, 0].astype(np.int64), pts[:, 0].astype(np.int64) - (W - 1)), 0)
+        dy = np.maximum(np.maximum(-pts[:, 1].astype(np.int64), pts[:, 1].astype(np.int64) - (H - 1)), 0)
+        beyond = (dx > R) | (dy > R)                         # no pixel of the disc inside the image: every s_k is 0, bin 0
+        assert beyond.sum() >= 6 and (eb[beyond] == 0).all() and len(np.unique(eb[~beyond])) >= 3
 
 
 def _detect_dev(eng, d_frames, F, w, h, cap, words, steered):
