@@ -11,16 +11,17 @@ import torch
 
 import photogrammetry_amd as pg
 import pyramid_ref as pr
-from match_gpu import DEV, I32, run_nn, upload
+from match_gpu import run_nn, upload
 from oracle import cref
 from photogrammetry_amd import synth
 from photogrammetry_amd._lib import PGX_E_BADARG, PGX_E_NOT_CONFIGURED
+from pyramid_gpu import buffers as _buffers, host as _host, run as _run
+from scale_limits_cases import SENT, check_lists as _check_lists
 
 pytestmark = pytest.mark.gpu
 W, H, F, T, RADIUS = 161, 140, 3, np.float32(0.1), 4
 STEPS = [69632, 78643, 92682, 100000, 131071, 131072]
 MODES = [(3, 92682), (8, 78643), (2, 131072)]
-SENT = -7
 
 
 @pytest.fixture(scope="module")
@@ -110,60 +111,6 @@ def _configure(eng, P, steered, n_levels, step, raw_cap=1 << 16, kp_cap=1 << 20)
     if steered:
         eng.set_brief_steering(rot, dirs, 15)
     eng.set_pyramid(n_levels, step)
-
-
-def _buffers(nf, cap, words, n_levels):
-    return dict(kp=torch.full((nf, cap, 4), SENT, **I32), desc=torch.full((nf, cap, words), SENT, **I32),
-                counts=torch.full((nf,), SENT, **I32), nraw=torch.full((nf,), SENT, **I32),
-                origin=torch.full((nf, cap, 3), SENT, **I32), stats=torch.full((nf, n_levels, 2), SENT, **I32),
-                bins=torch.full((nf, cap), SENT, **I32))
-
-
-def _host(b):
-    return {k: v.cpu().numpy() for k, v in b.items()}
-
-
-def _run(eng, frames, cap, words, n_levels, entry="pyramid", bins=False, expect=None):
-    """One of the batched entry points on host frames -> host arrays (sentinel-filled where nothing was written).  expect: an
-    exception class check_status must raise."""
-    nf, h, w = frames.shape[:3]
-    d_frames = torch.from_numpy(frames).to(DEV)
-    b = _buffers(nf, cap, words, n_levels)
-    torch.cuda.synchronize()   # torch's fills run on ITS stream; the engine's non-blocking stream does not order against it
-    if entry == "pyramid":
-        eng.detect_batch_pyramid_dev(d_frames, nf, w, h, b["kp"], b["desc"], b["counts"], b["nraw"], cap, b["origin"], b["stats"],
-                                     b["bins"] if bins else None)
-    elif entry == "plain":
-        eng.detect_batch_dev(d_frames, nf, w, h, b["kp"], b["desc"], b["counts"], b["nraw"], cap)
-    elif entry == "steered":
-        eng.detect_batch_steered_dev(d_frames, nf, w, h, b["kp"], b["desc"], b["counts"], b["nraw"], cap, b["bins"])
-    else:
-        assert entry == "sequence"
-        pl = torch.tensor([[0, 1]], **I32)
-        out = torch.full((1, cap, 3), SENT, **I32)
-        torch.cuda.synchronize()
-        eng.sequence_step_dev(d_frames, nf, nf, w, h, b["kp"], b["desc"], b["counts"], b["nraw"], cap, pl, 1, 1, out)
-    if expect is None:
-        eng.check_status()
-    else:
-        with pytest.raises(expect):
-            eng.check_status()
-    return _host(b)
-
-
-def _check_lists(got, ref, cap, origin=True, bins=False):
-    """The merged lists of every frame against the restatement's, every field exact; the rows behind a list untouched."""
-    for f, r in enumerate(ref):
-        n = r["count"]
-        assert int(got["counts"][f]) == n and int(got["nraw"][f]) == r["nraw"], (f, got["counts"][f], n, got["nraw"][f], r["nraw"])
-        assert (got["kp"][f, :n] == r["kp"].view(np.int32).reshape(-1, 4)).all(), f   # x, y, fast_score and the bits of value
-        assert (got["desc"][f, :n].view(np.uint32) == r["desc"]).all(), f
-        assert (got["kp"][f, n:] == SENT).all() and (got["desc"][f, n:] == SENT).all(), f
-        if origin:
-            assert (got["origin"][f, :n] == r["origin"]).all() and (got["origin"][f, n:] == SENT).all(), f
-            assert (got["stats"][f] == r["stats"]).all(), (f, got["stats"][f].tolist(), r["stats"].tolist())
-        if bins:
-            assert (got["bins"][f, :n] == r["bins"]).all() and (got["bins"][f, n:] == SENT).all(), f
 
 
 @pytest.mark.parametrize("steered", [False, True])

@@ -15,6 +15,7 @@ from oracle import cref
 from photogrammetry_amd import synth
 from photogrammetry_amd._lib import PGX_E_NOT_CONFIGURED
 from photogrammetry_amd.api import _ptr
+from scale_limits_cases import points as _points
 
 pytestmark = pytest.mark.gpu
 W, H = 161, 140
@@ -43,15 +44,6 @@ def _kps(xy):
 
 def _table(P, seed=21, reach=20):
     return np.random.default_rng(seed + P).integers(-reach, reach + 1, (P, 4)).astype(np.int32)
-
-
-def _points(w, h, R):
-    """The four corners, the edge mid-points, points R - 1, R and R + 1 from each border, interior points."""
-    pts = [(0, 0), (w - 1, 0), (0, h - 1), (w - 1, h - 1), (w // 2, 0), (w // 2, h - 1), (0, h // 2), (w - 1, h // 2)]
-    for d in (R - 1, R, R + 1):
-        pts += [(d, h // 2 + 3), (w - 1 - d, h // 2 - 3), (w // 2 + 3, d), (w // 2 - 3, h - 1 - d), (d, d), (w - 1 - d, h - 1 - d)]
-    pts += [(w // 2, h // 2), (40, 37), (101, 90), (77, 50), (33, 99)]
-    return np.array(pts, np.int32)
 
 
 def _set(eng, pairs, B, R):
