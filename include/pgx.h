@@ -79,7 +79,10 @@ int  pgx_check_status(pgx_ctx *ctx);
 enum { PGX_SRC_RGBA64 = 0, PGX_SRC_RGBA8 = 1 };
 int pgx_set_source_format(pgx_ctx *ctx, int format);
 /* DeWarpTransformStepFactory.Initialize (DeWarpTransformStepFactory.cs:26-31): the Matrix<Uv>
- * built by DeWarp.GetDistortionMatrix, as host int32 [H][W][2] = (U, V).  NULL = stage off. */
+ * built by DeWarp.GetDistortionMatrix, as host int32 [H][W][2] = (U, V).  NULL = stage off.
+ * Memory: the context keeps the table on the device (8 B per pixel) and, made from it once when it is installed (here or by
+ * pgx_set_dewarp_coeffs), its gather plan: one 32-bit source offset per pixel, 4 B per pixel more -- 12 B per pixel in all, 25 MB
+ * at 1920 x 1080.  The batched detect calls gather through the plan; it is rebuilt with every table and released with it. */
 int pgx_set_dewarp_map(pgx_ctx *ctx, const int32_t *uv, int W, int H);
 /* The same table built ON THE DEVICE from DeWarpOptions.DistortionCoefficients (DeWarp.GetDistortionMatrix,
  * DeWarp.cs:39-107; exactly 5 coefficients or PGX_E_BADARG like DeWarp.cs:46-48): no 8-66 MB upload, no host
@@ -269,7 +272,7 @@ int pgx_match_batch_dev(pgx_ctx *ctx, const uint32_t *d_desc, const int32_t *d_c
  * Memory: every context owns its workspaces.  The matcher's is about 5.5 MiB per image pair of a chunk at 4096 descriptors a
  * side (4 MiB of it the residual's byte matrix; allocations carry 25 % slack): 11 GB at the default chunk of 2048 pairs, so two
  * contexts in flight hold 22 GB plus their own output buffers -- sized for the 288 GB of an MI355X; pgx_set_match_chunk
- * lowers it. */
+ * lowers it.  Each context also holds its own dewarp table and gather plan (12 B per pixel, pgx_set_dewarp_map). */
 enum { PGX_STAGE_DETECT = 0, PGX_STAGE_MATCH_WIDE = 1, PGX_STAGE_MATCH_ROWS = 2, PGX_STAGE_MATCH_DONE = 3 };
 int pgx_wait_stage(pgx_ctx *ctx, pgx_ctx *other, int stage);
 /* The same wait, placed INSIDE ctx's next matcher call (pgx_match_batch_dev / pgx_sequence_step_dev; one shot): between its

@@ -9,7 +9,10 @@
 //   0,4,8,12) and the "fifth similar rejects" rule are both implied by "longest run >= 12",
 //   so score = longest circular run of zero bits of S if that is >= 12, else none.
 //
-// HBM-bound: 4 B/px grey read (+ 0.5 B/px of ballot planes written).  Three launches:
+// k_fast_planes is HBM-bound: 4 B/px grey read (+ 0.5 B/px of ballot planes written).  On the batch path's level 0 the grey
+// plane is never read back: k_dewarp_fast gathers the tile's source pixels through the map's gather plan (k_image.hip,
+// k_dewarp_plan), greys them into the LDS tile, stores the tile's interior for BRIEF and runs the same two passes
+// (fast_tile below: one body for both kernels).  Three launches:
 //   k_fast_planes   64x32-pixel tiles staged through LDS (halo 3).  Pass 1, one lane per pixel: the four
 //                   compass samples; pixels with at most one similar compass sample are queued in LDS.
 //                   Pass 2, one lane per QUEUED pixel (all lanes busy): the rest of the ring and the
@@ -19,52 +22,22 @@
 //                   k_fast_planes also writes, in (y, tx) order = raster order; n_raw[f]
 //   k_fast_compact  one thread per segment walks its set bits in x order -> raw_xy/raw_score
 #include "pgx_internal.h"
+#include "pgx_pixel.h"
 
 namespace {
 
 constexpr int TW = 64, TH = 32, HALO = 3;
 constexpr int LROWS = TH + 2 * HALO;  // 38
 constexpr int LSTRIDE = 72;           // >= 70, keeps rows 16-B aligned
+constexpr int NR = (LROWS + 3) / 4;   // 10: tile rows per wave
 
-__global__ __launch_bounds__(256) void k_fast_planes(const float *__restrict__ gray, int W, int H, float T,
-                                                     unsigned long long *__restrict__ seg, int ntx,
-                                                     uint32_t *__restrict__ segcnt)
+// The two FAST passes and the write-out of one staged tile (tx, ty) of frame f, for k_fast_planes and k_dewarp_fast alike.
+// The caller has cleared planes and *qcount and filled tile; both are ordered before pass 1 by the barrier in here.
+__device__ __forceinline__ void fast_tile(const float (*tile)[LSTRIDE], uint16_t *queue, unsigned (*planes)[3][2],
+                                          unsigned *qcount, int tx, int ty, int f, int W, int H, float T,
+                                          unsigned long long *__restrict__ seg, int ntx, uint32_t *__restrict__ segcnt)
 {
-    __shared__ float tile[LROWS][LSTRIDE];
-    __shared__ uint16_t queue[TW * TH];  // pixels that passed the compass test: row << 10 | column << 4 | compass bits
-    __shared__ unsigned planes[TH][3][2]; // score bit planes of the tile, one 64-bit word per row and plane
-    __shared__ unsigned qcount;
-    const int tx = blockIdx.x, ty = blockIdx.y, f = blockIdx.z;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const float *g = gray + (size_t)f * W * H;
-    const int x0 = tx * TW - HALO, y0 = ty * TH - HALO;
-    if (threadIdx.x < TH * 6) (&planes[0][0][0])[threadIdx.x] = 0u;
-    if (threadIdx.x == 0) qcount = 0u;
-
-    // each wave owns tile rows wv, wv+4, ...; all global loads are issued before the first LDS store
-    // (a load -> store loop serialises six HBM round trips per workgroup)
-    {
-        constexpr int NR = (LROWS + 3) / 4; // 10
-        float v[NR], hv[NR];
-#pragma unroll
-        for (int k = 0; k < NR; k++) {
-            const int r = wv + 4 * k;
-            const int gy = y0 + r;
-            const bool rowok = r < LROWS && gy >= 0 && gy < H;
-            const float *grow = g + (size_t)(rowok ? gy : 0) * W;
-            const int gx = x0 + lane, hx = x0 + 64 + lane;
-            v[k] = (rowok && gx >= 0 && gx < W) ? grow[gx] : 0.0f;
-            hv[k] = (rowok && lane < 2 * HALO && hx < W) ? grow[hx] : 0.0f;
-        }
-#pragma unroll
-        for (int k = 0; k < NR; k++) {
-            const int r = wv + 4 * k;
-            if (r < LROWS) {
-                tile[r][lane] = v[k];
-                if (lane < 2 * HALO) tile[r][64 + lane] = hv[k];
-            }
-        }
-    }
     __syncthreads();
 
     // Pass 1, every pixel: the four compass samples (:116-133).  A pixel goes on only with at most one of them
@@ -91,7 +64,7 @@ __global__ __launch_bounds__(256) void k_fast_planes(const float *__restrict__ g
         const unsigned long long pm = __ballot(pass);
         if (pm) {
             unsigned base = 0;
-            if (lane == 0) base = atomicAdd(&qcount, (unsigned)__popcll(pm));
+            if (lane == 0) base = atomicAdd(qcount, (unsigned)__popcll(pm));
             base = (unsigned)__shfl((int)base, 0);
             if (pass) queue[base + (unsigned)__popcll(pm & ((1ull << lane) - 1ull))] = (uint16_t)((ry << 10) | (lane << 4) | cb);
         }
@@ -100,7 +73,7 @@ __global__ __launch_bounds__(256) void k_fast_planes(const float *__restrict__ g
 
     // Pass 2, queued pixels only, all lanes busy: the other ring samples and the run-length rule; the
     // score bits go into the tile's ballot planes with LDS atomics (order-independent, so deterministic).
-    const unsigned nq = qcount;
+    const unsigned nq = *qcount;
     for (unsigned e = threadIdx.x; e < nq; e += 256) {
         const unsigned q = queue[e];
         const int ry = (int)(q >> 10), lx = (int)((q >> 4) & 63u);
@@ -163,6 +136,151 @@ __global__ __launch_bounds__(256) void k_fast_planes(const float *__restrict__ g
             segcnt[((size_t)f * H + y) * ntx + tx] = cnt; // dense copy of the counts: k_seg_scan turns it into offsets in place
         }
     }
+}
+
+__global__ __launch_bounds__(256) void k_fast_planes(const float *__restrict__ gray, int W, int H, float T,
+                                                     unsigned long long *__restrict__ seg, int ntx,
+                                                     uint32_t *__restrict__ segcnt)
+{
+    __shared__ float tile[LROWS][LSTRIDE];
+    __shared__ uint16_t queue[TW * TH];  // pixels that passed the compass test: row << 10 | column << 4 | compass bits
+    __shared__ unsigned planes[TH][3][2]; // score bit planes of the tile, one 64-bit word per row and plane
+    __shared__ unsigned qcount;
+    const int tx = blockIdx.x, ty = blockIdx.y, f = blockIdx.z;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const float *g = gray + (size_t)f * W * H;
+    const int x0 = tx * TW - HALO, y0 = ty * TH - HALO;
+    if (threadIdx.x < TH * 6) (&planes[0][0][0])[threadIdx.x] = 0u;
+    if (threadIdx.x == 0) qcount = 0u;
+
+    // each wave owns tile rows wv, wv+4, ...; all global loads are issued before the first LDS store
+    // (a load -> store loop serialises six HBM round trips per workgroup)
+    {
+        float v[NR], hv[NR];
+#pragma unroll
+        for (int k = 0; k < NR; k++) {
+            const int r = wv + 4 * k;
+            const int gy = y0 + r;
+            const bool rowok = r < LROWS && gy >= 0 && gy < H;
+            const float *grow = g + (size_t)(rowok ? gy : 0) * W;
+            const int gx = x0 + lane, hx = x0 + 64 + lane;
+            v[k] = (rowok && gx >= 0 && gx < W) ? grow[gx] : 0.0f;
+            hv[k] = (rowok && lane < 2 * HALO && hx < W) ? grow[hx] : 0.0f;
+        }
+#pragma unroll
+        for (int k = 0; k < NR; k++) {
+            const int r = wv + 4 * k;
+            if (r < LROWS) {
+                tile[r][lane] = v[k];
+                if (lane < 2 * HALO) tile[r][64 + lane] = hv[k];
+            }
+        }
+    }
+    fast_tile(tile, queue, planes, &qcount, tx, ty, f, W, H, T, seg, ntx, segcnt);
+}
+
+// ---- dewarp + grey + FAST in one tile kernel (the batch path's level 0) ---------------------------------------------
+// One workgroup owns one 64x32 tile of one frame.  Per wave the tile rows wv, wv + 4, ... (lane = column), and one position
+// of the 38 x 6 halo strip on the right per thread.  A position's source offset comes from the map's gather plan, or is the
+// pixel's own when no map is set; PGX_GATHER_OOB for a source outside the image and for tile positions outside it, which
+// read as grey of (0,0,0,0) = 0.0f: what k_dewarp_gray writes and k_fast_planes pads with.  The rows are gathered GB at a
+// time, plan words first and then the pixels (the register budget beside k_ham_fp4 is 32, and ten rows of pixels in flight
+// alone are 20), greyed by gray_of into the LDS tile, the tile's interior goes to the grey plane (BRIEF and the pyramid
+// read it), and fast_tile does the rest.  The offsets are not kept for a second frame: they would be live across
+// fast_tile's 30 registers.
+// Workgroup order: the grid is 1-D and the XCD that id % 8 selects (pgx_xcd_map's observation; speed only, any order is
+// correct) walks a contiguous run of (frame group, ty, tx, frame in group) with FG frames to the group: a tile's plan
+// words serve FG workgroups from one L2, and so do the halo pixels that two neighbouring tiles both gather.
+constexpr int FG = 8;  // frames that share a tile's plan words back to back
+constexpr int GB = NR / 2; // tile rows per wave gathered at a time
+constexpr int HALO_N = LROWS * 2 * HALO; // 228 halo positions, one per thread
+
+template <bool HAS_MAP, bool SRC8>
+__attribute__((amdgpu_num_vgpr(16))) // = 32 registers (the attribute counts half on gfx90a and later, as at k_ham_fp4)
+__global__ __launch_bounds__(256) void k_dewarp_fast(const typename SrcPix<SRC8>::type *__restrict__ rgba,
+                                                     const uint32_t *__restrict__ plan, const uint32_t *__restrict__ plan_oob,
+                                                     int W, int H, int F, float T, float *__restrict__ gray,
+                                                     unsigned long long *__restrict__ seg, int ntx, int nty,
+                                                     uint32_t *__restrict__ segcnt, int *status)
+{
+    using Px = typename SrcPix<SRC8>::type;
+    __shared__ float tile[LROWS][LSTRIDE];
+    __shared__ uint16_t queue[TW * TH];
+    __shared__ unsigned planes[TH][3][2];
+    __shared__ unsigned qcount;
+    if (HAS_MAP && blockIdx.x == 0 && threadIdx.x == 0 && *plan_oob) atomicOr(status, (int)PGX_ST_OOB_SOURCE);
+    const int nxy = ntx * nty, ntile = nxy * F;
+    const int per_xcd = (ntile + 7) >> 3;
+    const int id = (int)(blockIdx.x & 7u) * per_xcd + (int)(blockIdx.x >> 3);
+    if (id >= ntile) return; // block-uniform: the grid is 8 * per_xcd
+    int f, txy;
+    {
+        const int FF = (F / FG) * FG; // frames in full groups
+        if (id < nxy * FF) {
+            const int g = id / (nxy * FG), r = id - g * (nxy * FG);
+            txy = r / FG;
+            f = g * FG + r % FG;
+        } else {
+            const int r = id - nxy * FF, nl = F - FF;
+            txy = r / nl;
+            f = FF + r % nl;
+        }
+    }
+    const int ty = txy / ntx, tx = txy - ty * ntx;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int x0 = tx * TW - HALO, y0 = ty * TH - HALO;
+    const size_t npix = (size_t)W * H;
+    const Px *src = rgba + (size_t)f * npix;
+    float *gout = gray + (size_t)f * npix;
+    if (threadIdx.x < TH * 6) (&planes[0][0][0])[threadIdx.x] = 0u;
+    if (threadIdx.x == 0) qcount = 0u;
+
+    // this thread's positions: column gx of its wave's rows, and (hx, hy) of the halo strip
+    const int gx = x0 + lane;
+    const int hr = (int)threadIdx.x / (2 * HALO), hc = TW + (int)threadIdx.x % (2 * HALO);
+    const int hx = x0 + hc, hy = y0 + hr; // hx >= 0
+    const bool hin = threadIdx.x < HALO_N && hy >= 0 && hy < H && hx < W;
+    auto offset_of = [&](int k) { // row k of this wave
+        const int r = wv + 4 * k, gy = y0 + r;
+        uint32_t o = PGX_GATHER_OOB;
+        if (r < LROWS && gy >= 0 && gy < H && gx >= 0 && gx < W) {
+            o = (uint32_t)gy * (uint32_t)W + (uint32_t)gx;
+            if (HAS_MAP) o = plan[o];
+        }
+        return o;
+    };
+    auto pixel_at = [&](uint32_t o) { return o != PGX_GATHER_OOB ? load_px<SRC8>(src + o) : make_uint2(0u, 0u); };
+    auto put = [&](int k, uint2 p) { // grey into the tile, and into the grey plane when it is an interior pixel of the image
+        const int r = wv + 4 * k, gy = y0 + r;
+        if (r < LROWS) {
+            const float g = gray_of(p);
+            tile[r][lane] = g;
+            if (lane >= HALO && r >= HALO && r < TH + HALO && gx < W && gy < H) gout[(uint32_t)gy * (uint32_t)W + (uint32_t)gx] = g;
+        }
+    };
+    // four round trips: plan words and pixels of each half of the rows; the halo travels with the first half
+#pragma unroll
+    for (int k0 = 0; k0 < NR; k0 += GB) {
+        uint32_t off[GB], hoff = PGX_GATHER_OOB;
+        uint2 px[GB], hpx = make_uint2(0u, 0u);
+#pragma unroll
+        for (int j = 0; j < GB; j++) off[j] = offset_of(k0 + j);
+        if (k0 == 0 && hin) {
+            hoff = (uint32_t)hy * (uint32_t)W + (uint32_t)hx;
+            if (HAS_MAP) hoff = plan[hoff];
+        }
+#pragma unroll
+        for (int j = 0; j < GB; j++) px[j] = pixel_at(off[j]);
+        if (k0 == 0) hpx = pixel_at(hoff);
+#pragma unroll
+        for (int j = 0; j < GB; j++) put(k0 + j, px[j]);
+        if (k0 == 0 && threadIdx.x < HALO_N) {
+            const float g = gray_of(hpx);
+            tile[hr][hc] = g;
+            if (hc < TW + HALO && hr >= HALO && hr < TH + HALO && hin) gout[(uint32_t)hy * (uint32_t)W + (uint32_t)hx] = g;
+        }
+    }
+    fast_tile(tile, queue, planes, &qcount, tx, ty, f, W, H, T, seg, ntx, segcnt);
 }
 
 // exclusive scan of per-segment counts, one 1024-thread workgroup per frame
@@ -249,16 +367,31 @@ size_t pgx_fast_seg_count(int W, int H) { return (size_t)H * ((W + TW - 1) / TW)
 
 void pgx_launch_fast(hipStream_t s, const float *gray, int F, int W, int H, float T,
                      unsigned long long *seg, uint32_t *segoff, int32_t *n_raw, uint32_t *raw_xy,
-                     int32_t *raw_score, int raw_cap, int *status, bool compact)
+                     int32_t *raw_score, int raw_cap, int *status, bool compact, bool planes)
 {
     if (F <= 0 || W <= 0 || H <= 0) return;
     const int ntx = (W + TW - 1) / TW, nty = (H + TH - 1) / TH;
     const int nseg = H * ntx;
-    hipLaunchKernelGGL(k_fast_planes, dim3(ntx, nty, F), dim3(256), 0, s, gray, W, H, T, seg, ntx, segoff);
+    if (planes) // not behind pgx_launch_dewarp_fast: seg and the counts in segoff are there already
+        hipLaunchKernelGGL(k_fast_planes, dim3(ntx, nty, F), dim3(256), 0, s, gray, W, H, T, seg, ntx, segoff);
     hipLaunchKernelGGL(k_seg_scan, dim3(F), dim3(1024), 0, s, nseg, segoff, n_raw, raw_cap, status);
     // the raster-order raw lists; the fused path's champion NMS bins straight from the planes and writes the
     // list entries of the few points it keeps itself, so it skips this pass
     if (compact)
         hipLaunchKernelGGL(k_fast_compact, dim3((nseg + 255) / 256, F), dim3(256), 0, s, seg, segoff, H, ntx, raw_xy,
                            raw_score, raw_cap);
+}
+
+void pgx_launch_dewarp_fast(hipStream_t s, const void *rgba, int src8, const uint32_t *plan, const uint32_t *plan_oob, int F,
+                            int W, int H, float T, float *gray, unsigned long long *seg, uint32_t *segoff, int *status)
+{
+    if (F <= 0 || W <= 0 || H <= 0) return;
+    const int ntx = (W + TW - 1) / TW, nty = (H + TH - 1) / TH;
+    const int ntile = ntx * nty * F;
+    const dim3 grid((unsigned)(8 * ((ntile + 7) / 8))), block(256);
+#define PGX_DF(M, S8) hipLaunchKernelGGL((k_dewarp_fast<M, S8>), grid, block, 0, s, reinterpret_cast<const SrcPix<S8>::type *>(rgba), \
+                                         plan, plan_oob, W, H, F, T, gray, seg, ntx, nty, segoff, status)
+    if (src8) { if (plan) PGX_DF(true, true); else PGX_DF(false, true); }
+    else { if (plan) PGX_DF(true, false); else PGX_DF(false, false); }
+#undef PGX_DF
 }

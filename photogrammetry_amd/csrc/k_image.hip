@@ -3,36 +3,17 @@
 // Reference: ImageProcessing/DeWarp.cs:19-37 (integer gather through the Matrix<Uv> table) and
 // Images.Abstractions/Pixels/Grayscale.cs:19-23 (K = ((float)R + B + G) / (3*65535), float32).
 // HBM-bound: per pixel and frame 8 B gathered source (4 B for 8-bit sources, widened in registers) + 4 B grey, plus 8 B of map per pixel and group of
-// FB = 4 frames (the map is the same for every frame of a batch): 14 B/px/frame; FAST re-reads the 4 B.
+// FB = 4 frames (the map is the same for every frame of a batch): 14 B/px/frame.  This kernel runs where the dewarped RGBA is wanted,
+// in the stage entry points and in nothing else: the batch path's level 0 gathers, greys and runs FAST in one tile kernel
+// (k_fast.hip, k_dewarp_fast) off the gather plan that k_dewarp_plan below makes once per map.
 // Layout: every thread owns 4 consecutive output pixels of FB frames -> two 16-B map loads, then per
 // frame four 8-B gathers and one 16-B grey store.
 #include "pgx_internal.h"
+#include "pgx_pixel.h"
 
 namespace {
 
-__device__ __forceinline__ float gray_of(uint2 px)
-{
-    // px.x = R | G<<16, px.y = B | A<<16.  Sum order R, B, G as the C# writes it; the sum is
-    // exact (< 2^24) and the division is one correctly rounded float32 divide.
-    float r = (float)(px.x & 0xFFFFu), g = (float)(px.x >> 16), b = (float)(px.y & 0xFFFFu);
-    float s = __fadd_rn(__fadd_rn(r, b), g);
-    return __fdiv_rn(s, 196605.0f);
-}
-
 constexpr int FB = 4; // frames per thread: one map read serves FB frames
-
-// 8-bit sources (PGX_SRC_RGBA8): a channel c becomes c * 257 = c | c << 8, the scaling an 8-bit image gets when it is
-// loaded as Rgba64 (LocalImageReader.cs:22 via ImageSharp; 255 -> 65535).  Bytes r,g,b,a -> words r,r,g,g | b,b,a,a.
-__device__ __forceinline__ uint2 widen8(uint32_t v)
-{
-    return make_uint2(__builtin_amdgcn_perm(v, v, 0x01010000u), __builtin_amdgcn_perm(v, v, 0x03030202u));
-}
-
-template <bool SRC8> struct SrcPix { using type = uint2; };
-template <> struct SrcPix<true> { using type = uint32_t; };
-template <bool SRC8> __device__ __forceinline__ uint2 load_px(const typename SrcPix<SRC8>::type *p);
-template <> __device__ __forceinline__ uint2 load_px<false>(const uint2 *p) { return *p; }
-template <> __device__ __forceinline__ uint2 load_px<true>(const uint32_t *p) { return widen8(*p); }
 
 template <bool HAS_MAP, bool WRITE_RGBA, bool SRC8>
 __global__ __launch_bounds__(256) void k_dewarp_gray(const typename SrcPix<SRC8>::type *__restrict__ rgba,
@@ -123,6 +104,21 @@ __global__ __launch_bounds__(256) void k_dewarp_gray(const typename SrcPix<SRC8>
         }
     }
     if (HAS_MAP && oob) atomicOr(status, (int)PGX_ST_OOB_SOURCE);
+}
+
+// ---- the gather plan of a map, made once when the map is installed ------------------------------------------------------
+// One word per output pixel: sv * W + su after the unchecked (ushort) casts of the C#, PGX_GATHER_OOB where that source lies
+// outside W x H; *flag becomes 1 when any entry does.  The wrap, the bounds test and the multiply then cost nothing per frame.
+__global__ __launch_bounds__(256) void k_dewarp_plan(const int2 *__restrict__ map, int W, int H, uint32_t *__restrict__ plan,
+                                                     uint32_t *__restrict__ flag)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)W * H) return;
+    const int2 m = map[i];
+    const unsigned su = (unsigned)m.x & 0xFFFFu, sv = (unsigned)m.y & 0xFFFFu;
+    const bool ok = su < (unsigned)W && sv < (unsigned)H;
+    plan[i] = ok ? sv * (unsigned)W + su : PGX_GATHER_OOB;
+    if (!ok) atomicOr(flag, 1u);
 }
 
 // ---- DeWarp.GetDistortionMatrix on the device ------------------------------------------
@@ -223,6 +219,14 @@ void pgx_launch_dewarp_gray(hipStream_t s, const void *rgba, int src8, const int
         else { if (dw) PGX_DG(false, true, false); else PGX_DG(false, false, false); }
     }
 #undef PGX_DG
+}
+
+void pgx_launch_dewarp_plan(hipStream_t s, const int32_t *map_uv, int W, int H, uint32_t *plan, uint32_t *flag)
+{
+    const size_t npix = (size_t)W * H;
+    (void)hipMemsetAsync(flag, 0, 4, s);
+    hipLaunchKernelGGL(k_dewarp_plan, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const int2 *>(map_uv), W,
+                       H, plan, flag);
 }
 
 void pgx_launch_dewarp_map(hipStream_t s, int W, int H, const double *k, int32_t *map_uv, int *status)

@@ -209,12 +209,20 @@ void enqueue_from_gray(pgx_ctx *c, const float *gray, int F, int W, int H, int k
 {
     const int raw_cap = c->raw_cap;
     const size_t nms_stride = pgx_nms_ws_bytes(W, H, c->radius, raw_cap, true);
+    // level 0 of the batch path (enqueue_detect_bins sets fuse_rgba for that one call): gray is not there yet, the fused
+    // kernel makes it together with the planes
+    const void *rgba = c->fuse_rgba;
+    c->fuse_rgba = nullptr;
     {
         ProfScope ps(c, "fast");
+        if (rgba)
+            pgx_launch_dewarp_fast(c->stream, rgba, c->src8, c->map_set ? c->d_gather.as<uint32_t>() : nullptr,
+                                   c->map_set ? c->gather_flag() : nullptr, F, W, H, c->threshold, const_cast<float *>(gray),
+                                   c->ws_seg.as<unsigned long long>(), c->ws_segoff.as<uint32_t>(), c->d_status);
         pgx_launch_fast(c->stream, gray, F, W, H, c->threshold, c->ws_seg.as<unsigned long long>(),
                         c->ws_segoff.as<uint32_t>(), d_nraw, c->ws_rawxy.as<uint32_t>(),
                         c->ws_rawscore.as<int32_t>(), raw_cap, c->d_status,
-                        !pgx_nms_fills_raw_lists(W, H, c->radius, raw_cap));
+                        !pgx_nms_fills_raw_lists(W, H, c->radius, raw_cap), rgba == nullptr);
     }
     {
         ProfScope ps(c, "nms");
@@ -246,12 +254,10 @@ int enqueue_detect_bins(pgx_ctx *c, const uint16_t *d_rgba, int F, int W, int H,
     const bool kp_soft = c->kp_cap <= cap;
     const int kp_eff = kp_soft ? c->kp_cap : cap;
 
+    // No dewarped RGBA is wanted here, so level 0 gathers, greys and runs FAST in one tile kernel (k_dewarp_fast, inside the
+    // "fast" group of enqueue_from_gray): the grey plane is written for BRIEF and the pyramid and never read back by FAST
     float *gray = c->ws_gray.as<float>();
-    {
-        ProfScope ps(c, "dewarp_gray");
-        pgx_launch_dewarp_gray(c->stream, d_rgba, c->src8, c->map_set ? c->d_map.as<int32_t>() : nullptr, F, W, H, gray,
-                               nullptr, c->d_status);
-    }
+    c->fuse_rgba = d_rgba;
     if (c->pyr_levels <= 1) {
         enqueue_from_gray(c, gray, F, W, H, kp_eff, kp_soft, d_kp, d_desc, d_counts, d_nraw, cap, d_bins);
     } else {
@@ -455,7 +461,7 @@ void pgx_ctx_destroy(pgx_ctx *c)
     for (auto &kv : c->prof)
         for (auto &ev : kv.second.pending) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
     for (hipEvent_t ev : c->ev_pool) (void)hipEventDestroy(ev);
-    DevBuf *bufs[] = {&c->d_pairs, &c->d_plan, &c->d_steer_pairs, &c->d_steer_plans, &c->d_steer_dirs, &c->d_map, &c->ws_gray, &c->ws_seg, &c->ws_segoff, &c->ws_nraw, &c->ws_rawxy,
+    DevBuf *bufs[] = {&c->d_pairs, &c->d_plan, &c->d_steer_pairs, &c->d_steer_plans, &c->d_steer_dirs, &c->d_map, &c->d_gather, &c->ws_gray, &c->ws_seg, &c->ws_segoff, &c->ws_nraw, &c->ws_rawxy,
                       &c->ws_rawscore, &c->ws_nms, &c->ws_order, &c->ws_nkept, &c->st_a, &c->st_b, &c->st_c,
                       &c->st_d, &c->st_e, &c->st_f, &c->ws_pose, &c->ws_tracks, &c->ws_tracks_split, &c->ws_agree, &c->ws_matchn[0], &c->ws_matchn[1], &c->ws_matchn[2], &c->ws_knn, &c->ws_guided, &c->ws_tri, &c->ws_ba, &c->ws_reg, &c->ws_ver, &c->ws_init, &c->ws_cns, &c->ws_vocab,
                       &c->ws_pyr_a, &c->ws_pyr_b, &c->ws_pyr_kp, &c->ws_pyr_desc, &c->ws_pyr_bins, &c->ws_pyr_cnt};
@@ -511,13 +517,21 @@ int pgx_set_dewarp_map(pgx_ctx *c, const int32_t *uv, int W, int H)
     if (!c) return PGX_E_BADARG;
     Lock l(c);
     c->cfg_epoch++;
-    if (!uv) { c->map_set = false; c->mapW = c->mapH = 0; return PGX_OK; }
+    if (!uv) {
+        HIPCHK(c, hipStreamSynchronize(c->stream)); // a chain in flight may still read the plan
+        c->d_gather.release();
+        c->map_set = false; c->mapW = c->mapH = 0;
+        return PGX_OK;
+    }
     if (dims_ok(c, W, H, "map dimensions must fit ushort") != PGX_OK) return PGX_E_BADARG;
     const size_t bytes = (size_t)W * H * 8;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, c->d_map.ensure(bytes + 32));
+    HIPCHK(c, c->d_gather.ensure(bytes / 2 + 4));
     HIPCHK(c, hipMemcpy(c->d_map.p, uv, bytes, hipMemcpyHostToDevice));
     c->mapW = W; c->mapH = H; c->map_set = true;
+    pgx_launch_dewarp_plan(c->stream, c->d_map.as<int32_t>(), W, H, c->d_gather.as<uint32_t>(), c->gather_flag());
+    HIPCHK(c, hipGetLastError());
     return PGX_OK;
 }
 
@@ -531,9 +545,11 @@ int pgx_set_dewarp_coeffs(pgx_ctx *c, int W, int H, const double *coeffs, int nc
     const size_t bytes = (size_t)W * H * 8;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, c->d_map.ensure(bytes + 32));
+    HIPCHK(c, c->d_gather.ensure(bytes / 2 + 4));
     pgx_launch_dewarp_map(c->stream, W, H, coeffs, c->d_map.as<int32_t>(), c->d_status);
-    HIPCHK(c, hipGetLastError());
     c->mapW = W; c->mapH = H; c->map_set = true;
+    pgx_launch_dewarp_plan(c->stream, c->d_map.as<int32_t>(), W, H, c->d_gather.as<uint32_t>(), c->gather_flag());
+    HIPCHK(c, hipGetLastError());
     return sync_status(c);
 }
 

@@ -120,6 +120,11 @@ struct pgx_ctx {
     int mapW = 0, mapH = 0;
     bool map_set = false;
     DevBuf d_map;
+    // the map's gather plan, rebuilt behind every map that is installed and released when the map is cleared: W * H source
+    // offsets (4 B/px beside the map's 8), then one word "some entry lies outside the image" (gather_flag)
+    DevBuf d_gather;
+    uint32_t *gather_flag() const { return d_gather.as<uint32_t>() + (size_t)mapW * mapH; }
+    const void *fuse_rgba = nullptr; // enqueue_detect_bins -> its level-0 enqueue_from_gray: the source frames (one call)
     int raw_cap = 1 << 17;
     int kp_cap = 1 << PGX_IDX_BITS; // soft survivor limit of the fused path (pgx_set_capacity); default: none
     // image pairs per matcher workspace chunk (pgx_set_match_chunk).  The per-pair finish is one workgroup per image pair, and
@@ -248,6 +253,8 @@ struct ProfScope {
 void pgx_launch_dewarp_gray(hipStream_t s, const void *rgba, int src8, const int32_t *map_uv, int F, int W, int H,
                             float *gray, uint16_t *dewarped, int *status);
 void pgx_launch_dewarp_map(hipStream_t s, int W, int H, const double *k /*[5]*/, int32_t *map_uv, int *status);
+// the map's gather plan: plan[W * H] source offsets (PGX_GATHER_OOB outside the image), *flag = 1 when any entry is outside
+void pgx_launch_dewarp_plan(hipStream_t s, const int32_t *map_uv, int W, int H, uint32_t *plan, uint32_t *flag);
 
 // k_fast.hip
 size_t pgx_fast_seg_count(int W, int H);   // segments per frame
@@ -255,7 +262,13 @@ void pgx_launch_fast(hipStream_t s, const float *gray, int F, int W, int H, floa
                      unsigned long long *seg /*[F][nseg][4]*/, uint32_t *segoff /*[F][nseg]*/,
                      int32_t *n_raw /*[F]*/, uint32_t *raw_xy /*[F][raw_cap]*/,
                      int32_t *raw_score /*[F][raw_cap]*/, int raw_cap, int *status,
-                     bool compact = true /* false: planes and ranks only, raw_xy/raw_score are not written */);
+                     bool compact = true /* false: planes and ranks only, raw_xy/raw_score are not written */,
+                     bool planes = true /* false: pgx_launch_dewarp_fast has written seg and the counts in segoff; gray is not read */);
+// dewarp + grey + the FAST planes of F frames in one tile kernel: gray, seg and the counts in segoff as pgx_launch_dewarp_gray
+// and pgx_launch_fast's first kernel leave them.  plan / plan_oob: pgx_launch_dewarp_plan's, or nullptr with no map;
+// PGX_ST_OOB_SOURCE is raised when *plan_oob is set
+void pgx_launch_dewarp_fast(hipStream_t s, const void *rgba, int src8, const uint32_t *plan, const uint32_t *plan_oob, int F,
+                            int W, int H, float T, float *gray, unsigned long long *seg, uint32_t *segoff, int *status);
 
 // k_nms.hip
 size_t pgx_nms_ws_bytes(int W, int H, int radius, int n_cap, bool planes);
