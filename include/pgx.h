@@ -968,6 +968,92 @@ int pgx_select_pairs(pgx_ctx *ctx, const uint32_t *desc, const int32_t *counts, 
                      int V, int weighting, int top_k, int window, int min_score, int max_pairs, int32_t *pairlist,
                      int32_t *pair_score, int32_t *scores, int32_t *summary);
 
+/* ---- dense depth maps by census plane sweep, and a cross-view filter ------------------ */
+/* The sparse stages end with one point per track.  These three calls make a surface-dense cloud from the same frames and the
+ * cameras those stages estimated: grey images, one depth map per reference frame, and the pixels that other maps confirm as a
+ * point list.  Integer rules wherever a rule can be an integer, float64 in a stated order elsewhere (the library is built
+ * without contraction): bit-identical to a numpy restatement (tests/depth_ref.py).  Not in the C# reference.  k_depth.hip.
+ *
+ * pgx_gray_batch_dev: d_gray [F][H][W] float32 = the grey image of every frame of d_rgba [F][H][W] (the context's source
+ * format), gathered through the context's dewarp map when one is set (then W x H must be the map's: PGX_E_DIM_MISMATCH).
+ * Per frame the bits of pgx_gray (of pgx_gray on pgx_dewarp's output, with a map).  Asynchronous. */
+int pgx_gray_batch_dev(pgx_ctx *ctx, const uint16_t *d_rgba, int F, int W, int H, float *d_gray /* [F][H][W] */);
+/* pgx_depth_maps_dev.  Frames, slots, d_frame_ids and d_P as for pgx_triangulate_tracks_dev: d_gray holds F SLOTS, slot s shows
+ * frame d_frame_ids[s] (NULL: identity, n_frames = F; of two slots naming one frame the lower is used), d_P [n_frames][12] by
+ * frame NUMBER, u = column, v = row; M = P[:, 0:3], p4 = P[:, 3], m3 = M's third row, adj(M) the adjugate (cofactors
+ * transposed, each cofactor a b - c d), det M = (m00 adj00 + m01 adj10) + m02 adj20.  A camera is UNKNOWN if an entry is not
+ * finite or det M == 0.  Row r of d_views [R][1 + S] names the reference frame, then S source frames; -1 = no source there.
+ * d_range [R][2] = (z_near, z_far).  Everything is read on the device: the call can follow pgx_bundle_adjust_dev's P_out on the
+ * same stream.  a . b + c . d + e . f below always means (a b + c d) + e f.
+ *   1 census  per slot and pixel, the 9 wide x 7 high window in raster order without the centre: bit t (t = 0 .. 61) =
+ *             g(neighbour) < g(centre) in float32 (a NaN on either side gives 0), neighbour coordinates clamped to the image.
+ *   2 planes  for k < D: iz_k = 1/z_far + (k / (D - 1)) (1/z_near - 1/z_far); w_k = (sign(det M_r) ||m3_r||) (1 / iz_k), with
+ *             ||m3|| = sqrt(m20^2 + m21^2 + m22^2).  A reference with an unknown camera, a range that is not 0 < z_near < z_far
+ *             finite, or a frame that no slot shows is flagged NOCAMERA at every pixel.
+ *   3 warp    per (r, s): A_ij = (M_s[i] . adj(M_r)[:, j]) / det M_r, b_i = p4_s[i] - (A[i] . p4_r).  A source that is -1, has an
+ *             unknown camera or no slot is invalid everywhere.
+ *   4 cost    of reference pixel (u, v), plane k, source s: y_i = (A_i0 u + A_i1 v) + A_i2, q_i = w_k y_i + b_i.  The source is
+ *             valid iff q_2 > 0 and 0 <= q_0 / q_2 + 0.5 < W and 0 <= q_1 / q_2 + 0.5 < H (IEEE float64, correctly rounded
+ *             division; NaN fails); the source pixel is the floor of those two values.  cost = popcount(census_r(u, v) xor
+ *             census_s(pixel)) where valid, 31 where not.  raw(u, v, k) = the sum over the S sources, nvalid(u, v, k) = the
+ *             number of valid ones.
+ *   5 box     agg(u, v, k) = the sum of raw over the (2 agg_radius + 1)^2 box, box coordinates clamped to the image.
+ *   6 choice  k* = the argmin of agg over k, ties to the smallest k.  Flags (PGX_DEP_*, bits): NOCAMERA (step 2); NOVIEWS
+ *             nvalid(u, v, k*) < min_views; EDGE k* is 0 or D - 1; HIGHCOST agg(k*) > max_cost.
+ *   7 sub-plane position, in integers: n = agg(k* - 1) - agg(k* + 1), den = agg(k* - 1) - 2 agg(k*) + agg(k* + 1) >= 0;
+ *             off = 0 if den == 0, else sign(n) ((|n| 128) / den) truncated (|off| <= 128); kq8 = 256 k* + off;
+ *             depth = 1 / (1/z_far + ((kq8 / 256.0) / (D - 1)) (1/z_near - 1/z_far)).  With any flag set kq8 = -1, depth = NaN.
+ * Outputs: d_kq8, d_flags int32 and d_depth float64 [R][H][W]; d_cost [R][H][W] int32 or NULL = agg(k*), written unless
+ * NOCAMERA; d_warp [R][S][12] float64 or NULL = A row-major then b (NaN for an invalid source); d_planes [R][D] float64 or
+ * NULL = w_k (NaN for a NOCAMERA reference); d_summary [8] int32: pixels processed, pixels with flags 0, pixels carrying
+ * NOCAMERA, NOVIEWS, EDGE, HIGHCOST, reference maps with NOCAMERA, 0.
+ * Returned at once (PGX_E_BADARG): D outside [3, 256], S outside [1, 8], agg_radius outside [0, 3], min_views outside [1, S],
+ * max_cost < 0, R outside [1, 65535], F outside [1, 65535], W or H outside [1, 65535], max(F, R) W H > 2^30, n_frames != F
+ * without d_frame_ids, null required pointers.  Workspace: 8 bytes per pixel and slot.
+ * Results depend on the inputs only: the same bits from run to run, for any slot layout of the same frames, and from the host
+ * form.  Asynchronous on the context's stream. */
+#define PGX_DEP_NOCAMERA 1
+#define PGX_DEP_NOVIEWS  2
+#define PGX_DEP_EDGE     4
+#define PGX_DEP_HIGHCOST 8
+int pgx_depth_maps_dev(pgx_ctx *ctx, const float *d_gray /* [F][H][W] */, int F, int W, int H,
+                       const int32_t *d_frame_ids /* [F] or NULL */, int n_frames, const double *d_P /* [n_frames][12] */,
+                       const int32_t *d_views /* [R][1 + S] */, int R, int S, const double *d_range /* [R][2] = (z_near, z_far) */,
+                       int D, int agg_radius, int min_views, int max_cost,
+                       int32_t *d_kq8 /* [R][H][W] */, double *d_depth /* [R][H][W] */, int32_t *d_cost /* [R][H][W] or NULL */,
+                       int32_t *d_flags /* [R][H][W] */, double *d_warp /* [R][S][12] or NULL */, double *d_planes /* [R][D] or NULL */,
+                       int32_t *d_summary /* [8] */);
+/* pgx_depth_fuse_dev: the pixels of the maps that other maps of the same call confirm, as a point list.  d_depth, d_views as
+ * above (the frames of d_views are frame NUMBERS into d_P; no slots here: map r is row r).  A map whose reference frame is
+ * outside [0, n_frames) or has an unknown camera is skipped.  For pixel (u, v) of map r with finite depth z:
+ *   w = (sign(det M_r) ||m3_r||) z; t = (w u - p4_r[0], w v - p4_r[1], w - p4_r[2]); X_i = (adj(M_r)[i] . t) / det M_r.
+ *   For each source j of r's row, in the row's order, that is the reference of a row of this call with a known camera (the
+ *   first such row; -1 and other frames are passed over; a frame named twice counts twice; r's own frame counts if it is
+ *   named): q_i = (P_j[i][0:3] . X) + P_j[i][3]; pixel validity and the nearest pixel as in rule 4 above;
+ *   d = (sign(det M_j) q_2) / ||m3_j||; z_j = the depth of map j at that pixel; the view agrees iff z_j is finite and
+ *   |d - z_j| <= rel_tol z_j.
+ *   agree = the number of agreeing views; the pixel is kept iff agree >= min_agree.
+ * The kept pixels in (r, v, u) order: d_xyz [max_points][3] float64 = X, d_src [max_points][2] int32 = (r, v W + u).  More than
+ * max_points kept: the first max_points are written and pgx_check_status reports PGX_E_CAPACITY.  d_agree [R][H][W] int32 or
+ * NULL = agree, -1 for a pixel without a depth or of a skipped map.  d_summary [4] int32: pixels kept (the full count), pixels
+ * with a depth, those of them with at least one source of the kind above that they project into validly, maps skipped.
+ * Returned at once (PGX_E_BADARG): S outside [1, 8], R outside [1, 65535], R W H > 2^30, rel_tol negative or not finite,
+ * min_agree or max_points < 0, null required pointers (d_xyz and d_src may be NULL with max_points == 0).
+ * The same bit-identity properties as the depth maps.  Asynchronous on the context's stream. */
+int pgx_depth_fuse_dev(pgx_ctx *ctx, const double *d_depth /* [R][H][W] */, const int32_t *d_views /* [R][1 + S] */, int R, int S,
+                       int W, int H, int n_frames, const double *d_P, double rel_tol, int min_agree, int max_points,
+                       double *d_xyz /* [max_points][3] */, int32_t *d_src /* [max_points][2] = (r, v * W + u) */,
+                       int32_t *d_agree /* [R][H][W] or NULL */, int32_t *d_summary /* [4] */);
+/* Host forms: host arrays in the layouts above, the same kernels; they return when the results are in the caller's buffers.
+ * gray [n_frames][H][W] by frame number (no slots).  cost, warp, planes and agree may be NULL.  R == 0: the summary is zeroed and
+ * nothing else is written.  pgx_depth_fuse writes min(summary[0], max_points) rows of xyz and src. */
+int pgx_depth_maps(pgx_ctx *ctx, const float *gray, int n_frames, int W, int H, const double *P, const int32_t *views, int R, int S,
+                   const double *range, int D, int agg_radius, int min_views, int max_cost, int32_t *kq8, double *depth,
+                   int32_t *cost, int32_t *flags, double *warp, double *planes, int32_t *summary);
+int pgx_depth_fuse(pgx_ctx *ctx, const double *depth, const int32_t *views, int R, int S, int W, int H, int n_frames,
+                   const double *P, double rel_tol, int min_agree, int max_points, double *xyz, int32_t *src, int32_t *agree,
+                   int32_t *summary);
+
 /* ---- measurement hooks (bench.py) ---------------------------------------------------- */
 /* When on, the named hot kernels are bracketed by HIP events on the launch stream. */
 int pgx_profile_enable(pgx_ctx *ctx, int on);

@@ -26,6 +26,7 @@ internal static unsafe class PgxNative
     public const int RegBadK = 1, RegFewPoints = 2, RegNoSolution = 4, RegFewInliers = 8;   // PGX_REG_* (0 = registered)
     public const int CnsFewViews = 1, CnsLowParallax = 2, CnsNoConsensus = 4, CnsShort = 8;   // PGX_CNS_* (0 = a consensus, kept)
     public const int VerFewMatches = 1, VerNoModel = 2, VerFewInliers = 4;                 // PGX_VER_* (0 = accepted)
+    public const int DepNoCamera = 1, DepNoViews = 2, DepEdge = 4, DepHighCost = 8;       // PGX_DEP_* (0 = a depth)
     public const int InitSkipped = 1, InitBadInput = 2, InitDegenerate = 4, InitFewFront = 8, InitFewPoints = 16;   // PGX_INIT_* (0 = eligible)
 
     // Exports of include/pgx.h that this binding deliberately leaves out (tests/test_csharp_binding.py holds the list to the
@@ -237,6 +238,27 @@ internal static unsafe class PgxNative
                                                                int v, int weighting, int topK, int window, int minScore,
                                                                int maxPairs, int* pairlist, int* pairScore, int* scores,
                                                                int* summary);
+
+    // dense depth maps by census plane sweep and the cross-view filter (not in the reference): dGray [f][h][w] float32 by slot,
+    // dP [nFrames][12] float64, dViews [r][1 + s] (reference frame, then sources; -1 = none), dRange [r][2] = (zNear, zFar);
+    // dKq8, dFlags, dCost (or null) [r][h][w] int32, dDepth [r][h][w] float64, dWarp [r][s][12] and dPlanes [r][d] or null,
+    // dSummary [8]; the filter writes dXyz [maxPoints][3], dSrc [maxPoints][2] = (r, v w + u), dAgree [r][h][w] or null,
+    // dSummary [4].  The host forms take host arrays in the same layouts (gray [nFrames][h][w] by frame number).
+    [DllImport(Lib)] public static extern int pgx_gray_batch_dev(IntPtr ctx, void* dRgba, int f, int w, int h, void* dGray);
+    [DllImport(Lib)] public static extern int pgx_depth_maps_dev(IntPtr ctx, void* dGray, int f, int w, int h, void* dFrameIds, int nFrames,
+                                                                 void* dP, void* dViews, int r, int s, void* dRange, int d,
+                                                                 int aggRadius, int minViews, int maxCost, void* dKq8, void* dDepth,
+                                                                 void* dCost, void* dFlags, void* dWarp, void* dPlanes, void* dSummary);
+    [DllImport(Lib)] public static extern int pgx_depth_fuse_dev(IntPtr ctx, void* dDepth, void* dViews, int r, int s, int w, int h,
+                                                                 int nFrames, void* dP, double relTol, int minAgree, int maxPoints,
+                                                                 void* dXyz, void* dSrc, void* dAgree, void* dSummary);
+    [DllImport(Lib)] public static extern int pgx_depth_maps(IntPtr ctx, float* gray, int nFrames, int w, int h, double* p, int* views,
+                                                             int r, int s, double* range, int d, int aggRadius, int minViews,
+                                                             int maxCost, int* kq8, double* depth, int* cost, int* flags, double* warp,
+                                                             double* planes, int* summary);
+    [DllImport(Lib)] public static extern int pgx_depth_fuse(IntPtr ctx, double* depth, int* views, int r, int s, int w, int h,
+                                                             int nFrames, double* p, double relTol, int minAgree, int maxPoints,
+                                                             double* xyz, int* src, int* agree, int* summary);
 
     /// <summary>Maps a status code back to the exception type the managed implementation throws.</summary>
     public static void Check(IntPtr ctx, int rc)

@@ -701,6 +701,74 @@ class Engine:
         n = min(int(summary[0]), cap)
         return dict(pairs=pl[:n], pair_score=ps[:n], scores=sc, summary=summary)
 
+    # -- dense depth maps by census plane sweep and the cross-view filter (pgx_gray_batch_dev, pgx_depth_*) --------
+    def gray_batch_dev(self, d_rgba, F, W, H, d_gray):
+        """pgx_gray_batch_dev: d_gray [F][H][W] float32 from d_rgba [F][H][W] in the context's source format, through the
+        context's dewarp map when one is set.  No sync."""
+        self._chk(self._L.pgx_gray_batch_dev(self._h, _dptr(d_rgba), int(F), int(W), int(H), _dptr(d_gray)))
+
+    def depth_maps_dev(self, d_gray, F, W, H, n_frames, d_P, d_views, R, S, d_range, D, d_kq8, d_depth, d_flags, d_summary,
+                       agg_radius=2, min_views=2, max_cost=2**30, d_cost=None, d_warp=None, d_planes=None, d_frame_ids=None):
+        """pgx_depth_maps_dev: one depth map per row of d_views [R][1 + S] int32 (reference frame, then sources; -1 = none).
+        d_gray [F][H][W] float32 by slot, d_P [n_frames][12] float64 by frame number, d_range [R][2] float64 = (z_near,
+        z_far); d_kq8 / d_flags [R][H][W] int32, d_depth [R][H][W] float64, d_summary [8] int32; d_cost [R][H][W] int32,
+        d_warp [R][S][12] and d_planes [R][D] float64 or None.  No sync."""
+        self._chk(self._L.pgx_depth_maps_dev(
+            self._h, _dptr(d_gray), int(F), int(W), int(H), _dptr(d_frame_ids), int(n_frames), _dptr(d_P), _dptr(d_views), int(R),
+            int(S), _dptr(d_range), int(D), int(agg_radius), int(min_views), int(max_cost), _dptr(d_kq8), _dptr(d_depth),
+            _dptr(d_cost), _dptr(d_flags), _dptr(d_warp), _dptr(d_planes), _dptr(d_summary)))
+
+    def depth_fuse_dev(self, d_depth, d_views, R, S, W, H, n_frames, d_P, max_points, d_xyz, d_src, d_summary, rel_tol=0.05,
+                       min_agree=2, d_agree=None):
+        """pgx_depth_fuse_dev: the pixels of d_depth [R][H][W] that min_agree other maps of the call confirm within rel_tol, in
+        (r, v, u) order: d_xyz [max_points][3] float64, d_src [max_points][2] int32 = (r, v W + u), d_agree [R][H][W] int32 or
+        None, d_summary [4] int32 ([0] = the pixels kept).  More than max_points: CapacityError from check_status.  No sync."""
+        self._chk(self._L.pgx_depth_fuse_dev(
+            self._h, _dptr(d_depth), _dptr(d_views), int(R), int(S), int(W), int(H), int(n_frames), _dptr(d_P), float(rel_tol),
+            int(min_agree), int(max_points), _dptr(d_xyz), _dptr(d_src), _dptr(d_agree), _dptr(d_summary)))
+
+    def depth_maps(self, gray, cameras, views, depth_range, D=64, agg_radius=2, min_views=2, max_cost=2**30, cost=True,
+                   warp=True, planes=True):
+        """The host form (pgx_depth_maps).  gray [n_frames][H][W] float32, cameras [n_frames][3][4] (or [n_frames][12]) float64,
+        views [R][1 + S] int32, depth_range [R][2] float64 -> dict(kq8, depth, cost, flags [R][H][W], warp [R][S][12],
+        planes [R][D], summary [8]); cost, warp and planes are None when not asked for."""
+        g = np.ascontiguousarray(gray, dtype=np.float32)
+        nf, H, W = g.shape
+        P = np.ascontiguousarray(cameras, dtype=np.float64).reshape(nf, 12)
+        vw = np.ascontiguousarray(views, dtype=np.int32)
+        vw = vw.reshape(-1, vw.shape[-1])
+        R, S = vw.shape[0], vw.shape[1] - 1
+        rg = np.ascontiguousarray(depth_range, dtype=np.float64).reshape(R, 2)
+        shape = (max(R, 1), H, W)
+        kq8, dep, fl = np.zeros(shape, np.int32), np.zeros(shape), np.zeros(shape, np.int32)
+        cs = np.zeros(shape, np.int32) if cost else None
+        wp = np.zeros((max(R, 1), S, 12)) if warp else None
+        pl = np.zeros((max(R, 1), int(D))) if planes else None
+        summary = np.zeros(8, dtype=np.int32)
+        self._chk(self._L.pgx_depth_maps(self._h, _ptr(g), nf, W, H, _ptr(P), _ptr(vw), R, S, _ptr(rg), int(D), int(agg_radius),
+                                         int(min_views), int(max_cost), _ptr(kq8), _ptr(dep), _ptr(cs), _ptr(fl), _ptr(wp), _ptr(pl),
+                                         _ptr(summary)))
+        return dict(kq8=kq8[:R], depth=dep[:R], cost=None if cs is None else cs[:R], flags=fl[:R],
+                    warp=None if wp is None else wp[:R], planes=None if pl is None else pl[:R], summary=summary)
+
+    def depth_fuse(self, depth, views, cameras, rel_tol=0.05, min_agree=2, max_points=None, agree=True):
+        """The host form (pgx_depth_fuse).  depth [R][H][W] float64, views [R][1 + S] int32, cameras [n_frames][3][4] float64 ->
+        dict(xyz [n][3], src [n][2] trimmed to min(summary[0], max_points), agree [R][H][W] or None, summary [4]).  max_points
+        defaults to every pixel; a smaller one that cuts the list raises CapacityError."""
+        d = np.ascontiguousarray(depth, dtype=np.float64)
+        R, H, W = d.shape
+        vw = np.ascontiguousarray(views, dtype=np.int32)
+        vw = vw.reshape(R, vw.shape[-1])
+        P = np.ascontiguousarray(cameras, dtype=np.float64).reshape(-1, 12)
+        cap = R * H * W if max_points is None else int(max_points)
+        xyz, src = np.zeros((max(cap, 1), 3)), np.zeros((max(cap, 1), 2), dtype=np.int32)
+        ag = np.zeros((max(R, 1), H, W), dtype=np.int32) if agree else None
+        summary = np.zeros(4, dtype=np.int32)
+        self._chk(self._L.pgx_depth_fuse(self._h, _ptr(d), _ptr(vw), R, vw.shape[1] - 1, W, H, len(P), _ptr(P), float(rel_tol),
+                                         int(min_agree), cap, _ptr(xyz), _ptr(src), _ptr(ag), _ptr(summary)))
+        n = min(int(summary[0]), cap)
+        return dict(xyz=xyz[:n], src=src[:n], agree=None if ag is None else ag[:R], summary=summary)
+
     # -- multi-GPU: the context's own RCCL communicator (pgx_comm_*) ------------------------------
     def comm_init(self, rank, world, unique_id):
         """Collective: every rank calls this with the 128 bytes rank 0 got from comm_unique_id()."""

@@ -104,6 +104,8 @@ int decode_status(pgx_ctx *c, int bits)
         return fail(c, PGX_E_BADARG, "vocabulary training: fewer valid descriptors than words (d_vocab was not written)");
     if (bits & PGX_ST_SEL_CAP)
         return fail(c, PGX_E_CAPACITY, "pair selection: more than max_pairs pairs were selected (the first max_pairs were written)");
+    if (bits & PGX_ST_DEP_CAP)
+        return fail(c, PGX_E_CAPACITY, "depth fusion: more than max_points pixels were kept (the first max_points were written)");
     return PGX_OK;
 }
 
@@ -463,7 +465,7 @@ void pgx_ctx_destroy(pgx_ctx *c)
     for (hipEvent_t ev : c->ev_pool) (void)hipEventDestroy(ev);
     DevBuf *bufs[] = {&c->d_pairs, &c->d_plan, &c->d_steer_pairs, &c->d_steer_plans, &c->d_steer_dirs, &c->d_map, &c->d_gather, &c->ws_gray, &c->ws_seg, &c->ws_segoff, &c->ws_nraw, &c->ws_rawxy,
                       &c->ws_rawscore, &c->ws_nms, &c->ws_order, &c->ws_nkept, &c->st_a, &c->st_b, &c->st_c,
-                      &c->st_d, &c->st_e, &c->st_f, &c->ws_pose, &c->ws_tracks, &c->ws_tracks_split, &c->ws_agree, &c->ws_matchn[0], &c->ws_matchn[1], &c->ws_matchn[2], &c->ws_knn, &c->ws_guided, &c->ws_tri, &c->ws_ba, &c->ws_reg, &c->ws_ver, &c->ws_init, &c->ws_cns, &c->ws_vocab,
+                      &c->st_d, &c->st_e, &c->st_f, &c->ws_pose, &c->ws_tracks, &c->ws_tracks_split, &c->ws_agree, &c->ws_matchn[0], &c->ws_matchn[1], &c->ws_matchn[2], &c->ws_knn, &c->ws_guided, &c->ws_tri, &c->ws_ba, &c->ws_reg, &c->ws_ver, &c->ws_init, &c->ws_cns, &c->ws_vocab, &c->ws_depth,
                       &c->ws_pyr_a, &c->ws_pyr_b, &c->ws_pyr_kp, &c->ws_pyr_desc, &c->ws_pyr_bins, &c->ws_pyr_cnt};
     for (DevBuf *b : bufs) b->release();
     c->pin_in.release();
@@ -1900,6 +1902,150 @@ int pgx_relative_pose(pgx_ctx *c, const pgx_keypoint *kp1, int n1, const pgx_key
     }
     HIPCHK(c, hipGetLastError());
     return download_images(c, ot);
+}
+
+// ---- dense depth maps by census plane sweep, and the cross-view filter ------------------------------------------------
+
+int pgx_gray_batch_dev(pgx_ctx *c, const uint16_t *d_rgba, int F, int W, int H, float *d_gray)
+{
+    if (!c || !d_rgba || !d_gray) return c ? fail(c, PGX_E_BADARG, "null pointer") : PGX_E_BADARG;
+    Lock l(c);
+    if (F <= 0) return fail(c, PGX_E_BADARG, "F must be positive");
+    if (dims_ok(c, W, H) != PGX_OK) return PGX_E_BADARG;
+    if (c->map_set && (W != c->mapW || H != c->mapH))
+        return fail(c, PGX_E_DIM_MISMATCH, "image %dx%d vs dewarp map %dx%d (ArgumentException)", W, H, c->mapW, c->mapH);
+    {
+        ProfScope ps(c, "dewarp_gray");
+        pgx_launch_dewarp_gray(c->stream, d_rgba, c->src8, c->map_set ? c->d_map.as<int32_t>() : nullptr, F, W, H, d_gray, nullptr,
+                               c->d_status);
+    }
+    HIPCHK(c, hipGetLastError());
+    return PGX_OK;
+}
+
+namespace {
+// what the device and the host form of a stage check alike
+int depth_args(pgx_ctx *c, int F, int W, int H, int n_frames, bool has_ids, int R, int S, int D, int agg_radius, int min_views, int max_cost)
+{
+    if (dims_ok(c, W, H) != PGX_OK) return PGX_E_BADARG;
+    if (F <= 0 || F > 65535 || n_frames <= 0) return fail(c, PGX_E_BADARG, "F must be in [1, 65535] and n_frames positive");
+    if (!has_ids && n_frames != F) return fail(c, PGX_E_BADARG, "without d_frame_ids, n_frames must equal F");
+    if (R < 0 || R > 65535) return fail(c, PGX_E_BADARG, "R must be in [0, 65535]");
+    if (D < 3 || D > 256) return fail(c, PGX_E_BADARG, "D = %d, must be in [3, 256]", D);
+    if (S < 1 || S > 8) return fail(c, PGX_E_BADARG, "S = %d, must be in [1, 8]", S);
+    if (agg_radius < 0 || agg_radius > 3) return fail(c, PGX_E_BADARG, "agg_radius = %d, must be in [0, 3]", agg_radius);
+    if (min_views < 1 || min_views > S) return fail(c, PGX_E_BADARG, "min_views = %d, must be in [1, S]", min_views);
+    if (max_cost < 0) return fail(c, PGX_E_BADARG, "max_cost must be >= 0");
+    if ((long long)(R > F ? R : F) * W * H > (1ll << 30)) return fail(c, PGX_E_BADARG, "max(F, R) * W * H must be <= 2^30");
+    return PGX_OK;
+}
+
+int fuse_args(pgx_ctx *c, int R, int S, int W, int H, int n_frames, double rel_tol, int min_agree, int max_points)
+{
+    if (dims_ok(c, W, H) != PGX_OK) return PGX_E_BADARG;
+    if (R < 0 || R > 65535 || n_frames <= 0) return fail(c, PGX_E_BADARG, "R must be in [0, 65535] and n_frames positive");
+    if (S < 1 || S > 8) return fail(c, PGX_E_BADARG, "S = %d, must be in [1, 8]", S);
+    if (!(rel_tol >= 0.0) || std::isinf(rel_tol)) return fail(c, PGX_E_BADARG, "rel_tol must be finite and >= 0");
+    if (min_agree < 0 || max_points < 0) return fail(c, PGX_E_BADARG, "min_agree and max_points must be >= 0");
+    if ((long long)R * W * H > (1ll << 30)) return fail(c, PGX_E_BADARG, "R * W * H must be <= 2^30");
+    return PGX_OK;
+}
+} // namespace
+
+int pgx_depth_maps_dev(pgx_ctx *c, const float *d_gray, int F, int W, int H, const int32_t *d_frame_ids, int n_frames, const double *d_P,
+                       const int32_t *d_views, int R, int S, const double *d_range, int D, int agg_radius, int min_views, int max_cost,
+                       int32_t *d_kq8, double *d_depth, int32_t *d_cost, int32_t *d_flags, double *d_warp, double *d_planes,
+                       int32_t *d_summary)
+{
+    if (!c || !d_gray || !d_P || !d_views || !d_range || !d_kq8 || !d_depth || !d_flags || !d_summary)
+        return c ? fail(c, PGX_E_BADARG, "null pointer") : PGX_E_BADARG;
+    Lock l(c);
+    const int rc = depth_args(c, F, W, H, n_frames, d_frame_ids != nullptr, R, S, D, agg_radius, min_views, max_cost);
+    if (rc != PGX_OK) return rc;
+    if (R == 0) return fail(c, PGX_E_BADARG, "R must be positive");
+    HIPCHK(c, c->ws_depth.ensure(pgx_depth_ws_bytes(F, W, H, R, S, D)));
+    pgx_launch_depth_maps(c, c->stream, d_gray, F, W, H, d_frame_ids, n_frames, d_P, d_views, R, S, d_range, D, agg_radius, min_views,
+                          max_cost, d_kq8, d_depth, d_cost, d_flags, d_warp, d_planes, d_summary, c->ws_depth.p);
+    HIPCHK(c, hipGetLastError());
+    return PGX_OK;
+}
+
+int pgx_depth_maps(pgx_ctx *c, const float *gray, int n_frames, int W, int H, const double *P, const int32_t *views, int R, int S,
+                   const double *range, int D, int agg_radius, int min_views, int max_cost, int32_t *kq8, double *depth, int32_t *cost,
+                   int32_t *flags, double *warp, double *planes, int32_t *summary)
+{
+    if (!c || !gray || !P || !summary || R < 0 || (R > 0 && (!views || !range || !kq8 || !depth || !flags)))
+        return c ? fail(c, PGX_E_BADARG, "null pointer or bad size") : PGX_E_BADARG;
+    Lock l(c);
+    const int rc = depth_args(c, n_frames, W, H, n_frames, false, R, S, D, agg_radius, min_views, max_cost);
+    if (rc != PGX_OK) return rc;
+    for (int i = 0; i < 8; i++) summary[i] = 0;
+    if (R == 0) return PGX_OK;
+    const size_t npix = (size_t)W * H, n = (size_t)R * npix;
+    HostImage in, out;
+    const int i_g = in.add(gray, (size_t)n_frames * npix, 4), i_P = in.add(P, n_frames, 96), i_v = in.add(views, (size_t)R * (1 + S), 4),
+              i_r = in.add(range, R, 16);
+    const int o_kq = out.add(kq8, n, 4), o_d = out.add(depth, n, 8), o_c = out.add(cost, n, 4, 0, cost != nullptr),
+              o_f = out.add(flags, n, 4), o_w = out.add(warp, (size_t)R * S * 12, 8, 0, warp != nullptr),
+              o_p = out.add(planes, (size_t)R * D, 8, 0, planes != nullptr), o_s = out.add(summary, 8, 4, 64);
+    int rs = stage_images(c, in, out);
+    if (rs != PGX_OK) return rs;
+    HIPCHK(c, c->ws_depth.ensure(pgx_depth_ws_bytes(n_frames, W, H, R, S, D)));
+    pgx_launch_depth_maps(c, c->stream, in.dev<float>(i_g), n_frames, W, H, nullptr, n_frames, in.dev<double>(i_P), in.dev<int32_t>(i_v), R,
+                          S, in.dev<double>(i_r), D, agg_radius, min_views, max_cost, out.dev<int32_t>(o_kq), out.dev<double>(o_d),
+                          out.dev<int32_t>(o_c), out.dev<int32_t>(o_f), out.dev<double>(o_w), out.dev<double>(o_p), out.dev<int32_t>(o_s),
+                          c->ws_depth.p);
+    HIPCHK(c, hipGetLastError());
+    return download_images(c, out);
+}
+
+int pgx_depth_fuse_dev(pgx_ctx *c, const double *d_depth, const int32_t *d_views, int R, int S, int W, int H, int n_frames,
+                       const double *d_P, double rel_tol, int min_agree, int max_points, double *d_xyz, int32_t *d_src, int32_t *d_agree,
+                       int32_t *d_summary)
+{
+    if (!c || !d_depth || !d_views || !d_P || !d_summary || (max_points > 0 && (!d_xyz || !d_src)))
+        return c ? fail(c, PGX_E_BADARG, "null pointer") : PGX_E_BADARG;
+    Lock l(c);
+    const int rc = fuse_args(c, R, S, W, H, n_frames, rel_tol, min_agree, max_points);
+    if (rc != PGX_OK) return rc;
+    if (R == 0) return fail(c, PGX_E_BADARG, "R must be positive");
+    HIPCHK(c, c->ws_depth.ensure(pgx_depth_fuse_ws_bytes(R, S, W, H)));
+    pgx_launch_depth_fuse(c, c->stream, d_depth, d_views, R, S, W, H, n_frames, d_P, rel_tol, min_agree, max_points, d_xyz, d_src, d_agree,
+                          d_summary, c->ws_depth.p, c->d_status);
+    HIPCHK(c, hipGetLastError());
+    return PGX_OK;
+}
+
+int pgx_depth_fuse(pgx_ctx *c, const double *depth, const int32_t *views, int R, int S, int W, int H, int n_frames, const double *P,
+                   double rel_tol, int min_agree, int max_points, double *xyz, int32_t *src, int32_t *agree, int32_t *summary)
+{
+    if (!c || !P || !summary || R < 0 || (R > 0 && (!depth || !views)) || (max_points > 0 && (!xyz || !src)))
+        return c ? fail(c, PGX_E_BADARG, "null pointer or bad size") : PGX_E_BADARG;
+    Lock l(c);
+    const int rc = fuse_args(c, R, S, W, H, n_frames, rel_tol, min_agree, max_points);
+    if (rc != PGX_OK) return rc;
+    for (int i = 0; i < 4; i++) summary[i] = 0;
+    if (R == 0) return PGX_OK;
+    const size_t n = (size_t)R * W * H;
+    HostImage in, out;
+    const int i_d = in.add(depth, n, 8), i_v = in.add(views, (size_t)R * (1 + S), 4), i_P = in.add(P, n_frames, 96);
+    // the summary first: its download tells how many points there are to fetch
+    const int o_s = out.add(summary, 4, 4, 64), o_a = out.add(agree, n, 4, 0, agree != nullptr),
+              o_x = out.add(nullptr, 0, 24, (size_t)max_points + 1), o_r = out.add(nullptr, 0, 8, (size_t)max_points + 1);
+    int rs = stage_images(c, in, out);
+    if (rs != PGX_OK) return rs;
+    HIPCHK(c, c->ws_depth.ensure(pgx_depth_fuse_ws_bytes(R, S, W, H)));
+    pgx_launch_depth_fuse(c, c->stream, in.dev<double>(i_d), in.dev<int32_t>(i_v), R, S, W, H, n_frames, in.dev<double>(i_P), rel_tol,
+                          min_agree, max_points, out.dev<double>(o_x), out.dev<int32_t>(o_r), out.dev<int32_t>(o_a), out.dev<int32_t>(o_s),
+                          c->ws_depth.p, c->d_status);
+    HIPCHK(c, hipGetLastError());
+    rs = download_images(c, out);   // summary and agree; waits for the stream
+    const size_t np = (size_t)(summary[0] < max_points ? summary[0] : max_points);
+    if (np > 0) {
+        HIPCHK(c, hipMemcpy(xyz, out.dev<double>(o_x), np * 24, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(src, out.dev<int32_t>(o_r), np * 8, hipMemcpyDeviceToHost));
+    }
+    return rs;
 }
 
 // ---- measurement hooks ---------------------------------------------------------------------

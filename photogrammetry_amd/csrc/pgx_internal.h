@@ -39,6 +39,7 @@
 #define PGX_ST_CNS_DUP    4194304u /* pgx_track_consensus_dev: two slots of d_frame_ids name the same frame */
 #define PGX_ST_VOC_FEW    8388608u  /* pgx_vocab_train_dev: fewer valid descriptors than words */
 #define PGX_ST_SEL_CAP    16777216u /* pgx_select_pairs_dev: more than max_pairs pairs selected */
+#define PGX_ST_DEP_CAP    33554432u /* pgx_depth_fuse_dev: more than max_points pixels kept */
 
 // key = (distance << PGX_IDX_BITS) | index ; limits: index < 2^20, distance < 2^12
 #define PGX_IDX_BITS 20
@@ -159,6 +160,7 @@ struct pgx_ctx {
     DevBuf ws_cns;    // pgx_track_consensus*: frame table, ray records and keep flags per node, per-track state, scan block sums
     DevBuf ws_ver;    // pgx_verify_pair*: candidate lists of a chunk of image pairs, hypotheses of one chunk of samples, keys
     DevBuf ws_vocab;  // pgx_vocab_train*, pgx_select_pairs*: words per descriptor, members by word, histograms, weights, scores
+    DevBuf ws_depth;  // pgx_depth_maps*, pgx_depth_fuse*: census words per slot, warps, plane tables; camera table, keep flags, block sums
     DevBuf ws_init;   // pgx_init_pair_dev, pgx_relative_pose: per image pair the two rotations, t, the intrinsics and the counters
     hipStream_t mstream[3] = {nullptr, nullptr, nullptr}; // [0] wide rounds, [1] residual distance rows, [2] per-pair finish
     hipEvent_t ev_in = nullptr, ev_wide[3] = {nullptr, nullptr, nullptr}, ev_rows[3] = {nullptr, nullptr, nullptr},
@@ -464,3 +466,16 @@ size_t pgx_select_pairs_ws_bytes(int F, int S, int V, bool own_scores);
 void pgx_launch_select_pairs(pgx_ctx *ctx, hipStream_t s, const uint32_t *d_desc, const int32_t *d_counts, int F, int S,
                              const uint32_t *d_vocab, int V, int weighting, int top_k, int window, int min_score, int max_pairs,
                              int32_t *d_pairlist, int32_t *d_pair_score, int32_t *d_scores, int32_t *d_summary, void *ws, int *status);
+
+// k_depth.hip (census plane-sweep depth maps and the cross-view filter; pgx_depth_maps_dev and pgx_depth_fuse_dev semantics,
+// include/pgx.h).  ctx: the profiling groups depth_census / depth_plan / depth_sweep / depth_fuse
+size_t pgx_depth_ws_bytes(int F, int W, int H, int R, int S, int D);
+void pgx_launch_depth_maps(pgx_ctx *ctx, hipStream_t s, const float *d_gray, int F, int W, int H, const int32_t *d_frame_ids, int n_frames,
+                           const double *d_P, const int32_t *d_views, int R, int S, const double *d_range, int D, int agg_radius,
+                           int min_views, int max_cost, int32_t *d_kq8, double *d_depth, int32_t *d_cost, int32_t *d_flags, double *d_warp,
+                           double *d_planes, int32_t *d_summary, void *ws);
+size_t pgx_depth_fuse_ws_bytes(int R, int S, int W, int H);
+// more than max_points kept pixels: PGX_ST_DEP_CAP in *status
+void pgx_launch_depth_fuse(pgx_ctx *ctx, hipStream_t s, const double *d_depth, const int32_t *d_views, int R, int S, int W, int H,
+                           int n_frames, const double *d_P, double rel_tol, int min_agree, int max_points, double *d_xyz, int32_t *d_src,
+                           int32_t *d_agree, int32_t *d_summary, void *ws, int *status);
