@@ -154,6 +154,8 @@ class Problem:
         for i in range(3):
             Vd[:, i, i] += lam * np.clip(V[:, i, i], 1e-6, 1e32)
         if npt:
+            if not np.isfinite(Vd).all():       # a NaN block is not positive definite; LAPACK need not say so
+                raise NotPD()
             try:
                 np.linalg.cholesky(Vd)          # raises if any block is not positive definite
             except np.linalg.LinAlgError:
@@ -183,6 +185,8 @@ class Problem:
             Wb[cf, :, tcol, :] = W
             Sf -= Yb.reshape(6 * nfr, 3 * npt) @ Wb.reshape(6 * nfr, 3 * npt).T
         if nfr:
+            if not np.isfinite(Sf).all():
+                raise NotPD()
             try:
                 L = np.linalg.cholesky(np.tril(Sf) + np.tril(Sf, -1).T)
             except np.linalg.LinAlgError:
@@ -206,7 +210,8 @@ def bundle_adjust(kps, K, Rt, fixed, offsets, nodes, xyz, track_flags=None, max_
                   max_tracks=None, solver=None):
     """The contract's loop.  solver(problem, lin, lam) -> (dc, dX) replaces the Schur solve (tests/test_bundle_ref.py).
     -> dict(Rt, P, xyz [nt][3], node_err [n_nodes], trace [max_iters + 1][2], report [8], decisions (list of 'accept',
-    'reject', 'nonpd', 'small'), problem)"""
+    'reject', 'nonpd', 'small'), trial (per attempt: the trial cost C_new of an accept or a reject, NaN for 'nonpd' and
+    'small'), small_ratio (of a 'small' stop: ||delta|| / (1e-12 (1 + ||x||)), else None), problem)"""
     pb = Problem(kps, K, Rt, fixed, offsets, nodes, xyz, track_flags, max_tracks)
     solver = solver or (lambda p, lin, lam: p.solve_schur(lin, lam))
     Rt_c = pb.Rt0.copy()
@@ -217,7 +222,7 @@ def bundle_adjust(kps, K, Rt, fixed, offsets, nodes, xyz, track_flags=None, max_
     C = lin["C"]
     trace[0] = (C, lam)
     it = acc = nonpd = 0
-    decisions = []
+    decisions, trial, small_ratio = [], [], None
 
     def start_reason():
         if pb.err or len(pb.tracks) == 0:
@@ -242,12 +247,16 @@ def bundle_adjust(kps, K, Rt, fixed, offsets, nodes, xyz, track_flags=None, max_
             nonpd += 1
             lam *= 10.0
             decisions.append("nonpd")
+            trial.append(np.nan)
         elif np.sqrt((dc * dc).sum() + (dX * dX).sum()) <= 1e-12 * (1.0 + pb.x_norm(Rt_c, X)):
             reason_now = 3
             decisions.append("small")
+            trial.append(np.nan)
+            small_ratio = float(np.sqrt((dc * dc).sum() + (dX * dX).sum()) / (1e-12 * (1.0 + pb.x_norm(Rt_c, X))))
         else:
             Rt_t, X_t = pb.apply(Rt_c, X, dc, dX)
             Cn = pb.cost(Rt_t, X_t, huber_px)
+            trial.append(Cn)
             if Cn < C:
                 accepted = True
                 small = C - Cn <= 1e-12 * C
@@ -291,7 +300,8 @@ def bundle_adjust(kps, K, Rt, fixed, offsets, nodes, xyz, track_flags=None, max_
         node_err[pb.ob_node] = np.sqrt((r * r).sum(1))
         zneg = int((~(z > 0)).sum())
     report = np.array([it, acc, reason, pb.n_free_all, len(pb.tracks), len(pb.ob_t), zneg, nonpd], np.int32)
-    return dict(Rt=Rt_out, P=P, xyz=xyz_out, node_err=node_err, trace=trace, report=report, decisions=decisions, problem=pb)
+    return dict(Rt=Rt_out, P=P, xyz=xyz_out, node_err=node_err, trace=trace, report=report, decisions=decisions,
+                trial=np.array(trial, np.float64), small_ratio=small_ratio, problem=pb)
 
 
 def camera_centres(Rt):

@@ -6,6 +6,8 @@ A plain helper module: no test module imports another."""
 import numpy as np
 import torch
 
+import bundle_paths_cases as paths
+import bundle_ref
 import triangulate_ref
 from tracks_split_ref import KEYS as TRACK_KEYS
 from photogrammetry_amd import synth
@@ -118,6 +120,55 @@ def ba_check_against_yardstick(got, e, scale):
         assert np.nanmax(np.abs(got[k] - e[k])) <= 1e-8 * scale, k
     assert (got["report"][3:6] == e["report"][3:6]).all()
     return dg, de
+
+
+def ba_camera_rows(K, Rt, state):
+    """bundle_ref's P = K [R | t] rows of the frames that are not UNKNOWN (NaN rows for those), on a given Rt"""
+    P = np.full((len(Rt), 12), np.nan)
+    for f in range(len(Rt)):
+        if state[f] != bundle_ref.UNKNOWN:
+            M = np.concatenate([Rt[f, :9].reshape(3, 3), Rt[f, 9:, None]], 1)
+            P[f, 0:4] = K[f, 0] * M[0] + K[f, 2] * M[2]
+            P[f, 4:8] = K[f, 1] * M[1] + K[f, 3] * M[2]
+            P[f, 8:12] = M[2]
+    return P
+
+
+def ba_check_paths(got, e, scale, margin=paths.MARGIN, node_err_tol=paths.NODE_ERR_TOL, nonpd_compared=False):
+    """A device result against the yardstick's through rejected steps (tests/bundle_paths_cases.py).  Over the compared
+    attempts (yardstick margin >= `margin`): equal decisions, rejects and the accepts after them included, the cost column to
+    1e-9 relative and the lambda column bit for bit (a chain of * 10, / 10 and fmax on the same start).  The report entry for
+    entry when every attempt is compared, else its entries 3 .. 7 and no fewer attempts and accepts than the compared ones.
+    Rt and xyz to 1e-8 of the scene scale and node_err to node_err_tol, NaN where the yardstick's are; trace rows behind
+    report[0] NaN; P_out bit for bit K [R | t] of the device's own Rt_out; fixed and unknown frames bit-unchanged.
+    nonpd_compared: the scene's non-PD verdicts are exact by construction and compared too (paths.compared).
+    -> (device decisions, yardstick decisions, compared)"""
+    pb = e["problem"]
+    dg, de = decisions(got["trace"], got["report"]), yard_decisions(e)
+    n = paths.compared(e, margin, nonpd=nonpd_compared)
+    assert dg[:n] == de[:n], (n, dg, de)
+    tg, te = got["trace"], e["trace"]
+    assert tg.shape == te.shape
+    assert np.allclose(tg[:n + 1, 0], te[:n + 1, 0], rtol=paths.TRACE_TOL, atol=0), (tg[:n + 1], te[:n + 1])
+    assert bits(tg[:n + 1, 1]) == bits(te[:n + 1, 1]), (tg[:n + 1, 1], te[:n + 1, 1])
+    it = int(got["report"][0])
+    assert np.isfinite(tg[:it + 1]).all() and np.isnan(tg[it + 1:]).all(), tg
+    assert int(got["report"][1]) == dg.count("accept"), (got["report"], dg)
+    if n == len(de):
+        assert got["report"].tolist() == e["report"].tolist(), (got["report"], e["report"])
+    else:
+        assert got["report"][3:8].tolist() == e["report"][3:8].tolist(), (got["report"], e["report"])
+        assert it >= n and got["report"][1] >= de[:n].count("accept") and got["report"][2] in (1, 2, 3, 4), got["report"]
+    for k in ("Rt", "xyz"):
+        assert (np.isnan(got[k]) == np.isnan(e[k])).all(), k
+        assert np.nanmax(np.abs(got[k] - e[k])) <= paths.X_TOL * scale, (k, np.nanmax(np.abs(got[k] - e[k])))
+    assert (np.isnan(got["node_err"]) == np.isnan(e["node_err"])).all()
+    d = np.nanmax(np.abs(got["node_err"] - e["node_err"]))
+    assert d <= node_err_tol, d
+    assert bits(got["P"]) == bits(ba_camera_rows(pb.K, got["Rt"], pb.state))
+    still = pb.state < 0
+    assert bits(got["Rt"][still]) == bits(pb.Rt0[still])
+    return dg, de, n
 
 
 def tri_check_against_yardstick(got, kps, P, min_par, max_e, iters, stop_band=False):

@@ -1,12 +1,13 @@
 """CPU tests (no GPU): the bundle-adjustment yardstick (tests/bundle_ref.py) against an independent dense formulation.  The
-dense side builds the full Jacobian of every used observation over all free-camera and point parameters, checks it against
-central differences of the contract's parametrisation (R' = Exp(omega) R, t' = t + tau, X' = X + dX), and solves the full
-damped normal equations without a Schur complement.  Step for step both must agree; on unrounded projections with two true
-fixed frames the yardstick must recover the truth."""
+dense side (tests/bundle_dense.py) builds the full Jacobian of every used observation over all free-camera and point
+parameters; here it is checked against central differences of the contract's parametrisation (R' = Exp(omega) R,
+t' = t + tau, X' = X + dX), and the full damped normal equations are solved without a Schur complement.  Step for step both
+must agree; on unrounded projections with two true fixed frames the yardstick must recover the truth."""
 import numpy as np
 import pytest
 
 import bundle_ref as ref
+from bundle_dense import dense_jacobian, dense_solver
 from photogrammetry_amd import synth
 
 
@@ -25,18 +26,6 @@ def _residual_vector(pb, Rt, X):
     return r.reshape(-1)
 
 
-def dense_jacobian(pb, lin):
-    """Full J [2m][6 n_free + 3 n_points] from the yardstick's per-observation blocks"""
-    m, nfr, npt = len(pb.ob_t), pb.n_free, len(pb.tracks)
-    J = np.zeros((2 * m, 6 * nfr + 3 * npt))
-    for i in range(m):
-        c = pb.ob_cf[i]
-        if c >= 0:
-            J[2 * i:2 * i + 2, 6 * c:6 * c + 6] = lin["Jc"][i]
-        J[2 * i:2 * i + 2, 6 * nfr + 3 * pb.ob_t[i]:6 * nfr + 3 * pb.ob_t[i] + 3] = lin["Jp"][i]
-    return J
-
-
 def numeric_jacobian(pb, Rt, X, h=1e-6):
     nfr, npt = pb.n_free, len(pb.tracks)
     cols = []
@@ -47,22 +36,6 @@ def numeric_jacobian(pb, Rt, X, h=1e-6):
         Rm, Xm = pb.apply(Rt, X, -d[:6 * nfr], -d[6 * nfr:].reshape(-1, 3))
         cols.append((_residual_vector(pb, Rp, Xp) - _residual_vector(pb, Rm, Xm)) / (2 * h))
     return np.stack(cols, 1)
-
-
-def dense_solver(pb, lin, lam):
-    """(A + lam D) delta = -g on the full system, A = J^T W J, g = J^T W r"""
-    J = dense_jacobian(pb, lin)
-    w = np.repeat(lin["w"], 2)
-    A = J.T @ (w[:, None] * J)
-    g = J.T @ (w * lin["r"].reshape(-1))
-    Ad = A + lam * np.diag(np.clip(np.diag(A), 1e-6, 1e32))
-    try:
-        L = np.linalg.cholesky(Ad)
-    except np.linalg.LinAlgError:
-        raise ref.NotPD()
-    d = np.linalg.solve(L.T, np.linalg.solve(L, -g))
-    nfr = 6 * pb.n_free
-    return d[:nfr], d[nfr:].reshape(-1, 3)
 
 
 def test_jacobian_matches_central_differences():
