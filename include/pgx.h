@@ -996,7 +996,9 @@ int pgx_gray_batch_dev(pgx_ctx *ctx, const uint16_t *d_rgba, int F, int W, int H
  *             valid iff q_2 > 0 and 0 <= q_0 / q_2 + 0.5 < W and 0 <= q_1 / q_2 + 0.5 < H (IEEE float64, correctly rounded
  *             division; NaN fails); the source pixel is the floor of those two values.  cost = popcount(census_r(u, v) xor
  *             census_s(pixel)) where valid, 31 where not.  raw(u, v, k) = the sum over the S sources, nvalid(u, v, k) = the
- *             number of valid ones.
+ *             number of valid ones.  A consequence, here and in pgx_depth_fuse_dev: a source with det M_s < 0 (-P for a
+ *             camera P) has q_2 < 0 at every point in front of it, so q_2 > 0 passes over it there as over a source that is
+ *             -1 (its warp is finite all the same), while as a reference such a camera is as good as P (w_k < 0).
  *   5 box     agg(u, v, k) = the sum of raw over the (2 agg_radius + 1)^2 box, box coordinates clamped to the image.
  *   6 choice  k* = the argmin of agg over k, ties to the smallest k.  Flags (PGX_DEP_*, bits): NOCAMERA (step 2); NOVIEWS
  *             nvalid(u, v, k*) < min_views; EDGE k* is 0 or D - 1; HIGHCOST agg(k*) > max_cost.

@@ -1,7 +1,13 @@
 """The numpy yardstick of the dense stage (include/pgx.h: pgx_depth_maps_dev, pgx_depth_fuse_dev), operation by operation in the
 header's order, with the full cost volume in memory; a loop-per-pixel restatement of the depth maps that shares nothing with
 the vectorised one but the camera algebra; and the two-plane test scene.  Python floats and numpy float64 scalars do not
-contract a b + c, which is what the library's -ffp-contract=off build does.  A plain helper module."""
+contract a b + c, which is what the library's -ffp-contract=off build does.  The yardstick's camera algebra is a transcription
+of pgx.h, as the kernel's is: exact_warp and exact_plane_scale restate it in rationals and decimals without those lines, and
+scene_rotated shows the two planes to cameras that are turned, rolled, skewed, scaled and mirrored.  A plain helper module."""
+import decimal
+import itertools
+from fractions import Fraction
+
 import numpy as np
 
 NOCAMERA, NOVIEWS, EDGE, HIGHCOST = 1, 2, 4, 8
@@ -321,9 +327,8 @@ def scene_camera(C, W=SCENE_W, H=SCENE_H, f=SCENE_F):
     return K @ np.hstack([np.eye(3), -np.asarray(C, dtype=np.float64)[:, None]])
 
 
-def scene_render(C, slant=0.0, seed=1, W=SCENE_W, H=SCENE_H, f=SCENE_F):
-    """A back plane z = 4 + slant x and a front rectangle z = 3 (|x| < 0.5, |y| < 0.35), each with a bilinear texture of seeded
-    noise at 12 texels per unit, seen from centre C -> (grey [H][W] float32, true depth [H][W])"""
+def scene_texture(seed=1):
+    """tex(X, Y): the bilinear texture of seeded noise at 12 texels per unit that both scenes paint their planes with"""
     T = np.random.default_rng(seed).random((256, 256)).astype(np.float32)
 
     def tex(X, Y):
@@ -331,6 +336,13 @@ def scene_render(C, slant=0.0, seed=1, W=SCENE_W, H=SCENE_H, f=SCENE_F):
         x0, y0 = np.clip(np.floor(x).astype(int), 0, 254), np.clip(np.floor(y).astype(int), 0, 254)
         fx, fy = x - x0, y - y0
         return T[y0, x0] * (1 - fx) * (1 - fy) + T[y0, x0 + 1] * fx * (1 - fy) + T[y0 + 1, x0] * (1 - fx) * fy + T[y0 + 1, x0 + 1] * fx * fy
+    return tex
+
+
+def scene_render(C, slant=0.0, seed=1, W=SCENE_W, H=SCENE_H, f=SCENE_F):
+    """A back plane z = 4 + slant x and a front rectangle z = 3 (|x| < 0.5, |y| < 0.35), each with a bilinear texture of seeded
+    noise at 12 texels per unit, seen from centre C -> (grey [H][W] float32, true depth [H][W])"""
+    tex = scene_texture(seed)
     C = np.asarray(C, dtype=np.float64)
     v, u = np.mgrid[0:H, 0:W].astype(np.float64)
     dx, dy = (u - W / 2) / f, (v - H / 2) / f
@@ -354,3 +366,198 @@ def scene(slant=0.0, seed=1):
 def all_views(n=5):
     """every frame as the reference, the others as its sources"""
     return np.array([[r] + [j for j in range(n) if j != r] for r in range(n)], dtype=np.int32)
+
+
+# ---- an independent camera reference: exact rationals and decimals, no cofactor line of pgx.h written out ------------------
+
+U53 = Fraction(1, 2**53)
+
+
+def _exact_camera(P):
+    p = [[Fraction(float(x)) for x in row] for row in np.asarray(P, dtype=np.float64).reshape(3, 4)]
+    return [row[:3] for row in p], [row[3] for row in p]
+
+
+def _perm_terms(M):
+    """the six signed terms of the Leibniz determinant"""
+    out = []
+    for perm in itertools.permutations(range(3)):
+        inv = sum(1 for i in range(3) for j in range(i + 1, 3) if perm[i] > perm[j])
+        out.append((-1) ** inv * M[0][perm[0]] * M[1][perm[1]] * M[2][perm[2]])
+    return out
+
+
+def _gauss_jordan_inverse(M):
+    n = 3
+    a = [list(M[i]) + [Fraction(int(i == j)) for j in range(n)] for i in range(n)]
+    for c in range(n):
+        piv = max(range(c, n), key=lambda i: abs(a[i][c]))
+        if a[piv][c] == 0:
+            raise ZeroDivisionError("singular camera")
+        a[c], a[piv] = a[piv], a[c]
+        a[c] = [x / a[c][c] for x in a[c]]
+        for i in range(n):
+            if i != c and a[i][c] != 0:
+                a[i] = [x - a[i][c] * y for x, y in zip(a[i], a[c])]
+    return [row[n:] for row in a]
+
+
+def exact_warp(P_r, P_s):
+    """The plane-induced warp of rule 3 in exact rationals of the float64 inputs: A = M_s M_r^-1 by Gauss-Jordan, b = p4_s - A p4_r,
+    and a forward-error bound per entry for rule 3 evaluated in float64 (u = 2^-53):
+      bound(A_ij) = 16 u N_ij / |det| (1 + D_abs / |det|), N_ij = sum_k |M_s[i][k]| (|a b| + |c d|) over the two products of the
+      cofactor that is entry (k, j) of the adjugate, D_abs = the determinant's six terms taken absolute (at most 8 roundings on
+      the numerator, at most 7 on det);
+      bound(b_i) = 4 u (|p4_s[i]| + sum_k |A_ik| |p4_r[k]|) + sum_k bound(A_ik) |p4_r[k]|.
+    -> (A [3][3], b [3], bound_A [3][3], bound_b [3]), all Fractions"""
+    Mr, p4r = _exact_camera(P_r)
+    Ms, p4s = _exact_camera(P_s)
+    inv = _gauss_jordan_inverse(Mr)
+    terms = _perm_terms(Mr)
+    det, d_abs = abs(sum(terms)), sum(abs(t) for t in terms)
+    A = [[sum(Ms[i][k] * inv[k][j] for k in range(3)) for j in range(3)] for i in range(3)]
+    b = [p4s[i] - sum(A[i][k] * p4r[k] for k in range(3)) for i in range(3)]
+    # entry (k, j) of the adjugate is the minor of M_r without row j and column k: its two products, in absolute value
+    mag = [[abs(Mr[(j + 1) % 3][(k + 1) % 3] * Mr[(j + 2) % 3][(k + 2) % 3]) + abs(Mr[(j + 1) % 3][(k + 2) % 3] * Mr[(j + 2) % 3][(k + 1) % 3])
+            for j in range(3)] for k in range(3)]
+    bA = [[16 * U53 * sum(abs(Ms[i][k]) * mag[k][j] for k in range(3)) / det * (1 + d_abs / det) for j in range(3)] for i in range(3)]
+    bb = [4 * U53 * (abs(p4s[i]) + sum(abs(A[i][k]) * abs(p4r[k]) for k in range(3))) + sum(bA[i][k] * abs(p4r[k]) for k in range(3))
+          for i in range(3)]
+    return A, b, bA, bb
+
+
+def exact_plane_scale(P_r):
+    """sign(det M_r) ||m3_r|| of rule 2 as a Decimal at 200 digits"""
+    with decimal.localcontext() as ctx:
+        ctx.prec = 200
+        M = [[decimal.Decimal(float(x)) for x in row[:3]] for row in np.asarray(P_r, dtype=np.float64).reshape(3, 4)]
+        det = sum(_perm_terms(M))
+        n3 = (M[2][0] * M[2][0] + M[2][1] * M[2][1] + M[2][2] * M[2][2]).sqrt()
+        return n3.copy_sign(det)
+
+
+def plan_against_exact(P, views, ranges, D, warp, planes):
+    """A plan's tables (the yardstick's or the device's; every frame its own slot) against the exact reference, per (r, s) block:
+    -> (the worst |warp entry - exact| / its bound, the worst relative error of a w_k against exact_plane_scale (1 / iz_k) in
+    units of u = 2^-53, with 1 / iz_k the float64 of rule 2).  Blocks of -1 sources must be NaN, every other one finite."""
+    P = np.asarray(P, dtype=np.float64).reshape(-1, 12)
+    views = np.asarray(views, dtype=np.int64)
+    R, S = views.shape[0], views.shape[1] - 1
+    warp, planes = np.asarray(warp, dtype=np.float64).reshape(R, S, 12), np.asarray(planes, dtype=np.float64).reshape(R, D)
+    ranges = np.asarray(ranges, dtype=np.float64).reshape(-1, 2)
+    worst_w, worst_p = Fraction(0), Fraction(0)
+    for r in range(R):
+        sn = exact_plane_scale(P[views[r, 0]])
+        izf, izn = 1.0 / ranges[r, 1], 1.0 / ranges[r, 0]
+        with decimal.localcontext() as ctx:
+            ctx.prec = 200
+            for k in range(D):
+                want = sn * decimal.Decimal(1.0 / (izf + (float(k) / float(D - 1)) * (izn - izf)))
+                assert np.isfinite(planes[r, k]), (r, k)
+                rel = abs((decimal.Decimal(float(planes[r, k])) - want) / want)
+                worst_p = max(worst_p, Fraction(rel) / U53)
+        for s in range(S):
+            if views[r, 1 + s] < 0:
+                assert np.isnan(warp[r, s]).all(), (r, s)
+                continue
+            assert np.isfinite(warp[r, s]).all(), (r, s)
+            A, b, bA, bb = exact_warp(P[views[r, 0]], P[views[r, 1 + s]])
+            want = [A[i][j] for i in range(3) for j in range(3)] + b
+            bound = [bA[i][j] for i in range(3) for j in range(3)] + bb
+            for e in range(12):
+                err = abs(Fraction(float(warp[r, s, e])) - want[e])
+                if err > 0:
+                    worst_w = max(worst_w, err / bound[e] if bound[e] > 0 else Fraction(10**9))
+    return float(worst_w), float(worst_p)
+
+
+# ---- the same two planes seen by general cameras: rotated, rolled, skewed, scaled, mirrored ----------------------------------
+
+ROT_K = np.array([[120.0, 1.5, 51.0], [0.0, 132.0, 30.0], [0.0, 0.0, 1.0]])
+ROT_ROLLS = (7.0, -5.0, 11.0, -9.0, 4.0)
+ROT_TARGET = (0.0, 0.0, 4.0)
+ROT_SCALES = (-2.5, 1.0, 1e-3, 40.0, 0.3)              # any scale, one of them negative
+ROT_SCALES_POW2 = (-4.0, 1.0, 2.0**-10, 32.0, 0.25)    # scales that every float64 operation of the rule commutes with
+# frame 0 as the reference of row 0 only: with a negative scale it is no valid source (rule 4's q_2 > 0)
+ROT_VIEWS = np.array([[0, 1, 2, 3, 4], [1, 2, 3, 4, -1], [2, 1, 3, 4, -1], [3, 1, 2, 4, -1], [4, 1, 2, 3, -1]], dtype=np.int32)
+
+
+def posed_camera(K, R, C, lam=1.0):
+    """lam K [R | -R C] as [3][4]; lam multiplies the finished float64 matrix, so a power of two scales it exactly"""
+    R = np.asarray(R, dtype=np.float64)
+    return lam * (np.asarray(K, dtype=np.float64) @ np.hstack([R, -(R @ np.asarray(C, dtype=np.float64))[:, None]]))
+
+
+def look_at(C, target, roll_deg):
+    """The rotation (world -> camera) whose optical axis points from C at target, x to the right of world y, then rolled about
+    the optical axis by roll_deg"""
+    z = np.asarray(target, dtype=np.float64) - np.asarray(C, dtype=np.float64)
+    z /= np.linalg.norm(z)
+    x = np.cross([0.0, 1.0, 0.0], z)
+    x /= np.linalg.norm(x)
+    c, s = np.cos(np.radians(roll_deg)), np.sin(np.radians(roll_deg))
+    return np.array([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]]) @ np.stack([x, np.cross(z, x), z])
+
+
+def scaled_cameras(P, scales):
+    return np.asarray(P, dtype=np.float64).reshape(-1, 12) * np.asarray(scales, dtype=np.float64)[:, None]
+
+
+def scene_rotated(seed=1, W=SCENE_W, H=SCENE_H):
+    """scene()'s world (back plane z = 4, front rectangle z = 3, scene_render's textures) from SCENE_CENTRES, every optical axis
+    at ROT_TARGET and rolled by ROT_ROLLS, through ROT_K (skew, two focal lengths, an off-centre principal point).  Pixel (u, v)
+    sees along C + t R^T K^-1 (u, v, 1).  -> dict(gray [5][H][W], ztrue [5][H][W] = R[2] . (X - C), X [5][H][W][3], P [5][12]
+    at scale 1, R, C, ktrue in planes, range)"""
+    tex = scene_texture(seed)
+    v, u = np.mgrid[0:H, 0:W].astype(np.float64)
+    pix = np.stack([u, v, np.ones_like(u)], -1)
+    Kinv = np.linalg.inv(ROT_K)
+    gray, ztrue, Xs, Ps, Rs = [], [], [], [], []
+    for C, roll in zip(SCENE_CENTRES, ROT_ROLLS):
+        C = np.asarray(C, dtype=np.float64)
+        Rm = look_at(C, ROT_TARGET, roll)
+        d = pix @ (Rm.T @ Kinv).T                     # the ray directions in the world
+        tb, tf = (4.0 - C[2]) / d[..., 2], (3.0 - C[2]) / d[..., 2]
+        Xf = C + tf[..., None] * d
+        hit = (np.abs(Xf[..., 0]) < 0.5) & (np.abs(Xf[..., 1]) < 0.35)
+        X = np.where(hit[..., None], Xf, C + tb[..., None] * d)
+        gray.append(np.where(hit, tex(X[..., 0] + 7.3, X[..., 1] + 1.1), tex(X[..., 0], X[..., 1])).astype(np.float32))
+        ztrue.append((X - C) @ Rm[2])
+        Xs.append(X)
+        Ps.append(posed_camera(ROT_K, Rm, C).reshape(12))
+        Rs.append(Rm)
+    z = np.stack(ztrue)
+    izf, izn = SCENE_IZ
+    return dict(gray=np.stack(gray), ztrue=z, X=np.stack(Xs), P=np.stack(Ps), R=np.stack(Rs), C=np.array(SCENE_CENTRES),
+                ktrue=(1.0 / z - izf) / (izn - izf) * (SCENE_D - 1), range=(2.0, 6.0))
+
+
+def assert_scaled_tables(plain, scaled, views, lam):
+    """Cameras scaled by powers of two lam[f] scale the tables exactly: w_k by lam_r, A by lam_s / lam_r, b by lam_s"""
+    views, lam = np.asarray(views), np.asarray(lam, dtype=np.float64)
+    for r in range(len(views)):
+        lr = lam[views[r, 0]]
+        assert (scaled["planes"][r] == lr * plain["planes"][r]).all(), r
+        for s, f in enumerate(views[r, 1:]):
+            if f < 0:
+                assert np.isnan(scaled["warp"][r, s]).all() and np.isnan(plain["warp"][r, s]).all()
+                continue
+            assert np.isfinite(scaled["warp"][r, s]).all(), (r, s)
+            assert (scaled["warp"][r, s, :9] == (lam[f] / lr) * plain["warp"][r, s, :9]).all(), (r, s)
+            assert (scaled["warp"][r, s, 9:] == lam[f] * plain["warp"][r, s, 9:]).all(), (r, s)
+
+
+def saturated_case(W=35, H=34, S=8, D=9):
+    """The largest raw cost the rule can give: the reference image x + W y, S sources that are its negative (every census bit
+    the other way), 1 + S identical cameras (the warp is the identity at every plane) -> gray, P, views, ranges, parameters"""
+    v, u = np.mgrid[0:H, 0:W]
+    g = (u + W * v).astype(np.float32)
+    gray = np.stack([g] + [-g] * S)
+    P = np.stack([scene_camera((0.0, 0.0, 0.0), W, H, 40.0).reshape(12)] * (1 + S))
+    return gray, P, np.arange(1 + S, dtype=np.int32)[None], [(2.0, 6.0)], dict(D=D, a=3, min_views=S)
+
+
+def within_one_plane(kq8, flags, ktrue):
+    """per map the fraction of its pixels that carry no flag and lie within one plane of the truth"""
+    good = (np.asarray(flags) == 0) & (np.abs(np.asarray(kq8) / 256.0 - ktrue) <= 1.0)
+    return good.reshape(len(good), -1).mean(1)

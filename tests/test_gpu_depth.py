@@ -1,8 +1,9 @@
 """GPU tests of the dense stage (pgx_gray_batch_dev, pgx_depth_maps_dev, pgx_depth_fuse_dev and the two host forms; k_depth.hip)
 against tests/depth_ref.py: every integer output and every bit of d_depth equals the yardstick's, which is evaluated on the
 device's own d_warp and d_planes; those two are held to the yardstick's at 1e-9 of their largest entry (they differ by the
-rounding of a 3 x 3 adjugate at the most).  The shapes are the smallest at which the kernels can go wrong: the sweep's and the
-census' tiles and the filter's scan block and grid are read from the kernel source."""
+rounding of a 3 x 3 adjugate at the most), and on the rotated rig to exact rationals within a derived bound, block by block
+(ref.exact_warp), with the maps and the filter against the rendered truth.  The shapes are the smallest at which the kernels
+can go wrong: the sweep's and the census' tiles and the filter's scan block and grid are read from the kernel source."""
 import functools
 import os
 import re
@@ -391,6 +392,196 @@ def test_fuse_compaction_past_a_scan_block_and_a_grid_pass(engine):
     e = ref.fuse(depth, views, 5, P, 0.01, 2)
     check_fuse(f, e, 6.0)
     assert NT < e["summary"][0] < e["summary"][1]
+
+
+def test_fuse_inputs_that_are_finite_but_no_depths(engine):
+    """0.0, negative and infinite entries among the rendered depths of the rotated rig, as the pixel's own z (0 and negatives
+    count as depths: the rule asks for finite only) and as the z_j a valid pixel projects onto."""
+    sc = ref.scene_rotated()
+    rng = np.random.default_rng(31)
+    depth = sc["ztrue"].copy()
+    bad = np.array([0.0, -0.0, -3.5, -1e-300, np.inf, -np.inf])
+    pick = rng.random(depth.shape) < 0.25
+    depth[pick] = rng.choice(bad, pick.sum())
+    # pixels of map 1 that keep their depth and see map 2 where it holds such a value: every kind occurs as a z_j
+    P2 = sc["P"][2].reshape(3, 4)
+    q = sc["X"][1] @ P2[:, :3].T + P2[:, 3]
+    ok, iu, iv = ref.pixel(q[..., 0], q[..., 1], q[..., 2], ref.SCENE_W, ref.SCENE_H)
+    zj = depth[2][iv, iu][ok & ~pick[1]]
+    assert all((zj == b).any() for b in bad) and (np.signbit(zj) & (zj == 0)).any()
+    for views, ma in ((ref.all_views(), 1), (ref.ROT_VIEWS, 0)):
+        f = run_fuse(engine, depth, views, sc["P"], rel_tol=0.05, min_agree=ma)
+        e = ref.fuse(depth, views, 5, sc["P"], 0.05, ma)
+        check_fuse(f, e, 6.0)
+        assert 0 < e["summary"][0] and e["summary"][1] == np.isfinite(depth).sum() < depth.size
+    assert e["summary"][0] == e["summary"][1]                  # min_agree 0 keeps 0.0 and the negatives too
+
+
+def fuse_refused(engine, R=2, S=1, W=8, H=8, rel_tol=0.05, min_agree=1, max_points=16, alloc=None):
+    """pgx_depth_fuse_dev with these arguments over sentinel-filled buffers of size alloc = (R, W, H): refused, nothing written"""
+    aR, aW, aH = alloc or (R, W, H)
+    i32 = dict(dtype=torch.int32, device=DEV)
+    dd = torch.full((aR, aH, aW), 4.0, dtype=torch.float64, device=DEV)
+    dv, dP = torch.zeros((aR, 1 + S), **i32), torch.zeros((2, 12), dtype=torch.float64, device=DEV)
+    xyz, src = torch.full((16, 3), 5.0, dtype=torch.float64, device=DEV), torch.full((16, 2), 77, **i32)
+    ag, summary = torch.full((aR, aH, aW), 77, **i32), torch.full((4,), 77, **i32)
+    torch.cuda.synchronize()
+    with pytest.raises(pg.ArgumentException):
+        engine.depth_fuse_dev(dd, dv, R, S, W, H, 2, dP, max_points, xyz, src, summary, rel_tol=rel_tol, min_agree=min_agree, d_agree=ag)
+    torch.cuda.synchronize()
+    engine.check_status()
+    assert (xyz == 5.0).all() and (src == 77).all() and (ag == 77).all() and (summary == 77).all()
+
+
+@pytest.mark.parametrize("kw", [dict(S=0), dict(S=9), dict(rel_tol=-1e-300), dict(rel_tol=float("nan")), dict(rel_tol=float("inf")),
+                                dict(rel_tol=float("-inf")), dict(min_agree=-1), dict(max_points=-1), dict(R=65536, W=1, H=1),
+                                dict(R=1, W=32768, H=32769, alloc=(1, 8, 8))], ids=lambda kw: ",".join("%s=%s" % i for i in kw.items()))
+def test_fuse_refusals(engine, kw):
+    """fuse_args checks everything before the workspace is sized and a kernel launched, so the call over 2^30 pixels returns
+    without touching its (small) buffers."""
+    fuse_refused(engine, **kw)
+
+
+def maps_refused(engine, F=2, W=8, H=8, R=1, S=1, n_frames=None, alloc=None):
+    """pgx_depth_maps_dev with these sizes over sentinel-filled buffers of size alloc = (F, W, H, R): refused, nothing written"""
+    aF, aW, aH, aR = alloc or (F, W, H, R)
+    nf = F if n_frames is None else n_frames
+    i32 = dict(dtype=torch.int32, device=DEV)
+    f64 = dict(dtype=torch.float64, device=DEV)
+    dg, dP = torch.zeros((aF, aH, aW), dtype=torch.float32, device=DEV), torch.zeros((max(nf, aF), 12), **f64)
+    dv, dr = torch.zeros((aR, 1 + S), **i32), torch.ones((aR, 2), **f64)
+    out = [torch.full((aR, aH, aW), 77, **i32) for _ in range(3)] + [torch.full((8,), 77, **i32)]
+    dep, warp, planes = torch.full((aR, aH, aW), 5.0, **f64), torch.full((aR, S, 12), 5.0, **f64), torch.full((aR, 8), 5.0, **f64)
+    torch.cuda.synchronize()
+    with pytest.raises(pg.ArgumentException):
+        engine.depth_maps_dev(dg, F, W, H, nf, dP, dv, R, S, dr, 8, out[0], dep, out[1], out[3], agg_radius=1, min_views=1,
+                              max_cost=BIG, d_cost=out[2], d_warp=warp, d_planes=planes)
+    torch.cuda.synchronize()
+    engine.check_status()
+    assert all((o == 77).all() for o in out) and all((o == 5.0).all() for o in (dep, warp, planes))
+
+
+@pytest.mark.parametrize("kw", [dict(R=65536, W=1, H=1), dict(F=65536, W=1, H=1), dict(F=1, R=1, W=32768, H=32769, alloc=(1, 8, 8, 1)),
+                                dict(F=1, R=3, W=32768, H=16384, alloc=(1, 8, 8, 3)), dict(F=3, R=1, W=16384, H=32768, alloc=(3, 8, 8, 1)),
+                                dict(n_frames=3), dict(n_frames=1)], ids=lambda kw: ",".join("%s=%s" % i for i in kw.items()))
+def test_maps_refusals(engine, kw):
+    """depth_args checks everything before the workspace is sized and a kernel launched: R and F one above their limit at
+    1 x 1, max(F, R) W H above 2^30 through R, through F and by one row, n_frames on either side of F without ids."""
+    maps_refused(engine, **kw)
+
+
+# ---- general cameras: rotated, rolled, skewed, scaled, mirrored --------------------------------------------------------
+
+ROT_FLOOR = 0.81       # tests/test_depth_ref.py: 0.05 below the yardstick's lowest fraction of references 1 to 4, rounded down
+
+
+@functools.lru_cache(maxsize=None)
+def rotated(engine):
+    """ref.scene_rotated() and the device's maps of it at scale 1 over ROT_VIEWS"""
+    sc = ref.scene_rotated()
+    ranges = [sc["range"]] * 5
+    return sc, ranges, run_maps(engine, sc["gray"], sc["P"], ref.ROT_VIEWS, ranges, ref.SCENE_D, 2, 2, BIG)
+
+
+def test_rotated_rig_with_mixed_scales(engine):
+    """Cameras lam K [R | -R C] at scales (-2.5, 1, 1e-3, 40, 0.3): the integers and depth bits against the yardstick on the
+    device's tables, the tables per (r, s) block against exact rationals within the forward bound of rule 3 in float64, the
+    planes within 4 u of the exact scale, the maps against the rendered truth.  Measured on an MI355X: the worst warp entry at
+    0.0991 of its bound, the worst plane at 1.982 u, which are the yardstick's figures; within one plane 0.9645, 0.8742,
+    0.8296, 0.8571, 0.8812 of the five references' pixels (ROT_VIEWS keep the negated frame 0 out of the other rows)."""
+    sc, ranges, _ = rotated(engine)
+    P = ref.scaled_cameras(sc["P"], ref.ROT_SCALES)
+    got = run_maps(engine, sc["gray"], P, ref.ROT_VIEWS, ranges, ref.SCENE_D, 2, 2, BIG)
+    check_maps(got, sc["gray"], P, ref.ROT_VIEWS, ranges, ref.SCENE_D, 2, 2, BIG)
+    w, p = ref.plan_against_exact(P, ref.ROT_VIEWS, ranges, ref.SCENE_D, got["warp"], got["planes"])
+    frac = ref.within_one_plane(got["kq8"], got["flags"], sc["ktrue"])
+    print("device: worst warp error %.4f of its bound, worst plane error %.3f u; within one plane %s" % (w, p, np.round(frac, 4)))
+    assert w <= 1.0 and p <= 4.0
+    assert (got["planes"][0] < 0).all() and (got["planes"][1:] > 0).all()
+    assert frac[0] >= 0.95 and (frac[1:] >= ROT_FLOOR).all()
+
+
+def test_power_of_two_scales_change_no_bit(engine):
+    sc, ranges, plain = rotated(engine)
+    check_maps(plain, sc["gray"], sc["P"], ref.ROT_VIEWS, ranges, ref.SCENE_D, 2, 2, BIG)
+    P = ref.scaled_cameras(sc["P"], ref.ROT_SCALES_POW2)
+    got = run_maps(engine, sc["gray"], P, ref.ROT_VIEWS, ranges, ref.SCENE_D, 2, 2, BIG)
+    ref.assert_scaled_tables(plain, got, ref.ROT_VIEWS, ref.ROT_SCALES_POW2)
+    assert (got["planes"][0] == -4.0 * plain["planes"][0]).all()
+    for k in ("kq8", "flags", "cost", "depth", "summary"):
+        assert bits(got[k]) == bits(plain[k]), k
+    assert plain["summary"][1] > 0.8 * plain["summary"][0]
+    f1, f2 = (run_fuse(engine, plain["depth"], ref.ROT_VIEWS, p) for p in (sc["P"], P))
+    check_fuse(f1, ref.fuse(plain["depth"], ref.ROT_VIEWS, 5, sc["P"], 0.05, 2), 6.0)
+    for k in ("xyz", "src", "agree", "summary"):
+        assert bits(f1[k]) == bits(f2[k]), k
+    assert f1["summary"][0] > 0.8 * f1["summary"][1] > 0
+
+
+def test_a_negated_source_is_an_absent_source(engine):
+    """-P is the same camera with det M < 0: q_2 < 0 for every point in front of it, so rule 4 passes over it as a source, in
+    both calls, while its warp is finite.  As a reference it still gives its own points, bit for bit."""
+    sc, ranges, _ = rotated(engine)
+    P = sc["P"].copy()
+    P[4] = -P[4]
+    views = ref.ROT_VIEWS[:4]                                    # frame 4 is a source of every row and the reference of none
+    absent = np.where(views == 4, -1, views)
+    got = run_maps(engine, sc["gray"], P, views, ranges[:4], ref.SCENE_D, 2, 2, BIG)
+    exp = run_maps(engine, sc["gray"], sc["P"], absent, ranges[:4], ref.SCENE_D, 2, 2, BIG)
+    check_maps(got, sc["gray"], P, views, ranges[:4], ref.SCENE_D, 2, 2, BIG)
+    for k in ("kq8", "flags", "cost", "depth", "summary"):
+        assert bits(got[k]) == bits(exp[k]), k
+    at = views[:, 1:] == 4
+    assert at.sum() == 4 and np.isfinite(got["warp"][at]).all() and np.isnan(exp["warp"][at]).all()
+    assert np.isfinite(got["warp"][views[:, 1:] >= 0]).all() and np.isnan(got["warp"][views[:, 1:] < 0]).all()
+    assert got["summary"][1] > 0
+    # the filter: frame 4 named by no row (passed over either way), then as the reference of a row of its own
+    for v in (views, ref.ROT_VIEWS):
+        gone = np.c_[v[:, 0], np.where(v[:, 1:] == 4, -1, v[:, 1:])]
+        f = run_fuse(engine, sc["ztrue"][:len(v)], v, P, min_agree=1)
+        e = run_fuse(engine, sc["ztrue"][:len(v)], gone, sc["P"], min_agree=1)
+        check_fuse(f, ref.fuse(sc["ztrue"][:len(v)], v, 5, P, 0.05, 1), 6.0)
+        for k in ("xyz", "src", "agree", "summary"):
+            assert bits(f[k]) == bits(e[k]), k
+        assert f["summary"][0] > 0
+    assert (f["src"][:f["summary"][0], 0] == 4).any()
+
+
+@pytest.mark.parametrize("scales", [(1.0,) * 5, ref.ROT_SCALES_POW2], ids=["scale1", "pow2"])
+def test_fuse_at_the_true_depths_of_the_rotated_rig(engine, scales):
+    """The filter fed the rendered depths: every kept point is the rendered X of its pixel, one agreeing view at 5 % keeps at
+    least 0.95 of the pixels (the yardstick: 29249 of 30720), and powers of two change no bit."""
+    sc = ref.scene_rotated()
+    f = run_fuse(engine, sc["ztrue"], ref.ROT_VIEWS, ref.scaled_cameras(sc["P"], scales), min_agree=1)
+    e = ref.fuse(sc["ztrue"], ref.ROT_VIEWS, 5, sc["P"], 0.05, 1)
+    check_fuse(f, e, 6.0)
+    n = int(f["summary"][0])
+    X = sc["X"].reshape(5, -1, 3)[f["src"][:n, 0], f["src"][:n, 1]]
+    print("kept %d of %d, worst |xyz - X| %.2e" % (n, f["summary"][1], np.abs(f["xyz"][:n] - X).max()))
+    assert np.abs(f["xyz"][:n] - X).max() <= 1e-9 * 6.0
+    assert f["summary"][1] == sc["ztrue"].size and n >= 0.95 * f["summary"][1]
+    if scales[0] != 1.0:
+        plain = run_fuse(engine, sc["ztrue"], ref.ROT_VIEWS, sc["P"], min_agree=1)
+        for k in ("xyz", "src", "agree", "summary"):
+            assert bits(f[k]) == bits(plain[k]), k
+
+
+def test_saturated_costs(engine):
+    """The 9-bit raw field of the sweep at the most it can be asked to hold, 8 x 62 = 496 with nvalid = 8 above it, and the
+    7 x 7 box of it, 24304: at exactly the yardstick's 702 pixels; all planes tie, so k* = 0 and EDGE everywhere; max_cost at
+    and one below."""
+    gray, P, views, ranges, kw = ref.saturated_case()
+    runs = {}
+    for mc in (BIG, 24304, 24303):
+        got = run_maps(engine, gray, P, views, ranges, kw["D"], kw["a"], kw["min_views"], mc)
+        e = check_maps(got, gray, P, views, ranges, kw["D"], kw["a"], kw["min_views"], mc)
+        runs[mc] = got
+        assert (got["cost"] == e["cost"]).all() and got["cost"].max() == 49 * 496 == 24304
+        assert ((got["cost"] == 24304) == (e["cost"] == 24304)).all() and (got["cost"] == 24304).sum() == 702
+        assert ((got["flags"] & ~ref.HIGHCOST) == ref.EDGE).all() and (got["kq8"] == -1).all()
+    assert (runs[BIG]["flags"] == ref.EDGE).all() and (runs[24304]["flags"] == ref.EDGE).all()
+    assert ((runs[24303]["flags"] & ref.HIGHCOST) != 0).sum() == 702
+    assert (((runs[24303]["flags"] & ref.HIGHCOST) != 0) == (runs[BIG]["cost"] == 24304)).all()
 
 
 # ---- grey images ----------------------------------------------------------------------------------------------------------
