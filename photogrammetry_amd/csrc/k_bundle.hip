@@ -25,7 +25,14 @@
 // Determinism: per-track sums are xor butterflies over G = 16 lanes (their bits depend on the track's length only), the
 // reduced system's sums run in track order, and the sums over tracks are strided by 1024 and tree-reduced in a fixed shape.
 // Nothing depends on the grid, max_tracks, the slot layout or the run.  DESIGN.md section 16 has the measurements.
-#include "pgx_trackgraph.h"
+#include "pgx_stage_args.h"
+
+// what BaArgs::ctrl points to
+struct BaCtrl {
+    double lam, C, cam_dx2, cam_x2;
+    int it, acc, reason, done, relin, sel, pdfail, nonpd;
+    int n_free, n_fixed, err, nt, n_part, n_used, zneg, pad;
+};
 
 namespace {
 
@@ -38,37 +45,6 @@ constexpr int BA_LD = 6 * BA_MAX_FREE;  // leading dimension of S
 constexpr int BA_CH = 32;         // tracks per chunk of k_ba_schur
 constexpr int BA_ND = 21;         // doubles per node: Jc [2][6], Jp [2][3], r [2], w
 constexpr int FS_UNKNOWN = -1, FS_FIXED = -2;   // frame state; >= 0: the free frame's number
-
-struct BaCtrl {
-    double lam, C, cam_dx2, cam_x2;
-    int it, acc, reason, done, relin, sel, pdfail, nonpd;
-    int n_free, n_fixed, err, nt, n_part, n_used, zneg, pad;
-};
-
-struct BaArgs {
-    TrackView tv;
-    const double *K, *Rt_in;     // [n_frames][4], [n_frames][12]
-    const int32_t *fixed;        // [n_frames]
-    const double *xyz_in;        // [max_tracks][3]
-    const int32_t *track_flags;  // [max_tracks] or nullptr
-    int max_iters;
-    double huber, lambda0;
-    double *Rt_out, *P_out, *xyz_out, *node_err, *trace;
-    int32_t *report;
-    int *status;
-    // workspace
-    BaCtrl *ctrl;
-    int32_t *fstate, *free_frame, *cam_cnt, *csr_off; // [n_frames], [128] x3
-    double *cams;                // [2][n_frames][12] ping-pong by ctrl->sel
-    double *S, *rhs, *dc;        // [BA_LD][BA_LD], [BA_LD], [BA_LD]
-    double *X;                   // [2][max_tracks][3]
-    double *V, *g, *Vi;          // [max_tracks][6], [3], [6]
-    double *tcost, *tdx, *tx;    // [max_tracks] each
-    int32_t *part;               // [max_tracks]: used observations of a track that takes part, else 0
-    double *nd;                  // [node_cap][BA_ND]
-    int32_t *ncf;                // [node_cap]: free number, -1 used in a fixed frame, -2 unused
-    int32_t *csr_node, *csr_track;  // [node_cap]
-};
 
 // fixed-shape sum of v over the BA_RED threads of the workgroup (sh: BA_RED doubles of LDS); the result is in every thread
 __device__ double block_sum(double v, double *sh)
@@ -907,9 +883,10 @@ __global__ __launch_bounds__(BA_NT) void k_ba_out(BaArgs a)
 }
 
 // the workspace, described once: a's workspace pointers (none valid for ws = nullptr) and the bytes
-size_t ba_carve(BaArgs &a, void *ws, int n_frames, int max_tracks, long long node_cap)
+size_t ba_carve(BaArgs &a, void *ws)
 {
-    const size_t T = (size_t)(max_tracks > 0 ? max_tracks : 1), N = (size_t)(node_cap > 0 ? node_cap : 1);
+    const int n_frames = a.tv.n_frames;
+    const size_t T = (size_t)(a.tv.max_tracks > 0 ? a.tv.max_tracks : 1), N = (size_t)(a.tv.node_cap > 0 ? a.tv.node_cap : 1);
     WsCarver w(ws);
     a.ctrl = w.take<BaCtrl>(sizeof(BaCtrl));
     a.fstate = w.take<int32_t>((size_t)n_frames * 4);
@@ -944,43 +921,22 @@ int track_grid(int max_tracks)
 
 } // namespace
 
-size_t pgx_bundle_ws_bytes(int n_frames, int max_tracks, long long node_cap)
+size_t pgx_bundle_ws_bytes(const BaArgs &a)
 {
-    BaArgs a;
-    return ba_carve(a, nullptr, n_frames, max_tracks, node_cap);
+    BaArgs b = a;
+    return ba_carve(b, nullptr);
 }
 
-void pgx_launch_bundle(hipStream_t s, const pgx_keypoint *d_kp, int F, int stride, const int32_t *d_frame_ids, int n_frames,
-                       const double *d_K, const double *d_Rt_in, const int32_t *d_fixed, const int32_t *d_offsets, const int32_t *d_nodes,
-                       long long node_cap, const int32_t *d_track_summary, int max_tracks, const double *d_xyz_in,
-                       const int32_t *d_track_flags, int max_iters, double huber_px, double lambda0, double *d_Rt_out, double *d_P_out,
-                       double *d_xyz_out, double *d_node_err, double *d_trace, int32_t *d_report, void *ws, int *status)
+void pgx_launch_bundle(hipStream_t s, BaArgs a, void *ws)
 {
-    BaArgs a;
-    a.tv = TrackView{d_kp, d_frame_ids, d_offsets, d_nodes, d_track_summary, F, stride, n_frames, max_tracks, node_cap, nullptr};
-    a.K = d_K;
-    a.Rt_in = d_Rt_in;
-    a.fixed = d_fixed;
-    a.xyz_in = d_xyz_in;
-    a.track_flags = d_track_flags;
-    a.max_iters = max_iters;
-    a.huber = huber_px;
-    a.lambda0 = lambda0;
-    a.Rt_out = d_Rt_out;
-    a.P_out = d_P_out;
-    a.xyz_out = d_xyz_out;
-    a.node_err = d_node_err;
-    a.trace = d_trace;
-    a.report = d_report;
-    a.status = status;
-    ba_carve(a, ws, n_frames, max_tracks, node_cap);
-    const int grid = track_grid(max_tracks);
+    ba_carve(a, ws);
+    const int grid = track_grid(a.tv.max_tracks);
     hipLaunchKernelGGL(k_ba_frames, dim3(1), dim3(BA_NT), 0, s, a);
     hipLaunchKernelGGL(k_ba_setup, dim3(grid), dim3(BA_NT), 0, s, a);
     hipLaunchKernelGGL(k_ba_csr, dim3(BA_MAX_FREE), dim3(BA_NT), 0, s, a);
     hipLaunchKernelGGL(k_ba_lin, dim3(grid), dim3(BA_NT), 0, s, a, 1);
     hipLaunchKernelGGL(k_ba_start, dim3(1), dim3(BA_RED), 0, s, a);
-    for (int i = 0; i < max_iters; i++) {
+    for (int i = 0; i < a.max_iters; i++) {
         if (i > 0) hipLaunchKernelGGL(k_ba_lin, dim3(grid), dim3(BA_NT), 0, s, a, 0);
         hipLaunchKernelGGL(k_ba_vinv, dim3(grid), dim3(BA_NT), 0, s, a);
         hipLaunchKernelGGL(k_ba_schur, dim3(BA_MAX_FREE), dim3(BA_NT), 0, s, a);

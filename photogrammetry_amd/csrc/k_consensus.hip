@@ -24,7 +24,7 @@
 //   k_cns_write        grid-stride over the tracks in the same classes: a kept node goes to its rank inside the track (a
 //                      ballot prefix), the track's point and flag to its new index, d_track_of is rewritten
 // Counters are integers throughout (LDS, then one atomic per workgroup).  DESIGN.md section 22 has the measurements.
-#include "pgx_trackgraph.h"
+#include "pgx_stage_args.h"
 
 namespace {
 
@@ -39,24 +39,6 @@ constexpr int CNS_RAY = 6;              // doubles per known observation of a tr
 constexpr int CT_NODES_IN = 1, CT_OUTLIERS = 2, CT_NOCONS = 3, CT_SHORT = 4, CT_UNDECIDED = 5, CT_LONGEST = 6;
 
 static_assert(CNS_SCAN_ITEMS == CNS_NT * CNS_SCAN_PER_THREAD, "a scan block is CNS_SCAN_PER_THREAD tracks per thread");
-
-struct CnsArgs {
-    TrackView tv;
-    const double *P;              // [n_frames][12]
-    double inlier_px, cos2;
-    int min_inliers, min_len, max_hyp;
-    uint64_t seed;
-    int32_t *off_out, *nodes_out, *summary_out, *map, *flags_out, *stats, *track_of, *report;
-    double *xyz_out;
-    double *cam;                  // workspace [n_frames][CNS_CAM]
-    double *rays;                 // workspace [node_cap][CNS_RAY]: track t's known observations from its first node on
-    double *xyz;                  // workspace [max_tracks][3] by old index
-    int32_t *kept;                // workspace [max_tracks] nodes the track keeps, 0 = the track is removed
-    int32_t *bsum;                // workspace [scan blocks][2] tracks and nodes, exclusive after k_cns_scan_sums
-    int8_t *keep;                 // workspace [node_cap]
-    int32_t *meta;                // workspace [0] tracks to process, [CT_*] counters
-    int *status;
-};
 
 // a known observation as its owner lane holds it
 struct Obs {
@@ -465,9 +447,11 @@ int cns_grid(int max_tracks)
 int cns_scan_blocks(int max_tracks) { return max_tracks < 1 ? 1 : (int)(((long long)max_tracks + CNS_SCAN_ITEMS - 1) / CNS_SCAN_ITEMS); }
 
 // the workspace, described once: a's workspace pointers (none valid for ws = nullptr) and the bytes
-size_t cns_carve(CnsArgs &a, void *ws, int n_frames, int max_tracks, long long node_cap)
+size_t cns_carve(CnsArgs &a, void *ws)
 {
     WsCarver w(ws);
+    const int n_frames = a.tv.n_frames, max_tracks = a.tv.max_tracks;
+    const long long node_cap = a.tv.node_cap;
     const size_t mt = max_tracks < 1 ? 1 : max_tracks, nc = node_cap < 1 ? 1 : (size_t)node_cap;
     a.cam = w.take<double>((size_t)n_frames * CNS_CAM * sizeof(double));
     a.rays = w.take<double>(nc * CNS_RAY * sizeof(double));
@@ -482,40 +466,17 @@ size_t cns_carve(CnsArgs &a, void *ws, int n_frames, int max_tracks, long long n
 
 } // namespace
 
-size_t pgx_consensus_ws_bytes(int n_frames, int max_tracks, long long node_cap)
+size_t pgx_consensus_ws_bytes(const CnsArgs &a)
 {
-    CnsArgs a;
-    return cns_carve(a, nullptr, n_frames, max_tracks, node_cap);
+    CnsArgs b = a;
+    return cns_carve(b, nullptr);
 }
 
-void pgx_launch_consensus(pgx_ctx *ctx, hipStream_t s, const pgx_keypoint *d_kp, int F, int stride, const int32_t *d_frame_ids, int n_frames,
-                          const double *d_P, const int32_t *d_offsets, const int32_t *d_nodes, long long node_cap,
-                          const int32_t *d_track_summary, int max_tracks, double inlier_px, double cos2, int min_inliers, int min_len,
-                          int max_hyp, uint64_t seed, int32_t *d_offsets_out, int32_t *d_nodes_out, int32_t *d_summary_out,
-                          int32_t *d_track_map, double *d_xyz_out, int32_t *d_flags_out, int32_t *d_track_stats, int32_t *d_track_of,
-                          int32_t *d_report, void *ws, int *status)
+void pgx_launch_consensus(pgx_ctx *ctx, hipStream_t s, CnsArgs a, void *ws)
 {
-    CnsArgs a;
-    a.tv = TrackView{d_kp, d_frame_ids, d_offsets, d_nodes, d_track_summary, F, stride, n_frames, max_tracks, node_cap, nullptr};
-    a.P = d_P;
-    a.inlier_px = inlier_px;
-    a.cos2 = cos2;
-    a.min_inliers = min_inliers;
-    a.min_len = min_len < 1 ? 1 : min_len;
-    a.max_hyp = max_hyp;
-    a.seed = seed;
-    a.off_out = d_offsets_out;
-    a.nodes_out = d_nodes_out;
-    a.summary_out = d_summary_out;
-    a.map = d_track_map;
-    a.xyz_out = d_xyz_out;
-    a.flags_out = d_flags_out;
-    a.stats = d_track_stats;
-    a.track_of = d_track_of;
-    a.report = d_report;
-    a.status = status;
-    cns_carve(a, ws, n_frames, max_tracks, node_cap);
-    const int grid = cns_grid(max_tracks), nblk = cns_scan_blocks(max_tracks);
+    a.min_len = a.min_len < 1 ? 1 : a.min_len;
+    cns_carve(a, ws);
+    const int grid = cns_grid(a.tv.max_tracks), nblk = cns_scan_blocks(a.tv.max_tracks);
     // the profiling groups of the stage's parts (pgx_profile_get; nothing is recorded while profiling is off)
     {
         ProfScope ps(ctx, "consensus_frames", s);

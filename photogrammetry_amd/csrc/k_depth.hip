@@ -24,7 +24,7 @@
 //   k_fuse_write   the kept pixels of a block at block offset + rank in the block (block_excl_scan): the list is in (r, v, u)
 //                  order whatever the grid
 // Counters are integer atomics only.  DESIGN.md section 26.
-#include "pgx_trackgraph.h"
+#include "pgx_stage_args.h"
 
 namespace {
 
@@ -36,47 +36,6 @@ constexpr int DEP_PEN = 31;            // cost of a source that does not see the
 constexpr int CEN_TW = 32, CEN_TH = 8; // the census tile
 constexpr int FUSE_GRID_MAX = 1024;    // workgroups of k_fuse_count / k_fuse_write, grid-stride beyond
 constexpr int FUSE_CAM = 16;           // doubles per map in the filter's camera table: adj (9), det, sign, ||m3||, known, 3 unused
-
-struct DepArgs {
-    const float *gray;            // [F][H][W]
-    int F, W, H;
-    const int32_t *frame_ids;     // [F] or nullptr
-    int n_frames;
-    const double *P;              // [n_frames][12]
-    const int32_t *views;         // [R][1 + S]
-    int R, S;
-    const double *range;          // [R][2]
-    int D, min_views, max_cost;
-    int32_t *kq8;
-    double *depth;
-    int32_t *cost;                // or nullptr
-    int32_t *flags;
-    double *warp_out, *planes_out; // or nullptr
-    int32_t *summary;
-    uint2 *census;                // workspace [F][H][W]
-    double *warp;                 // workspace [R][S][12]: A row-major, then b
-    int32_t *slot;                // workspace [R][1 + S]: the slot of the reference (-1: NOCAMERA) and of every valid source (-1: none)
-    double *planes;               // workspace [R][D]: w_k
-};
-
-struct FuseArgs {
-    const double *depth;          // [R][H][W]
-    const int32_t *views;
-    int R, S, W, H, n_frames;
-    const double *P;
-    double rel_tol;
-    int min_agree, max_points;
-    double *xyz;
-    int32_t *src;
-    int32_t *agree;               // or nullptr
-    int32_t *summary;
-    double *cam;                  // workspace [R][FUSE_CAM]
-    int32_t *rowof;               // workspace [R][S]: the map a source is compared with, -1 = none
-    unsigned char *keep;          // workspace [nb * 256]
-    int32_t *bsum, *boff;         // workspace [nb]: kept pixels per block, their exclusive scan
-    int nb;                       // blocks of 256 pixels
-    int *status;
-};
 
 // adj(M) (adj[3 i + j]; M^-1 = adj / det) and det M of a 3 x 4 camera; false if an entry is not finite or det == 0
 __device__ __forceinline__ bool dep_camera(const double *p, double (&adj)[9], double &det)
@@ -515,36 +474,28 @@ size_t fuse_carve(FuseArgs &a, void *ws)
 
 } // namespace
 
-size_t pgx_depth_ws_bytes(int F, int W, int H, int R, int S, int D)
+size_t pgx_depth_ws_bytes(const DepArgs &a)
 {
-    DepArgs a{};
-    a.F = F; a.W = W; a.H = H; a.R = R; a.S = S; a.D = D;
-    return dep_carve(a, nullptr);
+    DepArgs b = a;
+    return dep_carve(b, nullptr);
 }
 
-void pgx_launch_depth_maps(pgx_ctx *ctx, hipStream_t s, const float *d_gray, int F, int W, int H, const int32_t *d_frame_ids, int n_frames,
-                           const double *d_P, const int32_t *d_views, int R, int S, const double *d_range, int D, int agg_radius,
-                           int min_views, int max_cost, int32_t *d_kq8, double *d_depth, int32_t *d_cost, int32_t *d_flags, double *d_warp,
-                           double *d_planes, int32_t *d_summary, void *ws)
+void pgx_launch_depth_maps(pgx_ctx *ctx, hipStream_t s, DepArgs a, int agg_radius, void *ws)
 {
-    DepArgs a{};
-    a.gray = d_gray; a.F = F; a.W = W; a.H = H; a.frame_ids = d_frame_ids; a.n_frames = n_frames; a.P = d_P;
-    a.views = d_views; a.R = R; a.S = S; a.range = d_range; a.D = D; a.min_views = min_views; a.max_cost = max_cost;
-    a.kq8 = d_kq8; a.depth = d_depth; a.cost = d_cost; a.flags = d_flags; a.warp_out = d_warp; a.planes_out = d_planes;
-    a.summary = d_summary;
+    const int W = a.W, H = a.H;
     dep_carve(a, ws);
     {
         ProfScope ps(ctx, "depth_census", s);
         const unsigned tiles = (unsigned)(((W + CEN_TW - 1) / CEN_TW) * ((H + CEN_TH - 1) / CEN_TH));
-        hipLaunchKernelGGL(k_dep_census, dim3(tiles, (unsigned)F), dim3(DEP_NT), 0, s, d_gray, W, H, a.census);
+        hipLaunchKernelGGL(k_dep_census, dim3(tiles, (unsigned)a.F), dim3(DEP_NT), 0, s, a.gray, W, H, a.census);
     }
     {
         ProfScope ps(ctx, "depth_plan", s);
-        hipLaunchKernelGGL(k_dep_plan, dim3((unsigned)R), dim3(DEP_NT), 0, s, a);
+        hipLaunchKernelGGL(k_dep_plan, dim3((unsigned)a.R), dim3(DEP_NT), 0, s, a);
     }
     {
         ProfScope ps(ctx, "depth_sweep", s);
-        const dim3 grid((unsigned)(((W + DEP_TW - 1) / DEP_TW) * ((H + DEP_TH - 1) / DEP_TH)), (unsigned)R);
+        const dim3 grid((unsigned)(((W + DEP_TW - 1) / DEP_TW) * ((H + DEP_TH - 1) / DEP_TH)), (unsigned)a.R);
         switch (agg_radius) {
         case 0: hipLaunchKernelGGL(k_dep_sweep<0>, grid, dim3(DEP_NT), 0, s, a); break;
         case 1: hipLaunchKernelGGL(k_dep_sweep<1>, grid, dim3(DEP_NT), 0, s, a); break;
@@ -554,25 +505,18 @@ void pgx_launch_depth_maps(pgx_ctx *ctx, hipStream_t s, const float *d_gray, int
     }
 }
 
-size_t pgx_depth_fuse_ws_bytes(int R, int S, int W, int H)
+size_t pgx_depth_fuse_ws_bytes(const FuseArgs &a)
 {
-    FuseArgs a{};
-    a.R = R; a.S = S; a.W = W; a.H = H;
-    return fuse_carve(a, nullptr);
+    FuseArgs b = a;
+    return fuse_carve(b, nullptr);
 }
 
-void pgx_launch_depth_fuse(pgx_ctx *ctx, hipStream_t s, const double *d_depth, const int32_t *d_views, int R, int S, int W, int H,
-                           int n_frames, const double *d_P, double rel_tol, int min_agree, int max_points, double *d_xyz, int32_t *d_src,
-                           int32_t *d_agree, int32_t *d_summary, void *ws, int *status)
+void pgx_launch_depth_fuse(pgx_ctx *ctx, hipStream_t s, FuseArgs a, void *ws)
 {
-    FuseArgs a{};
-    a.depth = d_depth; a.views = d_views; a.R = R; a.S = S; a.W = W; a.H = H; a.n_frames = n_frames; a.P = d_P;
-    a.rel_tol = rel_tol; a.min_agree = min_agree; a.max_points = max_points; a.xyz = d_xyz; a.src = d_src; a.agree = d_agree;
-    a.summary = d_summary; a.status = status;
     fuse_carve(a, ws);
     ProfScope ps(ctx, "depth_fuse", s);
     const unsigned grid = (unsigned)(a.nb < FUSE_GRID_MAX ? a.nb : FUSE_GRID_MAX);
-    hipLaunchKernelGGL(k_fuse_plan, dim3((unsigned)R), dim3(DEP_NT), 0, s, a);
+    hipLaunchKernelGGL(k_fuse_plan, dim3((unsigned)a.R), dim3(DEP_NT), 0, s, a);
     hipLaunchKernelGGL(k_fuse_count, dim3(grid), dim3(DEP_NT), 0, s, a);
     hipLaunchKernelGGL(k_fuse_scan, dim3(1), dim3(DEP_NT), 0, s, a);
     hipLaunchKernelGGL(k_fuse_write, dim3(grid), dim3(DEP_NT), 0, s, a);

@@ -17,7 +17,7 @@
 //   k_init_pick    one workgroup: the report, the choice (two integer keys: the wide count then the smaller frame of a,
 //                  and the smaller frame of b then the smaller m), the per-frame arrays
 // DESIGN.md section 21 has the measurements.
-#include "pgx_trackgraph.h"
+#include "pgx_stage_args.h"
 #include "pgx_eig.h"
 
 namespace {
@@ -27,20 +27,6 @@ static_assert(INIT_NT == 256, "block_sum_i (pgx_trackgraph.h) adds up four waves
 constexpr int INIT_ROWS = 2048;   // list entries per scoring workgroup before a pair gets another one
 constexpr int INIT_WS_D = 32;     // doubles per pair: R1 [9], R2 [9], t [3], K_a [4], K_b [4], 3 spare
 constexpr int INIT_WS_I = 12;     // ints per pair: flags, frame of a, frame of b, n, front [4], wide [4]
-
-struct InitArgs {
-    const pgx_keypoint *kp;
-    const pgx_pair *matches;
-    const int32_t *counts, *pairlist, *frame_ids;
-    const double *F, *K;
-    int M, nslots, stride, n_frames, max_dist, min_points, split;
-    double cos2, min_front_frac;
-    double *Rt_pair, *sigma, *cand_Rt, *Rt_out, *P_out;
-    int32_t *pair_stats, *fixed_out, *register_out, *report;
-    // workspace
-    double *wd;    // [M][INIT_WS_D]
-    int32_t *wi;   // [M][INIT_WS_I]
-};
 
 __device__ __forceinline__ double dot3(double a0, double a1, double a2, double b0, double b1, double b2)
 {
@@ -409,9 +395,9 @@ __global__ __launch_bounds__(INIT_NT) void k_init_pick(InitArgs a)
         }
 }
 
-size_t init_carve(InitArgs &a, void *ws, int M)
+size_t init_carve(InitArgs &a, void *ws)
 {
-    const size_t Mc = (size_t)(M > 0 ? M : 1);
+    const size_t Mc = (size_t)(a.M > 0 ? a.M : 1);
     WsCarver w(ws);
     a.wd = w.take<double>(Mc * INIT_WS_D * 8);
     a.wi = w.take<int32_t>(Mc * INIT_WS_I * 4);
@@ -420,45 +406,17 @@ size_t init_carve(InitArgs &a, void *ws, int M)
 
 } // namespace
 
-size_t pgx_init_pair_ws_bytes(int M)
+size_t pgx_init_pair_ws_bytes(const InitArgs &a)
 {
-    InitArgs a;
-    return init_carve(a, nullptr, M);
+    InitArgs b = a;
+    return init_carve(b, nullptr);
 }
 
-void pgx_launch_init_pair(hipStream_t s, const pgx_keypoint *d_kp, const pgx_pair *d_matches, const int32_t *d_counts,
-                          const int32_t *d_pairlist, int M, int F, int stride, const int32_t *d_frame_ids, int n_frames, int max_dist,
-                          const double *d_F, const double *d_K, double cos2, double min_front_frac, int min_points, double *d_Rt_pair,
-                          int32_t *d_pair_stats, double *d_sigma, double *d_cand_Rt, double *d_Rt_out, double *d_P_out,
-                          int32_t *d_fixed_out, int32_t *d_register_out, int32_t *d_report, void *ws)
+void pgx_launch_init_pair(hipStream_t s, InitArgs a, void *ws)
 {
-    InitArgs a;
-    a.kp = d_kp;
-    a.matches = d_matches;
-    a.counts = d_counts;
-    a.pairlist = d_pairlist;
-    a.frame_ids = d_frame_ids;
-    a.F = d_F;
-    a.K = d_K;
-    a.M = M;
-    a.nslots = F;
-    a.stride = stride;
-    a.n_frames = n_frames;
-    a.max_dist = max_dist;
-    a.min_points = min_points;
+    const int M = a.M, stride = a.stride;
     a.split = (stride + INIT_ROWS - 1) / INIT_ROWS;
-    a.cos2 = cos2;
-    a.min_front_frac = min_front_frac;
-    a.Rt_pair = d_Rt_pair;
-    a.sigma = d_sigma;
-    a.cand_Rt = d_cand_Rt;
-    a.Rt_out = d_Rt_out;
-    a.P_out = d_P_out;
-    a.pair_stats = d_pair_stats;
-    a.fixed_out = d_fixed_out;
-    a.register_out = d_register_out;
-    a.report = d_report;
-    init_carve(a, ws, M);
+    init_carve(a, ws);
     // the second grid dimension holds 65535 workgroups: longer pair lists go in slices (the kernels of a slice see its pointers)
     for (int m0 = 0; m0 < M; m0 += 65535) {
         InitArgs b = a;

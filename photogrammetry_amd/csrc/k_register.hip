@@ -25,7 +25,7 @@
 //   k_reg_summary  one workgroup: the report, integer sums over the frames
 // Samples run in chunks so that the hypothesis buffer stays bounded; the chunk size changes no result.
 // DESIGN.md section 17 has the measurements.
-#include "pgx_trackgraph.h"
+#include "pgx_stage_args.h"
 
 namespace {
 
@@ -35,31 +35,6 @@ constexpr int REG_G = 16;           // lanes per track in k_reg_count
 constexpr int REG_GRID_MAX = 1024;  // workgroups of k_reg_count, at most
 constexpr int REG_HD = 12;          // doubles per hypothesis: R row-major, t_S
 constexpr long long REG_CHUNK_CELLS = 1 << 17;  // (target slots x samples) per chunk, at most (25 MB of hypotheses)
-
-struct RegArgs {
-    TrackView tv;
-    const double *K, *Rt_in;     // [n_frames][4], [n_frames][12]
-    const int32_t *reg;          // [n_frames]
-    const double *xyz;           // [max_tracks][3]
-    const int32_t *track_flags;  // [max_tracks] or nullptr
-    int n_samples, min_inliers, refine_iters, nblk;
-    double inlier_px;
-    uint64_t seed;
-    double *Rt_out, *P_out, *frame_err;
-    int32_t *frame_stats, *node_inlier, *report;
-    int *status;
-    // workspace
-    int32_t *ctrl;               // [0] tracks to process, [1] targets
-    int32_t *tnum, *tframe, *cnt, *coff, *nlist;  // [n_frames] each
-    int32_t *cf;                 // [node_cap]: target number of a correspondence node, else -1
-    int32_t *corr_node;          // [node_cap]
-    double *cx, *cy, *cz, *cu, *cv;  // [node_cap] each, by position coff[target] + j
-    double *S;                   // [n_frames][4]
-    double *win;                 // [n_frames][16]: the winner's R, t_S
-    int32_t *winfo;              // [n_frames][2]: winning sample or -1, flags
-    double *hyp;                 // [n_frames][chunk][4][REG_HD]
-    unsigned long long *best;    // [n_frames][nblk]
-};
 
 __device__ __forceinline__ bool good_k(const double *K)
 {
@@ -834,11 +809,11 @@ int reg_chunk(int n_frames, int n_samples)
 }
 
 // the workspace, described once: a's workspace pointers (none valid for ws = nullptr) and nblk; the bytes
-size_t reg_carve(RegArgs &a, void *ws, int n_frames, long long node_cap, int n_samples)
+size_t reg_carve(RegArgs &a, void *ws)
 {
-    const size_t N = (size_t)(node_cap > 0 ? node_cap : 1), NF = (size_t)n_frames;
-    const size_t chunk = (size_t)reg_chunk(n_frames, n_samples);
-    a.nblk = (int)((4ll * n_samples + REG_NT - 1) / REG_NT);
+    const size_t N = (size_t)(a.tv.node_cap > 0 ? a.tv.node_cap : 1), NF = (size_t)a.tv.n_frames;
+    const size_t chunk = (size_t)reg_chunk(a.tv.n_frames, a.n_samples);
+    a.nblk = (int)((4ll * a.n_samples + REG_NT - 1) / REG_NT);
     WsCarver w(ws);
     a.ctrl = w.take<int32_t>(8 * 4);
     a.tv.inv = w.take<int32_t>(NF * 4);
@@ -864,46 +839,22 @@ size_t reg_carve(RegArgs &a, void *ws, int n_frames, long long node_cap, int n_s
 
 } // namespace
 
-size_t pgx_register_ws_bytes(int n_frames, long long node_cap, int n_samples)
+size_t pgx_register_ws_bytes(const RegArgs &a)
 {
-    RegArgs a;
-    return reg_carve(a, nullptr, n_frames, node_cap, n_samples);
+    RegArgs b = a;
+    return reg_carve(b, nullptr);
 }
 
-void pgx_launch_register(hipStream_t s, const pgx_keypoint *d_kp, int F, int stride, const int32_t *d_frame_ids, int n_frames,
-                         const double *d_K, const double *d_Rt_in, const int32_t *d_register, const int32_t *d_offsets,
-                         const int32_t *d_nodes, long long node_cap, const int32_t *d_track_summary, int max_tracks,
-                         const double *d_xyz, const int32_t *d_track_flags, int n_samples, double inlier_px, int min_inliers,
-                         int refine_iters, uint64_t seed, double *d_Rt_out, double *d_P_out, int32_t *d_frame_stats,
-                         double *d_frame_err, int32_t *d_node_inlier, int32_t *d_report, void *ws, int *status)
+void pgx_launch_register(hipStream_t s, RegArgs a, void *ws)
 {
-    RegArgs a;
-    a.tv = TrackView{d_kp, d_frame_ids, d_offsets, d_nodes, d_track_summary, F, stride, n_frames, max_tracks, node_cap, nullptr};
-    a.K = d_K;
-    a.Rt_in = d_Rt_in;
-    a.reg = d_register;
-    a.xyz = d_xyz;
-    a.track_flags = d_track_flags;
-    a.n_samples = n_samples;
-    a.min_inliers = min_inliers;
-    a.refine_iters = refine_iters;
-    a.inlier_px = inlier_px;
-    a.seed = seed;
-    a.Rt_out = d_Rt_out;
-    a.P_out = d_P_out;
-    a.frame_err = d_frame_err;
-    a.frame_stats = d_frame_stats;
-    a.node_inlier = d_node_inlier;
-    a.report = d_report;
-    a.status = status;
-    reg_carve(a, ws, n_frames, node_cap, n_samples);
-    const int chunk = reg_chunk(n_frames, n_samples);
-    const long long want = ((long long)max_tracks * REG_G + REG_NT - 1) / REG_NT;
+    reg_carve(a, ws);
+    const int n_frames = a.tv.n_frames, chunk = reg_chunk(n_frames, a.n_samples);
+    const long long want = ((long long)a.tv.max_tracks * REG_G + REG_NT - 1) / REG_NT;
     const int grid = (int)(want < 1 ? 1 : (want > REG_GRID_MAX ? REG_GRID_MAX : want));
     hipLaunchKernelGGL(k_reg_frames, dim3(1), dim3(REG_NT), 0, s, a);
     hipLaunchKernelGGL(k_reg_count, dim3(grid), dim3(REG_NT), 0, s, a);
     hipLaunchKernelGGL(k_reg_csr, dim3(n_frames), dim3(REG_NT), 0, s, a);
-    for (int s0 = 0; s0 < n_samples; s0 += chunk) {
+    for (int s0 = 0; s0 < a.n_samples; s0 += chunk) {
         hipLaunchKernelGGL(k_reg_hyp, dim3((chunk + REG_NT - 1) / REG_NT, n_frames), dim3(REG_NT), 0, s, a, s0, chunk);
         hipLaunchKernelGGL(k_reg_score, dim3(4 * chunk / REG_NT, n_frames), dim3(REG_NT), 0, s, a, s0, chunk);
     }

@@ -17,7 +17,7 @@
 //   k_tri_summary  one workgroup: the per-workgroup counters of k_tri_tracks (no same-address atomics over the grid)
 //                  summed into d_summary.
 // DESIGN.md section 15 has the lane mapping's measurements.
-#include "pgx_trackgraph.h"
+#include "pgx_stage_args.h"
 
 namespace {
 
@@ -25,21 +25,6 @@ constexpr int TRI_NT = 256;          // threads per workgroup of every kernel he
 constexpr int TRI_GRID_MAX = 1024;   // workgroups of k_tri_tracks (4 per CU), at most
 constexpr int TRI_JACOBI_SWEEPS = 8; // cyclic sweeps over the 6 pairs of the 4x4 Gram matrix (quadratic convergence: 3-4 suffice)
 constexpr int CAM_STRIDE = 8;        // doubles per frame in the camera table: C (3), sign det M, ||m3||, known (1 / 0), 2 unused
-
-struct TriArgs {
-    TrackView tv;
-    const double *P;              // [n_frames][12]
-    int refine_iters;
-    double min_par, max_reproj;
-    double *xyz, *quality;
-    int32_t *flags;
-    double *node_err;             // or nullptr
-    int32_t *summary;
-    double *cam;                  // workspace [n_frames][CAM_STRIDE]
-    int32_t *meta;                // workspace [0] tracks to process
-    int32_t *part;                // workspace [grid][8] per-workgroup counters
-    int *status;
-};
 
 // observation o of d_nodes: true if it is used (valid node, known camera); bad = the node itself is invalid.  The node
 // test and the keypoint fetch (and tri_phase's offsets test) stay written out here, not node_ok / node_keypoint /
@@ -412,8 +397,9 @@ int tri_grid(int max_tracks)
 }
 
 // the workspace, described once: a's workspace pointers (none valid for ws = nullptr) and the bytes
-size_t tri_carve(TriArgs &a, void *ws, int n_frames)
+size_t tri_carve(TriArgs &a, void *ws)
 {
+    const int n_frames = a.tv.n_frames;
     WsCarver w(ws);
     a.cam = w.take<double>((size_t)n_frames * CAM_STRIDE * sizeof(double));
     a.part = w.take<int32_t>((size_t)TRI_GRID_MAX * 8 * sizeof(int32_t));
@@ -424,32 +410,16 @@ size_t tri_carve(TriArgs &a, void *ws, int n_frames)
 
 } // namespace
 
-size_t pgx_triangulate_ws_bytes(int n_frames)
+size_t pgx_triangulate_ws_bytes(const TriArgs &a)
 {
-    TriArgs a;
-    return tri_carve(a, nullptr, n_frames);
+    TriArgs b = a;
+    return tri_carve(b, nullptr);
 }
 
-void pgx_launch_triangulate(hipStream_t s, const pgx_keypoint *d_kp, int F, int stride, const int32_t *d_frame_ids, int n_frames,
-                            const double *d_P, const int32_t *d_offsets, const int32_t *d_nodes, long long node_cap,
-                            const int32_t *d_track_summary, int max_tracks, double min_parallax_deg, double max_reproj_px,
-                            int refine_iters, double *d_xyz, double *d_quality, int32_t *d_flags, double *d_node_err,
-                            int32_t *d_summary, void *ws, int *status)
+void pgx_launch_triangulate(hipStream_t s, TriArgs a, void *ws)
 {
-    TriArgs a;
-    a.tv = TrackView{d_kp, d_frame_ids, d_offsets, d_nodes, d_track_summary, F, stride, n_frames, max_tracks, node_cap, nullptr};
-    a.P = d_P;
-    a.refine_iters = refine_iters;
-    a.min_par = min_parallax_deg;
-    a.max_reproj = max_reproj_px;
-    a.xyz = d_xyz;
-    a.quality = d_quality;
-    a.flags = d_flags;
-    a.node_err = d_node_err;
-    a.summary = d_summary;
-    a.status = status;
-    tri_carve(a, ws, n_frames);
-    const int grid = tri_grid(max_tracks);
+    tri_carve(a, ws);
+    const int grid = tri_grid(a.tv.max_tracks);
     hipLaunchKernelGGL(k_tri_frames, dim3(1), dim3(TRI_NT), 0, s, a);
     hipLaunchKernelGGL(k_tri_tracks, dim3(grid), dim3(TRI_NT), 0, s, a);
     hipLaunchKernelGGL(k_tri_summary, dim3(1), dim3(TRI_NT), 0, s, a, grid);

@@ -25,7 +25,7 @@
 //   k_ver_summary  one workgroup: the report, integer sums over all pairs
 // Pairs run in chunks of pgx_set_match_chunk pairs and samples in chunks of max(2^16 / pairs, 256) samples, so that the
 // workspace stays bounded; neither changes a result.  DESIGN.md section 20 has the measurements.
-#include "pgx_trackgraph.h"
+#include "pgx_stage_args.h"
 #include "pgx_eig.h"
 
 namespace {
@@ -36,32 +36,6 @@ constexpr int VER_SNT = 64;    // threads per workgroup of k_ver_samples (41 KB 
 // (pair x sample) cells per chunk of samples; a chunk is never below one scoring workgroup per pair, so the hypothesis
 // buffer holds max(2^16, 256 M) cells of 72 bytes: 37 MB at the default 2048 pairs per workspace, 75 MB at 4096
 constexpr long long VER_CHUNK_CELLS = 1 << 16;
-
-struct VerArgs {
-    const pgx_keypoint *kp;
-    const pgx_pair *matches;
-    const int32_t *counts, *pairlist;
-    int stride, max_dist, n_samples, min_inliers, refit_iters, nblk;
-    double inlier_px;
-    uint64_t seed;
-    pgx_pair *out;
-    double *F;
-    float *F32;
-    int32_t *stats, *inlier;
-    double *sample_F;
-    int32_t *sample_count;
-    // workspace, per pair of the chunk
-    int32_t *ncand;              // [M]
-    int32_t *cpos;               // [M][stride]: candidate position of an entry, -1 = not a candidate
-    double *x, *y, *u, *v;       // [M][stride] by candidate position
-    double *hyp;                 // [M][chunk][9]
-    unsigned long long *best;    // [M][nblk]: the scoring workgroups' keys of one chunk
-    int32_t *nvalid;             // [M][nblk]: their valid samples
-    unsigned long long *run;     // [M]: best key so far
-    int32_t *run_valid;          // [M]: valid samples so far
-    double *win;                 // [M][9]: the F of run
-    int32_t *winfo;              // [M][8]: d_stats' row
-};
 
 // the inlier predicate (include/pgx.h): no division, no square root
 __device__ __forceinline__ bool inlier(const double (&F)[9], double T, double x, double y, double u, double v)
@@ -579,40 +553,18 @@ size_t pgx_verify_ws_bytes(int M, int stride, int n_samples, int chunk)
 
 // M pairs that share one workspace of at least pgx_verify_ws_bytes(M, stride, n_samples, chunk) bytes (a chunk of the call's
 // pairs; the pointers are the chunk's), chunk a multiple of 256
-void pgx_launch_verify(hipStream_t s, const pgx_keypoint *d_kp, const pgx_pair *d_matches, const int32_t *d_counts,
-                       const int32_t *d_pairlist, int M, int stride, int max_dist, int n_samples, double inlier_px, int min_inliers,
-                       int refit_iters, uint64_t seed, pgx_pair *d_out, double *d_F, float *d_F32, int32_t *d_stats,
-                       int32_t *d_inlier, double *d_sample_F, int32_t *d_sample_count, int chunk, void *ws)
+void pgx_launch_verify(hipStream_t s, VerArgs a, int M, int chunk, void *ws)
 {
     if (M <= 0) return;
-    VerArgs a;
-    a.kp = d_kp;
-    a.matches = d_matches;
-    a.counts = d_counts;
-    a.pairlist = d_pairlist;
-    a.stride = stride;
-    a.max_dist = max_dist;
-    a.n_samples = n_samples;
-    a.min_inliers = min_inliers;
-    a.refit_iters = refit_iters;
-    a.inlier_px = inlier_px;
-    a.seed = seed;
-    a.out = d_out;
-    a.F = d_F;
-    a.F32 = d_F32;
-    a.stats = d_stats;
-    a.inlier = d_inlier;
-    a.sample_F = d_sample_F;
-    a.sample_count = d_sample_count;
-    ver_carve(a, ws, M, stride, n_samples, chunk);
+    ver_carve(a, ws, M, a.stride, a.n_samples, chunk);
     hipLaunchKernelGGL(k_ver_cand, dim3(M), dim3(VER_NT), 0, s, a);
-    for (int s0 = 0; s0 < n_samples; s0 += chunk) {
+    for (int s0 = 0; s0 < a.n_samples; s0 += chunk) {
         hipLaunchKernelGGL(k_ver_samples, dim3(chunk / VER_SNT, M), dim3(VER_SNT), 0, s, a, s0, chunk);
         hipLaunchKernelGGL(k_ver_score, dim3(chunk / VER_NT, M), dim3(VER_NT), 0, s, a, s0, chunk);
         hipLaunchKernelGGL(k_ver_pick, dim3(M), dim3(VER_NT), 0, s, a, s0, chunk);
     }
     hipLaunchKernelGGL(k_ver_refit, dim3(M), dim3(VER_NT), 0, s, a);
-    hipLaunchKernelGGL(k_ver_write, dim3((stride + VER_NT - 1) / VER_NT, M), dim3(VER_NT), 0, s, a);
+    hipLaunchKernelGGL(k_ver_write, dim3((a.stride + VER_NT - 1) / VER_NT, M), dim3(VER_NT), 0, s, a);
 }
 
 void pgx_launch_verify_summary(hipStream_t s, const int32_t *d_stats, int M, int32_t *d_report)

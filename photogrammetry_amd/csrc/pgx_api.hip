@@ -2,7 +2,7 @@
 // host-buffer entry points (copy in -> kernels -> copy out) and the device-resident batched
 // entry points.  All compute is in the k_*.hip kernels; there is no CPU fallback anywhere:
 // every entry point needs a working gfx950 device and fails with PGX_E_HIP without one.
-#include "pgx_trackgraph.h"
+#include "pgx_stage_args.h"
 #include "pgx_brief_plan.h"
 
 #include <atomic>
@@ -1405,26 +1405,134 @@ int ver_args(pgx_ctx *c, int M, int stride, int n_samples, double inlier_px, int
     return iters_ok(c, "refit_iters", refit_iters, 8);
 }
 
-// the M pairs of a call in chunks of pgx_set_match_chunk pairs that share ws_ver, then the report
-int enqueue_verify(pgx_ctx *c, const pgx_keypoint *d_kp, const pgx_pair *d_matches, const int32_t *d_counts, const int32_t *d_pairlist,
-                   int M, int stride, int max_dist, int n_samples, double inlier_px, int min_inliers, int refit_iters, uint64_t seed,
-                   pgx_pair *d_out, double *d_F, float *d_F32, int32_t *d_stats, int32_t *d_inlier, double *d_sample_F,
-                   int32_t *d_sample_count, int32_t *d_report)
+// ---- one body per stage: a stage's arguments are its kernels' struct (pgx_stage_args.h), filled by name by the device form and
+// the host form; run_X sizes the workspace from them, brackets the launch for the profile and picks up a launch error
+
+int run_triangulate(pgx_ctx *c, TriArgs &a)
+{
+    a.status = c->d_status;
+    HIPCHK(c, c->ws_tri.ensure(pgx_triangulate_ws_bytes(a)));
+    {
+        ProfScope ps(c, "triangulate");
+        pgx_launch_triangulate(c->stream, a, c->ws_tri.p);
+    }
+    HIPCHK(c, hipGetLastError());
+    return PGX_OK;
+}
+
+int run_bundle(pgx_ctx *c, BaArgs &a)
+{
+    a.status = c->d_status;
+    HIPCHK(c, c->ws_ba.ensure(pgx_bundle_ws_bytes(a)));
+    {
+        ProfScope ps(c, "bundle");
+        pgx_launch_bundle(c->stream, a, c->ws_ba.p);
+    }
+    HIPCHK(c, hipGetLastError());
+    return PGX_OK;
+}
+
+int run_register(pgx_ctx *c, RegArgs &a)
+{
+    a.status = c->d_status;
+    HIPCHK(c, c->ws_reg.ensure(pgx_register_ws_bytes(a)));
+    {
+        ProfScope ps(c, "register");
+        pgx_launch_register(c->stream, a, c->ws_reg.p);
+    }
+    HIPCHK(c, hipGetLastError());
+    return PGX_OK;
+}
+
+int run_consensus(pgx_ctx *c, CnsArgs &a)
+{
+    a.status = c->d_status;
+    HIPCHK(c, c->ws_cns.ensure(pgx_consensus_ws_bytes(a)));
+    {
+        ProfScope ps(c, "consensus");
+        pgx_launch_consensus(c, c->stream, a, c->ws_cns.p);
+    }
+    HIPCHK(c, hipGetLastError());
+    return PGX_OK;
+}
+
+// the M pairs of a call (a's pointers are the first pair's) in chunks of pgx_set_match_chunk pairs that share ws_ver, then the report
+int run_verify(pgx_ctx *c, VerArgs &a, int M, int32_t *d_report)
 {
     const int CHUNK = c->match_chunk < 65535 ? c->match_chunk : 65535, mc = M < CHUNK ? M : CHUNK;
-    const int chunk = pgx_verify_chunk(mc, n_samples);   // one value for every launch: a shorter last chunk of pairs fits too
-    HIPCHK(c, c->ws_ver.ensure(pgx_verify_ws_bytes(mc, stride, n_samples, chunk)));
-    ProfScope ps(c, "verify");
-    for (int m0 = 0; m0 < M; m0 += CHUNK) {
-        const int n = M - m0 < CHUNK ? M - m0 : CHUNK;
-        const size_t o = (size_t)m0 * stride, os = (size_t)m0 * n_samples;
-        pgx_launch_verify(c->stream, d_kp, d_matches + o, d_counts, d_pairlist + 2 * (size_t)m0, n, stride, max_dist, n_samples,
-                          inlier_px, min_inliers, refit_iters, seed, d_out + o, d_F + 9 * (size_t)m0,
-                          d_F32 ? d_F32 + 9 * (size_t)m0 : nullptr, d_stats + 8 * (size_t)m0, d_inlier ? d_inlier + o : nullptr,
-                          d_sample_F ? d_sample_F + 9 * os : nullptr, d_sample_count ? d_sample_count + os : nullptr, chunk, c->ws_ver.p);
+    const int chunk = pgx_verify_chunk(mc, a.n_samples);   // one value for every launch: a shorter last chunk of pairs fits too
+    HIPCHK(c, c->ws_ver.ensure(pgx_verify_ws_bytes(mc, a.stride, a.n_samples, chunk)));
+    {
+        ProfScope ps(c, "verify");
+        for (int m0 = 0; m0 < M; m0 += CHUNK) {
+            const size_t o = (size_t)m0 * a.stride, os = (size_t)m0 * a.n_samples;
+            VerArgs b = a;
+            b.matches = a.matches + o;
+            b.pairlist = a.pairlist + 2 * (size_t)m0;
+            b.out = a.out + o;
+            b.F = a.F + 9 * (size_t)m0;
+            b.F32 = a.F32 ? a.F32 + 9 * (size_t)m0 : nullptr;
+            b.stats = a.stats + 8 * (size_t)m0;
+            b.inlier = a.inlier ? a.inlier + o : nullptr;
+            b.sample_F = a.sample_F ? a.sample_F + 9 * os : nullptr;
+            b.sample_count = a.sample_count ? a.sample_count + os : nullptr;
+            pgx_launch_verify(c->stream, b, M - m0 < CHUNK ? M - m0 : CHUNK, chunk, c->ws_ver.p);
+        }
+        pgx_launch_verify_summary(c->stream, a.stats, M, d_report);
     }
-    pgx_launch_verify_summary(c->stream, d_stats, M, d_report);
+    HIPCHK(c, hipGetLastError());
     return PGX_OK;
+}
+
+int run_init_pair(pgx_ctx *c, InitArgs &a)
+{
+    HIPCHK(c, c->ws_init.ensure(pgx_init_pair_ws_bytes(a)));
+    {
+        ProfScope ps(c, "init_pair");
+        pgx_launch_init_pair(c->stream, a, c->ws_init.p);
+    }
+    HIPCHK(c, hipGetLastError());
+    return PGX_OK;
+}
+
+// the dense stages' launchers bracket their own parts
+int run_depth_maps(pgx_ctx *c, DepArgs &a, int agg_radius)
+{
+    HIPCHK(c, c->ws_depth.ensure(pgx_depth_ws_bytes(a)));
+    pgx_launch_depth_maps(c, c->stream, a, agg_radius, c->ws_depth.p);
+    HIPCHK(c, hipGetLastError());
+    return PGX_OK;
+}
+
+int run_depth_fuse(pgx_ctx *c, FuseArgs &a)
+{
+    a.status = c->d_status;
+    HIPCHK(c, c->ws_depth.ensure(pgx_depth_fuse_ws_bytes(a)));
+    pgx_launch_depth_fuse(c, c->stream, a, c->ws_depth.p);
+    HIPCHK(c, hipGetLastError());
+    return PGX_OK;
+}
+
+// ---- the track graph as a stage sees it (inv: the launcher's)
+
+// a device form's: an offset may reach every slot
+TrackView dev_tracks(const pgx_keypoint *d_kp, int F, int stride, const int32_t *d_frame_ids, int n_frames, const int32_t *d_offsets,
+                     const int32_t *d_nodes, const int32_t *d_track_summary, int max_tracks)
+{
+    TrackView tv{};
+    tv.kp = d_kp; tv.frame_ids = d_frame_ids; tv.offsets = d_offsets; tv.nodes = d_nodes; tv.track_summary = d_track_summary;
+    tv.F = F; tv.stride = stride; tv.n_frames = n_frames; tv.max_tracks = max_tracks; tv.node_cap = (long long)n_frames * stride;
+    return tv;
+}
+
+// a host form's, out of its upload image: slot = frame, exactly the caller's tracks and nodes
+TrackView host_tracks(const HostImage &in, const TracksIn &i, const HostTracks &t, int n_tracks)
+{
+    TrackView tv{};
+    tv.kp = in.dev<pgx_keypoint>(i.kp); tv.offsets = in.dev<int32_t>(i.off); tv.nodes = in.dev<int32_t>(i.nodes);
+    tv.track_summary = in.dev<int32_t>(i.ts);
+    tv.F = tv.n_frames = t.n_frames; tv.stride = t.stride; tv.max_tracks = n_tracks; tv.node_cap = t.n_nodes;
+    return tv;
 }
 } // namespace
 
@@ -1441,15 +1549,12 @@ int pgx_triangulate_tracks_dev(pgx_ctx *c, const pgx_keypoint *d_kp, int F, int 
     int rc = geom_dev_args(c, F, stride, n_frames, d_frame_ids, max_tracks);
     if (rc == PGX_OK) rc = tri_args(c, min_parallax_deg, max_reproj_px, refine_iters);
     if (rc != PGX_OK) return rc;
-    HIPCHK(c, c->ws_tri.ensure(pgx_triangulate_ws_bytes(n_frames)));
-    {
-        ProfScope ps(c, "triangulate");
-        pgx_launch_triangulate(c->stream, d_kp, F, stride, d_frame_ids, n_frames, d_P, d_offsets, d_nodes, (long long)n_frames * stride,
-                               d_track_summary, max_tracks, min_parallax_deg, max_reproj_px, refine_iters, d_xyz, d_quality, d_flags,
-                               d_node_err, d_summary, c->ws_tri.p, c->d_status);
-    }
-    HIPCHK(c, hipGetLastError());
-    return PGX_OK;
+    TriArgs a{};
+    a.tv = dev_tracks(d_kp, F, stride, d_frame_ids, n_frames, d_offsets, d_nodes, d_track_summary, max_tracks);
+    a.P = d_P;
+    a.refine_iters = refine_iters; a.min_par = min_parallax_deg; a.max_reproj = max_reproj_px;
+    a.xyz = d_xyz; a.quality = d_quality; a.flags = d_flags; a.node_err = d_node_err; a.summary = d_summary;
+    return run_triangulate(c, a);
 }
 
 int pgx_triangulate_tracks(pgx_ctx *c, const pgx_keypoint *kps, const int32_t *counts, int n_frames, const double *P,
@@ -1473,15 +1578,13 @@ int pgx_triangulate_tracks(pgx_ctx *c, const pgx_keypoint *kps, const int32_t *c
               o_err = out.add(node_err, t.n_nodes, 8, 1, node_err != nullptr), o_fl = out.add(flags, n_tracks, 4),
               o_sum = out.add(summary, 8, 4, 64);
     if ((rc = stage_images(c, in, out)) != PGX_OK) return rc;
-    HIPCHK(c, c->ws_tri.ensure(pgx_triangulate_ws_bytes(n_frames)));
-    {
-        ProfScope ps(c, "triangulate");
-        pgx_launch_triangulate(c->stream, in.dev<pgx_keypoint>(i.kp), n_frames, t.stride, nullptr, n_frames, in.dev<double>(i.frame[0]),
-                               in.dev<int32_t>(i.off), in.dev<int32_t>(i.nodes), t.n_nodes, in.dev<int32_t>(i.ts), n_tracks,
-                               min_parallax_deg, max_reproj_px, refine_iters, out.dev<double>(o_xyz), out.dev<double>(o_q),
-                               out.dev<int32_t>(o_fl), out.dev<double>(o_err), out.dev<int32_t>(o_sum), c->ws_tri.p, c->d_status);
-    }
-    HIPCHK(c, hipGetLastError());
+    TriArgs a{};
+    a.tv = host_tracks(in, i, t, n_tracks);
+    a.P = in.dev<double>(i.frame[0]);
+    a.refine_iters = refine_iters; a.min_par = min_parallax_deg; a.max_reproj = max_reproj_px;
+    a.xyz = out.dev<double>(o_xyz); a.quality = out.dev<double>(o_q); a.flags = out.dev<int32_t>(o_fl);
+    a.node_err = out.dev<double>(o_err); a.summary = out.dev<int32_t>(o_sum);
+    if ((rc = run_triangulate(c, a)) != PGX_OK) return rc;
     return download_images(c, out);
 }
 
@@ -1500,16 +1603,12 @@ int pgx_bundle_adjust_dev(pgx_ctx *c, const pgx_keypoint *d_kp, int F, int strid
     int rc = geom_dev_args(c, F, stride, n_frames, d_frame_ids, max_tracks);
     if (rc == PGX_OK) rc = ba_args(c, max_iters, huber_px, lambda0);
     if (rc != PGX_OK) return rc;
-    const long long node_cap = (long long)n_frames * stride;
-    HIPCHK(c, c->ws_ba.ensure(pgx_bundle_ws_bytes(n_frames, max_tracks, node_cap)));
-    {
-        ProfScope ps(c, "bundle");
-        pgx_launch_bundle(c->stream, d_kp, F, stride, d_frame_ids, n_frames, d_K, d_Rt_in, d_fixed, d_offsets, d_nodes, node_cap,
-                          d_track_summary, max_tracks, d_xyz_in, d_track_flags, max_iters, huber_px, lambda0, d_Rt_out, d_P_out, d_xyz_out,
-                          d_node_err, d_trace, d_report, c->ws_ba.p, c->d_status);
-    }
-    HIPCHK(c, hipGetLastError());
-    return PGX_OK;
+    BaArgs a{};
+    a.tv = dev_tracks(d_kp, F, stride, d_frame_ids, n_frames, d_offsets, d_nodes, d_track_summary, max_tracks);
+    a.K = d_K; a.Rt_in = d_Rt_in; a.fixed = d_fixed; a.xyz_in = d_xyz_in; a.track_flags = d_track_flags;
+    a.max_iters = max_iters; a.huber = huber_px; a.lambda0 = lambda0;
+    a.Rt_out = d_Rt_out; a.P_out = d_P_out; a.xyz_out = d_xyz_out; a.node_err = d_node_err; a.trace = d_trace; a.report = d_report;
+    return run_bundle(c, a);
 }
 
 int pgx_bundle_adjust(pgx_ctx *c, const pgx_keypoint *kps, const int32_t *counts, int n_frames, const double *K, const double *Rt_in,
@@ -1531,16 +1630,14 @@ int pgx_bundle_adjust(pgx_ctx *c, const pgx_keypoint *kps, const int32_t *counts
               o_err = out.add(node_err, t.n_nodes, 8, 1, node_err != nullptr), o_tr = out.add(trace, max_iters + 1, 16),
               o_rep = out.add(report, 8, 4, 64);
     if ((rc = stage_images(c, in, out)) != PGX_OK) return rc;
-    HIPCHK(c, c->ws_ba.ensure(pgx_bundle_ws_bytes(n_frames, n_tracks, t.n_nodes)));
-    {
-        ProfScope ps(c, "bundle");
-        pgx_launch_bundle(c->stream, in.dev<pgx_keypoint>(i.kp), n_frames, t.stride, nullptr, n_frames, in.dev<double>(i.frame[0]),
-                          in.dev<double>(i.frame[1]), in.dev<int32_t>(i.frame[2]), in.dev<int32_t>(i.off), in.dev<int32_t>(i.nodes),
-                          t.n_nodes, in.dev<int32_t>(i.ts), n_tracks, in.dev<double>(i.xyz), in.dev<int32_t>(i.flags), max_iters, huber_px,
-                          lambda0, out.dev<double>(o_Rt), out.dev<double>(o_P), out.dev<double>(o_xyz), out.dev<double>(o_err),
-                          out.dev<double>(o_tr), out.dev<int32_t>(o_rep), c->ws_ba.p, c->d_status);
-    }
-    HIPCHK(c, hipGetLastError());
+    BaArgs a{};
+    a.tv = host_tracks(in, i, t, n_tracks);
+    a.K = in.dev<double>(i.frame[0]); a.Rt_in = in.dev<double>(i.frame[1]); a.fixed = in.dev<int32_t>(i.frame[2]);
+    a.xyz_in = in.dev<double>(i.xyz); a.track_flags = in.dev<int32_t>(i.flags);
+    a.max_iters = max_iters; a.huber = huber_px; a.lambda0 = lambda0;
+    a.Rt_out = out.dev<double>(o_Rt); a.P_out = out.dev<double>(o_P); a.xyz_out = out.dev<double>(o_xyz);
+    a.node_err = out.dev<double>(o_err); a.trace = out.dev<double>(o_tr); a.report = out.dev<int32_t>(o_rep);
+    if ((rc = run_bundle(c, a)) != PGX_OK) return rc;
     return download_images(c, out);
 }
 
@@ -1560,16 +1657,13 @@ int pgx_register_frames_dev(pgx_ctx *c, const pgx_keypoint *d_kp, int F, int str
     int rc = geom_dev_args(c, F, stride, n_frames, d_frame_ids, max_tracks);
     if (rc == PGX_OK) rc = reg_args(c, n_samples, inlier_px, min_inliers, refine_iters);
     if (rc != PGX_OK) return rc;
-    const long long node_cap = (long long)n_frames * stride;
-    HIPCHK(c, c->ws_reg.ensure(pgx_register_ws_bytes(n_frames, node_cap, n_samples)));
-    {
-        ProfScope ps(c, "register");
-        pgx_launch_register(c->stream, d_kp, F, stride, d_frame_ids, n_frames, d_K, d_Rt_in, d_register, d_offsets, d_nodes, node_cap,
-                            d_track_summary, max_tracks, d_xyz, d_track_flags, n_samples, inlier_px, min_inliers, refine_iters, seed,
-                            d_Rt_out, d_P_out, d_frame_stats, d_frame_err, d_node_inlier, d_report, c->ws_reg.p, c->d_status);
-    }
-    HIPCHK(c, hipGetLastError());
-    return PGX_OK;
+    RegArgs a{};
+    a.tv = dev_tracks(d_kp, F, stride, d_frame_ids, n_frames, d_offsets, d_nodes, d_track_summary, max_tracks);
+    a.K = d_K; a.Rt_in = d_Rt_in; a.reg = d_register; a.xyz = d_xyz; a.track_flags = d_track_flags;
+    a.n_samples = n_samples; a.inlier_px = inlier_px; a.min_inliers = min_inliers; a.refine_iters = refine_iters; a.seed = seed;
+    a.Rt_out = d_Rt_out; a.P_out = d_P_out; a.frame_stats = d_frame_stats; a.frame_err = d_frame_err;
+    a.node_inlier = d_node_inlier; a.report = d_report;
+    return run_register(c, a);
 }
 
 int pgx_register_frames(pgx_ctx *c, const pgx_keypoint *kps, const int32_t *counts, int n_frames, const double *K, const double *Rt_in,
@@ -1591,16 +1685,14 @@ int pgx_register_frames(pgx_ctx *c, const pgx_keypoint *kps, const int32_t *coun
               o_er = out.add(frame_err, n_frames, 16), o_ni = out.add(node_inlier, t.n_nodes, 4, 1, node_inlier != nullptr),
               o_rep = out.add(report, 8, 4, 64);
     if ((rc = stage_images(c, in, out)) != PGX_OK) return rc;
-    HIPCHK(c, c->ws_reg.ensure(pgx_register_ws_bytes(n_frames, t.n_nodes, n_samples)));
-    {
-        ProfScope ps(c, "register");
-        pgx_launch_register(c->stream, in.dev<pgx_keypoint>(i.kp), n_frames, t.stride, nullptr, n_frames, in.dev<double>(i.frame[0]),
-                            in.dev<double>(i.frame[1]), in.dev<int32_t>(i.frame[2]), in.dev<int32_t>(i.off), in.dev<int32_t>(i.nodes),
-                            t.n_nodes, in.dev<int32_t>(i.ts), n_tracks, in.dev<double>(i.xyz), in.dev<int32_t>(i.flags), n_samples, inlier_px,
-                            min_inliers, refine_iters, seed, out.dev<double>(o_Rt), out.dev<double>(o_P), out.dev<int32_t>(o_st),
-                            out.dev<double>(o_er), out.dev<int32_t>(o_ni), out.dev<int32_t>(o_rep), c->ws_reg.p, c->d_status);
-    }
-    HIPCHK(c, hipGetLastError());
+    RegArgs a{};
+    a.tv = host_tracks(in, i, t, n_tracks);
+    a.K = in.dev<double>(i.frame[0]); a.Rt_in = in.dev<double>(i.frame[1]); a.reg = in.dev<int32_t>(i.frame[2]);
+    a.xyz = in.dev<double>(i.xyz); a.track_flags = in.dev<int32_t>(i.flags);
+    a.n_samples = n_samples; a.inlier_px = inlier_px; a.min_inliers = min_inliers; a.refine_iters = refine_iters; a.seed = seed;
+    a.Rt_out = out.dev<double>(o_Rt); a.P_out = out.dev<double>(o_P); a.frame_stats = out.dev<int32_t>(o_st);
+    a.frame_err = out.dev<double>(o_er); a.node_inlier = out.dev<int32_t>(o_ni); a.report = out.dev<int32_t>(o_rep);
+    if ((rc = run_register(c, a)) != PGX_OK) return rc;
     return download_images(c, out);
 }
 
@@ -1622,16 +1714,13 @@ int pgx_track_consensus_dev(pgx_ctx *c, const pgx_keypoint *d_kp, int F, int str
     if (rc != PGX_OK) return rc;
     if (d_offsets_out == d_offsets || d_nodes_out == d_nodes || d_summary_out == d_track_summary)
         return fail(c, PGX_E_BADARG, "the output graph must not alias the input graph");
-    const long long node_cap = (long long)n_frames * stride;
-    HIPCHK(c, c->ws_cns.ensure(pgx_consensus_ws_bytes(n_frames, max_tracks, node_cap)));
-    {
-        ProfScope ps(c, "consensus");
-        pgx_launch_consensus(c, c->stream, d_kp, F, stride, d_frame_ids, n_frames, d_P, d_offsets, d_nodes, node_cap, d_track_summary,
-                             max_tracks, inlier_px, cos2, min_inliers, min_len, max_hyp, seed, d_offsets_out, d_nodes_out, d_summary_out,
-                             d_track_map, d_xyz_out, d_flags_out, d_track_stats, d_track_of, d_report, c->ws_cns.p, c->d_status);
-    }
-    HIPCHK(c, hipGetLastError());
-    return PGX_OK;
+    CnsArgs a{};
+    a.tv = dev_tracks(d_kp, F, stride, d_frame_ids, n_frames, d_offsets, d_nodes, d_track_summary, max_tracks);
+    a.P = d_P;
+    a.inlier_px = inlier_px; a.cos2 = cos2; a.min_inliers = min_inliers; a.min_len = min_len; a.max_hyp = max_hyp; a.seed = seed;
+    a.off_out = d_offsets_out; a.nodes_out = d_nodes_out; a.summary_out = d_summary_out; a.map = d_track_map;
+    a.xyz_out = d_xyz_out; a.flags_out = d_flags_out; a.stats = d_track_stats; a.track_of = d_track_of; a.report = d_report;
+    return run_consensus(c, a);
 }
 
 int pgx_track_consensus(pgx_ctx *c, const pgx_keypoint *kps, const int32_t *counts, int n_frames, const double *P,
@@ -1660,16 +1749,14 @@ int pgx_track_consensus(pgx_ctx *c, const pgx_keypoint *kps, const int32_t *coun
               o_sum = out.add(summary_out, 8, 4, 64), o_map = out.add(track_map, n_tracks, 4), o_xyz = out.add(xyz_out, n_tracks, 24),
               o_fl = out.add(flags_out, n_tracks, 4), o_st = out.add(track_stats, n_tracks, 16), o_rep = out.add(report, 8, 4, 64);
     if ((rc = stage_images(c, in, out)) != PGX_OK) return rc;
-    HIPCHK(c, c->ws_cns.ensure(pgx_consensus_ws_bytes(n_frames, n_tracks, t.n_nodes)));
-    {
-        ProfScope ps(c, "consensus");
-        pgx_launch_consensus(c, c->stream, in.dev<pgx_keypoint>(i.kp), n_frames, t.stride, nullptr, n_frames, in.dev<double>(i.frame[0]),
-                             in.dev<int32_t>(i.off), in.dev<int32_t>(i.nodes), t.n_nodes, in.dev<int32_t>(i.ts), n_tracks, inlier_px, cos2,
-                             min_inliers, min_len, max_hyp, seed, out.dev<int32_t>(o_off), out.dev<int32_t>(o_nd), out.dev<int32_t>(o_sum),
-                             out.dev<int32_t>(o_map), out.dev<double>(o_xyz), out.dev<int32_t>(o_fl), out.dev<int32_t>(o_st), nullptr,
-                             out.dev<int32_t>(o_rep), c->ws_cns.p, c->d_status);
-    }
-    HIPCHK(c, hipGetLastError());
+    CnsArgs a{};
+    a.tv = host_tracks(in, i, t, n_tracks);
+    a.P = in.dev<double>(i.frame[0]);
+    a.inlier_px = inlier_px; a.cos2 = cos2; a.min_inliers = min_inliers; a.min_len = min_len; a.max_hyp = max_hyp; a.seed = seed;
+    a.off_out = out.dev<int32_t>(o_off); a.nodes_out = out.dev<int32_t>(o_nd); a.summary_out = out.dev<int32_t>(o_sum);
+    a.map = out.dev<int32_t>(o_map); a.xyz_out = out.dev<double>(o_xyz); a.flags_out = out.dev<int32_t>(o_fl);
+    a.stats = out.dev<int32_t>(o_st); a.report = out.dev<int32_t>(o_rep);   // no track_of
+    if ((rc = run_consensus(c, a)) != PGX_OK) return rc;
     return download_images(c, out);
 }
 
@@ -1794,11 +1881,13 @@ int pgx_verify_pairs_dev(pgx_ctx *c, const pgx_keypoint *d_kp, const pgx_pair *d
     Lock l(c);
     const int rc = ver_args(c, M, stride, n_samples, inlier_px, min_inliers, refit_iters);
     if (rc != PGX_OK) return rc;
-    const int rq = enqueue_verify(c, d_kp, d_matches, d_counts, d_pairlist, M, stride, max_dist, n_samples, inlier_px, min_inliers,
-                                  refit_iters, seed, d_out, d_F, d_F32, d_stats, d_inlier, d_sample_F, d_sample_count, d_report);
-    if (rq != PGX_OK) return rq;
-    HIPCHK(c, hipGetLastError());
-    return PGX_OK;
+    VerArgs a{};
+    a.kp = d_kp; a.matches = d_matches; a.counts = d_counts; a.pairlist = d_pairlist; a.stride = stride;
+    a.max_dist = max_dist; a.n_samples = n_samples; a.inlier_px = inlier_px; a.min_inliers = min_inliers; a.refit_iters = refit_iters;
+    a.seed = seed;
+    a.out = d_out; a.F = d_F; a.F32 = d_F32; a.stats = d_stats; a.inlier = d_inlier;
+    a.sample_F = d_sample_F; a.sample_count = d_sample_count;
+    return run_verify(c, a, M, d_report);
 }
 
 int pgx_verify_pair(pgx_ctx *c, const pgx_keypoint *kp1, int n1, const pgx_keypoint *kp2, int n2, const pgx_pair *matches, int max_dist,
@@ -1818,12 +1907,13 @@ int pgx_verify_pair(pgx_ctx *c, const pgx_keypoint *kp1, int n1, const pgx_keypo
     const int o_out = ot.add(out, n1, sizeof(pgx_pair), S), o_F = ot.add(F, 9, 8), o_st = ot.add(stats, 8, 4),
               o_in = ot.add(inlier, n1, 4, S, inlier != nullptr), o_rep = ot.add(nullptr, 0, 4, 8);
     if (const int rs = stage_images(c, in, ot); rs != PGX_OK) return rs;
-    const int32_t *d_meta = in.dev<int32_t>(i.meta);
-    const int rq = enqueue_verify(c, in.dev<pgx_keypoint>(i.kp), in.dev<pgx_pair>(i.list), d_meta, d_meta + 3, 1, S, max_dist, n_samples,
-                                  inlier_px, min_inliers, refit_iters, seed, ot.dev<pgx_pair>(o_out), ot.dev<double>(o_F), nullptr,
-                                  ot.dev<int32_t>(o_st), ot.dev<int32_t>(o_in), nullptr, nullptr, ot.dev<int32_t>(o_rep));
-    if (rq != PGX_OK) return rq;
-    HIPCHK(c, hipGetLastError());
+    VerArgs a{};
+    a.kp = in.dev<pgx_keypoint>(i.kp); a.matches = in.dev<pgx_pair>(i.list);
+    a.counts = in.dev<int32_t>(i.meta); a.pairlist = a.counts + 3; a.stride = S;
+    a.max_dist = max_dist; a.n_samples = n_samples; a.inlier_px = inlier_px; a.min_inliers = min_inliers; a.refit_iters = refit_iters;
+    a.seed = seed;
+    a.out = ot.dev<pgx_pair>(o_out); a.F = ot.dev<double>(o_F); a.stats = ot.dev<int32_t>(o_st); a.inlier = ot.dev<int32_t>(o_in);
+    if (const int rq = run_verify(c, a, 1, ot.dev<int32_t>(o_rep)); rq != PGX_OK) return rq;
     return download_images(c, ot);
 }
 
@@ -1857,15 +1947,14 @@ int pgx_init_pair_dev(pgx_ctx *c, const pgx_keypoint *d_kp, const pgx_pair *d_ma
     int rc = init_args(c, M, stride, min_angle_deg, min_front_frac, min_points, &cos2);
     if (rc == PGX_OK) rc = geom_dev_args(c, F, stride, n_frames, d_frame_ids, 0);
     if (rc != PGX_OK) return rc;
-    HIPCHK(c, c->ws_init.ensure(pgx_init_pair_ws_bytes(M)));
-    {
-        ProfScope ps(c, "init_pair");
-        pgx_launch_init_pair(c->stream, d_kp, d_matches, d_counts, d_pairlist, M, F, stride, d_frame_ids, n_frames, max_dist, d_F, d_K,
-                             cos2, min_front_frac, min_points, d_Rt_pair, d_pair_stats, d_sigma, d_cand_Rt, d_Rt_out, d_P_out,
-                             d_fixed_out, d_register_out, d_report, c->ws_init.p);
-    }
-    HIPCHK(c, hipGetLastError());
-    return PGX_OK;
+    InitArgs a{};
+    a.kp = d_kp; a.matches = d_matches; a.counts = d_counts; a.pairlist = d_pairlist; a.frame_ids = d_frame_ids;
+    a.F = d_F; a.K = d_K;
+    a.M = M; a.nslots = F; a.stride = stride; a.n_frames = n_frames;
+    a.max_dist = max_dist; a.cos2 = cos2; a.min_front_frac = min_front_frac; a.min_points = min_points;
+    a.Rt_pair = d_Rt_pair; a.pair_stats = d_pair_stats; a.sigma = d_sigma; a.cand_Rt = d_cand_Rt;
+    a.Rt_out = d_Rt_out; a.P_out = d_P_out; a.fixed_out = d_fixed_out; a.register_out = d_register_out; a.report = d_report;
+    return run_init_pair(c, a);
 }
 
 int pgx_relative_pose(pgx_ctx *c, const pgx_keypoint *kp1, int n1, const pgx_keypoint *kp2, int n2, const pgx_pair *matches, int max_dist,
@@ -1890,17 +1979,17 @@ int pgx_relative_pose(pgx_ctx *c, const pgx_keypoint *kp1, int n1, const pgx_key
     const int o_Rt = ot.add(Rt, 12, 8), o_st = ot.add(stats, 8, 4), o_sg = ot.add(sigma, 1, 8), o_cand = ot.add(cand_Rt, 48, 8, 0, cand_Rt != nullptr),
               o_fr = ot.add(nullptr, 0, 96, 2 * 3), o_fi = ot.add(nullptr, 0, 4, 2 * 3 + 16), o_rep = ot.add(nullptr, 0, 4, 8);
     if (const int rs = stage_images(c, in, ot); rs != PGX_OK) return rs;
-    HIPCHK(c, c->ws_init.ensure(pgx_init_pair_ws_bytes(1)));
-    const int32_t *d_meta = in.dev<int32_t>(i.meta);
-    {
-        ProfScope ps(c, "init_pair");
-        pgx_launch_init_pair(c->stream, in.dev<pgx_keypoint>(i.kp), in.dev<pgx_pair>(i.list), d_meta, d_meta + 3, 1, 3, S, nullptr, 3,
-                             max_dist, in.dev<double>(i_F), in.dev<double>(i_K), cos2, min_front_frac, min_points, ot.dev<double>(o_Rt),
-                             ot.dev<int32_t>(o_st), ot.dev<double>(o_sg), ot.dev<double>(o_cand), ot.dev<double>(o_fr),
-                             ot.dev<double>(o_fr) + 3 * 12, ot.dev<int32_t>(o_fi), ot.dev<int32_t>(o_fi) + 8, ot.dev<int32_t>(o_rep),
-                             c->ws_init.p);
-    }
-    HIPCHK(c, hipGetLastError());
+    InitArgs a{};
+    a.kp = in.dev<pgx_keypoint>(i.kp); a.matches = in.dev<pgx_pair>(i.list);
+    a.counts = in.dev<int32_t>(i.meta); a.pairlist = a.counts + 3;
+    a.F = in.dev<double>(i_F); a.K = in.dev<double>(i_K);
+    a.M = 1; a.nslots = a.n_frames = 3; a.stride = S;
+    a.max_dist = max_dist; a.cos2 = cos2; a.min_front_frac = min_front_frac; a.min_points = min_points;
+    a.Rt_pair = ot.dev<double>(o_Rt); a.pair_stats = ot.dev<int32_t>(o_st); a.sigma = ot.dev<double>(o_sg);
+    a.cand_Rt = ot.dev<double>(o_cand);
+    a.Rt_out = ot.dev<double>(o_fr); a.P_out = a.Rt_out + 3 * 12;
+    a.fixed_out = ot.dev<int32_t>(o_fi); a.register_out = a.fixed_out + 8; a.report = ot.dev<int32_t>(o_rep);
+    if (const int rq = run_init_pair(c, a); rq != PGX_OK) return rq;
     return download_images(c, ot);
 }
 
@@ -1963,11 +2052,12 @@ int pgx_depth_maps_dev(pgx_ctx *c, const float *d_gray, int F, int W, int H, con
     const int rc = depth_args(c, F, W, H, n_frames, d_frame_ids != nullptr, R, S, D, agg_radius, min_views, max_cost);
     if (rc != PGX_OK) return rc;
     if (R == 0) return fail(c, PGX_E_BADARG, "R must be positive");
-    HIPCHK(c, c->ws_depth.ensure(pgx_depth_ws_bytes(F, W, H, R, S, D)));
-    pgx_launch_depth_maps(c, c->stream, d_gray, F, W, H, d_frame_ids, n_frames, d_P, d_views, R, S, d_range, D, agg_radius, min_views,
-                          max_cost, d_kq8, d_depth, d_cost, d_flags, d_warp, d_planes, d_summary, c->ws_depth.p);
-    HIPCHK(c, hipGetLastError());
-    return PGX_OK;
+    DepArgs a{};
+    a.gray = d_gray; a.F = F; a.W = W; a.H = H; a.frame_ids = d_frame_ids; a.n_frames = n_frames; a.P = d_P;
+    a.views = d_views; a.R = R; a.S = S; a.range = d_range; a.D = D; a.min_views = min_views; a.max_cost = max_cost;
+    a.kq8 = d_kq8; a.depth = d_depth; a.cost = d_cost; a.flags = d_flags; a.warp_out = d_warp; a.planes_out = d_planes;
+    a.summary = d_summary;
+    return run_depth_maps(c, a, agg_radius);
 }
 
 int pgx_depth_maps(pgx_ctx *c, const float *gray, int n_frames, int W, int H, const double *P, const int32_t *views, int R, int S,
@@ -1990,12 +2080,13 @@ int pgx_depth_maps(pgx_ctx *c, const float *gray, int n_frames, int W, int H, co
               o_p = out.add(planes, (size_t)R * D, 8, 0, planes != nullptr), o_s = out.add(summary, 8, 4, 64);
     int rs = stage_images(c, in, out);
     if (rs != PGX_OK) return rs;
-    HIPCHK(c, c->ws_depth.ensure(pgx_depth_ws_bytes(n_frames, W, H, R, S, D)));
-    pgx_launch_depth_maps(c, c->stream, in.dev<float>(i_g), n_frames, W, H, nullptr, n_frames, in.dev<double>(i_P), in.dev<int32_t>(i_v), R,
-                          S, in.dev<double>(i_r), D, agg_radius, min_views, max_cost, out.dev<int32_t>(o_kq), out.dev<double>(o_d),
-                          out.dev<int32_t>(o_c), out.dev<int32_t>(o_f), out.dev<double>(o_w), out.dev<double>(o_p), out.dev<int32_t>(o_s),
-                          c->ws_depth.p);
-    HIPCHK(c, hipGetLastError());
+    DepArgs a{};
+    a.gray = in.dev<float>(i_g); a.F = a.n_frames = n_frames; a.W = W; a.H = H; a.P = in.dev<double>(i_P);
+    a.views = in.dev<int32_t>(i_v); a.R = R; a.S = S; a.range = in.dev<double>(i_r); a.D = D;
+    a.min_views = min_views; a.max_cost = max_cost;
+    a.kq8 = out.dev<int32_t>(o_kq); a.depth = out.dev<double>(o_d); a.cost = out.dev<int32_t>(o_c); a.flags = out.dev<int32_t>(o_f);
+    a.warp_out = out.dev<double>(o_w); a.planes_out = out.dev<double>(o_p); a.summary = out.dev<int32_t>(o_s);
+    if ((rs = run_depth_maps(c, a, agg_radius)) != PGX_OK) return rs;
     return download_images(c, out);
 }
 
@@ -2009,11 +2100,11 @@ int pgx_depth_fuse_dev(pgx_ctx *c, const double *d_depth, const int32_t *d_views
     const int rc = fuse_args(c, R, S, W, H, n_frames, rel_tol, min_agree, max_points);
     if (rc != PGX_OK) return rc;
     if (R == 0) return fail(c, PGX_E_BADARG, "R must be positive");
-    HIPCHK(c, c->ws_depth.ensure(pgx_depth_fuse_ws_bytes(R, S, W, H)));
-    pgx_launch_depth_fuse(c, c->stream, d_depth, d_views, R, S, W, H, n_frames, d_P, rel_tol, min_agree, max_points, d_xyz, d_src, d_agree,
-                          d_summary, c->ws_depth.p, c->d_status);
-    HIPCHK(c, hipGetLastError());
-    return PGX_OK;
+    FuseArgs a{};
+    a.depth = d_depth; a.views = d_views; a.R = R; a.S = S; a.W = W; a.H = H; a.n_frames = n_frames; a.P = d_P;
+    a.rel_tol = rel_tol; a.min_agree = min_agree; a.max_points = max_points;
+    a.xyz = d_xyz; a.src = d_src; a.agree = d_agree; a.summary = d_summary;
+    return run_depth_fuse(c, a);
 }
 
 int pgx_depth_fuse(pgx_ctx *c, const double *depth, const int32_t *views, int R, int S, int W, int H, int n_frames, const double *P,
@@ -2034,11 +2125,12 @@ int pgx_depth_fuse(pgx_ctx *c, const double *depth, const int32_t *views, int R,
               o_x = out.add(nullptr, 0, 24, (size_t)max_points + 1), o_r = out.add(nullptr, 0, 8, (size_t)max_points + 1);
     int rs = stage_images(c, in, out);
     if (rs != PGX_OK) return rs;
-    HIPCHK(c, c->ws_depth.ensure(pgx_depth_fuse_ws_bytes(R, S, W, H)));
-    pgx_launch_depth_fuse(c, c->stream, in.dev<double>(i_d), in.dev<int32_t>(i_v), R, S, W, H, n_frames, in.dev<double>(i_P), rel_tol,
-                          min_agree, max_points, out.dev<double>(o_x), out.dev<int32_t>(o_r), out.dev<int32_t>(o_a), out.dev<int32_t>(o_s),
-                          c->ws_depth.p, c->d_status);
-    HIPCHK(c, hipGetLastError());
+    FuseArgs a{};
+    a.depth = in.dev<double>(i_d); a.views = in.dev<int32_t>(i_v); a.R = R; a.S = S; a.W = W; a.H = H; a.n_frames = n_frames;
+    a.P = in.dev<double>(i_P);
+    a.rel_tol = rel_tol; a.min_agree = min_agree; a.max_points = max_points;
+    a.xyz = out.dev<double>(o_x); a.src = out.dev<int32_t>(o_r); a.agree = out.dev<int32_t>(o_a); a.summary = out.dev<int32_t>(o_s);
+    if ((rs = run_depth_fuse(c, a)) != PGX_OK) return rs;
     rs = download_images(c, out);   // summary and agree; waits for the stream
     const size_t np = (size_t)(summary[0] < max_points ? summary[0] : max_points);
     if (np > 0) {

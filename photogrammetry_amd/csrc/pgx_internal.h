@@ -391,65 +391,8 @@ void pgx_launch_guided(pgx_ctx *ctx, hipStream_t s, const uint32_t *d_desc, cons
                        const int32_t *d_pairlist, int M, int S, int words, int max_n, const float *d_F, float band, int k,
                        int32_t *d_idx, int32_t *d_dist, int32_t *d_col, void *ws, int *status);
 
-// k_triangulate.hip (multi-view triangulation of tracks; pgx_triangulate_tracks_dev semantics, include/pgx.h)
-size_t pgx_triangulate_ws_bytes(int n_frames);
-// node_cap: entries of d_nodes / d_node_err an offset may reach; PGX_ST_TRI_* bits go to *status
-void pgx_launch_triangulate(hipStream_t s, const pgx_keypoint *d_kp, int F, int stride, const int32_t *d_frame_ids, int n_frames,
-                            const double *d_P, const int32_t *d_offsets, const int32_t *d_nodes, long long node_cap,
-                            const int32_t *d_track_summary, int max_tracks, double min_parallax_deg, double max_reproj_px,
-                            int refine_iters, double *d_xyz, double *d_quality, int32_t *d_flags, double *d_node_err,
-                            int32_t *d_summary, void *ws, int *status);
-
-// k_bundle.hip (bundle adjustment of cameras and track points; pgx_bundle_adjust_dev semantics, include/pgx.h)
-size_t pgx_bundle_ws_bytes(int n_frames, int max_tracks, long long node_cap);
-// node_cap: entries of d_nodes / d_node_err an offset may reach; PGX_ST_BA_* bits go to *status
-void pgx_launch_bundle(hipStream_t s, const pgx_keypoint *d_kp, int F, int stride, const int32_t *d_frame_ids, int n_frames,
-                       const double *d_K, const double *d_Rt_in, const int32_t *d_fixed, const int32_t *d_offsets, const int32_t *d_nodes,
-                       long long node_cap, const int32_t *d_track_summary, int max_tracks, const double *d_xyz_in,
-                       const int32_t *d_track_flags, int max_iters, double huber_px, double lambda0, double *d_Rt_out, double *d_P_out,
-                       double *d_xyz_out, double *d_node_err, double *d_trace, int32_t *d_report, void *ws, int *status);
-
-// k_register.hip (frame registration by P3P RANSAC; pgx_register_frames_dev semantics, include/pgx.h)
-size_t pgx_register_ws_bytes(int n_frames, long long node_cap, int n_samples);
-// node_cap: entries of d_nodes / d_node_inlier an offset may reach; PGX_ST_REG_* bits go to *status
-void pgx_launch_register(hipStream_t s, const pgx_keypoint *d_kp, int F, int stride, const int32_t *d_frame_ids, int n_frames,
-                         const double *d_K, const double *d_Rt_in, const int32_t *d_register, const int32_t *d_offsets,
-                         const int32_t *d_nodes, long long node_cap, const int32_t *d_track_summary, int max_tracks,
-                         const double *d_xyz, const int32_t *d_track_flags, int n_samples, double inlier_px, int min_inliers,
-                         int refine_iters, uint64_t seed, double *d_Rt_out, double *d_P_out, int32_t *d_frame_stats,
-                         double *d_frame_err, int32_t *d_node_inlier, int32_t *d_report, void *ws, int *status);
-
-// k_consensus.hip (track consensus; pgx_track_consensus_dev semantics, include/pgx.h)
-size_t pgx_consensus_ws_bytes(int n_frames, int max_tracks, long long node_cap);
-// node_cap: entries of d_nodes / d_nodes_out an offset may reach; cos2 = the square of the cosine of min_parallax_deg;
-// PGX_ST_CNS_* bits go to *status; ctx: the profiling groups consensus_frames / _score / _scan / _write
-void pgx_launch_consensus(pgx_ctx *ctx, hipStream_t s, const pgx_keypoint *d_kp, int F, int stride, const int32_t *d_frame_ids, int n_frames,
-                          const double *d_P, const int32_t *d_offsets, const int32_t *d_nodes, long long node_cap,
-                          const int32_t *d_track_summary, int max_tracks, double inlier_px, double cos2, int min_inliers, int min_len,
-                          int max_hyp, uint64_t seed, int32_t *d_offsets_out, int32_t *d_nodes_out, int32_t *d_summary_out,
-                          int32_t *d_track_map, double *d_xyz_out, int32_t *d_flags_out, int32_t *d_track_stats, int32_t *d_track_of,
-                          int32_t *d_report, void *ws, int *status);
-
-// k_verify.hip (two-view verification by epipolar RANSAC; pgx_verify_pairs_dev semantics, include/pgx.h)
-// samples per chunk for a workspace of M pairs (a multiple of 256), and the bytes of that workspace: not less for more pairs
-int pgx_verify_chunk(int M, int n_samples);
-size_t pgx_verify_ws_bytes(int M, int stride, int n_samples, int chunk);
-// M <= 65535 pairs that share the workspace; every pointer is the first of those pairs' rows.  chunk: the workspace's
-void pgx_launch_verify(hipStream_t s, const pgx_keypoint *d_kp, const pgx_pair *d_matches, const int32_t *d_counts,
-                       const int32_t *d_pairlist, int M, int stride, int max_dist, int n_samples, double inlier_px, int min_inliers,
-                       int refit_iters, uint64_t seed, pgx_pair *d_out, double *d_F, float *d_F32, int32_t *d_stats,
-                       int32_t *d_inlier, double *d_sample_F, int32_t *d_sample_count, int chunk, void *ws);
-// d_report from the d_stats rows of all M pairs of a call
-void pgx_launch_verify_summary(hipStream_t s, const int32_t *d_stats, int M, int32_t *d_report);
-
-// k_initpair.hip (relative pose per image pair and the choice of the initial pair; pgx_init_pair_dev semantics, include/pgx.h)
-size_t pgx_init_pair_ws_bytes(int M);
-// all M pairs of a call; cos2 = the square of the cosine of min_angle_deg; d_sigma and d_cand_Rt may be null
-void pgx_launch_init_pair(hipStream_t s, const pgx_keypoint *d_kp, const pgx_pair *d_matches, const int32_t *d_counts,
-                          const int32_t *d_pairlist, int M, int F, int stride, const int32_t *d_frame_ids, int n_frames, int max_dist,
-                          const double *d_F, const double *d_K, double cos2, double min_front_frac, int min_points, double *d_Rt_pair,
-                          int32_t *d_pair_stats, double *d_sigma, double *d_cand_Rt, double *d_Rt_out, double *d_P_out,
-                          int32_t *d_fixed_out, int32_t *d_register_out, int32_t *d_report, void *ws);
+// the stages behind the matchers (k_triangulate.hip, k_bundle.hip, k_register.hip, k_consensus.hip, k_verify.hip,
+// k_initpair.hip, k_depth.hip): pgx_stage_args.h, each launcher beside its argument struct
 
 // k_vocab.hip (binary visual vocabulary and image-pair selection; pgx_vocab_quantize_dev, pgx_vocab_train_dev and
 // pgx_select_pairs_dev semantics, include/pgx.h).  256-bit descriptors; F in [1, 4096], S in [1, 65535], V in [1, 65536]
@@ -466,16 +409,3 @@ size_t pgx_select_pairs_ws_bytes(int F, int S, int V, bool own_scores);
 void pgx_launch_select_pairs(pgx_ctx *ctx, hipStream_t s, const uint32_t *d_desc, const int32_t *d_counts, int F, int S,
                              const uint32_t *d_vocab, int V, int weighting, int top_k, int window, int min_score, int max_pairs,
                              int32_t *d_pairlist, int32_t *d_pair_score, int32_t *d_scores, int32_t *d_summary, void *ws, int *status);
-
-// k_depth.hip (census plane-sweep depth maps and the cross-view filter; pgx_depth_maps_dev and pgx_depth_fuse_dev semantics,
-// include/pgx.h).  ctx: the profiling groups depth_census / depth_plan / depth_sweep / depth_fuse
-size_t pgx_depth_ws_bytes(int F, int W, int H, int R, int S, int D);
-void pgx_launch_depth_maps(pgx_ctx *ctx, hipStream_t s, const float *d_gray, int F, int W, int H, const int32_t *d_frame_ids, int n_frames,
-                           const double *d_P, const int32_t *d_views, int R, int S, const double *d_range, int D, int agg_radius,
-                           int min_views, int max_cost, int32_t *d_kq8, double *d_depth, int32_t *d_cost, int32_t *d_flags, double *d_warp,
-                           double *d_planes, int32_t *d_summary, void *ws);
-size_t pgx_depth_fuse_ws_bytes(int R, int S, int W, int H);
-// more than max_points kept pixels: PGX_ST_DEP_CAP in *status
-void pgx_launch_depth_fuse(pgx_ctx *ctx, hipStream_t s, const double *d_depth, const int32_t *d_views, int R, int S, int W, int H,
-                           int n_frames, const double *d_P, double rel_tol, int min_agree, int max_points, double *d_xyz, int32_t *d_src,
-                           int32_t *d_agree, int32_t *d_summary, void *ws, int *status);
