@@ -1056,6 +1056,84 @@ int pgx_depth_fuse(pgx_ctx *ctx, const double *depth, const int32_t *views, int 
                    const double *P, double rel_tol, int min_agree, int max_points, double *xyz, int32_t *src, int32_t *agree,
                    int32_t *summary);
 
+/* ---- the plan of the dense stage from the sparse model: sources and depth range per reference -------- */
+/* pgx_depth_maps_dev takes d_views and d_range from the caller.  This call derives both from the track graph, the track points
+ * and the cameras, on the device, so that tracks -> (consensus) -> triangulate -> bundle-adjust -> triangulate -> this ->
+ * pgx_gray_batch_dev -> pgx_depth_maps_dev -> pgx_depth_fuse_dev runs on one stream with no host round trip.  View selection by
+ * shared points at a usable triangulation angle and a depth range from the depths of the sparse points, as multi-view stereo
+ * packages do both; stated so that it is bit-identical to a numpy restatement (tests/dense_views_ref.py).  Not in the C#
+ * reference.  k_denseviews.hip.
+ * Inputs.  d_offsets, d_nodes, d_track_summary and max_tracks as for pgx_triangulate_tracks_dev; n_tracks = d_track_summary[0] is
+ * read on the device.  max_nodes = the entries of d_nodes that an offset may reach (n_frames * stride for a graph of
+ * pgx_tracks_dev or pgx_track_consensus_dev).  d_xyz [max_tracks][3] and d_track_flags [max_tracks] or NULL as for
+ * pgx_bundle_adjust_dev.  d_P [n_frames][12] by frame NUMBER.  d_refs [R] frame numbers, or NULL: reference r is frame r, and R must
+ * be n_frames.  Only the frame of a node is read: the call takes no keypoints and no slots.
+ * Values.  Every value is a double, every operation one IEEE double operation in the order written, nothing is contracted into
+ * a fused multiply-add; a dot product x . y is ((x0 y0 + x1 y1) + x2 y2).
+ * Frames.  A frame is KNOWN by the triangulation's test (all 12 entries finite and det M != 0).  Per known frame Minv,
+ * C = -(Minv p4) and sgn are exactly pgx_track_consensus_dev's; nrm = sqrt((m20 m20 + m21 m21) + m22 m22).
+ * Used tracks.  Track t is used iff t < min(n_tracks, max_tracks), d_track_flags[t] == 0 (or the pointer is NULL) and X = d_xyz[t]
+ * has three finite components.  Nothing else of an unused track is read.
+ * Used nodes.  Node i of a used track, in frame f, is USED iff f is in [0, n_frames) and known, and
+ *   z_i = (sgn_f ((P_f[2][0:3] . X) + P_f[2][3])) / nrm_f
+ * satisfies z_i > 0 (NaN fails).  This is the triangulation's depth_i and the z of the depth maps.
+ * Pairs.  For used nodes i < j (positions in d_nodes) of one track, in frames a and b: a pair with a == b is passed over.
+ * Otherwise r_i = C_a - X, r_j = C_b - X (componentwise), d = r_i . r_j, na = r_i . r_i, nb = r_j . r_j; the pair counts 1 in
+ * shared[a][b] and in shared[b][a], and 1 in good[a][b] and good[b][a] iff d > 0 and d d <= cmin2 (na nb) and
+ * d d >= cmax2 (na nb): the angle at X between the two centres lies in [min_angle_deg, max_angle_deg].  cmin2 and cmax2 are the
+ * squares of the host C library's cos(min_angle_deg * M_PI / 180.0) and cos(max_angle_deg * M_PI / 180.0), computed once.  No
+ * division and no p4 beyond C: a translated scene decides the same way, and -P decides exactly as P.  A track that names a
+ * frame twice counts each of its two nodes there against every other frame.  The counts are int32.
+ * Sources of reference a (a known frame).  The candidates are the known frames b != a with shared[a][b] >= min_shared (with
+ * min_shared = 0 every other known frame).  Ordered by good descending, then shared descending, then frame number ascending
+ * (an integer key: the grid and the order of the sums cannot matter), the first S are the row's sources; missing ones are -1.
+ * Range of reference a.  Z_a = the multiset of the z_i of the used nodes in frame a, n_a its size, z_(0) <= ... <= z_(n_a - 1)
+ * its order.  In 64-bit integers i_near = ((n_a - 1) q_near_pm) / 1000 and i_far = ((n_a - 1) q_far_pm + 999) / 1000;
+ * z_near = z_(i_near) / grow, z_far = z_(i_far) * grow: exact order statistics of the exact doubles (numpy.sort's), no
+ * histogram approximation.  n_a < min_points: the range is (NaN, NaN), and pgx_depth_maps_dev flags that map NOCAMERA by its
+ * rule 2.
+ * Outputs, per row r of d_refs:
+ *   d_views [R][1 + S] int32  the reference frame as given, then the sources
+ *   d_range [R][2] float64    (z_near, z_far)
+ *   d_pair_counts [R][n_frames][2] int32 or NULL  (shared[a][b], good[a][b]) for every frame b
+ *   d_ref_stats [R][4] int32  n_a, the candidates, the sources chosen, PGX_DVW_* bits: FEWPOINTS n_a < min_points; FEWVIEWS
+ *           fewer than S sources chosen; NARROW the range is finite but not z_near < z_far.  A reference that is outside
+ *           [0, n_frames) or not known has -1 for every source, a NaN range, zero counts and NOCAMERA alone.
+ *   d_report [8] int32: tracks processed, tracks used, nodes used, pairs counted (once each, whatever d_refs names), references
+ *           with a finite range, references with S sources, references with at least one source, 0.
+ * A frame named twice in d_refs gives two equal rows.
+ * Errors through pgx_check_status: n_tracks > max_tracks (PGX_E_CAPACITY; the first max_tracks tracks are processed); a node
+ * of a used track whose frame is outside [0, n_frames) (PGX_E_BADARG; the node is skipped); malformed offsets (o0 < 0,
+ * o1 < o0 or o1 > max_nodes: PGX_E_BADARG, the track counts as empty, as in the triangulation).  Only where malformed offsets make
+ * tracks overlap can there be more used nodes than max_nodes; the ranges are then unspecified (no access leaves the buffers).
+ * Returned at once (PGX_E_BADARG), with nothing written: S outside [1, 8], R or n_frames outside [1, 65535],
+ * R n_frames > 2^24, max_tracks or max_nodes < 0, angles that are not finite or not 0 <= min_angle_deg < max_angle_deg < 90,
+ * min_shared < 0, min_points < 1, R != n_frames without d_refs, q_near_pm or q_far_pm outside [0, 1000] or q_near_pm > q_far_pm, grow not finite or < 1, null
+ * required pointers, an output that overlaps an input.
+ * Workspace: 8 bytes per cell of R x n_frames, 8 bytes per entry of max_nodes, 112 bytes per frame.
+ * Results depend on the inputs only: the same bits from run to run, for any max_tracks >= n_tracks, on a used workspace and
+ * from the host form below.  Asynchronous on the context's stream. */
+#define PGX_DVW_NOCAMERA  1
+#define PGX_DVW_FEWPOINTS 2
+#define PGX_DVW_FEWVIEWS  4
+#define PGX_DVW_NARROW    8
+int pgx_dense_views_dev(pgx_ctx *ctx, const int32_t *d_offsets, const int32_t *d_nodes, const int32_t *d_track_summary,
+                        int max_tracks, int max_nodes, const double *d_xyz, const int32_t *d_track_flags, int n_frames,
+                        const double *d_P, const int32_t *d_refs /* [R] or NULL */, int R, int S, double min_angle_deg,
+                        double max_angle_deg, int min_shared, int min_points, int q_near_pm, int q_far_pm, double grow,
+                        int32_t *d_views /* [R][1 + S] */, double *d_range /* [R][2] */,
+                        int32_t *d_pair_counts /* [R][n_frames][2] or NULL */, int32_t *d_ref_stats /* [R][4] */,
+                        int32_t *d_report /* [8] */);
+/* Host form: host arrays in the layouts above, the same kernels (tracks as pgx_tracks_get writes them; offsets that are not
+ * non-decreasing from 0, or a node whose frame is outside [0, n_frames): PGX_E_BADARG before any GPU work).  nodes
+ * [n_nodes][2]; xyz [n_tracks][3]; track_flags [n_tracks] or NULL; refs [R] or NULL (then R = n_frames);
+ * pair_counts and ref_stats may be NULL.  R == 0: the report is zeroed and nothing else is written.  Returns when the
+ * outputs are in the caller's buffers. */
+int pgx_dense_views(pgx_ctx *ctx, const int32_t *track_offsets, const int32_t *nodes, int n_tracks, const double *xyz,
+                    const int32_t *track_flags, int n_frames, const double *P, const int32_t *refs, int R, int S,
+                    double min_angle_deg, double max_angle_deg, int min_shared, int min_points, int q_near_pm, int q_far_pm,
+                    double grow, int32_t *views, double *range, int32_t *pair_counts, int32_t *ref_stats, int32_t *report);
+
 /* ---- measurement hooks (bench.py) ---------------------------------------------------- */
 /* When on, the named hot kernels are bracketed by HIP events on the launch stream. */
 int pgx_profile_enable(pgx_ctx *ctx, int on);

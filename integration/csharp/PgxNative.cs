@@ -27,6 +27,7 @@ internal static unsafe class PgxNative
     public const int CnsFewViews = 1, CnsLowParallax = 2, CnsNoConsensus = 4, CnsShort = 8;   // PGX_CNS_* (0 = a consensus, kept)
     public const int VerFewMatches = 1, VerNoModel = 2, VerFewInliers = 4;                 // PGX_VER_* (0 = accepted)
     public const int DepNoCamera = 1, DepNoViews = 2, DepEdge = 4, DepHighCost = 8;       // PGX_DEP_* (0 = a depth)
+    public const int DvwNoCamera = 1, DvwFewPoints = 2, DvwFewViews = 4, DvwNarrow = 8;   // PGX_DVW_* (0 = S sources and a range)
     public const int InitSkipped = 1, InitBadInput = 2, InitDegenerate = 4, InitFewFront = 8, InitFewPoints = 16;   // PGX_INIT_* (0 = eligible)
 
     // Exports of include/pgx.h that this binding deliberately leaves out (tests/test_csharp_binding.py holds the list to the
@@ -259,6 +260,23 @@ internal static unsafe class PgxNative
     [DllImport(Lib)] public static extern int pgx_depth_fuse(IntPtr ctx, double* depth, int* views, int r, int s, int w, int h,
                                                              int nFrames, double* p, double relTol, int minAgree, int maxPoints,
                                                              double* xyz, int* src, int* agree, int* summary);
+
+    // the plan of the dense stage from the sparse model, between the last triangulation and pgx_depth_maps_dev: per reference
+    // (dRefs [r] frame numbers, or null: every frame, r = nFrames) dViews [r][1 + s] and dRange [r][2] as pgx_depth_maps_dev
+    // takes them, dPairCounts [r][nFrames][2] or null = (shared, good), dRefStats [r][4], dReport [8]; the graph is dOffsets,
+    // dNodes [maxNodes][2], dTrackSummary, the points dXyz [maxTracks][3] with dTrackFlags or null.  The host form takes host
+    // arrays in the same layouts (pairCounts and refStats may be null)
+    [DllImport(Lib)] public static extern int pgx_dense_views_dev(IntPtr ctx, void* dOffsets, void* dNodes, void* dTrackSummary,
+                                                                  int maxTracks, int maxNodes, void* dXyz, void* dTrackFlags,
+                                                                  int nFrames, void* dP, void* dRefs, int r, int s,
+                                                                  double minAngleDeg, double maxAngleDeg, int minShared,
+                                                                  int minPoints, int qNearPm, int qFarPm, double grow, void* dViews,
+                                                                  void* dRange, void* dPairCounts, void* dRefStats, void* dReport);
+    [DllImport(Lib)] public static extern int pgx_dense_views(IntPtr ctx, int* trackOffsets, int* nodes, int nTracks, double* xyz,
+                                                              int* trackFlags, int nFrames, double* p, int* refs, int r, int s,
+                                                              double minAngleDeg, double maxAngleDeg, int minShared, int minPoints,
+                                                              int qNearPm, int qFarPm, double grow, int* views, double* range,
+                                                              int* pairCounts, int* refStats, int* report);
 
     /// <summary>Maps a status code back to the exception type the managed implementation throws.</summary>
     public static void Check(IntPtr ctx, int rc)

@@ -17,6 +17,7 @@ PGX_E_BADARG, PGX_E_HIP, PGX_E_NOT_CONFIGURED, PGX_E_RCCL = 5, 6, 7, 8
 PGX_DIST_NONE = 2**31 - 1
 PGX_SRC_RGBA64, PGX_SRC_RGBA8 = 0, 1
 PGX_DEP_NOCAMERA, PGX_DEP_NOVIEWS, PGX_DEP_EDGE, PGX_DEP_HIGHCOST = 1, 2, 4, 8
+PGX_DVW_NOCAMERA, PGX_DVW_FEWPOINTS, PGX_DVW_FEWVIEWS, PGX_DVW_NARROW = 1, 2, 4, 8
 PGX_STAGE_DETECT, PGX_STAGE_MATCH_WIDE, PGX_STAGE_MATCH_ROWS, PGX_STAGE_MATCH_DONE = 0, 1, 2, 3
 
 # Every export of include/pgx.h with its signature, in the header's order: name -> (restype, [argtypes]).  lib() applies
@@ -106,6 +107,8 @@ SIGNATURES = {
     "pgx_depth_fuse_dev": (I, [P, P, P, I, I, I, I, I, P, D, I, I, P, P, P, P]),
     "pgx_depth_maps": (I, [P, P, I, I, I, P, P, I, I, P, I, I, I, I, P, P, P, P, P, P, P]),
     "pgx_depth_fuse": (I, [P, P, P, I, I, I, I, I, P, D, I, I, P, P, P, P]),
+    "pgx_dense_views_dev": (I, [P, P, P, P, I, I, P, P, I, P, P, I, I, D, D, I, I, I, I, D, P, P, P, P, P]),
+    "pgx_dense_views": (I, [P, P, P, I, P, P, I, P, P, I, I, D, D, I, I, I, I, D, P, P, P, P, P]),
     "pgx_profile_enable": (I, [P, I]),
     "pgx_profile_filter": (I, [P, S]),
     "pgx_profile_get": (I, [P, S, P, P]),

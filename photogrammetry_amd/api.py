@@ -769,6 +769,47 @@ class Engine:
         n = min(int(summary[0]), cap)
         return dict(xyz=xyz[:n], src=src[:n], agree=None if ag is None else ag[:R], summary=summary)
 
+    # -- the plan of the dense stage from the sparse model (pgx_dense_views*) ---------------------------------------
+    def dense_views_dev(self, d_offsets, d_nodes, d_track_summary, max_tracks, max_nodes, d_xyz, n_frames, d_P, R, S, d_views,
+                        d_range, d_ref_stats, d_report, d_track_flags=None, d_refs=None, min_angle_deg=2.0, max_angle_deg=45.0,
+                        min_shared=8, min_points=8, q_near_pm=10, q_far_pm=990, grow=1.25, d_pair_counts=None):
+        """pgx_dense_views_dev: per reference frame (d_refs [R] int32, or None: every frame, R = n_frames) its S source frames
+        and the depth interval to sweep, from the track graph (d_offsets, d_nodes [max_nodes][2], d_track_summary), the track
+        points d_xyz [max_tracks][3] (d_track_flags or None) and d_P [n_frames][12]: d_views [R][1 + S] int32 and d_range
+        [R][2] float64 as pgx_depth_maps_dev takes them, d_ref_stats [R][4], d_report [8] int32, d_pair_counts
+        [R][n_frames][2] int32 or None.  No sync."""
+        self._chk(self._L.pgx_dense_views_dev(
+            self._h, _dptr(d_offsets), _dptr(d_nodes), _dptr(d_track_summary), int(max_tracks), int(max_nodes), _dptr(d_xyz),
+            _dptr(d_track_flags), int(n_frames), _dptr(d_P), _dptr(d_refs), int(R), int(S), float(min_angle_deg),
+            float(max_angle_deg), int(min_shared), int(min_points), int(q_near_pm), int(q_far_pm), float(grow), _dptr(d_views),
+            _dptr(d_range), _dptr(d_pair_counts), _dptr(d_ref_stats), _dptr(d_report)))
+
+    def dense_views(self, track_offsets, nodes, xyz, cameras, S, refs=None, track_flags=None, min_angle_deg=2.0,
+                    max_angle_deg=45.0, min_shared=8, min_points=8, q_near_pm=10, q_far_pm=990, grow=1.25, pair_counts=True,
+                    ref_stats=True):
+        """The host form (pgx_dense_views).  Tracks as (track_offsets, nodes [n_nodes][2]), xyz [n_tracks][3], cameras
+        [n_frames][3][4] (or [n_frames][12]) float64, refs [R] or None (every frame) -> dict(views [R][1 + S], range [R][2],
+        pair_counts [R][n_frames][2], ref_stats [R][4], report [8]); pair_counts and ref_stats are None when not asked for."""
+        off = np.ascontiguousarray(track_offsets, dtype=np.int32).reshape(-1)
+        nd = np.ascontiguousarray(nodes, dtype=np.int32).reshape(-1, 2)
+        n = len(off) - 1
+        X = np.ascontiguousarray(xyz, dtype=np.float64).reshape(n, 3)
+        fl = None if track_flags is None else np.ascontiguousarray(track_flags, dtype=np.int32).reshape(n)
+        P = np.ascontiguousarray(cameras, dtype=np.float64).reshape(-1, 12)
+        nf = len(P)
+        rf = None if refs is None else np.ascontiguousarray(refs, dtype=np.int32).reshape(-1)
+        R = nf if rf is None else len(rf)
+        vw, rg = np.zeros((max(R, 1), 1 + int(S)), np.int32), np.zeros((max(R, 1), 2))
+        pc = np.zeros((max(R, 1), nf, 2), np.int32) if pair_counts else None
+        st = np.zeros((max(R, 1), 4), np.int32) if ref_stats else None
+        report = np.zeros(8, dtype=np.int32)
+        self._chk(self._L.pgx_dense_views(
+            self._h, _ptr(off), _ptr(nd) if len(nd) else None, n, _ptr(X) if n else None, _ptr(fl) if n else None, nf, _ptr(P),
+            _ptr(rf) if R else None, R, int(S), float(min_angle_deg), float(max_angle_deg), int(min_shared), int(min_points),
+            int(q_near_pm), int(q_far_pm), float(grow), _ptr(vw), _ptr(rg), _ptr(pc), _ptr(st), _ptr(report)))
+        return dict(views=vw[:R], range=rg[:R], pair_counts=None if pc is None else pc[:R],
+                    ref_stats=None if st is None else st[:R], report=report)
+
     # -- multi-GPU: the context's own RCCL communicator (pgx_comm_*) ------------------------------
     def comm_init(self, rank, world, unique_id):
         """Collective: every rank calls this with the 128 bytes rank 0 got from comm_unique_id()."""

@@ -106,6 +106,11 @@ int decode_status(pgx_ctx *c, int bits)
         return fail(c, PGX_E_CAPACITY, "pair selection: more than max_pairs pairs were selected (the first max_pairs were written)");
     if (bits & PGX_ST_DEP_CAP)
         return fail(c, PGX_E_CAPACITY, "depth fusion: more than max_points pixels were kept (the first max_points were written)");
+    if (bits & PGX_ST_DVW_CAP)
+        return fail(c, PGX_E_CAPACITY, "dense views: n_tracks exceeds max_tracks (only the first max_tracks were processed)");
+    if (bits & PGX_ST_DVW_NODE)
+        return fail(c, PGX_E_BADARG, "dense views: a node of a used track names a frame outside [0, n_frames), or the offsets are "
+                                     "malformed (those nodes were skipped)");
     return PGX_OK;
 }
 
@@ -465,7 +470,7 @@ void pgx_ctx_destroy(pgx_ctx *c)
     for (hipEvent_t ev : c->ev_pool) (void)hipEventDestroy(ev);
     DevBuf *bufs[] = {&c->d_pairs, &c->d_plan, &c->d_steer_pairs, &c->d_steer_plans, &c->d_steer_dirs, &c->d_map, &c->d_gather, &c->ws_gray, &c->ws_seg, &c->ws_segoff, &c->ws_nraw, &c->ws_rawxy,
                       &c->ws_rawscore, &c->ws_nms, &c->ws_order, &c->ws_nkept, &c->st_a, &c->st_b, &c->st_c,
-                      &c->st_d, &c->st_e, &c->st_f, &c->ws_pose, &c->ws_tracks, &c->ws_tracks_split, &c->ws_agree, &c->ws_matchn[0], &c->ws_matchn[1], &c->ws_matchn[2], &c->ws_knn, &c->ws_guided, &c->ws_tri, &c->ws_ba, &c->ws_reg, &c->ws_ver, &c->ws_init, &c->ws_cns, &c->ws_vocab, &c->ws_depth,
+                      &c->st_d, &c->st_e, &c->st_f, &c->ws_pose, &c->ws_tracks, &c->ws_tracks_split, &c->ws_agree, &c->ws_matchn[0], &c->ws_matchn[1], &c->ws_matchn[2], &c->ws_knn, &c->ws_guided, &c->ws_tri, &c->ws_ba, &c->ws_reg, &c->ws_ver, &c->ws_init, &c->ws_cns, &c->ws_vocab, &c->ws_depth, &c->ws_dviews,
                       &c->ws_pyr_a, &c->ws_pyr_b, &c->ws_pyr_kp, &c->ws_pyr_desc, &c->ws_pyr_bins, &c->ws_pyr_cnt};
     for (DevBuf *b : bufs) b->release();
     c->pin_in.release();
@@ -1513,6 +1518,16 @@ int run_depth_fuse(pgx_ctx *c, FuseArgs &a)
     return PGX_OK;
 }
 
+// the launcher brackets its own parts
+int run_dense_views(pgx_ctx *c, DvwArgs &a)
+{
+    a.status = c->d_status;
+    HIPCHK(c, c->ws_dviews.ensure(pgx_dense_views_ws_bytes(a)));
+    pgx_launch_dense_views(c, c->stream, a, c->ws_dviews.p);
+    HIPCHK(c, hipGetLastError());
+    return PGX_OK;
+}
+
 // ---- the track graph as a stage sees it (inv: the launcher's)
 
 // a device form's: an offset may reach every slot
@@ -2138,6 +2153,111 @@ int pgx_depth_fuse(pgx_ctx *c, const double *depth, const int32_t *views, int R,
         HIPCHK(c, hipMemcpy(src, out.dev<int32_t>(o_r), np * 8, hipMemcpyDeviceToHost));
     }
     return rs;
+}
+
+// ---- the plan of the dense stage: sources and depth range per reference ----------------------------------------------
+
+namespace {
+// what the device and the host form check alike (R == 0 is the host form's to allow); the squared cosines of the two angles
+int dvw_args(pgx_ctx *c, int R, int n_frames, int S, double min_angle_deg, double max_angle_deg, int min_shared, int min_points,
+             int q_near_pm, int q_far_pm, double grow, double *cmin2, double *cmax2)
+{
+    if (S < 1 || S > 8) return fail(c, PGX_E_BADARG, "S = %d, must be in [1, 8]", S);
+    if (R < 0 || R > 65535 || n_frames < 1 || n_frames > 65535) return fail(c, PGX_E_BADARG, "R and n_frames must be in [1, 65535]");
+    if ((long long)R * n_frames > (1ll << 24)) return fail(c, PGX_E_BADARG, "R * n_frames must be <= 2^24");
+    if (!std::isfinite(min_angle_deg) || !std::isfinite(max_angle_deg) || !(0.0 <= min_angle_deg && min_angle_deg < max_angle_deg && max_angle_deg < 90.0))
+        return fail(c, PGX_E_BADARG, "the angles must satisfy 0 <= min_angle_deg < max_angle_deg < 90");
+    if (min_shared < 0) return fail(c, PGX_E_BADARG, "min_shared must be >= 0");
+    if (min_points < 1) return fail(c, PGX_E_BADARG, "min_points must be >= 1");
+    if (q_near_pm < 0 || q_far_pm > 1000 || q_near_pm > q_far_pm)
+        return fail(c, PGX_E_BADARG, "the quantiles must satisfy 0 <= q_near_pm <= q_far_pm <= 1000");
+    if (!std::isfinite(grow) || grow < 1.0) return fail(c, PGX_E_BADARG, "grow must be finite and >= 1");
+    const double c0 = std::cos(min_angle_deg * M_PI / 180.0), c1 = std::cos(max_angle_deg * M_PI / 180.0);
+    *cmin2 = c0 * c0;
+    *cmax2 = c1 * c1;
+    return PGX_OK;
+}
+
+bool overlap(const void *p, size_t pn, const void *q, size_t qn)
+{
+    const char *a = static_cast<const char *>(p), *b = static_cast<const char *>(q);
+    return p && q && pn && qn && a < b + qn && b < a + pn;
+}
+} // namespace
+
+int pgx_dense_views_dev(pgx_ctx *c, const int32_t *d_offsets, const int32_t *d_nodes, const int32_t *d_track_summary, int max_tracks,
+                        int max_nodes, const double *d_xyz, const int32_t *d_track_flags, int n_frames, const double *d_P,
+                        const int32_t *d_refs, int R, int S, double min_angle_deg, double max_angle_deg, int min_shared,
+                        int min_points, int q_near_pm, int q_far_pm, double grow, int32_t *d_views, double *d_range,
+                        int32_t *d_pair_counts, int32_t *d_ref_stats, int32_t *d_report)
+{
+    if (!c || !d_offsets || !d_nodes || !d_track_summary || !d_xyz || !d_P || !d_views || !d_range || !d_ref_stats || !d_report)
+        return c ? fail(c, PGX_E_BADARG, "null pointer") : PGX_E_BADARG;
+    Lock l(c);
+    double cmin2 = 0.0, cmax2 = 0.0;
+    const int rc = dvw_args(c, R, n_frames, S, min_angle_deg, max_angle_deg, min_shared, min_points, q_near_pm, q_far_pm, grow, &cmin2, &cmax2);
+    if (rc != PGX_OK) return rc;
+    if (R == 0) return fail(c, PGX_E_BADARG, "R and n_frames must be in [1, 65535]");
+    if (!d_refs && R != n_frames) return fail(c, PGX_E_BADARG, "without d_refs, R must equal n_frames");
+    if (max_tracks < 0 || max_nodes < 0) return fail(c, PGX_E_BADARG, "max_tracks and max_nodes must be >= 0");
+    const size_t mt = max_tracks, nf = n_frames;
+    const struct { const void *p; size_t n; } in[] = {{d_offsets, (mt + 1) * 4}, {d_nodes, (size_t)max_nodes * 8}, {d_track_summary, 32},
+                                                      {d_xyz, mt * 24}, {d_track_flags, mt * 4}, {d_P, nf * 96}, {d_refs, (size_t)R * 4}},
+                                        out[] = {{d_views, (size_t)R * (1 + S) * 4}, {d_range, (size_t)R * 16},
+                                                 {d_pair_counts, (size_t)R * nf * 8}, {d_ref_stats, (size_t)R * 16}, {d_report, 32}};
+    for (const auto &o : out)
+        for (const auto &i : in)
+            if (overlap(o.p, o.n, i.p, i.n)) return fail(c, PGX_E_BADARG, "an output must not alias an input");
+    DvwArgs a{};
+    a.tv.offsets = d_offsets; a.tv.nodes = d_nodes; a.tv.track_summary = d_track_summary;
+    a.tv.n_frames = n_frames; a.tv.max_tracks = max_tracks; a.tv.node_cap = max_nodes;
+    a.xyz = d_xyz; a.track_flags = d_track_flags; a.P = d_P; a.refs = d_refs;
+    a.R = R; a.S = S; a.min_shared = min_shared; a.min_points = min_points; a.q_near_pm = q_near_pm; a.q_far_pm = q_far_pm;
+    a.cmin2 = cmin2; a.cmax2 = cmax2; a.grow = grow;
+    a.views = d_views; a.range = d_range; a.pair_counts = d_pair_counts; a.ref_stats = d_ref_stats; a.report = d_report;
+    return run_dense_views(c, a);
+}
+
+int pgx_dense_views(pgx_ctx *c, const int32_t *track_offsets, const int32_t *nodes, int n_tracks, const double *xyz,
+                    const int32_t *track_flags, int n_frames, const double *P, const int32_t *refs, int R, int S, double min_angle_deg,
+                    double max_angle_deg, int min_shared, int min_points, int q_near_pm, int q_far_pm, double grow, int32_t *views,
+                    double *range, int32_t *pair_counts, int32_t *ref_stats, int32_t *report)
+{
+    if (!c || !track_offsets || !P || !report || n_tracks < 0 || (n_tracks > 0 && !xyz) || (R > 0 && (!views || !range)))
+        return c ? fail(c, PGX_E_BADARG, "null pointer or bad size") : PGX_E_BADARG;
+    Lock l(c);
+    double cmin2 = 0.0, cmax2 = 0.0;
+    int rc = dvw_args(c, R, n_frames, S, min_angle_deg, max_angle_deg, min_shared, min_points, q_near_pm, q_far_pm, grow, &cmin2, &cmax2);
+    if (rc != PGX_OK) return rc;
+    if (track_offsets[0] != 0) return fail(c, PGX_E_BADARG, "track_offsets[0] must be 0");
+    for (int t = 0; t < n_tracks; t++)
+        if (track_offsets[t + 1] < track_offsets[t]) return fail(c, PGX_E_BADARG, "track_offsets decrease at track %d", t);
+    const long long n_nodes = track_offsets[n_tracks];
+    if (n_nodes > 0 && !nodes) return fail(c, PGX_E_BADARG, "null pointer (nodes)");
+    for (long long o = 0; o < n_nodes; o++)
+        if (nodes[2 * o] < 0 || nodes[2 * o] >= n_frames)
+            return fail(c, PGX_E_BADARG, "node %lld names frame %d outside [0, n_frames)", o, nodes[2 * o]);
+    for (int i = 0; i < 8; i++) report[i] = 0;
+    if (R == 0) return PGX_OK;
+    if (!refs && R != n_frames) return fail(c, PGX_E_BADARG, "without refs, R must equal n_frames");
+    HostImage in, out;
+    const int i_off = in.add(track_offsets, n_tracks + 1, 4), i_nd = in.add(nodes, n_nodes, 8, 1), i_xyz = in.add(xyz, n_tracks, 24, 1),
+              i_fl = in.add(track_flags, n_tracks, 4, 1, track_flags != nullptr), i_P = in.add(P, n_frames, 96),
+              i_refs = in.add(refs, R, 4, 0, refs != nullptr), i_ts = in.add_words({n_tracks, (int32_t)n_nodes}, 64);
+    const int o_v = out.add(views, (size_t)R * (1 + S), 4), o_r = out.add(range, R, 16),
+              o_pc = out.add(pair_counts, (size_t)R * n_frames, 8, 0, pair_counts != nullptr), o_st = out.add(ref_stats, R, 16),
+              o_rep = out.add(report, 8, 4, 64);
+    if ((rc = stage_images(c, in, out)) != PGX_OK) return rc;
+    DvwArgs a{};
+    a.tv.offsets = in.dev<int32_t>(i_off); a.tv.nodes = in.dev<int32_t>(i_nd); a.tv.track_summary = in.dev<int32_t>(i_ts);
+    a.tv.n_frames = n_frames; a.tv.max_tracks = n_tracks; a.tv.node_cap = n_nodes;
+    a.xyz = in.dev<double>(i_xyz); a.track_flags = in.dev<int32_t>(i_fl); a.P = in.dev<double>(i_P); a.refs = in.dev<int32_t>(i_refs);
+    a.R = R; a.S = S; a.min_shared = min_shared; a.min_points = min_points; a.q_near_pm = q_near_pm; a.q_far_pm = q_far_pm;
+    a.cmin2 = cmin2; a.cmax2 = cmax2; a.grow = grow;
+    a.views = out.dev<int32_t>(o_v); a.range = out.dev<double>(o_r); a.pair_counts = out.dev<int32_t>(o_pc);
+    a.ref_stats = out.dev<int32_t>(o_st); a.report = out.dev<int32_t>(o_rep);   // ref_stats is carved, and downloaded when given
+    if ((rc = run_dense_views(c, a)) != PGX_OK) return rc;
+    return download_images(c, out);
 }
 
 // ---- measurement hooks ---------------------------------------------------------------------

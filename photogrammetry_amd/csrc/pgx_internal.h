@@ -40,6 +40,8 @@
 #define PGX_ST_VOC_FEW    8388608u  /* pgx_vocab_train_dev: fewer valid descriptors than words */
 #define PGX_ST_SEL_CAP    16777216u /* pgx_select_pairs_dev: more than max_pairs pairs selected */
 #define PGX_ST_DEP_CAP    33554432u /* pgx_depth_fuse_dev: more than max_points pixels kept */
+#define PGX_ST_DVW_CAP    67108864u  /* pgx_dense_views_dev: n_tracks > max_tracks */
+#define PGX_ST_DVW_NODE   134217728u /* pgx_dense_views_dev: a node of a used track outside the frames, or malformed offsets */
 
 // key = (distance << PGX_IDX_BITS) | index ; limits: index < 2^20, distance < 2^12
 #define PGX_IDX_BITS 20
@@ -161,6 +163,7 @@ struct pgx_ctx {
     DevBuf ws_ver;    // pgx_verify_pair*: candidate lists of a chunk of image pairs, hypotheses of one chunk of samples, keys
     DevBuf ws_vocab;  // pgx_vocab_train*, pgx_select_pairs*: words per descriptor, members by word, histograms, weights, scores
     DevBuf ws_depth;  // pgx_depth_maps*, pgx_depth_fuse*: census words per slot, warps, plane tables; camera table, keep flags, block sums
+    DevBuf ws_dviews; // pgx_dense_views*: pair-count table, frame table, depths bucketed by frame, per-frame counts and cursors
     DevBuf ws_init;   // pgx_init_pair_dev, pgx_relative_pose: per image pair the two rotations, t, the intrinsics and the counters
     hipStream_t mstream[3] = {nullptr, nullptr, nullptr}; // [0] wide rounds, [1] residual distance rows, [2] per-pair finish
     hipEvent_t ev_in = nullptr, ev_wide[3] = {nullptr, nullptr, nullptr}, ev_rows[3] = {nullptr, nullptr, nullptr},

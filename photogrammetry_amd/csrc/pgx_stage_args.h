@@ -1,5 +1,5 @@
 // pgx_stage_args.h -- the arguments of the stages behind the matchers, each as the struct its kernels take by value:
-// triangulation, bundle adjustment, registration, consensus, verification, initial pair, depth maps, depth fuse.  The C ABI's
+// triangulation, bundle adjustment, registration, consensus, verification, initial pair, depth maps, depth fuse, dense views.  The C ABI's
 // two forms of a stage (pgx_api.hip) fill "the caller fills" by name and hand the struct to run_X; the launcher carves the
 // workspace into the rest and launches.  The layout IS the kernarg layout: fields, order and types are the kernels' (the
 // capitals in the shapes are constants of the stage's .hip file).  Internal to libpgx.so; DESIGN.md section 14h.
@@ -217,3 +217,30 @@ struct FuseArgs {
 };
 size_t pgx_depth_fuse_ws_bytes(const FuseArgs &a);
 void pgx_launch_depth_fuse(pgx_ctx *ctx, hipStream_t s, FuseArgs a, void *ws);
+
+// ---- k_denseviews.hip (sources and depth range per reference from the sparse model; pgx_dense_views_dev semantics) ---------
+// ctx: the profiling groups dense_views_nodes / _pairs / _select
+struct DvwArgs {
+    // the caller fills
+    TrackView tv;                 // the graph alone: no keypoints, no slots; node_cap = max_nodes
+    const double *xyz;            // [max_tracks][3]
+    const int32_t *track_flags;   // [max_tracks] or nullptr
+    const double *P;              // [n_frames][12]
+    const int32_t *refs;          // [R] or nullptr
+    int R, S, min_shared, min_points, q_near_pm, q_far_pm;
+    double cmin2, cmax2, grow;    // the squares of the cosines of min_angle_deg and max_angle_deg
+    int32_t *views;               // [R][1 + S]
+    double *range;                // [R][2]
+    int32_t *pair_counts, *ref_stats, *report;   // [R][n_frames][2] or nullptr, [R][4], [8]
+    // the launcher fills (workspace)
+    unsigned long long *cells;    // [R][n_frames]: shared | good << 32, counted in the first row that names a frame
+    double *cam;                  // [n_frames][DVW_CAM]
+    double *zb;                   // [node_cap]: the depths of the used nodes, frame f's at fbase[f] .. fbase[f + 1]
+    int32_t *rowof;               // [n_frames]: the first row of refs that names the frame, or DVW_NOROW
+    int32_t *fcnt, *fbase, *fcur; // [n_frames], [n_frames + 1], [n_frames]: used nodes, bucket starts, scatter cursors
+    int32_t *meta;                // [0] tracks to process
+    // the caller fills
+    int *status;                  // PGX_ST_DVW_* bits
+};
+size_t pgx_dense_views_ws_bytes(const DvwArgs &a);
+void pgx_launch_dense_views(pgx_ctx *ctx, hipStream_t s, DvwArgs a, void *ws);

@@ -1,0 +1,73 @@
+"""One command for the chain that DESIGN.md section 27 closes: pgx_triangulate_tracks_dev -> pgx_dense_views_dev ->
+pgx_gray_batch_dev -> pgx_depth_maps_dev -> pgx_depth_fuse_dev on one stream, with no synchronisation between the
+triangulation and the filter.  The scene is synth.make_scene's (frames on an arc, true tracks cut to runs); the frames are
+seeded noise, so the maps carry no meaning: the tool shows that the chain runs and what it costs.  Timed with HIP events on
+geom_bench's loop; prints one JSON line and writes profiles/dense_chain_<shape>.json (or --out DIR)."""
+import argparse
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+sys.path.insert(0, ROOT)
+import geom_bench as gb  # noqa: E402
+import photogrammetry_amd as pg  # noqa: E402
+from geom_bench import DEV, F64, I32  # noqa: E402
+
+PARTS = ("triangulate", "dense_views_nodes", "dense_views_pairs", "dense_views_select", "dewarp_gray", "depth_census", "depth_plan",
+         "depth_sweep", "depth_fuse")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=9)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--width", type=int, default=640)
+    ap.add_argument("--height", type=int, default=480)
+    ap.add_argument("--frames", type=int, default=16)
+    ap.add_argument("--points", type=int, default=4000)
+    ap.add_argument("--sources", type=int, default=4)
+    ap.add_argument("--planes", type=int, default=64)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles"))
+    args = ap.parse_args()
+    W, H, nf, S, D = args.width, args.height, args.frames, args.sources, args.planes
+    rng = np.random.default_rng(0)
+    eng = pg.Engine(0)
+    s, off, nodes, _ = gb.cut_scene(rng, nf, args.points)
+    d = gb.device_inputs(s["kps"], off, nodes, P=s["P"])
+    nt, N = d["n_tracks"], nf * d["stride"]
+    rgba = torch.from_numpy(rng.integers(0, 65536, (nf, H, W, 4), dtype=np.uint16)).to(DEV)
+    xyz, q, tfl, tsum = torch.empty((nt, 3), **F64), torch.empty((nt, 3), **F64), torch.empty(nt, **I32), torch.empty(8, **I32)
+    views, rng_d, st, rep = torch.empty((nf, 1 + S), **I32), torch.empty((nf, 2), **F64), torch.empty((nf, 4), **I32), torch.empty(8, **I32)
+    gray = torch.empty((nf, H, W), dtype=torch.float32, device=DEV)
+    kq8, fl, dep, msum = torch.empty((nf, H, W), **I32), torch.empty((nf, H, W), **I32), torch.empty((nf, H, W), **F64), torch.empty(8, **I32)
+    cap = nf * H * W
+    pts, src, fsum = torch.empty((cap, 3), **F64), torch.empty((cap, 2), **I32), torch.empty(4, **I32)
+    torch.cuda.synchronize()
+
+    def chain():
+        eng.triangulate_tracks_dev(d["kp"], nf, d["stride"], nf, d["P"], d["off"], d["nodes"], d["tsum"], nt, xyz, q, tfl, tsum, 1.0, 2.0, 10)
+        eng.dense_views_dev(d["off"], d["nodes"], d["tsum"], nt, N, xyz, nf, d["P"], nf, S, views, rng_d, st, rep, d_track_flags=tfl)
+        eng.gray_batch_dev(rgba, nf, W, H, gray)
+        eng.depth_maps_dev(gray, nf, W, H, nf, d["P"], views, nf, S, rng_d, D, kq8, dep, fl, msum, agg_radius=2, min_views=2)
+        eng.depth_fuse_dev(dep, views, nf, S, W, H, nf, d["P"], cap, pts, src, fsum)
+    ms = gb.time_on_stream(eng, chain, args.steps, args.warmup)
+    eng.profile_reset()
+    eng.profile_enable(True)
+    for _ in range(args.steps):
+        chain()
+    eng.check_status()
+    parts = {p: eng.profile_get(p)[1] / args.steps for p in PARTS}
+    eng.profile_enable(False)
+    rec = dict(shape="%dx%d_f%d_s%d_d%d" % (W, H, nf, S, D), frames=nf, tracks=nt, nodes=d["n_nodes"], steps=args.steps,
+               chain_ms_median=float(np.median(ms)), chain_ms_min=float(ms.min()), chain_ms_max=float(ms.max()),
+               parts_ms={k: round(v, 4) for k, v in parts.items()}, views_report=rep.cpu().tolist(), maps_summary=msum.cpu().tolist(),
+               fuse_summary=fsum.cpu().tolist(), refs_flagged=int((st.cpu().numpy()[:, 3] != 0).sum()))
+    gb.write_record(rec, args.out, "dense_chain")
+    eng.close()
+
+
+if __name__ == "__main__":
+    main()
