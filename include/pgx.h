@@ -1134,6 +1134,90 @@ int pgx_dense_views(pgx_ctx *ctx, const int32_t *track_offsets, const int32_t *n
                     double min_angle_deg, double max_angle_deg, int min_shared, int min_points, int q_near_pm, int q_far_pm,
                     double grow, int32_t *views, double *range, int32_t *pair_counts, int32_t *ref_stats, int32_t *report);
 
+/* ---- the fused points merged into one cloud, with normals and colour ------------------------------ */
+/* pgx_depth_fuse_dev ends with one list entry per kept pixel and map: a surface point seen by five references appears five
+ * times, without a normal and without a colour.  These calls make the cloud a user writes to a file and meshes: one point per
+ * occupied cell of a grid, its normal from the depth maps and its colour from the frames, on the same stream with no host
+ * round trip.  Integers wherever a rule can be an integer (every sum is one, so no order of execution changes a bit), float64
+ * elsewhere, one IEEE operation at a time in the order written, nothing contracted: bit-identical to a numpy restatement
+ * (tests/cloud_ref.py).  Not in the C# reference.  k_image.hip, k_cloud.hip.
+ *
+ * pgx_rgba8_batch_dev: d_rgba8 [F][H][W] uint32 = per frame and pixel the pixel that pgx_dewarp writes (the context's source
+ * format, gathered through the context's dewarp map when one is set: then W x H must be the map's, PGX_E_DIM_MISMATCH, and a map
+ * entry outside the image gives the zero pixel and PGX_E_OOB_SOURCE from pgx_check_status), channel c in bits 8 c .. 8 c + 7 in the
+ * source's channel order: the high byte of each 16-bit channel; an RGBA8 source's bytes as they are.  Asynchronous. */
+int pgx_rgba8_batch_dev(pgx_ctx *ctx, const uint16_t *d_rgba, int F, int W, int H, uint32_t *d_rgba8 /* [F][H][W] */);
+/* pgx_cloud_merge_dev.
+ * Inputs.  d_xyz [max_in][3] float64 and d_src [max_in][2] int32 = (r, v W + u) as pgx_depth_fuse_dev writes them; any list in
+ * that layout, in any order.  d_count int32 on the device or NULL (the filter's d_summary fits):
+ * n = min(max(d_count[0], 0), max_in), or max_in with NULL; n is read on the device.  d_depth [R][H][W], d_views [R][1 + S] (only
+ * column 0 is read), n_frames and d_P as for the filter.  d_rgba8 [F][H][W] (pgx_rgba8_batch_dev's) or NULL; F slots and
+ * d_frame_ids [F] or NULL as for pgx_depth_maps_dev: the lowest slot that shows a frame is used.  F and d_frame_ids are not read
+ * without d_rgba8.
+ *   1 used    point i < n is USED iff its three coordinates are finite, r = src[i][0] is in [0, R), pix = src[i][1] is in
+ *             [0, W H), and for every axis a, t_a = (X_a - o_a) / cell and g_a = floor(t_a) satisfy -2^20 <= g_a < 2^20
+ *             (o = (ox, oy, oz)).  key = (g_0 + 2^20) << 42 | (g_1 + 2^20) << 21 | (g_2 + 2^20).  The position in the cell:
+ *             p_a = (int) floor((t_a - g_a) 65536.0), 0 <= p_a <= 65535; the subtraction and the scaling are exact.
+ *   2 normal  of a used point, from its own map alone.  (u, v) = (pix % W, pix / W), z = depth[r][v][u].  No normal when map r is
+ *             skipped by the filter's rule (its frame outside [0, n_frames) or its camera unknown) or z is not finite.
+ *             X_c = the filter's back-projection of (u, v, z).  A neighbour (u', v') COUNTS iff it is inside the image, its
+ *             depth z' is finite and |z' - z| <= disc_tol z; its point is the same back-projection of (u', v', z').  Along u,
+ *             with the neighbours at u +- k (k = normal_step): d_u = X+ - X- when both count, X+ - X_c when only the forward
+ *             one does, X_c - X- when only the backward one does; no normal when neither counts.  d_v the same along v.
+ *             n = d_u x d_v, each component a b - c d: n_0 = d_u1 d_v2 - d_u2 d_v1, n_1 = d_u2 d_v0 - d_u0 d_v2,
+ *             n_2 = d_u0 d_v1 - d_u1 d_v0.  The ray: e_i = (adj(M_r)[i][0] u + adj(M_r)[i][1] v) + adj(M_r)[i][2];
+ *             dX/dz = (sign(det) ||m3|| / det) e has the direction of e for either sign of det, so the normal faces the camera
+ *             iff n . e < 0.  s = (n_0 e_0 + n_1 e_1) + n_2 e_2, L = sqrt((n_0 n_0 + n_1 n_1) + n_2 n_2).  No normal when L is not
+ *             finite, L == 0, s is not finite or s == 0.  Otherwise m = (s > 0 ? -n : n) / L and
+ *             q_a = (int) floor(m_a 32767.0 + 0.5).
+ *   3 colour  of a used point: word pix of the slot that shows frame views[r][0], its low three bytes.  No colour when d_rgba8
+ *             is NULL or no slot shows the frame.
+ *   4 cells   per key, over its used points, in int64 or int32: cnt; the three sums sp of p; nn and the three sums sn of q over
+ *             the points with a normal; nc and the three channel sums sc over the points with a colour; first = the smallest i.
+ *   5 output  a cell is KEPT iff cnt >= min_support.  The kept cells in ascending first, the order of first appearance in the
+ *             list:
+ *             d_out_xyz [max_points][3] float64 = o_a + ((double) g_a + ((double)(2 sp_a + cnt) / (double)(2 cnt)) / 65536.0) cell:
+ *               the mean of the points' positions to cell / 65536 (each point stands at the middle of its 1/65536 of the cell);
+ *             d_out_normal [max_points][3] float32 = (float)(s_a / L), s_a = (double) sn_a, L = sqrt((s_0 s_0 + s_1 s_1) + s_2 s_2);
+ *               zeros when nn == 0 or L == 0;
+ *             d_out_rgba8 [max_points] uint32: channel c = (2 sc_c + nc) / (2 nc) in integers in bits 8 c .. 8 c + 7, alpha 255;
+ *               0 when nc == 0;
+ *             d_out_info [max_points][4] int32 = (cnt, nn, nc, first).
+ * Optional: d_pt_normal [max_in][3] int32 = q, zeros for a point without a normal; d_cell_of [max_in] int32 = the output index
+ * of the point's cell (the full index, also at or past max_points), -1 for a point that is not used, -2 for a point of a dropped
+ * cell.  Rows i >= n of both are not written.
+ * d_report [8] int32: n, used, not used, points with a normal, points with a colour, cells, cells kept (the full count), 0.
+ * More than max_points cells kept: the first max_points are written and pgx_check_status reports PGX_E_CAPACITY.
+ * Returned at once (PGX_E_BADARG), with nothing written: S outside [1, 8], R outside [1, 65535], W or H outside [1, 65535],
+ * R W H > 2^30, n_frames < 1, max_in or max_points outside [0, 2^28]; with d_rgba8: F outside [1, 65535], F W H > 2^30, n_frames != F
+ * without d_frame_ids; cell not finite or <= 0, an origin that is not finite, normal_step outside [1, 8], disc_tol not finite or
+ * < 0, min_support < 1, null required pointers (d_xyz and d_src may be NULL with max_in == 0, the four outputs with
+ * max_points == 0), an output that overlaps an input.
+ * Workspace: 20 bytes per entry of a table of the power of two >= max(2 max_in, 256) entries, 20 bytes per entry of max_in,
+ * 84 bytes per entry of max_points.
+ * Results depend on the inputs only: the same bits from run to run, for any slot layout of the same frames, on a used
+ * workspace and from the host form; a permuted list gives the same cells with the same sums, in the order of their new first.
+ * Asynchronous on the context's stream. */
+int pgx_cloud_merge_dev(pgx_ctx *ctx, const double *d_xyz /* [max_in][3] */, const int32_t *d_src /* [max_in][2] */,
+                        const int32_t *d_count /* [1] or NULL */, int max_in, const double *d_depth /* [R][H][W] */,
+                        const int32_t *d_views /* [R][1 + S] */, int R, int S, int W, int H, int n_frames, const double *d_P,
+                        const uint32_t *d_rgba8 /* [F][H][W] or NULL */, int F, const int32_t *d_frame_ids /* [F] or NULL */,
+                        double cell, double ox, double oy, double oz, int normal_step, double disc_tol, int min_support,
+                        int max_points, double *d_out_xyz /* [max_points][3] */, float *d_out_normal /* [max_points][3] */,
+                        uint32_t *d_out_rgba8 /* [max_points] */, int32_t *d_out_info /* [max_points][4] */,
+                        int32_t *d_pt_normal /* [max_in][3] or NULL */, int32_t *d_cell_of /* [max_in] or NULL */,
+                        int32_t *d_report /* [8] */);
+/* Host forms: host arrays in the layouts above, the same kernels; they return when the results are in the caller's buffers.
+ * pgx_rgba8_batch: rgba [F][H][W] in the context's source format.  pgx_cloud_merge: the list has n_in entries (no d_count);
+ * rgba8 [n_frames][H][W] by frame number (no slots) or NULL; pt_normal and cell_of may be NULL; the report is downloaded first,
+ * then min(report[6], max_points) rows of the four outputs. */
+int pgx_rgba8_batch(pgx_ctx *ctx, const void *rgba, int F, int W, int H, uint32_t *rgba8);
+int pgx_cloud_merge(pgx_ctx *ctx, const double *xyz, const int32_t *src, int n_in, const double *depth, const int32_t *views, int R,
+                    int S, int W, int H, int n_frames, const double *P, const uint32_t *rgba8, double cell, double ox, double oy,
+                    double oz, int normal_step, double disc_tol, int min_support, int max_points, double *out_xyz,
+                    float *out_normal, uint32_t *out_rgba8, int32_t *out_info, int32_t *pt_normal, int32_t *cell_of,
+                    int32_t *report);
+
 /* ---- measurement hooks (bench.py) ---------------------------------------------------- */
 /* When on, the named hot kernels are bracketed by HIP events on the launch stream. */
 int pgx_profile_enable(pgx_ctx *ctx, int on);

@@ -278,6 +278,28 @@ internal static unsafe class PgxNative
                                                               int qNearPm, int qFarPm, double grow, int* views, double* range,
                                                               int* pairCounts, int* refStats, int* report);
 
+    // the fused points merged into one cloud with normals and colour (not in the reference): dRgba8 [f][h][w] uint32 = the dewarped
+    // pixel at 8 bits a channel; the merge takes the filter's dXyz [maxIn][3], dSrc [maxIn][2] and dCount (the filter's dSummary,
+    // or null: maxIn entries), the maps and cameras as the filter does, dRgba8 by slot with dFrameIds or null, and writes one point
+    // per occupied cell of the grid: dOutXyz [maxPoints][3] float64, dOutNormal [maxPoints][3] float32, dOutRgba8 [maxPoints],
+    // dOutInfo [maxPoints][4] = (cnt, nn, nc, first), dPtNormal [maxIn][3] and dCellOf [maxIn] or null, dReport [8].  The host
+    // forms take host arrays in the same layouts (rgba8 [nFrames][h][w] by frame number)
+    [DllImport(Lib)] public static extern int pgx_rgba8_batch_dev(IntPtr ctx, void* dRgba, int f, int w, int h, void* dRgba8);
+    [DllImport(Lib)] public static extern int pgx_cloud_merge_dev(IntPtr ctx, void* dXyz, void* dSrc, void* dCount, int maxIn,
+                                                                  void* dDepth, void* dViews, int r, int s, int w, int h,
+                                                                  int nFrames, void* dP, void* dRgba8, int f, void* dFrameIds,
+                                                                  double cell, double ox, double oy, double oz, int normalStep,
+                                                                  double discTol, int minSupport, int maxPoints, void* dOutXyz,
+                                                                  void* dOutNormal, void* dOutRgba8, void* dOutInfo,
+                                                                  void* dPtNormal, void* dCellOf, void* dReport);
+    [DllImport(Lib)] public static extern int pgx_rgba8_batch(IntPtr ctx, void* rgba, int f, int w, int h, uint* rgba8);
+    [DllImport(Lib)] public static extern int pgx_cloud_merge(IntPtr ctx, double* xyz, int* src, int nIn, double* depth, int* views,
+                                                              int r, int s, int w, int h, int nFrames, double* p, uint* rgba8,
+                                                              double cell, double ox, double oy, double oz, int normalStep,
+                                                              double discTol, int minSupport, int maxPoints, double* outXyz,
+                                                              float* outNormal, uint* outRgba8, int* outInfo, int* ptNormal,
+                                                              int* cellOf, int* report);
+
     /// <summary>Maps a status code back to the exception type the managed implementation throws.</summary>
     public static void Check(IntPtr ctx, int rc)
     {

@@ -109,6 +109,10 @@ SIGNATURES = {
     "pgx_depth_fuse": (I, [P, P, P, I, I, I, I, I, P, D, I, I, P, P, P, P]),
     "pgx_dense_views_dev": (I, [P, P, P, P, I, I, P, P, I, P, P, I, I, D, D, I, I, I, I, D, P, P, P, P, P]),
     "pgx_dense_views": (I, [P, P, P, I, P, P, I, P, P, I, I, D, D, I, I, I, I, D, P, P, P, P, P]),
+    "pgx_rgba8_batch_dev": (I, [P, P, I, I, I, P]),
+    "pgx_cloud_merge_dev": (I, [P, P, P, P, I, P, P, I, I, I, I, I, P, P, I, P, D, D, D, D, I, D, I, I, P, P, P, P, P, P, P]),
+    "pgx_rgba8_batch": (I, [P, P, I, I, I, P]),
+    "pgx_cloud_merge": (I, [P, P, P, I, P, P, I, I, I, I, I, P, P, D, D, D, D, I, D, I, I, P, P, P, P, P, P, P]),
     "pgx_profile_enable": (I, [P, I]),
     "pgx_profile_filter": (I, [P, S]),
     "pgx_profile_get": (I, [P, S, P, P]),

@@ -810,6 +810,67 @@ class Engine:
         return dict(views=vw[:R], range=rg[:R], pair_counts=None if pc is None else pc[:R],
                     ref_stats=None if st is None else st[:R], report=report)
 
+    # -- the fused points merged into one cloud with normals and colour (pgx_rgba8_batch*, pgx_cloud_merge*) ---------
+    def rgba8_batch_dev(self, d_rgba, F, W, H, d_rgba8):
+        """pgx_rgba8_batch_dev: d_rgba8 [F][H][W] uint32 = pgx_dewarp's pixel of every frame of d_rgba at 8 bits a channel
+        (channel c in bits 8 c .. 8 c + 7).  No sync."""
+        self._chk(self._L.pgx_rgba8_batch_dev(self._h, _dptr(d_rgba), int(F), int(W), int(H), _dptr(d_rgba8)))
+
+    def cloud_merge_dev(self, d_xyz, d_src, d_count, max_in, d_depth, d_views, R, S, W, H, n_frames, d_P, cell, origin, max_points,
+                        d_out_xyz, d_out_normal, d_out_rgba8, d_out_info, d_report, d_rgba8=None, F=0, d_frame_ids=None,
+                        normal_step=1, disc_tol=0.02, min_support=1, d_pt_normal=None, d_cell_of=None):
+        """pgx_cloud_merge_dev: the list d_xyz [max_in][3] float64 / d_src [max_in][2] int32 of pgx_depth_fuse_dev (d_count int32
+        on the device, e.g. the filter's d_summary, or None: max_in entries) merged into one point per occupied cell of the grid
+        of `cell` at `origin`: d_out_xyz [max_points][3] float64, d_out_normal [max_points][3] float32, d_out_rgba8 [max_points]
+        uint32, d_out_info [max_points][4] int32 = (cnt, nn, nc, first), d_report [8] int32 ([6] = the cells kept); d_pt_normal
+        [max_in][3] and d_cell_of [max_in] int32 or None.  More than max_points: CapacityError from check_status.  No sync."""
+        ox, oy, oz = (float(x) for x in origin)
+        self._chk(self._L.pgx_cloud_merge_dev(
+            self._h, _dptr(d_xyz), _dptr(d_src), _dptr(d_count), int(max_in), _dptr(d_depth), _dptr(d_views), int(R), int(S), int(W),
+            int(H), int(n_frames), _dptr(d_P), _dptr(d_rgba8), int(F), _dptr(d_frame_ids), float(cell), ox, oy, oz, int(normal_step),
+            float(disc_tol), int(min_support), int(max_points), _dptr(d_out_xyz), _dptr(d_out_normal), _dptr(d_out_rgba8),
+            _dptr(d_out_info), _dptr(d_pt_normal), _dptr(d_cell_of), _dptr(d_report)))
+
+    def rgba8_batch(self, rgba):
+        """The host form (pgx_rgba8_batch).  rgba [F][H][W][4] in the context's source format (uint16, or uint8 after
+        set_source_format(PGX_SRC_RGBA8)) -> [F][H][W] uint32."""
+        a = np.ascontiguousarray(rgba, dtype=getattr(self, "_src_dtype", np.uint16))
+        F, H, W = a.shape[:3]
+        out = np.zeros((F, H, W), dtype=np.uint32)
+        self._chk(self._L.pgx_rgba8_batch(self._h, _ptr(a), F, W, H, _ptr(out)))
+        return out
+
+    def cloud_merge(self, xyz, src, depth, views, cameras, cell, origin, rgba8=None, normal_step=1, disc_tol=0.02, min_support=1,
+                    max_points=None, pt_normal=True, cell_of=True):
+        """The host form (pgx_cloud_merge).  xyz [n][3] float64 and src [n][2] int32 as depth_fuse returns them, depth [R][H][W],
+        views [R][1 + S], cameras [n_frames][3][4], rgba8 [n_frames][H][W] uint32 or None -> dict(xyz [m][3], normal [m][3]
+        float32, rgba8 [m], info [m][4] trimmed to min(report[6], max_points), pt_normal [n][3], cell_of [n] or None, report [8]).
+        max_points defaults to n; a smaller one that cuts the cloud raises CapacityError."""
+        X = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+        sr = np.ascontiguousarray(src, dtype=np.int32).reshape(-1, 2)
+        n = len(X)
+        d = np.ascontiguousarray(depth, dtype=np.float64)
+        R, H, W = d.shape
+        vw = np.ascontiguousarray(views, dtype=np.int32)
+        vw = vw.reshape(R, vw.shape[-1])
+        P = np.ascontiguousarray(cameras, dtype=np.float64).reshape(-1, 12)
+        col = None if rgba8 is None else np.ascontiguousarray(rgba8, dtype=np.uint32).reshape(len(P), H, W)
+        cap = n if max_points is None else int(max_points)
+        m = max(cap, 1)
+        oxyz, onrm = np.zeros((m, 3)), np.zeros((m, 3), dtype=np.float32)
+        orgb, oinf = np.zeros(m, dtype=np.uint32), np.zeros((m, 4), dtype=np.int32)
+        pn = np.zeros((max(n, 1), 3), dtype=np.int32) if pt_normal else None
+        co = np.zeros(max(n, 1), dtype=np.int32) if cell_of else None
+        report = np.zeros(8, dtype=np.int32)
+        ox, oy, oz = (float(x) for x in origin)
+        self._chk(self._L.pgx_cloud_merge(
+            self._h, _ptr(X) if n else None, _ptr(sr) if n else None, n, _ptr(d), _ptr(vw), R, vw.shape[1] - 1, W, H, len(P), _ptr(P),
+            _ptr(col), float(cell), ox, oy, oz, int(normal_step), float(disc_tol), int(min_support), cap, _ptr(oxyz), _ptr(onrm),
+            _ptr(orgb), _ptr(oinf), _ptr(pn), _ptr(co), _ptr(report)))
+        k = min(int(report[6]), cap)
+        return dict(xyz=oxyz[:k], normal=onrm[:k], rgba8=orgb[:k], info=oinf[:k], pt_normal=None if pn is None else pn[:n],
+                    cell_of=None if co is None else co[:n], report=report)
+
     # -- multi-GPU: the context's own RCCL communicator (pgx_comm_*) ------------------------------
     def comm_init(self, rank, world, unique_id):
         """Collective: every rank calls this with the 128 bytes rank 0 got from comm_unique_id()."""

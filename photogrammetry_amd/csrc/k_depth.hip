@@ -25,6 +25,7 @@
 //                  order whatever the grid
 // Counters are integer atomics only.  DESIGN.md section 26.
 #include "pgx_stage_args.h"
+#include "pgx_densecam.h"   // dep_camera, m3_norm, dep_pixel, the filter's camera table and fuse_point: shared with k_cloud.hip
 
 namespace {
 
@@ -35,23 +36,6 @@ constexpr int DEP_DMAX = 256, DEP_SMAX = 8;   // the limits of D and S (pgx.h)
 constexpr int DEP_PEN = 31;            // cost of a source that does not see the pixel: half of the 62 bits
 constexpr int CEN_TW = 32, CEN_TH = 8; // the census tile
 constexpr int FUSE_GRID_MAX = 1024;    // workgroups of k_fuse_count / k_fuse_write, grid-stride beyond
-constexpr int FUSE_CAM = 16;           // doubles per map in the filter's camera table: adj (9), det, sign, ||m3||, known, 3 unused
-
-// adj(M) (adj[3 i + j]; M^-1 = adj / det) and det M of a 3 x 4 camera; false if an entry is not finite or det == 0
-__device__ __forceinline__ bool dep_camera(const double *p, double (&adj)[9], double &det)
-{
-    bool fin = true;
-#pragma unroll
-    for (int k = 0; k < 12; k++) fin = fin && isfinite(p[k]);
-    const double m00 = p[0], m01 = p[1], m02 = p[2], m10 = p[4], m11 = p[5], m12 = p[6], m20 = p[8], m21 = p[9], m22 = p[10];
-    adj[0] = m11 * m22 - m12 * m21; adj[3] = m12 * m20 - m10 * m22; adj[6] = m10 * m21 - m11 * m20;
-    adj[1] = m02 * m21 - m01 * m22; adj[4] = m00 * m22 - m02 * m20; adj[7] = m01 * m20 - m00 * m21;
-    adj[2] = m01 * m12 - m02 * m11; adj[5] = m02 * m10 - m00 * m12; adj[8] = m00 * m11 - m01 * m10;
-    det = (m00 * adj[0] + m01 * adj[3]) + m02 * adj[6];
-    return fin && det != 0.0;
-}
-
-__device__ __forceinline__ double m3_norm(const double *p) { return sqrt((p[8] * p[8] + p[9] * p[9]) + p[10] * p[10]); }
 
 // the lowest slot that holds frame f, -1 if none does or f is no frame number
 __device__ __forceinline__ int dep_slot(const DepArgs &a, int f)
@@ -61,16 +45,6 @@ __device__ __forceinline__ int dep_slot(const DepArgs &a, int f)
     for (int s = 0; s < a.F; s++)
         if (a.frame_ids[s] == f) return s;
     return -1;
-}
-
-// the rule's pixel test: q_2 > 0 and the nearest pixel inside W x H (NaN fails); iu, iv = that pixel
-__device__ __forceinline__ bool dep_pixel(double q0, double q1, double q2, int W, int H, int &iu, int &iv)
-{
-    const double us = q0 / q2 + 0.5, vs = q1 / q2 + 0.5;
-    const bool ok = q2 > 0.0 && us >= 0.0 && us < (double)W && vs >= 0.0 && vs < (double)H;
-    iu = ok ? (int)us : 0;
-    iv = ok ? (int)vs : 0;
-    return ok;
 }
 
 __device__ __forceinline__ int clampi(int x, int hi) { return x < 0 ? 0 : (x > hi ? hi : x); }
@@ -316,35 +290,11 @@ template <int A> __global__ __launch_bounds__(DEP_NT) void k_dep_sweep(DepArgs a
 
 // ---- the cross-view filter --------------------------------------------------------------------------------------------
 
-// X of pixel (u, v) of a map at depth z; c = the map's row of the camera table, p = its camera
-__device__ __forceinline__ void fuse_point(const double *c, const double *p, int u, int v, double z, double &X0, double &X1, double &X2)
-{
-    const double w = (c[10] * c[11]) * z;
-    const double t0 = w * (double)u - p[3], t1 = w * (double)v - p[7], t2 = w - p[11];
-    X0 = ((c[0] * t0 + c[1] * t1) + c[2] * t2) / c[9];
-    X1 = ((c[3] * t0 + c[4] * t1) + c[5] * t2) / c[9];
-    X2 = ((c[6] * t0 + c[7] * t1) + c[8] * t2) / c[9];
-}
-
 __global__ __launch_bounds__(DEP_NT) void k_fuse_plan(FuseArgs a)
 {
     const int r = blockIdx.x, t = threadIdx.x;
     if (t == 0) {
-        const int fr = a.views[(size_t)r * (1 + a.S)];
-        double adj[9], det = 0.0, sg = 0.0, n3 = 0.0;
-#pragma unroll
-        for (int k = 0; k < 9; k++) adj[k] = 0.0;
-        bool ok = fr >= 0 && fr < a.n_frames;
-        if (ok) {
-            const double *p = a.P + (size_t)fr * 12;
-            ok = dep_camera(p, adj, det);
-            sg = det > 0.0 ? 1.0 : -1.0;
-            n3 = m3_norm(p);
-        }
-        double *c = a.cam + (size_t)r * FUSE_CAM;
-#pragma unroll
-        for (int k = 0; k < 9; k++) c[k] = adj[k];
-        c[9] = det; c[10] = sg; c[11] = n3; c[12] = ok ? 1.0 : 0.0; c[13] = 0.0; c[14] = 0.0; c[15] = 0.0;
+        fuse_camera_row(a.P, a.n_frames, a.views[(size_t)r * (1 + a.S)], a.cam + (size_t)r * FUSE_CAM);
         if (r == 0) { a.summary[1] = 0; a.summary[2] = 0; }
     }
     if (t < a.S) {

@@ -106,6 +106,46 @@ __global__ __launch_bounds__(256) void k_dewarp_gray(const typename SrcPix<SRC8>
     if (HAS_MAP && oob) atomicOr(status, (int)PGX_ST_OOB_SOURCE);
 }
 
+// ---- pgx_dewarp's pixel at 8 bits a channel (pgx_rgba8_batch_dev) --------------------------------------------------------
+// One thread per output pixel and group of FB frames: the map entry is read once, then per frame one gather (8 bytes, 4 for an
+// 8-bit source) and one 4-byte store.  Channel c of the dewarped pixel goes to bits 8 c .. 8 c + 7: the high byte of a 16-bit
+// channel; an 8-bit source's bytes as they are (widen8 would make c | c << 8 of each, whose high byte is c).  A map entry
+// outside the image gives the zero pixel and PGX_ST_OOB_SOURCE, as in k_dewarp_gray.
+template <bool HAS_MAP, bool SRC8>
+__global__ __launch_bounds__(256) void k_dewarp_rgba8(const typename SrcPix<SRC8>::type *__restrict__ rgba, const int2 *__restrict__ map,
+                                                      int W, int H, int F, uint32_t *__restrict__ out, int *status)
+{
+    const size_t npix = (size_t)W * H;
+    const int f0 = blockIdx.y * FB;
+    const int nf = F - f0 < FB ? F - f0 : FB; // block-uniform
+    bool oob = false;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += (size_t)gridDim.x * blockDim.x) {
+        size_t o = i;
+        bool ok = true;
+        if (HAS_MAP) {
+            const int2 m = map[i];
+            const unsigned su = (unsigned)m.x & 0xFFFFu, sv = (unsigned)m.y & 0xFFFFu;
+            ok = su < (unsigned)W && sv < (unsigned)H;
+            oob |= !ok;
+            o = ok ? (size_t)sv * W + su : 0;
+        }
+        for (int fb = 0; fb < nf; fb++) {
+            const size_t base = (size_t)(f0 + fb) * npix;
+            uint32_t w = 0;
+            if (ok) {
+                if constexpr (SRC8) {
+                    w = rgba[base + o];
+                } else {
+                    const uint2 p = rgba[base + o];   // p.x = R | G << 16, p.y = B | A << 16
+                    w = __builtin_amdgcn_perm(p.y, p.x, 0x07050301u);   // the high bytes of the four channels, in order
+                }
+            }
+            out[base + i] = w;
+        }
+    }
+    if (HAS_MAP && oob) atomicOr(status, (int)PGX_ST_OOB_SOURCE);
+}
+
 // ---- the gather plan of a map, made once when the map is installed ------------------------------------------------------
 // One word per output pixel: sv * W + su after the unchecked (ushort) casts of the C#, PGX_GATHER_OOB where that source lies
 // outside W x H; *flag becomes 1 when any entry does.  The wrap, the bounds test and the multiply then cost nothing per frame.
@@ -219,6 +259,26 @@ void pgx_launch_dewarp_gray(hipStream_t s, const void *rgba, int src8, const int
         else { if (dw) PGX_DG(false, true, false); else PGX_DG(false, false, false); }
     }
 #undef PGX_DG
+}
+
+void pgx_launch_dewarp_rgba8(hipStream_t s, const void *rgba, int src8, const int32_t *map_uv, int F, int W, int H, uint32_t *rgba8,
+                             int *status)
+{
+    if (F <= 0 || W <= 0 || H <= 0) return;
+    const size_t npix = (size_t)W * H;
+    const unsigned ny = (unsigned)((F + FB - 1) / FB);
+    unsigned gx = (unsigned)((npix + 255) / 256);
+    const unsigned cap = 2048u / ny > 32u ? 2048u / ny : 32u;   // a bounded grid, grid-stride beyond, as pgx_launch_dewarp_gray's
+    if (gx > cap) gx = cap;
+    const dim3 grid(gx, ny), block(256);
+    const int2 *map = reinterpret_cast<const int2 *>(map_uv);
+    if (src8) {
+        if (map) hipLaunchKernelGGL((k_dewarp_rgba8<true, true>), grid, block, 0, s, static_cast<const uint32_t *>(rgba), map, W, H, F, rgba8, status);
+        else hipLaunchKernelGGL((k_dewarp_rgba8<false, true>), grid, block, 0, s, static_cast<const uint32_t *>(rgba), map, W, H, F, rgba8, status);
+    } else {
+        if (map) hipLaunchKernelGGL((k_dewarp_rgba8<true, false>), grid, block, 0, s, static_cast<const uint2 *>(rgba), map, W, H, F, rgba8, status);
+        else hipLaunchKernelGGL((k_dewarp_rgba8<false, false>), grid, block, 0, s, static_cast<const uint2 *>(rgba), map, W, H, F, rgba8, status);
+    }
 }
 
 void pgx_launch_dewarp_plan(hipStream_t s, const int32_t *map_uv, int W, int H, uint32_t *plan, uint32_t *flag)

@@ -106,6 +106,8 @@ int decode_status(pgx_ctx *c, int bits)
         return fail(c, PGX_E_CAPACITY, "pair selection: more than max_pairs pairs were selected (the first max_pairs were written)");
     if (bits & PGX_ST_DEP_CAP)
         return fail(c, PGX_E_CAPACITY, "depth fusion: more than max_points pixels were kept (the first max_points were written)");
+    if (bits & PGX_ST_CLD_CAP)
+        return fail(c, PGX_E_CAPACITY, "cloud merge: more than max_points cells were kept (the first max_points were written)");
     if (bits & PGX_ST_DVW_CAP)
         return fail(c, PGX_E_CAPACITY, "dense views: n_tracks exceeds max_tracks (only the first max_tracks were processed)");
     if (bits & PGX_ST_DVW_NODE)
@@ -470,7 +472,7 @@ void pgx_ctx_destroy(pgx_ctx *c)
     for (hipEvent_t ev : c->ev_pool) (void)hipEventDestroy(ev);
     DevBuf *bufs[] = {&c->d_pairs, &c->d_plan, &c->d_steer_pairs, &c->d_steer_plans, &c->d_steer_dirs, &c->d_map, &c->d_gather, &c->ws_gray, &c->ws_seg, &c->ws_segoff, &c->ws_nraw, &c->ws_rawxy,
                       &c->ws_rawscore, &c->ws_nms, &c->ws_order, &c->ws_nkept, &c->st_a, &c->st_b, &c->st_c,
-                      &c->st_d, &c->st_e, &c->st_f, &c->ws_pose, &c->ws_tracks, &c->ws_tracks_split, &c->ws_agree, &c->ws_matchn[0], &c->ws_matchn[1], &c->ws_matchn[2], &c->ws_knn, &c->ws_guided, &c->ws_tri, &c->ws_ba, &c->ws_reg, &c->ws_ver, &c->ws_init, &c->ws_cns, &c->ws_vocab, &c->ws_depth, &c->ws_dviews,
+                      &c->st_d, &c->st_e, &c->st_f, &c->ws_pose, &c->ws_tracks, &c->ws_tracks_split, &c->ws_agree, &c->ws_matchn[0], &c->ws_matchn[1], &c->ws_matchn[2], &c->ws_knn, &c->ws_guided, &c->ws_tri, &c->ws_ba, &c->ws_reg, &c->ws_ver, &c->ws_init, &c->ws_cns, &c->ws_vocab, &c->ws_depth, &c->ws_dviews, &c->ws_cloud,
                       &c->ws_pyr_a, &c->ws_pyr_b, &c->ws_pyr_kp, &c->ws_pyr_desc, &c->ws_pyr_bins, &c->ws_pyr_cnt};
     for (DevBuf *b : bufs) b->release();
     c->pin_in.release();
@@ -1528,6 +1530,16 @@ int run_dense_views(pgx_ctx *c, DvwArgs &a)
     return PGX_OK;
 }
 
+// the launcher brackets its own parts
+int run_cloud_merge(pgx_ctx *c, CloudArgs &a)
+{
+    a.status = c->d_status;
+    HIPCHK(c, c->ws_cloud.ensure(pgx_cloud_ws_bytes(a)));
+    pgx_launch_cloud_merge(c, c->stream, a, c->ws_cloud.p);
+    HIPCHK(c, hipGetLastError());
+    return PGX_OK;
+}
+
 // ---- the track graph as a stage sees it (inv: the launcher's)
 
 // a device form's: an offset may reach every slot
@@ -2258,6 +2270,153 @@ int pgx_dense_views(pgx_ctx *c, const int32_t *track_offsets, const int32_t *nod
     a.ref_stats = out.dev<int32_t>(o_st); a.report = out.dev<int32_t>(o_rep);   // ref_stats is carved, and downloaded when given
     if ((rc = run_dense_views(c, a)) != PGX_OK) return rc;
     return download_images(c, out);
+}
+
+// ---- the fused points merged into one cloud with normals and colour --------------------------------------------------
+
+namespace {
+// what both forms of pgx_rgba8_batch check
+int rgba8_args(pgx_ctx *c, int F, int W, int H)
+{
+    if (F <= 0) return fail(c, PGX_E_BADARG, "F must be positive");
+    if (dims_ok(c, W, H) != PGX_OK) return PGX_E_BADARG;
+    if (c->map_set && (W != c->mapW || H != c->mapH))
+        return fail(c, PGX_E_DIM_MISMATCH, "image %dx%d vs dewarp map %dx%d (ArgumentException)", W, H, c->mapW, c->mapH);
+    return PGX_OK;
+}
+
+int run_rgba8_batch(pgx_ctx *c, const void *d_rgba, int F, int W, int H, uint32_t *d_rgba8)
+{
+    {
+        ProfScope ps(c, "dewarp_rgba8");
+        pgx_launch_dewarp_rgba8(c->stream, d_rgba, c->src8, c->map_set ? c->d_map.as<int32_t>() : nullptr, F, W, H, d_rgba8, c->d_status);
+    }
+    HIPCHK(c, hipGetLastError());
+    return PGX_OK;
+}
+
+// what the device and the host form of the merge check alike
+int cloud_args(pgx_ctx *c, int max_in, int R, int S, int W, int H, int n_frames, bool has_rgba8, int F, bool has_ids, double cell,
+               double ox, double oy, double oz, int normal_step, double disc_tol, int min_support, int max_points)
+{
+    if (dims_ok(c, W, H) != PGX_OK) return PGX_E_BADARG;
+    if (R < 1 || R > 65535 || n_frames <= 0) return fail(c, PGX_E_BADARG, "R must be in [1, 65535] and n_frames positive");
+    if (S < 1 || S > 8) return fail(c, PGX_E_BADARG, "S = %d, must be in [1, 8]", S);
+    if ((long long)R * W * H > (1ll << 30)) return fail(c, PGX_E_BADARG, "R * W * H must be <= 2^30");
+    if (max_in < 0 || max_in > (1 << 28) || max_points < 0 || max_points > (1 << 28))
+        return fail(c, PGX_E_BADARG, "max_in and max_points must be in [0, 2^28]");
+    if (has_rgba8) {
+        if (F < 1 || F > 65535) return fail(c, PGX_E_BADARG, "F must be in [1, 65535]");
+        if (!has_ids && n_frames != F) return fail(c, PGX_E_BADARG, "without d_frame_ids, n_frames must equal F");
+        if ((long long)F * W * H > (1ll << 30)) return fail(c, PGX_E_BADARG, "F * W * H must be <= 2^30");
+    }
+    if (!std::isfinite(cell) || !(cell > 0.0)) return fail(c, PGX_E_BADARG, "cell must be finite and > 0");
+    if (!std::isfinite(ox) || !std::isfinite(oy) || !std::isfinite(oz)) return fail(c, PGX_E_BADARG, "the origin must be finite");
+    if (normal_step < 1 || normal_step > 8) return fail(c, PGX_E_BADARG, "normal_step = %d, must be in [1, 8]", normal_step);
+    if (!std::isfinite(disc_tol) || !(disc_tol >= 0.0)) return fail(c, PGX_E_BADARG, "disc_tol must be finite and >= 0");
+    if (min_support < 1) return fail(c, PGX_E_BADARG, "min_support must be >= 1");
+    return PGX_OK;
+}
+} // namespace
+
+int pgx_rgba8_batch_dev(pgx_ctx *c, const uint16_t *d_rgba, int F, int W, int H, uint32_t *d_rgba8)
+{
+    if (!c || !d_rgba || !d_rgba8) return c ? fail(c, PGX_E_BADARG, "null pointer") : PGX_E_BADARG;
+    Lock l(c);
+    if (const int rc = rgba8_args(c, F, W, H); rc != PGX_OK) return rc;
+    return run_rgba8_batch(c, d_rgba, F, W, H, d_rgba8);
+}
+
+int pgx_rgba8_batch(pgx_ctx *c, const void *rgba, int F, int W, int H, uint32_t *rgba8)
+{
+    if (!c || !rgba || !rgba8) return c ? fail(c, PGX_E_BADARG, "null pointer") : PGX_E_BADARG;
+    Lock l(c);
+    if (const int rc = rgba8_args(c, F, W, H); rc != PGX_OK) return rc;
+    const size_t n = (size_t)F * W * H;
+    HostImage in, out;
+    const int i_s = in.add(rgba, n, c->src8 ? 4 : 8), o_d = out.add(rgba8, n, 4);
+    int rs = stage_images(c, in, out);
+    if (rs != PGX_OK) return rs;
+    if ((rs = run_rgba8_batch(c, in.dev<void>(i_s), F, W, H, out.dev<uint32_t>(o_d))) != PGX_OK) return rs;
+    return download_images(c, out);
+}
+
+int pgx_cloud_merge_dev(pgx_ctx *c, const double *d_xyz, const int32_t *d_src, const int32_t *d_count, int max_in,
+                        const double *d_depth, const int32_t *d_views, int R, int S, int W, int H, int n_frames, const double *d_P,
+                        const uint32_t *d_rgba8, int F, const int32_t *d_frame_ids, double cell, double ox, double oy, double oz,
+                        int normal_step, double disc_tol, int min_support, int max_points, double *d_out_xyz, float *d_out_normal,
+                        uint32_t *d_out_rgba8, int32_t *d_out_info, int32_t *d_pt_normal, int32_t *d_cell_of, int32_t *d_report)
+{
+    if (!c || !d_depth || !d_views || !d_P || !d_report || (max_in > 0 && (!d_xyz || !d_src)) ||
+        (max_points > 0 && (!d_out_xyz || !d_out_normal || !d_out_rgba8 || !d_out_info)))
+        return c ? fail(c, PGX_E_BADARG, "null pointer") : PGX_E_BADARG;
+    Lock l(c);
+    const int rc = cloud_args(c, max_in, R, S, W, H, n_frames, d_rgba8 != nullptr, F, d_frame_ids != nullptr, cell, ox, oy, oz,
+                              normal_step, disc_tol, min_support, max_points);
+    if (rc != PGX_OK) return rc;
+    const size_t ni = max_in, no = max_points, npix = (size_t)W * H;
+    const struct { const void *p; size_t n; } in[] = {{d_xyz, ni * 24}, {d_src, ni * 8}, {d_count, 4}, {d_depth, (size_t)R * npix * 8},
+                                                      {d_views, (size_t)R * (1 + S) * 4}, {d_P, (size_t)n_frames * 96},
+                                                      {d_rgba8, d_rgba8 ? (size_t)F * npix * 4 : 0},
+                                                      {d_frame_ids, d_rgba8 ? (size_t)F * 4 : 0}},
+                                        out[] = {{d_out_xyz, no * 24}, {d_out_normal, no * 12}, {d_out_rgba8, no * 4}, {d_out_info, no * 16},
+                                                 {d_pt_normal, ni * 12}, {d_cell_of, ni * 4}, {d_report, 32}};
+    for (const auto &o : out)
+        for (const auto &i : in)
+            if (overlap(o.p, o.n, i.p, i.n)) return fail(c, PGX_E_BADARG, "an output must not alias an input");
+    CloudArgs a{};
+    a.xyz = d_xyz; a.src = d_src; a.count = d_count; a.max_in = max_in; a.depth = d_depth; a.views = d_views;
+    a.R = R; a.S = S; a.W = W; a.H = H; a.n_frames = n_frames; a.P = d_P;
+    a.rgba8 = d_rgba8; a.F = d_rgba8 ? F : 0; a.frame_ids = d_rgba8 ? d_frame_ids : nullptr;
+    a.cell = cell; a.ox = ox; a.oy = oy; a.oz = oz; a.disc_tol = disc_tol;
+    a.normal_step = normal_step; a.min_support = min_support; a.max_points = max_points;
+    a.out_xyz = d_out_xyz; a.out_normal = d_out_normal; a.out_rgba8 = d_out_rgba8; a.out_info = d_out_info;
+    a.pt_normal = d_pt_normal; a.cell_of = d_cell_of; a.report = d_report;
+    return run_cloud_merge(c, a);
+}
+
+int pgx_cloud_merge(pgx_ctx *c, const double *xyz, const int32_t *src, int n_in, const double *depth, const int32_t *views, int R, int S,
+                    int W, int H, int n_frames, const double *P, const uint32_t *rgba8, double cell, double ox, double oy, double oz,
+                    int normal_step, double disc_tol, int min_support, int max_points, double *out_xyz, float *out_normal,
+                    uint32_t *out_rgba8, int32_t *out_info, int32_t *pt_normal, int32_t *cell_of, int32_t *report)
+{
+    if (!c || !depth || !views || !P || !report || (n_in > 0 && (!xyz || !src)) ||
+        (max_points > 0 && (!out_xyz || !out_normal || !out_rgba8 || !out_info)))
+        return c ? fail(c, PGX_E_BADARG, "null pointer") : PGX_E_BADARG;
+    Lock l(c);
+    int rs = cloud_args(c, n_in, R, S, W, H, n_frames, rgba8 != nullptr, n_frames, false, cell, ox, oy, oz, normal_step, disc_tol,
+                        min_support, max_points);
+    if (rs != PGX_OK) return rs;
+    const size_t ni = n_in, no = max_points, npix = (size_t)W * H;
+    HostImage in, out;
+    const int i_x = in.add(xyz, ni, 24, 1), i_s = in.add(src, ni, 8, 1), i_d = in.add(depth, (size_t)R * npix, 8),
+              i_v = in.add(views, (size_t)R * (1 + S), 4), i_P = in.add(P, n_frames, 96),
+              i_c = in.add(rgba8, (size_t)n_frames * npix, 4, 0, rgba8 != nullptr);
+    // the report first: its download tells how many cells there are to fetch
+    const int o_r = out.add(report, 8, 4, 64), o_pn = out.add(pt_normal, ni * 3, 4, 0, pt_normal != nullptr),
+              o_co = out.add(cell_of, ni, 4, 0, cell_of != nullptr), o_x = out.add(nullptr, 0, 24, no + 1),
+              o_n = out.add(nullptr, 0, 12, no + 1), o_c = out.add(nullptr, 0, 4, no + 1), o_i = out.add(nullptr, 0, 16, no + 1);
+    if ((rs = stage_images(c, in, out)) != PGX_OK) return rs;
+    CloudArgs a{};
+    a.xyz = in.dev<double>(i_x); a.src = in.dev<int32_t>(i_s); a.count = nullptr; a.max_in = n_in;
+    a.depth = in.dev<double>(i_d); a.views = in.dev<int32_t>(i_v); a.R = R; a.S = S; a.W = W; a.H = H; a.n_frames = n_frames;
+    a.P = in.dev<double>(i_P); a.rgba8 = in.dev<uint32_t>(i_c); a.F = rgba8 ? n_frames : 0; a.frame_ids = nullptr;
+    a.cell = cell; a.ox = ox; a.oy = oy; a.oz = oz; a.disc_tol = disc_tol;
+    a.normal_step = normal_step; a.min_support = min_support; a.max_points = max_points;
+    a.out_xyz = out.dev<double>(o_x); a.out_normal = out.dev<float>(o_n); a.out_rgba8 = out.dev<uint32_t>(o_c);
+    a.out_info = out.dev<int32_t>(o_i); a.pt_normal = out.dev<int32_t>(o_pn); a.cell_of = out.dev<int32_t>(o_co);
+    a.report = out.dev<int32_t>(o_r);
+    if ((rs = run_cloud_merge(c, a)) != PGX_OK) return rs;
+    rs = download_images(c, out);   // the report and the per-point outputs; waits for the stream
+    if (rs != PGX_OK && rs != PGX_E_CAPACITY) return rs;   // the report was not downloaded: nothing tells how many rows there are
+    const size_t np = (size_t)(report[6] < max_points ? report[6] : max_points);
+    if (np > 0) {
+        HIPCHK(c, hipMemcpy(out_xyz, out.dev<double>(o_x), np * 24, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(out_normal, out.dev<float>(o_n), np * 12, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(out_rgba8, out.dev<uint32_t>(o_c), np * 4, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(out_info, out.dev<int32_t>(o_i), np * 16, hipMemcpyDeviceToHost));
+    }
+    return rs;
 }
 
 // ---- measurement hooks ---------------------------------------------------------------------

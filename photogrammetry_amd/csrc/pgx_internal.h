@@ -42,6 +42,7 @@
 #define PGX_ST_DEP_CAP    33554432u /* pgx_depth_fuse_dev: more than max_points pixels kept */
 #define PGX_ST_DVW_CAP    67108864u  /* pgx_dense_views_dev: n_tracks > max_tracks */
 #define PGX_ST_DVW_NODE   134217728u /* pgx_dense_views_dev: a node of a used track outside the frames, or malformed offsets */
+#define PGX_ST_CLD_CAP    268435456u /* pgx_cloud_merge_dev: more than max_points cells kept */
 
 // key = (distance << PGX_IDX_BITS) | index ; limits: index < 2^20, distance < 2^12
 #define PGX_IDX_BITS 20
@@ -163,6 +164,7 @@ struct pgx_ctx {
     DevBuf ws_ver;    // pgx_verify_pair*: candidate lists of a chunk of image pairs, hypotheses of one chunk of samples, keys
     DevBuf ws_vocab;  // pgx_vocab_train*, pgx_select_pairs*: words per descriptor, members by word, histograms, weights, scores
     DevBuf ws_depth;  // pgx_depth_maps*, pgx_depth_fuse*: census words per slot, warps, plane tables; camera table, keep flags, block sums
+    DevBuf ws_cloud;  // pgx_cloud_merge*: the cell table, per-point records, block sums, the accumulators of the kept cells
     DevBuf ws_dviews; // pgx_dense_views*: pair-count table, frame table, depths bucketed by frame, per-frame counts and cursors
     DevBuf ws_init;   // pgx_init_pair_dev, pgx_relative_pose: per image pair the two rotations, t, the intrinsics and the counters
     hipStream_t mstream[3] = {nullptr, nullptr, nullptr}; // [0] wide rounds, [1] residual distance rows, [2] per-pair finish
@@ -258,6 +260,9 @@ struct ProfScope {
 void pgx_launch_dewarp_gray(hipStream_t s, const void *rgba, int src8, const int32_t *map_uv, int F, int W, int H,
                             float *gray, uint16_t *dewarped, int *status);
 void pgx_launch_dewarp_map(hipStream_t s, int W, int H, const double *k /*[5]*/, int32_t *map_uv, int *status);
+// pgx_dewarp's pixel of F frames packed to 8 bits a channel (the high byte of a 16-bit channel): rgba8 [F][H][W]
+void pgx_launch_dewarp_rgba8(hipStream_t s, const void *rgba, int src8, const int32_t *map_uv, int F, int W, int H, uint32_t *rgba8,
+                             int *status);
 // the map's gather plan: plan[W * H] source offsets (PGX_GATHER_OOB outside the image), *flag = 1 when any entry is outside
 void pgx_launch_dewarp_plan(hipStream_t s, const int32_t *map_uv, int W, int H, uint32_t *plan, uint32_t *flag);
 

@@ -1,5 +1,5 @@
 // pgx_stage_args.h -- the arguments of the stages behind the matchers, each as the struct its kernels take by value:
-// triangulation, bundle adjustment, registration, consensus, verification, initial pair, depth maps, depth fuse, dense views.  The C ABI's
+// triangulation, bundle adjustment, registration, consensus, verification, initial pair, depth maps, depth fuse, dense views, cloud merge.  The C ABI's
 // two forms of a stage (pgx_api.hip) fill "the caller fills" by name and hand the struct to run_X; the launcher carves the
 // workspace into the rest and launches.  The layout IS the kernarg layout: fields, order and types are the kernels' (the
 // capitals in the shapes are constants of the stage's .hip file).  Internal to libpgx.so; DESIGN.md section 14h.
@@ -244,3 +244,46 @@ struct DvwArgs {
 };
 size_t pgx_dense_views_ws_bytes(const DvwArgs &a);
 void pgx_launch_dense_views(pgx_ctx *ctx, hipStream_t s, DvwArgs a, void *ws);
+
+// ---- k_cloud.hip (the fused point list merged into one cloud with normals and colour; pgx_cloud_merge_dev semantics) -------
+// ctx: the profiling groups cloud_plan / cloud_normals / cloud_points / cloud_rank / cloud_accum / cloud_final
+struct CloudArgs {
+    // the caller fills
+    const double *xyz;            // [max_in][3]
+    const int32_t *src;           // [max_in][2] = (r, v W + u)
+    const int32_t *count;         // [0] = the entries of the list, or nullptr: max_in
+    int max_in;
+    const double *depth;          // [R][H][W]
+    const int32_t *views;         // [R][1 + S]: column 0 alone is read
+    int R, S, W, H, n_frames;
+    const double *P;              // [n_frames][12]
+    const uint32_t *rgba8;        // [F][H][W] or nullptr
+    int F;
+    const int32_t *frame_ids;     // [F] or nullptr
+    double cell, ox, oy, oz, disc_tol;
+    int normal_step, min_support, max_points;
+    double *out_xyz;              // [max_points][3]
+    float *out_normal;            // [max_points][3]
+    uint32_t *out_rgba8;          // [max_points]
+    int32_t *out_info;            // [max_points][4] = (cnt, nn, nc, first)
+    int32_t *pt_normal;           // [max_in][3] or nullptr
+    int32_t *cell_of;             // [max_in] or nullptr
+    int32_t *report;              // [8]
+    // the launcher fills (workspace, derived)
+    int lg_table;                 // the table has 1 << lg_table entries
+    unsigned long long *keys;     // [table]: the cell's key, CLD_EMPTY = none
+    int32_t *tfirst, *tcnt, *tout; // [table]: the smallest point of the cell, its points, its output index (-2: dropped)
+    double *cam;                  // [R][FUSE_CAM]: the filter's camera table
+    int32_t *cslot;               // [R]: the slot that shows the map's frame, -1 = none
+    int32_t *slot;                // [max_in]: the point's table entry, -1 = not used
+    unsigned long long *rec;      // [max_in][2]: p (3 x 16 bits), flags, a colour byte | q (3 x 16 bits), two colour bytes
+    int32_t *bsum, *boff;         // [nb]: owners per block of 256 points, their exclusive scan
+    int32_t *oslot;               // [max_points]: the table entry of an output cell
+    unsigned long long *acc;      // [max_points][CLD_ACC]: the sums of p, q and colour, nn | nc << 32
+    int32_t *meta;                // [0] n, [1] used, [2] normals, [3] colours, [4] cells, [5] cells kept
+    int nb;                       // blocks of 256 points
+    // the caller fills
+    int *status;                  // more than max_points cells kept: PGX_ST_CLD_CAP
+};
+size_t pgx_cloud_ws_bytes(const CloudArgs &a);
+void pgx_launch_cloud_merge(pgx_ctx *ctx, hipStream_t s, CloudArgs a, void *ws);

@@ -1,6 +1,6 @@
-"""One command for the chain that DESIGN.md section 27 closes: pgx_triangulate_tracks_dev -> pgx_dense_views_dev ->
-pgx_gray_batch_dev -> pgx_depth_maps_dev -> pgx_depth_fuse_dev on one stream, with no synchronisation between the
-triangulation and the filter.  The scene is synth.make_scene's (frames on an arc, true tracks cut to runs); the frames are
+"""One command for the chain that DESIGN.md sections 27 and 28 close: pgx_triangulate_tracks_dev -> pgx_dense_views_dev ->
+pgx_gray_batch_dev -> pgx_depth_maps_dev -> pgx_depth_fuse_dev -> pgx_rgba8_batch_dev -> pgx_cloud_merge_dev on one stream, with
+no synchronisation between the triangulation and the merged cloud.  The scene is synth.make_scene's (frames on an arc, true tracks cut to runs); the frames are
 seeded noise, so the maps carry no meaning: the tool shows that the chain runs and what it costs.  Timed with HIP events on
 geom_bench's loop; prints one JSON line and writes profiles/dense_chain_<shape>.json (or --out DIR)."""
 import argparse
@@ -17,7 +17,8 @@ import photogrammetry_amd as pg  # noqa: E402
 from geom_bench import DEV, F64, I32  # noqa: E402
 
 PARTS = ("triangulate", "dense_views_nodes", "dense_views_pairs", "dense_views_select", "dewarp_gray", "depth_census", "depth_plan",
-         "depth_sweep", "depth_fuse")
+         "depth_sweep", "depth_fuse", "dewarp_rgba8", "cloud_plan", "cloud_normals", "cloud_points", "cloud_rank", "cloud_accum",
+         "cloud_final")
 
 
 def main():
@@ -30,6 +31,7 @@ def main():
     ap.add_argument("--points", type=int, default=4000)
     ap.add_argument("--sources", type=int, default=4)
     ap.add_argument("--planes", type=int, default=64)
+    ap.add_argument("--cell", type=float, default=0.02)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles"))
     args = ap.parse_args()
     W, H, nf, S, D = args.width, args.height, args.frames, args.sources, args.planes
@@ -45,6 +47,10 @@ def main():
     kq8, fl, dep, msum = torch.empty((nf, H, W), **I32), torch.empty((nf, H, W), **I32), torch.empty((nf, H, W), **F64), torch.empty(8, **I32)
     cap = nf * H * W
     pts, src, fsum = torch.empty((cap, 3), **F64), torch.empty((cap, 2), **I32), torch.empty(4, **I32)
+    col = torch.empty((nf, H, W), **I32)
+    oxyz, onrm = torch.empty((cap, 3), **F64), torch.empty((cap, 3), dtype=torch.float32, device=DEV)
+    orgb, oinf, crep = torch.empty(cap, **I32), torch.empty((cap, 4), **I32), torch.empty(8, **I32)
+    origin = (-(2**19) * args.cell,) * 3      # the scene in the middle of the grid
     torch.cuda.synchronize()
 
     def chain():
@@ -53,6 +59,9 @@ def main():
         eng.gray_batch_dev(rgba, nf, W, H, gray)
         eng.depth_maps_dev(gray, nf, W, H, nf, d["P"], views, nf, S, rng_d, D, kq8, dep, fl, msum, agg_radius=2, min_views=2)
         eng.depth_fuse_dev(dep, views, nf, S, W, H, nf, d["P"], cap, pts, src, fsum)
+        eng.rgba8_batch_dev(rgba, nf, W, H, col)
+        eng.cloud_merge_dev(pts, src, fsum, cap, dep, views, nf, S, W, H, nf, d["P"], args.cell, origin, cap, oxyz, onrm, orgb, oinf, crep,
+                            d_rgba8=col, F=nf)
     ms = gb.time_on_stream(eng, chain, args.steps, args.warmup)
     eng.profile_reset()
     eng.profile_enable(True)
@@ -64,7 +73,7 @@ def main():
     rec = dict(shape="%dx%d_f%d_s%d_d%d" % (W, H, nf, S, D), frames=nf, tracks=nt, nodes=d["n_nodes"], steps=args.steps,
                chain_ms_median=float(np.median(ms)), chain_ms_min=float(ms.min()), chain_ms_max=float(ms.max()),
                parts_ms={k: round(v, 4) for k, v in parts.items()}, views_report=rep.cpu().tolist(), maps_summary=msum.cpu().tolist(),
-               fuse_summary=fsum.cpu().tolist(), refs_flagged=int((st.cpu().numpy()[:, 3] != 0).sum()))
+               fuse_summary=fsum.cpu().tolist(), cloud_report=crep.cpu().tolist(), refs_flagged=int((st.cpu().numpy()[:, 3] != 0).sum()))
     gb.write_record(rec, args.out, "dense_chain")
     eng.close()
 
