@@ -1218,6 +1218,86 @@ int pgx_cloud_merge(pgx_ctx *ctx, const double *xyz, const int32_t *src, int n_i
                     float *out_normal, uint32_t *out_rgba8, int32_t *out_info, int32_t *pt_normal, int32_t *cell_of,
                     int32_t *report);
 
+/* ---- a triangle mesh from the depth maps: TSDF grid and surface nets -------------------------------- */
+/* The cloud above is points with normals; these calls make the surface, on the same stream with no host round trip: a truncated
+ * signed distance (TSDF) on the lattice nodes round the filter's points, in which the maps that see a node are averaged, and
+ * naive surface nets: one vertex in every cube of eight nodes with a sign change, one quad on every lattice edge with a sign
+ * change.  No case table.  Integers wherever a rule can be an integer (every sum over maps and nodes is one, so no order of
+ * execution changes a bit), float64 elsewhere, one IEEE operation at a time in the order written, a dot product as
+ * (a b + c d) + e f, nothing contracted: bit-identical to a numpy restatement (tests/mesh_ref.py).  Not in the C# reference.
+ * k_mesh.hip.
+ *
+ * pgx_mesh_dev.
+ * Inputs.  The list d_xyz, d_src, d_count, max_in, the maps d_depth, d_views (column 0 alone), n_frames, d_P and the colour
+ * d_rgba8, F, d_frame_ids exactly as for pgx_cloud_merge_dev.  d_agree [R][H][W] int32 (pgx_depth_fuse_dev's optional output) or
+ * NULL, with min_agree.  The grid cell, o = (ox, oy, oz).  band B in [1, 3], trunc_cells T in [1, 8]:
+ * trunc = (double) T * cell.  min_weight >= 1.
+ *   1 seeds     point i < n is USED by rule 1 of pgx_cloud_merge_dev (the same test, the same g and key) and, further,
+ *               -2^20 + 4 <= g_a < 2^20 - 4 on every axis.
+ *   2 voxels    a lattice node c (an integer triple) stands at X_a = o_a + (double) c_a * cell.  It is a VOXEL iff some used point
+ *               has g_a - B + 1 <= c_a <= g_a + B on every axis (B = 1: the eight corners of the point's own cell).  With
+ *               d = c - g + (B - 1): nb = (d_2 2B + d_1) 2B + d_0, and ord(c) = the minimum of 256 i + nb over all such
+ *               (point, node) incidences, a 64-bit integer; it equals the minimum over the occupied cells of
+ *               256 first(cell) + nb.
+ *   3 TSDF      per voxel over the maps r = 0 .. R - 1; a map is skipped by the filter's rule (its frame outside [0, n_frames) or
+ *               its camera unknown).  q = P_r (X, 1) row by row as ((p_0 X_0 + p_1 X_1) + p_2 X_2) + p_3; the projection is
+ *               VALID iff q_2 > 0 and the nearest pixel (u, v) = ((int)(q_0 / q_2 + 0.5), (int)(q_1 / q_2 + 0.5)) is inside the
+ *               image, as in the filter; d = (sign(det M_r) q_2) / ||m3_r||.  The observation COUNTS iff the projection is valid,
+ *               z = depth[r][v][u] is finite, and d_agree is NULL or agree[r][v][u] >= min_agree.  s = z - d.  If s < -trunc (or s
+ *               is NaN) the map is passed over: the voxel is hidden behind the surface.  t = s > trunc ? trunc : s,
+ *               tq = (int) floor((t / trunc) * 32767.0 + 0.5); in integers w += 1, st += tq; if s <= trunc and a slot shows frame
+ *               views[r][0] (the lowest, as in the cloud): nc += 1 and the three channel sums sc take the pixel's low three bytes.
+ *               A voxel is VALID iff w >= min_weight, INSIDE iff it is valid and st < 0; phi = (double) st / (double) w.
+ *   4 vertices  cube c has the nodes c + {0, 1}^3; node j has the offsets (j & 1, j >> 1 & 1, j >> 2 & 1) on axes 0, 1, 2.  It is
+ *               COMPLETE iff all eight are valid voxels, ACTIVE iff complete and their INSIDE bits are not all equal.  Its twelve
+ *               edges in the order axis a = 0, 1, 2 and, within an axis, the offsets 00, 10, 01, 11 on the two other axes, the
+ *               lower axis first; lo is the end with offset 0 along a.  For each edge whose ends differ in INSIDE:
+ *               tau = phi_lo / (phi_lo - phi_hi), and the crossing is lo's offsets with coordinate a replaced by tau.
+ *               m_a = (0.0 plus the crossings' coordinate a, added in edge order) / (double) k, k the number of crossings.
+ *               Position o_a + ((double) c_a + m_a) * cell.  Normal: G_a = 0.0 plus (phi_hi - phi_lo) of the four edges along a in
+ *               edge order, L = sqrt((G_0 G_0 + G_1 G_1) + G_2 G_2), (float)(G_a / L), zeros when L is 0 or not finite; it points
+ *               into free space, towards the cameras.  Colour: nc and sc summed over the eight nodes, the channel
+ *               (2 sc + nc) / (2 nc) in integers, alpha 255; 0 when nc == 0.  Info (c_0, c_1, c_2, mask | k << 8), mask the eight
+ *               INSIDE bits.  The vertices in ascending ord(c) of the cube's low node.
+ *   5 triangles node c and axis a with c and c + e_a both valid and differing in INSIDE; b = (a + 1) % 3, c' = (a + 2) % 3; the
+ *               cubes round the edge Q0 = c - e_b - e_c', Q1 = c - e_c', Q2 = c, Q3 = c - e_b.  A quad is emitted iff all four are
+ *               complete (they are then active); with v0 .. v3 their vertex indices: (v0, v1, v2), (v0, v2, v3) when c is INSIDE,
+ *               (v0, v2, v1), (v0, v3, v2) otherwise: the geometric normal faces free space.  The quads in ascending
+ *               (ord(c), a), the two triangles of a quad adjacent.
+ * Outputs.  d_out_xyz [max_vertices][3] float64, d_out_normal [max_vertices][3] float32, d_out_rgba8 [max_vertices] uint32,
+ * d_out_info [max_vertices][4] int32, d_out_tri [max_tris][3] int32 (full vertex indices, also at or past max_vertices).
+ * d_report [8] int32: n, used points, seed cells, voxels, valid voxels, vertices (the full count), triangles (the full count), 0.
+ * More vertices or triangles than the capacity: the first ones are written and pgx_check_status reports PGX_E_CAPACITY.  More
+ * voxels than max_voxels: PGX_E_CAPACITY, report[5] and report[6] are 0, report[3] > max_voxels (the entries of the table in use:
+ * the voxel count unless the table is full), no vertex or triangle is written, and no probe runs for more than one round of the
+ * table.
+ * Returned at once (PGX_E_BADARG), with nothing written: the refusals of pgx_cloud_merge_dev for the arguments the calls share,
+ * band outside [1, 3], trunc_cells outside [1, 8], min_weight < 1, min_agree < 0, max_voxels, max_vertices or max_tris outside
+ * [0, 2^28], null required pointers (the four vertex outputs may be NULL with max_vertices == 0, d_out_tri with max_tris == 0), an
+ * output that overlaps an input.
+ * Workspace: 58 bytes per entry of a table of the power of two >= max(2 max_voxels, 256) entries, 4 bytes per entry of the list
+ * and 16 bytes per block of 256 of them; nothing per vertex or triangle.
+ * Results depend on the inputs only: the same bits from run to run, for any slot layout of the same frames, on a used
+ * workspace and from the host form; a permuted list gives the same vertices and triangles up to renumbering.
+ * Asynchronous on the context's stream. */
+int pgx_mesh_dev(pgx_ctx *ctx, const double *d_xyz /* [max_in][3] */, const int32_t *d_src /* [max_in][2] */,
+                 const int32_t *d_count /* [1] or NULL */, int max_in, const double *d_depth /* [R][H][W] */,
+                 const int32_t *d_views /* [R][1 + S] */, int R, int S, int W, int H, int n_frames, const double *d_P,
+                 const int32_t *d_agree /* [R][H][W] or NULL */, int min_agree, const uint32_t *d_rgba8 /* [F][H][W] or NULL */,
+                 int F, const int32_t *d_frame_ids /* [F] or NULL */, double cell, double ox, double oy, double oz, int band,
+                 int trunc_cells, int min_weight, int max_voxels, int max_vertices, int max_tris,
+                 double *d_out_xyz /* [max_vertices][3] */, float *d_out_normal /* [max_vertices][3] */,
+                 uint32_t *d_out_rgba8 /* [max_vertices] */, int32_t *d_out_info /* [max_vertices][4] */,
+                 int32_t *d_out_tri /* [max_tris][3] */, int32_t *d_report /* [8] */);
+/* Host form: host arrays in the layouts above, the same kernels; it returns when the results are in the caller's buffers.  The
+ * list has n_in entries (no d_count); agree may be NULL; rgba8 [n_frames][H][W] by frame number (no slots) or NULL; the report
+ * is downloaded first, then min(report[5], max_vertices) rows of the four vertex outputs and min(report[6], max_tris) triangles. */
+int pgx_mesh(pgx_ctx *ctx, const double *xyz, const int32_t *src, int n_in, const double *depth, const int32_t *views, int R, int S,
+             int W, int H, int n_frames, const double *P, const int32_t *agree, int min_agree, const uint32_t *rgba8, double cell,
+             double ox, double oy, double oz, int band, int trunc_cells, int min_weight, int max_voxels, int max_vertices,
+             int max_tris, double *out_xyz, float *out_normal, uint32_t *out_rgba8, int32_t *out_info, int32_t *out_tri,
+             int32_t *report);
+
 /* ---- measurement hooks (bench.py) ---------------------------------------------------- */
 /* When on, the named hot kernels are bracketed by HIP events on the launch stream. */
 int pgx_profile_enable(pgx_ctx *ctx, int on);

@@ -300,6 +300,24 @@ internal static unsafe class PgxNative
                                                               float* outNormal, uint* outRgba8, int* outInfo, int* ptNormal,
                                                               int* cellOf, int* report);
 
+    // a triangle mesh from the depth maps (a TSDF on a hashed grid, then surface nets; not in the managed implementation): the
+    // list, maps, cameras and colours as for pgx_cloud_merge_dev, dAgree [r][h][w] (pgx_depth_fuse_dev's) or null -> dOutXyz
+    // [maxVertices][3] float64, dOutNormal [maxVertices][3] float32, dOutRgba8 [maxVertices], dOutInfo [maxVertices][4],
+    // dOutTri [maxTris][3] int32, dReport [8] ([5] vertices, [6] triangles).  The host form takes host arrays in the same layouts
+    [DllImport(Lib)] public static extern int pgx_mesh_dev(IntPtr ctx, void* dXyz, void* dSrc, void* dCount, int maxIn, void* dDepth,
+                                                           void* dViews, int r, int s, int w, int h, int nFrames, void* dP,
+                                                           void* dAgree, int minAgree, void* dRgba8, int f, void* dFrameIds,
+                                                           double cell, double ox, double oy, double oz, int band, int truncCells,
+                                                           int minWeight, int maxVoxels, int maxVertices, int maxTris, void* dOutXyz,
+                                                           void* dOutNormal, void* dOutRgba8, void* dOutInfo, void* dOutTri,
+                                                           void* dReport);
+    [DllImport(Lib)] public static extern int pgx_mesh(IntPtr ctx, double* xyz, int* src, int nIn, double* depth, int* views, int r,
+                                                       int s, int w, int h, int nFrames, double* p, int* agree, int minAgree,
+                                                       uint* rgba8, double cell, double ox, double oy, double oz, int band,
+                                                       int truncCells, int minWeight, int maxVoxels, int maxVertices, int maxTris,
+                                                       double* outXyz, float* outNormal, uint* outRgba8, int* outInfo, int* outTri,
+                                                       int* report);
+
     /// <summary>Maps a status code back to the exception type the managed implementation throws.</summary>
     public static void Check(IntPtr ctx, int rc)
     {

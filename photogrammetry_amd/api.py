@@ -871,6 +871,55 @@ class Engine:
         return dict(xyz=oxyz[:k], normal=onrm[:k], rgba8=orgb[:k], info=oinf[:k], pt_normal=None if pn is None else pn[:n],
                     cell_of=None if co is None else co[:n], report=report)
 
+    # -- a triangle mesh from the depth maps: TSDF grid and surface nets (pgx_mesh*) -------------------------------
+    def mesh_dev(self, d_xyz, d_src, d_count, max_in, d_depth, d_views, R, S, W, H, n_frames, d_P, cell, origin, max_voxels,
+                 max_vertices, max_tris, d_out_xyz, d_out_normal, d_out_rgba8, d_out_info, d_out_tri, d_report, d_agree=None,
+                 min_agree=0, d_rgba8=None, F=0, d_frame_ids=None, band=1, trunc_cells=3, min_weight=1):
+        """pgx_mesh_dev: the list, maps, cameras and colours as for cloud_merge_dev (d_agree [R][H][W] int32, the filter's optional
+        output, or None) -> the surface-nets mesh of the TSDF on the nodes within `band` cells of the list's points: d_out_xyz
+        [max_vertices][3] float64, d_out_normal [max_vertices][3] float32, d_out_rgba8 [max_vertices] uint32, d_out_info
+        [max_vertices][4] int32 = (c_0, c_1, c_2, mask | k << 8), d_out_tri [max_tris][3] int32, d_report [8] int32 ([3] voxels,
+        [5] vertices, [6] triangles).  A capacity exceeded: CapacityError from check_status.  No sync."""
+        ox, oy, oz = (float(x) for x in origin)
+        self._chk(self._L.pgx_mesh_dev(
+            self._h, _dptr(d_xyz), _dptr(d_src), _dptr(d_count), int(max_in), _dptr(d_depth), _dptr(d_views), int(R), int(S), int(W),
+            int(H), int(n_frames), _dptr(d_P), _dptr(d_agree), int(min_agree), _dptr(d_rgba8), int(F), _dptr(d_frame_ids), float(cell),
+            ox, oy, oz, int(band), int(trunc_cells), int(min_weight), int(max_voxels), int(max_vertices), int(max_tris),
+            _dptr(d_out_xyz), _dptr(d_out_normal), _dptr(d_out_rgba8), _dptr(d_out_info), _dptr(d_out_tri), _dptr(d_report)))
+
+    def mesh(self, xyz, src, depth, views, cameras, cell, origin, agree=None, min_agree=0, rgba8=None, band=1, trunc_cells=3,
+             min_weight=1, max_voxels=None, max_vertices=None, max_tris=None):
+        """The host form (pgx_mesh).  xyz [n][3] float64 and src [n][2] int32 as depth_fuse returns them, depth [R][H][W], views
+        [R][1 + S], cameras [n_frames][3][4], agree [R][H][W] int32 or None, rgba8 [n_frames][H][W] uint32 or None ->
+        dict(xyz [m][3], normal [m][3] float32, rgba8 [m], info [m][4], tri [t][3] int32, report [8]), trimmed to the counts of
+        the report.  max_voxels defaults to (2 band)^3 n, max_vertices to max_voxels, max_tris to 6 max_voxels (none of them can
+        then be exceeded); a smaller one that cuts the mesh raises CapacityError."""
+        X = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+        sr = np.ascontiguousarray(src, dtype=np.int32).reshape(-1, 2)
+        n = len(X)
+        d = np.ascontiguousarray(depth, dtype=np.float64)
+        R, H, W = d.shape
+        vw = np.ascontiguousarray(views, dtype=np.int32)
+        vw = vw.reshape(R, vw.shape[-1])
+        P = np.ascontiguousarray(cameras, dtype=np.float64).reshape(-1, 12)
+        ag = None if agree is None else np.ascontiguousarray(agree, dtype=np.int32).reshape(R, H, W)
+        col = None if rgba8 is None else np.ascontiguousarray(rgba8, dtype=np.uint32).reshape(len(P), H, W)
+        lim = 1 << 28
+        nvox = min((2 * int(band)) ** 3 * n, lim) if max_voxels is None else int(max_voxels)
+        nv = nvox if max_vertices is None else int(max_vertices)
+        nt = min(6 * nvox, lim) if max_tris is None else int(max_tris)
+        mv, mt = max(nv, 1), max(nt, 1)
+        oxyz, onrm = np.zeros((mv, 3)), np.zeros((mv, 3), dtype=np.float32)
+        orgb, oinf, otri = np.zeros(mv, dtype=np.uint32), np.zeros((mv, 4), dtype=np.int32), np.zeros((mt, 3), dtype=np.int32)
+        report = np.zeros(8, dtype=np.int32)
+        ox, oy, oz = (float(x) for x in origin)
+        self._chk(self._L.pgx_mesh(
+            self._h, _ptr(X) if n else None, _ptr(sr) if n else None, n, _ptr(d), _ptr(vw), R, vw.shape[1] - 1, W, H, len(P), _ptr(P),
+            _ptr(ag), int(min_agree), _ptr(col), float(cell), ox, oy, oz, int(band), int(trunc_cells), int(min_weight), nvox, nv, nt,
+            _ptr(oxyz), _ptr(onrm), _ptr(orgb), _ptr(oinf), _ptr(otri), _ptr(report)))
+        kv, kt = min(int(report[5]), nv), min(int(report[6]), nt)
+        return dict(xyz=oxyz[:kv], normal=onrm[:kv], rgba8=orgb[:kv], info=oinf[:kv], tri=otri[:kt], report=report)
+
     # -- multi-GPU: the context's own RCCL communicator (pgx_comm_*) ------------------------------
     def comm_init(self, rank, world, unique_id):
         """Collective: every rank calls this with the 128 bytes rank 0 got from comm_unique_id()."""

@@ -22,6 +22,7 @@
 // Every sum is an integer: no order of execution changes a bit.  DESIGN.md section 28.
 #include "pgx_stage_args.h"
 #include "pgx_densecam.h"
+#include "pgx_cloudkey.h"   // rule 1 (the used test, the key, the position in the cell) and the colour slot: shared with k_mesh.hip
 
 namespace {
 
@@ -29,21 +30,10 @@ constexpr int CLD_NT = 256;            // threads per workgroup of every kernel 
 constexpr int CLD_GRID_MAX = 1024;     // workgroups of the per-point kernels, grid-stride beyond
 constexpr int CLD_LG_TMIN = 8;         // the table has at least 1 << 8 entries
 constexpr int CLD_ACC = 10;            // 64-bit accumulators per kept cell: sp (3), sn (3), sc (3), nn | nc << 32
-constexpr int CLD_GBIAS = 1 << 20;     // g + CLD_GBIAS is a cell coordinate's 21-bit field of the key
 constexpr unsigned long long CLD_EMPTY = ~0ull;                    // no key: a key has 63 bits
 constexpr unsigned long long CLD_HASH_MUL = 0x9E3779B97F4A7C15ull; // cld_hash: the top lg_table bits of key * this (mod 2^64)
 
 __device__ __forceinline__ unsigned cld_hash(unsigned long long key, int lg) { return (unsigned)((key * CLD_HASH_MUL) >> (64 - lg)); }
-
-// the lowest slot that shows frame f, -1 if none does, f is no frame number or there are no colours
-__device__ __forceinline__ int cld_slot(const CloudArgs &a, int f)
-{
-    if (!a.rgba8 || f < 0 || f >= a.n_frames) return -1;
-    if (!a.frame_ids) return f < a.F ? f : -1;
-    for (int s = 0; s < a.F; s++)
-        if (a.frame_ids[s] == f) return s;
-    return -1;
-}
 
 __global__ __launch_bounds__(CLD_NT) void k_cld_plan(CloudArgs a)
 {
@@ -147,18 +137,9 @@ __global__ __launch_bounds__(CLD_NT) void k_cld_points(CloudArgs a)
         const int i = b * CLD_NT + (int)threadIdx.x;
         int used = 0, hasn = 0, hasc = 0;
         if (i < n) {
-            const int r = a.src[2 * (size_t)i], pix = a.src[2 * (size_t)i + 1];
-            bool ok = r >= 0 && r < a.R && pix >= 0 && pix < npix;
-            unsigned long long key = 0, pk = 0;
-#pragma unroll
-            for (int k = 0; k < 3; k++) {
-                const double X = a.xyz[3 * (size_t)i + k], org = k == 0 ? a.ox : (k == 1 ? a.oy : a.oz);
-                const double t = (X - org) / a.cell, g = floor(t);
-                const bool in = isfinite(X) && g >= -1048576.0 && g < 1048576.0;   // NaN fails
-                ok = ok && in;
-                key = (key << 21) | (unsigned long long)(in ? (long long)g + CLD_GBIAS : 0);
-                pk |= (unsigned long long)(in ? (int)floor((t - g) * 65536.0) : 0) << (16 * k);
-            }
+            int r, pix;
+            unsigned long long key, pk;
+            const bool ok = cld_point_key(a.xyz, a.src, (size_t)i, a.R, npix, a.cell, a.ox, a.oy, a.oz, r, pix, key, pk);
             int q0 = 0, q1 = 0, q2 = 0, sl = -1;
             if (ok) {
                 used = 1;

@@ -108,6 +108,9 @@ int decode_status(pgx_ctx *c, int bits)
         return fail(c, PGX_E_CAPACITY, "depth fusion: more than max_points pixels were kept (the first max_points were written)");
     if (bits & PGX_ST_CLD_CAP)
         return fail(c, PGX_E_CAPACITY, "cloud merge: more than max_points cells were kept (the first max_points were written)");
+    if (bits & PGX_ST_MSH_CAP)
+        return fail(c, PGX_E_CAPACITY, "mesh: more than max_voxels voxels (nothing was written), or more than max_vertices vertices or "
+                                       "max_tris triangles (the first ones were written)");
     if (bits & PGX_ST_DVW_CAP)
         return fail(c, PGX_E_CAPACITY, "dense views: n_tracks exceeds max_tracks (only the first max_tracks were processed)");
     if (bits & PGX_ST_DVW_NODE)
@@ -472,7 +475,7 @@ void pgx_ctx_destroy(pgx_ctx *c)
     for (hipEvent_t ev : c->ev_pool) (void)hipEventDestroy(ev);
     DevBuf *bufs[] = {&c->d_pairs, &c->d_plan, &c->d_steer_pairs, &c->d_steer_plans, &c->d_steer_dirs, &c->d_map, &c->d_gather, &c->ws_gray, &c->ws_seg, &c->ws_segoff, &c->ws_nraw, &c->ws_rawxy,
                       &c->ws_rawscore, &c->ws_nms, &c->ws_order, &c->ws_nkept, &c->st_a, &c->st_b, &c->st_c,
-                      &c->st_d, &c->st_e, &c->st_f, &c->ws_pose, &c->ws_tracks, &c->ws_tracks_split, &c->ws_agree, &c->ws_matchn[0], &c->ws_matchn[1], &c->ws_matchn[2], &c->ws_knn, &c->ws_guided, &c->ws_tri, &c->ws_ba, &c->ws_reg, &c->ws_ver, &c->ws_init, &c->ws_cns, &c->ws_vocab, &c->ws_depth, &c->ws_dviews, &c->ws_cloud,
+                      &c->st_d, &c->st_e, &c->st_f, &c->ws_pose, &c->ws_tracks, &c->ws_tracks_split, &c->ws_agree, &c->ws_matchn[0], &c->ws_matchn[1], &c->ws_matchn[2], &c->ws_knn, &c->ws_guided, &c->ws_tri, &c->ws_ba, &c->ws_reg, &c->ws_ver, &c->ws_init, &c->ws_cns, &c->ws_vocab, &c->ws_depth, &c->ws_dviews, &c->ws_cloud, &c->ws_mesh,
                       &c->ws_pyr_a, &c->ws_pyr_b, &c->ws_pyr_kp, &c->ws_pyr_desc, &c->ws_pyr_bins, &c->ws_pyr_cnt};
     for (DevBuf *b : bufs) b->release();
     c->pin_in.release();
@@ -1540,6 +1543,16 @@ int run_cloud_merge(pgx_ctx *c, CloudArgs &a)
     return PGX_OK;
 }
 
+// the launcher brackets its own parts; the workspace is sized before any launch
+int run_mesh(pgx_ctx *c, MeshArgs &a)
+{
+    a.status = c->d_status;
+    HIPCHK(c, c->ws_mesh.ensure(pgx_mesh_ws_bytes(a)));
+    pgx_launch_mesh(c, c->stream, a, c->ws_mesh.p);
+    HIPCHK(c, hipGetLastError());
+    return PGX_OK;
+}
+
 // ---- the track graph as a stage sees it (inv: the launcher's)
 
 // a device form's: an offset may reach every slot
@@ -2416,6 +2429,105 @@ int pgx_cloud_merge(pgx_ctx *c, const double *xyz, const int32_t *src, int n_in,
         HIPCHK(c, hipMemcpy(out_rgba8, out.dev<uint32_t>(o_c), np * 4, hipMemcpyDeviceToHost));
         HIPCHK(c, hipMemcpy(out_info, out.dev<int32_t>(o_i), np * 16, hipMemcpyDeviceToHost));
     }
+    return rs;
+}
+
+// ---- a triangle mesh from the depth maps: TSDF grid and surface nets ----------------------------------------------------
+
+namespace {
+// what the device and the host form of the mesh check alike: the cloud's refusals for the arguments the calls share, then its own
+int mesh_args(pgx_ctx *c, int max_in, int R, int S, int W, int H, int n_frames, int min_agree, bool has_rgba8, int F, bool has_ids,
+              double cell, double ox, double oy, double oz, int band, int trunc_cells, int min_weight, int max_voxels, int max_vertices,
+              int max_tris)
+{
+    if (const int rc = cloud_args(c, max_in, R, S, W, H, n_frames, has_rgba8, F, has_ids, cell, ox, oy, oz, 1, 0.0, 1, 0); rc != PGX_OK)
+        return rc;
+    if (band < 1 || band > 3) return fail(c, PGX_E_BADARG, "band = %d, must be in [1, 3]", band);
+    if (trunc_cells < 1 || trunc_cells > 8) return fail(c, PGX_E_BADARG, "trunc_cells = %d, must be in [1, 8]", trunc_cells);
+    if (min_weight < 1) return fail(c, PGX_E_BADARG, "min_weight must be >= 1");
+    if (min_agree < 0) return fail(c, PGX_E_BADARG, "min_agree must be >= 0");
+    for (const int cap : {max_voxels, max_vertices, max_tris})
+        if (cap < 0 || cap > (1 << 28)) return fail(c, PGX_E_BADARG, "max_voxels, max_vertices and max_tris must be in [0, 2^28]");
+    return PGX_OK;
+}
+} // namespace
+
+int pgx_mesh_dev(pgx_ctx *c, const double *d_xyz, const int32_t *d_src, const int32_t *d_count, int max_in, const double *d_depth,
+                 const int32_t *d_views, int R, int S, int W, int H, int n_frames, const double *d_P, const int32_t *d_agree,
+                 int min_agree, const uint32_t *d_rgba8, int F, const int32_t *d_frame_ids, double cell, double ox, double oy, double oz,
+                 int band, int trunc_cells, int min_weight, int max_voxels, int max_vertices, int max_tris, double *d_out_xyz,
+                 float *d_out_normal, uint32_t *d_out_rgba8, int32_t *d_out_info, int32_t *d_out_tri, int32_t *d_report)
+{
+    if (!c || !d_depth || !d_views || !d_P || !d_report || (max_in > 0 && (!d_xyz || !d_src)) ||
+        (max_vertices > 0 && (!d_out_xyz || !d_out_normal || !d_out_rgba8 || !d_out_info)) || (max_tris > 0 && !d_out_tri))
+        return c ? fail(c, PGX_E_BADARG, "null pointer") : PGX_E_BADARG;
+    Lock l(c);
+    const int rc = mesh_args(c, max_in, R, S, W, H, n_frames, min_agree, d_rgba8 != nullptr, F, d_frame_ids != nullptr, cell, ox, oy, oz,
+                             band, trunc_cells, min_weight, max_voxels, max_vertices, max_tris);
+    if (rc != PGX_OK) return rc;
+    const size_t ni = max_in, nv = max_vertices, nt = max_tris, npix = (size_t)W * H;
+    const struct { const void *p; size_t n; } in[] = {{d_xyz, ni * 24}, {d_src, ni * 8}, {d_count, 4}, {d_depth, (size_t)R * npix * 8},
+                                                      {d_views, (size_t)R * (1 + S) * 4}, {d_P, (size_t)n_frames * 96},
+                                                      {d_agree, (size_t)R * npix * 4}, {d_rgba8, d_rgba8 ? (size_t)F * npix * 4 : 0},
+                                                      {d_frame_ids, d_rgba8 ? (size_t)F * 4 : 0}},
+                                        out[] = {{d_out_xyz, nv * 24}, {d_out_normal, nv * 12}, {d_out_rgba8, nv * 4}, {d_out_info, nv * 16},
+                                                 {d_out_tri, nt * 12}, {d_report, 32}};
+    for (const auto &o : out)
+        for (const auto &i : in)
+            if (overlap(o.p, o.n, i.p, i.n)) return fail(c, PGX_E_BADARG, "an output must not alias an input");
+    MeshArgs a{};
+    a.xyz = d_xyz; a.src = d_src; a.count = d_count; a.max_in = max_in; a.depth = d_depth; a.views = d_views;
+    a.R = R; a.S = S; a.W = W; a.H = H; a.n_frames = n_frames; a.P = d_P; a.agree = d_agree; a.min_agree = min_agree;
+    a.rgba8 = d_rgba8; a.F = d_rgba8 ? F : 0; a.frame_ids = d_rgba8 ? d_frame_ids : nullptr;
+    a.cell = cell; a.ox = ox; a.oy = oy; a.oz = oz; a.band = band; a.trunc_cells = trunc_cells; a.min_weight = min_weight;
+    a.max_voxels = max_voxels; a.max_vertices = max_vertices; a.max_tris = max_tris;
+    a.out_xyz = d_out_xyz; a.out_normal = d_out_normal; a.out_rgba8 = d_out_rgba8; a.out_info = d_out_info; a.out_tri = d_out_tri;
+    a.report = d_report;
+    return run_mesh(c, a);
+}
+
+int pgx_mesh(pgx_ctx *c, const double *xyz, const int32_t *src, int n_in, const double *depth, const int32_t *views, int R, int S, int W,
+             int H, int n_frames, const double *P, const int32_t *agree, int min_agree, const uint32_t *rgba8, double cell, double ox,
+             double oy, double oz, int band, int trunc_cells, int min_weight, int max_voxels, int max_vertices, int max_tris,
+             double *out_xyz, float *out_normal, uint32_t *out_rgba8, int32_t *out_info, int32_t *out_tri, int32_t *report)
+{
+    if (!c || !depth || !views || !P || !report || (n_in > 0 && (!xyz || !src)) ||
+        (max_vertices > 0 && (!out_xyz || !out_normal || !out_rgba8 || !out_info)) || (max_tris > 0 && !out_tri))
+        return c ? fail(c, PGX_E_BADARG, "null pointer") : PGX_E_BADARG;
+    Lock l(c);
+    int rs = mesh_args(c, n_in, R, S, W, H, n_frames, min_agree, rgba8 != nullptr, n_frames, false, cell, ox, oy, oz, band, trunc_cells,
+                       min_weight, max_voxels, max_vertices, max_tris);
+    if (rs != PGX_OK) return rs;
+    const size_t ni = n_in, nv = max_vertices, nt = max_tris, npix = (size_t)W * H;
+    HostImage in, out;
+    const int i_x = in.add(xyz, ni, 24, 1), i_s = in.add(src, ni, 8, 1), i_d = in.add(depth, (size_t)R * npix, 8),
+              i_v = in.add(views, (size_t)R * (1 + S), 4), i_P = in.add(P, n_frames, 96),
+              i_a = in.add(agree, (size_t)R * npix, 4, 0, agree != nullptr),
+              i_c = in.add(rgba8, (size_t)n_frames * npix, 4, 0, rgba8 != nullptr);
+    // the report first: its download tells how many vertices and triangles there are to fetch
+    const int o_r = out.add(report, 8, 4, 64), o_x = out.add(nullptr, 0, 24, nv + 1), o_n = out.add(nullptr, 0, 12, nv + 1),
+              o_c = out.add(nullptr, 0, 4, nv + 1), o_i = out.add(nullptr, 0, 16, nv + 1), o_t = out.add(nullptr, 0, 12, nt + 1);
+    if ((rs = stage_images(c, in, out)) != PGX_OK) return rs;
+    MeshArgs a{};
+    a.xyz = in.dev<double>(i_x); a.src = in.dev<int32_t>(i_s); a.count = nullptr; a.max_in = n_in;
+    a.depth = in.dev<double>(i_d); a.views = in.dev<int32_t>(i_v); a.R = R; a.S = S; a.W = W; a.H = H; a.n_frames = n_frames;
+    a.P = in.dev<double>(i_P); a.agree = in.dev<int32_t>(i_a); a.min_agree = min_agree;
+    a.rgba8 = in.dev<uint32_t>(i_c); a.F = rgba8 ? n_frames : 0; a.frame_ids = nullptr;
+    a.cell = cell; a.ox = ox; a.oy = oy; a.oz = oz; a.band = band; a.trunc_cells = trunc_cells; a.min_weight = min_weight;
+    a.max_voxels = max_voxels; a.max_vertices = max_vertices; a.max_tris = max_tris;
+    a.out_xyz = out.dev<double>(o_x); a.out_normal = out.dev<float>(o_n); a.out_rgba8 = out.dev<uint32_t>(o_c);
+    a.out_info = out.dev<int32_t>(o_i); a.out_tri = out.dev<int32_t>(o_t); a.report = out.dev<int32_t>(o_r);
+    if ((rs = run_mesh(c, a)) != PGX_OK) return rs;
+    rs = download_images(c, out);   // the report; waits for the stream
+    if (rs != PGX_OK && rs != PGX_E_CAPACITY) return rs;   // the report was not downloaded: nothing tells how many rows there are
+    const size_t mv = (size_t)(report[5] < max_vertices ? report[5] : max_vertices), mt = (size_t)(report[6] < max_tris ? report[6] : max_tris);
+    if (mv > 0) {
+        HIPCHK(c, hipMemcpy(out_xyz, out.dev<double>(o_x), mv * 24, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(out_normal, out.dev<float>(o_n), mv * 12, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(out_rgba8, out.dev<uint32_t>(o_c), mv * 4, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(out_info, out.dev<int32_t>(o_i), mv * 16, hipMemcpyDeviceToHost));
+    }
+    if (mt > 0) HIPCHK(c, hipMemcpy(out_tri, out.dev<int32_t>(o_t), mt * 12, hipMemcpyDeviceToHost));
     return rs;
 }
 

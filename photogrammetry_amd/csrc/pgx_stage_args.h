@@ -1,5 +1,5 @@
 // pgx_stage_args.h -- the arguments of the stages behind the matchers, each as the struct its kernels take by value:
-// triangulation, bundle adjustment, registration, consensus, verification, initial pair, depth maps, depth fuse, dense views, cloud merge.  The C ABI's
+// triangulation, bundle adjustment, registration, consensus, verification, initial pair, depth maps, depth fuse, dense views, cloud merge, mesh.  The C ABI's
 // two forms of a stage (pgx_api.hip) fill "the caller fills" by name and hand the struct to run_X; the launcher carves the
 // workspace into the rest and launches.  The layout IS the kernarg layout: fields, order and types are the kernels' (the
 // capitals in the shapes are constants of the stage's .hip file).  Internal to libpgx.so; DESIGN.md section 14h.
@@ -287,3 +287,51 @@ struct CloudArgs {
 };
 size_t pgx_cloud_ws_bytes(const CloudArgs &a);
 void pgx_launch_cloud_merge(pgx_ctx *ctx, hipStream_t s, CloudArgs a, void *ws);
+
+// ---- k_mesh.hip (a triangle mesh from the depth maps: a TSDF on a hashed grid and surface nets; pgx_mesh_dev semantics) ---
+// ctx: the profiling groups mesh_plan / mesh_seed / mesh_dilate / mesh_tsdf / mesh_cubes / mesh_rank / mesh_vertices / mesh_tris
+struct MeshArgs {
+    // the caller fills
+    const double *xyz;            // [max_in][3]
+    const int32_t *src;           // [max_in][2] = (r, v W + u)
+    const int32_t *count;         // [0] = the entries of the list, or nullptr: max_in
+    int max_in;
+    const double *depth;          // [R][H][W]
+    const int32_t *views;         // [R][1 + S]: column 0 alone is read
+    int R, S, W, H, n_frames;
+    const double *P;              // [n_frames][12]
+    const int32_t *agree;         // [R][H][W] or nullptr
+    int min_agree;
+    const uint32_t *rgba8;        // [F][H][W] or nullptr
+    int F;
+    const int32_t *frame_ids;     // [F] or nullptr
+    double cell, ox, oy, oz;
+    int band, trunc_cells, min_weight, max_voxels, max_vertices, max_tris;
+    double *out_xyz;              // [max_vertices][3]
+    float *out_normal;            // [max_vertices][3]
+    uint32_t *out_rgba8;          // [max_vertices]
+    int32_t *out_info;            // [max_vertices][4] = (c_0, c_1, c_2, mask | k << 8)
+    int32_t *out_tri;             // [max_tris][3]
+    int32_t *report;              // [8]
+    // the launcher fills (workspace, derived)
+    int lg_table;                 // the table has 1 << lg_table entries
+    unsigned long long *keys;     // [table]: the node's key, MSH_EMPTY = none
+    unsigned long long *ord;      // [table]: ord(c), MSH_NOORD = none yet
+    int32_t *sfirst;              // [table]: the first point whose own cell is this node, MSH_NOSEED = none
+    int32_t *wst;                 // [table][2]: w, st
+    int32_t *col;                 // [table][4]: nc, sc
+    int32_t *cflag;               // [table]: of the cube whose low node this is: mask | complete << 8 | active << 9
+    int32_t *vidx, *qidx;         // [table]: the cube's vertex, the first quad of the node's edges
+    unsigned char *nflag;         // [table]: valid | inside << 1
+    unsigned char *qflag;         // [table]: bit a = the edge along axis a has a quad
+    double *cam;                  // [R][FUSE_CAM]: the filter's camera table
+    int32_t *cslot;               // [R]: the slot that shows the map's frame, -1 = none
+    int32_t *slot;                // [max_in]: the table entry of the point's own cell's node, -1 = not used
+    unsigned long long *bsum, *boff;   // [nb]: vertices | quads << 32 owned per block of 256 points, their exclusive scan
+    int32_t *meta;                // [0] n, [1] used, [2] seed cells, [3] voxels, [4] valid voxels, [5] vertices, [6] quads
+    int nb;                       // blocks of 256 points
+    // the caller fills
+    int *status;                  // a capacity exceeded: PGX_ST_MSH_CAP
+};
+size_t pgx_mesh_ws_bytes(const MeshArgs &a);
+void pgx_launch_mesh(pgx_ctx *ctx, hipStream_t s, MeshArgs a, void *ws);

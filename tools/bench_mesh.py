@@ -1,0 +1,92 @@
+"""Micro-benchmark of the mesh at tools/bench_cloud.py's shape: 8 references of 1920 x 1080 out of 12
+frames on a line, the filter's list of their depth maps (a smooth synthetic surface seen by every camera) meshed at a cell of
+--cell-scale pixel footprints, band 1, truncation 3 cells.  Timed with HIP events on geom_bench's loop: the whole pgx_mesh_dev
+call, and the whole pgx_cloud_merge_dev call on the same list for scale; then the mesh by pass from the stage's profiling groups
+(pgx_profile_get) in a second pass.  Writes profiles/mesh_<shape>.json (or --out DIR)."""
+import argparse
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+sys.path.insert(0, ROOT)
+import geom_bench as gb  # noqa: E402
+import photogrammetry_amd as pg  # noqa: E402
+from bench_cloud import surface_depths  # noqa: E402
+from bench_depth import cameras  # noqa: E402
+from geom_bench import DEV, F64, I32  # noqa: E402
+
+PARTS = ("mesh_plan", "mesh_seed", "mesh_dilate", "mesh_tsdf", "mesh_cubes", "mesh_rank", "mesh_vertices", "mesh_tris")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=9)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--width", type=int, default=1920)
+    ap.add_argument("--height", type=int, default=1080)
+    ap.add_argument("--frames", type=int, default=12)
+    ap.add_argument("--refs", type=int, default=8)
+    ap.add_argument("--cell-scale", type=float, default=1.0, help="the cell in pixel footprints")
+    ap.add_argument("--band", type=int, default=1)
+    ap.add_argument("--trunc-cells", type=int, default=3)
+    ap.add_argument("--max-voxels", type=int, default=1 << 25)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles"))
+    args = ap.parse_args()
+    assert args.steps >= 7, "the median of at least 7 calls"
+    W, H, F, R, S, focal = args.width, args.height, args.frames, args.refs, 4, 1500.0
+    eng = pg.Engine(0)
+    torch.manual_seed(0)
+    P = torch.from_numpy(cameras(F, W, H, focal, 0.25)).to(DEV)
+    first = (F - R) // 2
+    views = np.array([[first + r] + [first + r + o for o in (-2, -1, 1, 2)] for r in range(R)], dtype=np.int32)
+    views[(views < 0) | (views >= F)] = -1
+    d_views = torch.from_numpy(views).to(DEV)
+    dep = surface_depths(P, W, H, R, first)
+    rgba = torch.from_numpy(np.random.default_rng(0).integers(0, 65536, (F, H, W, 4), dtype=np.uint16)).to(DEV)
+    col, agr = torch.empty((F, H, W), **I32), torch.empty((R, H, W), **I32)
+    cap = R * W * H
+    xyz, src, fsum = torch.empty((cap, 3), **F64), torch.empty((cap, 2), **I32), torch.empty(4, **I32)
+    mvox, mv, mt = args.max_voxels, args.max_voxels // 2, args.max_voxels
+    oxyz, onrm = torch.empty((cap, 3), **F64), torch.empty((cap, 3), dtype=torch.float32, device=DEV)
+    orgb, oinf, crep = torch.empty(cap, **I32), torch.empty((cap, 4), **I32), torch.empty(8, **I32)
+    otri, rep = torch.empty((mt, 3), **I32), torch.empty(8, **I32)
+    cell = float(dep.median()) / focal * args.cell_scale
+    origin = (-(2**19) * cell,) * 3
+    torch.cuda.synchronize()
+    eng.depth_fuse_dev(dep, d_views, R, S, W, H, F, P, cap, xyz, src, fsum, rel_tol=0.05, min_agree=2, d_agree=agr)
+    eng.rgba8_batch_dev(rgba, F, W, H, col)
+    eng.check_status()
+
+    def mesh():   # the vertex outputs reuse the cloud's buffers: mv <= cap rows
+        eng.mesh_dev(xyz, src, fsum, cap, dep, d_views, R, S, W, H, F, P, cell, origin, mvox, min(mv, cap), mt, oxyz, onrm, orgb, oinf, otri,
+                     rep, d_agree=agr, min_agree=2, d_rgba8=col, F=F, band=args.band, trunc_cells=args.trunc_cells)
+
+    def merge():
+        eng.cloud_merge_dev(xyz, src, fsum, cap, dep, d_views, R, S, W, H, F, P, cell, origin, cap, oxyz, onrm, orgb, oinf, crep,
+                            d_rgba8=col, F=F, normal_step=1, disc_tol=0.02, min_support=1)
+    ms_merge = gb.time_on_stream(eng, merge, args.steps, args.warmup)
+    ms_mesh = gb.time_on_stream(eng, mesh, args.steps, args.warmup)
+    eng.profile_reset()
+    eng.profile_enable(True)
+    for _ in range(args.steps):
+        mesh()
+    eng.check_status()
+    parts = {p: eng.profile_get(p)[1] / args.steps for p in PARTS}
+    eng.profile_enable(False)
+    report = rep.cpu().tolist()
+    med = float(np.median(ms_mesh))
+    rec = dict(shape="%dx%d_r%d_c%g_b%d" % (W, H, R, args.cell_scale, args.band), frames=F, refs=R, cell=cell, band=args.band,
+               trunc_cells=args.trunc_cells, steps=args.steps, mesh_ms_median=med, mesh_ms_min=float(ms_mesh.min()),
+               mesh_ms_max=float(ms_mesh.max()), parts_ms={k: round(v, 4) for k, v in parts.items()}, report=report,
+               input_points=report[0], seed_cells=report[2], voxels=report[3], valid_voxels=report[4], vertices=report[5],
+               triangles=report[6], max_voxels=mvox, voxels_per_s=report[3] / (med * 1e-3),
+               cloud_merge_ms_median=float(np.median(ms_merge)), cloud_report=crep.cpu().tolist(), fuse_summary=fsum.cpu().tolist())
+    gb.write_record(rec, args.out, "mesh")
+    eng.close()
+
+
+if __name__ == "__main__":
+    main()

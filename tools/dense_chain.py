@@ -2,7 +2,8 @@
 pgx_gray_batch_dev -> pgx_depth_maps_dev -> pgx_depth_fuse_dev -> pgx_rgba8_batch_dev -> pgx_cloud_merge_dev on one stream, with
 no synchronisation between the triangulation and the merged cloud.  The scene is synth.make_scene's (frames on an arc, true tracks cut to runs); the frames are
 seeded noise, so the maps carry no meaning: the tool shows that the chain runs and what it costs.  Timed with HIP events on
-geom_bench's loop; prints one JSON line and writes profiles/dense_chain_<shape>.json (or --out DIR)."""
+geom_bench's loop; prints one JSON line and writes profiles/dense_chain_<shape>.json (or --out DIR).  --mesh adds pgx_mesh_dev
+behind the cloud and writes profiles/dense_chain_mesh_<shape>.json; the default run is the chain above."""
 import argparse
 import os
 import sys
@@ -19,6 +20,7 @@ from geom_bench import DEV, F64, I32  # noqa: E402
 PARTS = ("triangulate", "dense_views_nodes", "dense_views_pairs", "dense_views_select", "dewarp_gray", "depth_census", "depth_plan",
          "depth_sweep", "depth_fuse", "dewarp_rgba8", "cloud_plan", "cloud_normals", "cloud_points", "cloud_rank", "cloud_accum",
          "cloud_final")
+MESH_PARTS = ("mesh_plan", "mesh_seed", "mesh_dilate", "mesh_tsdf", "mesh_cubes", "mesh_rank", "mesh_vertices", "mesh_tris")
 
 
 def main():
@@ -32,6 +34,7 @@ def main():
     ap.add_argument("--sources", type=int, default=4)
     ap.add_argument("--planes", type=int, default=64)
     ap.add_argument("--cell", type=float, default=0.02)
+    ap.add_argument("--mesh", action="store_true", help="pgx_mesh_dev behind the cloud (band 2, truncation 3 cells); the record is dense_chain_mesh_*")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles"))
     args = ap.parse_args()
     W, H, nf, S, D = args.width, args.height, args.frames, args.sources, args.planes
@@ -51,6 +54,13 @@ def main():
     oxyz, onrm = torch.empty((cap, 3), **F64), torch.empty((cap, 3), dtype=torch.float32, device=DEV)
     orgb, oinf, crep = torch.empty(cap, **I32), torch.empty((cap, 4), **I32), torch.empty(8, **I32)
     origin = (-(2**19) * args.cell,) * 3      # the scene in the middle of the grid
+    parts_of = PARTS
+    if args.mesh:
+        parts_of = PARTS + MESH_PARTS
+        mvox, mv, mt = 1 << 24, 1 << 22, 1 << 23
+        agr = torch.empty((nf, H, W), **I32)
+        mxyz, mnrm = torch.empty((mv, 3), **F64), torch.empty((mv, 3), dtype=torch.float32, device=DEV)
+        mrgb, minf, mtri, mrep = torch.empty(mv, **I32), torch.empty((mv, 4), **I32), torch.empty((mt, 3), **I32), torch.empty(8, **I32)
     torch.cuda.synchronize()
 
     def chain():
@@ -58,23 +68,28 @@ def main():
         eng.dense_views_dev(d["off"], d["nodes"], d["tsum"], nt, N, xyz, nf, d["P"], nf, S, views, rng_d, st, rep, d_track_flags=tfl)
         eng.gray_batch_dev(rgba, nf, W, H, gray)
         eng.depth_maps_dev(gray, nf, W, H, nf, d["P"], views, nf, S, rng_d, D, kq8, dep, fl, msum, agg_radius=2, min_views=2)
-        eng.depth_fuse_dev(dep, views, nf, S, W, H, nf, d["P"], cap, pts, src, fsum)
+        eng.depth_fuse_dev(dep, views, nf, S, W, H, nf, d["P"], cap, pts, src, fsum, d_agree=agr if args.mesh else None)
         eng.rgba8_batch_dev(rgba, nf, W, H, col)
         eng.cloud_merge_dev(pts, src, fsum, cap, dep, views, nf, S, W, H, nf, d["P"], args.cell, origin, cap, oxyz, onrm, orgb, oinf, crep,
                             d_rgba8=col, F=nf)
+        if args.mesh:
+            eng.mesh_dev(pts, src, fsum, cap, dep, views, nf, S, W, H, nf, d["P"], args.cell, origin, mvox, mv, mt, mxyz, mnrm, mrgb, minf,
+                         mtri, mrep, d_agree=agr, min_agree=2, d_rgba8=col, F=nf, band=2, trunc_cells=3)
     ms = gb.time_on_stream(eng, chain, args.steps, args.warmup)
     eng.profile_reset()
     eng.profile_enable(True)
     for _ in range(args.steps):
         chain()
     eng.check_status()
-    parts = {p: eng.profile_get(p)[1] / args.steps for p in PARTS}
+    parts = {p: eng.profile_get(p)[1] / args.steps for p in parts_of}
     eng.profile_enable(False)
     rec = dict(shape="%dx%d_f%d_s%d_d%d" % (W, H, nf, S, D), frames=nf, tracks=nt, nodes=d["n_nodes"], steps=args.steps,
                chain_ms_median=float(np.median(ms)), chain_ms_min=float(ms.min()), chain_ms_max=float(ms.max()),
                parts_ms={k: round(v, 4) for k, v in parts.items()}, views_report=rep.cpu().tolist(), maps_summary=msum.cpu().tolist(),
                fuse_summary=fsum.cpu().tolist(), cloud_report=crep.cpu().tolist(), refs_flagged=int((st.cpu().numpy()[:, 3] != 0).sum()))
-    gb.write_record(rec, args.out, "dense_chain")
+    if args.mesh:
+        rec["mesh_report"] = mrep.cpu().tolist()
+    gb.write_record(rec, args.out, "dense_chain_mesh" if args.mesh else "dense_chain")
     eng.close()
 
 
