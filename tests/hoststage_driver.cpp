@@ -2,7 +2,10 @@
 // argv[1] names a host form, whose section lists are checked at every size of the test's docstring against images laid out
 // naively here.  The input lists are the header's own (tracks_in, pair_in, two_sets_in, batch_in), and so is knn_out; the
 // other output lists, F and K of pgx_relative_pose, and S and `used` of pgx_match_batch are declared or computed here word
-// for word as the form in pgx_api.hip does.  Host code only; the test
+// for word as the form in pgx_api.hip does.  So are both lists of the nine later forms (pgx_track_consensus's inputs excepted,
+// which are tracks_in): pgx_vocab_train, pgx_select_pairs, pgx_depth_maps, pgx_depth_fuse, pgx_dense_views, pgx_rgba8_batch,
+// pgx_cloud_merge and pgx_mesh declare them inside pgx_api.hip.  For pgx_depth_fuse, pgx_cloud_merge and pgx_mesh the report
+// must be the output image's first download, and the lists of max + 1 rows behind it none.  Host code only; the test
 // builds it with -fsanitize=address,undefined, and every buffer has its exact size, so a read or write past an end is a
 // sanitizer report.  Exit status 0 and "ok <checks>" on stdout, or 1 and the first failure on stderr.
 #include <cstdio>
@@ -106,9 +109,10 @@ const int32_t COUNTS[3] = {0, 5, 2};
 const int N_TRACKS[3] = {0, 1, 7}, N_NODES[2] = {0, 19};
 size_t max1(size_t n) { return n > 0 ? n : 1; }
 
-// kind 0: triangulation, 1: bundle adjustment, 2: registration
+// kind 0: triangulation, 1: bundle adjustment, 2: registration, 9: track consensus (triangulation's inputs)
 void tracks_form(int kind)
 {
+    const bool by_P = kind == 0 || kind == 9;
     for (int n_frames : {1, 3})
         for (int n_tracks : N_TRACKS)
             for (int n_nodes : N_NODES)
@@ -126,9 +130,9 @@ void tracks_form(int kind)
                     const Bytes ts_b(reinterpret_cast<const char *>(ts), reinterpret_cast<const char *>(ts) + 8);
                     HostImage in;
                     const HostTracks t = {kps.p(), COUNTS, off.p(), nodes.p(), n_frames, n_tracks, stride, n_nodes};
-                    const TracksIn i = kind == 0 ? tracks_in(in, t, {P.p(), nullptr, nullptr}, {96, 0, 0}, false, nullptr, nullptr)
-                                                 : tracks_in(in, t, {K.p(), Rt.p(), sel.p()}, {32, 96, 4}, true, xyz.p(), flags.p());
-                    if (kind == 0)
+                    const TracksIn i = by_P ? tracks_in(in, t, {P.p(), nullptr, nullptr}, {96, 0, 0}, false, nullptr, nullptr)
+                                            : tracks_in(in, t, {K.p(), Rt.p(), sel.p()}, {32, 96, 4}, true, xyz.p(), flags.p());
+                    if (by_P)
                         check_in(in, {i.kp, i.frame[0], i.off, i.nodes, i.ts},
                                  {in_sec(nf * stride * 16, slots), in_sec(nf * 96, P.bytes()), in_sec((nt + 1) * 4, off.bytes()),
                                   in_sec(max1(nn) * 8, nodes.bytes()), in_sec(256, ts_b)});
@@ -164,6 +168,16 @@ void tracks_form(int kind)
                                         out.add(per_node_i, t.n_nodes, 4, 1, per_node_i != nullptr), out.add(w + 1, 8, 4, 64)},
                                   {out_sec(nf * 96, d, nf * 96), out_sec(nf * 96, d + 1, nf * 96), out_sec(nf * 16, w, nf * 16),
                                    out_sec(nf * 16, d + 2, nf * 16), out_sec(max1(nn) * 4, per_node_i, nn * 4, optional), out_sec(256, w + 1, 32)});
+                    } else if (kind == 9 && n_tracks > 0) {   // the form returns before any staging at n_tracks == 0
+                        // the per-track outputs null in half of the cases: carved for the kernels, not downloaded
+                        int32_t *const map = optional ? w + 3 : nullptr, *const fl = optional ? w + 4 : nullptr, *const st = optional ? w + 5 : nullptr;
+                        double *const pts = optional ? d : nullptr;
+                        check_out(out, {out.add(w, n_tracks + 1, 4), out.add(w + 1, t.n_nodes, 8, 1), out.add(w + 2, 8, 4, 64),
+                                        out.add(map, n_tracks, 4), out.add(pts, n_tracks, 24), out.add(fl, n_tracks, 4),
+                                        out.add(st, n_tracks, 16), out.add(w + 6, 8, 4, 64)},
+                                  {out_sec((nt + 1) * 4, w, (nt + 1) * 4), out_sec(max1(nn) * 8, w + 1, nn * 8), out_sec(256, w + 2, 32),
+                                   out_sec(nt * 4, map, nt * 4), out_sec(nt * 24, pts, nt * 24), out_sec(nt * 4, fl, nt * 4),
+                                   out_sec(nt * 16, st, nt * 16), out_sec(256, w + 6, 32)});
                     }
                 }
 }
@@ -298,6 +312,207 @@ void batch_form()
             }
 }
 
+// ---- the nine later forms.  Their lists are declared inside pgx_api.hip; each is repeated here word for word. ----------------
+
+// the report travels first: the form reads from it how many rows of the lists behind it to fetch
+void report_first(const HostImage &out, const void *report, size_t bytes)
+{
+    CHECK(!out.moves.empty() && out.moves[0].off == 0 && out.moves[0].host == report && out.moves[0].bytes == bytes);
+}
+
+const int RS[3] = {0, 1, 3}, NS[3] = {0, 1, 7}, CAPS[2] = {0, 5}, DIMS[2][2] = {{1, 1}, {5, 3}};
+
+// kind 10: pgx_vocab_train, 11: pgx_select_pairs (scores optional)
+void vocab_form(int kind)
+{
+    for (int F : {1, 3})
+        for (int stride : {1, 5})
+            for (int V : {1, 7})
+                for (int max_pairs : CAPS)
+                    for (int optional = 0; optional < 2; optional++) {
+                        if (kind == 10 && (max_pairs || optional)) continue;   // pgx_vocab_train has neither
+                        const size_t nd = (size_t)F * stride;
+                        Src<uint32_t> desc(nd * 8, 1), vocab(kind == 11 ? (size_t)V * 8 : 0, 3);
+                        Src<int32_t> counts(F, 2);
+                        uint32_t voc_out[1];
+                        int32_t w[8];
+                        HostImage in, out;
+                        if (kind == 10) {
+                            check_in(in, {in.add(desc.p(), (size_t)F * stride, 32), in.add(counts.p(), F, 4)},
+                                     {in_sec(nd * 32, desc.bytes()), in_sec((size_t)F * 4, counts.bytes())});
+                            check_out(out, {out.add(voc_out, V, 32), out.add(w, 4, 4, 16)},
+                                      {out_sec((size_t)V * 32, voc_out, (size_t)V * 32), out_sec(64, w, 16)});
+                            continue;
+                        }
+                        check_in(in, {in.add(desc.p(), (size_t)F * stride, 32), in.add(counts.p(), F, 4), in.add(vocab.p(), V, 32)},
+                                 {in_sec(nd * 32, desc.bytes()), in_sec((size_t)F * 4, counts.bytes()), in_sec((size_t)V * 32, vocab.bytes())});
+                        int32_t *const pairlist = max_pairs ? w : nullptr, *const pair_score = max_pairs ? w + 1 : nullptr;
+                        int32_t *const scores = optional ? w + 2 : nullptr, *const summary = w + 3;
+                        const size_t mp = max_pairs, ff = (size_t)F * F;
+                        check_out(out, {out.add(pairlist, max_pairs, 8, 1), out.add(pair_score, max_pairs, 4, 1),
+                                        out.add(scores, (size_t)F * F, 4, 0, scores != nullptr), out.add(summary, 8, 4, 16)},
+                                  {out_sec(max1(mp) * 8, pairlist, mp * 8), out_sec(max1(mp) * 4, pair_score, mp * 4),
+                                   out_sec(ff * 4, scores, ff * 4, optional), out_sec(64, summary, 32)});
+                    }
+}
+
+// kind 12: pgx_depth_maps (cost, warp, planes optional: all eight combinations), 13: pgx_depth_fuse (agree optional).  The
+// forms return before any staging at R == 0; their lists hold there all the same.
+void depth_form(int kind)
+{
+    const int S = 2, D = 5;
+    for (int R : RS)
+        for (const int(&wh)[2] : DIMS)
+            for (int n_frames : {1, 3})
+                for (int optional = 0; optional < (kind == 12 ? 8 : 2); optional++)
+                    for (int max_points : CAPS) {
+                        if (kind == 12 && max_points) continue;   // pgx_depth_maps has no list
+                        const int W = wh[0], H = wh[1];
+                        const size_t npix = (size_t)W * H, n = (size_t)R * npix, nf = n_frames, r = R;
+                        Src<double> P(nf * 12, 2);
+                        Src<int32_t> views(r * (1 + S), 3);
+                        double d[8];
+                        int32_t w[8];
+                        HostImage in, out;
+                        if (kind == 12) {
+                            Src<float> gray(nf * npix, 1);
+                            Src<double> range(r * 2, 4);
+                            check_in(in, {in.add(gray.p(), (size_t)n_frames * npix, 4), in.add(P.p(), n_frames, 96),
+                                          in.add(views.p(), (size_t)R * (1 + S), 4), in.add(range.p(), R, 16)},
+                                     {in_sec(nf * npix * 4, gray.bytes()), in_sec(nf * 96, P.bytes()), in_sec(r * (1 + S) * 4, views.bytes()),
+                                      in_sec(r * 16, range.bytes())});
+                            int32_t *const cost = optional & 1 ? w + 1 : nullptr;
+                            double *const warp = optional & 2 ? d + 1 : nullptr, *const planes = optional & 4 ? d + 2 : nullptr;
+                            int32_t *const kq8 = w, *const flags = w + 2, *const summary = w + 3;
+                            double *const depth = d;
+                            check_out(out, {out.add(kq8, n, 4), out.add(depth, n, 8), out.add(cost, n, 4, 0, cost != nullptr), out.add(flags, n, 4),
+                                            out.add(warp, (size_t)R * S * 12, 8, 0, warp != nullptr),
+                                            out.add(planes, (size_t)R * D, 8, 0, planes != nullptr), out.add(summary, 8, 4, 64)},
+                                      {out_sec(n * 4, kq8, n * 4), out_sec(n * 8, depth, n * 8), out_sec(n * 4, cost, n * 4, cost != nullptr),
+                                       out_sec(n * 4, flags, n * 4), out_sec(r * S * 96, warp, r * S * 96, warp != nullptr),
+                                       out_sec(r * D * 8, planes, r * D * 8, planes != nullptr), out_sec(256, summary, 32)});
+                            continue;
+                        }
+                        Src<double> depth(n, 1);
+                        check_in(in, {in.add(depth.p(), n, 8), in.add(views.p(), (size_t)R * (1 + S), 4), in.add(P.p(), n_frames, 96)},
+                                 {in_sec(n * 8, depth.bytes()), in_sec(r * (1 + S) * 4, views.bytes()), in_sec(nf * 96, P.bytes())});
+                        int32_t *const agree = optional ? w + 1 : nullptr, *const summary = w;
+                        const size_t mp = max_points;
+                        check_out(out, {out.add(summary, 4, 4, 64), out.add(agree, n, 4, 0, agree != nullptr),
+                                        out.add(nullptr, 0, 24, (size_t)max_points + 1), out.add(nullptr, 0, 8, (size_t)max_points + 1)},
+                                  {out_sec(256, summary, 16), out_sec(n * 4, agree, n * 4, optional), out_sec((mp + 1) * 24, nullptr, 0),
+                                   out_sec((mp + 1) * 8, nullptr, 0)});
+                        report_first(out, summary, 16);
+                    }
+}
+
+// kind 14: pgx_dense_views: track_flags, refs and pair_counts optional (all eight combinations), ref_stats null or not with them
+void dense_views_form()
+{
+    const int S = 2;
+    for (int R : RS)
+        for (int n_frames : {1, 3})
+            for (int n_tracks : NS)
+                for (int n_nodes : {0, 19})
+                    for (int optional = 0; optional < 8; optional++) {
+                        if (n_tracks == 0 && n_nodes > 0) continue;
+                        const size_t nt = n_tracks, nn = n_nodes, nf = n_frames, r = R;
+                        Src<int32_t> off(nt + 1, 1), nodes(nn * 2, 2), flags(optional & 1 ? nt : 0, 4), refs(optional & 2 ? r : 0, 6);
+                        Src<double> xyz(nt * 3, 3), P(nf * 12, 5);
+                        const bool has_flags = optional & 1, has_refs = optional & 2;
+                        // a null source of an optional input that is there: never at these sizes but with nothing to copy
+                        const int32_t none = 0;
+                        const int32_t *const track_flags = has_flags ? (nt ? flags.p() : &none) : nullptr;
+                        const int32_t *const ref_list = has_refs ? (r ? refs.p() : &none) : nullptr;
+                        HostImage in, out;
+                        check_in(in, {in.add(off.p(), n_tracks + 1, 4), in.add(nodes.p(), n_nodes, 8, 1), in.add(xyz.p(), n_tracks, 24, 1),
+                                      in.add(track_flags, n_tracks, 4, 1, track_flags != nullptr), in.add(P.p(), n_frames, 96),
+                                      in.add(ref_list, R, 4, 0, ref_list != nullptr), in.add_words({n_tracks, (int32_t)n_nodes}, 64)},
+                                 {in_sec((nt + 1) * 4, off.bytes()), in_sec(max1(nn) * 8, nodes.bytes()), in_sec(max1(nt) * 24, xyz.bytes()),
+                                  in_sec(max1(nt) * 4, flags.bytes(), has_flags), in_sec(nf * 96, P.bytes()), in_sec(r * 4, refs.bytes(), has_refs),
+                                  in_sec(256, words_of({n_tracks, n_nodes}))});
+                        double d[2];
+                        int32_t w[4];
+                        int32_t *const views = w, *const pair_counts = optional & 4 ? w + 1 : nullptr, *const ref_stats = optional & 4 ? w + 2 : nullptr;
+                        int32_t *const report = w + 3;
+                        double *const range = d;
+                        check_out(out, {out.add(views, (size_t)R * (1 + S), 4), out.add(range, R, 16),
+                                        out.add(pair_counts, (size_t)R * n_frames, 8, 0, pair_counts != nullptr), out.add(ref_stats, R, 16),
+                                        out.add(report, 8, 4, 64)},
+                                  {out_sec(r * (1 + S) * 4, views, r * (1 + S) * 4), out_sec(r * 16, range, r * 16),
+                                   out_sec(r * nf * 8, pair_counts, r * nf * 8, pair_counts != nullptr), out_sec(r * 16, ref_stats, r * 16),
+                                   out_sec(256, report, 32)});
+                    }
+}
+
+// kind 15: pgx_rgba8_batch, the source at 8 bytes a pixel (RGBA64) and at 4 (the context's RGBA8 source format)
+void rgba8_form()
+{
+    for (int F : {1, 3})
+        for (const int(&wh)[2] : DIMS)
+            for (int src8 = 0; src8 < 2; src8++) {
+                const size_t n = (size_t)F * wh[0] * wh[1];
+                Src<uint32_t> rgba(n * (src8 ? 1 : 2), 1);
+                uint32_t dst[1];
+                HostImage in, out;
+                check_in(in, {in.add(rgba.p(), n, src8 ? 4 : 8)}, {in_sec(n * (src8 ? 4 : 8), rgba.bytes())});
+                check_out(out, {out.add(dst, n, 4)}, {out_sec(n * 4, dst, n * 4)});
+            }
+}
+
+// kind 16: pgx_cloud_merge (rgba8 in; pt_normal, cell_of out optional), 17: pgx_mesh (agree, rgba8 in optional).  Both refuse R == 0.
+void cloud_form(int kind)
+{
+    const int S = 2;
+    for (int R : {1, 3})
+        for (const int(&wh)[2] : DIMS)
+            for (int n_in : NS)
+                for (int cap : CAPS)         // max_points; max_vertices
+                    for (int cap_t : CAPS)   // max_tris
+                        for (int optional = 0; optional < (kind == 16 ? 8 : 4); optional++) {
+                            if (kind == 16 && cap_t) continue;
+                            const int n_frames = 3;
+                            const size_t npix = (size_t)wh[0] * wh[1], ni = n_in, nf = n_frames, r = R;
+                            const bool has_rgba8 = optional & 1, has_agree = kind == 17 && (optional & 2);
+                            Src<double> xyz(ni * 3, 1), depth(r * npix, 3), P(nf * 12, 5);
+                            Src<int32_t> src(ni * 2, 2), views(r * (1 + S), 4), agree(has_agree ? r * npix : 0, 6);
+                            Src<uint32_t> rgba8(has_rgba8 ? nf * npix : 0, 7);
+                            int32_t w[8];
+                            int32_t *const report = w;
+                            HostImage in, out;
+                            if (kind == 16) {
+                                check_in(in, {in.add(xyz.p(), ni, 24, 1), in.add(src.p(), ni, 8, 1), in.add(depth.p(), (size_t)R * npix, 8),
+                                              in.add(views.p(), (size_t)R * (1 + S), 4), in.add(P.p(), n_frames, 96),
+                                              in.add(rgba8.p(), (size_t)n_frames * npix, 4, 0, rgba8.p() != nullptr)},
+                                         {in_sec(max1(ni) * 24, xyz.bytes()), in_sec(max1(ni) * 8, src.bytes()), in_sec(r * npix * 8, depth.bytes()),
+                                          in_sec(r * (1 + S) * 4, views.bytes()), in_sec(nf * 96, P.bytes()),
+                                          in_sec(nf * npix * 4, rgba8.bytes(), has_rgba8)});
+                                int32_t *const pt_normal = optional & 2 ? w + 1 : nullptr, *const cell_of = optional & 4 ? w + 2 : nullptr;
+                                const size_t no = cap;
+                                check_out(out, {out.add(report, 8, 4, 64), out.add(pt_normal, ni * 3, 4, 0, pt_normal != nullptr),
+                                                out.add(cell_of, ni, 4, 0, cell_of != nullptr), out.add(nullptr, 0, 24, no + 1),
+                                                out.add(nullptr, 0, 12, no + 1), out.add(nullptr, 0, 4, no + 1), out.add(nullptr, 0, 16, no + 1)},
+                                          {out_sec(256, report, 32), out_sec(ni * 12, pt_normal, ni * 12, pt_normal != nullptr),
+                                           out_sec(ni * 4, cell_of, ni * 4, cell_of != nullptr), out_sec((no + 1) * 24, nullptr, 0),
+                                           out_sec((no + 1) * 12, nullptr, 0), out_sec((no + 1) * 4, nullptr, 0), out_sec((no + 1) * 16, nullptr, 0)});
+                            } else {
+                                check_in(in, {in.add(xyz.p(), ni, 24, 1), in.add(src.p(), ni, 8, 1), in.add(depth.p(), (size_t)R * npix, 8),
+                                              in.add(views.p(), (size_t)R * (1 + S), 4), in.add(P.p(), n_frames, 96),
+                                              in.add(agree.p(), (size_t)R * npix, 4, 0, agree.p() != nullptr),
+                                              in.add(rgba8.p(), (size_t)n_frames * npix, 4, 0, rgba8.p() != nullptr)},
+                                         {in_sec(max1(ni) * 24, xyz.bytes()), in_sec(max1(ni) * 8, src.bytes()), in_sec(r * npix * 8, depth.bytes()),
+                                          in_sec(r * (1 + S) * 4, views.bytes()), in_sec(nf * 96, P.bytes()),
+                                          in_sec(r * npix * 4, agree.bytes(), has_agree), in_sec(nf * npix * 4, rgba8.bytes(), has_rgba8)});
+                                const size_t nv = cap, nt = cap_t;
+                                check_out(out, {out.add(report, 8, 4, 64), out.add(nullptr, 0, 24, nv + 1), out.add(nullptr, 0, 12, nv + 1),
+                                                out.add(nullptr, 0, 4, nv + 1), out.add(nullptr, 0, 16, nv + 1), out.add(nullptr, 0, 12, nt + 1)},
+                                          {out_sec(256, report, 32), out_sec((nv + 1) * 24, nullptr, 0), out_sec((nv + 1) * 12, nullptr, 0),
+                                           out_sec((nv + 1) * 4, nullptr, 0), out_sec((nv + 1) * 16, nullptr, 0), out_sec((nt + 1) * 12, nullptr, 0)});
+                            }
+                            report_first(out, report, 32);
+                        }
+}
+
 // sources declared out of order (no form does that): pack() still zeroes every byte that none of them covers
 void out_of_order()
 {
@@ -317,14 +532,23 @@ void out_of_order()
 
 int main(int argc, char **argv)
 {
-    static const char *const FORMS[9] = {"triangulate_tracks", "bundle_adjust", "register_frames", "verify_pair", "relative_pose",
-                                         "match", "knn", "knn_guided", "match_batch"};
+    static const char *const FORMS[18] = {"triangulate_tracks", "bundle_adjust", "register_frames", "verify_pair", "relative_pose",
+                                          "match", "knn", "knn_guided", "match_batch", "track_consensus", "vocab_train", "select_pairs",
+                                          "depth_maps", "depth_fuse", "dense_views", "rgba8_batch", "cloud_merge", "mesh"};
     int kind = -1;
-    for (int k = 0; k < 9; k++)
+    for (int k = 0; k < 18; k++)
         if (argc == 2 && argv[1] == std::string(FORMS[k])) kind = k;
     if (kind < 0) return 2;
     out_of_order();
-    kind < 3 ? tracks_form(kind) : kind < 5 ? pair_form(kind) : kind < 8 ? two_sets_form(kind) : batch_form();
+    if (kind < 3 || kind == 9) tracks_form(kind);
+    else if (kind < 5) pair_form(kind);
+    else if (kind < 8) two_sets_form(kind);
+    else if (kind == 8) batch_form();
+    else if (kind < 12) vocab_form(kind);
+    else if (kind < 14) depth_form(kind);
+    else if (kind == 14) dense_views_form();
+    else if (kind == 15) rgba8_form();
+    else cloud_form(kind);
     std::printf("ok %d\n", n_checks);
     return 0;
 }
