@@ -1298,6 +1298,82 @@ int pgx_mesh(pgx_ctx *ctx, const double *xyz, const int32_t *src, int n_in, cons
              int max_tris, double *out_xyz, float *out_normal, uint32_t *out_rgba8, int32_t *out_info, int32_t *out_tri,
              int32_t *report);
 
+/* ---- the mesh cleaned: small components dropped, smoothed, normals again ---------------------------- */
+/* The mesh above is as rough as its maps and carries a closed blob for every wrong pixel that survived the filter.  These calls
+ * finish it where it lies, on the same stream with no host round trip: the connected components with few triangles are dropped,
+ * the rest is smoothed without shrinking (Taubin's lambda | mu on fixed-point positions) and takes its normals from the smoothed
+ * triangles.  Integers wherever a sum is taken (so no order of execution changes a bit; int64 arithmetic wraps in two's
+ * complement), float64 elsewhere, one IEEE operation at a time in the order written, nothing contracted: bit-identical to a numpy
+ * restatement (tests/mesh_clean_ref.py).  Not in the C# reference.  k_meshclean.hip.
+ *
+ * pgx_mesh_clean_dev.
+ * Inputs.  The outputs of pgx_mesh_dev, read where they lie: d_xyz [max_vertices][3] float64, d_normal [max_vertices][3] float32,
+ * d_rgba8 [max_vertices] uint32, d_info [max_vertices][4] int32, d_tri [max_tris][3] int32; any mesh in that layout.  d_counts int32
+ * [8] on the device or NULL (pgx_mesh_dev's d_report fits): nv = min(max(d_counts[5], 0), max_vertices),
+ * nt = min(max(d_counts[6], 0), max_tris), or the capacities with NULL; both are read on the device.  The grid of the fixed-point
+ * positions: cell, o = (ox, oy, oz), normally the mesh's.  min_tris >= 1, min_frac_pm in [0, 1000], iters in [0, 64], lambda in
+ * (0, 1], mu in [-1.5, 0].
+ *   1 valid, used  vertex v < nv is VALID iff its three coordinates are finite and t_a = (X_a - o_a) / cell satisfies
+ *               -2^20 <= t_a < 2^20 on every axis; its fixed-point position is q_a = (int64) floor(t_a * 65536.0 + 0.5).  Triangle
+ *               k < nt is USED iff its three indices are in [0, nv), pairwise distinct, and its three vertices are valid (this
+ *               disposes of the indices at or past max_vertices that pgx_mesh_dev writes after a capacity overflow).
+ *   2 components   two vertices are connected when a used triangle holds both; a component is named by its smallest vertex.
+ *               cnt(C) = its used triangles, big = the largest cnt (0 without a used triangle).  A component is KEPT iff
+ *               cnt >= min_tris and 1000 cnt >= min_frac_pm big, in int64.  A vertex in no used triangle is dropped.  A vertex
+ *               is KEPT iff it is in a used triangle and its component is kept, a triangle iff it is used and its component is
+ *               kept.
+ *   3 smoothing    only with iters > 0: iters times the half-step with f = lambda, then (unless mu == 0) the half-step with f = mu.
+ *               A half-step, for every kept vertex v with d kept triangles that hold it, from the values before the half-step
+ *               (Jacobi): D_a = the int64 sum over those triangles of (q_a[o1] - q_a[v]) + (q_a[o2] - q_a[v]), o1 and o2 the
+ *               triangle's two other vertices (an edge shared by two triangles counts twice, a boundary edge once: this is the
+ *               rule);  r = floor((f * (double) D_a) / (double)(2 d) + 0.5), the conversion of D_a rounding to nearest, r clamped
+ *               to [-2^62, 2^62];  q'_a = q_a + (int64) r.
+ *   4 normals      only with iters > 0, on the final q.  Per kept triangle (a, b, c): e1 = (double)(q[b] - q[a]),
+ *               e2 = (double)(q[c] - q[a]) per axis (the differences in int64); n = e1 x e2, each component x y - z w as in rule 2
+ *               of pgx_cloud_merge_dev: n_0 = e1_1 e2_2 - e1_2 e2_1, n_1 = e1_2 e2_0 - e1_0 e2_2, n_2 = e1_0 e2_1 - e1_1 e2_0;
+ *               L = sqrt((n_0 n_0 + n_1 n_1) + n_2 n_2).  The triangle contributes nothing when L is 0 or not finite; otherwise
+ *               m_a = (int) floor((n_a / L) * 32767.0 + 0.5).  Per kept vertex s_a = the int64 sum of m_a over the kept triangles
+ *               that hold it, x_a = (double) s_a, L' = sqrt((x_0 x_0 + x_1 x_1) + x_2 x_2); the normal is (float)(x_a / L'), zeros
+ *               when L' is 0.  pgx_mesh_dev's winding faces free space, so these normals do.
+ *   5 output       the kept vertices in ascending old index, the kept triangles in ascending old index with their vertices' new
+ *               indices in the old order (the winding stays).  iters == 0: xyz and normal are copied bit for bit; otherwise
+ *               xyz_a = o_a + ((double) q_a / 65536.0) * cell and the normal of rule 4.  rgba8 and info are always copied.
+ * Outputs.  d_out_xyz [max_out_vertices][3] float64, d_out_normal [max_out_vertices][3] float32, d_out_rgba8 [max_out_vertices]
+ * uint32, d_out_info [max_out_vertices][4] int32, d_out_tri [max_out_tris][3] int32 (full new indices, also at or past
+ * max_out_vertices).  Optional: d_vertex_map [max_vertices] int32 = the new index (the full one), -1 for a vertex that is not
+ * valid or in no used triangle, -2 for one of a dropped component; d_comp [max_vertices] int32 = the name of the vertex's
+ * component, -1 where vertex_map is -1.  Rows >= nv of both are not written.
+ * d_report [8] int32: nv, nt, used triangles, components, components kept, vertices out (the full count), triangles out (the
+ * full count), big.  More vertices or triangles kept than the capacity: the first ones are written and pgx_check_status reports
+ * PGX_E_CAPACITY.
+ * Returned at once (PGX_E_BADARG), with nothing written: max_vertices, max_tris, max_out_vertices or max_out_tris outside
+ * [0, 2^28], cell not finite or <= 0, an origin that is not finite, min_tris < 1, min_frac_pm outside [0, 1000], iters outside
+ * [0, 64], lambda not finite or outside (0, 1], mu not finite or outside [-1.5, 0], null required pointers (the four vertex inputs
+ * may be NULL with max_vertices == 0, d_tri with max_tris == 0, the four vertex outputs with max_out_vertices == 0, d_out_tri with
+ * max_out_tris == 0), an output that overlaps an input.
+ * Workspace: 81 bytes per entry of max_vertices, 25 bytes per entry of max_tris, 32 bytes per block of 256 entries of the
+ * larger of the two; sized and carved before any launch.
+ * Results depend on the inputs only: the same bits from run to run, on a used workspace and from the host form; a permuted
+ * triangle list gives the same vertices, and the same triangles in the new order.
+ * Asynchronous on the context's stream. */
+int pgx_mesh_clean_dev(pgx_ctx *ctx, const double *d_xyz /* [max_vertices][3] */, const float *d_normal /* [max_vertices][3] */,
+                       const uint32_t *d_rgba8 /* [max_vertices] */, const int32_t *d_info /* [max_vertices][4] */,
+                       const int32_t *d_tri /* [max_tris][3] */, const int32_t *d_counts /* [8] or NULL */, int max_vertices,
+                       int max_tris, double cell, double ox, double oy, double oz, int min_tris, int min_frac_pm, int iters,
+                       double lambda, double mu, int max_out_vertices, int max_out_tris,
+                       double *d_out_xyz /* [max_out_vertices][3] */, float *d_out_normal /* [max_out_vertices][3] */,
+                       uint32_t *d_out_rgba8 /* [max_out_vertices] */, int32_t *d_out_info /* [max_out_vertices][4] */,
+                       int32_t *d_out_tri /* [max_out_tris][3] */, int32_t *d_vertex_map /* [max_vertices] or NULL */,
+                       int32_t *d_comp /* [max_vertices] or NULL */, int32_t *d_report /* [8] */);
+/* Host form: host arrays in the layouts above, the same kernels; it returns when the results are in the caller's buffers.  The
+ * mesh has n_vertices vertices and n_tris triangles (no d_counts); vertex_map and comp may be NULL; the report is downloaded
+ * first, then min(report[5], max_out_vertices) rows of the four vertex outputs and min(report[6], max_out_tris) triangles. */
+int pgx_mesh_clean(pgx_ctx *ctx, const double *xyz, const float *normal, const uint32_t *rgba8, const int32_t *info,
+                   const int32_t *tri, int n_vertices, int n_tris, double cell, double ox, double oy, double oz, int min_tris,
+                   int min_frac_pm, int iters, double lambda, double mu, int max_out_vertices, int max_out_tris, double *out_xyz,
+                   float *out_normal, uint32_t *out_rgba8, int32_t *out_info, int32_t *out_tri, int32_t *vertex_map, int32_t *comp,
+                   int32_t *report);
+
 /* ---- measurement hooks (bench.py) ---------------------------------------------------- */
 /* When on, the named hot kernels are bracketed by HIP events on the launch stream. */
 int pgx_profile_enable(pgx_ctx *ctx, int on);

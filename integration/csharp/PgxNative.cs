@@ -318,6 +318,25 @@ internal static unsafe class PgxNative
                                                        double* outXyz, float* outNormal, uint* outRgba8, int* outInfo, int* outTri,
                                                        int* report);
 
+    // the mesh cleaned where it lies (not in the managed implementation): the outputs of pgx_mesh_dev and, as dCounts, its report
+    // (or null: the capacities) -> the components with fewer than minTris triangles or fewer than minFracPm / 1000 of the
+    // largest one's dropped, iters Taubin steps (lambda, mu), normals from the smoothed triangles: dOutXyz .. dOutTri as the
+    // mesh's, dVertexMap [maxVertices] and dComp [maxVertices] int32 or null, dReport [8] ([5] vertices, [6] triangles out).
+    // The host form takes host arrays in the same layouts
+    [DllImport(Lib)] public static extern int pgx_mesh_clean_dev(IntPtr ctx, void* dXyz, void* dNormal, void* dRgba8, void* dInfo,
+                                                                 void* dTri, void* dCounts, int maxVertices, int maxTris, double cell,
+                                                                 double ox, double oy, double oz, int minTris, int minFracPm,
+                                                                 int iters, double lambda, double mu, int maxOutVertices,
+                                                                 int maxOutTris, void* dOutXyz, void* dOutNormal, void* dOutRgba8,
+                                                                 void* dOutInfo, void* dOutTri, void* dVertexMap, void* dComp,
+                                                                 void* dReport);
+    [DllImport(Lib)] public static extern int pgx_mesh_clean(IntPtr ctx, double* xyz, float* normal, uint* rgba8, int* info, int* tri,
+                                                             int nVertices, int nTris, double cell, double ox, double oy, double oz,
+                                                             int minTris, int minFracPm, int iters, double lambda, double mu,
+                                                             int maxOutVertices, int maxOutTris, double* outXyz, float* outNormal,
+                                                             uint* outRgba8, int* outInfo, int* outTri, int* vertexMap, int* comp,
+                                                             int* report);
+
     /// <summary>Maps a status code back to the exception type the managed implementation throws.</summary>
     public static void Check(IntPtr ctx, int rc)
     {

@@ -920,6 +920,54 @@ class Engine:
         kv, kt = min(int(report[5]), nv), min(int(report[6]), nt)
         return dict(xyz=oxyz[:kv], normal=onrm[:kv], rgba8=orgb[:kv], info=oinf[:kv], tri=otri[:kt], report=report)
 
+    # -- the mesh cleaned: small components dropped, smoothed, normals again (pgx_mesh_clean*) ---------------------
+    def mesh_clean_dev(self, d_xyz, d_normal, d_rgba8, d_info, d_tri, d_counts, max_vertices, max_tris, cell, origin,
+                       max_out_vertices, max_out_tris, d_out_xyz, d_out_normal, d_out_rgba8, d_out_info, d_out_tri, d_report,
+                       min_tris=1, min_frac_pm=0, iters=0, lam=0.5, mu=-0.53, d_vertex_map=None, d_comp=None):
+        """pgx_mesh_clean_dev: the mesh d_xyz .. d_tri as mesh_dev writes it (d_counts int32 [8] on the device, mesh_dev's
+        d_report, or None: the capacities) without the components of fewer than min_tris triangles or fewer than
+        min_frac_pm / 1000 of the largest one's, after `iters` Taubin steps (lam, mu) on the grid of `cell` at `origin`, with the
+        normals of the smoothed triangles: d_out_xyz [max_out_vertices][3] float64, d_out_normal [max_out_vertices][3] float32,
+        d_out_rgba8 [max_out_vertices] uint32, d_out_info [max_out_vertices][4] int32, d_out_tri [max_out_tris][3] int32,
+        d_report [8] int32 ([5] vertices, [6] triangles out); d_vertex_map and d_comp [max_vertices] int32 or None.  A capacity
+        exceeded: CapacityError from check_status.  No sync."""
+        ox, oy, oz = (float(x) for x in origin)
+        self._chk(self._L.pgx_mesh_clean_dev(
+            self._h, _dptr(d_xyz), _dptr(d_normal), _dptr(d_rgba8), _dptr(d_info), _dptr(d_tri), _dptr(d_counts), int(max_vertices),
+            int(max_tris), float(cell), ox, oy, oz, int(min_tris), int(min_frac_pm), int(iters), float(lam), float(mu),
+            int(max_out_vertices), int(max_out_tris), _dptr(d_out_xyz), _dptr(d_out_normal), _dptr(d_out_rgba8), _dptr(d_out_info),
+            _dptr(d_out_tri), _dptr(d_vertex_map), _dptr(d_comp), _dptr(d_report)))
+
+    def mesh_clean(self, xyz, normal, rgba8, info, tri, cell, origin, min_tris=1, min_frac_pm=0, iters=0, lam=0.5, mu=-0.53,
+                   max_out_vertices=None, max_out_tris=None, vertex_map=True, comp=True):
+        """The host form (pgx_mesh_clean).  xyz [n][3] float64, normal [n][3] float32, rgba8 [n] uint32, info [n][4] int32 and tri
+        [t][3] int32 as mesh returns them -> dict(xyz [m][3], normal [m][3] float32, rgba8 [m], info [m][4], tri [k][3] int32
+        trimmed to the counts of the report, vertex_map [n], comp [n] or None, report [8]).  The capacities default to n and t
+        (they can then not be exceeded); a smaller one that cuts the mesh raises CapacityError."""
+        X = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+        n = len(X)
+        N = np.ascontiguousarray(normal, dtype=np.float32).reshape(n, 3)
+        col = np.ascontiguousarray(rgba8, dtype=np.uint32).reshape(n)
+        inf = np.ascontiguousarray(info, dtype=np.int32).reshape(n, 4)
+        T = np.ascontiguousarray(tri, dtype=np.int32).reshape(-1, 3)
+        t = len(T)
+        nv = n if max_out_vertices is None else int(max_out_vertices)
+        nt = t if max_out_tris is None else int(max_out_tris)
+        mv, mt = max(nv, 1), max(nt, 1)
+        oxyz, onrm = np.zeros((mv, 3)), np.zeros((mv, 3), dtype=np.float32)
+        orgb, oinf, otri = np.zeros(mv, dtype=np.uint32), np.zeros((mv, 4), dtype=np.int32), np.zeros((mt, 3), dtype=np.int32)
+        vm = np.zeros(max(n, 1), dtype=np.int32) if vertex_map else None
+        cp = np.zeros(max(n, 1), dtype=np.int32) if comp else None
+        report = np.zeros(8, dtype=np.int32)
+        ox, oy, oz = (float(x) for x in origin)
+        self._chk(self._L.pgx_mesh_clean(
+            self._h, _ptr(X) if n else None, _ptr(N) if n else None, _ptr(col) if n else None, _ptr(inf) if n else None,
+            _ptr(T) if t else None, n, t, float(cell), ox, oy, oz, int(min_tris), int(min_frac_pm), int(iters), float(lam), float(mu),
+            nv, nt, _ptr(oxyz), _ptr(onrm), _ptr(orgb), _ptr(oinf), _ptr(otri), _ptr(vm), _ptr(cp), _ptr(report)))
+        kv, kt = min(int(report[5]), nv), min(int(report[6]), nt)
+        return dict(xyz=oxyz[:kv], normal=onrm[:kv], rgba8=orgb[:kv], info=oinf[:kv], tri=otri[:kt],
+                    vertex_map=None if vm is None else vm[:n], comp=None if cp is None else cp[:n], report=report)
+
     # -- multi-GPU: the context's own RCCL communicator (pgx_comm_*) ------------------------------
     def comm_init(self, rank, world, unique_id):
         """Collective: every rank calls this with the 128 bytes rank 0 got from comm_unique_id()."""

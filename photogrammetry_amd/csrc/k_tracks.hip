@@ -31,7 +31,7 @@
 //                  segments are short: <= n_frames)
 // Same-address atomics serialise at about 10 ns each on this part: one global counter of the edges used cost 1.3 ms per launch
 // (130 k wavefront atomics), per-node atomicAdds on the junk component's root 0.56 ms -- hence the LDS stages and TRK_ECNT.
-#include "pgx_trackgraph.h"   // block_excl_scan
+#include "pgx_trackgraph.h"   // block_excl_scan, trk_find, trk_hook
 
 namespace {
 
@@ -67,32 +67,8 @@ struct TrkArgs {
     int32_t *track_of, *offsets, *nodes, *summary;
 };
 
-__device__ __forceinline__ int ld(const int32_t *p)
-{
-    // a plain load the compiler may not cache in a register across the loops below (no cache-bypass bits at this scope)
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-}
-__device__ __forceinline__ void st(int32_t *p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); }
-
+// trk_ld, trk_find and trk_hook, the lock-free union-find, are pgx_trackgraph.h's: k_meshclean.hip joins vertices with them
 __device__ __forceinline__ uint32_t trk_prio(int x) { return (uint32_t)x * 2654435761u; }   // a bijection on 32 bits: no ties
-
-// Root of x with intermediate pointer jumping.  Invariant: prio(parent[v]) < prio(v) unless v is a root (parent[v] == v), and
-// parent[v] only ever moves to an ancestor of v.  A value read here may be STALE (another XCD's L2, this CU's L1): every
-// earlier value of parent[v] is v itself or an ancestor, so a walk over stale values still descends in priority (it ends), and
-// a stale read can only name a node that is no longer a root -- the caller's atomicCAS then fails and returns the truth.
-__device__ __forceinline__ int trk_find(int32_t *parent, int x)
-{
-    int curr = ld(parent + x);
-    if (curr != x) {
-        int prev = x, next;
-        while (curr != (next = ld(parent + curr))) {
-            st(parent + prev, next);
-            prev = curr;
-            curr = next;
-        }
-    }
-    return curr;
-}
 
 __device__ __forceinline__ int fid_of(const TrkArgs &a, int slot) { return a.frame_ids ? a.frame_ids[slot] : slot; }
 
@@ -150,13 +126,7 @@ __global__ __launch_bounds__(TRK_NT) void k_trk_union(TrkArgs a, long long n_ite
         const unsigned long long bal = __ballot(edge);
         mine += __popcll(bal);
         if (!edge) continue;
-        int ru = trk_find(a.parent, u), rv = trk_find(a.parent, v);
-        while (ru != rv) {
-            if (trk_prio(ru) < trk_prio(rv)) { const int t = ru; ru = rv; rv = t; }   // ru hooks under rv
-            const int old = atomicCAS(a.parent + ru, ru, rv);
-            if (old == ru) break;
-            ru = trk_find(a.parent, old);   // ru was no root any more: go on from the root above its true parent
-        }
+        trk_hook(a.parent, u, v, [](int x) { return trk_prio(x); });
     }
     // edges used: through LDS into one of TRK_ECNT slots (same-address atomics serialise); k_trk_scan_sums adds them up
     __shared__ int n_edges;
@@ -400,7 +370,7 @@ __global__ __launch_bounds__(TRK_NT) void k_trks_prep(TrkArgs a, SplitArgs s)
 // grid: F * ceil(stride / TRK_NT), as k_trk_flatten
 __global__ __launch_bounds__(TRK_NT) void k_trks_mark(TrkArgs a, SplitArgs sp, int level, int last)
 {
-    if (level > 0 && ld(sp.live + level - 1) == 0) return;   // uniform: nothing was left unresolved
+    if (level > 0 && trk_ld(sp.live + level - 1) == 0) return;   // uniform: nothing was left unresolved
     const int chunks = (a.stride + TRK_NT - 1) / TRK_NT;
     const int s = blockIdx.x / chunks, k = (blockIdx.x % chunks) * TRK_NT + threadIdx.x;
     const int f = fid_of(a, s);
@@ -441,7 +411,7 @@ __global__ __launch_bounds__(TRK_NT) void k_trks_mark(TrkArgs a, SplitArgs sp, i
 // between level `level` and the next one; grid-stride over the nodes and the per-frame tables
 __global__ __launch_bounds__(TRK_NT) void k_trks_reset(TrkArgs a, SplitArgs sp, int level)
 {
-    if (ld(sp.live + level) == 0) return;
+    if (trk_ld(sp.live + level) == 0) return;
     const long long nthreads = (long long)gridDim.x * TRK_NT;
     const long long t0 = (long long)blockIdx.x * TRK_NT + threadIdx.x;
     for (long long x = t0; x < a.N; x += nthreads) {
@@ -459,17 +429,11 @@ __global__ __launch_bounds__(TRK_NT) void k_trks_reset(TrkArgs a, SplitArgs sp, 
 // (summary[4] is |E_0|)
 __global__ __launch_bounds__(TRK_NT) void k_trks_union(TrkArgs a, SplitArgs sp, int level, long long n_items)
 {
-    if (ld(sp.live + level - 1) == 0) return;
+    if (trk_ld(sp.live + level - 1) == 0) return;
     for (long long item = blockIdx.x; item < n_items; item += gridDim.x) {
         int u = 0, v = 0;
         if (!trk_edge(a, item, u, v) || !sp.active[u]) continue;
-        int ru = trk_find(a.parent, u), rv = trk_find(a.parent, v);
-        while (ru != rv) {
-            if (trk_prio(ru) < trk_prio(rv)) { const int t = ru; ru = rv; rv = t; }
-            const int old = atomicCAS(a.parent + ru, ru, rv);
-            if (old == ru) break;
-            ru = trk_find(a.parent, old);
-        }
+        trk_hook(a.parent, u, v, [](int x) { return trk_prio(x); });
     }
 }
 
@@ -477,7 +441,7 @@ __global__ __launch_bounds__(TRK_NT) void k_trks_flatten(TrkArgs a, SplitArgs sp
 {
     __shared__ uint32_t hkey[FL_SLOTS];
     __shared__ int hcnt[FL_SLOTS], hmin[FL_SLOTS];
-    if (ld(sp.live + level - 1) == 0) return;
+    if (trk_ld(sp.live + level - 1) == 0) return;
     trk_flatten(a, sp.active, hkey, hcnt, hmin);
 }
 

@@ -1,5 +1,5 @@
 // pgx_stage_args.h -- the arguments of the stages behind the matchers, each as the struct its kernels take by value:
-// triangulation, bundle adjustment, registration, consensus, verification, initial pair, depth maps, depth fuse, dense views, cloud merge, mesh.  The C ABI's
+// triangulation, bundle adjustment, registration, consensus, verification, initial pair, depth maps, depth fuse, dense views, cloud merge, mesh, mesh clean.  The C ABI's
 // two forms of a stage (pgx_api.hip) fill "the caller fills" by name and hand the struct to run_X; the launcher carves the
 // workspace into the rest and launches.  The layout IS the kernarg layout: fields, order and types are the kernels' (the
 // capitals in the shapes are constants of the stage's .hip file).  Internal to libpgx.so; DESIGN.md section 14h.
@@ -335,3 +335,50 @@ struct MeshArgs {
 };
 size_t pgx_mesh_ws_bytes(const MeshArgs &a);
 void pgx_launch_mesh(pgx_ctx *ctx, hipStream_t s, MeshArgs a, void *ws);
+
+// ---- k_meshclean.hip (the mesh cleaned: small components dropped, Taubin smoothing, normals again; pgx_mesh_clean_dev semantics) ---
+// ctx: the profiling groups mclean_init / mclean_union / mclean_count / mclean_rank / mclean_emit / mclean_rows / mclean_smooth /
+// mclean_normals
+struct MeshCleanArgs {
+    // the caller fills
+    const double *xyz;            // [max_vertices][3]
+    const float *normal;          // [max_vertices][3]
+    const uint32_t *rgba8;        // [max_vertices]
+    const int32_t *info;          // [max_vertices][4]
+    const int32_t *tri;           // [max_tris][3]
+    const int32_t *counts;        // [5] = the vertices, [6] = the triangles (pgx_mesh_dev's report), or nullptr: the capacities
+    int max_vertices, max_tris;
+    double cell, ox, oy, oz, lambda, mu;
+    int min_tris, min_frac_pm, iters, max_out_vertices, max_out_tris;
+    double *out_xyz;              // [max_out_vertices][3]
+    float *out_normal;            // [max_out_vertices][3]
+    uint32_t *out_rgba8;          // [max_out_vertices]
+    int32_t *out_info;            // [max_out_vertices][4]
+    int32_t *out_tri;             // [max_out_tris][3]
+    int32_t *vertex_map;          // [max_vertices] or nullptr
+    int32_t *comp;                // [max_vertices] or nullptr
+    int32_t *report;              // [8]
+    // the launcher fills (workspace, derived)
+    int32_t *parent;              // [max_vertices]: the union-find
+    int32_t *root;                // [max_vertices]: the root of a vertex of a used triangle, -1 otherwise
+    int32_t *rep;                 // [max_vertices]: at a root, the smallest vertex of its component: its name
+    int32_t *tcnt;                // [max_vertices]: at a root, the used triangles of its component
+    int32_t *deg;                 // [max_vertices]: the used triangles that hold the vertex
+    int32_t *vnew;                // [max_vertices]: the new index, -1, -2 as vertex_map
+    int32_t *roff;                // [max_vertices]: where the row of a kept vertex begins
+    int32_t *cursor;              // [max_vertices]: the entries of the row filled so far
+    long long *qa, *qb;           // [max_vertices][3] each: the fixed-point positions, the two buffers of the half-steps
+    unsigned char *vvalid;        // [max_vertices]
+    unsigned char *tused;         // [max_tris]
+    int32_t *tnew;                // [max_tris]: the new index of a kept triangle, -1 otherwise
+    int32_t *rows;                // [3 max_tris]: per kept vertex the kept triangles that hold it, in no order (iters > 0)
+    unsigned long long *tnrm;     // [max_tris]: m of rule 4, 16 bits a component; MCL_NONRM = the triangle contributes nothing
+    unsigned long long *bsum, *boff;   // [nb]: kept vertices | kept triangles << 32 per block of 256 indices, their exclusive scan
+    unsigned long long *rsum, *rbase;  // [nb]: row entries per block, their exclusive scan
+    int32_t *meta;                // [0] nv, [1] nt, [2] used, [3] components, [4] kept, [5] vertices out, [6] triangles out, [7] big
+    int nb;                       // blocks of 256 indices of max(max_vertices, max_tris)
+    // the caller fills
+    int *status;                  // an output capacity exceeded: PGX_ST_MCL_CAP
+};
+size_t pgx_mesh_clean_ws_bytes(const MeshCleanArgs &a);
+void pgx_launch_mesh_clean(pgx_ctx *ctx, hipStream_t s, MeshCleanArgs a, void *ws);

@@ -1,7 +1,8 @@
 // pgx_trackgraph.h -- what every consumer of the track graph shares (k_triangulate.hip, k_bundle.hip, k_register.hip, k_consensus.hip):
 // the read-only view of the graph and the keypoints, its validation and walking on the device, the lane-group and
 // workgroup reductions (k_verify.hip uses those too), the workgroup scan (k_tracks.hip, k_consensus.hip and k_vocab.hip compact
-// with it), and the workspace carver of the launchers.  It brings pgx_ransac.h along,
+// with it), the lock-free union-find (k_tracks.hip, k_meshclean.hip), and the workspace carver of the launchers.  It brings
+// pgx_ransac.h along,
 // the sampler and the keys of the RANSAC stages among its consumers.  Internal to libpgx.so; DESIGN.md section 14a.
 #pragma once
 
@@ -159,6 +160,47 @@ template <class T, int NT> __device__ __forceinline__ T block_excl_scan(T v, T *
     __syncthreads();
     total = tot;
     return base + inc - v;
+}
+
+// ---- lock-free union-find with hashed priorities (k_tracks.hip: keypoints joined by matches; k_meshclean.hip: vertices joined
+// by triangles).  The priority prio(x), a bijection on the ids so that there are no ties, is the graph's own (trk_prio, mcl_prio) --
+
+__device__ __forceinline__ int trk_ld(const int32_t *p)
+{
+    // a plain load the compiler may not cache in a register across the loops below (no cache-bypass bits at this scope)
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+}
+__device__ __forceinline__ void trk_st(int32_t *p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); }
+
+// Root of x with intermediate pointer jumping.  Invariant: prio(parent[v]) < prio(v) unless v is a root (parent[v] == v), and
+// parent[v] only ever moves to an ancestor of v.  A value read here may be STALE (another XCD's L2, this CU's L1): every
+// earlier value of parent[v] is v itself or an ancestor, so a walk over stale values still descends in priority (it ends), and
+// a stale read can only name a node that is no longer a root -- the caller's atomicCAS then fails and returns the truth.
+__device__ __forceinline__ int trk_find(int32_t *parent, int x)
+{
+    int curr = trk_ld(parent + x);
+    if (curr != x) {
+        int prev = x, next;
+        while (curr != (next = trk_ld(parent + curr))) {
+            trk_st(parent + prev, next);
+            prev = curr;
+            curr = next;
+        }
+    }
+    return curr;
+}
+
+// The trees of u and v become one: RANDOM linking -- of two roots the one with the larger hashed id hooks under the other, by an
+// atomicCAS on a root only.  A CAS that fails returns the root's true parent: the walk goes on from the root above it.
+template <class Prio> __device__ __forceinline__ void trk_hook(int32_t *parent, int u, int v, Prio prio)
+{
+    int ru = trk_find(parent, u), rv = trk_find(parent, v);
+    while (ru != rv) {
+        if (prio(ru) < prio(rv)) { const int t = ru; ru = rv; rv = t; }   // ru hooks under rv
+        const int old = atomicCAS(parent + ru, ru, rv);
+        if (old == ru) break;
+        ru = trk_find(parent, old);   // ru was no root any more: go on from the root above its true parent
+    }
 }
 
 // ---- cameras ----------------------------------------------------------------------------------------------------------

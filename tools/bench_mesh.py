@@ -2,7 +2,9 @@
 frames on a line, the filter's list of their depth maps (a smooth synthetic surface seen by every camera) meshed at a cell of
 --cell-scale pixel footprints, band 1, truncation 3 cells.  Timed with HIP events on geom_bench's loop: the whole pgx_mesh_dev
 call, and the whole pgx_cloud_merge_dev call on the same list for scale; then the mesh by pass from the stage's profiling groups
-(pgx_profile_get) in a second pass.  Writes profiles/mesh_<shape>.json (or --out DIR)."""
+(pgx_profile_get) in a second pass.  With --clean, pgx_mesh_clean_dev on the mesh's outputs and report:
+the whole call without smoothing and with --clean-iters iterations, and its passes as medians over the calls (one profile read
+per call).  Writes profiles/mesh_<shape>.json, with --clean profiles/mesh_clean_<shape>.json (or --out DIR)."""
 import argparse
 import os
 import sys
@@ -18,7 +20,42 @@ from bench_cloud import surface_depths  # noqa: E402
 from bench_depth import cameras  # noqa: E402
 from geom_bench import DEV, F64, I32  # noqa: E402
 
+CLEAN_PARTS = ("mclean_init", "mclean_union", "mclean_count", "mclean_rank", "mclean_emit", "mclean_rows", "mclean_smooth", "mclean_normals")
 PARTS = ("mesh_plan", "mesh_seed", "mesh_dilate", "mesh_tsdf", "mesh_cubes", "mesh_rank", "mesh_vertices", "mesh_tris")
+
+
+def bench_clean(eng, args, mesh_out, rep, nv, nt, cell, origin):
+    """pgx_mesh_clean_dev on the mesh's outputs where they lie, the counts from the mesh's report on the device -> the record"""
+    oxyz, onrm, orgb, oinf, otri = mesh_out
+    cx, cn = torch.empty((max(nv, 1), 3), **F64), torch.empty((max(nv, 1), 3), dtype=torch.float32, device=DEV)
+    cc, ci, ct, crep = torch.empty(max(nv, 1), **I32), torch.empty((max(nv, 1), 4), **I32), torch.empty((max(nt, 1), 3), **I32), torch.empty(8, **I32)
+    out = {}
+    for name, iters in (("iters0", 0), ("iters%d" % args.clean_iters, args.clean_iters)):
+        def clean():
+            eng.mesh_clean_dev(oxyz, onrm, orgb, oinf, otri, rep, nv, nt, cell, origin, nv, nt, cx, cn, cc, ci, ct, crep,
+                               min_tris=args.min_tris, iters=iters, lam=0.5, mu=-0.53)
+        ms = gb.time_on_stream(eng, clean, args.steps, args.warmup)
+        eng.profile_enable(True)
+        per = {p: [] for p in CLEAN_PARTS}
+        for _ in range(args.steps):
+            eng.profile_reset()
+            clean()
+            for p in CLEAN_PARTS:
+                per[p].append(eng.profile_get(p)[1])
+        eng.profile_enable(False)
+        eng.check_status()
+        parts = {p: round(float(np.median(v)), 4) for p, v in per.items()}
+        half = 2 * iters
+        # what a half-step must move: per kept vertex its row (4 B an entry, 3 entries a triangle in all), per entry a triangle
+        # (12 B) and three positions (72 B) that mostly hit in cache, one position read and one written (48 B)
+        r = crep.cpu().tolist()
+        floor_bytes = r[6] * 3 * 4 + r[6] * 12 + r[5] * 24 * 2
+        out[name] = dict(iters=iters, ms_median=float(np.median(ms)), ms_min=float(ms.min()), ms_max=float(ms.max()), parts_ms=parts,
+                         report=r, half_step_ms=(parts["mclean_smooth"] / half if half else None),
+                         half_step_floor_bytes=floor_bytes,
+                         half_step_gbps=(floor_bytes / (parts["mclean_smooth"] / half * 1e-3) / 1e9 if half and parts["mclean_smooth"] > 0 else None),
+                         union_ns_per_triangle=parts["mclean_union"] * 1e6 / max(r[1], 1))
+    return out
 
 
 def main():
@@ -33,6 +70,9 @@ def main():
     ap.add_argument("--band", type=int, default=1)
     ap.add_argument("--trunc-cells", type=int, default=3)
     ap.add_argument("--max-voxels", type=int, default=1 << 25)
+    ap.add_argument("--clean", action="store_true", help="also time pgx_mesh_clean_dev behind the mesh")
+    ap.add_argument("--clean-iters", type=int, default=5)
+    ap.add_argument("--min-tris", type=int, default=100)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles"))
     args = ap.parse_args()
     assert args.steps >= 7, "the median of at least 7 calls"
@@ -84,7 +124,9 @@ def main():
                input_points=report[0], seed_cells=report[2], voxels=report[3], valid_voxels=report[4], vertices=report[5],
                triangles=report[6], max_voxels=mvox, voxels_per_s=report[3] / (med * 1e-3),
                cloud_merge_ms_median=float(np.median(ms_merge)), cloud_report=crep.cpu().tolist(), fuse_summary=fsum.cpu().tolist())
-    gb.write_record(rec, args.out, "mesh")
+    if args.clean:
+        rec["clean"] = bench_clean(eng, args, (oxyz, onrm, orgb, oinf, otri), rep, report[5], report[6], cell, origin)
+    gb.write_record(rec, args.out, "mesh_clean" if args.clean else "mesh")
     eng.close()
 
 

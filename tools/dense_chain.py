@@ -3,7 +3,9 @@ pgx_gray_batch_dev -> pgx_depth_maps_dev -> pgx_depth_fuse_dev -> pgx_rgba8_batc
 no synchronisation between the triangulation and the merged cloud.  The scene is synth.make_scene's (frames on an arc, true tracks cut to runs); the frames are
 seeded noise, so the maps carry no meaning: the tool shows that the chain runs and what it costs.  Timed with HIP events on
 geom_bench's loop; prints one JSON line and writes profiles/dense_chain_<shape>.json (or --out DIR).  --mesh adds pgx_mesh_dev
-behind the cloud and writes profiles/dense_chain_mesh_<shape>.json; the default run is the chain above."""
+behind the cloud and writes profiles/dense_chain_mesh_<shape>.json; --mesh --clean adds pgx_mesh_clean_dev
+behind the mesh on the same stream (the mesh's outputs and its report on the device, no wait between them),
+its time as clean_ms in the record dense_chain_mesh_clean_<shape>.json; the default run is the chain above."""
 import argparse
 import os
 import sys
@@ -20,6 +22,7 @@ from geom_bench import DEV, F64, I32  # noqa: E402
 PARTS = ("triangulate", "dense_views_nodes", "dense_views_pairs", "dense_views_select", "dewarp_gray", "depth_census", "depth_plan",
          "depth_sweep", "depth_fuse", "dewarp_rgba8", "cloud_plan", "cloud_normals", "cloud_points", "cloud_rank", "cloud_accum",
          "cloud_final")
+CLEAN_PARTS = ("mclean_init", "mclean_union", "mclean_count", "mclean_rank", "mclean_emit", "mclean_rows", "mclean_smooth", "mclean_normals")
 MESH_PARTS = ("mesh_plan", "mesh_seed", "mesh_dilate", "mesh_tsdf", "mesh_cubes", "mesh_rank", "mesh_vertices", "mesh_tris")
 
 
@@ -35,8 +38,11 @@ def main():
     ap.add_argument("--planes", type=int, default=64)
     ap.add_argument("--cell", type=float, default=0.02)
     ap.add_argument("--mesh", action="store_true", help="pgx_mesh_dev behind the cloud (band 2, truncation 3 cells); the record is dense_chain_mesh_*")
+    ap.add_argument("--clean", action="store_true", help="with --mesh: pgx_mesh_clean_dev behind the mesh (min_tris 100, --clean-iters Taubin steps); the record is dense_chain_mesh_clean_*")
+    ap.add_argument("--clean-iters", type=int, default=5)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles"))
     args = ap.parse_args()
+    assert args.mesh or not args.clean, "--clean cleans the mesh: give --mesh too"
     W, H, nf, S, D = args.width, args.height, args.frames, args.sources, args.planes
     rng = np.random.default_rng(0)
     eng = pg.Engine(0)
@@ -61,6 +67,10 @@ def main():
         agr = torch.empty((nf, H, W), **I32)
         mxyz, mnrm = torch.empty((mv, 3), **F64), torch.empty((mv, 3), dtype=torch.float32, device=DEV)
         mrgb, minf, mtri, mrep = torch.empty(mv, **I32), torch.empty((mv, 4), **I32), torch.empty((mt, 3), **I32), torch.empty(8, **I32)
+    if args.clean:
+        parts_of = parts_of + CLEAN_PARTS
+        cxyz, cnrm = torch.empty((mv, 3), **F64), torch.empty((mv, 3), dtype=torch.float32, device=DEV)
+        crgb, cinf, ctri, clrep = torch.empty(mv, **I32), torch.empty((mv, 4), **I32), torch.empty((mt, 3), **I32), torch.empty(8, **I32)
     torch.cuda.synchronize()
 
     def chain():
@@ -75,6 +85,9 @@ def main():
         if args.mesh:
             eng.mesh_dev(pts, src, fsum, cap, dep, views, nf, S, W, H, nf, d["P"], args.cell, origin, mvox, mv, mt, mxyz, mnrm, mrgb, minf,
                          mtri, mrep, d_agree=agr, min_agree=2, d_rgba8=col, F=nf, band=2, trunc_cells=3)
+        if args.clean:
+            eng.mesh_clean_dev(mxyz, mnrm, mrgb, minf, mtri, mrep, mv, mt, args.cell, origin, mv, mt, cxyz, cnrm, crgb, cinf, ctri, clrep,
+                               min_tris=100, iters=args.clean_iters, lam=0.5, mu=-0.53)
     ms = gb.time_on_stream(eng, chain, args.steps, args.warmup)
     eng.profile_reset()
     eng.profile_enable(True)
@@ -89,7 +102,10 @@ def main():
                fuse_summary=fsum.cpu().tolist(), cloud_report=crep.cpu().tolist(), refs_flagged=int((st.cpu().numpy()[:, 3] != 0).sum()))
     if args.mesh:
         rec["mesh_report"] = mrep.cpu().tolist()
-    gb.write_record(rec, args.out, "dense_chain_mesh" if args.mesh else "dense_chain")
+    if args.clean:
+        rec["clean_report"] = clrep.cpu().tolist()
+        rec["clean_ms"] = round(sum(parts[p] for p in CLEAN_PARTS), 4)
+    gb.write_record(rec, args.out, "dense_chain_mesh_clean" if args.clean else ("dense_chain_mesh" if args.mesh else "dense_chain"))
     eng.close()
 
 
