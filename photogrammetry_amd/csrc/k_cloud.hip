@@ -13,7 +13,8 @@
 //                 (after a plain load: a key, once written, never changes), atomicMin on the cell's first point and atomicAdd
 //                 on its count.  What the accumulate pass needs of the point is kept in 16 bytes.
 //   k_cld_count   the owners (the first point of a cell that is kept) per block of 256 points, and the cells
-//   k_cld_scan    one workgroup: the exclusive scan of the block counts, the kept count, the capacity status, d_report
+//   k_cld_scan    one workgroup: the exclusive scan of the block counts (block_scan_array), the kept count, the capacity
+//                 status, d_report
 //   k_cld_rank    the owner's rank in its block (block_excl_scan) plus the block's offset is the cell's output index: the
 //                 cells come out in the order of their first points with no sort.  The owner clears its cell's accumulators.
 //   k_cld_accum   one thread per point: integer atomics into the accumulators of its cell (64-bit sums of p, q and colour);
@@ -22,7 +23,7 @@
 // Every sum is an integer: no order of execution changes a bit.  DESIGN.md section 28.
 #include "pgx_stage_args.h"
 #include "pgx_densecam.h"
-#include "pgx_cloudkey.h"   // rule 1 (the used test, the key, the position in the cell) and the colour slot: shared with k_mesh.hip
+#include "pgx_cloudkey.h"   // rule 1 (the used test, the key, the position in the cell), the colour slot, the plan's tail: shared with k_mesh.hip
 
 namespace {
 
@@ -45,21 +46,7 @@ __global__ __launch_bounds__(CLD_NT) void k_cld_plan(CloudArgs a)
         a.tout[i] = -1;
     }
     if (blockIdx.x != 0) return;
-    for (int r = threadIdx.x; r < a.R; r += CLD_NT) {
-        const int fr = a.views[(size_t)r * (1 + a.S)];
-        fuse_camera_row(a.P, a.n_frames, fr, a.cam + (size_t)r * FUSE_CAM);
-        a.cslot[r] = cld_slot(a, fr);
-    }
-    if (threadIdx.x == 0) {
-        int n = a.max_in;
-        if (a.count) {
-            n = a.count[0];
-            n = n < 0 ? 0 : (n > a.max_in ? a.max_in : n);
-        }
-        a.meta[0] = n;
-#pragma unroll
-        for (int k = 1; k < 8; k++) a.meta[k] = 0;
-    }
+    cld_plan_rows<CLD_NT>(a);
 }
 
 // the point of pixel (u2, v2) of map r if it counts as a neighbour of a pixel at depth z
@@ -211,14 +198,7 @@ __global__ __launch_bounds__(CLD_NT) void k_cld_scan(CloudArgs a)
 {
     __shared__ int s_lds[CLD_NT / 64];
     const int n = a.meta[0], nbn = (n + CLD_NT - 1) / CLD_NT;
-    int carry = 0;
-    for (int base = 0; base < nbn; base += CLD_NT) {
-        const int j = base + (int)threadIdx.x;
-        int tot;
-        const int ex = block_excl_scan<int, CLD_NT>(j < nbn ? a.bsum[j] : 0, s_lds, tot);
-        if (j < nbn) a.boff[j] = carry + ex;
-        carry += tot;
-    }
+    const int carry = block_scan_array<int, CLD_NT>(a.bsum, a.boff, nbn, s_lds);
     if (threadIdx.x == 0) {
         a.meta[5] = carry;
         if (carry > a.max_points) atomicOr(a.status, (int)PGX_ST_CLD_CAP);

@@ -18,7 +18,7 @@
 //                      and no floating-point reduction, so the key is the same for any lane mapping.  The winner is
 //                      recomputed from its pair (the same function on the same bits) for the keep flags and the point.
 //   k_cns_scan_reduce  per block of CNS_SCAN_ITEMS tracks the surviving tracks and nodes
-//   k_cns_scan_sums    one workgroup: the exclusive scan of the block sums (CNS_NT at a time with a carry), the totals,
+//   k_cns_scan_sums    one workgroup: the exclusive scans of the block sums (block_scan_array, tracks then nodes), the totals,
 //                      d_summary_out, d_report and the end of the offsets
 //   k_cns_scan_apply   per block the exclusive scan of its tracks: d_track_map and the offsets of the surviving tracks
 //   k_cns_write        grid-stride over the tracks in the same classes: a kept node goes to its rank inside the track (a
@@ -341,19 +341,9 @@ __global__ __launch_bounds__(CNS_NT) void k_cns_scan_reduce(CnsArgs a)
 __global__ __launch_bounds__(CNS_NT) void k_cns_scan_sums(CnsArgs a, int nblk)
 {
     __shared__ int sh[CNS_NT / 64];
-    int cx = 0, cy = 0;   // the carry: everything before this chunk of CNS_NT block sums
-    for (int b0 = 0; b0 < nblk; b0 += CNS_NT) {
-        const int b = b0 + threadIdx.x;
-        int tx, ty;
-        const int x = block_excl_scan<int, CNS_NT>(b < nblk ? a.bsum[2 * (size_t)b] : 0, sh, tx);
-        const int y = block_excl_scan<int, CNS_NT>(b < nblk ? a.bsum[2 * (size_t)b + 1] : 0, sh, ty);
-        if (b < nblk) {
-            a.bsum[2 * (size_t)b] = cx + x;
-            a.bsum[2 * (size_t)b + 1] = cy + y;
-        }
-        cx += tx;
-        cy += ty;
-    }
+    // the block sums are (tracks, nodes) pairs: each half in place, CNS_NT blocks at a time with a carry
+    const int cx = block_scan_array<int, CNS_NT>(a.bsum, a.bsum, nblk, sh, 2);
+    const int cy = block_scan_array<int, CNS_NT>(a.bsum + 1, a.bsum + 1, nblk, sh, 2);
     if (threadIdx.x == 0) {
         a.off_out[cx] = cy;
         const int32_t *si = a.tv.track_summary;

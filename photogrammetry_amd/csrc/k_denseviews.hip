@@ -162,14 +162,8 @@ __global__ __launch_bounds__(DVW_NT) void k_dvw_scan(DvwArgs a)
     __shared__ long long sh[DVW_NT / 64];
     const int nf = a.tv.n_frames;
     const long long cap = a.tv.node_cap;
-    long long carry = 0;
-    for (int f0 = 0; f0 < nf; f0 += DVW_NT) {
-        const int f = f0 + threadIdx.x;
-        long long tot;
-        const long long x = carry + block_excl_scan<long long, DVW_NT>(f < nf ? (long long)(unsigned)a.fcnt[f] : 0, sh, tot);
-        if (f < nf) a.fbase[f] = a.fcur[f] = (int)(x < cap ? x : cap);
-        carry += tot;
-    }
+    const long long carry = block_scan_array<long long, DVW_NT>(
+        nf, sh, [&](int f) { return (long long)(unsigned)a.fcnt[f]; }, [&](int f, long long x) { a.fbase[f] = a.fcur[f] = (int)(x < cap ? x : cap); });
     if (threadIdx.x == 0) a.fbase[nf] = (int)(carry < cap ? carry : cap);
 }
 

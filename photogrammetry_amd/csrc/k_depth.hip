@@ -20,7 +20,7 @@
 //                  that has this frame as its reference
 //   k_fuse_count   grid-stride over blocks of 256 pixels in (r, v, u) order: back-projection, the agreeing views, the keep flag,
 //                  the block's count
-//   k_fuse_scan    one workgroup: the exclusive scan of the block counts in chunks of 256 with a running carry
+//   k_fuse_scan    one workgroup: the exclusive scan of the block counts (block_scan_array: chunks of 256, a running carry)
 //   k_fuse_write   the kept pixels of a block at block offset + rank in the block (block_excl_scan): the list is in (r, v, u)
 //                  order whatever the grid
 // Counters are integer atomics only.  DESIGN.md section 26.
@@ -359,14 +359,7 @@ __global__ __launch_bounds__(DEP_NT) void k_fuse_count(FuseArgs a)
 __global__ __launch_bounds__(DEP_NT) void k_fuse_scan(FuseArgs a)
 {
     __shared__ int s_lds[DEP_NT / 64];
-    int carry = 0;
-    for (int base = 0; base < a.nb; base += DEP_NT) {
-        const int j = base + (int)threadIdx.x;
-        int tot;
-        const int ex = block_excl_scan<int, DEP_NT>(j < a.nb ? a.bsum[j] : 0, s_lds, tot);
-        if (j < a.nb) a.boff[j] = carry + ex;
-        carry += tot;
-    }
+    const int carry = block_scan_array<int, DEP_NT>(a.bsum, a.boff, a.nb, s_lds);
     int skipped = 0;
     for (int r = threadIdx.x; r < a.R; r += DEP_NT) skipped += a.cam[(size_t)r * FUSE_CAM + 12] == 0.0;
     skipped = block_sum_i(skipped, s_lds);

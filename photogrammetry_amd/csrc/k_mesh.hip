@@ -65,6 +65,8 @@ __device__ __forceinline__ int msh_find(const MeshArgs &a, unsigned long long ke
     return -1;
 }
 
+static_assert(MM_N == 0, "cld_plan_rows (pgx_cloudkey.h) leaves n in meta[0]");
+
 // more voxels than max_voxels (a full table has more): nothing behind k_msh_tsdf runs
 __device__ __forceinline__ bool msh_overflow(const MeshArgs &a) { return a.meta[MM_VOX] > a.max_voxels; }
 
@@ -77,21 +79,7 @@ __global__ __launch_bounds__(MSH_NT) void k_msh_plan(MeshArgs a)
         a.sfirst[i] = MSH_NOSEED;
     }
     if (blockIdx.x != 0) return;
-    for (int r = threadIdx.x; r < a.R; r += MSH_NT) {
-        const int fr = a.views[(size_t)r * (1 + a.S)];
-        fuse_camera_row(a.P, a.n_frames, fr, a.cam + (size_t)r * FUSE_CAM);
-        a.cslot[r] = cld_slot(a, fr);
-    }
-    if (threadIdx.x == 0) {
-        int n = a.max_in;
-        if (a.count) {
-            n = a.count[0];
-            n = n < 0 ? 0 : (n > a.max_in ? a.max_in : n);
-        }
-        a.meta[MM_N] = n;
-#pragma unroll
-        for (int k = 1; k < 8; k++) a.meta[k] = 0;
-    }
+    cld_plan_rows<MSH_NT>(a);
 }
 
 __global__ __launch_bounds__(MSH_NT) void k_msh_seed(MeshArgs a)
@@ -306,15 +294,7 @@ __global__ __launch_bounds__(MSH_NT) void k_msh_scan(MeshArgs a)
     __shared__ unsigned long long s_lds[MSH_NT / 64];
     const int n = a.meta[MM_N], nbn = (n + MSH_NT - 1) / MSH_NT;
     const bool over = msh_overflow(a);
-    unsigned long long carry = 0;
-    if (!over)
-        for (int base = 0; base < nbn; base += MSH_NT) {
-            const int j = base + (int)threadIdx.x;
-            unsigned long long tot;
-            const unsigned long long ex = block_excl_scan<unsigned long long, MSH_NT>(j < nbn ? a.bsum[j] : 0ull, s_lds, tot);
-            if (j < nbn) a.boff[j] = carry + ex;
-            carry += tot;
-        }
+    const unsigned long long carry = block_scan_array<unsigned long long, MSH_NT>(a.bsum, a.boff, over ? 0 : nbn, s_lds);
     if (threadIdx.x == 0) {
         const int nv = (int)(carry & 0xFFFFFFFFull), nq = (int)(carry >> 32);
         a.meta[MM_VERT] = nv;

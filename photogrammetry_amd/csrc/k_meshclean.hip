@@ -9,12 +9,13 @@
 //   k_mcl_roots    one thread per vertex: its root, into an array of its own
 //   k_mcl_count    one thread per used triangle: the triangles and the smallest vertex per root.  A real mesh is ONE large
 //                  component, and a global atomicAdd per triangle on its root serialises (about 10 ns each, k_tracks.hip): the
-//                  roots are counted in an LDS table that lives across the workgroup's grid-stride passes and is flushed when it
-//                  may fill and at the end: one global add and one atomicMin per distinct root and flush.  big: the flush's sums
+//                  roots are counted in an LDS table (block_tally_add) that lives across the workgroup's grid-stride passes and is
+//                  flushed when it may fill and at the end: one global add and one atomicMin per distinct root and flush.  big: the flush's sums
 //                  (old + n; the last add of a root gives its total) through an LDS maximum, one global atomicMax per flush
 //   k_mcl_bsum     per block of 256 indices: the kept vertices and kept triangles (one 64-bit value), the row entries of the kept
 //                  vertices; the components and the kept ones counted at their names
-//   k_mcl_scan     one workgroup: the exclusive scans of the block sums, the totals, the capacity status, d_report
+//   k_mcl_scan     one workgroup: the exclusive scans of the block sums (block_scan_array, twice), the totals, the capacity
+//                  status, d_report
 //   k_mcl_rank     the block's base plus block_excl_scan: new indices in old-index order with no sort; vertex_map, comp, row starts
 //   k_mcl_emit     the kept vertices' copied attributes and the kept triangles with their new indices
 //   k_mcl_rows     (iters > 0) one thread per kept triangle: its index into the rows of its three vertices (atomic cursor: no
@@ -34,7 +35,7 @@ constexpr int MCL_GRID_MAX = 1024;      // workgroups of the per-vertex and per-
 constexpr int MCL_UNION_GRID = 256;     // ... of k_mcl_union and k_mcl_count: one per CU, as k_trk_union's (fewer flushes, fresher trees)
 constexpr int MCL_SLOTS = 512;          // LDS aggregation table of k_mcl_count (>= 2 * MCL_NT)
 constexpr int MCL_LONG_ROW = 64;        // a row of more entries is summed by the 64 lanes of its vertex's wave, not by its thread alone
-constexpr uint32_t MCL_EMPTY = 0xFFFFFFFFu;
+constexpr uint32_t MCL_EMPTY = BLOCK_TALLY_EMPTY;   // hkey: block_tally_add (pgx_block.h) claims such an entry
 constexpr unsigned long long MCL_NONRM = ~0ull;   // tnrm: the triangle contributes nothing
 constexpr int MCL_NOREP = 0x7FFFFFFF;
 constexpr double MCL_STEP_MAX = 4611686018427387904.0;   // 2^62: the clamp of a half-step's increment
@@ -42,12 +43,10 @@ enum { MC_NV = 0, MC_NT, MC_USED, MC_COMPS, MC_KEPT, MC_VOUT, MC_TOUT, MC_BIG };
 
 __device__ __forceinline__ uint32_t mcl_prio(int x) { return (uint32_t)x * 2654435761u; }   // a bijection on 32 bits: no ties
 
-__device__ __forceinline__ int mcl_clamp(int n, int cap) { return n < 0 ? 0 : (n > cap ? cap : n); }
-
 __global__ __launch_bounds__(MCL_NT) void k_mcl_init(MeshCleanArgs a)
 {
-    const int nv = a.counts ? mcl_clamp(a.counts[5], a.max_vertices) : a.max_vertices;
-    const int nt = a.counts ? mcl_clamp(a.counts[6], a.max_tris) : a.max_tris;
+    const int nv = a.counts ? pgx_clamp_count(a.counts[5], a.max_vertices) : a.max_vertices;
+    const int nt = a.counts ? pgx_clamp_count(a.counts[6], a.max_tris) : a.max_tris;
     if (blockIdx.x == 0 && threadIdx.x < 8) a.meta[threadIdx.x] = threadIdx.x == MC_NV ? nv : (threadIdx.x == MC_NT ? nt : 0);
     const double o[3] = {a.ox, a.oy, a.oz};
     for (int v = blockIdx.x * MCL_NT + (int)threadIdx.x; v < nv; v += (int)gridDim.x * MCL_NT) {
@@ -139,15 +138,7 @@ __global__ __launch_bounds__(MCL_NT) void k_mcl_count(MeshCleanArgs a)
         const int k = b * MCL_NT + (int)threadIdx.x;
         if (k < nt && a.tused[k]) {
             const int i0 = a.tri[3 * (size_t)k], i1 = a.tri[3 * (size_t)k + 1], i2 = a.tri[3 * (size_t)k + 2];
-            const int r = a.root[i0], lo = min(i0, min(i1, i2));
-            uint32_t h = ((uint32_t)r * 2654435761u) >> 9;
-            for (;;) {
-                h &= (uint32_t)(MCL_SLOTS - 1);
-                const uint32_t old = atomicCAS(&hkey[h], MCL_EMPTY, (uint32_t)r);
-                if (old == MCL_EMPTY) atomicAdd(&s_ctl[0], 1);
-                if (old == MCL_EMPTY || old == (uint32_t)r) { atomicAdd(&hcnt[h], 1); atomicMin(&hmin[h], lo); break; }
-                h++;
-            }
+            if (block_tally_add(hkey, hcnt, hmin, MCL_SLOTS, a.root[i0], min(i0, min(i1, i2)))) atomicAdd(&s_ctl[0], 1);
         }
         __syncthreads();   // s_ctl[0] is read at the head of the next pass
     }
@@ -199,17 +190,8 @@ __global__ __launch_bounds__(MCL_NT) void k_mcl_scan(MeshCleanArgs a)
 {
     __shared__ unsigned long long s_lds[MCL_NT / 64];
     const int nv = a.meta[MC_NV], nt = a.meta[MC_NT], n = nv > nt ? nv : nt, nbn = (n + MCL_NT - 1) / MCL_NT;
-    unsigned long long carry = 0, rcarry = 0;
-    for (int base = 0; base < nbn; base += MCL_NT) {
-        const int j = base + (int)threadIdx.x;
-        unsigned long long tot;
-        const unsigned long long ex = block_excl_scan<unsigned long long, MCL_NT>(j < nbn ? a.bsum[j] : 0ull, s_lds, tot);
-        if (j < nbn) a.boff[j] = carry + ex;
-        carry += tot;
-        const unsigned long long rex = block_excl_scan<unsigned long long, MCL_NT>(j < nbn ? a.rsum[j] : 0ull, s_lds, tot);
-        if (j < nbn) a.rbase[j] = rcarry + rex;
-        rcarry += tot;
-    }
+    const unsigned long long carry = block_scan_array<unsigned long long, MCL_NT>(a.bsum, a.boff, nbn, s_lds);
+    block_scan_array<unsigned long long, MCL_NT>(a.rsum, a.rbase, nbn, s_lds);
     if (threadIdx.x == 0) {
         const int vo = (int)(carry & 0xFFFFFFFFull), to = (int)(carry >> 32);
         a.meta[MC_VOUT] = vo;

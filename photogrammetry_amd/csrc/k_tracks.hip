@@ -31,7 +31,7 @@
 //                  segments are short: <= n_frames)
 // Same-address atomics serialise at about 10 ns each on this part: one global counter of the edges used cost 1.3 ms per launch
 // (130 k wavefront atomics), per-node atomicAdds on the junk component's root 0.56 ms -- hence the LDS stages and TRK_ECNT.
-#include "pgx_trackgraph.h"   // block_excl_scan, trk_find, trk_hook
+#include "pgx_trackgraph.h"   // trk_find, trk_hook; block_excl_scan, block_scan_array and block_tally_add of pgx_block.h
 
 namespace {
 
@@ -40,7 +40,7 @@ constexpr int SCAN_NT = 256;         // scan kernels: 256 threads x 4 items.  Sm
                                      // slots on every SIMD of one CU at once, and beside another job's distance kernel it waited
                                      // 3 ms for them (the one-workgroup k_trk_scan_sums, kernel trace of round 5)
 constexpr int SCAN_ITEMS = 4 * SCAN_NT;
-constexpr uint32_t TRK_EMPTY = 0xFFFFFFFFu;
+constexpr uint32_t TRK_EMPTY = BLOCK_TALLY_EMPTY;   // of the frames' tables, and of k_trk_flatten's LDS table (block_tally_add)
 constexpr int TRK_ECNT = 256;        // slots of the edge counter
 // Workgroups of k_trk_union (grid-stride over the match entries).  The bench job's graph alone, ms per call: 32 workgroups 2.79,
 // 64: 1.45, 128: 0.82, 192: 0.62, 256: 0.55, 512: 0.59, 1024: 0.65, 2048: 0.81, 4096: 0.90, one per 256 entries (32 k): 0.70 --
@@ -161,13 +161,7 @@ __device__ __forceinline__ void trk_flatten(const TrkArgs &a, const int32_t *act
         const int r = trk_find(a.parent, x);
         // into an array of its own: other threads' pointer jumping still stores (older) ancestors into parent[x] while this runs
         a.root[x] = r;
-        uint32_t h = ((uint32_t)r * 2654435761u) >> 9;
-        for (;;) {
-            h &= (uint32_t)(FL_SLOTS - 1);
-            const uint32_t old = atomicCAS(&hkey[h], TRK_EMPTY, (uint32_t)r);
-            if (old == TRK_EMPTY || old == (uint32_t)r) { atomicAdd(&hcnt[h], 1); atomicMin(&hmin[h], x); break; }
-            h++;
-        }
+        block_tally_add(hkey, hcnt, hmin, FL_SLOTS, r, x);
     }
     __syncthreads();
     uint32_t *tab = a.table + (size_t)f * a.T;
@@ -249,15 +243,7 @@ __global__ __launch_bounds__(SCAN_NT) void k_trk_scan_reduce(TrkArgs a)
 __global__ __launch_bounds__(SCAN_NT) void k_trk_scan_sums(TrkArgs a, int nb)
 {
     __shared__ unsigned long long lds[SCAN_NT / 64];
-    unsigned long long carry = 0;
-    for (int b0 = 0; b0 < nb; b0 += SCAN_NT) {
-        const int b = b0 + threadIdx.x;
-        const unsigned long long v = b < nb ? a.bsum[b] : 0ull;
-        unsigned long long tot;
-        const unsigned long long ex = block_excl_scan<unsigned long long, SCAN_NT>(v, lds, tot);
-        if (b < nb) a.bsum[b] = carry + ex;
-        carry += tot;
-    }
+    const unsigned long long carry = block_scan_array<unsigned long long, SCAN_NT>(a.bsum, a.bsum, nb, lds);   // SCAN_NT block sums per pass
     unsigned long long etot;
     (void)block_excl_scan<unsigned long long, SCAN_NT>(threadIdx.x < TRK_ECNT ? (unsigned long long)a.ecnt[threadIdx.x] : 0ull, lds, etot);
     if (threadIdx.x == 0) {

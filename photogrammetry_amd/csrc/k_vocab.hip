@@ -21,7 +21,9 @@
 //   k_sel_topk         per slot: the key of its top_k-th candidate, found bit by bit on (score << 12 | 4095 - b) keys in LDS
 //   k_sel_count / _scan / _write / _fill   the selected pairs compacted in (a, b) order
 #include "pgx_fp4_nn.h"
-#include "pgx_trackgraph.h"
+#include "pgx_block.h"       // block_scan_array, block_sum_i, block_sum_ll, block_excl_scan, gsum_i
+#include "pgx_hoststage.h"   // WsCarver
+#include "pgx_ransac.h"      // splitmix64
 
 #include <climits>
 
@@ -55,16 +57,8 @@ __attribute__((amdgpu_num_vgpr(120))) __global__ __launch_bounds__(256, 2) void 
 // one workgroup of 256: out[i] = in[0] + .. + in[i - 1] for i <= n (out may be in); clamp_to >= 0 clamps the inputs to [0, clamp_to]
 __device__ __forceinline__ void scan_array(const int32_t *in, int32_t *out, int n, int clamp_to, int *sh)
 {
-    int carry = 0;
-    for (int b = 0; b < n; b += 256) {
-        const int i = b + threadIdx.x;
-        int v = i < n ? in[i] : 0;
-        if (clamp_to >= 0) v = pgx_clamp_count(v, clamp_to);
-        int tot;
-        const int e = block_excl_scan<int, 256>(v, sh, tot);
-        if (i < n) out[i] = carry + e;
-        carry += tot;
-    }
+    const int carry = block_scan_array<int, 256>(
+        n, sh, [&](int i) { return clamp_to >= 0 ? pgx_clamp_count(in[i], clamp_to) : in[i]; }, [&](int i, int v) { out[i] = v; });
     if (threadIdx.x == 0) out[n] = carry;
 }
 
@@ -234,17 +228,6 @@ __global__ __launch_bounds__(256) void k_sel_weights(SelArgs a)
     a.q[w] = q;
     if (df == 0) atomicAdd(&a.meta[4], 1);
     if (df == Fv) atomicAdd(&a.meta[5], 1);
-}
-
-__device__ __forceinline__ long long block_sum_ll(long long v, long long *sh)
-{
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m, 64);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    v = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-    __syncthreads();
-    return v;
 }
 
 __global__ __launch_bounds__(256) void k_sel_self(SelArgs a)

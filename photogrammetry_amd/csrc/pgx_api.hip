@@ -901,6 +901,19 @@ int download_images(pgx_ctx *c, const HostImage &out)
     return sync_status(c);
 }
 
+// ... and the first n rows of the sections that were added without a destination, once a downloaded report has told n
+struct FetchRows {
+    int sec;       // of out
+    void *host;
+    size_t elem;   // bytes per row
+};
+int fetch_rows(pgx_ctx *c, const HostImage &out, std::initializer_list<FetchRows> rows, size_t n)
+{
+    if (n == 0) return PGX_OK;
+    for (const FetchRows &r : rows) HIPCHK(c, hipMemcpy(r.host, out.dev<char>(r.sec), n * r.elem, hipMemcpyDeviceToHost));
+    return PGX_OK;
+}
+
 } // namespace
 
 int pgx_match(pgx_ctx *c, const uint32_t *desc1, int n1, const uint32_t *desc2, int n2, int words, pgx_pair *out)
@@ -2186,10 +2199,7 @@ int pgx_depth_fuse(pgx_ctx *c, const double *depth, const int32_t *views, int R,
     if ((rs = run_depth_fuse(c, a)) != PGX_OK) return rs;
     rs = download_images(c, out);   // summary and agree; waits for the stream
     const size_t np = (size_t)(summary[0] < max_points ? summary[0] : max_points);
-    if (np > 0) {
-        HIPCHK(c, hipMemcpy(xyz, out.dev<double>(o_x), np * 24, hipMemcpyDeviceToHost));
-        HIPCHK(c, hipMemcpy(src, out.dev<int32_t>(o_r), np * 8, hipMemcpyDeviceToHost));
-    }
+    if (const int rf = fetch_rows(c, out, {{o_x, xyz, 24}, {o_r, src, 8}}, np); rf != PGX_OK) return rf;
     return rs;
 }
 
@@ -2221,6 +2231,19 @@ bool overlap(const void *p, size_t pn, const void *q, size_t qn)
     const char *a = static_cast<const char *>(p), *b = static_cast<const char *>(q);
     return p && q && pn && qn && a < b + qn && b < a + pn;
 }
+
+// a device form's arrays, each with its bytes: no output may overlap an input
+struct Span {
+    const void *p;
+    size_t n;
+};
+int no_alias(pgx_ctx *c, const Span *in, size_t n_in, const Span *out, size_t n_out)
+{
+    for (size_t o = 0; o < n_out; o++)
+        for (size_t i = 0; i < n_in; i++)
+            if (overlap(out[o].p, out[o].n, in[i].p, in[i].n)) return fail(c, PGX_E_BADARG, "an output must not alias an input");
+    return PGX_OK;
+}
 } // namespace
 
 int pgx_dense_views_dev(pgx_ctx *c, const int32_t *d_offsets, const int32_t *d_nodes, const int32_t *d_track_summary, int max_tracks,
@@ -2239,13 +2262,11 @@ int pgx_dense_views_dev(pgx_ctx *c, const int32_t *d_offsets, const int32_t *d_n
     if (!d_refs && R != n_frames) return fail(c, PGX_E_BADARG, "without d_refs, R must equal n_frames");
     if (max_tracks < 0 || max_nodes < 0) return fail(c, PGX_E_BADARG, "max_tracks and max_nodes must be >= 0");
     const size_t mt = max_tracks, nf = n_frames;
-    const struct { const void *p; size_t n; } in[] = {{d_offsets, (mt + 1) * 4}, {d_nodes, (size_t)max_nodes * 8}, {d_track_summary, 32},
-                                                      {d_xyz, mt * 24}, {d_track_flags, mt * 4}, {d_P, nf * 96}, {d_refs, (size_t)R * 4}},
-                                        out[] = {{d_views, (size_t)R * (1 + S) * 4}, {d_range, (size_t)R * 16},
-                                                 {d_pair_counts, (size_t)R * nf * 8}, {d_ref_stats, (size_t)R * 16}, {d_report, 32}};
-    for (const auto &o : out)
-        for (const auto &i : in)
-            if (overlap(o.p, o.n, i.p, i.n)) return fail(c, PGX_E_BADARG, "an output must not alias an input");
+    const Span in[] = {{d_offsets, (mt + 1) * 4}, {d_nodes, (size_t)max_nodes * 8}, {d_track_summary, 32},
+                       {d_xyz, mt * 24}, {d_track_flags, mt * 4}, {d_P, nf * 96}, {d_refs, (size_t)R * 4}},
+               out[] = {{d_views, (size_t)R * (1 + S) * 4}, {d_range, (size_t)R * 16},
+                        {d_pair_counts, (size_t)R * nf * 8}, {d_ref_stats, (size_t)R * 16}, {d_report, 32}};
+    if (const int ra = no_alias(c, in, std::size(in), out, std::size(out)); ra != PGX_OK) return ra;
     DvwArgs a{};
     a.tv.offsets = d_offsets; a.tv.nodes = d_nodes; a.tv.track_summary = d_track_summary;
     a.tv.n_frames = n_frames; a.tv.max_tracks = max_tracks; a.tv.node_cap = max_nodes;
@@ -2381,15 +2402,13 @@ int pgx_cloud_merge_dev(pgx_ctx *c, const double *d_xyz, const int32_t *d_src, c
                               normal_step, disc_tol, min_support, max_points);
     if (rc != PGX_OK) return rc;
     const size_t ni = max_in, no = max_points, npix = (size_t)W * H;
-    const struct { const void *p; size_t n; } in[] = {{d_xyz, ni * 24}, {d_src, ni * 8}, {d_count, 4}, {d_depth, (size_t)R * npix * 8},
-                                                      {d_views, (size_t)R * (1 + S) * 4}, {d_P, (size_t)n_frames * 96},
-                                                      {d_rgba8, d_rgba8 ? (size_t)F * npix * 4 : 0},
-                                                      {d_frame_ids, d_rgba8 ? (size_t)F * 4 : 0}},
-                                        out[] = {{d_out_xyz, no * 24}, {d_out_normal, no * 12}, {d_out_rgba8, no * 4}, {d_out_info, no * 16},
-                                                 {d_pt_normal, ni * 12}, {d_cell_of, ni * 4}, {d_report, 32}};
-    for (const auto &o : out)
-        for (const auto &i : in)
-            if (overlap(o.p, o.n, i.p, i.n)) return fail(c, PGX_E_BADARG, "an output must not alias an input");
+    const Span in[] = {{d_xyz, ni * 24}, {d_src, ni * 8}, {d_count, 4}, {d_depth, (size_t)R * npix * 8},
+                       {d_views, (size_t)R * (1 + S) * 4}, {d_P, (size_t)n_frames * 96},
+                       {d_rgba8, d_rgba8 ? (size_t)F * npix * 4 : 0},
+                       {d_frame_ids, d_rgba8 ? (size_t)F * 4 : 0}},
+               out[] = {{d_out_xyz, no * 24}, {d_out_normal, no * 12}, {d_out_rgba8, no * 4}, {d_out_info, no * 16},
+                        {d_pt_normal, ni * 12}, {d_cell_of, ni * 4}, {d_report, 32}};
+    if (const int ra = no_alias(c, in, std::size(in), out, std::size(out)); ra != PGX_OK) return ra;
     CloudArgs a{};
     a.xyz = d_xyz; a.src = d_src; a.count = d_count; a.max_in = max_in; a.depth = d_depth; a.views = d_views;
     a.R = R; a.S = S; a.W = W; a.H = H; a.n_frames = n_frames; a.P = d_P;
@@ -2436,12 +2455,8 @@ int pgx_cloud_merge(pgx_ctx *c, const double *xyz, const int32_t *src, int n_in,
     rs = download_images(c, out);   // the report and the per-point outputs; waits for the stream
     if (rs != PGX_OK && rs != PGX_E_CAPACITY) return rs;   // the report was not downloaded: nothing tells how many rows there are
     const size_t np = (size_t)(report[6] < max_points ? report[6] : max_points);
-    if (np > 0) {
-        HIPCHK(c, hipMemcpy(out_xyz, out.dev<double>(o_x), np * 24, hipMemcpyDeviceToHost));
-        HIPCHK(c, hipMemcpy(out_normal, out.dev<float>(o_n), np * 12, hipMemcpyDeviceToHost));
-        HIPCHK(c, hipMemcpy(out_rgba8, out.dev<uint32_t>(o_c), np * 4, hipMemcpyDeviceToHost));
-        HIPCHK(c, hipMemcpy(out_info, out.dev<int32_t>(o_i), np * 16, hipMemcpyDeviceToHost));
-    }
+    if (const int rf = fetch_rows(c, out, {{o_x, out_xyz, 24}, {o_n, out_normal, 12}, {o_c, out_rgba8, 4}, {o_i, out_info, 16}}, np); rf != PGX_OK)
+        return rf;
     return rs;
 }
 
@@ -2479,15 +2494,13 @@ int pgx_mesh_dev(pgx_ctx *c, const double *d_xyz, const int32_t *d_src, const in
                              band, trunc_cells, min_weight, max_voxels, max_vertices, max_tris);
     if (rc != PGX_OK) return rc;
     const size_t ni = max_in, nv = max_vertices, nt = max_tris, npix = (size_t)W * H;
-    const struct { const void *p; size_t n; } in[] = {{d_xyz, ni * 24}, {d_src, ni * 8}, {d_count, 4}, {d_depth, (size_t)R * npix * 8},
-                                                      {d_views, (size_t)R * (1 + S) * 4}, {d_P, (size_t)n_frames * 96},
-                                                      {d_agree, (size_t)R * npix * 4}, {d_rgba8, d_rgba8 ? (size_t)F * npix * 4 : 0},
-                                                      {d_frame_ids, d_rgba8 ? (size_t)F * 4 : 0}},
-                                        out[] = {{d_out_xyz, nv * 24}, {d_out_normal, nv * 12}, {d_out_rgba8, nv * 4}, {d_out_info, nv * 16},
-                                                 {d_out_tri, nt * 12}, {d_report, 32}};
-    for (const auto &o : out)
-        for (const auto &i : in)
-            if (overlap(o.p, o.n, i.p, i.n)) return fail(c, PGX_E_BADARG, "an output must not alias an input");
+    const Span in[] = {{d_xyz, ni * 24}, {d_src, ni * 8}, {d_count, 4}, {d_depth, (size_t)R * npix * 8},
+                       {d_views, (size_t)R * (1 + S) * 4}, {d_P, (size_t)n_frames * 96},
+                       {d_agree, (size_t)R * npix * 4}, {d_rgba8, d_rgba8 ? (size_t)F * npix * 4 : 0},
+                       {d_frame_ids, d_rgba8 ? (size_t)F * 4 : 0}},
+               out[] = {{d_out_xyz, nv * 24}, {d_out_normal, nv * 12}, {d_out_rgba8, nv * 4}, {d_out_info, nv * 16},
+                        {d_out_tri, nt * 12}, {d_report, 32}};
+    if (const int ra = no_alias(c, in, std::size(in), out, std::size(out)); ra != PGX_OK) return ra;
     MeshArgs a{};
     a.xyz = d_xyz; a.src = d_src; a.count = d_count; a.max_in = max_in; a.depth = d_depth; a.views = d_views;
     a.R = R; a.S = S; a.W = W; a.H = H; a.n_frames = n_frames; a.P = d_P; a.agree = d_agree; a.min_agree = min_agree;
@@ -2534,13 +2547,9 @@ int pgx_mesh(pgx_ctx *c, const double *xyz, const int32_t *src, int n_in, const 
     rs = download_images(c, out);   // the report; waits for the stream
     if (rs != PGX_OK && rs != PGX_E_CAPACITY) return rs;   // the report was not downloaded: nothing tells how many rows there are
     const size_t mv = (size_t)(report[5] < max_vertices ? report[5] : max_vertices), mt = (size_t)(report[6] < max_tris ? report[6] : max_tris);
-    if (mv > 0) {
-        HIPCHK(c, hipMemcpy(out_xyz, out.dev<double>(o_x), mv * 24, hipMemcpyDeviceToHost));
-        HIPCHK(c, hipMemcpy(out_normal, out.dev<float>(o_n), mv * 12, hipMemcpyDeviceToHost));
-        HIPCHK(c, hipMemcpy(out_rgba8, out.dev<uint32_t>(o_c), mv * 4, hipMemcpyDeviceToHost));
-        HIPCHK(c, hipMemcpy(out_info, out.dev<int32_t>(o_i), mv * 16, hipMemcpyDeviceToHost));
-    }
-    if (mt > 0) HIPCHK(c, hipMemcpy(out_tri, out.dev<int32_t>(o_t), mt * 12, hipMemcpyDeviceToHost));
+    if (const int rf = fetch_rows(c, out, {{o_x, out_xyz, 24}, {o_n, out_normal, 12}, {o_c, out_rgba8, 4}, {o_i, out_info, 16}}, mv); rf != PGX_OK)
+        return rf;
+    if (const int rf = fetch_rows(c, out, {{o_t, out_tri, 12}}, mt); rf != PGX_OK) return rf;
     return rs;
 }
 
@@ -2587,13 +2596,11 @@ int pgx_mesh_clean_dev(pgx_ctx *c, const double *d_xyz, const float *d_normal, c
                                    max_out_tris);
     if (rc != PGX_OK) return rc;
     const size_t nv = max_vertices, nt = max_tris, mv = max_out_vertices, mt = max_out_tris;
-    const struct { const void *p; size_t n; } in[] = {{d_xyz, nv * 24}, {d_normal, nv * 12}, {d_rgba8, nv * 4}, {d_info, nv * 16},
-                                                      {d_tri, nt * 12}, {d_counts, 32}},
-                                        out[] = {{d_out_xyz, mv * 24}, {d_out_normal, mv * 12}, {d_out_rgba8, mv * 4}, {d_out_info, mv * 16},
-                                                 {d_out_tri, mt * 12}, {d_vertex_map, nv * 4}, {d_comp, nv * 4}, {d_report, 32}};
-    for (const auto &o : out)
-        for (const auto &i : in)
-            if (overlap(o.p, o.n, i.p, i.n)) return fail(c, PGX_E_BADARG, "an output must not alias an input");
+    const Span in[] = {{d_xyz, nv * 24}, {d_normal, nv * 12}, {d_rgba8, nv * 4}, {d_info, nv * 16},
+                       {d_tri, nt * 12}, {d_counts, 32}},
+               out[] = {{d_out_xyz, mv * 24}, {d_out_normal, mv * 12}, {d_out_rgba8, mv * 4}, {d_out_info, mv * 16},
+                        {d_out_tri, mt * 12}, {d_vertex_map, nv * 4}, {d_comp, nv * 4}, {d_report, 32}};
+    if (const int ra = no_alias(c, in, std::size(in), out, std::size(out)); ra != PGX_OK) return ra;
     MeshCleanArgs a{};
     a.xyz = d_xyz; a.normal = d_normal; a.rgba8 = d_rgba8; a.info = d_info; a.tri = d_tri; a.counts = d_counts;
     mesh_clean_fill(a, max_vertices, max_tris, cell, ox, oy, oz, min_tris, min_frac_pm, iters, lambda, mu, max_out_vertices, max_out_tris);
@@ -2635,13 +2642,9 @@ int pgx_mesh_clean(pgx_ctx *c, const double *xyz, const float *normal, const uin
     if (rs != PGX_OK && rs != PGX_E_CAPACITY) return rs;   // the report was not downloaded: nothing tells how many rows there are
     const size_t kv = (size_t)(report[5] < max_out_vertices ? report[5] : max_out_vertices),
                  kt = (size_t)(report[6] < max_out_tris ? report[6] : max_out_tris);
-    if (kv > 0) {
-        HIPCHK(c, hipMemcpy(out_xyz, out.dev<double>(o_x), kv * 24, hipMemcpyDeviceToHost));
-        HIPCHK(c, hipMemcpy(out_normal, out.dev<float>(o_n), kv * 12, hipMemcpyDeviceToHost));
-        HIPCHK(c, hipMemcpy(out_rgba8, out.dev<uint32_t>(o_c), kv * 4, hipMemcpyDeviceToHost));
-        HIPCHK(c, hipMemcpy(out_info, out.dev<int32_t>(o_i), kv * 16, hipMemcpyDeviceToHost));
-    }
-    if (kt > 0) HIPCHK(c, hipMemcpy(out_tri, out.dev<int32_t>(o_t), kt * 12, hipMemcpyDeviceToHost));
+    if (const int rf = fetch_rows(c, out, {{o_x, out_xyz, 24}, {o_n, out_normal, 12}, {o_c, out_rgba8, 4}, {o_i, out_info, 16}}, kv); rf != PGX_OK)
+        return rf;
+    if (const int rf = fetch_rows(c, out, {{o_t, out_tri, 12}}, kt); rf != PGX_OK) return rf;
     return rs;
 }
 

@@ -1,11 +1,13 @@
 // pgx_cloudkey.h -- what the stages that bin a point list into a grid share (k_cloud.hip: the merged cloud; k_mesh.hip: the
 // mesh's seed cells): rule 1 of pgx_cloud_merge_dev (include/pgx.h), i.e. the used test, g = floor((X - o) / cell), the key and
 // the position in the cell, and the colour slot of a frame.  One copy, so that a point of the mesh's list lies in the cell the
-// cloud puts it in.  Every line is the arithmetic of include/pgx.h in its order.  Internal to libpgx.so.
+// cloud puts it in.  Every line is the arithmetic of include/pgx.h in its order.  Besides the rule, the tail that the two plan
+// kernels share (cld_plan_rows).  Each file keeps its own table of keys: tests/cloud_ref.py and tests/mesh_ref.py hold the hash
+// and the probe to the text of k_cloud.hip and k_mesh.hip.  Internal to libpgx.so; DESIGN.md section 14i.
 #pragma once
 
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "pgx_block.h"      // pgx_clamp_count
+#include "pgx_densecam.h"   // fuse_camera_row
 
 constexpr int CLD_GBIAS = 1 << 20;     // g + CLD_GBIAS is a cell coordinate's 21-bit field of the key
 
@@ -47,4 +49,20 @@ template <class A> __device__ __forceinline__ int cld_slot(const A &a, int f)
     for (int s = 0; s < a.F; s++)
         if (a.frame_ids[s] == f) return s;
     return -1;
+}
+
+// The tail of a plan kernel, one workgroup of NT threads: per map the filter's camera row and the slot that shows its frame,
+// meta[0] = n = min(d_count[0], max_in) (no count: max_in), the other seven counters zero (A: CloudArgs, MeshArgs)
+template <int NT, class A> __device__ __forceinline__ void cld_plan_rows(const A &a)
+{
+    for (int r = threadIdx.x; r < a.R; r += NT) {
+        const int fr = a.views[(size_t)r * (1 + a.S)];
+        fuse_camera_row(a.P, a.n_frames, fr, a.cam + (size_t)r * FUSE_CAM);
+        a.cslot[r] = cld_slot(a, fr);
+    }
+    if (threadIdx.x == 0) {
+        a.meta[0] = a.count ? pgx_clamp_count(a.count[0], a.max_in) : a.max_in;
+#pragma unroll
+        for (int k = 1; k < 8; k++) a.meta[k] = 0;
+    }
 }

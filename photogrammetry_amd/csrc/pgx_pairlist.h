@@ -1,11 +1,12 @@
 // pgx_pairlist.h -- what the producers of per-pair neighbour lists share (k_knn.hip, k_guided.hip, and through pgx_fp4_nn.h
-// the quantiser of k_vocab.hip): the clamped counts of an image pair, the write-out of (distance << 20 | index) keys, and the
-// k in {1, 2} x column side on / off dispatch of their launchers.  The column-key kernels themselves live in k_knn.hip
-// (pgx_launch_colkeys, pgx_internal.h).
+// the quantiser of k_vocab.hip): the clamped counts of an image pair (the clamp itself, pgx_clamp_count, is pgx_block.h's), the
+// write-out of (distance << 20 | index) keys, and the k in {1, 2} x column side on / off dispatch of their launchers.  The
+// column-key kernels themselves live in k_knn.hip (pgx_launch_colkeys, pgx_internal.h).
 // Internal to libpgx.so; DESIGN.md section 14b.
 #pragma once
 
 #include "pgx_internal.h"
+#include "pgx_block.h"   // pgx_clamp_count
 
 // calls fn(integral_constant<int, k>, bool_constant<col>) for k in {1, 2}: a launcher names its argument list once
 template <class Fn> void pgx_dispatch_k_col(int k, bool col, Fn &&fn)
@@ -19,8 +20,6 @@ template <class Fn> void pgx_dispatch_k_col(int k, bool col, Fn &&fn)
 }
 
 #ifdef __HIPCC__
-
-__device__ __forceinline__ int pgx_clamp_count(int n, int max_n) { return n < 0 ? 0 : (n > max_n ? max_n : n); }
 
 // image pair m: its two frames and their counts clamped to [0, max_n]
 struct PairCounts {

@@ -1,12 +1,13 @@
-// pgx_trackgraph.h -- what every consumer of the track graph shares (k_triangulate.hip, k_bundle.hip, k_register.hip, k_consensus.hip):
-// the read-only view of the graph and the keypoints, its validation and walking on the device, the lane-group and
-// workgroup reductions (k_verify.hip uses those too), the workgroup scan (k_tracks.hip, k_consensus.hip and k_vocab.hip compact
-// with it), the lock-free union-find (k_tracks.hip, k_meshclean.hip), and the workspace carver of the launchers.  It brings
-// pgx_ransac.h along,
-// the sampler and the keys of the RANSAC stages among its consumers.  Internal to libpgx.so; DESIGN.md section 14a.
+// pgx_trackgraph.h -- what every consumer of the track graph shares (k_triangulate.hip, k_bundle.hip, k_register.hip, k_consensus.hip,
+// k_denseviews.hip): the read-only view of the graph and the keypoints, its validation and walking on the device, the lock-free
+// union-find (k_tracks.hip, k_meshclean.hip), the cameras, and the workspace carver of the launchers.  The lane-group and
+// workgroup reductions and the workgroup scans that stood here are pgx_block.h's, which this header brings along with
+// pgx_hoststage.h and pgx_ransac.h (the sampler and the keys of the RANSAC stages among its consumers): a file that wants the
+// primitives alone includes pgx_block.h.  Internal to libpgx.so; DESIGN.md sections 14a and 14i.
 #pragma once
 
 #include "pgx_internal.h"
+#include "pgx_block.h"      // gsum, block_sums, block_excl_scan, block_scan_array, block_tally_add, pgx_clamp_count
 #include "pgx_hoststage.h"   // WsCarver, the workspace carver of the launchers
 #include "pgx_ransac.h"
 
@@ -81,86 +82,6 @@ __device__ __forceinline__ int clamp_tracks(const TrackView &tv, int *status, un
     const long long ngroups = (long long)gridDim.x * blockDim.x / (G);                       \
     const int lane = threadIdx.x & ((G) - 1);                                                \
     for (long long t = gid; t < (nt); t += ngroups)
-
-// ---- reductions over the G lanes of a group: xor butterflies, identical bits in every lane ----------------------------
-
-__device__ __forceinline__ double nan_max(double a, double b)
-{
-    if (a != a || b != b) return __builtin_nan("");
-    return a > b ? a : b;
-}
-
-template <int G> __device__ __forceinline__ double gsum(double x)
-{
-#pragma unroll
-    for (int m = 1; m < G; m <<= 1) x += __shfl_xor(x, m, G);
-    return x;
-}
-template <int G> __device__ __forceinline__ int gsum_i(int x)
-{
-#pragma unroll
-    for (int m = 1; m < G; m <<= 1) x += __shfl_xor(x, m, G);
-    return x;
-}
-template <int G> __device__ __forceinline__ double gmax(double x)
-{
-#pragma unroll
-    for (int m = 1; m < G; m <<= 1) x = nan_max(x, __shfl_xor(x, m, G));
-    return x;
-}
-
-// Fixed-shape sum over a workgroup of 256 threads of NV values per thread: xor butterflies per wave, then the four waves in a
-// fixed order; identical bits in every thread.  sh: NV rows of LDS.
-template <int NV> __device__ __forceinline__ void block_sums(double (&v)[NV], double (*sh)[4])
-{
-#pragma unroll
-    for (int k = 0; k < NV; k++) v[k] = gsum<64>(v[k]);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-        for (int k = 0; k < NV; k++) sh[k][w] = v[k];
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < NV; k++) v[k] = (sh[k][0] + sh[k][1]) + (sh[k][2] + sh[k][3]);
-    __syncthreads();
-}
-
-// block_sums' integer sibling: the sum of one count per thread over the workgroup of 256 threads, in every thread.  sh: 4 ints.
-__device__ __forceinline__ int block_sum_i(int c, int *sh)
-{
-    c = gsum_i<64>(c);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = c;
-    __syncthreads();
-    c = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-    __syncthreads();
-    return c;
-}
-
-// The exclusive prefix of one value per thread over a workgroup of NT threads, in thread order (shuffle-up scan per wave, then the
-// waves in order), and the workgroup's total in every thread.  lds: NT / 64 values.  Two counts whose SUMS stay below 2^32 scan
-// as one 64-bit value (hi << 32 | lo), as k_tracks.hip's (tracks, nodes) do: no carry crosses.
-template <class T, int NT> __device__ __forceinline__ T block_excl_scan(T v, T *lds, T &total)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    T inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const T o = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += o;
-    }
-    if (lane == 63) lds[w] = inc;
-    __syncthreads();
-    T base = 0, tot = 0;
-#pragma unroll
-    for (int i = 0; i < NT / 64; i++) {
-        const T s = lds[i];
-        if (i < w) base += s;
-        tot += s;
-    }
-    __syncthreads();
-    total = tot;
-    return base + inc - v;
-}
 
 // ---- lock-free union-find with hashed priorities (k_tracks.hip: keypoints joined by matches; k_meshclean.hip: vertices joined
 // by triangles).  The priority prio(x), a bijection on the ids so that there are no ties, is the graph's own (trk_prio, mcl_prio) --

@@ -43,7 +43,10 @@ def test_constants_and_rules_equal_the_kernel_sources():
                  "b = j % nblk;", "const int r = lin - nblk * F8;", "f = F8 + r / nblk;", "b = r % nblk;"):
         assert line in body, line
     # the scans: 256 values per pass, a carry between the passes; the trainer's search reads the scanned offsets
-    assert "for (int b = 0; b < n; b += %d) {" % pc.SCAN_NT in voc and "if (i < n) out[i] = carry + e;" in voc
+    block = source("pgx_block.h")
+    assert "for (int base = 0; base < n; base += NT) {" in block and "if (j < n) store(j, carry + ex);" in block and "carry += tot;" in block
+    assert "block_scan_array<int, %d>(" % pc.SCAN_NT in voc and "[&](int i, int v) { out[i] = v; });" in voc
+    assert "if (threadIdx.x == 0) out[n] = carry;" in voc
     assert "scan_array(counts, off, F, S, sh);" in voc and "if (off[mid] <= rk) a = mid;" in voc
     # the histogram's halves
     assert "atomicAdd(&a.hist[e >> 1], (e & 1) ? 0x10000u : 1u);" in voc and "const size_t e = (size_t)f * a.Vp + a.word[idx];" in voc

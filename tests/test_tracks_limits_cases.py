@@ -14,6 +14,7 @@ import tracks_split_ref as ref
 from oracle import tracks_np
 
 SRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "photogrammetry_amd", "csrc", "k_tracks.hip")
+BLOCK = os.path.join(os.path.dirname(SRC), "pgx_block.h")   # block_scan_array and block_tally_add, which k_tracks.hip calls
 
 
 # ---------------------------------------------------------------------------------------------------- the mirrored launch facts
@@ -33,11 +34,14 @@ def test_constants_equal_the_kernel_source():
     assert "if (gi > TRK_INIT_GRID_MAX) gi = TRK_INIT_GRID_MAX;" in body and "(init_items + TRK_NT - 1) / TRK_NT" in body
     assert "a.N > (long long)a.n_frames * a.T ? a.N : (long long)a.n_frames * a.T" in body
     # k_trk_scan_sums: SCAN_NT block sums per pass; the union grids; the table size; the two hash rules and the priority
-    assert "for (int b0 = 0; b0 < nb; b0 += SCAN_NT)" in text
+    block = open(BLOCK).read()
+    assert "block_scan_array<unsigned long long, SCAN_NT>(a.bsum, a.bsum, nb, lds);" in text
+    assert "for (int base = 0; base < n; base += NT) {" in block and "if (j < n) store(j, carry + ex);" in block and "carry += tot;" in block
     assert "n_items < TRK_UNION_GRID ? n_items : TRK_UNION_GRID" in text and "n_items < TRKS_UNION_GRID ? n_items : TRKS_UNION_GRID" in text
     assert text.count("a.T = 64;") == 1 and "while (a.T < 2 * stride) a.T <<= 1;" in text
     assert "return (uint32_t)x * %du;" % tc.HASH_MUL in text
-    assert "((uint32_t)r * %du) >> 9;" % tc.HASH_MUL in text and "h &= (uint32_t)(FL_SLOTS - 1);" in text
+    assert "block_tally_add(hkey, hcnt, hmin, FL_SLOTS, r, x);" in text
+    assert "((uint32_t)r * %du) >> 9;" % tc.HASH_MUL in block and "h &= (uint32_t)(slots - 1);" in block
     assert "(r * %du) >> 7;" % tc.HASH_MUL in text and "h &= (uint32_t)(a.T - 1);" in text
     assert (tc.SCAN_PASS, tc.INIT_PASS) == (262144, 1048576)
 
