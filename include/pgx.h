@@ -1374,6 +1374,83 @@ int pgx_mesh_clean(pgx_ctx *ctx, const double *xyz, const float *normal, const u
                    float *out_normal, uint32_t *out_rgba8, int32_t *out_info, int32_t *out_tri, int32_t *vertex_map, int32_t *comp,
                    int32_t *report);
 
+/* ---- the mesh decimated: adaptive vertex clustering over grid blocks ------------------------------- */
+/* Surface nets gives one vertex per active cube: a flat wall costs as many triangles per square metre as a corner.  These calls
+ * merge the vertices of a grid block of 2^l cells into one where the triangle normals round the block agree, up to level lmax, and
+ * keep them apart where they do not; on the same stream, reading the previous stage's report on the device.  Integers wherever a
+ * sum is taken (no order of execution changes a bit; int64 arithmetic wraps in two's complement), float64 elsewhere, one IEEE
+ * operation at a time in the order written, nothing contracted: bit-identical to a numpy restatement
+ * (tests/mesh_decimate_ref.py).  Not in the C# reference.  k_meshdecimate.hip.
+ *
+ * pgx_mesh_decimate_dev.
+ * Inputs.  A mesh in pgx_mesh_dev's layout, read where it lies: d_xyz, d_normal, d_rgba8, d_info, d_tri with the capacities
+ * max_vertices and max_tris (d_normal and d_info belong to the layout and are not read).  d_counts int32 [8] on the device or NULL:
+ * nv = min(max(d_counts[5], 0), max_vertices), nt = min(max(d_counts[6], 0), max_tris), or the capacities with NULL; the reports
+ * of pgx_mesh_dev, pgx_mesh_clean_dev and of this call fit.  The grid: cell, o = (ox, oy, oz).  lmin in [0, 6], lmax in [lmin, 6],
+ * flat_q in [0, 1024].
+ *   1 valid, used, q   rule 1 of pgx_mesh_clean_dev: vertex v < nv is VALID iff its coordinates are finite and
+ *               t_a = (X_a - o_a) / cell satisfies -2^20 <= t_a < 2^20; q_a = min((int64) floor(t_a * 65536.0 + 0.5), 2^36 - 1) (the
+ *               clamp is this stage's: t just below 2^20 rounds to 2^36, one past the last cell; the clamp keeps every q in a
+ *               cell of the grid).  Triangle k < nt is USED iff its indices are in [0, nv), pairwise distinct, and its vertices
+ *               valid.  A vertex is a MEMBER iff it is in a used triangle.
+ *   2 triangle normals   per used triangle (a, b, c): e1, e2, n and L as in rule 4 of pgx_mesh_clean_dev, on q;
+ *               m_a = (int64) floor((n_a / L) * 1024.0 + 0.5), m = 0 when L is 0 or not finite.
+ *   3 blocks, flat   the block of vertex v at level l is B_a = q_a >> (16 + l), the shift arithmetic (the floor): a side of 2^l cells.
+ *               For every level l in lmin + 1 .. lmax and every block: N = the number of incidences (triangle, corner) of used
+ *               triangles whose corner vertex lies in the block, S_a = the int64 sum of those triangles' m_a (a triangle with
+ *               three corners in the block counts three times), S2 = (S_0 S_0 + S_1 S_1) + S_2 S_2 in int64.  The block is FLAT
+ *               iff (double) S2 >= (double)(flat_q * flat_q) * ((double) N * (double) N).  With flat_q = 1024 a block whose
+ *               normals are all exactly one axis passes at equality; with flat_q = 0 every block passes.
+ *   4 level     L(v) of a member = the largest l in lmin .. lmax such that v's blocks at every level lmin + 1 .. l are flat
+ *               (lmin when there is none or lmax == lmin).  The cluster of a member is the pair (L(v), block of v at L(v)): a
+ *               partition of the members.
+ *   5 clusters  a cluster is named by its smallest member; clusters are ordered by name.  Over its n members, each once, with
+ *               org_a = B_a << (16 + L): s_a = sum (q_a - org_a), Q_a = org_a + (2 s_a + n) / (2 n) (integers; s_a >= 0), and per
+ *               byte of rgba8 the sum sc and the byte (2 sc + n) / (2 n).  Q lies in the cluster's block.
+ *   6 triangles a used triangle maps to its three clusters and is DEGENERATE unless they are pairwise distinct.  Otherwise it is
+ *               rotated so that the cluster of the smallest name comes first (the winding stays).  Triangles with the same rotated
+ *               triple are duplicates: the one of the smallest old index is KEPT.  The same clusters in the opposite winding are
+ *               another triangle.  The kept triangles are written in ascending old index as the rotated triples of new indices.
+ *   7 output    the output vertices are the clusters that occur in a kept triangle, in order of name.
+ *               xyz_a = o_a + ((double) Q_a / 65536.0) * cell; rgba8 of rule 5; info = (name, L, n, 0).  The normal is rule 4 of
+ *               pgx_mesh_clean_dev on the kept triangles and the Q values (m in 1/32767, zeros when the sum is zero).  A kept
+ *               triangle is FLIPPED iff the integer dot product of its m in 1/32767 (zeros when L is 0 or not finite) with the m of
+ *               rule 2 of the same triangle is negative.
+ * Outputs.  d_out_xyz, d_out_normal, d_out_rgba8, d_out_info [max_out_vertices] and d_out_tri [max_out_tris][3] (full new
+ * indices, also at or past max_out_vertices).  Optional: d_vertex_map [max_vertices] int32 = the new index of the vertex's cluster
+ * (the full one), -1 for a vertex that is no member, -2 for a member whose cluster is in no kept triangle; d_level [max_vertices]
+ * int32 = L(v), -1 for a vertex that is no member.  Rows >= nv of both are not written.
+ * d_report [8] int32: nv, nt, used triangles, clusters, duplicates dropped, vertices out, triangles out (the full counts),
+ * flipped (among all kept triangles); used = degenerate + duplicates + triangles out.  More vertices or triangles than the
+ * capacity: the first ones are written and pgx_check_status reports PGX_E_CAPACITY.
+ * Returned at once (PGX_E_BADARG), with nothing written: max_vertices, max_tris, max_out_vertices or max_out_tris outside
+ * [0, 2^28], cell not finite or <= 0, an origin that is not finite, lmin outside [0, 6], lmax outside [lmin, 6], flat_q outside
+ * [0, 1024], null required pointers (the four vertex inputs may be NULL with max_vertices == 0, d_tri with max_tris == 0, the four
+ * vertex outputs with max_out_vertices == 0, d_out_tri with max_out_tris == 0), an output that overlaps an input.
+ * Workspace: 30 bytes per entry of max_vertices, 28 per entry of max_tris, 157 per entry of the vertex tables (the power of two
+ * >= 2 max_vertices, at least 512), 4 per entry of the triangle table (likewise of max_tris), 16 per block of 256 entries; sized and
+ * carved before any launch: 1.3 GB for 2.8 M vertices and 4.6 M triangles, 84 GB at max_vertices = 2^28.  A workspace that cannot be
+ * allocated returns PGX_E_HIP with nothing launched: the practical limit is the device's free memory over 350 to 660 bytes a vertex.
+ * Results depend on the inputs only: the same bits from run to run, on a used workspace and from the host form; a permuted
+ * triangle list gives the same vertices bit for bit and the same set of triangle rows.
+ * Asynchronous on the context's stream. */
+int pgx_mesh_decimate_dev(pgx_ctx *ctx, const double *d_xyz /* [max_vertices][3] */, const float *d_normal /* [max_vertices][3] */,
+                          const uint32_t *d_rgba8 /* [max_vertices] */, const int32_t *d_info /* [max_vertices][4] */,
+                          const int32_t *d_tri /* [max_tris][3] */, const int32_t *d_counts /* [8] or NULL */, int max_vertices,
+                          int max_tris, double cell, double ox, double oy, double oz, int lmin, int lmax, int flat_q,
+                          int max_out_vertices, int max_out_tris, double *d_out_xyz /* [max_out_vertices][3] */,
+                          float *d_out_normal /* [max_out_vertices][3] */, uint32_t *d_out_rgba8 /* [max_out_vertices] */,
+                          int32_t *d_out_info /* [max_out_vertices][4] */, int32_t *d_out_tri /* [max_out_tris][3] */,
+                          int32_t *d_vertex_map /* [max_vertices] or NULL */, int32_t *d_level /* [max_vertices] or NULL */,
+                          int32_t *d_report /* [8] */);
+/* Host form: host arrays in the layouts above, the same kernels; it returns when the results are in the caller's buffers.  The
+ * mesh has n_vertices vertices and n_tris triangles (no d_counts); vertex_map and level may be NULL; the report is downloaded
+ * first, then min(report[5], max_out_vertices) rows of the four vertex outputs and min(report[6], max_out_tris) triangles. */
+int pgx_mesh_decimate(pgx_ctx *ctx, const double *xyz, const float *normal, const uint32_t *rgba8, const int32_t *info,
+                      const int32_t *tri, int n_vertices, int n_tris, double cell, double ox, double oy, double oz, int lmin, int lmax,
+                      int flat_q, int max_out_vertices, int max_out_tris, double *out_xyz, float *out_normal, uint32_t *out_rgba8,
+                      int32_t *out_info, int32_t *out_tri, int32_t *vertex_map, int32_t *level, int32_t *report);
+
 /* ---- measurement hooks (bench.py) ---------------------------------------------------- */
 /* When on, the named hot kernels are bracketed by HIP events on the launch stream. */
 int pgx_profile_enable(pgx_ctx *ctx, int on);

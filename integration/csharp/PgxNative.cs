@@ -337,6 +337,23 @@ internal static unsafe class PgxNative
                                                              uint* outRgba8, int* outInfo, int* outTri, int* vertexMap, int* comp,
                                                              int* report);
 
+    // The mesh decimated by adaptive vertex clustering.  A mesh in the layout above (dCounts: the report of pgx_mesh_dev, of
+    // pgx_mesh_clean_dev or of this call on the device, or null) with the vertices of a grid block of 2^l cells, l in lmin .. lmax,
+    // merged where the block's triangle normals agree (flatQ in 1/1024): dOutXyz .. dOutTri as the mesh's, dOutInfo =
+    // (name, level, members, 0), dVertexMap [maxVertices] and dLevel [maxVertices] int32 or null, dReport [8] ([5] vertices,
+    // [6] triangles out).  The host form takes host arrays in the same layouts
+    [DllImport(Lib)] public static extern int pgx_mesh_decimate_dev(IntPtr ctx, void* dXyz, void* dNormal, void* dRgba8, void* dInfo,
+                                                                    void* dTri, void* dCounts, int maxVertices, int maxTris, double cell,
+                                                                    double ox, double oy, double oz, int lmin, int lmax, int flatQ,
+                                                                    int maxOutVertices, int maxOutTris, void* dOutXyz, void* dOutNormal,
+                                                                    void* dOutRgba8, void* dOutInfo, void* dOutTri, void* dVertexMap,
+                                                                    void* dLevel, void* dReport);
+    [DllImport(Lib)] public static extern int pgx_mesh_decimate(IntPtr ctx, double* xyz, float* normal, uint* rgba8, int* info, int* tri,
+                                                                int nVertices, int nTris, double cell, double ox, double oy, double oz,
+                                                                int lmin, int lmax, int flatQ, int maxOutVertices, int maxOutTris,
+                                                                double* outXyz, float* outNormal, uint* outRgba8, int* outInfo,
+                                                                int* outTri, int* vertexMap, int* level, int* report);
+
     /// <summary>Maps a status code back to the exception type the managed implementation throws.</summary>
     public static void Check(IntPtr ctx, int rc)
     {

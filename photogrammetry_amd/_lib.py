@@ -117,6 +117,8 @@ SIGNATURES = {
     "pgx_mesh": (I, [P, P, P, I, P, P, I, I, I, I, I, P, P, I, P, D, D, D, D, I, I, I, I, I, I, P, P, P, P, P, P]),
     "pgx_mesh_clean_dev": (I, [P, P, P, P, P, P, P, I, I, D, D, D, D, I, I, I, D, D, I, I, P, P, P, P, P, P, P, P]),
     "pgx_mesh_clean": (I, [P, P, P, P, P, P, I, I, D, D, D, D, I, I, I, D, D, I, I, P, P, P, P, P, P, P, P]),
+    "pgx_mesh_decimate_dev": (I, [P, P, P, P, P, P, P, I, I, D, D, D, D, I, I, I, I, I, P, P, P, P, P, P, P, P]),
+    "pgx_mesh_decimate": (I, [P, P, P, P, P, P, I, I, D, D, D, D, I, I, I, I, I, P, P, P, P, P, P, P, P]),
     "pgx_profile_enable": (I, [P, I]),
     "pgx_profile_filter": (I, [P, S]),
     "pgx_profile_get": (I, [P, S, P, P]),

@@ -968,6 +968,54 @@ class Engine:
         return dict(xyz=oxyz[:kv], normal=onrm[:kv], rgba8=orgb[:kv], info=oinf[:kv], tri=otri[:kt],
                     vertex_map=None if vm is None else vm[:n], comp=None if cp is None else cp[:n], report=report)
 
+    # -- the mesh decimated: adaptive vertex clustering over grid blocks (pgx_mesh_decimate*) ----------------------
+    def mesh_decimate_dev(self, d_xyz, d_normal, d_rgba8, d_info, d_tri, d_counts, max_vertices, max_tris, cell, origin,
+                          max_out_vertices, max_out_tris, d_out_xyz, d_out_normal, d_out_rgba8, d_out_info, d_out_tri, d_report,
+                          lmin=0, lmax=3, flat_q=1015, d_vertex_map=None, d_level=None):
+        """pgx_mesh_decimate_dev: the mesh d_xyz .. d_tri in mesh_dev's layout (d_counts int32 [8] on the device: the report of
+        mesh_dev, mesh_clean_dev or of this call, or None: the capacities) with the vertices of a grid block of 2^l cells, l in
+        lmin .. lmax, merged where the block's triangle normals agree (|sum m| >= flat_q / 1024 of their number) on the grid of
+        `cell` at `origin`: d_out_xyz [max_out_vertices][3] float64, d_out_normal [max_out_vertices][3] float32, d_out_rgba8
+        [max_out_vertices] uint32, d_out_info [max_out_vertices][4] int32 = (name, L, members, 0), d_out_tri [max_out_tris][3] int32,
+        d_report [8] int32 ([5] vertices, [6] triangles out); d_vertex_map and d_level [max_vertices] int32 or None.  A capacity
+        exceeded: CapacityError from check_status.  No sync."""
+        ox, oy, oz = (float(x) for x in origin)
+        self._chk(self._L.pgx_mesh_decimate_dev(
+            self._h, _dptr(d_xyz), _dptr(d_normal), _dptr(d_rgba8), _dptr(d_info), _dptr(d_tri), _dptr(d_counts), int(max_vertices),
+            int(max_tris), float(cell), ox, oy, oz, int(lmin), int(lmax), int(flat_q), int(max_out_vertices), int(max_out_tris),
+            _dptr(d_out_xyz), _dptr(d_out_normal), _dptr(d_out_rgba8), _dptr(d_out_info), _dptr(d_out_tri), _dptr(d_vertex_map),
+            _dptr(d_level), _dptr(d_report)))
+
+    def mesh_decimate(self, xyz, normal, rgba8, info, tri, cell, origin, lmin=0, lmax=3, flat_q=1015, max_out_vertices=None,
+                      max_out_tris=None, vertex_map=True, level=True):
+        """The host form (pgx_mesh_decimate).  xyz [n][3] float64, normal [n][3] float32, rgba8 [n] uint32, info [n][4] int32 and tri
+        [t][3] int32 as mesh or mesh_clean return them -> dict(xyz [m][3], normal [m][3] float32, rgba8 [m], info [m][4], tri [k][3]
+        int32 trimmed to the counts of the report, vertex_map [n], level [n] or None, report [8]).  The capacities default to n and
+        t (they can then not be exceeded); a smaller one that cuts the mesh raises CapacityError."""
+        X = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+        n = len(X)
+        N = np.ascontiguousarray(normal, dtype=np.float32).reshape(n, 3)
+        col = np.ascontiguousarray(rgba8, dtype=np.uint32).reshape(n)
+        inf = np.ascontiguousarray(info, dtype=np.int32).reshape(n, 4)
+        T = np.ascontiguousarray(tri, dtype=np.int32).reshape(-1, 3)
+        t = len(T)
+        nv = n if max_out_vertices is None else int(max_out_vertices)
+        nt = t if max_out_tris is None else int(max_out_tris)
+        mv, mt = max(nv, 1), max(nt, 1)
+        oxyz, onrm = np.zeros((mv, 3)), np.zeros((mv, 3), dtype=np.float32)
+        orgb, oinf, otri = np.zeros(mv, dtype=np.uint32), np.zeros((mv, 4), dtype=np.int32), np.zeros((mt, 3), dtype=np.int32)
+        vm = np.zeros(max(n, 1), dtype=np.int32) if vertex_map else None
+        lv = np.zeros(max(n, 1), dtype=np.int32) if level else None
+        report = np.zeros(8, dtype=np.int32)
+        ox, oy, oz = (float(x) for x in origin)
+        self._chk(self._L.pgx_mesh_decimate(
+            self._h, _ptr(X) if n else None, _ptr(N) if n else None, _ptr(col) if n else None, _ptr(inf) if n else None,
+            _ptr(T) if t else None, n, t, float(cell), ox, oy, oz, int(lmin), int(lmax), int(flat_q), nv, nt, _ptr(oxyz), _ptr(onrm),
+            _ptr(orgb), _ptr(oinf), _ptr(otri), _ptr(vm), _ptr(lv), _ptr(report)))
+        kv, kt = min(int(report[5]), nv), min(int(report[6]), nt)
+        return dict(xyz=oxyz[:kv], normal=onrm[:kv], rgba8=orgb[:kv], info=oinf[:kv], tri=otri[:kt],
+                    vertex_map=None if vm is None else vm[:n], level=None if lv is None else lv[:n], report=report)
+
     # -- multi-GPU: the context's own RCCL communicator (pgx_comm_*) ------------------------------
     def comm_init(self, rank, world, unique_id):
         """Collective: every rank calls this with the 128 bytes rank 0 got from comm_unique_id()."""

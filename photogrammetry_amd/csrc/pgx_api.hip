@@ -114,6 +114,9 @@ int decode_status(pgx_ctx *c, int bits)
     if (bits & PGX_ST_MCL_CAP)
         return fail(c, PGX_E_CAPACITY, "mesh clean: more than max_out_vertices vertices or max_out_tris triangles were kept (the first "
                                        "ones were written)");
+    if (bits & PGX_ST_MDC_CAP)
+        return fail(c, PGX_E_CAPACITY, "mesh decimate: more than max_out_vertices vertices or max_out_tris triangles were kept (the "
+                                       "first ones were written)");
     if (bits & PGX_ST_DVW_CAP)
         return fail(c, PGX_E_CAPACITY, "dense views: n_tracks exceeds max_tracks (only the first max_tracks were processed)");
     if (bits & PGX_ST_DVW_NODE)
@@ -478,7 +481,7 @@ void pgx_ctx_destroy(pgx_ctx *c)
     for (hipEvent_t ev : c->ev_pool) (void)hipEventDestroy(ev);
     DevBuf *bufs[] = {&c->d_pairs, &c->d_plan, &c->d_steer_pairs, &c->d_steer_plans, &c->d_steer_dirs, &c->d_map, &c->d_gather, &c->ws_gray, &c->ws_seg, &c->ws_segoff, &c->ws_nraw, &c->ws_rawxy,
                       &c->ws_rawscore, &c->ws_nms, &c->ws_order, &c->ws_nkept, &c->st_a, &c->st_b, &c->st_c,
-                      &c->st_d, &c->st_e, &c->st_f, &c->ws_pose, &c->ws_tracks, &c->ws_tracks_split, &c->ws_agree, &c->ws_matchn[0], &c->ws_matchn[1], &c->ws_matchn[2], &c->ws_knn, &c->ws_guided, &c->ws_tri, &c->ws_ba, &c->ws_reg, &c->ws_ver, &c->ws_init, &c->ws_cns, &c->ws_vocab, &c->ws_depth, &c->ws_dviews, &c->ws_cloud, &c->ws_mesh, &c->ws_mclean,
+                      &c->st_d, &c->st_e, &c->st_f, &c->ws_pose, &c->ws_tracks, &c->ws_tracks_split, &c->ws_agree, &c->ws_matchn[0], &c->ws_matchn[1], &c->ws_matchn[2], &c->ws_knn, &c->ws_guided, &c->ws_tri, &c->ws_ba, &c->ws_reg, &c->ws_ver, &c->ws_init, &c->ws_cns, &c->ws_vocab, &c->ws_depth, &c->ws_dviews, &c->ws_cloud, &c->ws_mesh, &c->ws_mclean, &c->ws_mdec,
                       &c->ws_pyr_a, &c->ws_pyr_b, &c->ws_pyr_kp, &c->ws_pyr_desc, &c->ws_pyr_bins, &c->ws_pyr_cnt};
     for (DevBuf *b : bufs) b->release();
     c->pin_in.release();
@@ -1579,6 +1582,16 @@ int run_mesh_clean(pgx_ctx *c, MeshCleanArgs &a)
     return PGX_OK;
 }
 
+// the launcher brackets its own parts; the workspace is sized before any launch
+int run_mesh_decimate(pgx_ctx *c, MeshDecimateArgs &a)
+{
+    a.status = c->d_status;
+    HIPCHK(c, c->ws_mdec.ensure(pgx_mesh_decimate_ws_bytes(a)));
+    pgx_launch_mesh_decimate(c, c->stream, a, c->ws_mdec.p);
+    HIPCHK(c, hipGetLastError());
+    return PGX_OK;
+}
+
 // ---- the track graph as a stage sees it (inv: the launcher's)
 
 // a device form's: an offset may reach every slot
@@ -2638,6 +2651,96 @@ int pgx_mesh_clean(pgx_ctx *c, const double *xyz, const float *normal, const uin
     a.out_info = out.dev<int32_t>(o_i); a.out_tri = out.dev<int32_t>(o_t); a.vertex_map = out.dev<int32_t>(o_vm);
     a.comp = out.dev<int32_t>(o_cp); a.report = out.dev<int32_t>(o_r);
     if ((rs = run_mesh_clean(c, a)) != PGX_OK) return rs;
+    rs = download_images(c, out);   // the report and the per-vertex maps; waits for the stream
+    if (rs != PGX_OK && rs != PGX_E_CAPACITY) return rs;   // the report was not downloaded: nothing tells how many rows there are
+    const size_t kv = (size_t)(report[5] < max_out_vertices ? report[5] : max_out_vertices),
+                 kt = (size_t)(report[6] < max_out_tris ? report[6] : max_out_tris);
+    if (const int rf = fetch_rows(c, out, {{o_x, out_xyz, 24}, {o_n, out_normal, 12}, {o_c, out_rgba8, 4}, {o_i, out_info, 16}}, kv); rf != PGX_OK)
+        return rf;
+    if (const int rf = fetch_rows(c, out, {{o_t, out_tri, 12}}, kt); rf != PGX_OK) return rf;
+    return rs;
+}
+
+// ---- the mesh decimated: adaptive vertex clustering over grid blocks ----------------------------------------------------------
+
+namespace {
+// what the device and the host form of the decimation check alike
+int mesh_decimate_args(pgx_ctx *c, int max_vertices, int max_tris, double cell, double ox, double oy, double oz, int lmin, int lmax,
+                       int flat_q, int max_out_vertices, int max_out_tris)
+{
+    for (const int cap : {max_vertices, max_tris, max_out_vertices, max_out_tris})
+        if (cap < 0 || cap > (1 << 28))
+            return fail(c, PGX_E_BADARG, "max_vertices, max_tris, max_out_vertices and max_out_tris must be in [0, 2^28]");
+    if (!std::isfinite(cell) || !(cell > 0.0)) return fail(c, PGX_E_BADARG, "cell must be finite and > 0");
+    if (!std::isfinite(ox) || !std::isfinite(oy) || !std::isfinite(oz)) return fail(c, PGX_E_BADARG, "the origin must be finite");
+    if (lmin < 0 || lmin > 6) return fail(c, PGX_E_BADARG, "lmin = %d, must be in [0, 6]", lmin);
+    if (lmax < lmin || lmax > 6) return fail(c, PGX_E_BADARG, "lmax = %d, must be in [lmin, 6]", lmax);
+    if (flat_q < 0 || flat_q > 1024) return fail(c, PGX_E_BADARG, "flat_q = %d, must be in [0, 1024]", flat_q);
+    return PGX_OK;
+}
+
+void mesh_decimate_fill(MeshDecimateArgs &a, int max_vertices, int max_tris, double cell, double ox, double oy, double oz, int lmin, int lmax,
+                        int flat_q, int max_out_vertices, int max_out_tris)
+{
+    a.max_vertices = max_vertices; a.max_tris = max_tris; a.cell = cell; a.ox = ox; a.oy = oy; a.oz = oz; a.lmin = lmin; a.lmax = lmax;
+    a.flat_q = flat_q; a.max_out_vertices = max_out_vertices; a.max_out_tris = max_out_tris;
+}
+} // namespace
+
+int pgx_mesh_decimate_dev(pgx_ctx *c, const double *d_xyz, const float *d_normal, const uint32_t *d_rgba8, const int32_t *d_info,
+                          const int32_t *d_tri, const int32_t *d_counts, int max_vertices, int max_tris, double cell, double ox, double oy,
+                          double oz, int lmin, int lmax, int flat_q, int max_out_vertices, int max_out_tris, double *d_out_xyz,
+                          float *d_out_normal, uint32_t *d_out_rgba8, int32_t *d_out_info, int32_t *d_out_tri, int32_t *d_vertex_map,
+                          int32_t *d_level, int32_t *d_report)
+{
+    if (!c || !d_report || (max_vertices > 0 && (!d_xyz || !d_normal || !d_rgba8 || !d_info)) || (max_tris > 0 && !d_tri) ||
+        (max_out_vertices > 0 && (!d_out_xyz || !d_out_normal || !d_out_rgba8 || !d_out_info)) || (max_out_tris > 0 && !d_out_tri))
+        return c ? fail(c, PGX_E_BADARG, "null pointer") : PGX_E_BADARG;
+    Lock l(c);
+    const int rc = mesh_decimate_args(c, max_vertices, max_tris, cell, ox, oy, oz, lmin, lmax, flat_q, max_out_vertices, max_out_tris);
+    if (rc != PGX_OK) return rc;
+    const size_t nv = max_vertices, nt = max_tris, mv = max_out_vertices, mt = max_out_tris;
+    const Span in[] = {{d_xyz, nv * 24}, {d_normal, nv * 12}, {d_rgba8, nv * 4}, {d_info, nv * 16},
+                       {d_tri, nt * 12}, {d_counts, 32}},
+               out[] = {{d_out_xyz, mv * 24}, {d_out_normal, mv * 12}, {d_out_rgba8, mv * 4}, {d_out_info, mv * 16},
+                        {d_out_tri, mt * 12}, {d_vertex_map, nv * 4}, {d_level, nv * 4}, {d_report, 32}};
+    if (const int ra = no_alias(c, in, std::size(in), out, std::size(out)); ra != PGX_OK) return ra;
+    MeshDecimateArgs a{};
+    a.xyz = d_xyz; a.normal = d_normal; a.rgba8 = d_rgba8; a.info = d_info; a.tri = d_tri; a.counts = d_counts;
+    mesh_decimate_fill(a, max_vertices, max_tris, cell, ox, oy, oz, lmin, lmax, flat_q, max_out_vertices, max_out_tris);
+    a.out_xyz = d_out_xyz; a.out_normal = d_out_normal; a.out_rgba8 = d_out_rgba8; a.out_info = d_out_info; a.out_tri = d_out_tri;
+    a.vertex_map = d_vertex_map; a.level = d_level; a.report = d_report;
+    return run_mesh_decimate(c, a);
+}
+
+int pgx_mesh_decimate(pgx_ctx *c, const double *xyz, const float *normal, const uint32_t *rgba8, const int32_t *info, const int32_t *tri,
+                      int n_vertices, int n_tris, double cell, double ox, double oy, double oz, int lmin, int lmax, int flat_q,
+                      int max_out_vertices, int max_out_tris, double *out_xyz, float *out_normal, uint32_t *out_rgba8, int32_t *out_info,
+                      int32_t *out_tri, int32_t *vertex_map, int32_t *level, int32_t *report)
+{
+    if (!c || !report || (n_vertices > 0 && (!xyz || !normal || !rgba8 || !info)) || (n_tris > 0 && !tri) ||
+        (max_out_vertices > 0 && (!out_xyz || !out_normal || !out_rgba8 || !out_info)) || (max_out_tris > 0 && !out_tri))
+        return c ? fail(c, PGX_E_BADARG, "null pointer") : PGX_E_BADARG;
+    Lock l(c);
+    int rs = mesh_decimate_args(c, n_vertices, n_tris, cell, ox, oy, oz, lmin, lmax, flat_q, max_out_vertices, max_out_tris);
+    if (rs != PGX_OK) return rs;
+    const size_t nv = n_vertices, nt = n_tris, mv = max_out_vertices, mt = max_out_tris;
+    HostImage in, out;
+    const int i_x = in.add(xyz, nv, 24, 1), i_n = in.add(normal, nv, 12, 1), i_c = in.add(rgba8, nv, 4, 1), i_i = in.add(info, nv, 16, 1),
+              i_t = in.add(tri, nt, 12, 1);
+    // the report first: its download tells how many vertices and triangles there are to fetch
+    const int o_r = out.add(report, 8, 4, 64), o_vm = out.add(vertex_map, nv, 4, 1, vertex_map != nullptr),
+              o_lv = out.add(level, nv, 4, 1, level != nullptr), o_x = out.add(nullptr, 0, 24, mv + 1), o_n = out.add(nullptr, 0, 12, mv + 1),
+              o_c = out.add(nullptr, 0, 4, mv + 1), o_i = out.add(nullptr, 0, 16, mv + 1), o_t = out.add(nullptr, 0, 12, mt + 1);
+    if ((rs = stage_images(c, in, out)) != PGX_OK) return rs;
+    MeshDecimateArgs a{};
+    a.xyz = in.dev<double>(i_x); a.normal = in.dev<float>(i_n); a.rgba8 = in.dev<uint32_t>(i_c); a.info = in.dev<int32_t>(i_i);
+    a.tri = in.dev<int32_t>(i_t); a.counts = nullptr;
+    mesh_decimate_fill(a, n_vertices, n_tris, cell, ox, oy, oz, lmin, lmax, flat_q, max_out_vertices, max_out_tris);
+    a.out_xyz = out.dev<double>(o_x); a.out_normal = out.dev<float>(o_n); a.out_rgba8 = out.dev<uint32_t>(o_c);
+    a.out_info = out.dev<int32_t>(o_i); a.out_tri = out.dev<int32_t>(o_t); a.vertex_map = out.dev<int32_t>(o_vm);
+    a.level = out.dev<int32_t>(o_lv); a.report = out.dev<int32_t>(o_r);
+    if ((rs = run_mesh_decimate(c, a)) != PGX_OK) return rs;
     rs = download_images(c, out);   // the report and the per-vertex maps; waits for the stream
     if (rs != PGX_OK && rs != PGX_E_CAPACITY) return rs;   // the report was not downloaded: nothing tells how many rows there are
     const size_t kv = (size_t)(report[5] < max_out_vertices ? report[5] : max_out_vertices),

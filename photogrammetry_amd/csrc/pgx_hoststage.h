@@ -1,8 +1,8 @@
 // pgx_hoststage.h -- buffers laid out in 256-byte-aligned sections: the workspace carver of the launchers and, on it, the
-// image that a host form uploads or downloads in (HostImage), with the section lists that the nineteen host forms on it share:
+// image that a host form uploads or downloads in (HostImage), with the section lists that the twenty host forms on it share:
 // tracks_in (triangulation, bundle adjustment, registration, track consensus), pair_in (verification, relative pose),
-// two_sets_in and knn_out (pgx_match, pgx_knn, pgx_knn_guided), batch_in (pgx_match_batch).  The other nine (pgx_vocab_train,
-// pgx_select_pairs, pgx_depth_maps, pgx_depth_fuse, pgx_dense_views, pgx_rgba8_batch, pgx_cloud_merge, pgx_mesh, pgx_mesh_clean)
+// two_sets_in and knn_out (pgx_match, pgx_knn, pgx_knn_guided), batch_in (pgx_match_batch).  The other ten (pgx_vocab_train,
+// pgx_select_pairs, pgx_depth_maps, pgx_depth_fuse, pgx_dense_views, pgx_rgba8_batch, pgx_cloud_merge, pgx_mesh, pgx_mesh_clean, pgx_mesh_decimate)
 // declare their lists where they stand in pgx_api.hip.
 // Host code without HIP: tests/hoststage_driver.cpp builds it with g++ under sanitizers, and pgx_api.hip puts the copies
 // around it (stage_images, download_images).  Internal to libpgx.so; DESIGN.md section 14g.

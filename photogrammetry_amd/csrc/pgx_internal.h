@@ -45,6 +45,8 @@
 #define PGX_ST_CLD_CAP    268435456u /* pgx_cloud_merge_dev: more than max_points cells kept */
 #define PGX_ST_MSH_CAP    536870912u /* pgx_mesh_dev: more than max_voxels voxels, max_vertices vertices or max_tris triangles */
 #define PGX_ST_MCL_CAP    1073741824u /* pgx_mesh_clean_dev: more than max_out_vertices vertices or max_out_tris triangles kept */
+/* bit 31, the last one: the word is an int on the device and in decode_status, where `bits & 2147483648u` converts it to unsigned */
+#define PGX_ST_MDC_CAP    2147483648u /* pgx_mesh_decimate_dev: more than max_out_vertices vertices or max_out_tris triangles kept */
 
 // key = (distance << PGX_IDX_BITS) | index ; limits: index < 2^20, distance < 2^12
 #define PGX_IDX_BITS 20
@@ -169,6 +171,7 @@ struct pgx_ctx {
     DevBuf ws_cloud;  // pgx_cloud_merge*: the cell table, per-point records, block sums, the accumulators of the kept cells
     DevBuf ws_mesh;   // pgx_mesh*: the node table with its sums, flags and indices, per-point entries, block sums
     DevBuf ws_mclean; // pgx_mesh_clean*: the union-find, counts and indices per vertex, two position buffers, rows and flags per triangle, block sums
+    DevBuf ws_mdec;   // pgx_mesh_decimate*: positions, levels and cluster entries per vertex, the level and cluster tables, triples per triangle, block sums
     DevBuf ws_dviews; // pgx_dense_views*: pair-count table, frame table, depths bucketed by frame, per-frame counts and cursors
     DevBuf ws_init;   // pgx_init_pair_dev, pgx_relative_pose: per image pair the two rotations, t, the intrinsics and the counters
     hipStream_t mstream[3] = {nullptr, nullptr, nullptr}; // [0] wide rounds, [1] residual distance rows, [2] per-pair finish

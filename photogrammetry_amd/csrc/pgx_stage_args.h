@@ -382,3 +382,53 @@ struct MeshCleanArgs {
 };
 size_t pgx_mesh_clean_ws_bytes(const MeshCleanArgs &a);
 void pgx_launch_mesh_clean(pgx_ctx *ctx, hipStream_t s, MeshCleanArgs a, void *ws);
+
+// ---- k_meshdecimate.hip (the mesh decimated: adaptive vertex clustering over grid blocks; pgx_mesh_decimate_dev semantics) ---
+// ctx: the profiling groups mdec_init / mdec_tris / mdec_levels / mdec_clusters / mdec_dedup / mdec_rank / mdec_emit / mdec_normals
+struct MeshDecimateArgs {
+    // the caller fills
+    const double *xyz;            // [max_vertices][3]
+    const float *normal;          // [max_vertices][3]: of the layout, not read
+    const uint32_t *rgba8;        // [max_vertices]
+    const int32_t *info;          // [max_vertices][4]: of the layout, not read
+    const int32_t *tri;           // [max_tris][3]
+    const int32_t *counts;        // [5] = the vertices, [6] = the triangles (a mesh stage's report), or nullptr: the capacities
+    int max_vertices, max_tris;
+    double cell, ox, oy, oz;
+    int lmin, lmax, flat_q, max_out_vertices, max_out_tris;
+    double *out_xyz;              // [max_out_vertices][3]
+    float *out_normal;            // [max_out_vertices][3]
+    uint32_t *out_rgba8;          // [max_out_vertices]
+    int32_t *out_info;            // [max_out_vertices][4] = (name, L, n, 0)
+    int32_t *out_tri;             // [max_out_tris][3]
+    int32_t *vertex_map;          // [max_vertices] or nullptr
+    int32_t *level;               // [max_vertices] or nullptr
+    int32_t *report;              // [8]
+    // the launcher fills (workspace, derived)
+    int lg_vcap, lg_tcap;         // the carved tables have 1 << lg_vcap and 1 << lg_tcap entries; the device uses 1 << meta[2], 1 << meta[3] of them
+    long long *q;                 // [max_vertices][3]: the fixed-point positions
+    unsigned char *member;        // [max_vertices]: the vertex is in a used triangle
+    unsigned char *lev;           // [max_vertices]: L(v) so far
+    int32_t *vslot;               // [max_vertices]: the entry of a member's cluster
+    unsigned long long *fkey[2];  // [1 << lg_vcap] each: the blocks of one level (two tables, a level and the one above), MDC_EMPTY = none
+    unsigned long long *fsum[2];  // [1 << lg_vcap][4] each: S_0, S_1, S_2, N of the block
+    unsigned long long *ckey;     // [1 << lg_vcap]: the clusters' keys
+    int32_t *cname;               // [..]: the cluster's smallest member
+    int32_t *cn;                  // [..]: its members
+    int32_t *cnew;                // [..]: its output index, -1 = in no kept triangle (then cused is 0)
+    unsigned char *cused;         // [..]: a kept triangle holds it
+    unsigned long long *cs;       // [..][3]: the sums of q - org; from k_mdc_emit on Q
+    unsigned long long *csc;      // [..][4]: the sums of the colour bytes; from k_mdc_emit on [0..2] the sums of the triangles' m
+    int32_t *trot;                // [max_tris][3]: the rotated triple of cluster entries, [0] = -1: not used or degenerate
+    unsigned long long *tm;       // [max_tris]: m of rule 2, 16 bits a component
+    int32_t *tslot;               // [max_tris]: the triangle's entry of the table of triples
+    int32_t *towner;              // [1 << lg_tcap]: the smallest triangle of the entry's triple, -1 = none
+    int32_t *tnew;                // [max_tris]: the new index of a kept triangle, -1 otherwise
+    unsigned long long *bsum, *boff;   // [nb]: output vertices | kept triangles << 32 per block of 256 indices, their exclusive scan
+    int32_t *meta;                // [16]: nv, nt, lg of the vertex tables, lg of the triple table, used, clusters, non-degenerate, vertices out, triangles out
+    int nb;                       // blocks of 256 indices of max(max_vertices, max_tris)
+    // the caller fills
+    int *status;                  // an output capacity exceeded: PGX_ST_MDC_CAP
+};
+size_t pgx_mesh_decimate_ws_bytes(const MeshDecimateArgs &a);
+void pgx_launch_mesh_decimate(pgx_ctx *ctx, hipStream_t s, MeshDecimateArgs a, void *ws);

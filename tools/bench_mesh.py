@@ -4,7 +4,9 @@ frames on a line, the filter's list of their depth maps (a smooth synthetic surf
 call, and the whole pgx_cloud_merge_dev call on the same list for scale; then the mesh by pass from the stage's profiling groups
 (pgx_profile_get) in a second pass.  With --clean, pgx_mesh_clean_dev on the mesh's outputs and report:
 the whole call without smoothing and with --clean-iters iterations, and its passes as medians over the calls (one profile read
-per call).  Writes profiles/mesh_<shape>.json, with --clean profiles/mesh_clean_<shape>.json (or --out DIR)."""
+per call).  With --clean --decimate, pgx_mesh_decimate_dev behind the clean stage, on its outputs and report: the
+whole call and its passes for a uniform and an adaptive setting.  Writes profiles/mesh_<shape>.json, with --clean
+profiles/mesh_clean_<shape>.json, with --decimate profiles/mesh_decimate_<shape>.json (or --out DIR)."""
 import argparse
 import os
 import sys
@@ -21,6 +23,8 @@ from bench_depth import cameras  # noqa: E402
 from geom_bench import DEV, F64, I32  # noqa: E402
 
 CLEAN_PARTS = ("mclean_init", "mclean_union", "mclean_count", "mclean_rank", "mclean_emit", "mclean_rows", "mclean_smooth", "mclean_normals")
+DECIMATE_PARTS = ("mdec_init", "mdec_tris", "mdec_levels", "mdec_clusters", "mdec_dedup", "mdec_rank", "mdec_emit", "mdec_normals")
+DECIMATE_SETTINGS = (("uniform", 1, 1, 1015), ("adaptive", 0, 3, 1015), ("adaptive6", 0, 6, 1015))
 PARTS = ("mesh_plan", "mesh_seed", "mesh_dilate", "mesh_tsdf", "mesh_cubes", "mesh_rank", "mesh_vertices", "mesh_tris")
 
 
@@ -58,6 +62,42 @@ def bench_clean(eng, args, mesh_out, rep, nv, nt, cell, origin):
     return out
 
 
+def bench_decimate(eng, args, mesh_out, rep, nv, nt, cell, origin):
+    """pgx_mesh_decimate_dev behind pgx_mesh_clean_dev (--clean-iters iterations) on the clean stage's outputs where they lie, the
+    counts from its report on the device -> the record"""
+    def bufs():
+        return (torch.empty((max(nv, 1), 3), **F64), torch.empty((max(nv, 1), 3), dtype=torch.float32, device=DEV), torch.empty(max(nv, 1), **I32),
+                torch.empty((max(nv, 1), 4), **I32), torch.empty((max(nt, 1), 3), **I32), torch.empty(8, **I32))
+    c, d = bufs(), bufs()
+    eng.mesh_clean_dev(*mesh_out, rep, nv, nt, cell, origin, nv, nt, *c, min_tris=args.min_tris, iters=args.clean_iters, lam=0.5, mu=-0.53)
+    eng.check_status()
+    crep = c[5].cpu().tolist()
+    out = dict(clean_iters=args.clean_iters, clean_report=crep)
+    for name, lmin, lmax, flat_q in DECIMATE_SETTINGS:
+        def decimate():
+            eng.mesh_decimate_dev(*c, nv, nt, cell, origin, nv, nt, *d, lmin=lmin, lmax=lmax, flat_q=flat_q)
+        ms = gb.time_on_stream(eng, decimate, args.steps, args.warmup)
+        eng.profile_enable(True)
+        per = {p: [] for p in DECIMATE_PARTS}
+        for _ in range(args.steps):
+            eng.profile_reset()
+            decimate()
+            for p in DECIMATE_PARTS:
+                per[p].append(eng.profile_get(p)[1])
+        eng.profile_enable(False)
+        eng.check_status()
+        parts = {p: round(float(np.median(v)), 4) for p, v in per.items()}
+        r = d[5].cpu().tolist()
+        # what the incidence pass must move: per triangle its indices (12 B), the used mark and m (4 + 8 B written); per vertex its
+        # position once (24 B; the other reads of it hit in cache) and the member byte
+        floor_bytes = r[1] * 24 + r[0] * 25
+        out[name] = dict(lmin=lmin, lmax=lmax, flat_q=flat_q, ms_median=float(np.median(ms)), ms_min=float(ms.min()), ms_max=float(ms.max()),
+                         parts_ms=parts, report=r, tris_floor_bytes=floor_bytes,
+                         tris_gbps=(floor_bytes / (parts["mdec_tris"] * 1e-3) / 1e9 if parts["mdec_tris"] > 0 else None),
+                         tris_ns_per_triangle=parts["mdec_tris"] * 1e6 / max(r[1], 1))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=9)
@@ -72,10 +112,12 @@ def main():
     ap.add_argument("--max-voxels", type=int, default=1 << 25)
     ap.add_argument("--clean", action="store_true", help="also time pgx_mesh_clean_dev behind the mesh")
     ap.add_argument("--clean-iters", type=int, default=5)
+    ap.add_argument("--decimate", action="store_true", help="with --clean: also time pgx_mesh_decimate_dev behind the clean stage")
     ap.add_argument("--min-tris", type=int, default=100)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles"))
     args = ap.parse_args()
     assert args.steps >= 7, "the median of at least 7 calls"
+    assert args.clean or not args.decimate, "--decimate follows the clean stage: give --clean too"
     W, H, F, R, S, focal = args.width, args.height, args.frames, args.refs, 4, 1500.0
     eng = pg.Engine(0)
     torch.manual_seed(0)
@@ -126,7 +168,9 @@ def main():
                cloud_merge_ms_median=float(np.median(ms_merge)), cloud_report=crep.cpu().tolist(), fuse_summary=fsum.cpu().tolist())
     if args.clean:
         rec["clean"] = bench_clean(eng, args, (oxyz, onrm, orgb, oinf, otri), rep, report[5], report[6], cell, origin)
-    gb.write_record(rec, args.out, "mesh_clean" if args.clean else "mesh")
+    if args.decimate:
+        rec["decimate"] = bench_decimate(eng, args, (oxyz, onrm, orgb, oinf, otri), rep, report[5], report[6], cell, origin)
+    gb.write_record(rec, args.out, "mesh_decimate" if args.decimate else "mesh_clean" if args.clean else "mesh")
     eng.close()
 
 

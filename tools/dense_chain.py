@@ -5,7 +5,9 @@ seeded noise, so the maps carry no meaning: the tool shows that the chain runs a
 geom_bench's loop; prints one JSON line and writes profiles/dense_chain_<shape>.json (or --out DIR).  --mesh adds pgx_mesh_dev
 behind the cloud and writes profiles/dense_chain_mesh_<shape>.json; --mesh --clean adds pgx_mesh_clean_dev
 behind the mesh on the same stream (the mesh's outputs and its report on the device, no wait between them),
-its time as clean_ms in the record dense_chain_mesh_clean_<shape>.json; the default run is the chain above."""
+its time as clean_ms in the record dense_chain_mesh_clean_<shape>.json; --mesh --clean --decimate adds pgx_mesh_decimate_dev behind
+the clean stage in the same way, its time as decimate_ms in dense_chain_mesh_clean_decimate_<shape>.json; the
+default run is the chain above."""
 import argparse
 import os
 import sys
@@ -23,6 +25,7 @@ PARTS = ("triangulate", "dense_views_nodes", "dense_views_pairs", "dense_views_s
          "depth_sweep", "depth_fuse", "dewarp_rgba8", "cloud_plan", "cloud_normals", "cloud_points", "cloud_rank", "cloud_accum",
          "cloud_final")
 CLEAN_PARTS = ("mclean_init", "mclean_union", "mclean_count", "mclean_rank", "mclean_emit", "mclean_rows", "mclean_smooth", "mclean_normals")
+DECIMATE_PARTS = ("mdec_init", "mdec_tris", "mdec_levels", "mdec_clusters", "mdec_dedup", "mdec_rank", "mdec_emit", "mdec_normals")
 MESH_PARTS = ("mesh_plan", "mesh_seed", "mesh_dilate", "mesh_tsdf", "mesh_cubes", "mesh_rank", "mesh_vertices", "mesh_tris")
 
 
@@ -40,9 +43,11 @@ def main():
     ap.add_argument("--mesh", action="store_true", help="pgx_mesh_dev behind the cloud (band 2, truncation 3 cells); the record is dense_chain_mesh_*")
     ap.add_argument("--clean", action="store_true", help="with --mesh: pgx_mesh_clean_dev behind the mesh (min_tris 100, --clean-iters Taubin steps); the record is dense_chain_mesh_clean_*")
     ap.add_argument("--clean-iters", type=int, default=5)
+    ap.add_argument("--decimate", action="store_true", help="with --mesh --clean: pgx_mesh_decimate_dev behind the clean stage (lmin 0, lmax 3, flat_q 1015); the record is dense_chain_mesh_clean_decimate_*")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles"))
     args = ap.parse_args()
     assert args.mesh or not args.clean, "--clean cleans the mesh: give --mesh too"
+    assert args.clean or not args.decimate, "--decimate follows the clean stage: give --mesh --clean too"
     W, H, nf, S, D = args.width, args.height, args.frames, args.sources, args.planes
     rng = np.random.default_rng(0)
     eng = pg.Engine(0)
@@ -71,6 +76,10 @@ def main():
         parts_of = parts_of + CLEAN_PARTS
         cxyz, cnrm = torch.empty((mv, 3), **F64), torch.empty((mv, 3), dtype=torch.float32, device=DEV)
         crgb, cinf, ctri, clrep = torch.empty(mv, **I32), torch.empty((mv, 4), **I32), torch.empty((mt, 3), **I32), torch.empty(8, **I32)
+    if args.decimate:
+        parts_of = parts_of + DECIMATE_PARTS
+        dxyz, dnrm = torch.empty((mv, 3), **F64), torch.empty((mv, 3), dtype=torch.float32, device=DEV)
+        drgb, dinf, dtri, dcrep = torch.empty(mv, **I32), torch.empty((mv, 4), **I32), torch.empty((mt, 3), **I32), torch.empty(8, **I32)
     torch.cuda.synchronize()
 
     def chain():
@@ -88,6 +97,9 @@ def main():
         if args.clean:
             eng.mesh_clean_dev(mxyz, mnrm, mrgb, minf, mtri, mrep, mv, mt, args.cell, origin, mv, mt, cxyz, cnrm, crgb, cinf, ctri, clrep,
                                min_tris=100, iters=args.clean_iters, lam=0.5, mu=-0.53)
+        if args.decimate:
+            eng.mesh_decimate_dev(cxyz, cnrm, crgb, cinf, ctri, clrep, mv, mt, args.cell, origin, mv, mt, dxyz, dnrm, drgb, dinf, dtri, dcrep,
+                                  lmin=0, lmax=3, flat_q=1015)
     ms = gb.time_on_stream(eng, chain, args.steps, args.warmup)
     eng.profile_reset()
     eng.profile_enable(True)
@@ -105,7 +117,10 @@ def main():
     if args.clean:
         rec["clean_report"] = clrep.cpu().tolist()
         rec["clean_ms"] = round(sum(parts[p] for p in CLEAN_PARTS), 4)
-    gb.write_record(rec, args.out, "dense_chain_mesh_clean" if args.clean else ("dense_chain_mesh" if args.mesh else "dense_chain"))
+    if args.decimate:
+        rec["decimate_report"] = dcrep.cpu().tolist()
+        rec["decimate_ms"] = round(sum(parts[p] for p in DECIMATE_PARTS), 4)
+    gb.write_record(rec, args.out, "dense_chain_mesh_clean_decimate" if args.decimate else "dense_chain_mesh_clean" if args.clean else ("dense_chain_mesh" if args.mesh else "dense_chain"))
     eng.close()
 
 
