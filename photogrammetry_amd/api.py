@@ -104,6 +104,42 @@ def _desc_pair(desc1, desc2):
     return d1, d2, words
 
 
+def _dense_inputs(xyz, src, depth, views, cameras, rgba8):
+    """what cloud_merge and mesh take alike, converted: the list (xyz [n][3], src [n][2]), depth [R][H][W], views [R][1 + S], cameras
+    [n_frames][12] and rgba8 [n_frames][H][W] or None"""
+    X = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+    sr = np.ascontiguousarray(src, dtype=np.int32).reshape(-1, 2)
+    d = np.ascontiguousarray(depth, dtype=np.float64)
+    R, H, W = d.shape
+    vw = np.ascontiguousarray(views, dtype=np.int32)
+    vw = vw.reshape(R, vw.shape[-1])
+    P = np.ascontiguousarray(cameras, dtype=np.float64).reshape(-1, 12)
+    col = None if rgba8 is None else np.ascontiguousarray(rgba8, dtype=np.uint32).reshape(len(P), H, W)
+    return X, sr, d, vw, P, col
+
+
+def _mesh_inputs(xyz, normal, rgba8, info, tri):
+    """the five arrays of a mesh in pgx_mesh's layout, converted"""
+    X = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+    n = len(X)
+    return (X, np.ascontiguousarray(normal, dtype=np.float32).reshape(n, 3), np.ascontiguousarray(rgba8, dtype=np.uint32).reshape(n),
+            np.ascontiguousarray(info, dtype=np.int32).reshape(n, 4), np.ascontiguousarray(tri, dtype=np.int32).reshape(-1, 3))
+
+
+def _mesh_outputs(nv, nt):
+    """... for a stage to write at most nv vertices and nt triangles into, and its report"""
+    mv, mt = max(nv, 1), max(nt, 1)
+    return (np.zeros((mv, 3)), np.zeros((mv, 3), dtype=np.float32), np.zeros(mv, dtype=np.uint32), np.zeros((mv, 4), dtype=np.int32),
+            np.zeros((mt, 3), dtype=np.int32), np.zeros(8, dtype=np.int32))
+
+
+def _mesh_result(out, nv, nt, **per_vertex):
+    """... trimmed to the counts of the report, with the stage's per-vertex maps"""
+    oxyz, onrm, orgb, oinf, otri, report = out
+    kv, kt = min(int(report[5]), nv), min(int(report[6]), nt)
+    return dict(xyz=oxyz[:kv], normal=onrm[:kv], rgba8=orgb[:kv], info=oinf[:kv], tri=otri[:kt], **per_vertex, report=report)
+
+
 class Engine:
     """One pgx context = one GPU (pgx_ctx_create).  Thin, 1:1 with the C ABI."""
 
@@ -846,15 +882,8 @@ class Engine:
         views [R][1 + S], cameras [n_frames][3][4], rgba8 [n_frames][H][W] uint32 or None -> dict(xyz [m][3], normal [m][3]
         float32, rgba8 [m], info [m][4] trimmed to min(report[6], max_points), pt_normal [n][3], cell_of [n] or None, report [8]).
         max_points defaults to n; a smaller one that cuts the cloud raises CapacityError."""
-        X = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
-        sr = np.ascontiguousarray(src, dtype=np.int32).reshape(-1, 2)
-        n = len(X)
-        d = np.ascontiguousarray(depth, dtype=np.float64)
-        R, H, W = d.shape
-        vw = np.ascontiguousarray(views, dtype=np.int32)
-        vw = vw.reshape(R, vw.shape[-1])
-        P = np.ascontiguousarray(cameras, dtype=np.float64).reshape(-1, 12)
-        col = None if rgba8 is None else np.ascontiguousarray(rgba8, dtype=np.uint32).reshape(len(P), H, W)
+        X, sr, d, vw, P, col = _dense_inputs(xyz, src, depth, views, cameras, rgba8)
+        n, (R, H, W) = len(X), d.shape
         cap = n if max_points is None else int(max_points)
         m = max(cap, 1)
         oxyz, onrm = np.zeros((m, 3)), np.zeros((m, 3), dtype=np.float32)
@@ -894,31 +923,20 @@ class Engine:
         dict(xyz [m][3], normal [m][3] float32, rgba8 [m], info [m][4], tri [t][3] int32, report [8]), trimmed to the counts of
         the report.  max_voxels defaults to (2 band)^3 n, max_vertices to max_voxels, max_tris to 6 max_voxels (none of them can
         then be exceeded); a smaller one that cuts the mesh raises CapacityError."""
-        X = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
-        sr = np.ascontiguousarray(src, dtype=np.int32).reshape(-1, 2)
-        n = len(X)
-        d = np.ascontiguousarray(depth, dtype=np.float64)
-        R, H, W = d.shape
-        vw = np.ascontiguousarray(views, dtype=np.int32)
-        vw = vw.reshape(R, vw.shape[-1])
-        P = np.ascontiguousarray(cameras, dtype=np.float64).reshape(-1, 12)
+        X, sr, d, vw, P, col = _dense_inputs(xyz, src, depth, views, cameras, rgba8)
+        n, (R, H, W) = len(X), d.shape
         ag = None if agree is None else np.ascontiguousarray(agree, dtype=np.int32).reshape(R, H, W)
-        col = None if rgba8 is None else np.ascontiguousarray(rgba8, dtype=np.uint32).reshape(len(P), H, W)
         lim = 1 << 28
         nvox = min((2 * int(band)) ** 3 * n, lim) if max_voxels is None else int(max_voxels)
         nv = nvox if max_vertices is None else int(max_vertices)
         nt = min(6 * nvox, lim) if max_tris is None else int(max_tris)
-        mv, mt = max(nv, 1), max(nt, 1)
-        oxyz, onrm = np.zeros((mv, 3)), np.zeros((mv, 3), dtype=np.float32)
-        orgb, oinf, otri = np.zeros(mv, dtype=np.uint32), np.zeros((mv, 4), dtype=np.int32), np.zeros((mt, 3), dtype=np.int32)
-        report = np.zeros(8, dtype=np.int32)
+        out = _mesh_outputs(nv, nt)
         ox, oy, oz = (float(x) for x in origin)
         self._chk(self._L.pgx_mesh(
             self._h, _ptr(X) if n else None, _ptr(sr) if n else None, n, _ptr(d), _ptr(vw), R, vw.shape[1] - 1, W, H, len(P), _ptr(P),
             _ptr(ag), int(min_agree), _ptr(col), float(cell), ox, oy, oz, int(band), int(trunc_cells), int(min_weight), nvox, nv, nt,
-            _ptr(oxyz), _ptr(onrm), _ptr(orgb), _ptr(oinf), _ptr(otri), _ptr(report)))
-        kv, kt = min(int(report[5]), nv), min(int(report[6]), nt)
-        return dict(xyz=oxyz[:kv], normal=onrm[:kv], rgba8=orgb[:kv], info=oinf[:kv], tri=otri[:kt], report=report)
+            *(_ptr(o) for o in out)))
+        return _mesh_result(out, nv, nt)
 
     # -- the mesh cleaned: small components dropped, smoothed, normals again (pgx_mesh_clean*) ---------------------
     def mesh_clean_dev(self, d_xyz, d_normal, d_rgba8, d_info, d_tri, d_counts, max_vertices, max_tris, cell, origin,
@@ -944,29 +962,18 @@ class Engine:
         [t][3] int32 as mesh returns them -> dict(xyz [m][3], normal [m][3] float32, rgba8 [m], info [m][4], tri [k][3] int32
         trimmed to the counts of the report, vertex_map [n], comp [n] or None, report [8]).  The capacities default to n and t
         (they can then not be exceeded); a smaller one that cuts the mesh raises CapacityError."""
-        X = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
-        n = len(X)
-        N = np.ascontiguousarray(normal, dtype=np.float32).reshape(n, 3)
-        col = np.ascontiguousarray(rgba8, dtype=np.uint32).reshape(n)
-        inf = np.ascontiguousarray(info, dtype=np.int32).reshape(n, 4)
-        T = np.ascontiguousarray(tri, dtype=np.int32).reshape(-1, 3)
-        t = len(T)
+        arrays = _mesh_inputs(xyz, normal, rgba8, info, tri)
+        n, t = len(arrays[0]), len(arrays[4])
         nv = n if max_out_vertices is None else int(max_out_vertices)
         nt = t if max_out_tris is None else int(max_out_tris)
-        mv, mt = max(nv, 1), max(nt, 1)
-        oxyz, onrm = np.zeros((mv, 3)), np.zeros((mv, 3), dtype=np.float32)
-        orgb, oinf, otri = np.zeros(mv, dtype=np.uint32), np.zeros((mv, 4), dtype=np.int32), np.zeros((mt, 3), dtype=np.int32)
+        out = _mesh_outputs(nv, nt)
         vm = np.zeros(max(n, 1), dtype=np.int32) if vertex_map else None
         cp = np.zeros(max(n, 1), dtype=np.int32) if comp else None
-        report = np.zeros(8, dtype=np.int32)
         ox, oy, oz = (float(x) for x in origin)
         self._chk(self._L.pgx_mesh_clean(
-            self._h, _ptr(X) if n else None, _ptr(N) if n else None, _ptr(col) if n else None, _ptr(inf) if n else None,
-            _ptr(T) if t else None, n, t, float(cell), ox, oy, oz, int(min_tris), int(min_frac_pm), int(iters), float(lam), float(mu),
-            nv, nt, _ptr(oxyz), _ptr(onrm), _ptr(orgb), _ptr(oinf), _ptr(otri), _ptr(vm), _ptr(cp), _ptr(report)))
-        kv, kt = min(int(report[5]), nv), min(int(report[6]), nt)
-        return dict(xyz=oxyz[:kv], normal=onrm[:kv], rgba8=orgb[:kv], info=oinf[:kv], tri=otri[:kt],
-                    vertex_map=None if vm is None else vm[:n], comp=None if cp is None else cp[:n], report=report)
+            self._h, *(_ptr(a) if len(a) else None for a in arrays), n, t, float(cell), ox, oy, oz, int(min_tris), int(min_frac_pm),
+            int(iters), float(lam), float(mu), nv, nt, *(_ptr(o) for o in out[:5]), _ptr(vm), _ptr(cp), _ptr(out[5])))
+        return _mesh_result(out, nv, nt, vertex_map=None if vm is None else vm[:n], comp=None if cp is None else cp[:n])
 
     # -- the mesh decimated: adaptive vertex clustering over grid blocks (pgx_mesh_decimate*) ----------------------
     def mesh_decimate_dev(self, d_xyz, d_normal, d_rgba8, d_info, d_tri, d_counts, max_vertices, max_tris, cell, origin,
@@ -992,29 +999,18 @@ class Engine:
         [t][3] int32 as mesh or mesh_clean return them -> dict(xyz [m][3], normal [m][3] float32, rgba8 [m], info [m][4], tri [k][3]
         int32 trimmed to the counts of the report, vertex_map [n], level [n] or None, report [8]).  The capacities default to n and
         t (they can then not be exceeded); a smaller one that cuts the mesh raises CapacityError."""
-        X = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
-        n = len(X)
-        N = np.ascontiguousarray(normal, dtype=np.float32).reshape(n, 3)
-        col = np.ascontiguousarray(rgba8, dtype=np.uint32).reshape(n)
-        inf = np.ascontiguousarray(info, dtype=np.int32).reshape(n, 4)
-        T = np.ascontiguousarray(tri, dtype=np.int32).reshape(-1, 3)
-        t = len(T)
+        arrays = _mesh_inputs(xyz, normal, rgba8, info, tri)
+        n, t = len(arrays[0]), len(arrays[4])
         nv = n if max_out_vertices is None else int(max_out_vertices)
         nt = t if max_out_tris is None else int(max_out_tris)
-        mv, mt = max(nv, 1), max(nt, 1)
-        oxyz, onrm = np.zeros((mv, 3)), np.zeros((mv, 3), dtype=np.float32)
-        orgb, oinf, otri = np.zeros(mv, dtype=np.uint32), np.zeros((mv, 4), dtype=np.int32), np.zeros((mt, 3), dtype=np.int32)
+        out = _mesh_outputs(nv, nt)
         vm = np.zeros(max(n, 1), dtype=np.int32) if vertex_map else None
         lv = np.zeros(max(n, 1), dtype=np.int32) if level else None
-        report = np.zeros(8, dtype=np.int32)
         ox, oy, oz = (float(x) for x in origin)
         self._chk(self._L.pgx_mesh_decimate(
-            self._h, _ptr(X) if n else None, _ptr(N) if n else None, _ptr(col) if n else None, _ptr(inf) if n else None,
-            _ptr(T) if t else None, n, t, float(cell), ox, oy, oz, int(lmin), int(lmax), int(flat_q), nv, nt, _ptr(oxyz), _ptr(onrm),
-            _ptr(orgb), _ptr(oinf), _ptr(otri), _ptr(vm), _ptr(lv), _ptr(report)))
-        kv, kt = min(int(report[5]), nv), min(int(report[6]), nt)
-        return dict(xyz=oxyz[:kv], normal=onrm[:kv], rgba8=orgb[:kv], info=oinf[:kv], tri=otri[:kt],
-                    vertex_map=None if vm is None else vm[:n], level=None if lv is None else lv[:n], report=report)
+            self._h, *(_ptr(a) if len(a) else None for a in arrays), n, t, float(cell), ox, oy, oz, int(lmin), int(lmax), int(flat_q),
+            nv, nt, *(_ptr(o) for o in out[:5]), _ptr(vm), _ptr(lv), _ptr(out[5])))
+        return _mesh_result(out, nv, nt, vertex_map=None if vm is None else vm[:n], level=None if lv is None else lv[:n])
 
     # -- multi-GPU: the context's own RCCL communicator (pgx_comm_*) ------------------------------
     def comm_init(self, rank, world, unique_id):

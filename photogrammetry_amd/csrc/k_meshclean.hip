@@ -27,6 +27,7 @@
 //   k_mcl_finish   one thread per kept vertex: the sum of m over its row, the normal, the position
 // DESIGN.md section 30.
 #include "pgx_stage_args.h"
+#include "pgx_meshlist.h"   // what every stage does to a mesh list: shared with k_meshdecimate.hip
 
 namespace {
 
@@ -45,21 +46,15 @@ __device__ __forceinline__ uint32_t mcl_prio(int x) { return (uint32_t)x * 26544
 
 __global__ __launch_bounds__(MCL_NT) void k_mcl_init(MeshCleanArgs a)
 {
-    const int nv = a.counts ? pgx_clamp_count(a.counts[5], a.max_vertices) : a.max_vertices;
-    const int nt = a.counts ? pgx_clamp_count(a.counts[6], a.max_tris) : a.max_tris;
+    int nv, nt;
+    mesh_counts(a.counts, a.max_vertices, a.max_tris, nv, nt);
     if (blockIdx.x == 0 && threadIdx.x < 8) a.meta[threadIdx.x] = threadIdx.x == MC_NV ? nv : (threadIdx.x == MC_NT ? nt : 0);
     const double o[3] = {a.ox, a.oy, a.oz};
     for (int v = blockIdx.x * MCL_NT + (int)threadIdx.x; v < nv; v += (int)gridDim.x * MCL_NT) {
-        bool ok = true;
         long long q[3];
+        const bool ok = mesh_fix_q(a.xyz, (size_t)v, o, a.cell, q);
 #pragma unroll
-        for (int k = 0; k < 3; k++) {
-            const double X = a.xyz[3 * (size_t)v + k], t = (X - o[k]) / a.cell;
-            ok = ok && isfinite(X) && t >= -1048576.0 && t < 1048576.0;
-            q[k] = ok ? (long long)floor(t * 65536.0 + 0.5) : 0;
-        }
-#pragma unroll
-        for (int k = 0; k < 3; k++) a.qa[3 * (size_t)v + k] = q[k];
+        for (int k = 0; k < 3; k++) a.qa[3 * (size_t)v + k] = ok ? q[k] : 0;
         a.vvalid[v] = ok ? 1 : 0;
         a.parent[v] = v;
         a.rep[v] = MCL_NOREP;
@@ -178,7 +173,7 @@ __global__ __launch_bounds__(MCL_NT) void k_mcl_bsum(MeshCleanArgs a)
         // the rows of a block: at most 3 * 2^28 in all, below 2^32; summed as two halves that cannot carry into each other
         const int rl = block_sum_i(rows & 0xFFFF, s_sum), rh = block_sum_i(rows >> 16, s_sum);
         if (threadIdx.x == 0) {
-            a.bsum[b] = (unsigned long long)(unsigned)sv | (unsigned long long)(unsigned)st << 32;
+            a.bsum[b] = mesh_pack_kept(sv, st);
             a.rsum[b] = (unsigned long long)(unsigned)rl + ((unsigned long long)(unsigned)rh << 16);
             if (sc) atomicAdd(&a.meta[MC_COMPS], sc);
             if (sk) atomicAdd(&a.meta[MC_KEPT], sk);
@@ -193,7 +188,7 @@ __global__ __launch_bounds__(MCL_NT) void k_mcl_scan(MeshCleanArgs a)
     const unsigned long long carry = block_scan_array<unsigned long long, MCL_NT>(a.bsum, a.boff, nbn, s_lds);
     block_scan_array<unsigned long long, MCL_NT>(a.rsum, a.rbase, nbn, s_lds);
     if (threadIdx.x == 0) {
-        const int vo = (int)(carry & 0xFFFFFFFFull), to = (int)(carry >> 32);
+        const int vo = mesh_kept_vertices(carry), to = mesh_kept_tris(carry);
         a.meta[MC_VOUT] = vo;
         a.meta[MC_TOUT] = to;
         if (vo > a.max_out_vertices || to > a.max_out_tris) atomicOr(a.status, (int)PGX_ST_MCL_CAP);
@@ -211,17 +206,16 @@ __global__ __launch_bounds__(MCL_NT) void k_mcl_rank(MeshCleanArgs a)
         int vk, tk, rows, r;
         mcl_item(a, i, nv, nt, big, vk, tk, rows, r);
         unsigned long long tot;
-        const unsigned long long at =
-            a.boff[b] + block_excl_scan<unsigned long long, MCL_NT>((unsigned long long)(unsigned)vk | (unsigned long long)(unsigned)tk << 32, s_lds, tot);
+        const unsigned long long at = a.boff[b] + block_excl_scan<unsigned long long, MCL_NT>(mesh_pack_kept(vk, tk), s_lds, tot);
         const unsigned long long rat = a.rbase[b] + block_excl_scan<unsigned long long, MCL_NT>((unsigned long long)(unsigned)rows, s_lds, tot);
         if (i < nv) {
-            const int nw = vk ? (int)(at & 0xFFFFFFFFull) : (r >= 0 ? -2 : -1);
+            const int nw = vk ? mesh_kept_vertices(at) : (r >= 0 ? -2 : -1);
             a.vnew[i] = nw;
             a.roff[i] = (int)rat;
             if (a.vertex_map) a.vertex_map[i] = nw;
             if (a.comp) a.comp[i] = r >= 0 ? a.rep[r] : -1;
         }
-        if (i < nt) a.tnew[i] = tk ? (int)(at >> 32) : -1;
+        if (i < nt) a.tnew[i] = tk ? mesh_kept_tris(at) : -1;
     }
 }
 
@@ -291,9 +285,8 @@ __device__ __forceinline__ void mcl_row_normals(const MeshCleanArgs &a, const in
     for (int j = j0; j < d; j += step) {
         const unsigned long long m = a.tnrm[row[j]];
         if (m == MCL_NONRM) continue;
-        s[0] += (unsigned long long)(long long)(short)(m & 0xFFFF);
-        s[1] += (unsigned long long)(long long)(short)((m >> 16) & 0xFFFF);
-        s[2] += (unsigned long long)(long long)(short)((m >> 32) & 0xFFFF);
+#pragma unroll
+        for (int c = 0; c < 3; c++) s[c] += (unsigned long long)(long long)mesh_unpack_m(m, c);
     }
 }
 
@@ -355,21 +348,8 @@ __global__ __launch_bounds__(MCL_NT) void k_mcl_tnormal(MeshCleanArgs a, const l
         if (a.tnew[k] < 0) continue;
         const long long *qa = q + 3 * (size_t)a.tri[3 * (size_t)k], *qb = q + 3 * (size_t)a.tri[3 * (size_t)k + 1],
                         *qc = q + 3 * (size_t)a.tri[3 * (size_t)k + 2];
-        double e1[3], e2[3];
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            e1[c] = (double)(long long)((unsigned long long)qb[c] - (unsigned long long)qa[c]);
-            e2[c] = (double)(long long)((unsigned long long)qc[c] - (unsigned long long)qa[c]);
-        }
-        const double n0 = e1[1] * e2[2] - e1[2] * e2[1], n1 = e1[2] * e2[0] - e1[0] * e2[2], n2 = e1[0] * e2[1] - e1[1] * e2[0];
-        const double L = sqrt((n0 * n0 + n1 * n1) + n2 * n2);
-        unsigned long long w = MCL_NONRM;
-        if (L != 0.0 && isfinite(L)) {
-            const int m0 = (int)floor((n0 / L) * 32767.0 + 0.5), m1 = (int)floor((n1 / L) * 32767.0 + 0.5),
-                      m2 = (int)floor((n2 / L) * 32767.0 + 0.5);
-            w = (unsigned long long)(m0 & 0xFFFF) | (unsigned long long)(m1 & 0xFFFF) << 16 | (unsigned long long)(m2 & 0xFFFF) << 32;
-        }
-        a.tnrm[k] = w;
+        int m[3];
+        a.tnrm[k] = mesh_tri_m(qa, qb, qc, 32767.0, m) ? mesh_pack_m(m) : MCL_NONRM;   // rule 4
     }
 }
 
@@ -383,14 +363,9 @@ __global__ __launch_bounds__(MCL_NT) void k_mcl_finish(MeshCleanArgs a, const lo
         unsigned long long s[3];
         mcl_row_sums<true>(a, nullptr, out ? a.roff[v] : 0, out ? a.deg[v] : 0, s);
         if (!out) continue;
-        const double x0 = (double)(long long)s[0], x1 = (double)(long long)s[1], x2 = (double)(long long)s[2],
-                     L = sqrt((x0 * x0 + x1 * x1) + x2 * x2);
-        const bool hn = L != 0.0;
-        a.out_normal[3 * (size_t)w] = hn ? (float)(x0 / L) : 0.0f;
-        a.out_normal[3 * (size_t)w + 1] = hn ? (float)(x1 / L) : 0.0f;
-        a.out_normal[3 * (size_t)w + 2] = hn ? (float)(x2 / L) : 0.0f;
+        mesh_unit_normal(a.out_normal, w, s[0], s[1], s[2]);
 #pragma unroll
-        for (int c = 0; c < 3; c++) a.out_xyz[3 * (size_t)w + c] = o[c] + ((double)q[3 * (size_t)v + c] / 65536.0) * a.cell;
+        for (int c = 0; c < 3; c++) a.out_xyz[3 * (size_t)w + c] = mesh_q_to_world(o[c], q[3 * (size_t)v + c], a.cell);
     }
 }
 

@@ -26,6 +26,7 @@
 // Every probe loop is bounded by one round of its table.  DESIGN.md section 31.
 #include "pgx_stage_args.h"
 #include "pgx_cloudkey.h"
+#include "pgx_meshlist.h"   // what every stage does to a mesh list: shared with k_meshclean.hip
 
 namespace {
 
@@ -116,8 +117,8 @@ __host__ __device__ inline int mdc_lg(int n)
 __global__ __launch_bounds__(MDC_NT) void k_mdc_plan(MeshDecimateArgs a)
 {
     if (threadIdx.x >= 16) return;
-    const int nv = a.counts ? pgx_clamp_count(a.counts[5], a.max_vertices) : a.max_vertices;
-    const int nt = a.counts ? pgx_clamp_count(a.counts[6], a.max_tris) : a.max_tris;
+    int nv, nt;
+    mesh_counts(a.counts, a.max_vertices, a.max_tris, nv, nt);
     const int k = threadIdx.x;
     a.meta[k] = k == MD_NV ? nv : (k == MD_NT ? nt : (k == MD_LGV ? mdc_lg(nv) : (k == MD_LGT ? mdc_lg(nt) : 0)));
 }
@@ -129,17 +130,11 @@ __global__ __launch_bounds__(MDC_NT) void k_mdc_init(MeshDecimateArgs a)
                  at = (size_t)blockIdx.x * MDC_NT + threadIdx.x;
     const double o[3] = {a.ox, a.oy, a.oz};
     for (size_t v = at; v < (size_t)nv; v += stride) {
-        bool ok = true;
         long long q[3];
+        const bool ok = mesh_fix_q(a.xyz, v, o, a.cell, q);
 #pragma unroll
-        for (int k = 0; k < 3; k++) {
-            const double X = a.xyz[3 * v + k], t = (X - o[k]) / a.cell;
-            ok = ok && isfinite(X) && t >= -1048576.0 && t < 1048576.0;
-            q[k] = (long long)floor(t * 65536.0 + 0.5);
-            q[k] = q[k] > MDC_Q_MAX ? MDC_Q_MAX : q[k];   // t just below 2^20 rounds to 2^36, one past the last cell: rule 1 here clamps it
-        }
-#pragma unroll
-        for (int k = 0; k < 3; k++) a.q[3 * v + k] = ok ? q[k] : 0;
+        for (int k = 0; k < 3; k++)   // t just below 2^20 rounds to 2^36, one past the last cell: rule 1 here clamps it
+            a.q[3 * v + k] = ok ? (q[k] > MDC_Q_MAX ? MDC_Q_MAX : q[k]) : 0;
         a.member[v] = ok ? 0 : 2;   // 2: not valid; k_mdc_tris sets 1
         a.lev[v] = (unsigned char)a.lmin;
         a.vslot[v] = -1;
@@ -153,30 +148,6 @@ __global__ __launch_bounds__(MDC_NT) void k_mdc_init(MeshDecimateArgs a)
         for (int k = 0; k < 3; k++) a.cs[3 * i + k] = 0;
     }
     for (size_t i = at; i < TT; i += stride) a.towner[i] = -1;
-}
-
-// m of a triangle as k_mcl_tnormal packs it: 16 bits a component
-__device__ __forceinline__ unsigned long long mdc_pack(int m0, int m1, int m2)
-{
-    return (unsigned long long)(m0 & 0xFFFF) | (unsigned long long)(m1 & 0xFFFF) << 16 | (unsigned long long)(m2 & 0xFFFF) << 32;
-}
-__device__ __forceinline__ int mdc_unpack(unsigned long long w, int k) { return (int)(short)((w >> (16 * k)) & 0xFFFF); }
-
-// floor((n_a / L) * scale + 0.5) of the normal of the triangle (qa, qb, qc), zeros when L is 0 or not finite (rule 2; rule 7)
-__device__ __forceinline__ void mdc_tri_m(const long long *qa, const long long *qb, const long long *qc, double scale, int (&m)[3])
-{
-    double e1[3], e2[3];
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-        e1[c] = (double)(long long)((unsigned long long)qb[c] - (unsigned long long)qa[c]);
-        e2[c] = (double)(long long)((unsigned long long)qc[c] - (unsigned long long)qa[c]);
-    }
-    const double n0 = e1[1] * e2[2] - e1[2] * e2[1], n1 = e1[2] * e2[0] - e1[0] * e2[2], n2 = e1[0] * e2[1] - e1[1] * e2[0];
-    const double L = sqrt((n0 * n0 + n1 * n1) + n2 * n2);
-    const bool ok = L != 0.0 && isfinite(L);
-    m[0] = ok ? (int)floor((n0 / L) * scale + 0.5) : 0;
-    m[1] = ok ? (int)floor((n1 / L) * scale + 0.5) : 0;
-    m[2] = ok ? (int)floor((n2 / L) * scale + 0.5) : 0;
 }
 
 // the LDS table into the level table: one claim and four adds per distinct block
@@ -245,8 +216,8 @@ __global__ __launch_bounds__(MDC_NT) void k_mdc_tris(MeshDecimateArgs a)
             a.trot[3 * (size_t)k] = used ? 0 : -1;   // k_mdc_map reads the used test here
             if (used) {
                 const long long *q0 = a.q + 3 * (size_t)i0, *q1 = a.q + 3 * (size_t)i1, *q2 = a.q + 3 * (size_t)i2;
-                mdc_tri_m(q0, q1, q2, 1024.0, m);
-                a.tm[k] = mdc_pack(m[0], m[1], m[2]);
+                mesh_tri_m(q0, q1, q2, 1024.0, m);   // rule 2
+                a.tm[k] = mesh_pack_m(m);
                 a.member[i0] = 1; a.member[i1] = 1; a.member[i2] = 1;   // the same byte from every writer
                 mine++;
                 if (levels) {   // the distinct blocks of the three corners, each with its number of corners
@@ -488,7 +459,7 @@ __global__ __launch_bounds__(MDC_NT) void k_mdc_bsum(MeshDecimateArgs a)
         int vk, tk, e;
         mdc_item(a, b * MDC_NT + (int)threadIdx.x, nv, nt, vk, tk, e);
         const int sv = block_sum_i(vk, s_sum), st = block_sum_i(tk, s_sum);
-        if (threadIdx.x == 0) a.bsum[b] = (unsigned long long)(unsigned)sv | (unsigned long long)(unsigned)st << 32;
+        if (threadIdx.x == 0) a.bsum[b] = mesh_pack_kept(sv, st);
     }
 }
 
@@ -498,7 +469,7 @@ __global__ __launch_bounds__(MDC_NT) void k_mdc_scan(MeshDecimateArgs a)
     const int nv = a.meta[MD_NV], nt = a.meta[MD_NT], n = nv > nt ? nv : nt, nbn = (n + MDC_NT - 1) / MDC_NT;
     const unsigned long long carry = block_scan_array<unsigned long long, MDC_NT>(a.bsum, a.boff, nbn, s_lds);
     if (threadIdx.x == 0) {
-        const int vo = (int)(carry & 0xFFFFFFFFull), to = (int)(carry >> 32);
+        const int vo = mesh_kept_vertices(carry), to = mesh_kept_tris(carry);
         a.meta[MD_VOUT] = vo;
         a.meta[MD_TOUT] = to;
         if (vo > a.max_out_vertices || to > a.max_out_tris) atomicOr((unsigned *)a.status, PGX_ST_MDC_CAP);
@@ -516,10 +487,9 @@ __global__ __launch_bounds__(MDC_NT) void k_mdc_rank(MeshDecimateArgs a)
         int vk, tk, e;
         mdc_item(a, i, nv, nt, vk, tk, e);
         unsigned long long tot;
-        const unsigned long long at =
-            a.boff[b] + block_excl_scan<unsigned long long, MDC_NT>((unsigned long long)(unsigned)vk | (unsigned long long)(unsigned)tk << 32, s_lds, tot);
-        if (vk) a.cnew[e] = (int)(at & 0xFFFFFFFFull);
-        if (i < nt) a.tnew[i] = tk ? (int)(at >> 32) : -1;
+        const unsigned long long at = a.boff[b] + block_excl_scan<unsigned long long, MDC_NT>(mesh_pack_kept(vk, tk), s_lds, tot);
+        if (vk) a.cnew[e] = mesh_kept_vertices(at);
+        if (i < nt) a.tnew[i] = tk ? mesh_kept_tris(at) : -1;
     }
 }
 
@@ -542,7 +512,7 @@ __global__ __launch_bounds__(MDC_NT) void k_mdc_emit(MeshDecimateArgs a)
                     const long long q = a.q[3 * (size_t)i + k], org = q - (q & ((1ll << (16 + L)) - 1));   // B << (16 + L)
                     const long long Q = org + (2ll * (long long)a.cs[3 * (size_t)e + k] + cn) / n2;
                     a.cs[3 * (size_t)e + k] = (unsigned long long)Q;
-                    if (out) a.out_xyz[3 * (size_t)w + k] = o[k] + ((double)Q / 65536.0) * a.cell;
+                    if (out) a.out_xyz[3 * (size_t)w + k] = mesh_q_to_world(o[k], Q, a.cell);
                 }
                 uint32_t c = 0;
 #pragma unroll
@@ -574,9 +544,9 @@ __global__ __launch_bounds__(MDC_NT) void k_mdc_tnormal(MeshDecimateArgs a)
         if (k >= nt || a.tnew[k] < 0) continue;
         const int c0 = a.trot[3 * (size_t)k], c1 = a.trot[3 * (size_t)k + 1], c2 = a.trot[3 * (size_t)k + 2];
         int m[3];
-        mdc_tri_m((const long long *)a.cs + 3 * (size_t)c0, (const long long *)a.cs + 3 * (size_t)c1, (const long long *)a.cs + 3 * (size_t)c2, 32767.0, m);
+        mesh_tri_m((const long long *)a.cs + 3 * (size_t)c0, (const long long *)a.cs + 3 * (size_t)c1, (const long long *)a.cs + 3 * (size_t)c2, 32767.0, m);   // rule 7
         const unsigned long long w = a.tm[k];
-        const long long dot = ((long long)m[0] * mdc_unpack(w, 0) + (long long)m[1] * mdc_unpack(w, 1)) + (long long)m[2] * mdc_unpack(w, 2);
+        const long long dot = ((long long)m[0] * mesh_unpack_m(w, 0) + (long long)m[1] * mesh_unpack_m(w, 1)) + (long long)m[2] * mesh_unpack_m(w, 2);
         flipped += dot < 0 ? 1 : 0;
 #pragma unroll
         for (int j = 0; j < 3; j++) {
@@ -599,12 +569,7 @@ __global__ __launch_bounds__(MDC_NT) void k_mdc_finish(MeshDecimateArgs a)
         if (e < 0 || a.cname[e] != i || !a.cused[e]) continue;
         const int w = a.cnew[e];
         if (w < 0 || w >= a.max_out_vertices) continue;
-        const double x0 = (double)(long long)a.csc[4 * (size_t)e], x1 = (double)(long long)a.csc[4 * (size_t)e + 1],
-                     x2 = (double)(long long)a.csc[4 * (size_t)e + 2], L = sqrt((x0 * x0 + x1 * x1) + x2 * x2);
-        const bool hn = L != 0.0;
-        a.out_normal[3 * (size_t)w] = hn ? (float)(x0 / L) : 0.0f;
-        a.out_normal[3 * (size_t)w + 1] = hn ? (float)(x1 / L) : 0.0f;
-        a.out_normal[3 * (size_t)w + 2] = hn ? (float)(x2 / L) : 0.0f;
+        mesh_unit_normal(a.out_normal, w, a.csc[4 * (size_t)e], a.csc[4 * (size_t)e + 1], a.csc[4 * (size_t)e + 2]);
     }
 }
 

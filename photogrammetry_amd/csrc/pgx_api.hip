@@ -917,6 +917,14 @@ int fetch_rows(pgx_ctx *c, const HostImage &out, std::initializer_list<FetchRows
     return PGX_OK;
 }
 
+// ... of a mesh list (mesh_out) into the caller's arrays: report[5] vertices and report[6] triangles, at most the capacities
+int fetch_mesh(pgx_ctx *c, const HostImage &out, const MeshOut &o, const MeshRows &host, const int32_t *report, int max_vertices, int max_tris)
+{
+    const size_t nv = (size_t)(report[5] < max_vertices ? report[5] : max_vertices), nt = (size_t)(report[6] < max_tris ? report[6] : max_tris);
+    const int rf = fetch_rows(c, out, {{o.xyz, host.xyz, 24}, {o.normal, host.normal, 12}, {o.rgba8, host.rgba8, 4}, {o.info, host.info, 16}}, nv);
+    return rf != PGX_OK ? rf : fetch_rows(c, out, {{o.tri, host.tri, 12}}, nt);
+}
+
 } // namespace
 
 int pgx_match(pgx_ctx *c, const uint32_t *desc1, int n1, const uint32_t *desc2, int n2, int words, pgx_pair *out)
@@ -2544,8 +2552,8 @@ int pgx_mesh(pgx_ctx *c, const double *xyz, const int32_t *src, int n_in, const 
               i_a = in.add(agree, (size_t)R * npix, 4, 0, agree != nullptr),
               i_c = in.add(rgba8, (size_t)n_frames * npix, 4, 0, rgba8 != nullptr);
     // the report first: its download tells how many vertices and triangles there are to fetch
-    const int o_r = out.add(report, 8, 4, 64), o_x = out.add(nullptr, 0, 24, nv + 1), o_n = out.add(nullptr, 0, 12, nv + 1),
-              o_c = out.add(nullptr, 0, 4, nv + 1), o_i = out.add(nullptr, 0, 16, nv + 1), o_t = out.add(nullptr, 0, 12, nt + 1);
+    const int o_r = out.add(report, 8, 4, 64);
+    const MeshOut o = mesh_out(out, nv, nt);
     if ((rs = stage_images(c, in, out)) != PGX_OK) return rs;
     MeshArgs a{};
     a.xyz = in.dev<double>(i_x); a.src = in.dev<int32_t>(i_s); a.count = nullptr; a.max_in = n_in;
@@ -2554,17 +2562,49 @@ int pgx_mesh(pgx_ctx *c, const double *xyz, const int32_t *src, int n_in, const 
     a.rgba8 = in.dev<uint32_t>(i_c); a.F = rgba8 ? n_frames : 0; a.frame_ids = nullptr;
     a.cell = cell; a.ox = ox; a.oy = oy; a.oz = oz; a.band = band; a.trunc_cells = trunc_cells; a.min_weight = min_weight;
     a.max_voxels = max_voxels; a.max_vertices = max_vertices; a.max_tris = max_tris;
-    a.out_xyz = out.dev<double>(o_x); a.out_normal = out.dev<float>(o_n); a.out_rgba8 = out.dev<uint32_t>(o_c);
-    a.out_info = out.dev<int32_t>(o_i); a.out_tri = out.dev<int32_t>(o_t); a.report = out.dev<int32_t>(o_r);
+    const MeshRows r = mesh_dev(out, o);
+    a.out_xyz = r.xyz; a.out_normal = r.normal; a.out_rgba8 = r.rgba8; a.out_info = r.info; a.out_tri = r.tri; a.report = out.dev<int32_t>(o_r);
     if ((rs = run_mesh(c, a)) != PGX_OK) return rs;
     rs = download_images(c, out);   // the report; waits for the stream
     if (rs != PGX_OK && rs != PGX_E_CAPACITY) return rs;   // the report was not downloaded: nothing tells how many rows there are
-    const size_t mv = (size_t)(report[5] < max_vertices ? report[5] : max_vertices), mt = (size_t)(report[6] < max_tris ? report[6] : max_tris);
-    if (const int rf = fetch_rows(c, out, {{o_x, out_xyz, 24}, {o_n, out_normal, 12}, {o_c, out_rgba8, 4}, {o_i, out_info, 16}}, mv); rf != PGX_OK)
-        return rf;
-    if (const int rf = fetch_rows(c, out, {{o_t, out_tri, 12}}, mt); rf != PGX_OK) return rf;
-    return rs;
+    const int rf = fetch_mesh(c, out, o, {out_xyz, out_normal, out_rgba8, out_info, out_tri}, report, max_vertices, max_tris);
+    return rf != PGX_OK ? rf : rs;
 }
+
+// ---- what the stages that take a mesh list and write one share (the clean stage, the decimation) ------------------------------
+
+namespace {
+// the refusals of both stages, device and host form
+int mesh_list_args(pgx_ctx *c, int max_vertices, int max_tris, double cell, double ox, double oy, double oz, int max_out_vertices,
+                   int max_out_tris)
+{
+    for (const int cap : {max_vertices, max_tris, max_out_vertices, max_out_tris})
+        if (cap < 0 || cap > (1 << 28))
+            return fail(c, PGX_E_BADARG, "max_vertices, max_tris, max_out_vertices and max_out_tris must be in [0, 2^28]");
+    if (!std::isfinite(cell) || !(cell > 0.0)) return fail(c, PGX_E_BADARG, "cell must be finite and > 0");
+    if (!std::isfinite(ox) || !std::isfinite(oy) || !std::isfinite(oz)) return fail(c, PGX_E_BADARG, "the origin must be finite");
+    return PGX_OK;
+}
+
+// a device form's lists, read from the filled arguments: aux is the stage's own per-vertex output (comp, level)
+extern "C++" template <class A> int mesh_list_no_alias(pgx_ctx *c, const A &a, const int32_t *aux)
+{
+    const size_t nv = a.max_vertices, nt = a.max_tris, mv = a.max_out_vertices, mt = a.max_out_tris;
+    const Span in[] = {{a.xyz, nv * 24}, {a.normal, nv * 12}, {a.rgba8, nv * 4}, {a.info, nv * 16}, {a.tri, nt * 12}, {a.counts, 32}},
+               out[] = {{a.out_xyz, mv * 24}, {a.out_normal, mv * 12}, {a.out_rgba8, mv * 4}, {a.out_info, mv * 16},
+                        {a.out_tri, mt * 12}, {a.vertex_map, nv * 4}, {aux, nv * 4}, {a.report, 32}};
+    return no_alias(c, in, std::size(in), out, std::size(out));
+}
+
+// the pointers that MeshCleanArgs and MeshDecimateArgs name alike; the scalars are assigned by name where the form stands
+extern "C++" template <class A>
+void mesh_list_fill(A &a, const MeshList &i, const int32_t *counts, const MeshRows &o, int32_t *vertex_map, int32_t *report)
+{
+    a.xyz = i.xyz; a.normal = i.normal; a.rgba8 = i.rgba8; a.info = i.info; a.tri = i.tri; a.counts = counts;
+    a.out_xyz = o.xyz; a.out_normal = o.normal; a.out_rgba8 = o.rgba8; a.out_info = o.info; a.out_tri = o.tri;
+    a.vertex_map = vertex_map; a.report = report;
+}
+} // namespace
 
 // ---- the mesh cleaned: small components dropped, smoothed, normals again ----------------------------------------------------
 
@@ -2573,25 +2613,13 @@ namespace {
 int mesh_clean_args(pgx_ctx *c, int max_vertices, int max_tris, double cell, double ox, double oy, double oz, int min_tris, int min_frac_pm,
                     int iters, double lambda, double mu, int max_out_vertices, int max_out_tris)
 {
-    for (const int cap : {max_vertices, max_tris, max_out_vertices, max_out_tris})
-        if (cap < 0 || cap > (1 << 28))
-            return fail(c, PGX_E_BADARG, "max_vertices, max_tris, max_out_vertices and max_out_tris must be in [0, 2^28]");
-    if (!std::isfinite(cell) || !(cell > 0.0)) return fail(c, PGX_E_BADARG, "cell must be finite and > 0");
-    if (!std::isfinite(ox) || !std::isfinite(oy) || !std::isfinite(oz)) return fail(c, PGX_E_BADARG, "the origin must be finite");
+    if (const int rc = mesh_list_args(c, max_vertices, max_tris, cell, ox, oy, oz, max_out_vertices, max_out_tris); rc != PGX_OK) return rc;
     if (min_tris < 1) return fail(c, PGX_E_BADARG, "min_tris must be >= 1");
     if (min_frac_pm < 0 || min_frac_pm > 1000) return fail(c, PGX_E_BADARG, "min_frac_pm = %d, must be in [0, 1000]", min_frac_pm);
     if (iters < 0 || iters > 64) return fail(c, PGX_E_BADARG, "iters = %d, must be in [0, 64]", iters);
     if (!std::isfinite(lambda) || !(lambda > 0.0) || lambda > 1.0) return fail(c, PGX_E_BADARG, "lambda must be in (0, 1]");
     if (!std::isfinite(mu) || mu < -1.5 || mu > 0.0) return fail(c, PGX_E_BADARG, "mu must be in [-1.5, 0]");
     return PGX_OK;
-}
-
-void mesh_clean_fill(MeshCleanArgs &a, int max_vertices, int max_tris, double cell, double ox, double oy, double oz, int min_tris,
-                     int min_frac_pm, int iters, double lambda, double mu, int max_out_vertices, int max_out_tris)
-{
-    a.max_vertices = max_vertices; a.max_tris = max_tris; a.cell = cell; a.ox = ox; a.oy = oy; a.oz = oz; a.lambda = lambda; a.mu = mu;
-    a.min_tris = min_tris; a.min_frac_pm = min_frac_pm; a.iters = iters; a.max_out_vertices = max_out_vertices;
-    a.max_out_tris = max_out_tris;
 }
 } // namespace
 
@@ -2608,17 +2636,13 @@ int pgx_mesh_clean_dev(pgx_ctx *c, const double *d_xyz, const float *d_normal, c
     const int rc = mesh_clean_args(c, max_vertices, max_tris, cell, ox, oy, oz, min_tris, min_frac_pm, iters, lambda, mu, max_out_vertices,
                                    max_out_tris);
     if (rc != PGX_OK) return rc;
-    const size_t nv = max_vertices, nt = max_tris, mv = max_out_vertices, mt = max_out_tris;
-    const Span in[] = {{d_xyz, nv * 24}, {d_normal, nv * 12}, {d_rgba8, nv * 4}, {d_info, nv * 16},
-                       {d_tri, nt * 12}, {d_counts, 32}},
-               out[] = {{d_out_xyz, mv * 24}, {d_out_normal, mv * 12}, {d_out_rgba8, mv * 4}, {d_out_info, mv * 16},
-                        {d_out_tri, mt * 12}, {d_vertex_map, nv * 4}, {d_comp, nv * 4}, {d_report, 32}};
-    if (const int ra = no_alias(c, in, std::size(in), out, std::size(out)); ra != PGX_OK) return ra;
     MeshCleanArgs a{};
-    a.xyz = d_xyz; a.normal = d_normal; a.rgba8 = d_rgba8; a.info = d_info; a.tri = d_tri; a.counts = d_counts;
-    mesh_clean_fill(a, max_vertices, max_tris, cell, ox, oy, oz, min_tris, min_frac_pm, iters, lambda, mu, max_out_vertices, max_out_tris);
-    a.out_xyz = d_out_xyz; a.out_normal = d_out_normal; a.out_rgba8 = d_out_rgba8; a.out_info = d_out_info; a.out_tri = d_out_tri;
-    a.vertex_map = d_vertex_map; a.comp = d_comp; a.report = d_report;
+    mesh_list_fill(a, {d_xyz, d_normal, d_rgba8, d_info, d_tri}, d_counts, {d_out_xyz, d_out_normal, d_out_rgba8, d_out_info, d_out_tri}, d_vertex_map,
+                   d_report);
+    a.max_vertices = max_vertices; a.max_tris = max_tris; a.cell = cell; a.ox = ox; a.oy = oy; a.oz = oz;
+    a.max_out_vertices = max_out_vertices; a.max_out_tris = max_out_tris;
+    a.min_tris = min_tris; a.min_frac_pm = min_frac_pm; a.iters = iters; a.lambda = lambda; a.mu = mu; a.comp = d_comp;
+    if (const int ra = mesh_list_no_alias(c, a, a.comp); ra != PGX_OK) return ra;
     return run_mesh_clean(c, a);
 }
 
@@ -2634,31 +2658,24 @@ int pgx_mesh_clean(pgx_ctx *c, const double *xyz, const float *normal, const uin
     int rs = mesh_clean_args(c, n_vertices, n_tris, cell, ox, oy, oz, min_tris, min_frac_pm, iters, lambda, mu, max_out_vertices,
                              max_out_tris);
     if (rs != PGX_OK) return rs;
-    const size_t nv = n_vertices, nt = n_tris, mv = max_out_vertices, mt = max_out_tris;
+    const size_t nv = n_vertices;
     HostImage in, out;
-    const int i_x = in.add(xyz, nv, 24, 1), i_n = in.add(normal, nv, 12, 1), i_c = in.add(rgba8, nv, 4, 1), i_i = in.add(info, nv, 16, 1),
-              i_t = in.add(tri, nt, 12, 1);
+    const MeshIn i = mesh_in(in, xyz, normal, rgba8, info, tri, nv, n_tris);
     // the report first: its download tells how many vertices and triangles there are to fetch
     const int o_r = out.add(report, 8, 4, 64), o_vm = out.add(vertex_map, nv, 4, 1, vertex_map != nullptr),
-              o_cp = out.add(comp, nv, 4, 1, comp != nullptr), o_x = out.add(nullptr, 0, 24, mv + 1), o_n = out.add(nullptr, 0, 12, mv + 1),
-              o_c = out.add(nullptr, 0, 4, mv + 1), o_i = out.add(nullptr, 0, 16, mv + 1), o_t = out.add(nullptr, 0, 12, mt + 1);
+              o_cp = out.add(comp, nv, 4, 1, comp != nullptr);
+    const MeshOut o = mesh_out(out, max_out_vertices, max_out_tris);
     if ((rs = stage_images(c, in, out)) != PGX_OK) return rs;
     MeshCleanArgs a{};
-    a.xyz = in.dev<double>(i_x); a.normal = in.dev<float>(i_n); a.rgba8 = in.dev<uint32_t>(i_c); a.info = in.dev<int32_t>(i_i);
-    a.tri = in.dev<int32_t>(i_t); a.counts = nullptr;
-    mesh_clean_fill(a, n_vertices, n_tris, cell, ox, oy, oz, min_tris, min_frac_pm, iters, lambda, mu, max_out_vertices, max_out_tris);
-    a.out_xyz = out.dev<double>(o_x); a.out_normal = out.dev<float>(o_n); a.out_rgba8 = out.dev<uint32_t>(o_c);
-    a.out_info = out.dev<int32_t>(o_i); a.out_tri = out.dev<int32_t>(o_t); a.vertex_map = out.dev<int32_t>(o_vm);
-    a.comp = out.dev<int32_t>(o_cp); a.report = out.dev<int32_t>(o_r);
+    mesh_list_fill(a, mesh_dev(in, i), nullptr, mesh_dev(out, o), out.dev<int32_t>(o_vm), out.dev<int32_t>(o_r));
+    a.max_vertices = n_vertices; a.max_tris = n_tris; a.cell = cell; a.ox = ox; a.oy = oy; a.oz = oz;
+    a.max_out_vertices = max_out_vertices; a.max_out_tris = max_out_tris;
+    a.min_tris = min_tris; a.min_frac_pm = min_frac_pm; a.iters = iters; a.lambda = lambda; a.mu = mu; a.comp = out.dev<int32_t>(o_cp);
     if ((rs = run_mesh_clean(c, a)) != PGX_OK) return rs;
     rs = download_images(c, out);   // the report and the per-vertex maps; waits for the stream
     if (rs != PGX_OK && rs != PGX_E_CAPACITY) return rs;   // the report was not downloaded: nothing tells how many rows there are
-    const size_t kv = (size_t)(report[5] < max_out_vertices ? report[5] : max_out_vertices),
-                 kt = (size_t)(report[6] < max_out_tris ? report[6] : max_out_tris);
-    if (const int rf = fetch_rows(c, out, {{o_x, out_xyz, 24}, {o_n, out_normal, 12}, {o_c, out_rgba8, 4}, {o_i, out_info, 16}}, kv); rf != PGX_OK)
-        return rf;
-    if (const int rf = fetch_rows(c, out, {{o_t, out_tri, 12}}, kt); rf != PGX_OK) return rf;
-    return rs;
+    const int rf = fetch_mesh(c, out, o, {out_xyz, out_normal, out_rgba8, out_info, out_tri}, report, max_out_vertices, max_out_tris);
+    return rf != PGX_OK ? rf : rs;
 }
 
 // ---- the mesh decimated: adaptive vertex clustering over grid blocks ----------------------------------------------------------
@@ -2668,22 +2685,11 @@ namespace {
 int mesh_decimate_args(pgx_ctx *c, int max_vertices, int max_tris, double cell, double ox, double oy, double oz, int lmin, int lmax,
                        int flat_q, int max_out_vertices, int max_out_tris)
 {
-    for (const int cap : {max_vertices, max_tris, max_out_vertices, max_out_tris})
-        if (cap < 0 || cap > (1 << 28))
-            return fail(c, PGX_E_BADARG, "max_vertices, max_tris, max_out_vertices and max_out_tris must be in [0, 2^28]");
-    if (!std::isfinite(cell) || !(cell > 0.0)) return fail(c, PGX_E_BADARG, "cell must be finite and > 0");
-    if (!std::isfinite(ox) || !std::isfinite(oy) || !std::isfinite(oz)) return fail(c, PGX_E_BADARG, "the origin must be finite");
+    if (const int rc = mesh_list_args(c, max_vertices, max_tris, cell, ox, oy, oz, max_out_vertices, max_out_tris); rc != PGX_OK) return rc;
     if (lmin < 0 || lmin > 6) return fail(c, PGX_E_BADARG, "lmin = %d, must be in [0, 6]", lmin);
     if (lmax < lmin || lmax > 6) return fail(c, PGX_E_BADARG, "lmax = %d, must be in [lmin, 6]", lmax);
     if (flat_q < 0 || flat_q > 1024) return fail(c, PGX_E_BADARG, "flat_q = %d, must be in [0, 1024]", flat_q);
     return PGX_OK;
-}
-
-void mesh_decimate_fill(MeshDecimateArgs &a, int max_vertices, int max_tris, double cell, double ox, double oy, double oz, int lmin, int lmax,
-                        int flat_q, int max_out_vertices, int max_out_tris)
-{
-    a.max_vertices = max_vertices; a.max_tris = max_tris; a.cell = cell; a.ox = ox; a.oy = oy; a.oz = oz; a.lmin = lmin; a.lmax = lmax;
-    a.flat_q = flat_q; a.max_out_vertices = max_out_vertices; a.max_out_tris = max_out_tris;
 }
 } // namespace
 
@@ -2699,17 +2705,13 @@ int pgx_mesh_decimate_dev(pgx_ctx *c, const double *d_xyz, const float *d_normal
     Lock l(c);
     const int rc = mesh_decimate_args(c, max_vertices, max_tris, cell, ox, oy, oz, lmin, lmax, flat_q, max_out_vertices, max_out_tris);
     if (rc != PGX_OK) return rc;
-    const size_t nv = max_vertices, nt = max_tris, mv = max_out_vertices, mt = max_out_tris;
-    const Span in[] = {{d_xyz, nv * 24}, {d_normal, nv * 12}, {d_rgba8, nv * 4}, {d_info, nv * 16},
-                       {d_tri, nt * 12}, {d_counts, 32}},
-               out[] = {{d_out_xyz, mv * 24}, {d_out_normal, mv * 12}, {d_out_rgba8, mv * 4}, {d_out_info, mv * 16},
-                        {d_out_tri, mt * 12}, {d_vertex_map, nv * 4}, {d_level, nv * 4}, {d_report, 32}};
-    if (const int ra = no_alias(c, in, std::size(in), out, std::size(out)); ra != PGX_OK) return ra;
     MeshDecimateArgs a{};
-    a.xyz = d_xyz; a.normal = d_normal; a.rgba8 = d_rgba8; a.info = d_info; a.tri = d_tri; a.counts = d_counts;
-    mesh_decimate_fill(a, max_vertices, max_tris, cell, ox, oy, oz, lmin, lmax, flat_q, max_out_vertices, max_out_tris);
-    a.out_xyz = d_out_xyz; a.out_normal = d_out_normal; a.out_rgba8 = d_out_rgba8; a.out_info = d_out_info; a.out_tri = d_out_tri;
-    a.vertex_map = d_vertex_map; a.level = d_level; a.report = d_report;
+    mesh_list_fill(a, {d_xyz, d_normal, d_rgba8, d_info, d_tri}, d_counts, {d_out_xyz, d_out_normal, d_out_rgba8, d_out_info, d_out_tri}, d_vertex_map,
+                   d_report);
+    a.max_vertices = max_vertices; a.max_tris = max_tris; a.cell = cell; a.ox = ox; a.oy = oy; a.oz = oz;
+    a.max_out_vertices = max_out_vertices; a.max_out_tris = max_out_tris;
+    a.lmin = lmin; a.lmax = lmax; a.flat_q = flat_q; a.level = d_level;
+    if (const int ra = mesh_list_no_alias(c, a, a.level); ra != PGX_OK) return ra;
     return run_mesh_decimate(c, a);
 }
 
@@ -2724,31 +2726,24 @@ int pgx_mesh_decimate(pgx_ctx *c, const double *xyz, const float *normal, const 
     Lock l(c);
     int rs = mesh_decimate_args(c, n_vertices, n_tris, cell, ox, oy, oz, lmin, lmax, flat_q, max_out_vertices, max_out_tris);
     if (rs != PGX_OK) return rs;
-    const size_t nv = n_vertices, nt = n_tris, mv = max_out_vertices, mt = max_out_tris;
+    const size_t nv = n_vertices;
     HostImage in, out;
-    const int i_x = in.add(xyz, nv, 24, 1), i_n = in.add(normal, nv, 12, 1), i_c = in.add(rgba8, nv, 4, 1), i_i = in.add(info, nv, 16, 1),
-              i_t = in.add(tri, nt, 12, 1);
+    const MeshIn i = mesh_in(in, xyz, normal, rgba8, info, tri, nv, n_tris);
     // the report first: its download tells how many vertices and triangles there are to fetch
     const int o_r = out.add(report, 8, 4, 64), o_vm = out.add(vertex_map, nv, 4, 1, vertex_map != nullptr),
-              o_lv = out.add(level, nv, 4, 1, level != nullptr), o_x = out.add(nullptr, 0, 24, mv + 1), o_n = out.add(nullptr, 0, 12, mv + 1),
-              o_c = out.add(nullptr, 0, 4, mv + 1), o_i = out.add(nullptr, 0, 16, mv + 1), o_t = out.add(nullptr, 0, 12, mt + 1);
+              o_lv = out.add(level, nv, 4, 1, level != nullptr);
+    const MeshOut o = mesh_out(out, max_out_vertices, max_out_tris);
     if ((rs = stage_images(c, in, out)) != PGX_OK) return rs;
     MeshDecimateArgs a{};
-    a.xyz = in.dev<double>(i_x); a.normal = in.dev<float>(i_n); a.rgba8 = in.dev<uint32_t>(i_c); a.info = in.dev<int32_t>(i_i);
-    a.tri = in.dev<int32_t>(i_t); a.counts = nullptr;
-    mesh_decimate_fill(a, n_vertices, n_tris, cell, ox, oy, oz, lmin, lmax, flat_q, max_out_vertices, max_out_tris);
-    a.out_xyz = out.dev<double>(o_x); a.out_normal = out.dev<float>(o_n); a.out_rgba8 = out.dev<uint32_t>(o_c);
-    a.out_info = out.dev<int32_t>(o_i); a.out_tri = out.dev<int32_t>(o_t); a.vertex_map = out.dev<int32_t>(o_vm);
-    a.level = out.dev<int32_t>(o_lv); a.report = out.dev<int32_t>(o_r);
+    mesh_list_fill(a, mesh_dev(in, i), nullptr, mesh_dev(out, o), out.dev<int32_t>(o_vm), out.dev<int32_t>(o_r));
+    a.max_vertices = n_vertices; a.max_tris = n_tris; a.cell = cell; a.ox = ox; a.oy = oy; a.oz = oz;
+    a.max_out_vertices = max_out_vertices; a.max_out_tris = max_out_tris;
+    a.lmin = lmin; a.lmax = lmax; a.flat_q = flat_q; a.level = out.dev<int32_t>(o_lv);
     if ((rs = run_mesh_decimate(c, a)) != PGX_OK) return rs;
     rs = download_images(c, out);   // the report and the per-vertex maps; waits for the stream
     if (rs != PGX_OK && rs != PGX_E_CAPACITY) return rs;   // the report was not downloaded: nothing tells how many rows there are
-    const size_t kv = (size_t)(report[5] < max_out_vertices ? report[5] : max_out_vertices),
-                 kt = (size_t)(report[6] < max_out_tris ? report[6] : max_out_tris);
-    if (const int rf = fetch_rows(c, out, {{o_x, out_xyz, 24}, {o_n, out_normal, 12}, {o_c, out_rgba8, 4}, {o_i, out_info, 16}}, kv); rf != PGX_OK)
-        return rf;
-    if (const int rf = fetch_rows(c, out, {{o_t, out_tri, 12}}, kt); rf != PGX_OK) return rf;
-    return rs;
+    const int rf = fetch_mesh(c, out, o, {out_xyz, out_normal, out_rgba8, out_info, out_tri}, report, max_out_vertices, max_out_tris);
+    return rf != PGX_OK ? rf : rs;
 }
 
 // ---- measurement hooks ---------------------------------------------------------------------

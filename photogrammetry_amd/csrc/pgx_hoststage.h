@@ -1,8 +1,9 @@
 // pgx_hoststage.h -- buffers laid out in 256-byte-aligned sections: the workspace carver of the launchers and, on it, the
 // image that a host form uploads or downloads in (HostImage), with the section lists that the twenty host forms on it share:
 // tracks_in (triangulation, bundle adjustment, registration, track consensus), pair_in (verification, relative pose),
-// two_sets_in and knn_out (pgx_match, pgx_knn, pgx_knn_guided), batch_in (pgx_match_batch).  The other ten (pgx_vocab_train,
-// pgx_select_pairs, pgx_depth_maps, pgx_depth_fuse, pgx_dense_views, pgx_rgba8_batch, pgx_cloud_merge, pgx_mesh, pgx_mesh_clean, pgx_mesh_decimate)
+// two_sets_in and knn_out (pgx_match, pgx_knn, pgx_knn_guided), batch_in (pgx_match_batch), mesh_in (pgx_mesh_clean,
+// pgx_mesh_decimate) and mesh_out (those two and pgx_mesh).  The other seven (pgx_vocab_train, pgx_select_pairs, pgx_depth_maps,
+// pgx_depth_fuse, pgx_dense_views, pgx_rgba8_batch, pgx_cloud_merge) and what the three mesh forms have besides a mesh list
 // declare their lists where they stand in pgx_api.hip.
 // Host code without HIP: tests/hoststage_driver.cpp builds it with g++ under sanitizers, and pgx_api.hip puts the copies
 // around it (stage_images, download_images).  Internal to libpgx.so; DESIGN.md section 14g.
@@ -166,4 +167,34 @@ inline BatchIn batch_in(HostImage &in, const uint32_t *const *descs, const int32
     for (int f = 0; f < n_frames; f++)
         if (used[f]) in.put_at((size_t)f * S * D, descs[f], counts[f] * D);
     return {desc, in.add(counts, n_frames, 4), in.add(pair_list, n_pairs, 8)};   // in this order
+}
+
+// the five arrays of a mesh in pgx_mesh_dev's layout, as a stage reads them and as it writes them
+struct MeshList { const double *xyz; const float *normal; const uint32_t *rgba8; const int32_t *info, *tri; };
+struct MeshRows { double *xyz; float *normal; uint32_t *rgba8; int32_t *info, *tri; };
+
+// ... and as sections of an image; mesh_dev: where they lie on the device
+struct MeshIn { int xyz, normal, rgba8, info, tri; };
+struct MeshOut { int xyz, normal, rgba8, info, tri; };
+template <class P, class S> P mesh_dev_of(const HostImage &im, const S &s)
+{
+    return {im.dev<double>(s.xyz), im.dev<float>(s.normal), im.dev<uint32_t>(s.rgba8), im.dev<int32_t>(s.info), im.dev<int32_t>(s.tri)};
+}
+inline MeshList mesh_dev(const HostImage &in, const MeshIn &s) { return mesh_dev_of<MeshList>(in, s); }
+inline MeshRows mesh_dev(const HostImage &out, const MeshOut &s) { return mesh_dev_of<MeshRows>(out, s); }
+
+// pgx_mesh_clean, pgx_mesh_decimate: a mesh list of n vertices (xyz, normal, rgba8, info) and t triangles
+inline MeshIn mesh_in(HostImage &in, const double *xyz, const float *normal, const uint32_t *rgba8, const int32_t *info, const int32_t *tri,
+                      size_t n, size_t t)
+{
+    return {in.add(xyz, n, 24, 1), in.add(normal, n, 12, 1), in.add(rgba8, n, 4, 1), in.add(info, n, 16, 1), in.add(tri, t, 12, 1)};   // in this order
+}
+
+// ... and the mesh list that those two and pgx_mesh write, of at most mv vertices and mt triangles: carved and not downloaded.  The
+// form declares the report before it (and its per-vertex maps behind the report): the report's download tells how many rows
+// of these sections there are to fetch.
+inline MeshOut mesh_out(HostImage &out, size_t mv, size_t mt)
+{
+    return {out.add(nullptr, 0, 24, mv + 1), out.add(nullptr, 0, 12, mv + 1), out.add(nullptr, 0, 4, mv + 1), out.add(nullptr, 0, 16, mv + 1),
+            out.add(nullptr, 0, 12, mt + 1)};   // in this order
 }

@@ -1,10 +1,11 @@
 // Stand-alone driver of the host forms' staging images (photogrammetry_amd/csrc/pgx_hoststage.h) for tests/test_hoststage.py:
 // argv[1] names a host form, whose section lists are checked at every size of the test's docstring against images laid out
-// naively here.  The input lists are the header's own (tracks_in, pair_in, two_sets_in, batch_in), and so is knn_out; the
-// other output lists, F and K of pgx_relative_pose, and S and `used` of pgx_match_batch are declared or computed here word
-// for word as the form in pgx_api.hip does.  So are both lists of the nine later forms (pgx_track_consensus's inputs excepted,
-// which are tracks_in): pgx_vocab_train, pgx_select_pairs, pgx_depth_maps, pgx_depth_fuse, pgx_dense_views, pgx_rgba8_batch,
-// pgx_cloud_merge and pgx_mesh declare them inside pgx_api.hip.  For pgx_depth_fuse, pgx_cloud_merge and pgx_mesh the report
+// naively here.  The input lists are the header's own (tracks_in, pair_in, two_sets_in, batch_in, mesh_in), and so are knn_out
+// and mesh_out; the other output lists, F and K of pgx_relative_pose, and S and `used` of pgx_match_batch are declared or
+// computed here word for word as the form in pgx_api.hip does.  So are both lists of the nine later forms (pgx_track_consensus's
+// inputs and pgx_mesh's mesh_out excepted): pgx_vocab_train, pgx_select_pairs, pgx_depth_maps, pgx_depth_fuse, pgx_dense_views,
+// pgx_rgba8_batch, pgx_cloud_merge and pgx_mesh declare them inside pgx_api.hip, and so are the report and the per-vertex maps
+// of pgx_mesh_clean and pgx_mesh_decimate.  For pgx_depth_fuse, pgx_cloud_merge and the three mesh forms the report
 // must be the output image's first download, and the lists of max + 1 rows behind it none.  Host code only; the test
 // builds it with -fsanitize=address,undefined, and every buffer has its exact size, so a read or write past an end is a
 // sanitizer report.  Exit status 0 and "ok <checks>" on stdout, or 1 and the first failure on stderr.
@@ -504,13 +505,56 @@ void cloud_form(int kind)
                                           in_sec(r * (1 + S) * 4, views.bytes()), in_sec(nf * 96, P.bytes()),
                                           in_sec(r * npix * 4, agree.bytes(), has_agree), in_sec(nf * npix * 4, rgba8.bytes(), has_rgba8)});
                                 const size_t nv = cap, nt = cap_t;
-                                check_out(out, {out.add(report, 8, 4, 64), out.add(nullptr, 0, 24, nv + 1), out.add(nullptr, 0, 12, nv + 1),
-                                                out.add(nullptr, 0, 4, nv + 1), out.add(nullptr, 0, 16, nv + 1), out.add(nullptr, 0, 12, nt + 1)},
+                                const int o_r = out.add(report, 8, 4, 64);
+                                const MeshOut o = mesh_out(out, nv, nt);
+                                check_out(out, {o_r, o.xyz, o.normal, o.rgba8, o.info, o.tri},
                                           {out_sec(256, report, 32), out_sec((nv + 1) * 24, nullptr, 0), out_sec((nv + 1) * 12, nullptr, 0),
                                            out_sec((nv + 1) * 4, nullptr, 0), out_sec((nv + 1) * 16, nullptr, 0), out_sec((nt + 1) * 12, nullptr, 0)});
                             }
                             report_first(out, report, 32);
                         }
+}
+
+// kind 18: pgx_mesh_clean (vertex_map, comp out optional), 19: pgx_mesh_decimate (vertex_map, level): the same lists, mesh_in and
+// behind the report and the two per-vertex maps mesh_out
+void mesh_list_form()
+{
+    for (int n : {0, 1, 7})
+        for (int t : {0, 1, 5})
+            for (int mv : {0, 1, 9})          // max_out_vertices: none, one, more than there are vertices
+                for (int mt : {0, 1, 11})     // max_out_tris
+                    for (int optional = 0; optional < 4; optional++) {
+                        const size_t nv = n, nt = t, cv = mv, ct = mt;
+                        Src<double> xyz(nv * 3, 1);
+                        Src<float> normal(nv * 3, 2);
+                        Src<uint32_t> rgba8(nv, 3);
+                        Src<int32_t> info(nv * 4, 4), tri(nt * 3, 5);
+                        int32_t w[8];
+                        std::vector<int32_t> vm(optional & 1 ? nv : 0), aux(optional & 2 ? nv : 0);
+                        // a null map is an absent one; at n = 0 a present one is a destination that nothing goes to
+                        int32_t *const report = w, *const vertex_map = optional & 1 ? (nv ? vm.data() : w + 1) : nullptr,
+                                       *const per_vertex = optional & 2 ? (nv ? aux.data() : w + 2) : nullptr;
+                        HostImage in, out;
+                        const MeshIn i = mesh_in(in, xyz.p(), normal.p(), rgba8.p(), info.p(), tri.p(), nv, nt);
+                        check_in(in, {i.xyz, i.normal, i.rgba8, i.info, i.tri},
+                                 {in_sec(max1(nv) * 24, xyz.bytes()), in_sec(max1(nv) * 12, normal.bytes()), in_sec(max1(nv) * 4, rgba8.bytes()),
+                                  in_sec(max1(nv) * 16, info.bytes()), in_sec(max1(nt) * 12, tri.bytes())});
+                        const MeshList di = mesh_dev(in, i);
+                        CHECK(di.xyz == in.dev<double>(i.xyz) && di.normal == in.dev<float>(i.normal) && di.rgba8 == in.dev<uint32_t>(i.rgba8) &&
+                              di.info == in.dev<int32_t>(i.info) && di.tri == in.dev<int32_t>(i.tri));
+                        const int o_r = out.add(report, 8, 4, 64), o_vm = out.add(vertex_map, nv, 4, 1, vertex_map != nullptr),
+                                  o_pv = out.add(per_vertex, nv, 4, 1, per_vertex != nullptr);
+                        const MeshOut o = mesh_out(out, cv, ct);
+                        check_out(out, {o_r, o_vm, o_pv, o.xyz, o.normal, o.rgba8, o.info, o.tri},
+                                  {out_sec(256, report, 32), out_sec(max1(nv) * 4, vertex_map, nv * 4, vertex_map != nullptr),
+                                   out_sec(max1(nv) * 4, per_vertex, nv * 4, per_vertex != nullptr), out_sec((cv + 1) * 24, nullptr, 0),
+                                   out_sec((cv + 1) * 12, nullptr, 0), out_sec((cv + 1) * 4, nullptr, 0), out_sec((cv + 1) * 16, nullptr, 0),
+                                   out_sec((ct + 1) * 12, nullptr, 0)});
+                        const MeshRows dr = mesh_dev(out, o);
+                        CHECK(dr.xyz == out.dev<double>(o.xyz) && dr.normal == out.dev<float>(o.normal) && dr.rgba8 == out.dev<uint32_t>(o.rgba8) &&
+                              dr.info == out.dev<int32_t>(o.info) && dr.tri == out.dev<int32_t>(o.tri));
+                        report_first(out, report, 32);
+                    }
 }
 
 // sources declared out of order (no form does that): pack() still zeroes every byte that none of them covers
@@ -532,11 +576,12 @@ void out_of_order()
 
 int main(int argc, char **argv)
 {
-    static const char *const FORMS[18] = {"triangulate_tracks", "bundle_adjust", "register_frames", "verify_pair", "relative_pose",
+    static const char *const FORMS[20] = {"triangulate_tracks", "bundle_adjust", "register_frames", "verify_pair", "relative_pose",
                                           "match", "knn", "knn_guided", "match_batch", "track_consensus", "vocab_train", "select_pairs",
-                                          "depth_maps", "depth_fuse", "dense_views", "rgba8_batch", "cloud_merge", "mesh"};
+                                          "depth_maps", "depth_fuse", "dense_views", "rgba8_batch", "cloud_merge", "mesh", "mesh_clean",
+                                          "mesh_decimate"};
     int kind = -1;
-    for (int k = 0; k < 18; k++)
+    for (int k = 0; k < 20; k++)
         if (argc == 2 && argv[1] == std::string(FORMS[k])) kind = k;
     if (kind < 0) return 2;
     out_of_order();
@@ -548,7 +593,8 @@ int main(int argc, char **argv)
     else if (kind < 14) depth_form(kind);
     else if (kind == 14) dense_views_form();
     else if (kind == 15) rgba8_form();
-    else cloud_form(kind);
+    else if (kind < 18) cloud_form(kind);
+    else mesh_list_form();
     std::printf("ok %d\n", n_checks);
     return 0;
 }
